@@ -11,9 +11,18 @@ processes with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, started BEFORE thi
 relays rank 0's JSON line; a failing rank => non-zero exit).  Under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`
 the ranks come from the environment; WORLD_SIZE != --gpus is an error, never a silent single-GPU run.
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, runs W warm-up steps and K timed steps, writes the outputs of the last
+timed step when --dump-outputs DIR is given, and prints the result line; `roofline`, `cpu_baseline`, `end_to_end` and `conv` are null in it.
+--full adds everything else the benchmark measures (the frames workload's extra legs below, per-kernel events in the timed region).
+
+--dump-outputs DIR (frames workload): the last timed step's results as DIR/<name>.npy, float32 / float64 -- per-frame key-point counts,
+and for a fixed, seeded sample of at most DUMP_SAMPLE_ROWS key points: location + scale, orientation, sign of the Laplacian, SURF-64
+descriptor, associated key point of the next frame and its fit score (see dump_frames_outputs).  The inputs are seeded: two runs with the
+same arguments see the same frames, so two builds can be compared output for output.
+
 Workloads (--workload):
   frames         (default) the headline metric.  Frames are independent units: each rank runs its own batch, no data-path collective,
-                 "scaling": "weak".  Rank 0 prints ONE JSON line, which also carries
+                 "scaling": "weak".  Rank 0 prints ONE JSON line, which with --full also carries
                    roofline      the dominant kernel's algorithmic bytes / its HIP-event time measured live in the timed region
                    cpu_baseline  the CPU oracle (C++ restatement of BoofCV's MT path) on a bounded sample of the same frames (N=1 only)
                    end_to_end    the same step through the host-buffer boundary a JNI caller uses (bhip_surf_detect_f32 -> bhip_surf_fetch ->
@@ -47,6 +56,8 @@ FP64_VECTOR_PEAK_TFLOPS = 78.6  # MI355X fp64 vector peak (spec); the exact-fp64
 PCIE_GBS = 63.0  # MI355X_MICROARCH.md: host link PCIe Gen5 x16 (spec)
 _T0 = time.perf_counter()
 MIN_TIMED_SECONDS = 3.0  # default --steps: enough steps for a timed region an external GPU-busy sampler can see
+DUMP_SAMPLE_ROWS = 65536  # --dump-outputs: key points written per run (a fixed, seeded sample when the last step found more); ~37 MB
+DUMP_SAMPLE_SEED = 20261016
 
 
 # ---------------------------------------------------------------------------------------------------------------- launcher
@@ -59,10 +70,13 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=None, help="frames per step per GPU (frames: 256 = BASELINE config; chain4k: 8)")
     ap.add_argument("--height", type=int, default=None)
     ap.add_argument("--width", type=int, default=None)
-    ap.add_argument("--cpu-frames", type=int, default=256, help="frames in the bounded CPU-baseline sample (0 = skip)")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the host-boundary (PCIe-inclusive) leg")
-    ap.add_argument("--end-to-end", action="store_true", help="run the host-boundary leg at --gpus > 1 too (default there: skipped, the scaling run stays short)")
-    ap.add_argument("--no-conv", action="store_true", help="skip the convolution front-end leg (Gaussian blur, Sobel, pyramid layer on 64 of the resident frames)")
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: per-kernel events (roofline), CPU baseline, "
+                    "host-boundary and convolution legs (frames workload)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy (frames workload)")
+    ap.add_argument("--cpu-frames", type=int, default=256, help="with --full: frames in the bounded CPU-baseline sample (0 = skip)")
+    ap.add_argument("--no-end-to-end", action="store_true", help="with --full: skip the host-boundary (PCIe-inclusive) leg")
+    ap.add_argument("--end-to-end", action="store_true", help="with --full: run the host-boundary leg at --gpus > 1 too (default there: skipped, the scaling run stays short)")
+    ap.add_argument("--no-conv", action="store_true", help="with --full: skip the convolution front-end leg (Gaussian blur, Sobel, pyramid layer on 64 of the resident frames)")
     ap.add_argument("--dry-launch", action="store_true", help="ranks only report their environment; no GPU call anywhere (launcher test)")
     return ap.parse_args(argv)
 
@@ -338,6 +352,28 @@ def pmc_traffic(tag, batch, height, width):
     return None, None
 
 
+def dump_frames_outputs(hp, out_dir):
+    """--dump-outputs for the frames workload: what the last timed step hands its caller.  counts.npy holds every frame's key-point
+    count; the per-key-point arrays hold the rows listed in rows.npy (indices into the batch's compact key-point list: all of them, or
+    a fixed, seeded sample of DUMP_SAMPLE_ROWS when the step found more): xy_scale [n,3], orientation [n], white [n] (sign of the
+    Laplacian), descriptors [n,64], pairs [n] (the associated key point of the next frame, -1 = none) and fit [n]."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    xys, ang, white, desc, starts = hp.dd.fetchAll()
+    total = int(starts[-1])
+    pairs = hp.pairs[:total].cpu().numpy()
+    fit = hp.fit[:total].cpu().numpy()
+    if total > DUMP_SAMPLE_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(total, DUMP_SAMPLE_ROWS, replace=False))
+    else:
+        rows = np.arange(total)
+    arrays = {"counts": np.diff(starts).astype(np.float64), "rows": rows.astype(np.float64), "xy_scale": xys[rows], "orientation": ang[rows],
+              "white": white[rows].astype(np.float32), "descriptors": desc[rows], "pairs": pairs[rows].astype(np.float64), "fit": fit[rows]}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    trace("outputs of the last step written to %s" % out_dir)
+
+
 def cpu_baseline(frames_cpu, threads):
     """The oracle restatement of the same step on host cores: detect+describe every frame, associate consecutive frames."""
     from oracle import pyoracle as orc
@@ -469,7 +505,7 @@ def run_frames(args, D):
     hp = HotPath(D.local_rank, B, H, W)
 
     kp = [0]
-    # Per-kernel HIP events (the live roofline numbers) bracket every launch of every PROFILE_EVERY-th step of the timed region: an event
+    # With --full, per-kernel HIP events (the live roofline numbers) bracket every launch of every PROFILE_EVERY-th step of the timed region: an event
     # pair costs ~10 us of dependency latency per kernel, ~0.4 ms over the ~40 kernels of a step, so bracketing every step would take 2 %
     # off the throughput it measures.  The sampled steps are ordinary steps of the timed region.
     sampling = {"on": False, "n": 0, "sampled": 0}
@@ -492,18 +528,21 @@ def run_frames(args, D):
         t0 = time.perf_counter(); step(); torch.cuda.synchronize()
         one = D.max(time.perf_counter() - t0)
         args.steps = int(D.max(float(max(3, int(MIN_TIMED_SECONDS / max(one, 1e-6)) + 1))))
-    sampling.update(on=True, n=0, sampled=0)
-    hp.ctx.profileReset()
+    sampling.update(on=args.full, n=0, sampled=0)
+    if args.full:
+        hp.ctx.profileReset()
     steps, elapsed, _ = timed_steps(D, args, step)
     args.warmup = warm
-    prof = hp.ctx.profileReport()
+    prof = hp.ctx.profileReport() if args.full else {}
     hp.ctx.profile(False)
+    if args.dump_outputs and D.rank == 0:
+        dump_frames_outputs(hp, args.dump_outputs)
     psteps = max(sampling["sampled"], 1)   # steps whose kernels were bracketed
     kp_all = D.sum(float(kp[0]))
 
     # host-boundary leg (every rank runs it at the same time: the ranks share the host's PCIe complex and cores)
     e2e = None
-    if not args.no_end_to_end and (D.world == 1 or args.end_to_end):
+    if args.full and not args.no_end_to_end and (D.world == 1 or args.end_to_end):
         host = torch.empty((B, H, W), dtype=torch.float32, pin_memory=True)
         host.copy_(frames)
         torch.cuda.synchronize()
@@ -564,7 +603,7 @@ def run_frames(args, D):
     # SURVEY 8d), Sobel (12P), the discrete pyramid's first down-sampling layer (4(P + P/2) + 4(P/2 + P/4))
     conv = None
     devices = D.device_ids()
-    if D.rank == 0 and not args.no_conv and D.world == 1:
+    if args.full and D.rank == 0 and not args.no_conv and D.world == 1:
         from boofcv_amd import device as dv
         ops = dv.DeviceImageOps(hp.ctx)
         nb = min(B, 64)
@@ -646,7 +685,7 @@ def run_frames(args, D):
             det_gbs = 66.5 * W * H * B * psteps / (det_ms / 1e3) / 1e9
             roofline["detect_stage"] = {"ms_per_step": round(det_ms / psteps, 3), "algorithmic_GBs": round(det_gbs, 1), "frac": round(det_gbs / HBM_PEAK_GBS, 4)}
     cpu = None
-    if D.world == 1 and args.cpu_frames > 0:
+    if args.full and D.world == 1 and args.cpu_frames > 0:
         threads = min(os.cpu_count() or 1, 16)
         sample = frames[:args.cpu_frames].cpu().numpy()
         fps, dt, kps = cpu_baseline(sample, threads)
@@ -891,6 +930,8 @@ def main():
     args = parse_args(argv)
     if args.gpus < 1:
         sys.exit("--gpus must be >= 1")
+    if args.dump_outputs and args.workload != "frames":
+        sys.exit("--dump-outputs is implemented for the frames workload only")
     under_launcher = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     if not under_launcher and args.gpus > 1:
         sys.exit(launch_ranks(args, argv))      # no GPU call has been made in this process

@@ -11,6 +11,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 rnd = sys.argv[1]
 G = os.path.join(ROOT, "gpurun_out")
 P = os.path.join(ROOT, "profiles")
+if rnd == "--input-dir":   # where the profile scripts write what this script reads (scripts/profile_all.sh asks)
+    print(G)
+    sys.exit(0)
 
 
 def copy(src, name):

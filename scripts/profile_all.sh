@@ -1,6 +1,7 @@
 # everything profiles/rNN_* is made from, in one GPU call (results under gpurun_out/, copied to profiles/ by scripts/collect_profiles.py)
 set -x
-timeout -k 10 900 python bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err
+out=$(python scripts/collect_profiles.py --input-dir) && mkdir -p "$out"
+timeout -k 10 900 python bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err"
 timeout -k 10 600 bash scripts/profile_bench.sh > gpurun_out/profile_bench.log 2>&1
 timeout -k 10 600 bash scripts/pmc_traffic.sh > gpurun_out/pmc_traffic.log 2>&1
 timeout -k 10 600 bash scripts/pmc_insts.sh > gpurun_out/pmc_insts.log 2>&1

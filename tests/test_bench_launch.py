@@ -60,3 +60,16 @@ def test_failing_rank_fails_the_run():
     p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "1", "--warmup", "0", "--batch", "1", "--cpu-frames", "0"], env=_clean_env(),
                        capture_output=True, text=True, timeout=300)
     assert p.returncode != 0 and not p.stdout.strip()
+
+
+def test_full_and_dump_outputs_are_accepted():
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--dry-launch", "--full", "--dump-outputs", "unused"], env=_clean_env(), capture_output=True,
+                       text=True, timeout=120)
+    assert p.returncode == 0, p.stderr
+    assert json.loads(p.stdout.strip())["n_gpus"] == 1
+
+
+def test_dump_outputs_needs_the_frames_workload():
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--dry-launch", "--workload", "chain4k", "--dump-outputs", "unused"], env=_clean_env(),
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode != 0 and "frames workload" in p.stderr and not p.stdout.strip()
