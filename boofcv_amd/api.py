@@ -17,6 +17,7 @@ import atexit
 import ctypes as C
 import math
 import sys
+import threading
 import weakref
 from dataclasses import dataclass
 
@@ -128,10 +129,12 @@ atexit.register(Context._close_all)   # runs before module teardown and before t
 class _PinnedPool:
     """Page-locked host blocks (bhip_host_alloc) for the arrays this wrapper hands out or fills on every call -- fetched key points and
     descriptors, match lists -- so that their copies are DMA transfers instead of staged pageable copies (what a JNI provider gets from direct
-    ByteBuffers over the same allocator).  Blocks are recycled by size class when the numpy arrays built on them are garbage collected."""
+    ByteBuffers over the same allocator).  Blocks are recycled by size class when the numpy arrays built on them are garbage collected,
+    from any thread.  A block still in use when the interpreter exits is left to the runtime, never freed under a live array."""
     _free = {}      # size class -> [address]
     _pooled = 0     # bytes sitting in _free
     _closed = False
+    _lock = threading.RLock()   # guards the three above (reentrant: a garbage collection inside a locked section may run _release)
     MIN = 4096
     MAX_POOLED = 1 << 30   # blocks released beyond this go back to the runtime instead of the pool
 
@@ -149,31 +152,32 @@ class _PinnedPool:
             return None
         size = cls._size_class(max(int(nbytes), 1))
         addr = None
-        lst = cls._free.get(size)
-        if lst:
-            try:
-                addr = lst.pop()      # (list.pop is atomic; another thread may have taken the last block in between)
+        with cls._lock:
+            if cls._free.get(size):
+                addr = cls._free[size].pop()
                 cls._pooled -= size
-            except IndexError:
-                addr = None
         if addr is None:
             p = C.c_void_p()
             if _lib.load().bhip_host_alloc(ctx._h, size, C.byref(p)) != _lib.BHIP_OK or not p.value:
                 return None
             addr = p.value
         buf = (C.c_uint8 * size).from_address(addr)
-        weakref.finalize(buf, cls._release, addr, size)
+        weakref.finalize(buf, cls._release, addr, size).atexit = False   # not at exit: numpy arrays may still point into the block
         return buf
 
     @classmethod
     def _release(cls, addr, size, _finalizing=sys.is_finalizing):
-        if cls._closed or _finalizing():
-            return   # the exit hook has run (or the interpreter is going down): the runtime reclaims the block
-        if cls._pooled + size > cls.MAX_POOLED:
+        if _finalizing():
+            return   # the interpreter is going down: the runtime reclaims the block
+        with cls._lock:
+            if cls._closed:
+                return   # the exit hook has run: as above
+            pooled = cls._pooled + size <= cls.MAX_POOLED
+            if pooled:
+                cls._free.setdefault(size, []).append(addr)
+                cls._pooled += size
+        if not pooled:
             _lib.load().bhip_host_free(C.c_void_p(addr))
-            return
-        cls._free.setdefault(size, []).append(addr)
-        cls._pooled += size
 
     @classmethod
     def arrays(cls, ctx, specs):
@@ -192,13 +196,14 @@ class _PinnedPool:
 
     @classmethod
     def _close(cls):
-        cls._closed = True
         L = _lib.load()
-        for lst in cls._free.values():
-            for addr in lst:
-                L.bhip_host_free(C.c_void_p(addr))
-        cls._free.clear()
-        cls._pooled = 0
+        with cls._lock:
+            cls._closed = True
+            blocks = [addr for lst in cls._free.values() for addr in lst]
+            cls._free.clear()
+            cls._pooled = 0
+        for addr in blocks:
+            L.bhip_host_free(C.c_void_p(addr))
 
 
 atexit.register(_PinnedPool._close)   # registered after Context._close_all, so it runs before it (contexts are still alive)

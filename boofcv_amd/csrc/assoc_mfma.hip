@@ -592,9 +592,9 @@ int bhip_assoc_l2_mfma_batched(bhip_ctx* ctx, AssocMfmaWork& W, const double* de
 		hipLaunchKernelGGL(k_assoc_argsel, dim3(exactBlocks), dim3(256), 0, st, A.probs, A.cand, counters, cap, rowBest, colBest, rowArg, colArg, colCnt);
 	}
 	// degenerate inputs? (one small read-back; the result kernels below are only trusted when the flags are clean)
-	BHIP_HIP(ctx, hipMemcpyAsync(ctx->hostScratch, flags, 16, hipMemcpyDeviceToHost, st));
+	BHIP_HIP(ctx, hipMemcpyAsync(ctx->hostScratch.p, flags, 16, hipMemcpyDeviceToHost, st));
 	BHIP_HIP(ctx, hipStreamSynchronize(st));
-	const int* hf = ctx->hostScratch;
+	const int* hf = ctx->hostScratch.as<int>();
 	if (hf[0] != 0 || hf[2] > cap) return BHIP_OK;  // *usedMfma stays 0
 	int maxNs = 0;
 	for (int p = 0; p < count; p++) maxNs = std::max(maxNs, ns[p]);
@@ -603,9 +603,4 @@ int bhip_assoc_l2_mfma_batched(bhip_ctx* ctx, AssocMfmaWork& W, const double* de
 	BHIP_HIP(ctx, hipGetLastError());
 	*usedMfma = 1;
 	return BHIP_OK;
-}
-
-void bhip_assoc_mfma_release(AssocMfmaWork& W) {
-	DevBuf* b[] = {&W.Fs, &W.Fd, &W.nrmS, &W.nrmD, &W.probs, &W.blocks, &W.keys, &W.thr, &W.best, &W.args, &W.cand, &W.flags};
-	for (DevBuf* x : b) x->release();
 }

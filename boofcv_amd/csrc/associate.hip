@@ -400,7 +400,7 @@ int bhip_assoc_hamming_batched(bhip_ctx* ctx, const int32_t* src, const int32_t*
 	if (count <= 0) return BHIP_OK;
 	if (words <= 0 || words > 64) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "BRIEF descriptor too long for the batched Hamming kernel");
 	if ((size_t)count * sizeof(HamProb) > (1u << 20)) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "too many problems in one batched call");
-	HamProb* hp = (HamProb*)ctx->hostScratch;   // pinned: the copy below is asynchronous
+	HamProb* hp = ctx->hostScratch.as<HamProb>();   // pinned: the copy below is asynchronous
 	long long cols = 0;
 	int maxNs = 0, maxNd = 0;
 	for (int p = 0; p < count; p++) {

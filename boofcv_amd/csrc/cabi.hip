@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cfloat>
 #include <algorithm>
+#include <atomic>
 #include <memory>
 #include <mutex>
 #include <unordered_set>
@@ -26,7 +27,6 @@ int bhip_launch_integral_u8(bhip_ctx* ctx, const unsigned char* in, long long in
 int bhip_assoc_l2_mfma_batched(bhip_ctx* ctx, AssocMfmaWork& W, const double* dev_src, const double* dev_dst, int count, const long long* srcOff,
 								 const int* ns, const long long* dstOff, const int* nd, double maxErr, int backwards, int* dev_pairs, double* dev_fit,
 								 int* usedMfma);
-void bhip_assoc_mfma_release(AssocMfmaWork& W);
 
 bool bhip_fused_plan(int skip, int nlevels, const int* sizes, int radius, int* TX, int* TY, int* ldsBytes);
 bool bhip_fused_is_fixed(int skip, int nlevels, const int* sizes, int radius);
@@ -34,7 +34,7 @@ int bhip_launch_detect_fused(bhip_ctx* ctx, ImgView ii, int batch, int skip, int
 							 const int* midLevels, int radius, float threshold, unsigned int* bitmap, int bitmapWords, KeyPoint* cand, int* candCount,
 							 int cap, const FusedExport* exp, bool intTaps = false);
 
-// per-context scratch that the stateless entry points reuse
+// per-context scratch that the stateless entry points reuse (freed with the context)
 struct CtxScratch {
 	DevBuf a, b, c, d, e, work, nmsBitmap, nmsPrefix, nmsPos, ipTmp, ipKernel;
 	AssocMfmaWork mfma;
@@ -52,12 +52,13 @@ static CtxScratch* scratchOf(bhip_ctx* ctx) { return &static_cast<bhip_ctx_full*
 // releases the device side of every detect+describe object created on it and leaves those objects as inert shells (every call on them
 // returns BHIP_ERR_INVALID, bhip_surf_destroy only frees the shell); a pointer that is not in the registry is refused instead of
 // dereferenced.  Once the process has started to exit (atexit) the destroy calls touch neither the HIP runtime nor the handles -- the
-// runtime's own teardown may already have run.  The registry is a leaked singleton so it outlives every static destructor.
+// runtime's own teardown may already have run.  The registry is a leaked singleton so it outlives every static destructor.  Creating an
+// object holds the lock from the context's liveness check to the insert, so a concurrent bhip_ctx_destroy waits for it.
 struct HandleRegistry {
 	std::mutex m;
 	std::unordered_set<bhip_ctx*> ctxs;
 	std::unordered_set<bhip_surf*> surfs;
-	bool exiting = false;
+	std::atomic<bool> exiting{false};
 };
 static HandleRegistry& registry() {
 	static HandleRegistry* r = [] {
@@ -96,27 +97,20 @@ static int ctxCreate(int device, void* stream, bool useGiven, bhip_ctx** out) {
 	if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return BHIP_ERR_HIP;  // no GPU: fail loudly, never fall back
 	if (device < 0 || device >= count) return BHIP_ERR_INVALID;
 	if (hipSetDevice(device) != hipSuccess) return BHIP_ERR_HIP;
-	bhip_ctx_full* ctx = new (std::nothrow) bhip_ctx_full();
+	std::unique_ptr<bhip_ctx_full> ctx(new (std::nothrow) bhip_ctx_full());
 	if (!ctx) return BHIP_ERR_NOMEM;
 	ctx->device = device;
 	if (useGiven) {
 		ctx->stream = (hipStream_t)stream;
-		ctx->ownStream = false;
 	} else {
-		if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return BHIP_ERR_HIP; }
-		ctx->ownStream = true;
+		if (hipStreamCreateWithFlags(&ctx->ownedStream.h, hipStreamNonBlocking) != hipSuccess) return BHIP_ERR_HIP;
+		ctx->stream = ctx->ownedStream;
 	}
-	if (hipHostMalloc((void**)&ctx->hostScratch, 1 << 20, hipHostMallocDefault) != hipSuccess) {
-		if (ctx->ownStream) (void)hipStreamDestroy(ctx->stream);
-		delete ctx;
-		return BHIP_ERR_HIP;
-	}
-	{
-		HandleRegistry& R = registry();
-		std::lock_guard<std::mutex> lock(R.m);
-		R.ctxs.insert(ctx);
-	}
-	*out = ctx;
+	if (ctx->hostScratch.reserve(ctx.get(), 1 << 20) != BHIP_OK) return BHIP_ERR_HIP;
+	HandleRegistry& R = registry();
+	std::lock_guard<std::mutex> lock(R.m);
+	R.ctxs.insert(ctx.get());
+	*out = ctx.release();
 	return BHIP_OK;
 }
 int bhip_ctx_create(int device, bhip_ctx** out) { return ctxCreate(device, nullptr, false, out); }
@@ -128,19 +122,11 @@ int bhip_ctx_destroy(bhip_ctx* c) {
 	if (R.exiting) return BHIP_OK;                        // process teardown: the runtime reclaims everything
 	if (!R.ctxs.count(c)) return BHIP_ERR_INVALID;        // not a live context (destroyed twice, or never created)
 	R.ctxs.erase(c);
-	bhip_ctx_full* ctx = static_cast<bhip_ctx_full*>(c);
-	(void)hipSetDevice(ctx->device);
-	(void)hipStreamSynchronize(ctx->stream);
+	(void)hipSetDevice(c->device);
+	(void)hipStreamSynchronize(c->stream);
 	// detect+describe objects still alive on this context lose their device side now and become inert shells
 	surfOrphanChildren(c);
-	CtxScratch& s = ctx->scratch;
-	s.a.release(); s.b.release(); s.c.release(); s.d.release(); s.e.release(); s.work.release();
-	s.nmsBitmap.release(); s.nmsPrefix.release(); s.nmsPos.release(); s.ipTmp.release(); s.ipKernel.release();
-	bhip_assoc_mfma_release(s.mfma);
-	bhip_profile_release(ctx);
-	if (ctx->hostScratch) (void)hipHostFree(ctx->hostScratch);
-	if (ctx->ownStream) (void)hipStreamDestroy(ctx->stream);
-	delete ctx;
+	delete static_cast<bhip_ctx_full*>(c);   // scratch, profiling events, staging block, then the stream it owns
 	return BHIP_OK;
 }
 int bhip_ctx_synchronize(bhip_ctx* ctx) {
@@ -166,11 +152,7 @@ int bhip_host_alloc(bhip_ctx* ctx, long long bytes, uint8_t** host_mem) {
 }
 int bhip_host_free(void* host_mem) {
 	if (!host_mem) return BHIP_OK;
-	{
-		HandleRegistry& R = registry();
-		std::lock_guard<std::mutex> lock(R.m);
-		if (R.exiting) return BHIP_OK;   // process teardown: the runtime reclaims it
-	}
+	if (registry().exiting) return BHIP_OK;   // process teardown: the runtime reclaims it
 	return hipHostFree(host_mem) == hipSuccess ? BHIP_OK : BHIP_ERR_HIP;
 }
 
@@ -209,7 +191,7 @@ struct FhDetector {
 	bool intTaps = false;   // the integral image holds int32 (GrayS32, from a GrayU8 frame) instead of float
 	std::vector<FhOctavePlan> plan;
 	int bitmapWords = 0;
-	DevBuf inten, expBuf, bitmap, prefix, cand, sorted, count, selKey, selIdx, selLevels;
+	DevBuf inten, bitmap, prefix, cand, sorted, count, selKey, selIdx, selLevels;
 	bool nBest() const { return cfg.maxFeaturesPerScale > 0; }   // SelectNBestFeatures between the NMS and the scale-space test
 	std::vector<int> counts;   // per image, host
 	long long total = 0;
@@ -398,9 +380,9 @@ struct FhDetector {
 			BHIP_TRY(bhip_launch_word_prefix(ctx, bitmap.as<unsigned int>(), bitmapWords, batch, prefix.as<unsigned int>(), count.as<int>() + batch));
 			counts.resize(batch);
 			if ((size_t)batch * 4 <= (1u << 20)) {
-				BHIP_HIP(ctx, hipMemcpyAsync(ctx->hostScratch, count.p, (size_t)batch * 4, hipMemcpyDeviceToHost, ctx->stream));
+				BHIP_HIP(ctx, hipMemcpyAsync(ctx->hostScratch.p, count.p, (size_t)batch * 4, hipMemcpyDeviceToHost, ctx->stream));
 				BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-				memcpy(counts.data(), ctx->hostScratch, (size_t)batch * 4);
+				memcpy(counts.data(), ctx->hostScratch.p, (size_t)batch * 4);
 			} else {
 				BHIP_HIP(ctx, hipMemcpyAsync(counts.data(), count.p, (size_t)batch * 4, hipMemcpyDeviceToHost, ctx->stream));
 				BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -446,26 +428,32 @@ struct FhDetector {
 		for (int c : counts) total += c;
 		return BHIP_OK;
 	}
-	void release() {
-		inten.release(); expBuf.release(); bitmap.release(); prefix.release(); cand.release(); sorted.release(); count.release();
-		selKey.release(); selIdx.release(); selLevels.release();
-	}
 };
 
 // ---------------------------------------------------------------------------------------------------------------
 // SURF detect + describe object
 // ---------------------------------------------------------------------------------------------------------------
-struct bhip_surf {
+// Everything a detect+describe object holds on its context's device.  It is dropped as a whole, by destruction or by assigning an empty
+// SurfDevice (surfReleaseDevice); the owner synchronizes the context stream and the copy stream first.
+struct SurfDevice {
+	FhDetector det;
+	DevBuf tabBuf, inBuf, iiBuf, startBuf, angBuf, descBuf, whiteBuf, xysBuf, tmpKp, tmpAng, tmpDesc, tmpWhite, permBuf;
+	DevBuf briefTab, wordsBuf;   // BRIEF: [samplePoints | compare] on the device; words of the whole batch, compact [total][briefWords]
+	PinnedBuf startsPinned;      // page-locked staging copy of `starts` for its upload
+	// host-frame batches are processed in chunks so that the upload of chunk k+1 (copy stream) runs under the kernels of chunk k: the
+	// chunks go through `worker` (same configuration, chunk-sized work buffers), whose results are appended to this object's arrays
+	std::unique_ptr<bhip_surf> worker;
+	HipStream copyStream;
+	const int* briefBorrow = nullptr;   // chunk worker: the owner's BRIEF table (not owned: never freed twice)
+};
+
+struct bhip_surf : SurfDevice {
 	bhip_ctx* ctx = nullptr;
 	int stable = 1;
 	bhip_surf_cfg sd;
 	bhip_ori_cfg ori;
-	FhDetector det;
 	SurfTables tables;
-	DevBuf tabBuf, inBuf, iiBuf, startBuf, angBuf, descBuf, whiteBuf, xysBuf, tmpKp, tmpAng, tmpDesc, tmpWhite, permBuf;
 	std::vector<int> starts;  // batch+1
-	int* startsPinned = nullptr;          // page-locked staging copy of `starts` for its upload
-	size_t startsPinnedBytes = 0;
 	int W = 0, H = 0, batch = 0;
 	bool haveResult = false;
 	ImgView iiView;
@@ -473,18 +461,12 @@ struct bhip_surf {
 	DescPlanar planar{};
 	bool descOptions = false;  // the last detect needs `planar` passed to the describe kernel (colour bands and / or integer taps)
 	int dofOut() const { return tables.dof * (planarBands > 0 ? planarBands : 1); }
-	// host-frame batches are processed in chunks so that the upload of chunk k+1 (copy stream) runs under the kernels of chunk k: the
-	// chunks go through `worker` (same configuration, chunk-sized work buffers), whose results are appended to this object's arrays
-	bhip_surf* worker = nullptr;
-	hipStream_t copyStream = nullptr;
 	float* extII = nullptr;    // worker only: where the integral images of the current chunk go (a slice of the owner's iiBuf)
 	// describe = BRIEF (DetectDescribeFusion(fastHessian, null, brief), bhip_surf_create_brief): no orientation / SURF stage; every detected
 	// point gets its TupleDesc_B words from the input frame itself
 	bool brief = false;
 	int briefRadius = 0, briefPoints = 0, briefWords = 0;
-	DevBuf briefTab, wordsBuf;   // [samplePoints | compare] on the device; words of the whole batch, compact [total][briefWords]
 	bool briefPatch = false;            // the definition fits the LDS-patch kernel
-	const int* briefBorrow = nullptr;   // chunk worker: the owner's table
 	const int* briefSample() const { return briefBorrow ? briefBorrow : briefTab.as<int>(); }
 	const int* briefCompare() const { return briefSample() + briefCompareOff; }
 	size_t briefCompareOff = 0;
@@ -585,13 +567,9 @@ static int surfRun(bhip_surf* s, ImgView in, int batch, int planarBands = 0, boo
 		// through a page-locked staging copy owned by the object: the transfer then reads it in stream order, and nothing rewrites it before the
 		// next detect has synchronized on its own count read-back
 		const size_t need = (size_t)(batch + 1) * 4;
-		if (need > s->startsPinnedBytes) {
-			if (s->startsPinned) { BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream)); (void)hipHostFree(s->startsPinned); s->startsPinned = nullptr; s->startsPinnedBytes = 0; }
-			if (hipHostMalloc((void**)&s->startsPinned, need * 2, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return bhip_fail(ctx, BHIP_ERR_NOMEM, "page-locked staging buffer"); }
-			s->startsPinnedBytes = need * 2;
-		}
-		memcpy(s->startsPinned, s->starts.data(), need);
-		BHIP_HIP(ctx, hipMemcpyAsync(s->startBuf.p, s->startsPinned, need, hipMemcpyHostToDevice, ctx->stream));
+		if (need > s->startsPinned.cap) BHIP_TRY(s->startsPinned.reserve(ctx, need * 2));
+		memcpy(s->startsPinned.p, s->starts.data(), need);
+		BHIP_HIP(ctx, hipMemcpyAsync(s->startBuf.p, s->startsPinned.p, need, hipMemcpyHostToDevice, ctx->stream));
 	}
 	if (s->brief) {
 		// DetectDescribeFusion.detect (F:abst/feature/detdesc/DetectDescribeFusion.java:95-127) with orientation == null and
@@ -646,7 +624,8 @@ static int surfRun(bhip_surf* s, ImgView in, int batch, int planarBands = 0, boo
 	return BHIP_OK;
 }
 
-static int surfCreateUnregistered(bhip_ctx* ctx, const bhip_fh_cfg* fh, const bhip_surf_cfg* surf, const bhip_ori_cfg* ori, int stable, bhip_surf** out);
+static int surfCreateUnregistered(bhip_ctx* ctx, const bhip_fh_cfg* fh, const bhip_surf_cfg* surf, const bhip_ori_cfg* ori, int stable,
+								  std::unique_ptr<bhip_surf>& out);
 
 // device buffer growth that keeps the first `keep` bytes (result arrays that chunks are appended to)
 static int growKeep(bhip_ctx* ctx, DevBuf& b, size_t bytes, size_t keep) {
@@ -654,8 +633,8 @@ static int growKeep(bhip_ctx* ctx, DevBuf& b, size_t bytes, size_t keep) {
 	DevBuf n;
 	BHIP_TRY(n.reserve(ctx, bytes + bytes / 4));
 	if (b.p && keep) BHIP_HIP(ctx, hipMemcpyAsync(n.p, b.p, keep, hipMemcpyDeviceToDevice, ctx->stream));
-	if (b.p) { BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream)); b.release(); }
-	b = n;
+	if (b.p) BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	b = std::move(n);   // the old block (now in n) is freed on return, after the copy out of it has finished
 	return BHIP_OK;
 }
 
@@ -673,16 +652,16 @@ static int surfRunChunked(bhip_surf* s, int width, int height, int batch, size_t
 	{ const char* e = getenv("BHIP_SURF_CHUNK"); if (e && atoi(e) > 0) chunk = atoi(e); }   // tests: chunk small batches too
 	if (batch < 2 * chunk) return BHIP_OK;
 	if (!s->worker) {
-		BHIP_TRY(surfCreateUnregistered(ctx, &s->det.cfg, &s->sd, &s->ori, s->stable, &s->worker));
+		BHIP_TRY(surfCreateUnregistered(ctx, &s->det.cfg, &s->sd, &s->ori, s->stable, s->worker));
 		if (s->brief) {
 			// the worker samples with the owner's definition (it borrows the device table; briefTab stays empty so it is never freed twice)
-			bhip_surf* w0 = s->worker;
+			bhip_surf* w0 = s->worker.get();
 			w0->brief = true; w0->briefRadius = s->briefRadius; w0->briefPoints = s->briefPoints; w0->briefWords = s->briefWords;
 			w0->briefBorrow = s->briefTab.as<int>(); w0->briefCompareOff = s->briefCompareOff; w0->briefPatch = s->briefPatch;
 		}
-		BHIP_HIP(ctx, hipStreamCreateWithFlags(&s->copyStream, hipStreamNonBlocking));
+		BHIP_HIP(ctx, hipStreamCreateWithFlags(&s->copyStream.h, hipStreamNonBlocking));
 	}
-	bhip_surf* w = s->worker;
+	bhip_surf* w = s->worker.get();
 	const size_t px = (size_t)width * height;
 	s->haveResult = false;
 	s->det.intTaps = u8;
@@ -691,21 +670,17 @@ static int surfRunChunked(bhip_surf* s, int width, int height, int batch, size_t
 	// everything queued on the compute stream so far (an earlier batch may still read inBuf) precedes the first upload
 	const int nchunks = (batch + chunk - 1) / chunk;
 	// events are destroyed on every way out of this function
-	struct EventSet {
-		std::vector<hipEvent_t> evs;
-		~EventSet() { for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e); }
-	} events;
-	events.evs.assign(nchunks + 1, nullptr);
-	hipEvent_t& ev = events.evs[nchunks];
-	hipEvent_t* arrived = events.evs.data();
-	BHIP_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+	std::vector<HipEvent> events(nchunks + 1);
+	HipEvent& ev = events[nchunks];
+	HipEvent* arrived = events.data();
+	BHIP_HIP(ctx, hipEventCreateWithFlags(&ev.h, hipEventDisableTiming));
 	BHIP_HIP(ctx, hipEventRecord(ev, ctx->stream));
 	BHIP_HIP(ctx, hipStreamWaitEvent(s->copyStream, ev, 0));
 	int status = BHIP_OK;
 	for (int c = 0; c < nchunks && status == BHIP_OK; c++) {
 		const int a = c * chunk, n = std::min(chunk, batch - a);
 		for (int i = a; i < a + n && status == BHIP_OK; i++) status = upload(i, (char*)s->inBuf.p + imgBytes * i, s->copyStream);
-		if (status == BHIP_OK && (hipEventCreateWithFlags(&arrived[c], hipEventDisableTiming) != hipSuccess || hipEventRecord(arrived[c], s->copyStream) != hipSuccess))
+		if (status == BHIP_OK && (hipEventCreateWithFlags(&arrived[c].h, hipEventDisableTiming) != hipSuccess || hipEventRecord(arrived[c], s->copyStream) != hipSuccess))
 			status = bhip_fail(ctx, BHIP_ERR_HIP, "event");
 	}
 	const int dof = s->tables.dof;
@@ -770,10 +745,8 @@ static int surfRunChunked(bhip_surf* s, int width, int height, int batch, size_t
 	return BHIP_OK;
 }
 
-static int surfCreateUnregistered(bhip_ctx* ctx, const bhip_fh_cfg* fh, const bhip_surf_cfg* surf, const bhip_ori_cfg* ori, int stable, bhip_surf** out) {
-	CHECK_CTX(ctx);
-	if (!out) return bhip_fail(ctx, BHIP_ERR_INVALID, "null output");
-	*out = nullptr;
+static int surfCreateUnregistered(bhip_ctx* ctx, const bhip_fh_cfg* fh, const bhip_surf_cfg* surf, const bhip_ori_cfg* ori, int stable,
+								  std::unique_ptr<bhip_surf>& out) {
 	std::unique_ptr<bhip_surf> s(new (std::nothrow) bhip_surf());
 	if (!s) return bhip_fail(ctx, BHIP_ERR_NOMEM, "out of host memory");
 	s->ctx = ctx;
@@ -781,26 +754,19 @@ static int surfCreateUnregistered(bhip_ctx* ctx, const bhip_fh_cfg* fh, const bh
 	if (fh) s->det.cfg = *fh; else bhip_fh_cfg_default(&s->det.cfg);
 	if (surf) s->sd = *surf; else bhip_surf_cfg_default(&s->sd);
 	if (ori) s->ori = *ori; else bhip_ori_cfg_default(&s->ori, s->stable);
-	const int st = buildTables(s.get());
-	if (st != BHIP_OK) { s->tabBuf.release(); return st; }
-	*out = s.release();
+	BHIP_TRY(buildTables(s.get()));
+	out = std::move(s);
 	return BHIP_OK;
 }
 
 // Frees everything s holds on the device (its context must still be alive) and detaches it from the context: s is an inert shell afterwards.
 // The chunk worker is owned by s and is not in the registry.
 static void surfReleaseDevice(bhip_surf* s) {
-	if (!s || !s->ctx) return;
+	if (!s->ctx) return;
 	(void)hipSetDevice(s->ctx->device);
 	(void)hipStreamSynchronize(s->ctx->stream);
-	if (s->worker) { surfReleaseDevice(s->worker); delete s->worker; s->worker = nullptr; }
-	if (s->copyStream) { (void)hipStreamSynchronize(s->copyStream); (void)hipStreamDestroy(s->copyStream); s->copyStream = nullptr; }
-	s->det.release();
-	if (s->startsPinned) { (void)hipHostFree(s->startsPinned); s->startsPinned = nullptr; s->startsPinnedBytes = 0; }
-	DevBuf* bufs[] = {&s->tabBuf, &s->inBuf, &s->iiBuf, &s->startBuf, &s->angBuf, &s->descBuf, &s->whiteBuf, &s->xysBuf, &s->tmpKp, &s->tmpAng, &s->tmpDesc, &s->tmpWhite, &s->permBuf,
-					  &s->briefTab, &s->wordsBuf};
-	for (DevBuf* b : bufs) b->release();
-	s->briefBorrow = nullptr;
+	if (s->copyStream) (void)hipStreamSynchronize(s->copyStream);
+	static_cast<SurfDevice&>(*s) = SurfDevice();
 	s->haveResult = false;
 	s->ctx = nullptr;
 }
@@ -820,13 +786,15 @@ extern "C" {
 
 int bhip_surf_create(bhip_ctx* ctx, const bhip_fh_cfg* fh, const bhip_surf_cfg* surf, const bhip_ori_cfg* ori, int stable, bhip_surf** out) {
 	HandleRegistry& R = registry();
-	{
-		std::lock_guard<std::mutex> lock(R.m);
-		if (!ctx || !R.ctxs.count(ctx)) return BHIP_ERR_INVALID;
-	}
-	BHIP_TRY(surfCreateUnregistered(ctx, fh, surf, ori, stable, out));
 	std::lock_guard<std::mutex> lock(R.m);
-	R.surfs.insert(*out);
+	if (!ctx || !R.ctxs.count(ctx)) return BHIP_ERR_INVALID;
+	CHECK_CTX(ctx);
+	if (!out) return bhip_fail(ctx, BHIP_ERR_INVALID, "null output");
+	*out = nullptr;
+	std::unique_ptr<bhip_surf> s;
+	BHIP_TRY(surfCreateUnregistered(ctx, fh, surf, ori, stable, s));
+	R.surfs.insert(s.get());
+	*out = s.release();
 	return BHIP_OK;
 }
 
@@ -1017,10 +985,8 @@ int bhip_surf_dev_view(bhip_surf* s, int image, const double** dev_desc, const d
 // config.fixed): the returned object is driven through the same bhip_surf_detect_* / _count / _fetch calls as the SURF one.
 int bhip_surf_create_brief(bhip_ctx* ctx, const bhip_fh_cfg* fh, int radius, int numPoints, const int32_t* samplePoints, const int32_t* compare, bhip_surf** out) {
 	HandleRegistry& R = registry();
-	{
-		std::lock_guard<std::mutex> lock(R.m);
-		if (!ctx || !R.ctxs.count(ctx)) return BHIP_ERR_INVALID;
-	}
+	std::lock_guard<std::mutex> lock(R.m);
+	if (!ctx || !R.ctxs.count(ctx)) return BHIP_ERR_INVALID;
 	CHECK_CTX(ctx);
 	if (!out) return bhip_fail(ctx, BHIP_ERR_INVALID, "null output");
 	*out = nullptr;
@@ -1030,20 +996,18 @@ int bhip_surf_create_brief(bhip_ctx* ctx, const bhip_fh_cfg* fh, int radius, int
 		if (compare[i] < 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "negative sample index");
 		maxIdx = std::max(maxIdx, compare[i]);
 	}
-	bhip_surf* s = nullptr;
-	BHIP_TRY(surfCreateUnregistered(ctx, fh, nullptr, nullptr, 0, &s));   // (the SURF tables of the shell are never used)
+	std::unique_ptr<bhip_surf> s;
+	BHIP_TRY(surfCreateUnregistered(ctx, fh, nullptr, nullptr, 0, s));   // (the SURF tables of the shell are never used)
 	s->brief = true;
 	s->briefRadius = radius; s->briefPoints = numPoints; s->briefWords = (numPoints + 31) / 32;
 	const size_t nSample = (size_t)(maxIdx + 1) * 2, nCompare = (size_t)numPoints * 2;
 	s->briefCompareOff = nSample;
 	s->briefPatch = briefPatchOk(samplePoints, maxIdx + 1, radius);
-	int st = s->briefTab.reserve(ctx, (nSample + nCompare) * 4);
-	if (st == BHIP_OK && hipMemcpy(s->briefTab.p, samplePoints, nSample * 4, hipMemcpyHostToDevice) != hipSuccess) st = bhip_fail(ctx, BHIP_ERR_HIP, "BRIEF table upload");
-	if (st == BHIP_OK && hipMemcpy(s->briefTab.as<int>() + nSample, compare, nCompare * 4, hipMemcpyHostToDevice) != hipSuccess) st = bhip_fail(ctx, BHIP_ERR_HIP, "BRIEF table upload");
-	if (st != BHIP_OK) { surfReleaseDevice(s); delete s; return st; }
-	std::lock_guard<std::mutex> lock(R.m);
-	R.surfs.insert(s);
-	*out = s;
+	BHIP_TRY(s->briefTab.reserve(ctx, (nSample + nCompare) * 4));
+	if (hipMemcpy(s->briefTab.p, samplePoints, nSample * 4, hipMemcpyHostToDevice) != hipSuccess) return bhip_fail(ctx, BHIP_ERR_HIP, "BRIEF table upload");
+	if (hipMemcpy(s->briefTab.as<int>() + nSample, compare, nCompare * 4, hipMemcpyHostToDevice) != hipSuccess) return bhip_fail(ctx, BHIP_ERR_HIP, "BRIEF table upload");
+	R.surfs.insert(s.get());
+	*out = s.release();
 	return BHIP_OK;
 }
 
@@ -1203,9 +1167,9 @@ int bhip_nonmax_block_f32(bhip_ctx* ctx, const float* intensity, int start, int 
 	BHIP_TRY(sc->d.reserve(ctx, 16));
 	BHIP_TRY(sc->e.reserve(ctx, (size_t)std::max(cap, 1) * 4));
 	BHIP_TRY(nonmaxDevice(ctx, sc->a.as<float>(), 0, width, width, height, 1, radius, threshold, border, sc->e.as<int16_t>(), cap, sc->d.as<int>()));
-	BHIP_HIP(ctx, hipMemcpyAsync(ctx->hostScratch, sc->d.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(ctx->hostScratch.p, sc->d.p, 4, hipMemcpyDeviceToHost, ctx->stream));
 	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	*n = ctx->hostScratch[0];
+	*n = ctx->hostScratch.as<int>()[0];
 	const int ncopy = std::min(*n, cap);
 	if (ncopy > 0) {
 		BHIP_HIP(ctx, hipMemcpyAsync(xy, sc->e.p, (size_t)ncopy * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1245,44 +1209,15 @@ int bhip_select_nbest_f32(bhip_ctx* ctx, const float* intensity, int start, int 
 	return BHIP_OK;
 }
 
-int bhip_fh_detect_f32(bhip_ctx* ctx, const bhip_fh_cfg* cfg, const float* ii, int iiStart, int iiStride, int width, int height, double* xy_scale,
-					   int cap, int* n) {
+// FastHessianFeatureDetector.detect(integral): intTaps = the integral image holds int32 (GrayS32, from a GrayU8 frame) instead of float
+static int fhDetect(bhip_ctx* ctx, const bhip_fh_cfg* cfg, const void* ii, bool intTaps, int iiStart, int iiStride, int width, int height,
+					double* xy_scale, int cap, int* n) {
 	CHECK_CTX(ctx);
 	CHECK_IMG(ctx, ii, iiStride, width, height);
 	if (!n || cap < 0 || (cap > 0 && !xy_scale)) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad output");
 	*n = 0;
 	FhDetector det;
-	if (cfg) det.cfg = *cfg; else bhip_fh_cfg_default(&det.cfg);
-	CtxScratch* sc = scratchOf(ctx);
-	int status = uploadImage(ctx, sc->a, ii, iiStart, iiStride, width, height);
-	if (status == BHIP_OK) status = det.prepare(ctx, width, height, 1);
-	ImgView iv{sc->a.as<float>(), (long long)width * height, width, width, height};
-	if (status == BHIP_OK) status = det.run(ctx, iv);
-	if (status == BHIP_OK) {
-		*n = det.counts[0];
-		const int ncopy = std::min(*n, cap);
-		if (ncopy > 0) {
-			std::vector<KeyPoint> kps(ncopy);
-			hipError_t e = hipMemcpyAsync(kps.data(), det.sorted.p, (size_t)ncopy * sizeof(KeyPoint), hipMemcpyDeviceToHost, ctx->stream);
-			if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-			if (e != hipSuccess) status = bhip_fail(ctx, BHIP_ERR_HIP, hipGetErrorString(e));
-			else for (int i = 0; i < ncopy; i++) { xy_scale[3 * i] = kps[i].x; xy_scale[3 * i + 1] = kps[i].y; xy_scale[3 * i + 2] = kps[i].scale; }
-		}
-	}
-	(void)hipStreamSynchronize(ctx->stream);
-	det.release();
-	return status;
-}
-
-// FastHessianFeatureDetector<GrayS32>.detect(integral) (the integral image of a GrayU8 frame)
-int bhip_fh_detect_s32(bhip_ctx* ctx, const bhip_fh_cfg* cfg, const int32_t* ii, int iiStart, int iiStride, int width, int height, double* xy_scale,
-					   int cap, int* n) {
-	CHECK_CTX(ctx);
-	if (!ii || width <= 0 || height <= 0 || iiStride < width) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image");
-	if (!n || cap < 0 || (cap > 0 && !xy_scale)) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad output");
-	*n = 0;
-	FhDetector det;
-	det.intTaps = true;
+	det.intTaps = intTaps;
 	if (cfg) det.cfg = *cfg; else bhip_fh_cfg_default(&det.cfg);
 	CtxScratch* sc = scratchOf(ctx);
 	int status = uploadImage(ctx, sc->a, (const float*)ii, iiStart, iiStride, width, height);   // 32-bit words either way
@@ -1300,9 +1235,16 @@ int bhip_fh_detect_s32(bhip_ctx* ctx, const bhip_fh_cfg* cfg, const int32_t* ii,
 			else for (int i = 0; i < ncopy; i++) { xy_scale[3 * i] = kps[i].x; xy_scale[3 * i + 1] = kps[i].y; xy_scale[3 * i + 2] = kps[i].scale; }
 		}
 	}
-	(void)hipStreamSynchronize(ctx->stream);
-	det.release();
+	(void)hipStreamSynchronize(ctx->stream);   // det's buffers are freed on return
 	return status;
+}
+int bhip_fh_detect_f32(bhip_ctx* ctx, const bhip_fh_cfg* cfg, const float* ii, int iiStart, int iiStride, int width, int height, double* xy_scale,
+					   int cap, int* n) {
+	return fhDetect(ctx, cfg, ii, false, iiStart, iiStride, width, height, xy_scale, cap, n);
+}
+int bhip_fh_detect_s32(bhip_ctx* ctx, const bhip_fh_cfg* cfg, const int32_t* ii, int iiStart, int iiStride, int width, int height, double* xy_scale,
+					   int cap, int* n) {
+	return fhDetect(ctx, cfg, ii, true, iiStart, iiStride, width, height, xy_scale, cap, n);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 #include <new>
+#include <utility>
 #include "../../include/boofhip.h"
 
 #define BHIP_WAVE 64
@@ -26,25 +27,54 @@ static inline bool bhip_env_flag(const char* name) {
 #define BHIP_ABLATE(P, bits) 0
 #endif
 
+// ---------------- owners of HIP resources ----------------
+// Move-only; the destructor frees, and a move assignment swaps (the old resource leaves with the moved-from object).  Destructors never
+// synchronize: the owner synchronizes before it drops device state, with the resource's device current.
+
+// a stream or an event the library created
+template <class H, hipError_t (*Destroy)(H)>
+struct HipHandle {
+	H h = nullptr;
+	HipHandle() = default;
+	HipHandle(HipHandle&& o) noexcept : h(o.h) { o.h = nullptr; }
+	HipHandle& operator=(HipHandle&& o) noexcept { std::swap(h, o.h); return *this; }
+	~HipHandle() { if (h) (void)Destroy(h); }
+	operator H() const { return h; }
+};
+using HipStream = HipHandle<hipStream_t, hipStreamDestroy>;
+using HipEvent = HipHandle<hipEvent_t, hipEventDestroy>;
+
+// grow-only page-locked host block
+struct PinnedBuf {
+	void* p = nullptr;
+	size_t cap = 0;
+	PinnedBuf() = default;
+	PinnedBuf(PinnedBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+	PinnedBuf& operator=(PinnedBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+	~PinnedBuf() { if (p) (void)hipHostFree(p); }
+	int reserve(bhip_ctx* ctx, size_t bytes);   // grows to exactly `bytes` (defined below DevBuf)
+	template <class T> T* as() const { return (T*)p; }
+};
+
 // one bracketed kernel launch (profiling mode only)
 struct ProfRecord {
 	const char* tag;
 	double algBytes;     // algorithmic HBM bytes of this launch, 0 when not an HBM-roofline kernel
 	double algFlops;     // algorithmic flops / integer ops of this launch, 0 when not a compute-roofline kernel
-	hipEvent_t start, stop;
+	HipEvent start, stop;
 };
 
 struct bhip_ctx {
 	int device = 0;
-	hipStream_t stream = nullptr;
-	bool ownStream = false;
+	hipStream_t stream = nullptr;   // ownedStream, or the caller's (bhip_ctx_create_on_stream)
+	HipStream ownedStream;          // declared first: destroyed last
 	std::string error;
 	// small pinned staging buffer for count read-backs
-	int* hostScratch = nullptr;
-	// optional per-kernel HIP-event timing on the ctx stream (bhip_profile_*)
+	PinnedBuf hostScratch;
+	// optional per-kernel HIP-event timing on the ctx stream (bhip_profile_*); every event of the ctx sits in one of the two lists
 	bool profiling = false;
 	std::vector<ProfRecord> profRecords;
-	std::vector<hipEvent_t> eventPool;
+	std::vector<HipEvent> eventPool;
 	size_t integralLdsAttr = 0;   // largest dynamic-LDS size k_integral_fused has been configured for on this ctx's device
 };
 
@@ -55,8 +85,6 @@ struct ProfScope {
 	ProfScope(bhip_ctx* c, const char* tag, double algBytes = 0, double algFlops = 0);
 	~ProfScope();
 };
-
-void bhip_profile_release(bhip_ctx* ctx);   // destroys the ctx's profiling events (profile.hip)
 
 static inline int bhip_fail(bhip_ctx* ctx, int code, const std::string& msg) {
 	if (ctx) ctx->error = msg;
@@ -80,6 +108,10 @@ static inline int bhip_fail(bhip_ctx* ctx, int code, const std::string& msg) {
 struct DevBuf {
 	void* p = nullptr;
 	size_t cap = 0;
+	DevBuf() = default;
+	DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+	DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+	~DevBuf() { if (p) (void)hipFree(p); }
 	int reserve(bhip_ctx* ctx, size_t bytes) {
 		if (bytes <= cap) return BHIP_OK;
 		if (p) { BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream)); BHIP_HIP(ctx, hipFree(p)); p = nullptr; cap = 0; }
@@ -88,9 +120,16 @@ struct DevBuf {
 		cap = want;
 		return BHIP_OK;
 	}
-	void release() { if (p) { (void)hipFree(p); p = nullptr; cap = 0; } }
 	template <class T> T* as() const { return (T*)p; }
 };
+
+inline int PinnedBuf::reserve(bhip_ctx* ctx, size_t bytes) {
+	if (bytes <= cap) return BHIP_OK;
+	if (p) { BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream)); (void)hipHostFree(p); p = nullptr; cap = 0; }
+	if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return bhip_fail(ctx, BHIP_ERR_NOMEM, "page-locked staging buffer"); }
+	cap = bytes;
+	return BHIP_OK;
+}
 
 // work buffers of the MFMA association path (assoc_mfma.hip)
 struct AssocMfmaWork {

@@ -3,10 +3,10 @@
 #include <map>
 #include <algorithm>
 
-static hipEvent_t takeEvent(bhip_ctx* ctx) {
-	if (!ctx->eventPool.empty()) { hipEvent_t e = ctx->eventPool.back(); ctx->eventPool.pop_back(); return e; }
-	hipEvent_t e = nullptr;
-	(void)hipEventCreate(&e);
+static HipEvent takeEvent(bhip_ctx* ctx) {
+	HipEvent e;
+	if (!ctx->eventPool.empty()) { e = std::move(ctx->eventPool.back()); ctx->eventPool.pop_back(); }
+	else (void)hipEventCreate(&e.h);
 	return e;
 }
 
@@ -21,18 +21,10 @@ ProfScope::ProfScope(bhip_ctx* c, const char* tag, double algBytes, double algFl
 	r.stop = takeEvent(ctx);
 	(void)hipEventRecord(r.start, ctx->stream);
 	idx = (int)ctx->profRecords.size();
-	ctx->profRecords.push_back(r);
+	ctx->profRecords.push_back(std::move(r));
 }
 ProfScope::~ProfScope() {
 	if (idx >= 0) (void)hipEventRecord(ctx->profRecords[idx].stop, ctx->stream);
-}
-
-// ctx teardown: every event ever created for this ctx sits in profRecords or in the pool
-void bhip_profile_release(bhip_ctx* ctx) {
-	for (auto& r : ctx->profRecords) { if (r.start) (void)hipEventDestroy(r.start); if (r.stop) (void)hipEventDestroy(r.stop); }
-	ctx->profRecords.clear();
-	for (hipEvent_t e : ctx->eventPool) if (e) (void)hipEventDestroy(e);
-	ctx->eventPool.clear();
 }
 
 struct ProfAgg { double ms = 0, bytes = 0, flops = 0; long long launches = 0; };
@@ -48,7 +40,7 @@ int bhip_profile_enable(bhip_ctx* ctx, int on) {
 int bhip_profile_reset(bhip_ctx* ctx) {
 	if (!ctx) return BHIP_ERR_INVALID;
 	(void)hipStreamSynchronize(ctx->stream);
-	for (auto& r : ctx->profRecords) { ctx->eventPool.push_back(r.start); ctx->eventPool.push_back(r.stop); }
+	for (auto& r : ctx->profRecords) { ctx->eventPool.push_back(std::move(r.start)); ctx->eventPool.push_back(std::move(r.stop)); }
 	ctx->profRecords.clear();
 	return BHIP_OK;
 }

@@ -23,7 +23,8 @@
  *  - handles may be destroyed in any order and more than once: bhip_ctx_destroy releases the device side of every bhip_surf created on
  *    that context (they become inert: every call on them returns BHIP_ERR_INVALID, bhip_surf_destroy then only frees the shell), a
  *    pointer that is not a live handle is refused with BHIP_ERR_INVALID, and once the process is exiting the destroy calls do nothing
- *    (a finaliser that runs after the HIP runtime has shut down is harmless).
+ *    (a finaliser that runs after the HIP runtime has shut down is harmless);
+ *  - a context must not be destroyed while another thread is inside a call on it or on an object created on it.
  */
 #ifndef BOOFHIP_H
 #define BOOFHIP_H
