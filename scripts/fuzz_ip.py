@@ -2,7 +2,9 @@
 """One-off wide parity sweep of the boofcv-ip front end (GPU vs the CPU oracle), bit-exact: separable convolution (plain and
 border-normalised, unrolled and standard widths), Gaussian blur, mean / median blur, Sobel / three-tap gradients (with and without the
 zero border), the down-sampling convolution and the discrete pyramid (incl. the step >= 3 quirks), Shi-Tomasi / Harris corner
-intensity -- random shapes, radii, steps and value ranges.
+intensity -- random shapes, radii, steps and value ranges.  About one case in four also draws a wide case: 18..255 taps, a random origin, one
+of the four separable variants or the two-pass Gaussian blur (the tiled, general and naive kernels).  The wide cases come from a second
+generator seeded from `seed`, so a seed replays the same narrow cases as before they were added.
 
     python scripts/fuzz_ip.py [seed] [cases]"""
 import os
@@ -25,6 +27,47 @@ def bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
+def wide_case(rng, check):
+    """one wide separable convolution or two-pass Gaussian blur: kw 18..255, a random origin, the filtered axis from half the kernel
+    (naive form) to 300 pixels past it, the other axis short, so that a case stays cheap"""
+    kw = int(rng.integers(18, 256))
+    variant = ["h", "v", "norm_h", "norm_v", "gaussian"][int(rng.integers(0, 5))]
+    L = int(rng.integers(max(kw // 2, 1), kw + 300))
+    S = int(rng.integers(4, 48))
+    w, h = (L, S) if variant in ("h", "norm_h", "gaussian") else (S, L)
+    if variant == "gaussian" and rng.random() < 0.5:
+        w, h = h, w
+    lo, hi = [(0, 255), (-5, 5), (1e3, 1e4)][int(rng.integers(0, 3))]
+    img = orc.Gray.from_array(rng.uniform(lo, hi, (h, w)).astype(np.float32))
+    if variant == "gaussian":
+        r = kw // 2
+        check("wide gaussian", api.BlurImageOps.gaussian(G(img), None, -1, r).array(), orc.gaussian_blur(img, -1, r).array(), w, h, r)
+        return
+    off = int(rng.integers(0, kw))
+    kind_of_kernel = int(rng.integers(0, 3 if variant in ("h", "v") else 2))
+    if kind_of_kernel == 0:
+        ker = orc.gaussian1d_f32(-1, kw // 2)[:kw].copy()
+    elif kind_of_kernel == 1:   # positive, sum 1.3: re-normalised by the normalised variants
+        ker = rng.uniform(0.5, 1.5, kw).astype(np.float32)
+        ker = (ker * np.float32(1.3 / ker.sum())).astype(np.float32)
+    else:                       # signed (no-border variants only: clipped weights could sum to 0)
+        ker = (rng.uniform(-1, 1, kw) / np.sqrt(kw)).astype(np.float32)
+    cls = api.ConvolveImageNormalized if variant.startswith("norm") else api.ConvolveImageNoBorder
+    out = api.GrayF32(w, h)
+    out.data[:] = -7.0
+    getattr(cls, "horizontal" if variant.endswith("h") else "vertical")(api.Kernel1D_F32(ker, offset=off), G(img), out)
+    exp = orc.conv(variant, ker, off, img).array().copy()
+    if not variant.startswith("norm"):   # the frame keeps the caller's pixels
+        keep = np.ones((h, w), bool)
+        offR = kw - off - 1
+        if variant == "h":
+            keep[:, off:max(off, w - offR)] = False
+        else:
+            keep[off:max(off, h - offR), :] = False
+        exp[keep] = -7.0
+    check("wide conv " + variant, out.array(), exp, w, h, kw, off, kind_of_kernel)
+
+
 def main(seed=None, cases=None):
     """seed / cases default to the command line (tests/test_gpu_fuzz_slice.py runs a bounded slice in-process)"""
     if seed is None:
@@ -32,9 +75,11 @@ def main(seed=None, cases=None):
     if cases is None:
         cases = int(sys.argv[2]) if len(sys.argv) > 2 else 100
     rng = np.random.default_rng(seed)
+    wide_rng = np.random.default_rng([seed, 0x77])   # the wide cases: a stream of their own (the narrow draws above stay as they were)
     orc.build()
     bad = 0
     checks = 0
+    wide = 0
     t0 = time.time()
 
     def check(name, got, exp, *ctx):
@@ -128,9 +173,16 @@ def main(seed=None, cases=None):
         except Exception as ex:
             bad += 1
             print("EXCEPTION", w, h, type(ex).__name__, str(ex)[:160], flush=True)
+        if wide_rng.random() < 0.25:
+            wide += 1
+            try:
+                wide_case(wide_rng, check)
+            except Exception as ex:
+                bad += 1
+                print("EXCEPTION wide", type(ex).__name__, str(ex)[:160], flush=True)
         if k % 25 == 24:
             print("progress", k + 1, "cases", checks, "checks", round(time.time() - t0, 1), "s, mismatches", bad, flush=True)
-    print("done:", cases, "cases,", checks, "checks,", bad, "mismatches")
+    print("done:", cases, "cases (%d with a wide case)," % wide, checks, "checks,", bad, "mismatches")
     return 1 if bad else 0
 
 
