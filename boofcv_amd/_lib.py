@@ -105,6 +105,11 @@ SIGNATURES = {
     "bhip_mean_f32": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _i, _fp, _i, _i]),
     "bhip_median_f32": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _fp, _i, _i]),
     "bhip_corner_intensity_f32": (_i, [_vp, _i, _i, _f, _fp, _fp, _i, _i, _i, _i, _fp, _i, _i]),
+    "bhip_sobel_u8_s16": (_i, [_vp, _u8p, _i, _i, _i, _i, _i16p, _i16p, _i, _i, _i]),
+    "bhip_three_u8_s16": (_i, [_vp, _u8p, _i, _i, _i, _i, _i16p, _i16p, _i, _i, _i]),
+    "bhip_corner_intensity_s16": (_i, [_vp, _i, _i, _f, _i, _i16p, _i16p, _i, _i, _i, _i, _fp, _i, _i]),
+    "bhip_corner_intensity_weighted_f32": (_i, [_vp, _i, _i, _f, _fp, _fp, _i, _i, _i, _i, _fp, _i, _i]),
+    "bhip_gaussian_kernel1d_s32": (_i, [_i, _i32p, _i]),
     "bhip_integral_u8_s32": (_i, [_vp, _u8p, _i, _i, _i, _i, _i32p, _i, _i]),
     "bhip_hessian_s32": (_i, [_vp, _i32p, _i, _i, _i, _i, _i, _i, _fp, _i, _i]),
     "bhip_fh_detect_s32": (_i, [_vp, P(FhCfg), _i32p, _i, _i, _i, _i, _dp, _i, _ip]),
@@ -120,6 +125,10 @@ SIGNATURES = {
     "bhip_gradient_intensity_dev_f32": (_i, [_vp, _i, _vp, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i]),
     "bhip_nonmax_block_dev_f32": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _i, _vp, _i, _vp]),
     "bhip_corner_intensity_dev_f32": (_i, [_vp, _i, _i, _f, _vp, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i]),
+    "bhip_sobel_dev_u8_s16": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _vp, _vp, _ll, _i, _i]),
+    "bhip_three_dev_u8_s16": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _vp, _vp, _ll, _i, _i]),
+    "bhip_corner_intensity_dev_s16": (_i, [_vp, _i, _i, _f, _i, _vp, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i]),
+    "bhip_corner_intensity_weighted_dev_f32": (_i, [_vp, _i, _i, _f, _vp, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i]),
     "bhip_brief_dev_f32": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _i32p, _i32p, _vp, _ip, _vp]),
 }
 

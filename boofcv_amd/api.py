@@ -293,7 +293,7 @@ class TupleDesc_F64:
 
 
 class _GrayInt:
-    """Integer single-band images (T:struct/image/GrayU8.java, GrayS32.java): pixel (x,y) = data[startIndex + y*stride + x]."""
+    """Integer single-band images (T:struct/image/GrayU8.java, GrayS16.java, GrayS32.java): pixel (x,y) = data[startIndex + y*stride + x]."""
     dtype = None
 
     def __init__(self, width=0, height=0, data=None, startIndex=0, stride=None):
@@ -333,6 +333,13 @@ class GrayU8(_GrayInt):
 
     def _p(self):
         return self.data.ctypes.data_as(_lib._u8p)
+
+
+class GrayS16(_GrayInt):
+    dtype = np.int16
+
+    def _p(self):
+        return self.data.ctypes.data_as(_lib._i16p)
 
 
 class GrayS32(_GrayInt):
@@ -1363,44 +1370,67 @@ class SelectNBestFeatures:
 
 
 class GradientCornerIntensity:
-    """FactoryIntensityPointAlg.shiTomasi / harris (unweighted, GrayF32 derivatives): ImplSsdCorner_F32 with ShiTomasiCorner_F32 /
-    HarrisCorner_F32 (F:alg/feature/detect/intensity/impl/ImplSsdCorner_F32.java:62-196).  Single-threaded summation order."""
+    """FactoryIntensityPointAlg.shiTomasi / harris (F:factory/feature/detect/intensity/FactoryIntensityPointAlg.java:91-160):
+      unweighted, GrayF32   ImplSsdCorner_F32 with ShiTomasiCorner_F32 / HarrisCorner_F32 (F:alg/feature/detect/intensity/impl/ImplSsdCorner_F32.java:62-196),
+                            the single-threaded summation order
+      unweighted, GrayS16   ImplSsdCorner_S16 with ShiTomasiCorner_S32 / HarrisCorner_S32 (.../impl/ImplSsdCorner_S16.java:63-198)
+      weighted, GrayF32     ImplSsdCornerWeighted_F32 (.../impl/ImplSsdCornerWeighted_F32.java:46-104)
+      weighted, GrayS16     ImplSsdCornerWeighted_S16 (.../impl/ImplSsdCornerWeighted_S16.java:50-108)"""
 
-    def __init__(self, kind, windowRadius, kappa=0.0, ctx=None):
+    def __init__(self, kind, windowRadius, kappa=0.0, ctx=None, weighted=False, derivType=None):
         self.kind, self.radius, self.kappa = kind, int(windowRadius), float(kappa)
+        self.weighted = bool(weighted)
+        self.derivType = GrayF32 if derivType is None else derivType
         self.ctx = _ctx(ctx)
 
     def getRadius(self):
         return self.radius
 
     def getIgnoreBorder(self):
-        return self.radius
+        return 0 if self.weighted else self.radius   # ImplSsdCornerWeighted_*.getIgnoreBorder / ImplSsdCornerBox
+
+    def getInputType(self):
+        return self.derivType
 
     def process(self, derivX, derivY, intensity):
+        for d in (derivX, derivY):
+            if isinstance(d, GrayS16) != (self.derivType is GrayS16) or isinstance(d, (GrayU8, GrayS32)):
+                raise IllegalArgumentException("derivatives must be %s" % self.derivType.__name__)
         if derivX.width != derivY.width or derivX.height != derivY.height:
             raise IllegalArgumentException("Image shapes do not match")   # InputSanityCheck.checkSameShape
         if (derivX.startIndex, derivX.stride) != (derivY.startIndex, derivY.stride):
             raise IllegalArgumentException("derivX and derivY must share startIndex and stride")
         intensity.reshape(derivX.width, derivX.height)
-        _check(self.ctx, _lib.load().bhip_corner_intensity_f32(self.ctx._h, self.kind, self.radius, self.kappa, derivX._p(), derivY._p(), derivX.startIndex,
-                                                               derivX.stride, derivX.width, derivX.height, intensity._p(), intensity.startIndex,
-                                                               intensity.stride))
+        L = _lib.load()
+        args = (derivX._p(), derivY._p(), derivX.startIndex, derivX.stride, derivX.width, derivX.height, intensity._p(), intensity.startIndex,
+                intensity.stride)
+        if self.derivType is GrayS16:
+            _check(self.ctx, L.bhip_corner_intensity_s16(self.ctx._h, self.kind, self.radius, self.kappa, 1 if self.weighted else 0, *args))
+        elif self.weighted:
+            _check(self.ctx, L.bhip_corner_intensity_weighted_f32(self.ctx._h, self.kind, self.radius, self.kappa, *args))
+        else:
+            _check(self.ctx, L.bhip_corner_intensity_f32(self.ctx._h, self.kind, self.radius, self.kappa, *args))
+
+
+def _corner_intensity(kind, windowRadius, kappa, weighted, derivType, ctx):
+    derivType = GrayF32 if derivType is None else derivType
+    if derivType is not GrayF32 and derivType is not GrayS16:
+        raise RuntimeError("only GrayF32 and GrayS16 derivatives are implemented on the GPU (use the Java path)")
+    if weighted and int(windowRadius) <= 0:
+        raise IllegalArgumentException("Radius must be > 0")   # FactoryKernelGaussian.sigmaForRadius, from the ImplSsdCornerWeighted_* constructor
+    return GradientCornerIntensity(kind, windowRadius, kappa, ctx, weighted, derivType)
 
 
 class FactoryIntensityPointAlg:
     @staticmethod
     def shiTomasi(windowRadius, weighted=False, derivType=None, ctx=None):
         """F:factory/feature/detect/intensity/FactoryIntensityPointAlg.java:132-160"""
-        if weighted or (derivType is not None and derivType is not GrayF32):
-            raise RuntimeError("only the unweighted GrayF32 corner intensity is implemented on the GPU (use the Java path)")
-        return GradientCornerIntensity(0, windowRadius, 0.0, ctx)
+        return _corner_intensity(0, windowRadius, 0.0, weighted, derivType, ctx)
 
     @staticmethod
     def harris(windowRadius, kappa, weighted=False, derivType=None, ctx=None):
         """F:factory/feature/detect/intensity/FactoryIntensityPointAlg.java:91-118"""
-        if weighted or (derivType is not None and derivType is not GrayF32):
-            raise RuntimeError("only the unweighted GrayF32 corner intensity is implemented on the GPU (use the Java path)")
-        return GradientCornerIntensity(1, windowRadius, kappa, ctx)
+        return _corner_intensity(1, windowRadius, kappa, weighted, derivType, ctx)
 
 
 class GeneralFeatureDetector:
@@ -1540,6 +1570,17 @@ class FactoryKernelGaussian:
         out = np.zeros(w, dtype=np.float32)
         L.bhip_gaussian_kernel1d_f32(float(sigma), int(radius), out.ctypes.data_as(_lib._fp), w)
         return Kernel1D_F32(out)
+
+    @staticmethod
+    def gaussian1D_S32(radius):
+        """FactoryKernelGaussian.gaussian(Kernel1D_S32.class, -1, radius) (I:factory/filter/kernel/FactoryKernelGaussian.java:120-160): int32 taps"""
+        if radius <= 0:
+            raise IllegalArgumentException("Radius must be > 0")
+        L = _lib.load()
+        w = -L.bhip_gaussian_kernel1d_s32(int(radius), None, 0)
+        out = np.zeros(w, dtype=np.int32)
+        L.bhip_gaussian_kernel1d_s32(int(radius), out.ctypes.data_as(_lib._i32p), w)
+        return out
 
 
 class ConvolveImageDownNormalized:
@@ -1690,25 +1731,36 @@ class BlurImageOps:
 
 class _Gradient:
     fn = None
+    fn_u8 = None
 
     @classmethod
     def process(cls, orig, derivX, derivY, border=None, ctx=None):
-        """border: None = null (frame untouched) or 0 = ImageBorderValue(0)"""
+        """border: None = null (frame untouched) or 0 = ImageBorderValue(0).  GrayF32 -> GrayF32, or GrayU8 -> GrayS16."""
         ctx = _ctx(ctx)
         if border not in (None, 0):
             raise RuntimeError("border policy not implemented on the GPU")
-        _check(ctx, getattr(_lib.load(), cls.fn)(ctx._h, orig._p(), orig.startIndex, orig.stride, orig.width, orig.height, derivX._p(), derivY._p(),
-                                                 derivX.startIndex, derivX.stride, 0 if border is None else 1))
+        if isinstance(orig, GrayU8):
+            if not isinstance(derivX, GrayS16) or not isinstance(derivY, GrayS16):
+                raise IllegalArgumentException("a GrayU8 image has GrayS16 derivatives")
+            fn = cls.fn_u8
+        elif isinstance(orig, GrayF32):
+            fn = cls.fn
+        else:
+            raise RuntimeError("only GrayF32 and GrayU8 images are implemented on the GPU (use the Java path)")
+        _check(ctx, getattr(_lib.load(), fn)(ctx._h, orig._p(), orig.startIndex, orig.stride, orig.width, orig.height, derivX._p(), derivY._p(),
+                                             derivX.startIndex, derivX.stride, 0 if border is None else 1))
 
 
 class GradientSobel(_Gradient):
-    """I:alg/filter/derivative/GradientSobel.java:158-173"""
+    """I:alg/filter/derivative/GradientSobel.java:110-124 (GrayU8), 158-173 (GrayF32)"""
     fn = "bhip_sobel_f32"
+    fn_u8 = "bhip_sobel_u8_s16"
 
 
 class GradientThree(_Gradient):
-    """I:alg/filter/derivative/GradientThree.java -> impl/GradientThree_Standard.java:40-62"""
+    """I:alg/filter/derivative/GradientThree.java -> impl/GradientThree_Standard.java:40-62 (GrayF32), 67-88 (GrayU8)"""
     fn = "bhip_three_f32"
+    fn_u8 = "bhip_three_u8_s16"
 
 
 class DescribePointBrief:

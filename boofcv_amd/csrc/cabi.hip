@@ -1735,6 +1735,92 @@ int bhip_corner_intensity_f32(bhip_ctx* ctx, int kind, int radius, float kappa, 
 	return downloadImage(ctx, sc->d.p, intensity, iStart, iStride, width, height);
 }
 
+// ---- GrayU8 -> GrayS16 gradients and the S16 / weighted corner intensity ----
+// element-size copies of an image view to / from a dense device copy (integer images)
+static int uploadElems(bhip_ctx* ctx, DevBuf& buf, const void* in, size_t es, int start, int stride, int w, int h) {
+	BHIP_TRY(buf.reserve(ctx, es * w * h));
+	BHIP_HIP(ctx, hipMemcpy2DAsync(buf.p, es * w, static_cast<const char*>(in) + es * start, es * stride, es * w, h, hipMemcpyHostToDevice, ctx->stream));
+	return BHIP_OK;
+}
+static int downloadElems(bhip_ctx* ctx, const void* dev, void* out, size_t es, int start, int stride, int w, int h) {
+	BHIP_HIP(ctx, hipMemcpy2DAsync(static_cast<char*>(out) + es * start, es * stride, dev, es * w, es * w, h, hipMemcpyDeviceToHost, ctx->stream));
+	return BHIP_OK;
+}
+static int gradU8Host(bhip_ctx* ctx, int kind, const uint8_t* in, int inStart, int inStride, int width, int height, int16_t* dx, int16_t* dy, int outStart,
+					  int outStride, int border) {
+	CHECK_IMG(ctx, in, inStride, width, height);
+	CHECK_IMG(ctx, dx, outStride, width, height);
+	CHECK_IMG(ctx, dy, outStride, width, height);
+	if (border != 0 && border != 1) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "border policy not supported on the GPU");
+	CtxScratch* sc = scratchOf(ctx);
+	BHIP_TRY(uploadElems(ctx, sc->a, in, 1, inStart, inStride, width, height));
+	// without a border policy the frame keeps the caller's values
+	BHIP_TRY(uploadElems(ctx, sc->b, dx, 2, outStart, outStride, width, height));
+	BHIP_TRY(uploadElems(ctx, sc->c, dy, 2, outStart, outStride, width, height));
+	BHIP_TRY(bhip_launch_gradient_u8(ctx, kind, static_cast<const uint8_t*>(sc->a.p), 0, width, width, height, 1, static_cast<int16_t*>(sc->b.p),
+									 static_cast<int16_t*>(sc->c.p), 0, width, border));
+	BHIP_TRY(downloadElems(ctx, sc->b.p, dx, 2, outStart, outStride, width, height));
+	BHIP_TRY(downloadElems(ctx, sc->c.p, dy, 2, outStart, outStride, width, height));
+	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return BHIP_OK;
+}
+int bhip_sobel_u8_s16(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, int16_t* dx, int16_t* dy, int outStart,
+					  int outStride, int border) {
+	CHECK_CTX(ctx);
+	return gradU8Host(ctx, 0, in, inStart, inStride, width, height, dx, dy, outStart, outStride, border);
+}
+int bhip_three_u8_s16(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, int16_t* dx, int16_t* dy, int outStart,
+					  int outStride, int border) {
+	CHECK_CTX(ctx);
+	return gradU8Host(ctx, 1, in, inStart, inStride, width, height, dx, dy, outStart, outStride, border);
+}
+
+// box (ImplSsdCorner_S16) or weighted (ImplSsdCornerWeighted_S16) on device images; scratch from the context when the box radius needs it
+static int cornerS16Dev(bhip_ctx* ctx, DevBuf& scratch, int kind, int radius, float kappa, int weighted, const int16_t* dx, const int16_t* dy,
+						long long dImageStride, int dStride, int width, int height, int batch, float* intensity, long long iImageStride, int iStride) {
+	if (weighted)
+		return bhip_launch_corner_weighted(ctx, true, kind, radius, kappa, dx, dy, dImageStride, dStride, width, height, batch, intensity, iImageStride, iStride);
+	if (radius >= 0 && 2 * radius + 1 <= width && 2 * radius + 1 <= height) {
+		const size_t bytes = bhip_corner_box_s16_scratch(radius, width, height, batch);
+		if (bytes) BHIP_TRY(scratch.reserve(ctx, bytes));
+	}
+	return bhip_launch_corner_box_s16(ctx, kind, radius, kappa, dx, dy, dImageStride, dStride, width, height, batch, intensity, iImageStride, iStride, scratch.p);
+}
+int bhip_corner_intensity_s16(bhip_ctx* ctx, int kind, int radius, float kappa, int weighted, const int16_t* derivX, const int16_t* derivY, int dStart,
+							  int dStride, int width, int height, float* intensity, int iStart, int iStride) {
+	CHECK_CTX(ctx);
+	CHECK_IMG(ctx, derivX, dStride, width, height);
+	CHECK_IMG(ctx, derivY, dStride, width, height);
+	CHECK_IMG(ctx, intensity, iStride, width, height);
+	CtxScratch* sc = scratchOf(ctx);
+	BHIP_TRY(uploadElems(ctx, sc->a, derivX, 2, dStart, dStride, width, height));
+	BHIP_TRY(uploadElems(ctx, sc->b, derivY, 2, dStart, dStride, width, height));
+	BHIP_TRY(sc->d.reserve(ctx, (size_t)width * height * 4));
+	BHIP_TRY(cornerS16Dev(ctx, sc->c, kind, radius, kappa, weighted, static_cast<const int16_t*>(sc->a.p), static_cast<const int16_t*>(sc->b.p), 0, width,
+						  width, height, 1, sc->d.as<float>(), 0, width));
+	return downloadImage(ctx, sc->d.p, intensity, iStart, iStride, width, height);
+}
+int bhip_corner_intensity_weighted_f32(bhip_ctx* ctx, int kind, int radius, float kappa, const float* derivX, const float* derivY, int dStart, int dStride,
+									   int width, int height, float* intensity, int iStart, int iStride) {
+	CHECK_CTX(ctx);
+	CHECK_IMG(ctx, derivX, dStride, width, height);
+	CHECK_IMG(ctx, derivY, dStride, width, height);
+	CHECK_IMG(ctx, intensity, iStride, width, height);
+	CtxScratch* sc = scratchOf(ctx);
+	BHIP_TRY(uploadImage(ctx, sc->a, derivX, dStart, dStride, width, height));
+	BHIP_TRY(uploadImage(ctx, sc->b, derivY, dStart, dStride, width, height));
+	BHIP_TRY(sc->d.reserve(ctx, (size_t)width * height * 4));
+	BHIP_TRY(bhip_launch_corner_weighted(ctx, false, kind, radius, kappa, sc->a.p, sc->b.p, 0, width, width, height, 1, sc->d.as<float>(), 0, width));
+	return downloadImage(ctx, sc->d.p, intensity, iStart, iStride, width, height);
+}
+int bhip_gaussian_kernel1d_s32(int radius, int32_t* out, int capacity) {
+	if (radius <= 0) return -1;
+	std::vector<int32_t> k = bhip_gaussian1d_s32(radius);
+	if (!out || (int)k.size() > capacity) return -(int)k.size();
+	for (size_t i = 0; i < k.size(); i++) out[i] = k[i];
+	return (int)k.size();
+}
+
 // ---- integer image variants, stage level ----
 int bhip_integral_u8_s32(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, int32_t* out, int outStart, int outStride) {
 	CHECK_CTX(ctx);
@@ -1917,6 +2003,43 @@ int bhip_corner_intensity_dev_f32(bhip_ctx* ctx, int kind, int radius, float kap
 	float* h = sc->ipTmp.as<float>();
 	return bhip_launch_corner_intensity(ctx, kind, radius, kappa, dev_dx, dev_dy, dStride, width, height, h, h + px, h + 2 * px, dev_intensity, iStride, batch,
 										dImageStride, (long long)px * 3, iImageStride);
+}
+
+static int gradU8Dev(bhip_ctx* ctx, int kind, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dev_dx,
+					 int16_t* dev_dy, long long outImageStride, int outStride, int border) {
+	CHECK_DEV_BATCH(ctx, dev_in, inStride, width, height, batch);
+	CHECK_DEV_BATCH(ctx, dev_dx, outStride, width, height, batch);
+	CHECK_DEV_BATCH(ctx, dev_dy, outStride, width, height, batch);
+	if (border != 0 && border != 1) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "border policy not supported on the GPU");
+	return bhip_launch_gradient_u8(ctx, kind, dev_in, inImageStride, inStride, width, height, batch, dev_dx, dev_dy, outImageStride, outStride, border);
+}
+int bhip_sobel_dev_u8_s16(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dev_dx,
+						  int16_t* dev_dy, long long outImageStride, int outStride, int border) {
+	CHECK_CTX(ctx);
+	return gradU8Dev(ctx, 0, dev_in, inImageStride, inStride, width, height, batch, dev_dx, dev_dy, outImageStride, outStride, border);
+}
+int bhip_three_dev_u8_s16(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dev_dx,
+						  int16_t* dev_dy, long long outImageStride, int outStride, int border) {
+	CHECK_CTX(ctx);
+	return gradU8Dev(ctx, 1, dev_in, inImageStride, inStride, width, height, batch, dev_dx, dev_dy, outImageStride, outStride, border);
+}
+int bhip_corner_intensity_dev_s16(bhip_ctx* ctx, int kind, int radius, float kappa, int weighted, const int16_t* dev_dx, const int16_t* dev_dy,
+								  long long dImageStride, int dStride, int width, int height, int batch, float* dev_intensity, long long iImageStride, int iStride) {
+	CHECK_CTX(ctx);
+	CHECK_DEV_BATCH(ctx, dev_dx, dStride, width, height, batch);
+	CHECK_DEV_BATCH(ctx, dev_dy, dStride, width, height, batch);
+	CHECK_DEV_BATCH(ctx, dev_intensity, iStride, width, height, batch);
+	return cornerS16Dev(ctx, scratchOf(ctx)->ipTmp, kind, radius, kappa, weighted, dev_dx, dev_dy, dImageStride, dStride, width, height, batch, dev_intensity,
+						iImageStride, iStride);
+}
+int bhip_corner_intensity_weighted_dev_f32(bhip_ctx* ctx, int kind, int radius, float kappa, const float* dev_dx, const float* dev_dy, long long dImageStride,
+										   int dStride, int width, int height, int batch, float* dev_intensity, long long iImageStride, int iStride) {
+	CHECK_CTX(ctx);
+	CHECK_DEV_BATCH(ctx, dev_dx, dStride, width, height, batch);
+	CHECK_DEV_BATCH(ctx, dev_dy, dStride, width, height, batch);
+	CHECK_DEV_BATCH(ctx, dev_intensity, iStride, width, height, batch);
+	return bhip_launch_corner_weighted(ctx, false, kind, radius, kappa, dev_dx, dev_dy, dImageStride, dStride, width, height, batch, dev_intensity, iImageStride,
+									   iStride);
 }
 
 // DescribePointBrief.process over a batch: the points of image b are dev_xy[start[b] .. start[b+1]) (host prefix `start`, batch+1 entries);

@@ -186,6 +186,7 @@ struct SurfTables {
 std::vector<double> bhip_gaussian2d_f64(double sigma, int radius);          // FactoryKernelGaussian.gaussian(2,true,64,sigma,radius)
 std::vector<double> bhip_gaussian_width(double sigma, int width);           // FactoryKernelGaussian.gaussianWidth
 std::vector<float> bhip_gaussian1d_f32(double sigma, int radius);           // FactoryKernelGaussian.gaussian(Kernel1D_F32,sigma,radius)
+std::vector<int32_t> bhip_gaussian1d_s32(int radius);                       // FactoryKernelGaussian.gaussian(Kernel1D_S32,-1,radius)
 
 // ---------------- kernel launchers (defined in the .hip files) ----------------
 int bhip_launch_integral(bhip_ctx* ctx, ImgView in, ImgViewW out, int batch);
@@ -269,6 +270,16 @@ int bhip_launch_mean(bhip_ctx* ctx, bool vertical, const float* in, float* out, 
 int bhip_launch_median(bhip_ctx* ctx, const float* in, int inStride, float* out, int outStride, int width, int height, int radius);
 int bhip_launch_gradient(bhip_ctx* ctx, int kind, const float* in, int inStride, int width, int height, float* dx, float* dy, int outStride, int border,
 						 int batch = 1, long long inImageStride = 0, long long outImageStride = 0);
+// integer gradient + corner path (ip.hip): GrayU8 -> GrayS16 gradients (kind 0 Sobel, 1 three-tap), fused S16 box corner intensity,
+// fused Gaussian-weighted corner intensity on F32 or S16 derivatives.  Element strides throughout.
+int bhip_launch_gradient_u8(bhip_ctx* ctx, int kind, const uint8_t* in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dx,
+							int16_t* dy, long long outImageStride, int outStride, int border);
+size_t bhip_corner_box_s16_scratch(int radius, int width, int height, int batch);   // bytes of `scratch` bhip_launch_corner_box_s16 needs (0: none)
+int bhip_launch_corner_box_s16(bhip_ctx* ctx, int kind, int radius, float kappa, const int16_t* dx, const int16_t* dy, long long dImageStride, int dStride,
+							   int width, int height, int batch, float* intensity, long long iImageStride, int iStride, void* scratch);
+int bhip_corner_weighted_max_radius();
+int bhip_launch_corner_weighted(bhip_ctx* ctx, bool s16, int kind, int radius, float kappa, const void* dx, const void* dy, long long dImageStride, int dStride,
+								int width, int height, int batch, float* intensity, long long iImageStride, int iStride);
 int bhip_launch_grad_intensity(bhip_ctx* ctx, int kind, const float* dx, const float* dy, long long dImageStride, int dStride, float* out,
 							   long long oImageStride, int oStride, int width, int height, int batch);
 int bhip_launch_brief(bhip_ctx* ctx, const float* img, int stride, int width, int height, int radius, int numPoints, const int* samplePoints,

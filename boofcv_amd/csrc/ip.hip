@@ -15,6 +15,7 @@
 //   ImplDescribeBinaryCompare_F32                 F:alg/feature/describe/impl/ImplDescribeBinaryCompare_F32.java:47-101
 // Bound: HBM (8P bytes per separable pass, 12P for a gradient); taps are re-read through L1/L2.
 #include "common.h"
+#include <type_traits>
 
 #define BHIP_MAX_TAPS 255
 
@@ -629,6 +630,27 @@ __global__ __launch_bounds__(64 * WPB) void k_blur_fused(ConvParams P) {
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// ConvolveImageNormalized.horizontal / vertical (F32) along an axis of `extent` pixels: the naive form (mode 2) when the kernel is at least as
+// wide as the image, else border re-normalisation (mode 1) with the kernel re-normalised first when |sum - 1| > 1e-4 (Kernel1D_F32.computeSum
+// is a sequential fp32 sum).  P.k / P.kw must be set.
+static void setNormalizedMode(ConvParams& P, int extent) {
+	const int kw = P.kw;
+	if (kw >= extent) {
+		P.mode = 2;
+		return;
+	}
+	P.mode = 1;
+	float sum = 0;
+	for (int i = 0; i < kw; i++) sum += P.k[i];
+	float diff = sum - 1.0f;
+	if (diff < 0) diff = -diff;
+	if (diff > 1e-4f) {
+		float total = 0;
+		for (int i = 0; i < kw; i++) total += P.k[i];
+		for (int i = 0; i < kw; i++) P.k[i] /= total;
+	}
+}
+
 int bhip_launch_conv(bhip_ctx* ctx, bool vertical, bool normalized, const float* kernel, int kw, int koff, const float* in, int inStride, int width,
 					 int height, float* out, int outStride, int batch, long long inImageStride, long long outImageStride) {
 	if (kw <= 0 || kw > BHIP_MAX_TAPS || koff < 0 || koff >= kw) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "kernel width not supported");
@@ -640,24 +662,7 @@ int bhip_launch_conv(bhip_ctx* ctx, bool vertical, bool normalized, const float*
 	P.unrolled = (koff == kw / 2 && kw % 2 == 1 && (kw == 3 || kw == 5 || kw == 7 || kw == 9 || kw == 11)) ? 1 : 0;
 	P.mode = 0;
 	P.borderOnly = 0;
-	if (normalized) {
-		const int extent = vertical ? height : width;
-		if (kw >= extent) {
-			P.mode = 2;
-		} else {
-			P.mode = 1;
-			// ConvolveImageNormalized: re-normalise when |sum - 1| > 1e-4 (Kernel1D_F32.computeSum is a sequential fp32 sum)
-			float sum = 0;
-			for (int i = 0; i < kw; i++) sum += P.k[i];
-			float diff = sum - 1.0f;
-			if (diff < 0) diff = -diff;
-			if (diff > 1e-4f) {
-				float total = 0;
-				for (int i = 0; i < kw; i++) total += P.k[i];
-				for (int i = 0; i < kw; i++) P.k[i] /= total;
-			}
-		}
-	}
+	if (normalized) setNormalizedMode(P, vertical ? height : width);
 	ProfScope prof(ctx, vertical ? "k_conv_v" : "k_conv_h", 8.0 * width * height * batch);
 	// tiled forms need 16-byte aligned rows on both sides; the naive form (kernel wider than the image) stays on the general kernel
 	const bool tiled = P.mode != 2 && aligned16(in) && aligned16(out) && inStride % 4 == 0 && outStride % 4 == 0 && inImageStride % 4 == 0 &&
@@ -1930,6 +1935,442 @@ int bhip_launch_integral_u8(bhip_ctx* ctx, const unsigned char* in, long long in
 		ProfScope prof(ctx, "k_integral_cols_s32", 8.0 * width * height * batch);
 		hipLaunchKernelGGL(k_integral_cols_s32, dim3((width + 255) / 256, batch), dim3(256), 0, ctx->stream, out, outImageStride, outStride, width, height);
 	}
+	BHIP_HIP(ctx, hipGetLastError());
+	return BHIP_OK;
+}
+
+// ---------------- integer gradient + corner path: GrayU8 -> GrayS16 gradients, S16 / weighted corner intensity ----------------
+// GradientSobel_Outer.process_sub(GrayU8, GrayS16, GrayS16)     I:alg/filter/derivative/impl/GradientSobel_Outer.java:76-
+//   border: ConvolveJustBorder_General_SB.convolve(kernelDerivX/Y_I32, ImageBorderValue(0))   I:alg/filter/derivative/GradientSobel.java:73-74,110-124
+// GradientThree_Standard.process(GrayU8, GrayS16, GrayS16)      I:alg/filter/derivative/impl/GradientThree_Standard.java:67-88
+//   border: DerivativeHelperFunctions.processBorderHorizontal/Vertical with kernelDeriv_I32
+// The arithmetic is integer, so the interior expression and every border form give the same value: the 3x3 (3-tap) formula on the image
+// padded with 0.  With border 1 every pixel is written, with border 0 only the interior (frame untouched).  Results fit in a short.
+struct GradU8Params {
+	const uint8_t* in;
+	int16_t* dx;
+	int16_t* dy;
+	long long inImageStride, outImageStride;   // elements between the images of a batch
+	int inStride, outStride, width, height;
+	int border;
+};
+struct GradRowU8 { int v[6]; };   // columns x-1 .. x+4 of one row (0 outside the image)
+__device__ __forceinline__ GradRowU8 gradU8LoadRow(const GradU8Params& P, const uint8_t* img, int x, int y, int lane) {
+	GradRowU8 r;
+	if (y < 0 || y >= P.height) {
+#pragma unroll
+		for (int i = 0; i < 6; i++) r.v[i] = 0;
+		return r;
+	}
+	const uint8_t* row = img + (long long)y * P.inStride;
+	int c[4];
+	if (x + 3 < P.width && (reinterpret_cast<uintptr_t>(row + x) & 3) == 0) {
+		const unsigned w = *reinterpret_cast<const unsigned*>(row + x);
+		c[0] = w & 255; c[1] = (w >> 8) & 255; c[2] = (w >> 16) & 255; c[3] = w >> 24;
+	} else {
+#pragma unroll
+		for (int j = 0; j < 4; j++) c[j] = x + j < P.width ? row[x + j] : 0;
+	}
+	int left = __shfl_up(c[3], 1, 64), right = __shfl_down(c[0], 1, 64);
+	if (lane == 0) left = (x - 1 >= 0 && x - 1 < P.width) ? row[x - 1] : 0;
+	if (lane == 63) right = (x + 4 < P.width) ? row[x + 4] : 0;
+	r.v[0] = left; r.v[1] = c[0]; r.v[2] = c[1]; r.v[3] = c[2]; r.v[4] = c[3]; r.v[5] = right;
+	return r;
+}
+// A wave walks GR_ROWS rows of a 256-column strip, lane l owns columns 4l .. 4l+3 and keeps three rows in registers (as k_grad_stream).
+// HBM: 1P read + 4P written.
+template <int KIND>
+__global__ __launch_bounds__(256) void k_grad_u8(GradU8Params P) {
+	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	const int x = blockIdx.x * 256 + 4 * lane;
+	const int y0 = (blockIdx.y * 4 + wave) * GR_ROWS;
+	if (y0 >= P.height) return;
+	const uint8_t* img = P.in + (long long)blockIdx.z * P.inImageStride;
+	int16_t* dxImg = P.dx + (long long)blockIdx.z * P.outImageStride;
+	int16_t* dyImg = P.dy + (long long)blockIdx.z * P.outImageStride;
+	GradRowU8 r0 = gradU8LoadRow(P, img, x, y0 - 1, lane), r1 = gradU8LoadRow(P, img, x, y0, lane), r2 = gradU8LoadRow(P, img, x, y0 + 1, lane);
+	const int yEnd = min(y0 + GR_ROWS, P.height);
+	for (int y = y0; y < yEnd; y++) {
+		GradRowU8 r3 = r2;
+		if (y + 1 < yEnd) r3 = gradU8LoadRow(P, img, x, y + 2, lane);
+		if (x < P.width) {
+			int16_t dx[4], dy[4];
+			bool wr[4];
+			const bool rowIn = y >= 1 && y < P.height - 1;
+#pragma unroll
+			for (int j = 0; j < 4; j++) {
+				const int a00 = r0.v[j], a01 = r0.v[j + 1], a02 = r0.v[j + 2];
+				const int a10 = r1.v[j], a12 = r1.v[j + 2];
+				const int a20 = r2.v[j], a21 = r2.v[j + 1], a22 = r2.v[j + 2];
+				if (KIND == 0) {
+					const int v = a22 - a00, w = a20 - a02;
+					dy[j] = (int16_t)((a21 - a01) * 2 + v + w);
+					dx[j] = (int16_t)((a12 - a10) * 2 + v - w);
+				} else {
+					dx[j] = (int16_t)(a12 - a10);
+					dy[j] = (int16_t)(a21 - a01);
+				}
+				wr[j] = P.border || (rowIn && x + j >= 1 && x + j < P.width - 1);
+			}
+			int16_t* ox = dxImg + (long long)y * P.outStride + x;
+			int16_t* oy = dyImg + (long long)y * P.outStride + x;
+			if (x + 3 < P.width && wr[0] && wr[1] && wr[2] && wr[3] && (reinterpret_cast<uintptr_t>(ox) & 7) == 0 &&
+				(reinterpret_cast<uintptr_t>(oy) & 7) == 0) {
+				short4 sx, sy;
+				sx.x = dx[0]; sx.y = dx[1]; sx.z = dx[2]; sx.w = dx[3];
+				sy.x = dy[0]; sy.y = dy[1]; sy.z = dy[2]; sy.w = dy[3];
+				*reinterpret_cast<short4*>(ox) = sx;
+				*reinterpret_cast<short4*>(oy) = sy;
+			} else {
+#pragma unroll
+				for (int j = 0; j < 4; j++)
+					if (x + j < P.width && wr[j]) { ox[j] = dx[j]; oy[j] = dy[j]; }
+			}
+		}
+		r0 = r1; r1 = r2; r2 = r3;
+	}
+}
+
+int bhip_launch_gradient_u8(bhip_ctx* ctx, int kind, const uint8_t* in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dx,
+							int16_t* dy, long long outImageStride, int outStride, int border) {
+	if (width <= 0 || height <= 0 || batch <= 0) return BHIP_OK;
+	GradU8Params P{in, dx, dy, inImageStride, outImageStride, inStride, outStride, width, height, border};
+	ProfScope prof(ctx, kind == 0 ? "k_sobel_u8" : "k_three_u8", 5.0 * width * height * batch);
+	dim3 grid((width + 255) / 256, (height + 4 * GR_ROWS - 1) / (4 * GR_ROWS), batch);
+	if (kind == 0) hipLaunchKernelGGL(k_grad_u8<0>, grid, dim3(256), 0, ctx->stream, P);
+	else hipLaunchKernelGGL(k_grad_u8<1>, grid, dim3(256), 0, ctx->stream, P);
+	BHIP_HIP(ctx, hipGetLastError());
+	return BHIP_OK;
+}
+
+// ---- corner scores on int32 window sums ----
+// ShiTomasiCorner_S32.compute   F:alg/feature/detect/intensity/impl/ShiTomasiCorner_S32.java:34-42 (int adds wrap, then double, Math.sqrt)
+// HarrisCorner_S32.compute      F:alg/feature/detect/intensity/impl/HarrisCorner_S32.java:45-51 (each int to float, then the F32 expression)
+// The sums arrive as uint32_t: Java's int arithmetic wraps, C++ signed overflow is undefined.
+__device__ __forceinline__ float cornerScoreS32(int kind, float kappa, uint32_t xx, uint32_t xy, uint32_t yy) {
+	if (kind == 0) {
+		const double left = (double)(int32_t)(xx + yy) * 0.5;
+		const double b = (double)(int32_t)(xx - yy) * 0.5;
+		const double sxy = (double)(int32_t)xy;
+		const double right = sqrt(b * b + sxy * sxy);   // correctly rounded f64 square root, as Math.sqrt
+		return (float)(left - right);
+	}
+	const float fxx = (float)(int32_t)xx, fyy = (float)(int32_t)yy, fxy = (float)(int32_t)xy;
+	const float trace = fxx + fyy;
+	return (fxx * fyy - fxy * fxy) - kappa * trace * trace;
+}
+
+// ---- unweighted S16 corner intensity, fused ----
+// GradientCornerIntensity.process = ImplSsdCornerBox.process   F:alg/feature/detect/intensity/impl/ImplSsdCornerBox.java:36-54
+//   horizontal() / vertical()                                  F:alg/feature/detect/intensity/impl/ImplSsdCorner_S16.java:63-198
+// Window sums of the int products are int32 with wrap-around, so they do not depend on the summation order: one pass stages dx,dy of a
+// (CB_TX + 2r) x (CB_TY + 2r) block in LDS (packed 16+16 bits), forms the horizontal window sums of the three products for the block's
+// columns, then each lane walks its column down CB_TY / 4 rows with a running vertical sum and writes the score.  Pixels within `radius` of the
+// image edge get 0 (ImplSsdCornerBox fills the border), so every intensity pixel is written exactly once and nothing else is.
+// HBM: 4P read (+ halo, mostly served by L2) + 4P written.
+#define CB_TX 64
+#define CB_TY 32
+struct CornerS16Params {
+	const int16_t* dx; const int16_t* dy;
+	long long dImageStride, iImageStride;
+	int dStride, width, height, radius;
+	float* intensity; int iStride;
+	int kind; float kappa;
+};
+static size_t cornerBoxLds(int r) { return (size_t)(CB_TX + 2 * r) * (CB_TY + 2 * r) * 4 + (size_t)3 * CB_TX * (CB_TY + 2 * r) * 4; }
+
+__global__ __launch_bounds__(256) void k_corner_box_s16(CornerS16Params P) {
+	extern __shared__ uint32_t cbLds[];
+	const int r = P.radius, RW = CB_TX + 2 * r, RH = CB_TY + 2 * r, W = P.width, H = P.height;
+	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	const int x0 = blockIdx.x * CB_TX, y0 = blockIdx.y * CB_TY;
+	uint32_t* d = cbLds;                       // [RH][RW]: dx in the low half, dy in the high half
+	uint32_t* hXX = d + RW * RH;               // [RH][CB_TX] horizontal window sums
+	uint32_t* hXY = hXX + CB_TX * RH;
+	uint32_t* hYY = hXY + CB_TX * RH;
+	const long long img = (long long)blockIdx.z * P.dImageStride;
+	for (int ry = wave; ry < RH; ry += 4) {
+		const int gy = y0 - r + ry;
+		const bool rowIn = gy >= 0 && gy < H;
+		for (int rx = lane; rx < RW; rx += 64) {
+			const int gx = x0 - r + rx;
+			uint32_t v = 0;
+			if (rowIn && gx >= 0 && gx < W) {
+				const long long o = img + (long long)gy * P.dStride + gx;
+				v = (uint32_t)(uint16_t)P.dx[o] | ((uint32_t)(uint16_t)P.dy[o] << 16);
+			}
+			d[ry * RW + rx] = v;
+		}
+	}
+	__syncthreads();
+	const int kw = 2 * r + 1;
+	for (int ry = wave; ry < RH; ry += 4) {
+		uint32_t sXX = 0, sXY = 0, sYY = 0;
+		const uint32_t* s = d + ry * RW + lane;
+		for (int k = 0; k < kw; k++) {
+			const uint32_t v = s[k];
+			const int32_t ix = (int16_t)(v & 0xffff), iy = (int16_t)(v >> 16);
+			sXX += (uint32_t)(ix * ix); sXY += (uint32_t)(ix * iy); sYY += (uint32_t)(iy * iy);   // |product| <= 2^30
+		}
+		hXX[ry * CB_TX + lane] = sXX; hXY[ry * CB_TX + lane] = sXY; hYY[ry * CB_TX + lane] = sYY;
+	}
+	__syncthreads();
+	const int gx = x0 + lane;
+	if (gx >= W) return;
+	const bool colIn = gx >= r && gx < W - r;
+	const int oy0 = wave * (CB_TY / 4);
+	uint32_t tXX = 0, tXY = 0, tYY = 0;
+	for (int k = 0; k < kw; k++) {
+		const int i = (oy0 + k) * CB_TX + lane;
+		tXX += hXX[i]; tXY += hXY[i]; tYY += hYY[i];
+	}
+	float* out = P.intensity + (long long)blockIdx.z * P.iImageStride + gx;
+	for (int oy = oy0; oy < oy0 + CB_TY / 4; oy++) {
+		const int gy = y0 + oy;
+		if (gy >= H) break;
+		if (oy > oy0) {
+			const int iOut = (oy - 1) * CB_TX + lane, iIn = (oy + 2 * r) * CB_TX + lane;
+			tXX += hXX[iIn] - hXX[iOut]; tXY += hXY[iIn] - hXY[iOut]; tYY += hYY[iIn] - hYY[iOut];
+		}
+		const bool in = colIn && gy >= r && gy < H - r;
+		out[(long long)gy * P.iStride] = in ? cornerScoreS32(P.kind, P.kappa, tXX, tXY, tYY) : 0.0f;
+	}
+}
+
+// Radii whose block does not fit the LDS: ImplSsdCorner_S16's two passes over int32 planes (dense width x height per image).  Running sums
+// with wrap-around equal the direct sums.  The caller clears the intensity border.
+__global__ __launch_bounds__(64) void k_corner_rows_s16(CornerS16Params P, uint32_t* hXX, uint32_t* hXY, uint32_t* hYY, long long hImageStride) {
+	const int row = blockIdx.x * blockDim.x + threadIdx.x;
+	if (row >= P.height) return;
+	const int W = P.width, r = P.radius, ww = 2 * r + 1;
+	const int16_t* X = P.dx + (long long)blockIdx.y * P.dImageStride + (long long)row * P.dStride;
+	const int16_t* Y = P.dy + (long long)blockIdx.y * P.dImageStride + (long long)row * P.dStride;
+	const long long ho = (long long)blockIdx.y * hImageStride + (long long)row * W;
+	uint32_t tXX = 0, tXY = 0, tYY = 0;
+	for (int i = 0; i < W; i++) {
+		int32_t dx = X[i], dy = Y[i];
+		tXX += (uint32_t)(dx * dx); tXY += (uint32_t)(dx * dy); tYY += (uint32_t)(dy * dy);
+		if (i >= ww) {
+			dx = X[i - ww]; dy = Y[i - ww];
+			tXX -= (uint32_t)(dx * dx); tXY -= (uint32_t)(dx * dy); tYY -= (uint32_t)(dy * dy);
+		}
+		if (i >= ww - 1) { hXX[ho + i - r] = tXX; hXY[ho + i - r] = tXY; hYY[ho + i - r] = tYY; }
+	}
+}
+__global__ __launch_bounds__(256) void k_corner_cols_s16(CornerS16Params P, const uint32_t* hXX, const uint32_t* hXY, const uint32_t* hYY, long long hImageStride) {
+	const int W = P.width, H = P.height, r = P.radius, kw = 2 * r + 1;
+	const int x = r + blockIdx.x * blockDim.x + threadIdx.x;
+	if (x >= W - r) return;
+	const long long h0 = (long long)blockIdx.y * hImageStride + x;
+	float* inten = P.intensity + (long long)blockIdx.y * P.iImageStride + x;
+	uint32_t tXX = 0, tXY = 0, tYY = 0;
+	for (int y = 0; y < H; y++) {
+		const long long s = h0 + (long long)y * W;
+		tXX += hXX[s]; tXY += hXY[s]; tYY += hYY[s];
+		if (y >= kw) {
+			const long long o = s - (long long)kw * W;
+			tXX -= hXX[o]; tXY -= hXY[o]; tYY -= hYY[o];
+		}
+		if (y >= kw - 1) inten[(long long)(y - r) * P.iStride] = cornerScoreS32(P.kind, P.kappa, tXX, tXY, tYY);
+	}
+}
+
+// scratch: 3 * width * height * 4 bytes per image, used only when the radius is beyond the fused block (bhip_corner_box_s16_scratch)
+size_t bhip_corner_box_s16_scratch(int radius, int width, int height, int batch) {
+	return cornerBoxLds(radius) <= 65536 ? 0 : (size_t)3 * width * height * 4 * batch;
+}
+int bhip_launch_corner_box_s16(bhip_ctx* ctx, int kind, int radius, float kappa, const int16_t* dx, const int16_t* dy, long long dImageStride, int dStride,
+							   int width, int height, int batch, float* intensity, long long iImageStride, int iStride, void* scratch) {
+	if (kind != 0 && kind != 1) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "corner score not supported");
+	if (radius < 0 || 2 * radius + 1 > width || 2 * radius + 1 > height) return bhip_fail(ctx, BHIP_ERR_INVALID, "window larger than the image");
+	if (batch <= 0) return BHIP_OK;
+	CornerS16Params P{dx, dy, dImageStride, iImageStride, dStride, width, height, radius, intensity, iStride, kind, kappa};
+	const size_t lds = cornerBoxLds(radius);
+	if (lds <= 65536) {
+		const int bx = (width + CB_TX - 1) / CB_TX, by = (height + CB_TY - 1) / CB_TY;
+		// bytes: every block reads its dx,dy halo block (4 B/px), every pixel is written once (4 B/px)
+		const double in = 4.0 * bx * by * (CB_TX + 2.0 * radius) * (CB_TY + 2.0 * radius);
+		ProfScope prof(ctx, "k_corner_box_s16", (in + 4.0 * width * height) * batch);
+		hipLaunchKernelGGL(k_corner_box_s16, dim3(bx, by, batch), dim3(256), lds, ctx->stream, P);
+		BHIP_HIP(ctx, hipGetLastError());
+		return BHIP_OK;
+	}
+	if (!scratch) return bhip_fail(ctx, BHIP_ERR_INVALID, "no scratch for the two-pass corner form");
+	const long long px = (long long)width * height;
+	uint32_t* h = static_cast<uint32_t*>(scratch);
+	for (int b = 0; b < batch; b++)
+		BHIP_HIP(ctx, hipMemset2DAsync(intensity + (long long)b * iImageStride, (size_t)iStride * 4, 0, (size_t)width * 4, (size_t)height, ctx->stream));
+	{
+		ProfScope prof(ctx, "k_corner_rows_s16", (4.0 + 12.0) * px * batch);
+		hipLaunchKernelGGL(k_corner_rows_s16, dim3((height + 63) / 64, batch), dim3(64), 0, ctx->stream, P, h, h + px, h + 2 * px, px * 3);
+	}
+	{
+		ProfScope prof(ctx, "k_corner_cols_s16", 16.0 * px * batch);
+		hipLaunchKernelGGL(k_corner_cols_s16, dim3((width - 2 * radius + 255) / 256, batch), dim3(256), 0, ctx->stream, P, h, h + px, h + 2 * px, px * 3);
+	}
+	BHIP_HIP(ctx, hipGetLastError());
+	return BHIP_OK;
+}
+
+// ---- Gaussian-weighted corner intensity, fused (F32 and S16 derivatives) ----
+// ImplSsdCornerWeighted_F32.process   F:alg/feature/detect/intensity/impl/ImplSsdCornerWeighted_F32.java:46-104
+// ImplSsdCornerWeighted_S16.process   F:alg/feature/detect/intensity/impl/ImplSsdCornerWeighted_S16.java:50-108
+//   products, then ConvolveImageNormalized.horizontal then vertical on each of XX, XY, YY, then the score on every pixel (getIgnoreBorder() 0)
+//   F32: ConvolveImageNormalized.java:48-93 -- the arithmetic of bhip_conv_norm_h/v (convOne, setNormalizedMode), per axis
+//   S32: ConvolveImageNormalized.java:768-800 -- interior (total + divisor/2) / divisor with divisor = kernel.computeSum()
+//        (noborder/ConvolveImageUnrolled_SB_S32_S32_Div), border and naive forms (total + weight/2) / weight with the clipped weight
+//        (normalized/ConvolveNormalized_JustBorder_SB.java:1147-1250, ConvolveNormalizedNaive_SB.java:504-560): one formula, the clipped
+//        weight equals the divisor inside.  int adds and multiplies wrap; / truncates toward zero.
+// One block: a CW_TX x CW_TY tile.  The products of the (tile + 2r)^2 block go to LDS, the horizontal pass writes CW_TX x (CW_TY + 2r) values
+// to LDS, the vertical pass and the score run from there.  Only the intensity is written.  HBM: 8P (F32) / 4P (S16) read + halo, 4P written.
+#define CW_TX 32
+#define CW_TY 16
+#define CW_MAX_RADIUS 15
+struct CornerWParams {
+	const void* dx; const void* dy;
+	long long dImageStride, iImageStride;
+	int dStride, width, height, radius;
+	float* intensity; int iStride;
+	int kind; float kappa;
+	int ks[2 * CW_MAX_RADIUS + 1];   // S32 kernel
+};
+template <class T>
+static size_t cornerWeightedLds(int r) {
+	return (size_t)3 * sizeof(T) * ((size_t)(CW_TX + 2 * r) * (CW_TY + 2 * r) + (size_t)CW_TX * (CW_TY + 2 * r)) + (size_t)2 * (2 * r + 1) * 4;
+}
+
+// one normalised S32 output from taps s[k*step], k in [0, kw), centred (offset r) on `pos` of an axis of `extent` pixels
+__device__ __forceinline__ int32_t convNormS32(const int32_t* s, int step, int pos, int extent, int kw, int r, const int32_t* kc) {
+	const int k0 = max(0, r - pos);
+	const int k1 = min(kw, extent - pos + r);
+	uint32_t total = 0;
+	int32_t weight = 0;
+	for (int k = k0; k < k1; k++) {
+		const int32_t w = kc[k];
+		weight += w;
+		total += (uint32_t)s[k * step] * (uint32_t)w;
+	}
+	return (int32_t)(total + (uint32_t)(weight / 2)) / weight;
+}
+
+template <bool S16>
+__global__ __launch_bounds__(256) void k_corner_weighted(CornerWParams Q, ConvParams Ph, ConvParams Pv) {
+	typedef typename std::conditional<S16, int32_t, float>::type T;
+	extern __shared__ uint32_t cwLds[];
+	const int r = Q.radius, kw = 2 * r + 1, RW = CW_TX + 2 * r, RH = CW_TY + 2 * r, W = Q.width, H = Q.height;
+	const int tx = threadIdx.x & (CW_TX - 1), ty = threadIdx.x / CW_TX;   // 32 x 8
+	const int x0 = blockIdx.x * CW_TX, y0 = blockIdx.y * CW_TY;
+	T* pXX = reinterpret_cast<T*>(cwLds);   // [RH][RW] products
+	T* pXY = pXX + RW * RH;
+	T* pYY = pXY + RW * RH;
+	T* hXX = pYY + RW * RH;                 // [RH][CW_TX] horizontal pass
+	T* hXY = hXX + CW_TX * RH;
+	T* hYY = hXY + CW_TX * RH;
+	float* kh = reinterpret_cast<float*>(hYY + CW_TX * RH);   // F32 horizontal / vertical kernels
+	float* kv = kh + kw;
+	int32_t* ks = reinterpret_cast<int32_t*>(kh);            // S32 kernel
+	if (threadIdx.x < kw) {
+		if constexpr (S16) ks[threadIdx.x] = Q.ks[threadIdx.x];
+		else { kh[threadIdx.x] = Ph.k[threadIdx.x]; kv[threadIdx.x] = Pv.k[threadIdx.x]; }
+	}
+	const long long img = (long long)blockIdx.z * Q.dImageStride;
+	for (int ry = ty; ry < RH; ry += 8) {
+		const int gy = y0 - r + ry;
+		const bool rowIn = gy >= 0 && gy < H;
+		for (int rx = tx; rx < RW; rx += CW_TX) {
+			const int gx = x0 - r + rx;
+			T xx = 0, xy = 0, yy = 0;
+			if (rowIn && gx >= 0 && gx < W) {
+				const long long o = img + (long long)gy * Q.dStride + gx;
+				if constexpr (S16) {
+					const int32_t a = static_cast<const int16_t*>(Q.dx)[o], b = static_cast<const int16_t*>(Q.dy)[o];
+					xx = a * a; xy = a * b; yy = b * b;   // |product| <= 2^30: no wrap
+				} else {
+					const float a = static_cast<const float*>(Q.dx)[o], b = static_cast<const float*>(Q.dy)[o];
+					xx = a * a; xy = a * b; yy = b * b;
+				}
+			}
+			const int i = ry * RW + rx;
+			pXX[i] = xx; pXY[i] = xy; pYY[i] = yy;
+		}
+	}
+	__syncthreads();
+	// horizontal pass: rows of the block inside the image, the tile's columns; tap 0 of column c is block column c (image column gx - r)
+	const int gx = x0 + tx;
+	for (int ry = ty; ry < RH; ry += 8) {
+		const int gy = y0 - r + ry;
+		if (gy < 0 || gy >= H || gx >= W) continue;
+		const int i = ry * RW + tx, o = ry * CW_TX + tx;
+		if constexpr (S16) {
+			hXX[o] = convNormS32(reinterpret_cast<const int32_t*>(pXX) + i, 1, gx, W, kw, r, ks);
+			hXY[o] = convNormS32(reinterpret_cast<const int32_t*>(pXY) + i, 1, gx, W, kw, r, ks);
+			hYY[o] = convNormS32(reinterpret_cast<const int32_t*>(pYY) + i, 1, gx, W, kw, r, ks);
+		} else {
+			float v;
+			convOne<0>(Ph, reinterpret_cast<const float*>(pXX) + i, 1, gx, W, v, kh); hXX[o] = v;
+			convOne<0>(Ph, reinterpret_cast<const float*>(pXY) + i, 1, gx, W, v, kh); hXY[o] = v;
+			convOne<0>(Ph, reinterpret_cast<const float*>(pYY) + i, 1, gx, W, v, kh); hYY[o] = v;
+		}
+	}
+	__syncthreads();
+	if (gx >= W) return;
+	float* out = Q.intensity + (long long)blockIdx.z * Q.iImageStride + gx;
+	for (int oy = ty; oy < CW_TY; oy += 8) {
+		const int gy = y0 + oy;
+		if (gy >= H) break;
+		const int i = oy * CW_TX + tx;   // tap 0 of row oy is block row oy (image row gy - r)
+		float score;
+		if constexpr (S16) {
+			const int32_t xx = convNormS32(reinterpret_cast<const int32_t*>(hXX) + i, CW_TX, gy, H, kw, r, ks);
+			const int32_t xy = convNormS32(reinterpret_cast<const int32_t*>(hXY) + i, CW_TX, gy, H, kw, r, ks);
+			const int32_t yy = convNormS32(reinterpret_cast<const int32_t*>(hYY) + i, CW_TX, gy, H, kw, r, ks);
+			score = cornerScoreS32(Q.kind, Q.kappa, (uint32_t)xx, (uint32_t)xy, (uint32_t)yy);
+		} else {
+			float xx, xy, yy;
+			convOne<0>(Pv, reinterpret_cast<const float*>(hXX) + i, CW_TX, gy, H, xx, kv);
+			convOne<0>(Pv, reinterpret_cast<const float*>(hXY) + i, CW_TX, gy, H, xy, kv);
+			convOne<0>(Pv, reinterpret_cast<const float*>(hYY) + i, CW_TX, gy, H, yy, kv);
+			score = cornerScore(Q.kind, Q.kappa, xx, xy, yy);
+		}
+		out[(long long)gy * Q.iStride] = score;
+	}
+}
+
+int bhip_corner_weighted_max_radius() { return CW_MAX_RADIUS; }
+
+// s16: derivatives are int16_t (ImplSsdCornerWeighted_S16), else float (ImplSsdCornerWeighted_F32).  radius must be 1 .. CW_MAX_RADIUS.
+int bhip_launch_corner_weighted(bhip_ctx* ctx, bool s16, int kind, int radius, float kappa, const void* dx, const void* dy, long long dImageStride, int dStride,
+								int width, int height, int batch, float* intensity, long long iImageStride, int iStride) {
+	if (kind != 0 && kind != 1) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "corner score not supported");
+	if (radius <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Radius must be > 0");
+	if (radius > CW_MAX_RADIUS) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "weighted corner radius above the supported limit");
+	if (width <= 0 || height <= 0 || batch <= 0) return BHIP_OK;
+	CornerWParams Q{};
+	Q.dx = dx; Q.dy = dy; Q.dImageStride = dImageStride; Q.iImageStride = iImageStride; Q.dStride = dStride; Q.width = width; Q.height = height;
+	Q.radius = radius; Q.intensity = intensity; Q.iStride = iStride; Q.kind = kind; Q.kappa = kappa;
+	const int kw = 2 * radius + 1;
+	ConvParams Ph{}, Pv{};
+	if (s16) {
+		std::vector<int32_t> k = bhip_gaussian1d_s32(radius);
+		for (int i = 0; i < kw; i++) Q.ks[i] = k[i];
+	} else {
+		// FactoryKernelGaussian.gaussian(Kernel1D_F32.class, -1, radius), each axis normalised as ConvolveImageNormalized does
+		std::vector<float> k = bhip_gaussian1d_f32(-1, radius);
+		for (ConvParams* P : {&Ph, &Pv}) {
+			P->kw = kw; P->koff = radius;
+			for (int i = 0; i < kw; i++) P->k[i] = k[i];
+			P->unrolled = kw <= 11 ? 1 : 0;   // ConvolveImageUnrolled widths 3..11 (first tap assigns)
+		}
+		setNormalizedMode(Ph, width);
+		setNormalizedMode(Pv, height);
+	}
+	const int bx = (width + CW_TX - 1) / CW_TX, by = (height + CW_TY - 1) / CW_TY;
+	const size_t lds = s16 ? cornerWeightedLds<int32_t>(radius) : cornerWeightedLds<float>(radius);
+	// bytes: every block reads its dx,dy halo block (8 B/px F32, 4 B/px S16), every pixel is written once
+	const double in = (s16 ? 4.0 : 8.0) * bx * by * (CW_TX + 2.0 * radius) * (CW_TY + 2.0 * radius);
+	ProfScope prof(ctx, s16 ? "k_corner_weighted_s16" : "k_corner_weighted_f32", (in + 4.0 * width * height) * batch);
+	if (s16) hipLaunchKernelGGL(k_corner_weighted<true>, dim3(bx, by, batch), dim3(256), lds, ctx->stream, Q, Ph, Pv);
+	else hipLaunchKernelGGL(k_corner_weighted<false>, dim3(bx, by, batch), dim3(256), lds, ctx->stream, Q, Ph, Pv);
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
 }

@@ -1,10 +1,11 @@
 // Host-side synthesis of the small Gaussian weight tables the orientation / SURF kernels read.
 // Restates I:factory/filter/kernel/FactoryKernelGaussian.java (gaussian :120-135, gaussian1D_F32 :218-238,
 // gaussian2D_F64 :297-306, sigmaForRadius :388, radiusForSigma :404, gaussianWidth :418-448) and
-// I:alg/filter/kernel/KernelMath.java (convolve2D :365-383, normalizeSumToOne :417-452).
+// I:alg/filter/kernel/KernelMath.java (convolve2D :365-383, normalizeSumToOne :417-452, convert :556-620).
 // UtilGaussian.computePDF is a ddogleg function (not in the reference tree): exp(-d^2/(2 s^2)) / (s sqrt(2 pi)).
 #include "common.h"
 #include <cmath>
+#include <limits>
 
 static double pdf(double sigma, double sample) {
 	return std::exp(-sample * sample / (2.0 * sigma * sigma)) / (sigma * std::sqrt(2.0 * M_PI));
@@ -65,4 +66,24 @@ std::vector<float> bhip_gaussian1d_f32(double sigma, int radius) {
 	for (float v : k) total += v;
 	for (float& v : k) v /= total;
 	return k;
+}
+
+// FactoryKernelGaussian.gaussian(Kernel1D_S32.class, -1, radius) = gaussian(1, false, 32, -1, radius) (FactoryKernelGaussian.java:120-160):
+// the un-normalised float PDF (gaussian1D_F32(sigma, radius, true, false), :218-238) through KernelMath.convert(k, MIN_FRAC = 1/100f)
+// (KernelMath.java:556-620): min = the smallest |v| >= max|v| * minFrac, out[i] = (int)(v[i] / min).  radius must be > 0.
+std::vector<int32_t> bhip_gaussian1d_s32(int radius) {
+	const double sigma = sigmaForRadius(radius);
+	std::vector<float> k;
+	for (int i = radius; i >= -radius; i--) k.push_back((float)pdf(sigma, i));
+	float max = 0;
+	for (float v : k) if (std::fabs(v) > max) max = std::fabs(v);
+	const float minValue = max * (1.0f / 100.0f);
+	float min = std::numeric_limits<float>::max();
+	for (float v : k) {
+		const float a = std::fabs(v);
+		if (a < min && a >= minValue) min = a;
+	}
+	std::vector<int32_t> out;
+	for (float v : k) out.push_back((int32_t)(v / min));
+	return out;
 }

@@ -6,7 +6,7 @@ Names follow the reference classes the host-buffer forms in boofcv_amd/api.py mi
 
   DeviceImageOps.convolve*      ConvolveImageNoBorder / ConvolveImageNormalized      I:alg/filter/convolve/*.java
   DeviceImageOps.gaussian       BlurImageOps.gaussian                               I:alg/filter/blur/BlurImageOps.java:406-425
-  DeviceImageOps.sobel / three  GradientSobel / GradientThree .process              I:alg/filter/derivative/GradientSobel.java:158-173
+  DeviceImageOps.sobel / three  GradientSobel / GradientThree .process              I:alg/filter/derivative/GradientSobel.java:110-124,158-173
   DeviceImageOps.intensity      GradientToEdgeFeatures.intensityE / intensityAbs    F:alg/feature/detect/edge/GradientToEdgeFeatures.java:61-95
   DeviceImageOps.nonmax         NonMaxBlock.process (strict)                        F:alg/feature/detect/extract/NonMaxBlock.java:69-94
   DeviceImageOps.pyramid        PyramidDiscreteSampleBlur.process                   I:alg/transform/pyramid/PyramidDiscreteSampleBlur.java:88-118
@@ -24,12 +24,12 @@ from .api import Context, IllegalArgumentException, _check
 INTENSITY_E, INTENSITY_ABS, INTENSITY_SQ = 0, 1, 2
 
 
-def _geom(t):
-    """(ptr, imageStride, rowStride, W, H, B) of a [B,H,W] float32 CUDA tensor with unit stride along x"""
+def _geom(t, dtype=torch.float32):
+    """(ptr, imageStride, rowStride, W, H, B) of a [B,H,W] CUDA tensor of `dtype` with unit stride along x (strides in elements)"""
     if t.dim() == 2:
         t = t.unsqueeze(0)
-    if t.dim() != 3 or t.dtype != torch.float32 or not t.is_cuda:
-        raise IllegalArgumentException("expected a [B,H,W] float32 CUDA tensor")
+    if t.dim() != 3 or t.dtype != dtype or not t.is_cuda:
+        raise IllegalArgumentException("expected a [B,H,W] %s CUDA tensor" % str(dtype).replace("torch.", ""))
     B, H, W = t.shape
     if W > 1 and t.stride(2) != 1:
         raise IllegalArgumentException("the last dimension must be contiguous")
@@ -77,28 +77,32 @@ class DeviceImageOps:
         return out
 
     def _grad(self, fn, src, border, dx, dy):
-        """border: None = frame untouched (as the reference with a null border), 0 = ImageBorderValue(0)"""
+        """border: None = frame untouched (as the reference with a null border), 0 = ImageBorderValue(0).  float32 -> float32, uint8 -> int16."""
+        fn_f32, fn_u8 = fn
+        u8 = src.dtype == torch.uint8
+        fn, dt = (fn_u8, torch.int16) if u8 else (fn_f32, torch.float32)
         if dx is None:
             # with a border policy every pixel is written; without one the frame keeps what the caller put there (zeros here, filled on
             # torch's stream: make sure that fill is ordered before the kernel when the ctx runs on another stream)
             if border is None:
-                dx, dy = torch.zeros(src.shape, dtype=torch.float32, device=src.device), torch.zeros(src.shape, dtype=torch.float32, device=src.device)
+                dx, dy = torch.zeros(src.shape, dtype=dt, device=src.device), torch.zeros(src.shape, dtype=dt, device=src.device)
                 torch.cuda.current_stream(src.device).synchronize()
             else:
-                dx, dy = self._like(src), self._like(src)
-        ip, iis, irs, W, H, B = _geom(src)
-        xp, ois, ors, _, _, _ = _geom(dx)
-        yp, ois2, ors2, _, _, _ = _geom(dy)
+                dx, dy = torch.empty(src.shape, dtype=dt, device=src.device), torch.empty(src.shape, dtype=dt, device=src.device)
+        ip, iis, irs, W, H, B = _geom(src, src.dtype if u8 else torch.float32)
+        xp, ois, ors, _, _, _ = _geom(dx, dt)
+        yp, ois2, ors2, _, _, _ = _geom(dy, dt)
         if (ois, ors) != (ois2, ors2):
             raise IllegalArgumentException("derivX and derivY must share their layout")
         _check(self.ctx, fn(self.ctx._h, ip, iis, irs, W, H, B, xp, yp, ois, ors, 0 if border is None else 1))
         return dx, dy
 
     def sobel(self, src, border=0, dx=None, dy=None):
-        return self._grad(self.L.bhip_sobel_dev_f32, src, border, dx, dy)
+        """float32 -> float32 (GradientSobel.process(GrayF32, ...)) or uint8 -> int16 (GradientSobel.process(GrayU8, GrayS16, GrayS16, ...))"""
+        return self._grad((self.L.bhip_sobel_dev_f32, self.L.bhip_sobel_dev_u8_s16), src, border, dx, dy)
 
     def three(self, src, border=0, dx=None, dy=None):
-        return self._grad(self.L.bhip_three_dev_f32, src, border, dx, dy)
+        return self._grad((self.L.bhip_three_dev_f32, self.L.bhip_three_dev_u8_s16), src, border, dx, dy)
 
     def intensity(self, kind, dx, dy, out=None):
         out = self._like(dx) if out is None else out
@@ -122,15 +126,25 @@ class DeviceImageOps:
                                                         C.c_void_p(xy.data_ptr()), cap, C.c_void_p(n.data_ptr())))
         return xy, n
 
-    def cornerIntensity(self, kind, radius, kappa, dx, dy, out=None):
-        """kind: 0 Shi-Tomasi, 1 Harris"""
-        out = self._like(dx) if out is None else out
-        xp, dis, drs, W, H, B = _geom(dx)
-        yp, dis2, drs2, _, _, _ = _geom(dy)
+    def cornerIntensity(self, kind, radius, kappa, dx, dy, out=None, weighted=False):
+        """kind: 0 Shi-Tomasi, 1 Harris.  float32 derivatives: ImplSsdCorner_F32 / ImplSsdCornerWeighted_F32; int16 derivatives:
+        ImplSsdCorner_S16 / ImplSsdCornerWeighted_S16.  The intensity is float32."""
+        s16 = dx.dtype == torch.int16
+        dt = torch.int16 if s16 else torch.float32
+        out = torch.empty(dx.shape, dtype=torch.float32, device=dx.device) if out is None else out
+        xp, dis, drs, W, H, B = _geom(dx, dt)
+        yp, dis2, drs2, _, _, _ = _geom(dy, dt)
         if (dis, drs) != (dis2, drs2):
             raise IllegalArgumentException("derivX and derivY must share their layout")
         op, ois, ors, _, _, _ = _geom(out)
-        _check(self.ctx, self.L.bhip_corner_intensity_dev_f32(self.ctx._h, int(kind), int(radius), float(kappa), xp, yp, dis, drs, W, H, B, op, ois, ors))
+        if s16:
+            st = self.L.bhip_corner_intensity_dev_s16(self.ctx._h, int(kind), int(radius), float(kappa), 1 if weighted else 0, xp, yp, dis, drs, W, H, B, op,
+                                                      ois, ors)
+        elif weighted:
+            st = self.L.bhip_corner_intensity_weighted_dev_f32(self.ctx._h, int(kind), int(radius), float(kappa), xp, yp, dis, drs, W, H, B, op, ois, ors)
+        else:
+            st = self.L.bhip_corner_intensity_dev_f32(self.ctx._h, int(kind), int(radius), float(kappa), xp, yp, dis, drs, W, H, B, op, ois, ors)
+        _check(self.ctx, st)
         return out
 
     def pyramidLayout(self, width, height, scales):

@@ -315,6 +315,33 @@ int bhip_pyramid_dev_f32(bhip_ctx* ctx, const float* kernel, int kernelWidth, co
  * (F:alg/feature/detect/interest/GeneralFeatureDetector.java:118-160). */
 int bhip_corner_intensity_f32(bhip_ctx* ctx, int kind, int radius, float kappa, const float* derivX, const float* derivY, int dStart, int dStride,
 							  int width, int height, float* intensity, int iStart, int iStride);
+/* GrayU8 -> GrayS16 gradients: GradientSobel.process(GrayU8, GrayS16, GrayS16, border) (I:alg/filter/derivative/GradientSobel.java:110-124 ->
+ * impl/GradientSobel_Outer.java:76- process_sub) and GradientThree.process(GrayU8, ...) (I:alg/filter/derivative/GradientThree.java:86-101 ->
+ * impl/GradientThree_Standard.java:67-88).  Integer arithmetic stored as (short).  border: 0 = null (frame untouched), 1 = ImageBorderValue(0)
+ * (ConvolveJustBorder_General_SB with kernelDerivX/Y_I32, DerivativeHelperFunctions.processBorderHorizontal/Vertical with kernelDeriv_I32).
+ * dx and dy share outStart / outStride. */
+int bhip_sobel_u8_s16(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, int16_t* dx, int16_t* dy, int outStart,
+					  int outStride, int border);
+int bhip_three_u8_s16(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, int16_t* dx, int16_t* dy, int outStart,
+					  int outStride, int border);
+/* FactoryIntensityPointAlg.shiTomasi(radius, weighted, GrayS16) / harris(radius, kappa, weighted, GrayS16)
+ * (F:factory/feature/detect/intensity/FactoryIntensityPointAlg.java:91-160) -> GradientCornerIntensity<GrayS16>.process.
+ * weighted 0: ImplSsdCorner_S16 (F:alg/feature/detect/intensity/impl/ImplSsdCorner_S16.java:63-198) with ShiTomasiCorner_S32 (kind 0) or
+ * HarrisCorner_S32 (kind 1): int32 box-window sums (wrapping as Java int), intensity 0 inside the border of `radius` pixels; 2r+1 <= width, height.
+ * weighted 1: ImplSsdCornerWeighted_S16 (F:alg/feature/detect/intensity/impl/ImplSsdCornerWeighted_S16.java:50-108): products, then
+ * ConvolveImageNormalized.horizontal / vertical (Kernel1D_S32) with FactoryKernelGaussian.gaussian(Kernel1D_S32, -1, radius), score on every
+ * pixel; radius 1 .. 15, BHIP_ERR_UNSUPPORTED above (output untouched).  derivX / derivY share startIndex and stride. */
+int bhip_corner_intensity_s16(bhip_ctx* ctx, int kind, int radius, float kappa, int weighted, const int16_t* derivX, const int16_t* derivY, int dStart,
+							  int dStride, int width, int height, float* intensity, int iStart, int iStride);
+/* FactoryIntensityPointAlg.shiTomasi(radius, true, GrayF32) / harris(radius, kappa, true, GrayF32) -> ImplSsdCornerWeighted_F32
+ * (F:alg/feature/detect/intensity/impl/ImplSsdCornerWeighted_F32.java:46-104): products, ConvolveImageNormalized.horizontal / vertical
+ * (I:alg/filter/convolve/ConvolveImageNormalized.java:48-93) with FactoryKernelGaussian.gaussian(Kernel1D_F32, -1, radius), score on every
+ * pixel.  radius 1 .. 15, BHIP_ERR_UNSUPPORTED above (output untouched). */
+int bhip_corner_intensity_weighted_f32(bhip_ctx* ctx, int kind, int radius, float kappa, const float* derivX, const float* derivY, int dStart, int dStride,
+									   int width, int height, float* intensity, int iStart, int iStride);
+/* FactoryKernelGaussian.gaussian(Kernel1D_S32.class, -1, radius) (I:factory/filter/kernel/FactoryKernelGaussian.java:120-160, KernelMath.convert
+ * :556-620): host-only, same contract as bhip_gaussian_kernel1d_f32; -1 for radius <= 0 (the reference throws). */
+int bhip_gaussian_kernel1d_s32(int radius, int32_t* out, int capacity);
 /* Integer image variants at stage level.
  * bhip_integral_u8_s32: IntegralImageOps.transform(GrayU8, GrayS32) (I:alg/transform/ii/impl/ImplIntegralImageOps.java:94-118).
  * bhip_hessian_s32: IntegralImageFeatureIntensity.hessian(GrayS32, skip, size, GrayF32) (F:alg/feature/detect/intensity/impl/
@@ -371,6 +398,16 @@ int bhip_nonmax_block_dev_f32(bhip_ctx* ctx, const float* dev_intensity, long lo
 /* GradientCornerIntensity.process (see bhip_corner_intensity_f32) on a batch; derivX / derivY share dImageStride / dStride */
 int bhip_corner_intensity_dev_f32(bhip_ctx* ctx, int kind, int radius, float kappa, const float* dev_dx, const float* dev_dy, long long dImageStride,
 								  int dStride, int width, int height, int batch, float* dev_intensity, long long iImageStride, int iStride);
+/* bhip_sobel_u8_s16 / bhip_three_u8_s16 on a batch (element strides: bytes in, shorts out); dx and dy share outImageStride / outStride */
+int bhip_sobel_dev_u8_s16(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dev_dx,
+						  int16_t* dev_dy, long long outImageStride, int outStride, int border);
+int bhip_three_dev_u8_s16(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dev_dx,
+						  int16_t* dev_dy, long long outImageStride, int outStride, int border);
+/* bhip_corner_intensity_s16 / bhip_corner_intensity_weighted_f32 on a batch; derivX / derivY share dImageStride / dStride */
+int bhip_corner_intensity_dev_s16(bhip_ctx* ctx, int kind, int radius, float kappa, int weighted, const int16_t* dev_dx, const int16_t* dev_dy,
+								  long long dImageStride, int dStride, int width, int height, int batch, float* dev_intensity, long long iImageStride, int iStride);
+int bhip_corner_intensity_weighted_dev_f32(bhip_ctx* ctx, int kind, int radius, float kappa, const float* dev_dx, const float* dev_dy, long long dImageStride,
+										   int dStride, int width, int height, int batch, float* dev_intensity, long long iImageStride, int iStride);
 /* DescribePointBrief.process (see bhip_brief_f32) for the points of a batch: image b owns points [start[b], start[b+1]) of dev_xy ((x,y) doubles;
  * `start` is a host array of batch+1 entries); point p's words go to dev_out[p * ceil(numPoints/32) ...] */
 int bhip_brief_dev_f32(bhip_ctx* ctx, const float* dev_img, long long imageStride, int stride, int width, int height, int batch, int radius, int numPoints,
