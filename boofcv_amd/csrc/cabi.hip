@@ -34,9 +34,13 @@ int bhip_launch_detect_fused(bhip_ctx* ctx, ImgView ii, int batch, int skip, int
 							 const int* midLevels, int radius, float threshold, unsigned int* bitmap, int bitmapWords, KeyPoint* cand, int* candCount,
 							 int cap, const FusedExport* exp, bool intTaps = false);
 
-// per-context scratch that the stateless entry points reuse (freed with the context)
+// Per-context scratch that the stateless entry points reuse (freed with the context).  The staging slots belong to the host-buffer export
+// that is running: the caller's views it uploads, the results it downloads, its own working buffers.  Code on device pointers (the
+// implementations behind the _dev exports, which host exports run on their staged copies) uses only the device-side slots, so nothing a
+// host export calls can overwrite what it staged.
 struct CtxScratch {
-	DevBuf a, b, c, d, e, work, nmsBitmap, nmsPrefix, nmsPos, ipTmp, ipKernel;
+	DevBuf in0, in1, out0, out1, tmp0, tmp1;                                 // staging
+	DevBuf work, assocCol, nmsBitmap, nmsPrefix, nmsPos, ipTmp, ipKernel;   // device side
 	AssocMfmaWork mfma;
 	int assocExactOnly = -1;  // BHIP_ASSOC_EXACT=1 forces the exact VALU association kernels (parity cross-check)
 };
@@ -163,6 +167,28 @@ int bhip_host_free(void* host_mem) {
 		if (!(ctx)) return BHIP_ERR_INVALID;             \
 		BHIP_HIP((ctx), hipSetDevice((ctx)->device));    \
 	} while (0)
+
+// `batch` images (a host view is one) of w x h elements, rows `stride` elements apart
+#define CHECK_IMG(ctx, p, stride, w, h, batch)                                                                                       \
+	do {                                                                                                                             \
+		if (!(p) || (w) <= 0 || (h) <= 0 || (batch) <= 0 || (stride) < (w)) return bhip_fail((ctx), BHIP_ERR_INVALID, "bad image"); \
+	} while (0)
+
+// Host view (rows `stride` elements apart from `start`) to / from a device image with rows `pitch` elements apart, enqueued on `st`.  Two
+// dense sides are one linear copy (the 2-D form is several times slower over PCIe even when the pitches match).  Neither synchronizes: an
+// export synchronizes once, before it returns.
+template <class T>
+static int upload(bhip_ctx* ctx, T* dev, int pitch, const T* in, int start, int stride, int w, int h, hipStream_t st) {
+	if (pitch == w && stride == w) BHIP_HIP(ctx, hipMemcpyAsync(dev, in + start, sizeof(T) * w * h, hipMemcpyHostToDevice, st));
+	else BHIP_HIP(ctx, hipMemcpy2DAsync(dev, sizeof(T) * pitch, in + start, sizeof(T) * stride, sizeof(T) * w, h, hipMemcpyHostToDevice, st));
+	return BHIP_OK;
+}
+template <class T>
+static int download(bhip_ctx* ctx, T* out, int start, int stride, const T* dev, int pitch, int w, int h, hipStream_t st) {
+	if (pitch == w && stride == w) BHIP_HIP(ctx, hipMemcpyAsync(out + start, dev, sizeof(T) * w * h, hipMemcpyDeviceToHost, st));
+	else BHIP_HIP(ctx, hipMemcpy2DAsync(out + start, sizeof(T) * stride, dev, sizeof(T) * pitch, sizeof(T) * w, h, hipMemcpyDeviceToHost, st));
+	return BHIP_OK;
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Fast-Hessian detector: octave schedule + buffers (FastHessianFeatureDetector.detect :156-188, detectOctave :198-221)
@@ -782,6 +808,63 @@ static bool briefPatchOk(const int32_t* samplePoints, int nSamples, int radius) 
 	return radius >= 0 && radius <= 40;
 }
 
+// bhip_surf_detect_f32 (T = float) and bhip_surf_detect_u8 (T = uint8_t: GrayS32 integral images, integer taps)
+template <class T>
+static int surfDetectHost(bhip_surf* s, const T* const* img, const int* startIndex, const int* stride, int width, int height, int batch) {
+	if (!s) return BHIP_ERR_INVALID;
+	bhip_ctx* ctx = s->ctx;
+	CHECK_CTX(ctx);
+	if (!img || width <= 0 || height <= 0 || batch <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image batch");
+	const bool u8 = sizeof(T) == 1;
+	const size_t imgBytes = (size_t)width * height * sizeof(T);
+	BHIP_TRY(s->inBuf.reserve(ctx, imgBytes * batch));
+	for (int i = 0; i < batch; i++)
+		if (!img[i] || (stride ? stride[i] : width) < width) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image (null or stride < width)");
+	auto put = [&](int i, void* dst, hipStream_t st) {
+		return upload(ctx, (T*)dst, width, img[i], startIndex ? startIndex[i] : 0, stride ? stride[i] : width, width, height, st);
+	};
+	bool done = false;
+	BHIP_TRY(surfRunChunked(s, width, height, batch, imgBytes, u8, put, &done));
+	if (done) return BHIP_OK;
+	for (int i = 0; i < batch; i++) BHIP_TRY(put(i, (char*)s->inBuf.p + imgBytes * i, ctx->stream));
+	ImgView in{s->inBuf.as<float>(), (long long)width * height, width, width, height};   // u8: only the pointer and the shape are used
+	return surfRun(s, in, batch, 0, u8);
+}
+
+// AssociateDescription over the descriptors still resident from the last detect of `s`: checks the problem table of
+// bhip_assoc_l2_surf / bhip_assoc_hamming_surf, has `match` write problem p (source image srcImage[p], destination dstImage[p]) into device
+// arrays prefilled with "no match", and downloads them.
+template <class Match>
+static int assocSurf(bhip_surf* s, int count, const int* srcImage, const int* dstImage, int* pairs, double* fit, Match match) {
+	bhip_ctx* ctx = s->ctx;
+	if (!s->haveResult) return bhip_fail(ctx, BHIP_ERR_INVALID, "no detect result");
+	if (count < 0 || (count > 0 && (!srcImage || !dstImage || !pairs || !fit))) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad problem table");
+	if (count == 0) return BHIP_OK;
+	const long long total = s->det.total;
+	std::vector<long long> so(count), doff(count);
+	std::vector<int> ns(count), nd(count);
+	std::vector<char> used(s->batch, 0);
+	for (int p = 0; p < count; p++) {
+		const int a = srcImage[p], b = dstImage[p];
+		if (a < 0 || a >= s->batch || b < 0 || b >= s->batch) return bhip_fail(ctx, BHIP_ERR_INVALID, "image index outside the last batch");
+		if (used[a]) return bhip_fail(ctx, BHIP_ERR_INVALID, "an image may be the source of one problem per call");
+		used[a] = 1;
+		so[p] = s->starts[a]; ns[p] = s->det.counts[a];
+		doff[p] = s->starts[b]; nd[p] = s->det.counts[b];
+	}
+	if (total == 0) return BHIP_OK;
+	CtxScratch* sc = scratchOf(ctx);
+	BHIP_TRY(sc->out0.reserve(ctx, (size_t)total * 4));
+	BHIP_TRY(sc->out1.reserve(ctx, (size_t)total * 8));
+	// rows of images that are the source of no problem in this call come back as "no match" (-1, 0), not as whatever an earlier call left
+	BHIP_HIP(ctx, hipMemsetAsync(sc->out0.p, 0xff, (size_t)total * 4, ctx->stream));
+	BHIP_HIP(ctx, hipMemsetAsync(sc->out1.p, 0, (size_t)total * 8, ctx->stream));
+	BHIP_TRY(match(so.data(), ns.data(), doff.data(), nd.data(), sc->out0.as<int>(), sc->out1.as<double>()));
+	BHIP_HIP(ctx, hipMemcpyAsync(pairs, sc->out0.p, (size_t)total * 4, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(fit, sc->out1.p, (size_t)total * 8, hipMemcpyDeviceToHost, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
+}
+
 extern "C" {
 
 int bhip_surf_create(bhip_ctx* ctx, const bhip_fh_cfg* fh, const bhip_surf_cfg* surf, const bhip_ori_cfg* ori, int stable, bhip_surf** out) {
@@ -822,28 +905,7 @@ int bhip_surf_detect_dev_f32(bhip_surf* s, const float* dev_images, long long im
 }
 
 int bhip_surf_detect_f32(bhip_surf* s, const float* const* img, const int* startIndex, const int* stride, int width, int height, int batch) {
-	if (!s) return BHIP_ERR_INVALID;
-	bhip_ctx* ctx = s->ctx;
-	CHECK_CTX(ctx);
-	if (!img || width <= 0 || height <= 0 || batch <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image batch");
-	const size_t imgBytes = (size_t)width * height * 4;
-	BHIP_TRY(s->inBuf.reserve(ctx, imgBytes * batch));
-	for (int i = 0; i < batch; i++)
-		if (!img[i] || (stride ? stride[i] : width) < width) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image (null or stride < width)");
-	auto upload = [&](int i, void* dst, hipStream_t st_) -> int {
-		const int st = stride ? stride[i] : width;
-		const float* src = img[i] + (startIndex ? startIndex[i] : 0);
-		// a dense frame is one linear copy (the 2-D form is several times slower over PCIe even when pitch == width)
-		if (st == width) BHIP_HIP(ctx, hipMemcpyAsync(dst, src, imgBytes, hipMemcpyHostToDevice, st_));
-		else BHIP_HIP(ctx, hipMemcpy2DAsync(dst, (size_t)width * 4, src, (size_t)st * 4, (size_t)width * 4, height, hipMemcpyHostToDevice, st_));
-		return BHIP_OK;
-	};
-	bool done = false;
-	BHIP_TRY(surfRunChunked(s, width, height, batch, imgBytes, false, upload, &done));
-	if (done) return BHIP_OK;
-	for (int i = 0; i < batch; i++) BHIP_TRY(upload(i, (char*)s->inBuf.p + imgBytes * i, ctx->stream));
-	ImgView in{s->inBuf.as<float>(), (long long)width * height, width, width, height};
-	return surfRun(s, in, batch);
+	return surfDetectHost(s, img, startIndex, stride, width, height, batch);
 }
 
 // FactoryDetectDescribe.surfColorStable / surfColorFast on one Planar<GrayF32> frame:
@@ -860,8 +922,7 @@ int bhip_surf_detect_planar_f32(bhip_surf* s, const float* const* bands, int num
 	BHIP_TRY(s->inBuf.reserve(ctx, px * 4 * (1 + numBands)));
 	for (int b = 0; b < numBands; b++) {
 		if (!bands[b]) return bhip_fail(ctx, BHIP_ERR_INVALID, "null band");
-		BHIP_HIP(ctx, hipMemcpy2DAsync((char*)s->inBuf.p + px * 4 * (1 + b), (size_t)width * 4, bands[b] + startIndex, (size_t)stride * 4, (size_t)width * 4, height,
-									   hipMemcpyHostToDevice, ctx->stream));
+		BHIP_TRY(upload(ctx, s->inBuf.as<float>() + px * (1 + b), width, bands[b], startIndex, stride, width, height, ctx->stream));
 	}
 	BHIP_TRY(bhip_launch_planar_average(ctx, s->inBuf.as<float>() + px, (long long)px, numBands, (long long)px, s->inBuf.as<float>()));
 	ImgView in{s->inBuf.as<float>(), (long long)px, width, width, height};
@@ -871,27 +932,7 @@ int bhip_surf_detect_planar_f32(bhip_surf* s, const float* const* bands, int num
 // FactoryDetectDescribe.surfStable / surfFast on GrayU8 frames (integral type GrayS32, GIntegralImageOps.getIntegralType): same results
 // interface as bhip_surf_detect_f32
 int bhip_surf_detect_u8(bhip_surf* s, const uint8_t* const* img, const int* startIndex, const int* stride, int width, int height, int batch) {
-	if (!s) return BHIP_ERR_INVALID;
-	bhip_ctx* ctx = s->ctx;
-	CHECK_CTX(ctx);
-	if (!img || width <= 0 || height <= 0 || batch <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image batch");
-	const size_t imgBytes = (size_t)width * height;
-	BHIP_TRY(s->inBuf.reserve(ctx, imgBytes * batch));
-	for (int i = 0; i < batch; i++)
-		if (!img[i] || (stride ? stride[i] : width) < width) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image (null or stride < width)");
-	auto upload = [&](int i, void* dst, hipStream_t st_) -> int {
-		const int st = stride ? stride[i] : width;
-		const uint8_t* src = img[i] + (startIndex ? startIndex[i] : 0);
-		if (st == width) BHIP_HIP(ctx, hipMemcpyAsync(dst, src, imgBytes, hipMemcpyHostToDevice, st_));
-		else BHIP_HIP(ctx, hipMemcpy2DAsync(dst, (size_t)width, src, (size_t)st, (size_t)width, height, hipMemcpyHostToDevice, st_));
-		return BHIP_OK;
-	};
-	bool done = false;
-	BHIP_TRY(surfRunChunked(s, width, height, batch, imgBytes, true, upload, &done));
-	if (done) return BHIP_OK;
-	for (int i = 0; i < batch; i++) BHIP_TRY(upload(i, (char*)s->inBuf.p + imgBytes * i, ctx->stream));
-	ImgView in{s->inBuf.as<float>(), (long long)width * height, width, width, height};   // only the pointer and the shape are used
-	return surfRun(s, in, batch, 0, true);
+	return surfDetectHost(s, img, startIndex, stride, width, height, batch);
 }
 
 int bhip_surf_count(bhip_surf* s, int image, int* n) {
@@ -1074,52 +1115,40 @@ int bhip_surf_describe_points(bhip_surf* s, int image, const double* xy_scale, i
 // ---------------------------------------------------------------------------------------------------------------
 // stage-level entry points (host buffers in / out)
 // ---------------------------------------------------------------------------------------------------------------
-// pitch = floats between rows of the device copy (0: dense).  pitch4(w) keeps rows 16-byte aligned so the tiled ip kernels apply.
+// pitch4(w): device rows 16-byte aligned so that the tiled ip kernels apply
 static inline int pitch4(int w) { return (w + 3) & ~3; }
-static int uploadImage(bhip_ctx* ctx, DevBuf& buf, const float* in, int start, int stride, int w, int h, int pitch = 0) {
-	if (pitch == 0) pitch = w;
-	BHIP_TRY(buf.reserve(ctx, (size_t)pitch * h * 4));
-	BHIP_HIP(ctx, hipMemcpy2DAsync(buf.p, (size_t)pitch * 4, in + start, (size_t)stride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
-	return BHIP_OK;
-}
-static int downloadImage(bhip_ctx* ctx, const void* dev, float* out, int start, int stride, int w, int h, int pitch = 0) {
-	if (pitch == 0) pitch = w;
-	BHIP_HIP(ctx, hipMemcpy2DAsync(out + start, (size_t)stride * 4, dev, (size_t)pitch * 4, (size_t)w * 4, h, hipMemcpyDeviceToHost, ctx->stream));
-	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return BHIP_OK;
-}
-#define CHECK_IMG(ctx, p, stride, w, h)                                                                                 \
-	do {                                                                                                                \
-		if (!(p) || (w) <= 0 || (h) <= 0 || (stride) < (w)) return bhip_fail((ctx), BHIP_ERR_INVALID, "bad image");     \
-	} while (0)
 
 int bhip_integral_f32(bhip_ctx* ctx, const float* in, int inStart, int inStride, int width, int height, float* out, int outStart, int outStride) {
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, in, inStride, width, height);
-	CHECK_IMG(ctx, out, outStride, width, height);
+	CHECK_IMG(ctx, in, inStride, width, height, 1);
+	CHECK_IMG(ctx, out, outStride, width, height, 1);
 	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(uploadImage(ctx, sc->a, in, inStart, inStride, width, height));
-	BHIP_TRY(sc->b.reserve(ctx, (size_t)width * height * 4));
-	ImgView iv{sc->a.as<float>(), (long long)width * height, width, width, height};
-	ImgViewW ov{sc->b.as<float>(), (long long)width * height, width, width, height};
+	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
+	BHIP_TRY(sc->out0.reserve(ctx, (size_t)width * height * 4));
+	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, in, inStart, inStride, width, height, ctx->stream));
+	ImgView iv{sc->in0.as<float>(), (long long)width * height, width, width, height};
+	ImgViewW ov{sc->out0.as<float>(), (long long)width * height, width, width, height};
 	BHIP_TRY(bhip_launch_integral(ctx, iv, ov, 1));
-	return downloadImage(ctx, sc->b.p, out, outStart, outStride, width, height);
+	BHIP_TRY(download(ctx, out, outStart, outStride, sc->out0.as<float>(), width, width, height, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
 }
 
 int bhip_hessian_f32(bhip_ctx* ctx, const float* ii, int iiStart, int iiStride, int width, int height, int skip, int size, float* intensity,
 					 int outStart, int outStride) {
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, ii, iiStride, width, height);
+	CHECK_IMG(ctx, ii, iiStride, width, height, 1);
 	if (skip < 1 || size < 3) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad skip/size");
 	const int w = width / skip, h = height / skip;
 	if (w <= 0 || h <= 0) return BHIP_OK;
-	CHECK_IMG(ctx, intensity, outStride, w, h);
+	CHECK_IMG(ctx, intensity, outStride, w, h, 1);
 	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(uploadImage(ctx, sc->a, ii, iiStart, iiStride, width, height));
-	BHIP_TRY(sc->b.reserve(ctx, (size_t)w * h * 4));
-	ImgView iv{sc->a.as<float>(), (long long)width * height, width, width, height};
-	BHIP_TRY(bhip_launch_hessian(ctx, iv, 1, skip, 1, &size, sc->b.as<float>(), (long long)w * h, (long long)w * h, w));
-	return downloadImage(ctx, sc->b.p, intensity, outStart, outStride, w, h);
+	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
+	BHIP_TRY(sc->out0.reserve(ctx, (size_t)w * h * 4));
+	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, ii, iiStart, iiStride, width, height, ctx->stream));
+	ImgView iv{sc->in0.as<float>(), (long long)width * height, width, width, height};
+	BHIP_TRY(bhip_launch_hessian(ctx, iv, 1, skip, 1, &size, sc->out0.as<float>(), (long long)w * h, (long long)w * h, w));
+	BHIP_TRY(download(ctx, intensity, outStart, outStride, sc->out0.as<float>(), w, w, h, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
 }
 
 // strict block NMS of `batch` dense device images: lists into dev_xy ([batch][cap] (x,y) int16 pairs, block-raster order), counts into
@@ -1151,7 +1180,7 @@ static int nonmaxDevice(bhip_ctx* ctx, const float* dev_intensity, long long ima
 int bhip_nonmax_block_dev_f32(bhip_ctx* ctx, const float* dev_intensity, long long imageStride, int stride, int width, int height, int batch, int radius,
 							  float threshold, int border, int16_t* dev_xy, int cap, int* dev_n) {
 	CHECK_CTX(ctx);
-	if (!dev_intensity || width <= 0 || height <= 0 || batch <= 0 || stride < width) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image batch");
+	CHECK_IMG(ctx, dev_intensity, stride, width, height, batch);
 	if (!dev_n || cap < 0 || (cap > 0 && !dev_xy)) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad output");
 	return nonmaxDevice(ctx, dev_intensity, imageStride, stride, width, height, batch, radius, threshold, border, dev_xy, cap, dev_n);
 }
@@ -1159,29 +1188,28 @@ int bhip_nonmax_block_dev_f32(bhip_ctx* ctx, const float* dev_intensity, long lo
 int bhip_nonmax_block_f32(bhip_ctx* ctx, const float* intensity, int start, int stride, int width, int height, int radius, float threshold,
 						  int border, int16_t* xy, int cap, int* n) {
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, intensity, stride, width, height);
+	CHECK_IMG(ctx, intensity, stride, width, height, 1);
 	if (!n || cap < 0 || (cap > 0 && !xy)) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad output");
 	*n = 0;
 	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(uploadImage(ctx, sc->a, intensity, start, stride, width, height));
-	BHIP_TRY(sc->d.reserve(ctx, 16));
-	BHIP_TRY(sc->e.reserve(ctx, (size_t)std::max(cap, 1) * 4));
-	BHIP_TRY(nonmaxDevice(ctx, sc->a.as<float>(), 0, width, width, height, 1, radius, threshold, border, sc->e.as<int16_t>(), cap, sc->d.as<int>()));
-	BHIP_HIP(ctx, hipMemcpyAsync(ctx->hostScratch.p, sc->d.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
+	BHIP_TRY(sc->out0.reserve(ctx, (size_t)std::max(cap, 1) * 4));
+	BHIP_TRY(sc->out1.reserve(ctx, 16));
+	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, intensity, start, stride, width, height, ctx->stream));
+	BHIP_TRY(nonmaxDevice(ctx, sc->in0.as<float>(), 0, width, width, height, 1, radius, threshold, border, sc->out0.as<int16_t>(), cap, sc->out1.as<int>()));
+	BHIP_HIP(ctx, hipMemcpyAsync(ctx->hostScratch.p, sc->out1.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the count decides how much of the list to copy
 	*n = ctx->hostScratch.as<int>()[0];
 	const int ncopy = std::min(*n, cap);
-	if (ncopy > 0) {
-		BHIP_HIP(ctx, hipMemcpyAsync(xy, sc->e.p, (size_t)ncopy * 4, hipMemcpyDeviceToHost, ctx->stream));
-		BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	}
-	return BHIP_OK;
+	if (ncopy == 0) return BHIP_OK;
+	BHIP_HIP(ctx, hipMemcpyAsync(xy, sc->out0.p, (size_t)ncopy * 4, hipMemcpyDeviceToHost, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
 }
 
 int bhip_select_nbest_f32(bhip_ctx* ctx, const float* intensity, int start, int stride, int width, int height, const int16_t* xy, int n, int target,
 						  int positive, int16_t* out_xy, int* out_n) {
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, intensity, stride, width, height);
+	CHECK_IMG(ctx, intensity, stride, width, height, 1);
 	if (n < 0 || !out_n || (n > 0 && (!xy || !out_xy))) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad corner list");
 	for (int i = 0; i < n; i++)
 		if (xy[2 * i] < 0 || xy[2 * i] >= width || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= height)
@@ -1195,15 +1223,16 @@ int bhip_select_nbest_f32(bhip_ctx* ctx, const float* intensity, int start, int 
 	*out_n = 0;
 	if (target <= 0) return BHIP_OK;   // n > target, nothing to keep (QuickSelect with k = 0 is never reached with a positive N in the reference)
 	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(uploadImage(ctx, sc->a, intensity, start, stride, width, height));
-	BHIP_TRY(sc->b.reserve(ctx, (size_t)n * 4));
-	BHIP_TRY(sc->c.reserve(ctx, (size_t)n * 4));
-	BHIP_TRY(sc->d.reserve(ctx, (size_t)n * 4));
-	BHIP_TRY(sc->e.reserve(ctx, (size_t)target * 4));
-	BHIP_HIP(ctx, hipMemcpyAsync(sc->b.p, xy, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-	BHIP_TRY(bhip_launch_select_nbest_xy(ctx, sc->a.as<float>(), width, sc->b.as<int16_t>(), n, target, positive != 0, sc->c.as<float>(), sc->d.as<int>(),
-										 sc->e.as<int16_t>()));
-	BHIP_HIP(ctx, hipMemcpyAsync(out_xy, sc->e.p, (size_t)target * 4, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
+	BHIP_TRY(sc->in1.reserve(ctx, (size_t)n * 4));
+	BHIP_TRY(sc->tmp0.reserve(ctx, (size_t)n * 4));
+	BHIP_TRY(sc->tmp1.reserve(ctx, (size_t)n * 4));
+	BHIP_TRY(sc->out0.reserve(ctx, (size_t)target * 4));
+	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, intensity, start, stride, width, height, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(sc->in1.p, xy, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+	BHIP_TRY(bhip_launch_select_nbest_xy(ctx, sc->in0.as<float>(), width, sc->in1.as<int16_t>(), n, target, positive != 0, sc->tmp0.as<float>(),
+										 sc->tmp1.as<int>(), sc->out0.as<int16_t>()));
+	BHIP_HIP(ctx, hipMemcpyAsync(out_xy, sc->out0.p, (size_t)target * 4, hipMemcpyDeviceToHost, ctx->stream));
 	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	*out_n = target;
 	return BHIP_OK;
@@ -1213,16 +1242,17 @@ int bhip_select_nbest_f32(bhip_ctx* ctx, const float* intensity, int start, int 
 static int fhDetect(bhip_ctx* ctx, const bhip_fh_cfg* cfg, const void* ii, bool intTaps, int iiStart, int iiStride, int width, int height,
 					double* xy_scale, int cap, int* n) {
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, ii, iiStride, width, height);
+	CHECK_IMG(ctx, ii, iiStride, width, height, 1);
 	if (!n || cap < 0 || (cap > 0 && !xy_scale)) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad output");
 	*n = 0;
 	FhDetector det;
 	det.intTaps = intTaps;
 	if (cfg) det.cfg = *cfg; else bhip_fh_cfg_default(&det.cfg);
 	CtxScratch* sc = scratchOf(ctx);
-	int status = uploadImage(ctx, sc->a, (const float*)ii, iiStart, iiStride, width, height);   // 32-bit words either way
+	int status = sc->in0.reserve(ctx, (size_t)width * height * 4);
+	if (status == BHIP_OK) status = upload(ctx, sc->in0.as<float>(), width, (const float*)ii, iiStart, iiStride, width, height, ctx->stream);   // 32-bit words either way
 	if (status == BHIP_OK) status = det.prepare(ctx, width, height, 1);
-	ImgView iv{sc->a.as<float>(), (long long)width * height, width, width, height};
+	ImgView iv{sc->in0.as<float>(), (long long)width * height, width, width, height};
 	if (status == BHIP_OK) status = det.run(ctx, iv);
 	if (status == BHIP_OK) {
 		*n = det.counts[0];
@@ -1284,7 +1314,7 @@ static int assocL2Exact(bhip_ctx* ctx, const double* dev_src, int ns, const doub
 						int sqrtScore, int* dev_pairs, double* dev_fit) {
 	CtxScratch* sc = scratchOf(ctx);
 	void* col = nullptr;
-	if (backwards && nd > 0) { BHIP_TRY(sc->d.reserve(ctx, (size_t)nd * bhip_assoc_coltop_size())); col = sc->d.p; }
+	if (backwards && nd > 0) { BHIP_TRY(sc->assocCol.reserve(ctx, (size_t)nd * bhip_assoc_coltop_size())); col = sc->assocCol.p; }
 	BHIP_TRY(bhip_assoc_phase1_l2(ctx, dev_src, ns, 0, dev_dst, nd, dof, maxErr, sqrtScore, dev_pairs, dev_fit, col, sc->work));
 	if (col) BHIP_TRY(bhip_assoc_phase2(ctx, col, 1, nd, ns, 0, dev_pairs, dev_fit));
 	return BHIP_OK;
@@ -1296,7 +1326,7 @@ int bhip_assoc_hamming_dev(bhip_ctx* ctx, const int32_t* dev_src, int ns, const 
 	if (ns == 0) return BHIP_OK;
 	CtxScratch* sc = scratchOf(ctx);
 	void* col = nullptr;
-	if (backwards && nd > 0) { BHIP_TRY(sc->d.reserve(ctx, (size_t)nd * bhip_assoc_coltop_size())); col = sc->d.p; }
+	if (backwards && nd > 0) { BHIP_TRY(sc->assocCol.reserve(ctx, (size_t)nd * bhip_assoc_coltop_size())); col = sc->assocCol.p; }
 	BHIP_TRY(bhip_assoc_phase1_ham(ctx, dev_src, ns, 0, dev_dst, nd, words, maxErr, dev_pairs, dev_fit, col, sc->work));
 	if (col) BHIP_TRY(bhip_assoc_phase2(ctx, col, 1, nd, ns, 0, dev_pairs, dev_fit));
 	return BHIP_OK;
@@ -1345,37 +1375,10 @@ int bhip_assoc_hamming_surf(bhip_surf* s, int count, const int* srcImage, const 
 	bhip_ctx* ctx = s->ctx;
 	CHECK_CTX(ctx);
 	if (!s->brief) return bhip_fail(ctx, BHIP_ERR_INVALID, "not a BRIEF detect+describe object");
-	if (!s->haveResult) return bhip_fail(ctx, BHIP_ERR_INVALID, "no detect result");
-	if (count < 0 || (count > 0 && (!srcImage || !dstImage || !pairs || !fit))) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad problem table");
-	if (count == 0) return BHIP_OK;
-	const long long total = s->det.total;
-	std::vector<char> used(s->batch, 0);
-	for (int p = 0; p < count; p++) {
-		const int a = srcImage[p], b = dstImage[p];
-		if (a < 0 || a >= s->batch || b < 0 || b >= s->batch) return bhip_fail(ctx, BHIP_ERR_INVALID, "image index outside the last batch");
-		if (used[a]) return bhip_fail(ctx, BHIP_ERR_INVALID, "an image may be the source of one problem per call");
-		used[a] = 1;
-	}
-	if (total == 0) return BHIP_OK;
-	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(sc->c.reserve(ctx, (size_t)total * 4));
-	BHIP_TRY(sc->e.reserve(ctx, (size_t)total * 8));
-	BHIP_HIP(ctx, hipMemsetAsync(sc->c.p, 0xff, (size_t)total * 4, ctx->stream));
-	BHIP_HIP(ctx, hipMemsetAsync(sc->e.p, 0, (size_t)total * 8, ctx->stream));
 	const int32_t* W = s->wordsBuf.as<int32_t>();
-	std::vector<long long> so(count), doff(count);
-	std::vector<int> ns(count), nd(count);
-	for (int p = 0; p < count; p++) {
-		const int a = srcImage[p], b = dstImage[p];
-		so[p] = s->starts[a]; ns[p] = s->det.counts[a];
-		doff[p] = s->starts[b]; nd[p] = s->det.counts[b];
-	}
-	BHIP_TRY(bhip_assoc_hamming_batched(ctx, W, W, s->briefWords, count, so.data(), ns.data(), doff.data(), nd.data(), maxErr, backwards, sc->c.as<int>(),
-										sc->e.as<double>(), sc->work));
-	BHIP_HIP(ctx, hipMemcpyAsync(pairs, sc->c.p, (size_t)total * 4, hipMemcpyDeviceToHost, ctx->stream));
-	BHIP_HIP(ctx, hipMemcpyAsync(fit, sc->e.p, (size_t)total * 8, hipMemcpyDeviceToHost, ctx->stream));
-	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return BHIP_OK;
+	return assocSurf(s, count, srcImage, dstImage, pairs, fit, [&](const long long* so, const int* ns, const long long* doff, const int* nd, int* dp, double* df) {
+		return bhip_assoc_hamming_batched(ctx, W, W, s->briefWords, count, so, ns, doff, nd, maxErr, backwards, dp, df, scratchOf(ctx)->work);
+	});
 }
 
 int bhip_assoc_l2_surf(bhip_surf* s, int count, const int* srcImage, const int* dstImage, double maxErr, int backwards, int* pairs, double* fit) {
@@ -1383,34 +1386,10 @@ int bhip_assoc_l2_surf(bhip_surf* s, int count, const int* srcImage, const int* 
 	bhip_ctx* ctx = s->ctx;
 	CHECK_CTX(ctx);
 	if (s->brief) return bhip_fail(ctx, BHIP_ERR_INVALID, "this object describes with BRIEF: use bhip_assoc_hamming_surf");
-	if (!s->haveResult) return bhip_fail(ctx, BHIP_ERR_INVALID, "no detect result");
-	if (count < 0 || (count > 0 && (!srcImage || !dstImage || !pairs || !fit))) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad problem table");
-	if (count == 0) return BHIP_OK;
-	const long long total = s->det.total;
-	std::vector<long long> so(count), doff(count);
-	std::vector<int> ns(count), nd(count);
-	std::vector<char> used(s->batch, 0);
-	for (int p = 0; p < count; p++) {
-		const int a = srcImage[p], b = dstImage[p];
-		if (a < 0 || a >= s->batch || b < 0 || b >= s->batch) return bhip_fail(ctx, BHIP_ERR_INVALID, "image index outside the last batch");
-		if (used[a]) return bhip_fail(ctx, BHIP_ERR_INVALID, "an image may be the source of one problem per call");
-		used[a] = 1;
-		so[p] = s->starts[a]; ns[p] = s->det.counts[a];
-		doff[p] = s->starts[b]; nd[p] = s->det.counts[b];
-	}
-	if (total == 0) return BHIP_OK;
-	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(sc->c.reserve(ctx, (size_t)total * 4));
-	BHIP_TRY(sc->e.reserve(ctx, (size_t)total * 8));
-	// rows of images that are the source of no problem in this call come back as "no match" (-1, 0), not as whatever an earlier call left
-	BHIP_HIP(ctx, hipMemsetAsync(sc->c.p, 0xff, (size_t)total * 4, ctx->stream));
-	BHIP_HIP(ctx, hipMemsetAsync(sc->e.p, 0, (size_t)total * 8, ctx->stream));
-	BHIP_TRY(bhip_assoc_l2_dev_batched(ctx, s->descBuf.as<double>(), s->descBuf.as<double>(), s->dofOut(), count, so.data(), ns.data(), doff.data(), nd.data(),
-									   maxErr, backwards, sc->c.as<int>(), sc->e.as<double>()));
-	BHIP_HIP(ctx, hipMemcpyAsync(pairs, sc->c.p, (size_t)total * 4, hipMemcpyDeviceToHost, ctx->stream));
-	BHIP_HIP(ctx, hipMemcpyAsync(fit, sc->e.p, (size_t)total * 8, hipMemcpyDeviceToHost, ctx->stream));
-	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return BHIP_OK;
+	const double* D = s->descBuf.as<double>();
+	return assocSurf(s, count, srcImage, dstImage, pairs, fit, [&](const long long* so, const int* ns, const long long* doff, const int* nd, int* dp, double* df) {
+		return bhip_assoc_l2_dev_batched(ctx, D, D, s->dofOut(), count, so, ns, doff, nd, maxErr, backwards, dp, df);
+	});
 }
 
 }  // extern "C"
@@ -1422,16 +1401,16 @@ static int assocHost(bhip_ctx* ctx, bool hamming, const E* src, int ns, const E*
 	if (ns == 0) return BHIP_OK;
 	if (!src || (nd > 0 && !dst) || !pairs || !fit) return bhip_fail(ctx, BHIP_ERR_INVALID, "null buffer");
 	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(sc->a.reserve(ctx, (size_t)ns * len * sizeof(E)));
-	BHIP_TRY(sc->b.reserve(ctx, (size_t)std::max(nd, 1) * len * sizeof(E)));
-	BHIP_TRY(sc->c.reserve(ctx, (size_t)ns * 4));
-	BHIP_TRY(sc->e.reserve(ctx, (size_t)ns * 8));
-	BHIP_HIP(ctx, hipMemcpyAsync(sc->a.p, src, (size_t)ns * len * sizeof(E), hipMemcpyHostToDevice, ctx->stream));
-	if (nd > 0) BHIP_HIP(ctx, hipMemcpyAsync(sc->b.p, dst, (size_t)nd * len * sizeof(E), hipMemcpyHostToDevice, ctx->stream));
-	if (hamming) BHIP_TRY(bhip_assoc_hamming_dev(ctx, (const int32_t*)sc->a.p, ns, (const int32_t*)sc->b.p, nd, len, maxErr, backwards, sc->c.as<int>(), sc->e.as<double>()));
-	else BHIP_TRY(bhip_assoc_l2_dev(ctx, (const double*)sc->a.p, ns, (const double*)sc->b.p, nd, len, maxErr, backwards, sqrtScore, sc->c.as<int>(), sc->e.as<double>()));
-	BHIP_HIP(ctx, hipMemcpyAsync(pairs, sc->c.p, (size_t)ns * 4, hipMemcpyDeviceToHost, ctx->stream));
-	BHIP_HIP(ctx, hipMemcpyAsync(fit, sc->e.p, (size_t)ns * 8, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_TRY(sc->in0.reserve(ctx, (size_t)ns * len * sizeof(E)));
+	BHIP_TRY(sc->in1.reserve(ctx, (size_t)std::max(nd, 1) * len * sizeof(E)));
+	BHIP_TRY(sc->out0.reserve(ctx, (size_t)ns * 4));
+	BHIP_TRY(sc->out1.reserve(ctx, (size_t)ns * 8));
+	BHIP_HIP(ctx, hipMemcpyAsync(sc->in0.p, src, (size_t)ns * len * sizeof(E), hipMemcpyHostToDevice, ctx->stream));
+	if (nd > 0) BHIP_HIP(ctx, hipMemcpyAsync(sc->in1.p, dst, (size_t)nd * len * sizeof(E), hipMemcpyHostToDevice, ctx->stream));
+	if (hamming) BHIP_TRY(bhip_assoc_hamming_dev(ctx, sc->in0.as<int32_t>(), ns, sc->in1.as<int32_t>(), nd, len, maxErr, backwards, sc->out0.as<int>(), sc->out1.as<double>()));
+	else BHIP_TRY(bhip_assoc_l2_dev(ctx, sc->in0.as<double>(), ns, sc->in1.as<double>(), nd, len, maxErr, backwards, sqrtScore, sc->out0.as<int>(), sc->out1.as<double>()));
+	BHIP_HIP(ctx, hipMemcpyAsync(pairs, sc->out0.p, (size_t)ns * 4, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(fit, sc->out1.p, (size_t)ns * 8, hipMemcpyDeviceToHost, ctx->stream));
 	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return BHIP_OK;
 }
@@ -1468,85 +1447,247 @@ int bhip_assoc_shard_phase2(bhip_ctx* ctx, const void* dev_colTopAll, int nranks
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// boofcv-ip front end
+// boofcv-ip front end.  Most operations have a host-buffer export (the caller's image view) and a device-batched _dev export (BASELINE
+// config 5: pyramid -> gradient -> NMS -> SURF on a 4K stream without leaving HBM).  Both run one implementation (xxxImpl) on device
+// images: `batch` of them imageStride elements apart, rows `stride` elements apart, asynchronous on the ctx stream.  The _dev export calls
+// it after its argument checks.  The host export checks, stages the view (rows pitch4(width) apart where the tiled kernels apply, dense
+// otherwise), calls it with batch 1, downloads and synchronizes; when the implementation fails, nothing is downloaded.
 // ---------------------------------------------------------------------------------------------------------------
+}  // extern "C"
+
+static int convImpl(bhip_ctx* ctx, bool vertical, bool normalized, const float* kernel, int kw, int koff, const float* in, long long inImageStride,
+					int inStride, int width, int height, int batch, float* out, long long outImageStride, int outStride) {
+	return bhip_launch_conv(ctx, vertical, normalized, kernel, kw, koff, in, inStride, width, height, out, outStride, batch, inImageStride, outImageStride);
+}
+
+// BlurImageOps.gaussian: one fused pass, or a horizontal pass into the library's `storage` and a vertical pass into `out`
+static int gaussianImpl(bhip_ctx* ctx, double sigma, int radius, const float* in, long long inImageStride, int inStride, int width, int height, int batch,
+						float* out, long long outImageStride, int outStride) {
+	std::vector<float> k = bhip_gaussian1d_f32(sigma, radius);
+	const int kw = (int)k.size(), koff = kw / 2;
+	bool fused = false;
+	BHIP_TRY(bhip_launch_blur_fused(ctx, k.data(), kw, in, inStride, width, height, out, outStride, batch, inImageStride, outImageStride, &fused));
+	if (fused) return BHIP_OK;
+	const int pitch = pitch4(width);
+	const long long tmpImage = (long long)pitch * height;
+	DevBuf& tmp = scratchOf(ctx)->ipTmp;
+	BHIP_TRY(tmp.reserve(ctx, (size_t)tmpImage * 4 * batch));
+	BHIP_TRY(bhip_launch_conv(ctx, false, true, k.data(), kw, koff, in, inStride, width, height, tmp.as<float>(), pitch, batch, inImageStride, tmpImage));
+	return bhip_launch_conv(ctx, true, true, k.data(), kw, koff, tmp.as<float>(), pitch, width, height, out, outStride, batch, tmpImage, outImageStride);
+}
+
+// GradientSobel / GradientThree (kind 0 / 1): GrayF32 -> GrayF32, GrayU8 -> GrayS16
+static int gradImpl(bhip_ctx* ctx, int kind, const float* in, long long inImageStride, int inStride, int width, int height, int batch, float* dx, float* dy,
+					long long outImageStride, int outStride, int border) {
+	return bhip_launch_gradient(ctx, kind, in, inStride, width, height, dx, dy, outStride, border, batch, inImageStride, outImageStride);
+}
+static int gradImpl(bhip_ctx* ctx, int kind, const uint8_t* in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dx,
+					int16_t* dy, long long outImageStride, int outStride, int border) {
+	return bhip_launch_gradient_u8(ctx, kind, in, inImageStride, inStride, width, height, batch, dx, dy, outImageStride, outStride, border);
+}
+
+// GradientCornerIntensity.process (FactoryIntensityPointAlg.shiTomasi / harris) on GrayF32 or GrayS16 (s16) derivatives: box window
+// (ImplSsdCornerBox, ImplSsdCorner_S16) or Gaussian-weighted window (ImplSsdCornerWeighted_F32 / _S16)
+static int cornerImpl(bhip_ctx* ctx, bool s16, bool weighted, int kind, int radius, float kappa, const void* dx, const void* dy, long long dImageStride,
+					  int dStride, int width, int height, int batch, float* intensity, long long iImageStride, int iStride) {
+	if (weighted)
+		return bhip_launch_corner_weighted(ctx, s16, kind, radius, kappa, dx, dy, dImageStride, dStride, width, height, batch, intensity, iImageStride, iStride);
+	DevBuf& tmp = scratchOf(ctx)->ipTmp;
+	if (s16) {
+		if (radius >= 0 && 2 * radius + 1 <= width && 2 * radius + 1 <= height) {
+			const size_t bytes = bhip_corner_box_s16_scratch(radius, width, height, batch);
+			if (bytes) BHIP_TRY(tmp.reserve(ctx, bytes));
+		}
+		return bhip_launch_corner_box_s16(ctx, kind, radius, kappa, (const int16_t*)dx, (const int16_t*)dy, dImageStride, dStride, width, height, batch,
+										  intensity, iImageStride, iStride, tmp.p);
+	}
+	const size_t px = (size_t)width * height;
+	BHIP_TRY(tmp.reserve(ctx, px * 4 * 3 * batch));
+	// ImageMiscOps.fillBorder(intensity, 0, radius): clear every image, the interior is overwritten
+	for (int b = 0; b < batch; b++)
+		BHIP_HIP(ctx, hipMemset2DAsync(intensity + b * iImageStride, (size_t)iStride * 4, 0, (size_t)width * 4, (size_t)height, ctx->stream));
+	float* h = tmp.as<float>();
+	return bhip_launch_corner_intensity(ctx, kind, radius, kappa, (const float*)dx, (const float*)dy, dStride, width, height, h, h + px, h + 2 * px, intensity,
+										iStride, batch, dImageStride, (long long)px * 3, iImageStride);
+}
+
+// DescribePointBrief.process: the points of image b are xy[start[b] .. start[b+1]) (host prefix, batch+1 entries, at most maxCount per
+// image), or with start == nullptr the n points of one image; words of point p at out[p * ceil(numPoints/32)].  The first nSample sample
+// points are uploaded and decide between the LDS-patch and the gather kernel.
+static int briefImpl(bhip_ctx* ctx, bool u8, const void* img, long long imageStride, int stride, int width, int height, int batch, int radius, int numPoints,
+					 const int32_t* samplePoints, int nSample, const int32_t* compare, const double* xy, const int* start, int n, int maxCount, int32_t* out) {
+	const size_t nS = (size_t)nSample * 2, nC = (size_t)numPoints * 2;
+	DevBuf& tab = scratchOf(ctx)->ipKernel;
+	BHIP_TRY(tab.reserve(ctx, (nS + nC + (start ? batch + 1 : 0)) * 4));
+	int* dSample = tab.as<int>();
+	int* dCompare = dSample + nS;
+	int* dStart = start ? dCompare + nC : nullptr;
+	BHIP_HIP(ctx, hipMemcpyAsync(dSample, samplePoints, nS * 4, hipMemcpyHostToDevice, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(dCompare, compare, nC * 4, hipMemcpyHostToDevice, ctx->stream));
+	if (start) BHIP_HIP(ctx, hipMemcpyAsync(dStart, start, (size_t)(batch + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+	return bhip_launch_brief(ctx, (const float*)img, stride, width, height, radius, numPoints, dSample, dCompare, xy, n, out, u8, batch, imageStride, dStart,
+							 maxCount, 2, 0, briefPatchOk(samplePoints, nSample, radius));
+}
+
+// host forms: GrayF32 gradients re-pitch rows to pitch4 (the streaming kernels), GrayU8 ones stay dense; without a border policy the frame
+// keeps the caller's values, so dx and dy are staged too
+template <class TI, class TO>
+static int gradHost(bhip_ctx* ctx, int kind, const TI* in, int inStart, int inStride, int width, int height, TO* dx, TO* dy, int outStart, int outStride,
+					int border) {
+	CHECK_CTX(ctx);
+	CHECK_IMG(ctx, in, inStride, width, height, 1);
+	CHECK_IMG(ctx, dx, outStride, width, height, 1);
+	CHECK_IMG(ctx, dy, outStride, width, height, 1);
+	if (border != 0 && border != 1) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "border policy not supported on the GPU");
+	CtxScratch* sc = scratchOf(ctx);
+	const int pitch = sizeof(TI) == 4 ? pitch4(width) : width;
+	const long long img = (long long)pitch * height;
+	BHIP_TRY(sc->in0.reserve(ctx, img * sizeof(TI)));
+	BHIP_TRY(sc->out0.reserve(ctx, img * sizeof(TO)));
+	BHIP_TRY(sc->out1.reserve(ctx, img * sizeof(TO)));
+	TI* din = sc->in0.as<TI>();
+	TO *ddx = sc->out0.as<TO>(), *ddy = sc->out1.as<TO>();
+	BHIP_TRY(upload(ctx, din, pitch, in, inStart, inStride, width, height, ctx->stream));
+	BHIP_TRY(upload(ctx, ddx, pitch, dx, outStart, outStride, width, height, ctx->stream));
+	BHIP_TRY(upload(ctx, ddy, pitch, dy, outStart, outStride, width, height, ctx->stream));
+	BHIP_TRY(gradImpl(ctx, kind, din, img, pitch, width, height, 1, ddx, ddy, img, pitch, border));
+	BHIP_TRY(download(ctx, dx, outStart, outStride, ddx, pitch, width, height, ctx->stream));
+	BHIP_TRY(download(ctx, dy, outStart, outStride, ddy, pitch, width, height, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
+}
+template <class TI, class TO>
+static int gradDev(bhip_ctx* ctx, int kind, const TI* dev_in, long long inImageStride, int inStride, int width, int height, int batch, TO* dev_dx, TO* dev_dy,
+				   long long outImageStride, int outStride, int border) {
+	CHECK_CTX(ctx);
+	CHECK_IMG(ctx, dev_in, inStride, width, height, batch);
+	CHECK_IMG(ctx, dev_dx, outStride, width, height, batch);
+	CHECK_IMG(ctx, dev_dy, outStride, width, height, batch);
+	if (border != 0 && border != 1) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "border policy not supported on the GPU");
+	return gradImpl(ctx, kind, dev_in, inImageStride, inStride, width, height, batch, dev_dx, dev_dy, outImageStride, outStride, border);
+}
+
+// host forms of the corner intensity: dense derivatives (T = float or int16_t)
+template <class T>
+static int cornerHost(bhip_ctx* ctx, bool weighted, int kind, int radius, float kappa, const T* dx, const T* dy, int dStart, int dStride, int width, int height,
+					  float* intensity, int iStart, int iStride) {
+	CHECK_CTX(ctx);
+	CHECK_IMG(ctx, dx, dStride, width, height, 1);
+	CHECK_IMG(ctx, dy, dStride, width, height, 1);
+	CHECK_IMG(ctx, intensity, iStride, width, height, 1);
+	CtxScratch* sc = scratchOf(ctx);
+	const long long px = (long long)width * height;
+	BHIP_TRY(sc->in0.reserve(ctx, px * sizeof(T)));
+	BHIP_TRY(sc->in1.reserve(ctx, px * sizeof(T)));
+	BHIP_TRY(sc->out0.reserve(ctx, px * 4));
+	BHIP_TRY(upload(ctx, sc->in0.as<T>(), width, dx, dStart, dStride, width, height, ctx->stream));
+	BHIP_TRY(upload(ctx, sc->in1.as<T>(), width, dy, dStart, dStride, width, height, ctx->stream));
+	BHIP_TRY(cornerImpl(ctx, sizeof(T) == 2, weighted, kind, radius, kappa, sc->in0.p, sc->in1.p, px, width, width, height, 1, sc->out0.as<float>(), px, width));
+	BHIP_TRY(download(ctx, intensity, iStart, iStride, sc->out0.as<float>(), width, width, height, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
+}
+static int cornerDev(bhip_ctx* ctx, bool s16, bool weighted, int kind, int radius, float kappa, const void* dev_dx, const void* dev_dy, long long dImageStride,
+					 int dStride, int width, int height, int batch, float* dev_intensity, long long iImageStride, int iStride) {
+	CHECK_CTX(ctx);
+	CHECK_IMG(ctx, dev_dx, dStride, width, height, batch);
+	CHECK_IMG(ctx, dev_dy, dStride, width, height, batch);
+	CHECK_IMG(ctx, dev_intensity, iStride, width, height, batch);
+	return cornerImpl(ctx, s16, weighted, kind, radius, kappa, dev_dx, dev_dy, dImageStride, dStride, width, height, batch, dev_intensity, iImageStride, iStride);
+}
+
+// bhip_brief_f32 / bhip_brief_u8 after their checks: the view staged dense, the n points as given
+template <class T>
+static int briefHost(bhip_ctx* ctx, const T* img, int start, int stride, int width, int height, int radius, int numPoints, const int32_t* samplePoints,
+					 int nSample, const int32_t* compare, const double* xy, int n, int32_t* out) {
+	CtxScratch* sc = scratchOf(ctx);
+	const size_t words = (numPoints + 31) / 32;
+	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * sizeof(T)));
+	BHIP_TRY(sc->in1.reserve(ctx, (size_t)n * 16));
+	BHIP_TRY(sc->out0.reserve(ctx, (size_t)n * words * 4));
+	BHIP_TRY(upload(ctx, sc->in0.as<T>(), width, img, start, stride, width, height, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(sc->in1.p, xy, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
+	BHIP_TRY(briefImpl(ctx, sizeof(T) == 1, sc->in0.p, (long long)width * height, width, width, height, 1, radius, numPoints, samplePoints, nSample, compare,
+					   sc->in1.as<double>(), nullptr, n, 0, sc->out0.as<int32_t>()));
+	BHIP_HIP(ctx, hipMemcpyAsync(out, sc->out0.p, (size_t)n * words * 4, hipMemcpyDeviceToHost, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
+}
+
+extern "C" {
+
 static int convHost(bhip_ctx* ctx, bool vertical, bool normalized, const float* kernel, int kw, int koff, const float* in, int inStart, int inStride,
 					int width, int height, float* out, int outStart, int outStride) {
-	CHECK_IMG(ctx, in, inStride, width, height);
-	CHECK_IMG(ctx, out, outStride, width, height);
+	CHECK_CTX(ctx);
+	CHECK_IMG(ctx, in, inStride, width, height, 1);
+	CHECK_IMG(ctx, out, outStride, width, height, 1);
 	if (!kernel) return bhip_fail(ctx, BHIP_ERR_INVALID, "null kernel");
 	CtxScratch* sc = scratchOf(ctx);
 	const int pitch = pitch4(width);
-	BHIP_TRY(uploadImage(ctx, sc->a, in, inStart, inStride, width, height, pitch));
+	const long long img = (long long)pitch * height;
+	BHIP_TRY(sc->in0.reserve(ctx, img * 4));
+	BHIP_TRY(sc->out0.reserve(ctx, img * 4));
+	BHIP_TRY(upload(ctx, sc->in0.as<float>(), pitch, in, inStart, inStride, width, height, ctx->stream));
 	// the no-border variants leave the frame of `out` untouched: start from the caller's pixels
-	BHIP_TRY(uploadImage(ctx, sc->b, out, outStart, outStride, width, height, pitch));
-	BHIP_TRY(bhip_launch_conv(ctx, vertical, normalized, kernel, kw, koff, sc->a.as<float>(), pitch, width, height, sc->b.as<float>(), pitch));
-	return downloadImage(ctx, sc->b.p, out, outStart, outStride, width, height, pitch);
+	BHIP_TRY(upload(ctx, sc->out0.as<float>(), pitch, out, outStart, outStride, width, height, ctx->stream));
+	BHIP_TRY(convImpl(ctx, vertical, normalized, kernel, kw, koff, sc->in0.as<float>(), img, pitch, width, height, 1, sc->out0.as<float>(), img, pitch));
+	BHIP_TRY(download(ctx, out, outStart, outStride, sc->out0.as<float>(), pitch, width, height, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
 }
 int bhip_conv_h_f32(bhip_ctx* ctx, const float* kernel, int kw, int koff, const float* in, int inStart, int inStride, int width, int height, float* out,
 					int outStart, int outStride) {
-	CHECK_CTX(ctx);
 	return convHost(ctx, false, false, kernel, kw, koff, in, inStart, inStride, width, height, out, outStart, outStride);
 }
 int bhip_conv_v_f32(bhip_ctx* ctx, const float* kernel, int kw, int koff, const float* in, int inStart, int inStride, int width, int height, float* out,
 					int outStart, int outStride) {
-	CHECK_CTX(ctx);
 	return convHost(ctx, true, false, kernel, kw, koff, in, inStart, inStride, width, height, out, outStart, outStride);
 }
 int bhip_conv_norm_h_f32(bhip_ctx* ctx, const float* kernel, int kw, int koff, const float* in, int inStart, int inStride, int width, int height,
 						 float* out, int outStart, int outStride) {
-	CHECK_CTX(ctx);
 	return convHost(ctx, false, true, kernel, kw, koff, in, inStart, inStride, width, height, out, outStart, outStride);
 }
 int bhip_conv_norm_v_f32(bhip_ctx* ctx, const float* kernel, int kw, int koff, const float* in, int inStart, int inStride, int width, int height,
 						 float* out, int outStart, int outStride) {
-	CHECK_CTX(ctx);
 	return convHost(ctx, true, true, kernel, kw, koff, in, inStart, inStride, width, height, out, outStart, outStride);
 }
 
 int bhip_gaussian_f32(bhip_ctx* ctx, const float* in, int inStart, int inStride, int width, int height, double sigma, int radius, float* out,
 					  int outStart, int outStride) {
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, in, inStride, width, height);
-	CHECK_IMG(ctx, out, outStride, width, height);
+	CHECK_IMG(ctx, in, inStride, width, height, 1);
+	CHECK_IMG(ctx, out, outStride, width, height, 1);
 	if (sigma <= 0 && radius <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Sigma must be > 0");
-	std::vector<float> k = bhip_gaussian1d_f32(sigma, radius);
-	const int kw = (int)k.size(), koff = kw / 2;
 	CtxScratch* sc = scratchOf(ctx);
 	const int pitch = pitch4(width);
-	BHIP_TRY(uploadImage(ctx, sc->a, in, inStart, inStride, width, height, pitch));
-	BHIP_TRY(sc->c.reserve(ctx, (size_t)pitch * height * 4));
-	bool fused = false;
-	BHIP_TRY(bhip_launch_blur_fused(ctx, k.data(), kw, sc->a.as<float>(), pitch, width, height, sc->c.as<float>(), pitch, 1, 0, 0, &fused));
-	if (!fused) {
-		BHIP_TRY(sc->b.reserve(ctx, (size_t)pitch * height * 4));
-		BHIP_TRY(bhip_launch_conv(ctx, false, true, k.data(), kw, koff, sc->a.as<float>(), pitch, width, height, sc->b.as<float>(), pitch));
-		BHIP_TRY(bhip_launch_conv(ctx, true, true, k.data(), kw, koff, sc->b.as<float>(), pitch, width, height, sc->c.as<float>(), pitch));
-	}
-	return downloadImage(ctx, sc->c.p, out, outStart, outStride, width, height, pitch);
+	const long long img = (long long)pitch * height;
+	BHIP_TRY(sc->in0.reserve(ctx, img * 4));
+	BHIP_TRY(sc->out0.reserve(ctx, img * 4));
+	BHIP_TRY(upload(ctx, sc->in0.as<float>(), pitch, in, inStart, inStride, width, height, ctx->stream));
+	BHIP_TRY(gaussianImpl(ctx, sigma, radius, sc->in0.as<float>(), img, pitch, width, height, 1, sc->out0.as<float>(), img, pitch));
+	BHIP_TRY(download(ctx, out, outStart, outStride, sc->out0.as<float>(), pitch, width, height, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
 }
 
 static int convDownHost(bhip_ctx* ctx, bool vertical, const float* kernel, int kw, const float* in, int inStart, int inStride, int width, int height,
 						float* out, int outStart, int outStride, int outWidth, int outHeight, int skip) {
-	CHECK_IMG(ctx, in, inStride, width, height);
-	CHECK_IMG(ctx, out, outStride, outWidth, outHeight);
+	CHECK_CTX(ctx);
+	CHECK_IMG(ctx, in, inStride, width, height, 1);
+	CHECK_IMG(ctx, out, outStride, outWidth, outHeight, 1);
 	if (!kernel) return bhip_fail(ctx, BHIP_ERR_INVALID, "null kernel");
 	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(uploadImage(ctx, sc->a, in, inStart, inStride, width, height));
+	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
+	BHIP_TRY(sc->out0.reserve(ctx, (size_t)outWidth * outHeight * 4));
+	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, in, inStart, inStride, width, height, ctx->stream));
 	// pixels the reference does not write keep the caller's values
-	BHIP_TRY(uploadImage(ctx, sc->b, out, outStart, outStride, outWidth, outHeight));
-	BHIP_TRY(bhip_launch_conv_down(ctx, vertical, kernel, kw, sc->a.as<float>(), 0, width, width, height, sc->b.as<float>(), 0, outWidth, outWidth,
+	BHIP_TRY(upload(ctx, sc->out0.as<float>(), outWidth, out, outStart, outStride, outWidth, outHeight, ctx->stream));
+	BHIP_TRY(bhip_launch_conv_down(ctx, vertical, kernel, kw, sc->in0.as<float>(), 0, width, width, height, sc->out0.as<float>(), 0, outWidth, outWidth,
 								   outHeight, skip, 1));
-	return downloadImage(ctx, sc->b.p, out, outStart, outStride, outWidth, outHeight);
+	BHIP_TRY(download(ctx, out, outStart, outStride, sc->out0.as<float>(), outWidth, outWidth, outHeight, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
 }
 int bhip_conv_down_norm_h_f32(bhip_ctx* ctx, const float* kernel, int kw, const float* in, int inStart, int inStride, int width, int height, float* out,
 							  int outStart, int outStride, int outWidth, int outHeight, int skip) {
-	CHECK_CTX(ctx);
 	return convDownHost(ctx, false, kernel, kw, in, inStart, inStride, width, height, out, outStart, outStride, outWidth, outHeight, skip);
 }
 int bhip_conv_down_norm_v_f32(bhip_ctx* ctx, const float* kernel, int kw, const float* in, int inStart, int inStride, int width, int height, float* out,
 							  int outStart, int outStride, int outWidth, int outHeight, int skip) {
-	CHECK_CTX(ctx);
 	return convDownHost(ctx, true, kernel, kw, in, inStart, inStride, width, height, out, outStart, outStride, outWidth, outHeight, skip);
 }
 
@@ -1607,8 +1748,8 @@ int bhip_pyramid_dev_f32(bhip_ctx* ctx, const float* kernel, int kw, const int* 
 		}
 	}
 	if (tempCap > 0) {
-		BHIP_TRY(sc->d.reserve(ctx, (size_t)tempCap * 4 * batch));
-		BHIP_HIP(ctx, hipMemsetAsync(sc->d.p, 0, (size_t)tempCap * 4 * batch, ctx->stream));
+		BHIP_TRY(sc->ipTmp.reserve(ctx, (size_t)tempCap * 4 * batch));
+		BHIP_HIP(ctx, hipMemsetAsync(sc->ipTmp.p, 0, (size_t)tempCap * 4 * batch, ctx->stream));
 	}
 	const float* prev = dev_in;
 	long long prevImageStride = inImageStride;
@@ -1625,9 +1766,9 @@ int bhip_pyramid_dev_f32(bhip_ctx* ctx, const float* kernel, int kw, const int* 
 			bool fused = false;
 			BHIP_TRY(bhip_launch_pyr_layer_fused(ctx, kernel, kw, prev, prevImageStride, prevStride, pw, ph, layer, total, lw, skip, batch, &fused));
 			if (!fused) {
-				BHIP_TRY(bhip_launch_conv_down(ctx, false, kernel, kw, prev, prevImageStride, prevStride, pw, ph, sc->d.as<float>(), tempCap, tw, tw, ph, skip,
+				BHIP_TRY(bhip_launch_conv_down(ctx, false, kernel, kw, prev, prevImageStride, prevStride, pw, ph, sc->ipTmp.as<float>(), tempCap, tw, tw, ph, skip,
 											   batch));
-				BHIP_TRY(bhip_launch_conv_down(ctx, true, kernel, kw, sc->d.as<float>(), tempCap, tw, tw, ph, layer, total, lw, lw, lh, skip, batch));
+				BHIP_TRY(bhip_launch_conv_down(ctx, true, kernel, kw, sc->ipTmp.as<float>(), tempCap, tw, tw, ph, layer, total, lw, lw, lh, skip, batch));
 			}
 		}
 		prev = layer; prevImageStride = total; prevStride = lw; pw = lw; ph = lh;
@@ -1638,180 +1779,92 @@ int bhip_pyramid_dev_f32(bhip_ctx* ctx, const float* kernel, int kw, const int* 
 int bhip_pyramid_f32(bhip_ctx* ctx, const float* kernel, int kw, const int* scales, int n, const float* in, int inStart, int inStride, int width,
 					 int height, float* out) {
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, in, inStride, width, height);
+	CHECK_IMG(ctx, in, inStride, width, height, 1);
 	if (!out || !kernel || !scales) return bhip_fail(ctx, BHIP_ERR_INVALID, "null buffer");
 	long long total = 0;
 	if (bhip_pyramid_layout(width, height, scales, n, nullptr, nullptr, &total) != BHIP_OK) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad pyramid scales");
 	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(uploadImage(ctx, sc->a, in, inStart, inStride, width, height));
-	BHIP_TRY(sc->b.reserve(ctx, (size_t)total * 4));
-	BHIP_TRY(bhip_pyramid_dev_f32(ctx, kernel, kw, scales, n, sc->a.as<float>(), (long long)width * height, width, width, height, 1, sc->b.as<float>()));
-	BHIP_HIP(ctx, hipMemcpyAsync(out, sc->b.p, (size_t)total * 4, hipMemcpyDeviceToHost, ctx->stream));
-	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return BHIP_OK;
+	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
+	BHIP_TRY(sc->out0.reserve(ctx, (size_t)total * 4));
+	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, in, inStart, inStride, width, height, ctx->stream));
+	BHIP_TRY(bhip_pyramid_dev_f32(ctx, kernel, kw, scales, n, sc->in0.as<float>(), (long long)width * height, width, width, height, 1, sc->out0.as<float>()));
+	BHIP_HIP(ctx, hipMemcpyAsync(out, sc->out0.p, (size_t)total * 4, hipMemcpyDeviceToHost, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
 }
 
 int bhip_conv2d_f32(bhip_ctx* ctx, const float* kernel, int kw, int koff, const float* in, int inStart, int inStride, int width, int height, float* out,
 					int outStart, int outStride) {
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, in, inStride, width, height);
-	CHECK_IMG(ctx, out, outStride, width, height);
+	CHECK_IMG(ctx, in, inStride, width, height, 1);
+	CHECK_IMG(ctx, out, outStride, width, height, 1);
 	if (!kernel) return bhip_fail(ctx, BHIP_ERR_INVALID, "null kernel");
 	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(uploadImage(ctx, sc->a, in, inStart, inStride, width, height));
-	BHIP_TRY(uploadImage(ctx, sc->b, out, outStart, outStride, width, height));   // the frame keeps the caller's pixels
-	BHIP_TRY(bhip_launch_conv2d(ctx, kernel, kw, koff, sc->a.as<float>(), width, width, height, sc->b.as<float>(), width));
-	return downloadImage(ctx, sc->b.p, out, outStart, outStride, width, height);
+	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
+	BHIP_TRY(sc->out0.reserve(ctx, (size_t)width * height * 4));
+	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, in, inStart, inStride, width, height, ctx->stream));
+	BHIP_TRY(upload(ctx, sc->out0.as<float>(), width, out, outStart, outStride, width, height, ctx->stream));   // the frame keeps the caller's pixels
+	BHIP_TRY(bhip_launch_conv2d(ctx, kernel, kw, koff, sc->in0.as<float>(), width, width, height, sc->out0.as<float>(), width));
+	BHIP_TRY(download(ctx, out, outStart, outStride, sc->out0.as<float>(), width, width, height, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
 }
 int bhip_mean_f32(bhip_ctx* ctx, const float* in, int inStart, int inStride, int width, int height, int radiusX, int radiusY, float* out, int outStart,
 				  int outStride) {
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, in, inStride, width, height);
-	CHECK_IMG(ctx, out, outStride, width, height);
+	CHECK_IMG(ctx, in, inStride, width, height, 1);
+	CHECK_IMG(ctx, out, outStride, width, height, 1);
 	if (radiusX <= 0 || radiusY <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Radius must be > 0");
 	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(uploadImage(ctx, sc->a, in, inStart, inStride, width, height));
-	BHIP_TRY(sc->b.reserve(ctx, (size_t)width * height * 4));
-	BHIP_TRY(sc->c.reserve(ctx, (size_t)width * height * 4));
-	BHIP_TRY(bhip_launch_mean(ctx, false, sc->a.as<float>(), sc->b.as<float>(), width, height, radiusX));
-	BHIP_TRY(bhip_launch_mean(ctx, true, sc->b.as<float>(), sc->c.as<float>(), width, height, radiusY));
-	return downloadImage(ctx, sc->c.p, out, outStart, outStride, width, height);
+	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
+	BHIP_TRY(sc->tmp0.reserve(ctx, (size_t)width * height * 4));
+	BHIP_TRY(sc->out0.reserve(ctx, (size_t)width * height * 4));
+	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, in, inStart, inStride, width, height, ctx->stream));
+	BHIP_TRY(bhip_launch_mean(ctx, false, sc->in0.as<float>(), sc->tmp0.as<float>(), width, height, radiusX));
+	BHIP_TRY(bhip_launch_mean(ctx, true, sc->tmp0.as<float>(), sc->out0.as<float>(), width, height, radiusY));
+	BHIP_TRY(download(ctx, out, outStart, outStride, sc->out0.as<float>(), width, width, height, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
 }
 int bhip_median_f32(bhip_ctx* ctx, const float* in, int inStart, int inStride, int width, int height, int radius, float* out, int outStart, int outStride) {
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, in, inStride, width, height);
-	CHECK_IMG(ctx, out, outStride, width, height);
+	CHECK_IMG(ctx, in, inStride, width, height, 1);
+	CHECK_IMG(ctx, out, outStride, width, height, 1);
 	if (radius <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Radius must be > 0");
 	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(uploadImage(ctx, sc->a, in, inStart, inStride, width, height));
-	BHIP_TRY(sc->b.reserve(ctx, (size_t)width * height * 4));
-	BHIP_TRY(bhip_launch_median(ctx, sc->a.as<float>(), width, sc->b.as<float>(), width, width, height, radius));
-	return downloadImage(ctx, sc->b.p, out, outStart, outStride, width, height);
+	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
+	BHIP_TRY(sc->out0.reserve(ctx, (size_t)width * height * 4));
+	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, in, inStart, inStride, width, height, ctx->stream));
+	BHIP_TRY(bhip_launch_median(ctx, sc->in0.as<float>(), width, sc->out0.as<float>(), width, width, height, radius));
+	BHIP_TRY(download(ctx, out, outStart, outStride, sc->out0.as<float>(), width, width, height, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
 }
 
-static int gradHost(bhip_ctx* ctx, int kind, const float* in, int inStart, int inStride, int width, int height, float* dx, float* dy, int outStart,
-					int outStride, int border) {
-	CHECK_IMG(ctx, in, inStride, width, height);
-	CHECK_IMG(ctx, dx, outStride, width, height);
-	CHECK_IMG(ctx, dy, outStride, width, height);
-	if (border != 0 && border != 1) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "border policy not supported on the GPU");
-	CtxScratch* sc = scratchOf(ctx);
-	const int pitch = pitch4(width);
-	BHIP_TRY(uploadImage(ctx, sc->a, in, inStart, inStride, width, height, pitch));
-	BHIP_TRY(uploadImage(ctx, sc->b, dx, outStart, outStride, width, height, pitch));
-	BHIP_TRY(uploadImage(ctx, sc->c, dy, outStart, outStride, width, height, pitch));
-	BHIP_TRY(bhip_launch_gradient(ctx, kind, sc->a.as<float>(), pitch, width, height, sc->b.as<float>(), sc->c.as<float>(), pitch, border));
-	BHIP_TRY(downloadImage(ctx, sc->b.p, dx, outStart, outStride, width, height, pitch));
-	return downloadImage(ctx, sc->c.p, dy, outStart, outStride, width, height, pitch);
-}
 int bhip_sobel_f32(bhip_ctx* ctx, const float* in, int inStart, int inStride, int width, int height, float* dx, float* dy, int outStart, int outStride,
 				   int border) {
-	CHECK_CTX(ctx);
 	return gradHost(ctx, 0, in, inStart, inStride, width, height, dx, dy, outStart, outStride, border);
 }
 int bhip_three_f32(bhip_ctx* ctx, const float* in, int inStart, int inStride, int width, int height, float* dx, float* dy, int outStart, int outStride,
 				   int border) {
-	CHECK_CTX(ctx);
 	return gradHost(ctx, 1, in, inStart, inStride, width, height, dx, dy, outStart, outStride, border);
-}
-
-// FactoryIntensityPointAlg.shiTomasi / harris (unweighted, GrayF32) -> GradientCornerIntensity.process(derivX, derivY, intensity)
-int bhip_corner_intensity_f32(bhip_ctx* ctx, int kind, int radius, float kappa, const float* derivX, const float* derivY, int dStart, int dStride, int width,
-							  int height, float* intensity, int iStart, int iStride) {
-	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, derivX, dStride, width, height);
-	CHECK_IMG(ctx, derivY, dStride, width, height);
-	CHECK_IMG(ctx, intensity, iStride, width, height);
-	CtxScratch* sc = scratchOf(ctx);
-	const size_t px = (size_t)width * height;
-	BHIP_TRY(uploadImage(ctx, sc->a, derivX, dStart, dStride, width, height));
-	BHIP_TRY(uploadImage(ctx, sc->b, derivY, dStart, dStride, width, height));
-	BHIP_TRY(sc->c.reserve(ctx, px * 4 * 3));
-	BHIP_TRY(sc->d.reserve(ctx, px * 4));
-	BHIP_HIP(ctx, hipMemsetAsync(sc->d.p, 0, px * 4, ctx->stream));   // ImageMiscOps.fillBorder(intensity, 0, radius); the interior is overwritten
-	float* h = sc->c.as<float>();
-	BHIP_TRY(bhip_launch_corner_intensity(ctx, kind, radius, kappa, sc->a.as<float>(), sc->b.as<float>(), width, width, height, h, h + px, h + 2 * px,
-										  sc->d.as<float>(), width));
-	return downloadImage(ctx, sc->d.p, intensity, iStart, iStride, width, height);
-}
-
-// ---- GrayU8 -> GrayS16 gradients and the S16 / weighted corner intensity ----
-// element-size copies of an image view to / from a dense device copy (integer images)
-static int uploadElems(bhip_ctx* ctx, DevBuf& buf, const void* in, size_t es, int start, int stride, int w, int h) {
-	BHIP_TRY(buf.reserve(ctx, es * w * h));
-	BHIP_HIP(ctx, hipMemcpy2DAsync(buf.p, es * w, static_cast<const char*>(in) + es * start, es * stride, es * w, h, hipMemcpyHostToDevice, ctx->stream));
-	return BHIP_OK;
-}
-static int downloadElems(bhip_ctx* ctx, const void* dev, void* out, size_t es, int start, int stride, int w, int h) {
-	BHIP_HIP(ctx, hipMemcpy2DAsync(static_cast<char*>(out) + es * start, es * stride, dev, es * w, es * w, h, hipMemcpyDeviceToHost, ctx->stream));
-	return BHIP_OK;
-}
-static int gradU8Host(bhip_ctx* ctx, int kind, const uint8_t* in, int inStart, int inStride, int width, int height, int16_t* dx, int16_t* dy, int outStart,
-					  int outStride, int border) {
-	CHECK_IMG(ctx, in, inStride, width, height);
-	CHECK_IMG(ctx, dx, outStride, width, height);
-	CHECK_IMG(ctx, dy, outStride, width, height);
-	if (border != 0 && border != 1) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "border policy not supported on the GPU");
-	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(uploadElems(ctx, sc->a, in, 1, inStart, inStride, width, height));
-	// without a border policy the frame keeps the caller's values
-	BHIP_TRY(uploadElems(ctx, sc->b, dx, 2, outStart, outStride, width, height));
-	BHIP_TRY(uploadElems(ctx, sc->c, dy, 2, outStart, outStride, width, height));
-	BHIP_TRY(bhip_launch_gradient_u8(ctx, kind, static_cast<const uint8_t*>(sc->a.p), 0, width, width, height, 1, static_cast<int16_t*>(sc->b.p),
-									 static_cast<int16_t*>(sc->c.p), 0, width, border));
-	BHIP_TRY(downloadElems(ctx, sc->b.p, dx, 2, outStart, outStride, width, height));
-	BHIP_TRY(downloadElems(ctx, sc->c.p, dy, 2, outStart, outStride, width, height));
-	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return BHIP_OK;
 }
 int bhip_sobel_u8_s16(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, int16_t* dx, int16_t* dy, int outStart,
 					  int outStride, int border) {
-	CHECK_CTX(ctx);
-	return gradU8Host(ctx, 0, in, inStart, inStride, width, height, dx, dy, outStart, outStride, border);
+	return gradHost(ctx, 0, in, inStart, inStride, width, height, dx, dy, outStart, outStride, border);
 }
 int bhip_three_u8_s16(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, int16_t* dx, int16_t* dy, int outStart,
 					  int outStride, int border) {
-	CHECK_CTX(ctx);
-	return gradU8Host(ctx, 1, in, inStart, inStride, width, height, dx, dy, outStart, outStride, border);
+	return gradHost(ctx, 1, in, inStart, inStride, width, height, dx, dy, outStart, outStride, border);
 }
 
-// box (ImplSsdCorner_S16) or weighted (ImplSsdCornerWeighted_S16) on device images; scratch from the context when the box radius needs it
-static int cornerS16Dev(bhip_ctx* ctx, DevBuf& scratch, int kind, int radius, float kappa, int weighted, const int16_t* dx, const int16_t* dy,
-						long long dImageStride, int dStride, int width, int height, int batch, float* intensity, long long iImageStride, int iStride) {
-	if (weighted)
-		return bhip_launch_corner_weighted(ctx, true, kind, radius, kappa, dx, dy, dImageStride, dStride, width, height, batch, intensity, iImageStride, iStride);
-	if (radius >= 0 && 2 * radius + 1 <= width && 2 * radius + 1 <= height) {
-		const size_t bytes = bhip_corner_box_s16_scratch(radius, width, height, batch);
-		if (bytes) BHIP_TRY(scratch.reserve(ctx, bytes));
-	}
-	return bhip_launch_corner_box_s16(ctx, kind, radius, kappa, dx, dy, dImageStride, dStride, width, height, batch, intensity, iImageStride, iStride, scratch.p);
+int bhip_corner_intensity_f32(bhip_ctx* ctx, int kind, int radius, float kappa, const float* derivX, const float* derivY, int dStart, int dStride, int width,
+							  int height, float* intensity, int iStart, int iStride) {
+	return cornerHost(ctx, false, kind, radius, kappa, derivX, derivY, dStart, dStride, width, height, intensity, iStart, iStride);
 }
 int bhip_corner_intensity_s16(bhip_ctx* ctx, int kind, int radius, float kappa, int weighted, const int16_t* derivX, const int16_t* derivY, int dStart,
 							  int dStride, int width, int height, float* intensity, int iStart, int iStride) {
-	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, derivX, dStride, width, height);
-	CHECK_IMG(ctx, derivY, dStride, width, height);
-	CHECK_IMG(ctx, intensity, iStride, width, height);
-	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(uploadElems(ctx, sc->a, derivX, 2, dStart, dStride, width, height));
-	BHIP_TRY(uploadElems(ctx, sc->b, derivY, 2, dStart, dStride, width, height));
-	BHIP_TRY(sc->d.reserve(ctx, (size_t)width * height * 4));
-	BHIP_TRY(cornerS16Dev(ctx, sc->c, kind, radius, kappa, weighted, static_cast<const int16_t*>(sc->a.p), static_cast<const int16_t*>(sc->b.p), 0, width,
-						  width, height, 1, sc->d.as<float>(), 0, width));
-	return downloadImage(ctx, sc->d.p, intensity, iStart, iStride, width, height);
+	return cornerHost(ctx, weighted != 0, kind, radius, kappa, derivX, derivY, dStart, dStride, width, height, intensity, iStart, iStride);
 }
 int bhip_corner_intensity_weighted_f32(bhip_ctx* ctx, int kind, int radius, float kappa, const float* derivX, const float* derivY, int dStart, int dStride,
 									   int width, int height, float* intensity, int iStart, int iStride) {
-	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, derivX, dStride, width, height);
-	CHECK_IMG(ctx, derivY, dStride, width, height);
-	CHECK_IMG(ctx, intensity, iStride, width, height);
-	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(uploadImage(ctx, sc->a, derivX, dStart, dStride, width, height));
-	BHIP_TRY(uploadImage(ctx, sc->b, derivY, dStart, dStride, width, height));
-	BHIP_TRY(sc->d.reserve(ctx, (size_t)width * height * 4));
-	BHIP_TRY(bhip_launch_corner_weighted(ctx, false, kind, radius, kappa, sc->a.p, sc->b.p, 0, width, width, height, 1, sc->d.as<float>(), 0, width));
-	return downloadImage(ctx, sc->d.p, intensity, iStart, iStride, width, height);
+	return cornerHost(ctx, true, kind, radius, kappa, derivX, derivY, dStart, dStride, width, height, intensity, iStart, iStride);
 }
 int bhip_gaussian_kernel1d_s32(int radius, int32_t* out, int capacity) {
 	if (radius <= 0) return -1;
@@ -1824,15 +1877,15 @@ int bhip_gaussian_kernel1d_s32(int radius, int32_t* out, int capacity) {
 // ---- integer image variants, stage level ----
 int bhip_integral_u8_s32(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, int32_t* out, int outStart, int outStride) {
 	CHECK_CTX(ctx);
-	if (!in || !out || width <= 0 || height <= 0 || inStride < width || outStride < width) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image");
+	CHECK_IMG(ctx, in, inStride, width, height, 1);
+	CHECK_IMG(ctx, out, outStride, width, height, 1);
 	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(sc->a.reserve(ctx, (size_t)width * height));
-	BHIP_TRY(sc->b.reserve(ctx, (size_t)width * height * 4));
-	BHIP_HIP(ctx, hipMemcpy2DAsync(sc->a.p, (size_t)width, in + inStart, (size_t)inStride, (size_t)width, height, hipMemcpyHostToDevice, ctx->stream));
-	BHIP_TRY(bhip_launch_integral_u8(ctx, (const unsigned char*)sc->a.p, 0, width, sc->b.as<int>(), 0, width, width, height, 1));
-	BHIP_HIP(ctx, hipMemcpy2DAsync(out + outStart, (size_t)outStride * 4, sc->b.p, (size_t)width * 4, (size_t)width * 4, height, hipMemcpyDeviceToHost, ctx->stream));
-	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return BHIP_OK;
+	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height));
+	BHIP_TRY(sc->out0.reserve(ctx, (size_t)width * height * 4));
+	BHIP_TRY(upload(ctx, sc->in0.as<uint8_t>(), width, in, inStart, inStride, width, height, ctx->stream));
+	BHIP_TRY(bhip_launch_integral_u8(ctx, sc->in0.as<unsigned char>(), 0, width, sc->out0.as<int>(), 0, width, width, height, 1));
+	BHIP_TRY(download(ctx, out, outStart, outStride, sc->out0.as<int32_t>(), width, width, height, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
 }
 int bhip_hessian_s32(bhip_ctx* ctx, const int32_t* ii, int iiStart, int iiStride, int width, int height, int skip, int size, float* out, int outStart,
 					 int outStride) {
@@ -1842,204 +1895,112 @@ int bhip_hessian_s32(bhip_ctx* ctx, const int32_t* ii, int iiStart, int iiStride
 	const int w = width / skip, h = height / skip;
 	if (w <= 0 || h <= 0 || outStride < w) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad intensity image");
 	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(uploadImage(ctx, sc->a, (const float*)ii, iiStart, iiStride, width, height));   // 32-bit words either way
-	BHIP_TRY(sc->b.reserve(ctx, (size_t)w * h * 4));
-	ImgView iv{sc->a.as<float>(), (long long)width * height, width, width, height};
-	BHIP_TRY(bhip_launch_hessian(ctx, iv, 1, skip, 1, &size, sc->b.as<float>(), (long long)w * h, (long long)w * h, w, nullptr, true));
-	return downloadImage(ctx, sc->b.p, out, outStart, outStride, w, h);
+	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
+	BHIP_TRY(sc->out0.reserve(ctx, (size_t)w * h * 4));
+	BHIP_TRY(upload(ctx, sc->in0.as<int32_t>(), width, ii, iiStart, iiStride, width, height, ctx->stream));
+	ImgView iv{sc->in0.as<float>(), (long long)width * height, width, width, height};   // 32-bit words either way
+	BHIP_TRY(bhip_launch_hessian(ctx, iv, 1, skip, 1, &size, sc->out0.as<float>(), (long long)w * h, (long long)w * h, w, nullptr, true));
+	BHIP_TRY(download(ctx, out, outStart, outStride, sc->out0.as<float>(), w, w, h, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
 }
+
+// The BRIEF exports differ in what they accept (not harmonised): bhip_brief_f32 rejects a pair index >= numPoints and decides the kernel over
+// numPoints sample points; bhip_brief_u8 and bhip_brief_dev_f32 accept any non-negative index and use maxIdx + 1 points.
 int bhip_brief_u8(bhip_ctx* ctx, const uint8_t* img, int start, int stride, int width, int height, int radius, int numPoints, const int32_t* samplePoints,
 				  const int32_t* compare, const double* xy, int n, int32_t* out) {
 	CHECK_CTX(ctx);
-	if (!img || width <= 0 || height <= 0 || stride < width) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image");
+	CHECK_IMG(ctx, img, stride, width, height, 1);
 	if (numPoints <= 0 || !samplePoints || !compare || n < 0 || (n > 0 && (!xy || !out))) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad BRIEF arguments");
 	if (n == 0) return BHIP_OK;
 	int maxIdx = 0;
 	for (int i = 0; i < 2 * numPoints; i++) { if (compare[i] < 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "negative sample index"); maxIdx = std::max(maxIdx, compare[i]); }
-	const int words = (numPoints + 31) / 32;
-	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(sc->a.reserve(ctx, (size_t)width * height));
-	BHIP_TRY(sc->b.reserve(ctx, (size_t)(maxIdx + 1) * 8 + (size_t)numPoints * 8));
-	BHIP_TRY(sc->c.reserve(ctx, (size_t)n * 16));
-	BHIP_TRY(sc->d.reserve(ctx, (size_t)n * words * 4));
-	BHIP_HIP(ctx, hipMemcpy2DAsync(sc->a.p, (size_t)width, img + start, (size_t)stride, (size_t)width, height, hipMemcpyHostToDevice, ctx->stream));
-	int* dSample = sc->b.as<int>();
-	int* dCompare = dSample + 2 * (maxIdx + 1);
-	BHIP_HIP(ctx, hipMemcpyAsync(dSample, samplePoints, (size_t)(maxIdx + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-	BHIP_HIP(ctx, hipMemcpyAsync(dCompare, compare, (size_t)numPoints * 8, hipMemcpyHostToDevice, ctx->stream));
-	BHIP_HIP(ctx, hipMemcpyAsync(sc->c.p, xy, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-	BHIP_TRY(bhip_launch_brief(ctx, (const float*)sc->a.p, width, width, height, radius, numPoints, dSample, dCompare, sc->c.as<double>(), n, sc->d.as<int>(), true, 1, 0, nullptr, 0, 2, 0,
-							   briefPatchOk(samplePoints, maxIdx + 1, radius)));
-	BHIP_HIP(ctx, hipMemcpyAsync(out, sc->d.p, (size_t)n * words * 4, hipMemcpyDeviceToHost, ctx->stream));
-	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return BHIP_OK;
+	return briefHost(ctx, img, start, stride, width, height, radius, numPoints, samplePoints, maxIdx + 1, compare, xy, n, out);
 }
 
 int bhip_brief_f32(bhip_ctx* ctx, const float* img, int start, int stride, int width, int height, int radius, int numPoints,
 				   const int32_t* samplePoints, const int32_t* compare, const double* xy, int n, int32_t* out) {
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, img, stride, width, height);
+	CHECK_IMG(ctx, img, stride, width, height, 1);
 	if (numPoints <= 0 || !samplePoints || !compare || n < 0 || (n > 0 && (!xy || !out))) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad BRIEF arguments");
 	if (n == 0) return BHIP_OK;
 	for (int i = 0; i < 2 * numPoints; i++)
 		if (compare[i] < 0 || compare[i] >= numPoints) return bhip_fail(ctx, BHIP_ERR_INVALID, "pair index outside the sample point list");
-	const int words = (numPoints + 31) / 32;
-	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(uploadImage(ctx, sc->a, img, start, stride, width, height));
-	BHIP_TRY(sc->b.reserve(ctx, (size_t)numPoints * 16));
-	BHIP_TRY(sc->c.reserve(ctx, (size_t)n * 16));
-	BHIP_TRY(sc->e.reserve(ctx, (size_t)n * words * 4));
-	int* dsp = sc->b.as<int>();
-	int* dcp = dsp + 2 * numPoints;
-	BHIP_HIP(ctx, hipMemcpyAsync(dsp, samplePoints, (size_t)numPoints * 8, hipMemcpyHostToDevice, ctx->stream));
-	BHIP_HIP(ctx, hipMemcpyAsync(dcp, compare, (size_t)numPoints * 8, hipMemcpyHostToDevice, ctx->stream));
-	BHIP_HIP(ctx, hipMemcpyAsync(sc->c.p, xy, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-	BHIP_TRY(bhip_launch_brief(ctx, sc->a.as<float>(), width, width, height, radius, numPoints, dsp, dcp, sc->c.as<double>(), n, sc->e.as<int>(), false, 1, 0, nullptr, 0, 2, 0,
-							   briefPatchOk(samplePoints, numPoints, radius)));
-	BHIP_HIP(ctx, hipMemcpyAsync(out, sc->e.p, (size_t)n * words * 4, hipMemcpyDeviceToHost, ctx->stream));
-	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return BHIP_OK;
+	return briefHost(ctx, img, start, stride, width, height, radius, numPoints, samplePoints, numPoints, compare, xy, n, out);
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// device-resident, batched forms of the boofcv-ip front end (BASELINE config 5: pyramid -> gradient -> NMS -> SURF on a 4K stream without
-// leaving HBM).  Image b of a batch starts imageStride floats after image 0, rows are `stride` floats apart; everything is
-// asynchronous on the ctx stream.  Same kernels and arithmetic as the host-buffer entry points above.
-// ---------------------------------------------------------------------------------------------------------------
-#define CHECK_DEV_BATCH(ctx, p, stride, w, h, batch)                                                                                      \
-	do {                                                                                                                                  \
-		if (!(p) || (w) <= 0 || (h) <= 0 || (batch) <= 0 || (stride) < (w)) return bhip_fail((ctx), BHIP_ERR_INVALID, "bad image batch"); \
-	} while (0)
-
+// ---- device-batched forms ----
 static int convDev(bhip_ctx* ctx, bool vertical, bool normalized, const float* kernel, int kw, int koff, const float* dev_in, long long inImageStride,
 				   int inStride, int width, int height, int batch, float* dev_out, long long outImageStride, int outStride) {
-	CHECK_DEV_BATCH(ctx, dev_in, inStride, width, height, batch);
-	CHECK_DEV_BATCH(ctx, dev_out, outStride, width, height, batch);
+	CHECK_CTX(ctx);
+	CHECK_IMG(ctx, dev_in, inStride, width, height, batch);
+	CHECK_IMG(ctx, dev_out, outStride, width, height, batch);
 	if (!kernel) return bhip_fail(ctx, BHIP_ERR_INVALID, "null kernel");
-	return bhip_launch_conv(ctx, vertical, normalized, kernel, kw, koff, dev_in, inStride, width, height, dev_out, outStride, batch, inImageStride, outImageStride);
+	return convImpl(ctx, vertical, normalized, kernel, kw, koff, dev_in, inImageStride, inStride, width, height, batch, dev_out, outImageStride, outStride);
 }
 int bhip_conv_h_dev_f32(bhip_ctx* ctx, const float* kernel, int kw, int koff, const float* dev_in, long long inImageStride, int inStride, int width, int height,
 						int batch, float* dev_out, long long outImageStride, int outStride) {
-	CHECK_CTX(ctx);
 	return convDev(ctx, false, false, kernel, kw, koff, dev_in, inImageStride, inStride, width, height, batch, dev_out, outImageStride, outStride);
 }
 int bhip_conv_v_dev_f32(bhip_ctx* ctx, const float* kernel, int kw, int koff, const float* dev_in, long long inImageStride, int inStride, int width, int height,
 						int batch, float* dev_out, long long outImageStride, int outStride) {
-	CHECK_CTX(ctx);
 	return convDev(ctx, true, false, kernel, kw, koff, dev_in, inImageStride, inStride, width, height, batch, dev_out, outImageStride, outStride);
 }
 int bhip_conv_norm_h_dev_f32(bhip_ctx* ctx, const float* kernel, int kw, int koff, const float* dev_in, long long inImageStride, int inStride, int width,
 							 int height, int batch, float* dev_out, long long outImageStride, int outStride) {
-	CHECK_CTX(ctx);
 	return convDev(ctx, false, true, kernel, kw, koff, dev_in, inImageStride, inStride, width, height, batch, dev_out, outImageStride, outStride);
 }
 int bhip_conv_norm_v_dev_f32(bhip_ctx* ctx, const float* kernel, int kw, int koff, const float* dev_in, long long inImageStride, int inStride, int width,
 							 int height, int batch, float* dev_out, long long outImageStride, int outStride) {
-	CHECK_CTX(ctx);
 	return convDev(ctx, true, true, kernel, kw, koff, dev_in, inImageStride, inStride, width, height, batch, dev_out, outImageStride, outStride);
 }
 
-// BlurImageOps.gaussian on a device batch: horizontal pass into the library's `storage`, vertical pass into dev_out
 int bhip_gaussian_dev_f32(bhip_ctx* ctx, const float* dev_in, long long inImageStride, int inStride, int width, int height, int batch, double sigma, int radius,
 						  float* dev_out, long long outImageStride, int outStride) {
 	CHECK_CTX(ctx);
-	CHECK_DEV_BATCH(ctx, dev_in, inStride, width, height, batch);
-	CHECK_DEV_BATCH(ctx, dev_out, outStride, width, height, batch);
+	CHECK_IMG(ctx, dev_in, inStride, width, height, batch);
+	CHECK_IMG(ctx, dev_out, outStride, width, height, batch);
 	if (sigma <= 0 && radius <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Sigma must be > 0");
-	std::vector<float> k = bhip_gaussian1d_f32(sigma, radius);
-	const int kw = (int)k.size(), koff = kw / 2;
-	CtxScratch* sc = scratchOf(ctx);
-	bool fused = false;
-	BHIP_TRY(bhip_launch_blur_fused(ctx, k.data(), kw, dev_in, inStride, width, height, dev_out, outStride, batch, inImageStride, outImageStride, &fused));
-	if (fused) return BHIP_OK;
-	const int pitch = pitch4(width);
-	const long long tmpImage = (long long)pitch * height;
-	BHIP_TRY(sc->ipTmp.reserve(ctx, (size_t)tmpImage * 4 * batch));
-	BHIP_TRY(bhip_launch_conv(ctx, false, true, k.data(), kw, koff, dev_in, inStride, width, height, sc->ipTmp.as<float>(), pitch, batch, inImageStride, tmpImage));
-	return bhip_launch_conv(ctx, true, true, k.data(), kw, koff, sc->ipTmp.as<float>(), pitch, width, height, dev_out, outStride, batch, tmpImage, outImageStride);
+	return gaussianImpl(ctx, sigma, radius, dev_in, inImageStride, inStride, width, height, batch, dev_out, outImageStride, outStride);
 }
 
-static int gradDev(bhip_ctx* ctx, int kind, const float* dev_in, long long inImageStride, int inStride, int width, int height, int batch, float* dev_dx,
-				   float* dev_dy, long long outImageStride, int outStride, int border) {
-	CHECK_DEV_BATCH(ctx, dev_in, inStride, width, height, batch);
-	CHECK_DEV_BATCH(ctx, dev_dx, outStride, width, height, batch);
-	CHECK_DEV_BATCH(ctx, dev_dy, outStride, width, height, batch);
-	if (border != 0 && border != 1) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "border policy not supported on the GPU");
-	return bhip_launch_gradient(ctx, kind, dev_in, inStride, width, height, dev_dx, dev_dy, outStride, border, batch, inImageStride, outImageStride);
-}
 int bhip_sobel_dev_f32(bhip_ctx* ctx, const float* dev_in, long long inImageStride, int inStride, int width, int height, int batch, float* dev_dx, float* dev_dy,
 					   long long outImageStride, int outStride, int border) {
-	CHECK_CTX(ctx);
 	return gradDev(ctx, 0, dev_in, inImageStride, inStride, width, height, batch, dev_dx, dev_dy, outImageStride, outStride, border);
 }
 int bhip_three_dev_f32(bhip_ctx* ctx, const float* dev_in, long long inImageStride, int inStride, int width, int height, int batch, float* dev_dx, float* dev_dy,
 					   long long outImageStride, int outStride, int border) {
-	CHECK_CTX(ctx);
+	return gradDev(ctx, 1, dev_in, inImageStride, inStride, width, height, batch, dev_dx, dev_dy, outImageStride, outStride, border);
+}
+int bhip_sobel_dev_u8_s16(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dev_dx,
+						  int16_t* dev_dy, long long outImageStride, int outStride, int border) {
+	return gradDev(ctx, 0, dev_in, inImageStride, inStride, width, height, batch, dev_dx, dev_dy, outImageStride, outStride, border);
+}
+int bhip_three_dev_u8_s16(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dev_dx,
+						  int16_t* dev_dy, long long outImageStride, int outStride, int border) {
 	return gradDev(ctx, 1, dev_in, inImageStride, inStride, width, height, batch, dev_dx, dev_dy, outImageStride, outStride, border);
 }
 
 int bhip_gradient_intensity_dev_f32(bhip_ctx* ctx, int kind, const float* dev_dx, const float* dev_dy, long long dImageStride, int dStride, int width, int height,
 									int batch, float* dev_out, long long outImageStride, int outStride) {
 	CHECK_CTX(ctx);
-	CHECK_DEV_BATCH(ctx, dev_dx, dStride, width, height, batch);
-	CHECK_DEV_BATCH(ctx, dev_dy, dStride, width, height, batch);
-	CHECK_DEV_BATCH(ctx, dev_out, outStride, width, height, batch);
+	CHECK_IMG(ctx, dev_dx, dStride, width, height, batch);
+	CHECK_IMG(ctx, dev_dy, dStride, width, height, batch);
+	CHECK_IMG(ctx, dev_out, outStride, width, height, batch);
 	return bhip_launch_grad_intensity(ctx, kind, dev_dx, dev_dy, dImageStride, dStride, dev_out, outImageStride, outStride, width, height, batch);
 }
 
 int bhip_corner_intensity_dev_f32(bhip_ctx* ctx, int kind, int radius, float kappa, const float* dev_dx, const float* dev_dy, long long dImageStride, int dStride,
 								  int width, int height, int batch, float* dev_intensity, long long iImageStride, int iStride) {
-	CHECK_CTX(ctx);
-	CHECK_DEV_BATCH(ctx, dev_dx, dStride, width, height, batch);
-	CHECK_DEV_BATCH(ctx, dev_dy, dStride, width, height, batch);
-	CHECK_DEV_BATCH(ctx, dev_intensity, iStride, width, height, batch);
-	CtxScratch* sc = scratchOf(ctx);
-	const size_t px = (size_t)width * height;
-	BHIP_TRY(sc->ipTmp.reserve(ctx, px * 4 * 3 * batch));
-	// ImageMiscOps.fillBorder(intensity, 0, radius): clear every image, the interior is overwritten
-	BHIP_HIP(ctx, hipMemset2DAsync(dev_intensity, (size_t)iStride * 4, 0, (size_t)width * 4, (size_t)height, ctx->stream));
-	for (int b = 1; b < batch; b++)
-		BHIP_HIP(ctx, hipMemset2DAsync(dev_intensity + (long long)b * iImageStride, (size_t)iStride * 4, 0, (size_t)width * 4, (size_t)height, ctx->stream));
-	float* h = sc->ipTmp.as<float>();
-	return bhip_launch_corner_intensity(ctx, kind, radius, kappa, dev_dx, dev_dy, dStride, width, height, h, h + px, h + 2 * px, dev_intensity, iStride, batch,
-										dImageStride, (long long)px * 3, iImageStride);
-}
-
-static int gradU8Dev(bhip_ctx* ctx, int kind, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dev_dx,
-					 int16_t* dev_dy, long long outImageStride, int outStride, int border) {
-	CHECK_DEV_BATCH(ctx, dev_in, inStride, width, height, batch);
-	CHECK_DEV_BATCH(ctx, dev_dx, outStride, width, height, batch);
-	CHECK_DEV_BATCH(ctx, dev_dy, outStride, width, height, batch);
-	if (border != 0 && border != 1) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "border policy not supported on the GPU");
-	return bhip_launch_gradient_u8(ctx, kind, dev_in, inImageStride, inStride, width, height, batch, dev_dx, dev_dy, outImageStride, outStride, border);
-}
-int bhip_sobel_dev_u8_s16(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dev_dx,
-						  int16_t* dev_dy, long long outImageStride, int outStride, int border) {
-	CHECK_CTX(ctx);
-	return gradU8Dev(ctx, 0, dev_in, inImageStride, inStride, width, height, batch, dev_dx, dev_dy, outImageStride, outStride, border);
-}
-int bhip_three_dev_u8_s16(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dev_dx,
-						  int16_t* dev_dy, long long outImageStride, int outStride, int border) {
-	CHECK_CTX(ctx);
-	return gradU8Dev(ctx, 1, dev_in, inImageStride, inStride, width, height, batch, dev_dx, dev_dy, outImageStride, outStride, border);
+	return cornerDev(ctx, false, false, kind, radius, kappa, dev_dx, dev_dy, dImageStride, dStride, width, height, batch, dev_intensity, iImageStride, iStride);
 }
 int bhip_corner_intensity_dev_s16(bhip_ctx* ctx, int kind, int radius, float kappa, int weighted, const int16_t* dev_dx, const int16_t* dev_dy,
 								  long long dImageStride, int dStride, int width, int height, int batch, float* dev_intensity, long long iImageStride, int iStride) {
-	CHECK_CTX(ctx);
-	CHECK_DEV_BATCH(ctx, dev_dx, dStride, width, height, batch);
-	CHECK_DEV_BATCH(ctx, dev_dy, dStride, width, height, batch);
-	CHECK_DEV_BATCH(ctx, dev_intensity, iStride, width, height, batch);
-	return cornerS16Dev(ctx, scratchOf(ctx)->ipTmp, kind, radius, kappa, weighted, dev_dx, dev_dy, dImageStride, dStride, width, height, batch, dev_intensity,
-						iImageStride, iStride);
+	return cornerDev(ctx, true, weighted != 0, kind, radius, kappa, dev_dx, dev_dy, dImageStride, dStride, width, height, batch, dev_intensity, iImageStride,
+					 iStride);
 }
 int bhip_corner_intensity_weighted_dev_f32(bhip_ctx* ctx, int kind, int radius, float kappa, const float* dev_dx, const float* dev_dy, long long dImageStride,
 										   int dStride, int width, int height, int batch, float* dev_intensity, long long iImageStride, int iStride) {
-	CHECK_CTX(ctx);
-	CHECK_DEV_BATCH(ctx, dev_dx, dStride, width, height, batch);
-	CHECK_DEV_BATCH(ctx, dev_dy, dStride, width, height, batch);
-	CHECK_DEV_BATCH(ctx, dev_intensity, iStride, width, height, batch);
-	return bhip_launch_corner_weighted(ctx, false, kind, radius, kappa, dev_dx, dev_dy, dImageStride, dStride, width, height, batch, dev_intensity, iImageStride,
-									   iStride);
+	return cornerDev(ctx, false, true, kind, radius, kappa, dev_dx, dev_dy, dImageStride, dStride, width, height, batch, dev_intensity, iImageStride, iStride);
 }
 
 // DescribePointBrief.process over a batch: the points of image b are dev_xy[start[b] .. start[b+1]) (host prefix `start`, batch+1 entries);
@@ -2047,7 +2008,7 @@ int bhip_corner_intensity_weighted_dev_f32(bhip_ctx* ctx, int kind, int radius, 
 int bhip_brief_dev_f32(bhip_ctx* ctx, const float* dev_img, long long imageStride, int stride, int width, int height, int batch, int radius, int numPoints,
 					   const int32_t* samplePoints, const int32_t* compare, const double* dev_xy, const int* start, int32_t* dev_out) {
 	CHECK_CTX(ctx);
-	CHECK_DEV_BATCH(ctx, dev_img, stride, width, height, batch);
+	CHECK_IMG(ctx, dev_img, stride, width, height, batch);
 	if (numPoints <= 0 || !samplePoints || !compare || !start) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad BRIEF arguments");
 	int maxCount = 0;
 	for (int b = 0; b < batch; b++) {
@@ -2059,19 +2020,9 @@ int bhip_brief_dev_f32(bhip_ctx* ctx, const float* dev_img, long long imageStrid
 	if (!dev_xy || !dev_out) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad BRIEF arguments");
 	int maxIdx = 0;
 	for (int i = 0; i < 2 * numPoints; i++) { if (compare[i] < 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "negative sample index"); maxIdx = std::max(maxIdx, compare[i]); }
-	CtxScratch* sc = scratchOf(ctx);
-	const size_t nSample = (size_t)(maxIdx + 1) * 2, nCompare = (size_t)numPoints * 2;
-	BHIP_TRY(sc->ipKernel.reserve(ctx, (nSample + nCompare + batch + 1) * 4));
-	int* dSample = sc->ipKernel.as<int>();
-	int* dCompare = dSample + nSample;
-	int* dStart = dCompare + nCompare;
-	BHIP_HIP(ctx, hipMemcpyAsync(dSample, samplePoints, nSample * 4, hipMemcpyHostToDevice, ctx->stream));
-	BHIP_HIP(ctx, hipMemcpyAsync(dCompare, compare, nCompare * 4, hipMemcpyHostToDevice, ctx->stream));
-	BHIP_HIP(ctx, hipMemcpyAsync(dStart, start, (size_t)(batch + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-	BHIP_TRY(bhip_launch_brief(ctx, dev_img, stride, width, height, radius, numPoints, dSample, dCompare, dev_xy, n, dev_out, false, batch, imageStride, dStart, maxCount, 2, 0,
-							   briefPatchOk(samplePoints, maxIdx + 1, radius)));
-	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the host tables were handed to async copies
-	return BHIP_OK;
+	BHIP_TRY(briefImpl(ctx, false, dev_img, imageStride, stride, width, height, batch, radius, numPoints, samplePoints, maxIdx + 1, compare, dev_xy, start, n,
+					   maxCount, dev_out));
+	return bhip_ctx_synchronize(ctx);   // the host tables were handed to async copies
 }
 
 }  // extern "C"
