@@ -33,6 +33,14 @@ class OriCfg(C.Structure):
                 ("weightSigma", C.c_double), ("sampleWidth", C.c_int)]
 
 
+class KltCfg(C.Structure):
+    _fields_ = [("forbiddenBorder", C.c_int), ("maxPerPixelError", C.c_float), ("maxIterations", C.c_int), ("minDeterminant", C.c_float),
+                ("minPositionDelta", C.c_float)]
+
+
+# KltTrackFault ordinals (+ the library's own code for positions where the reference throws)
+BHIP_KLT_SUCCESS, BHIP_KLT_DRIFTED, BHIP_KLT_OUT_OF_BOUNDS, BHIP_KLT_FAILED, BHIP_KLT_LARGE_ERROR, BHIP_KLT_REFERENCE_THROWS = range(6)
+
 P = C.POINTER
 _vp, _i, _f, _d, _ll = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_longlong
 _fp, _dp, _ip, _u8p, _i16p, _i32p, _llp = P(C.c_float), P(C.c_double), P(C.c_int), P(C.c_uint8), P(C.c_int16), P(C.c_int32), P(C.c_longlong)
@@ -130,6 +138,24 @@ SIGNATURES = {
     "bhip_corner_intensity_dev_s16": (_i, [_vp, _i, _i, _f, _i, _vp, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i]),
     "bhip_corner_intensity_weighted_dev_f32": (_i, [_vp, _i, _i, _f, _vp, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i]),
     "bhip_brief_dev_f32": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _i32p, _i32p, _vp, _ip, _vp]),
+    "bhip_klt_cfg_default": (None, [P(KltCfg)]),
+    "bhip_klt_create": (_i, [_vp, P(KltCfg), _i, _ip, _i, _i, _f, _i, _i, _i, _i, P(_vp)]),
+    "bhip_klt_destroy": (_i, [_vp]),
+    "bhip_klt_process_dev_f32": (_i, [_vp, _vp, _ll, _i]),
+    "bhip_klt_process_f32": (_i, [_vp, P(_fp), _ip, _ip]),
+    "bhip_klt_spawn": (_i, [_vp, _i]),
+    "bhip_klt_spawn_points": (_i, [_vp, _i16p, _ip, _i]),
+    "bhip_klt_add_tracks": (_i, [_vp, _ip, _dp, _i, _u8p]),
+    "bhip_klt_drop_tracks": (_i, [_vp, _ip, _llp, _i, _u8p]),
+    "bhip_klt_drop_all": (_i, [_vp]),
+    "bhip_klt_reset": (_i, [_vp]),
+    "bhip_klt_counts": (_i, [_vp, _ip, _ip, _ip]),
+    "bhip_klt_fetch": (_i, [_vp, _i, _i, _llp, _fp, _ip, _fp]),
+    "bhip_klt_stats": (_i, [_vp, _llp, _llp, _llp]),
+    "bhip_klt_fetch_layer": (_i, [_vp, _i, _i, _i, _fp]),
+    "bhip_klt_dev_view": (_i, [_vp, P(_vp), P(_vp), P(_vp), P(_vp), P(_vp), P(_vp), P(_vp), P(_vp), _ip, _llp]),
+    "bhip_klt_set_description_f32": (_i, [_vp, P(KltCfg), _i, _fp, _i, _i, _fp, _fp, _i, _i, _i, _i, _fp, _i, _fp, _fp, _fp, _fp, _u8p]),
+    "bhip_klt_track_f32": (_i, [_vp, P(KltCfg), _i, _fp, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _i, _ip, _fp]),
 }
 
 _lib = None

@@ -62,6 +62,7 @@ struct HandleRegistry {
 	std::mutex m;
 	std::unordered_set<bhip_ctx*> ctxs;
 	std::unordered_set<bhip_surf*> surfs;
+	std::unordered_set<bhip_klt*> klts;
 	std::atomic<bool> exiting{false};
 };
 static HandleRegistry& registry() {
@@ -73,6 +74,7 @@ static HandleRegistry& registry() {
 	return *r;
 }
 static void surfOrphanChildren(bhip_ctx* ctx);   // registry lock held: releases the device side of every live bhip_surf created on ctx
+static void kltOrphanChildren(bhip_ctx* ctx);    // the same for every live bhip_klt
 
 extern "C" {
 
@@ -81,6 +83,9 @@ const char* bhip_version(void) { return "boofhip 0.1 (gfx950)"; }
 void bhip_fh_cfg_default(bhip_fh_cfg* c) {
 	c->detectThreshold = 1; c->extractRadius = 2; c->maxFeaturesPerScale = -1; c->initialSampleSize = 1; c->initialSize = 9;
 	c->numberScalesPerOctave = 4; c->numberOfOctaves = 4; c->scaleStepSize = 6;
+}
+void bhip_klt_cfg_default(bhip_klt_cfg* c) {
+	c->forbiddenBorder = 0; c->maxPerPixelError = 25; c->maxIterations = 15; c->minDeterminant = 0.001f; c->minPositionDelta = 0.01f;
 }
 void bhip_surf_cfg_default(bhip_surf_cfg* c) {
 	c->widthLargeGrid = 4; c->widthSubRegion = 5; c->widthSample = 3; c->weightSigma = 4.5; c->overLap = 2; c->sigmaLargeGrid = 2.5;
@@ -130,6 +135,7 @@ int bhip_ctx_destroy(bhip_ctx* c) {
 	(void)hipStreamSynchronize(c->stream);
 	// detect+describe objects still alive on this context lose their device side now and become inert shells
 	surfOrphanChildren(c);
+	kltOrphanChildren(c);
 	delete static_cast<bhip_ctx_full*>(c);   // scratch, profiling events, staging block, then the stream it owns
 	return BHIP_OK;
 }
@@ -1538,7 +1544,8 @@ static int gradHost(bhip_ctx* ctx, int kind, const TI* in, int inStart, int inSt
 	CHECK_IMG(ctx, in, inStride, width, height, 1);
 	CHECK_IMG(ctx, dx, outStride, width, height, 1);
 	CHECK_IMG(ctx, dy, outStride, width, height, 1);
-	if (border != 0 && border != 1) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "border policy not supported on the GPU");
+	if (border != 0 && border != 1 && !(border == 2 && kind == 0 && sizeof(TI) == 4))   // 2 = BorderType.EXTENDED: GradientSobel on GrayF32 only
+		return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "border policy not supported on the GPU");
 	CtxScratch* sc = scratchOf(ctx);
 	const int pitch = sizeof(TI) == 4 ? pitch4(width) : width;
 	const long long img = (long long)pitch * height;
@@ -1562,7 +1569,8 @@ static int gradDev(bhip_ctx* ctx, int kind, const TI* dev_in, long long inImageS
 	CHECK_IMG(ctx, dev_in, inStride, width, height, batch);
 	CHECK_IMG(ctx, dev_dx, outStride, width, height, batch);
 	CHECK_IMG(ctx, dev_dy, outStride, width, height, batch);
-	if (border != 0 && border != 1) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "border policy not supported on the GPU");
+	if (border != 0 && border != 1 && !(border == 2 && kind == 0 && sizeof(TI) == 4))   // 2 = BorderType.EXTENDED: GradientSobel on GrayF32 only
+		return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "border policy not supported on the GPU");
 	return gradImpl(ctx, kind, dev_in, inImageStride, inStride, width, height, batch, dev_dx, dev_dy, outImageStride, outStride, border);
 }
 
@@ -2023,6 +2031,515 @@ int bhip_brief_dev_f32(bhip_ctx* ctx, const float* dev_img, long long imageStrid
 	BHIP_TRY(briefImpl(ctx, false, dev_img, imageStride, stride, width, height, batch, radius, numPoints, samplePoints, maxIdx + 1, compare, dev_xy, start, n,
 					   maxCount, dev_out));
 	return bhip_ctx_synchronize(ctx);   // the host tables were handed to async copies
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------
+// Pyramid KLT point tracker (kernels: klt.hip)
+// ---------------------------------------------------------------------------------------------------------------
+// The track table: every per-track array of KltTab carved out of one device block, the per-sequence counters out of another (they do not
+// depend on the capacity, so a regrown table keeps them).
+namespace {
+struct KltArr { size_t elem; int outer; size_t inner; };   // [outer][batch][cap * inner] elements of `elem` bytes
+enum { KA_ACT, KA_DRP, KA_SPW, KA_FREE, KA_ID, KA_X, KA_Y, KA_TX, KA_TY, KA_ERR, KA_FAULT, KA_KEEP, KA_ITERS, KA_LX, KA_LY, KA_GXX, KA_GXY, KA_GYY, KA_TMPL, KA_N };
+
+struct KltTable {
+	DevBuf buf, cnt;
+	KltTab v{};
+	KltArr arr[KA_N];
+	size_t off[KA_N + 1];
+
+	int alloc(bhip_ctx* ctx, int batch, int cap, int L, int r, DevBuf* keepCnt = nullptr) {
+		const int len = (2 * r + 1) * (2 * r + 1);
+		for (int i = 0; i < KA_N; i++) arr[i] = KltArr{4, 1, 1};
+		arr[KA_ID].elem = 8;
+		for (int i = KA_LX; i <= KA_GYY; i++) arr[i].outer = L;
+		arr[KA_TMPL].inner = (size_t)L * 3 * len;
+		off[0] = 0;
+		for (int i = 0; i < KA_N; i++) off[i + 1] = off[i] + ((arr[i].elem * arr[i].outer * batch * cap * arr[i].inner + 15) & ~(size_t)15);
+		BHIP_TRY(buf.reserve(ctx, off[KA_N]));
+		BHIP_HIP(ctx, hipMemsetAsync(buf.p, 0, off[KA_N], ctx->stream));
+		if (keepCnt) cnt = std::move(*keepCnt);
+		else {
+			BHIP_TRY(cnt.reserve(ctx, (size_t)batch * 24));
+			BHIP_HIP(ctx, hipMemsetAsync(cnt.p, 0, (size_t)batch * 24, ctx->stream));
+		}
+		char* p = (char*)buf.p;
+		v.cap = cap; v.batch = batch; v.L = L; v.r = r; v.len = len;
+		v.act = (int*)(p + off[KA_ACT]); v.drp = (int*)(p + off[KA_DRP]); v.spw = (int*)(p + off[KA_SPW]); v.freeL = (int*)(p + off[KA_FREE]);
+		v.id = (long long*)(p + off[KA_ID]);
+		v.x = (float*)(p + off[KA_X]); v.y = (float*)(p + off[KA_Y]); v.tx = (float*)(p + off[KA_TX]); v.ty = (float*)(p + off[KA_TY]);
+		v.err = (float*)(p + off[KA_ERR]); v.fault = (int*)(p + off[KA_FAULT]); v.keep = (int*)(p + off[KA_KEEP]); v.iters = (int*)(p + off[KA_ITERS]);
+		v.lx = (float*)(p + off[KA_LX]); v.ly = (float*)(p + off[KA_LY]); v.gxx = (float*)(p + off[KA_GXX]); v.gxy = (float*)(p + off[KA_GXY]);
+		v.gyy = (float*)(p + off[KA_GYY]); v.tmpl = (float*)(p + off[KA_TMPL]);
+		v.total = (long long*)cnt.p;
+		v.nAct = (int*)((char*)cnt.p + (size_t)batch * 8);
+		v.nDrp = v.nAct + batch; v.nSpw = v.nDrp + batch; v.nFree = v.nSpw + batch;
+		return BHIP_OK;
+	}
+};
+}  // namespace
+
+// everything a tracker holds on its context's device; dropped as a whole like SurfDevice
+struct KltDevice {
+	KltTable tab;
+	DevBuf frames, pyr, dx, dy, intensity, candXY, candN, stage;
+	PinnedBuf pinned;
+};
+
+struct bhip_klt : KltDevice {
+	bhip_ctx* ctx = nullptr;
+	bhip_klt_cfg cfg;
+	int r = 0, L = 0, W = 0, H = 0, batch = 0;
+	int scales[BHIP_KLT_MAX_LAYERS];
+	int dims[2 * BHIP_KLT_MAX_LAYERS];
+	long long offs[BHIP_KLT_MAX_LAYERS], total = 0;
+	int detectRadius = 0, detectBorder = 0;
+	float detectThreshold = 0;
+	std::vector<float> kernel;   // FactoryPyramid.discreteGaussian(scales, -1, 2)
+	bool haveFrame = false;
+	int ub = 0;                  // no sequence has more active tracks than this (exact after a spawn or bhip_klt_counts)
+	KltPyr view() const {
+		KltPyr P{};
+		P.img = pyr.as<float>(); P.dx = dx.as<float>(); P.dy = dy.as<float>();
+		P.frameStride = total;
+		for (int l = 0; l < L; l++) { P.off[l] = offs[l]; P.w[l] = dims[2 * l]; P.h[l] = dims[2 * l + 1]; P.stride[l] = dims[2 * l]; P.scale[l] = (float)(double)scales[l]; }
+		P.numLayers = L; P.frameW = W; P.frameH = H;
+		return P;
+	}
+};
+
+static void kltReleaseDevice(bhip_klt* k) {
+	if (!k->ctx) return;
+	(void)hipSetDevice(k->ctx->device);
+	(void)hipStreamSynchronize(k->ctx->stream);
+	static_cast<KltDevice&>(*k) = KltDevice();
+	k->haveFrame = false;
+	k->ctx = nullptr;
+}
+static void kltOrphanChildren(bhip_ctx* ctx) {
+	for (bhip_klt* k : registry().klts)
+		if (k->ctx == ctx) kltReleaseDevice(k);
+}
+
+static bool kltRangeOk(int radius, int numLayers) { return radius >= 1 && radius <= BHIP_KLT_MAX_RADIUS && numLayers >= 1 && numLayers <= BHIP_KLT_MAX_LAYERS; }
+
+// the table regrows like the other device lists: a larger block, the old contents copied array by array, the new slots appended to every
+// sequence's unused list
+static int kltGrow(bhip_klt* k, int newCap) {
+	bhip_ctx* ctx = k->ctx;
+	KltTable nt;
+	const KltTable& ot = k->tab;
+	const int oldCap = ot.v.cap;
+	if (nt.alloc(ctx, k->batch, newCap, k->L, k->r, &k->tab.cnt) != BHIP_OK) {
+		if (nt.cnt.p) k->tab.cnt = std::move(nt.cnt);
+		return bhip_fail(ctx, BHIP_ERR_CAPACITY, "the track table could not grow");
+	}
+	for (int i = 0; i < KA_N; i++) {
+		const size_t oldRow = ot.arr[i].elem * ot.arr[i].inner * oldCap, newRow = nt.arr[i].elem * nt.arr[i].inner * newCap;
+		BHIP_HIP(ctx, hipMemcpy2DAsync((char*)nt.buf.p + nt.off[i], newRow, (const char*)ot.buf.p + ot.off[i], oldRow, oldRow,
+									   (size_t)ot.arr[i].outer * k->batch, hipMemcpyDeviceToDevice, ctx->stream));
+	}
+	BHIP_TRY(bhip_launch_klt_init(ctx, nt.v, oldCap));
+	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	k->tab = std::move(nt);
+	return BHIP_OK;
+}
+
+// counters of every sequence to the host: [nAct | nDrp | nSpw | nFree][batch] ints
+static int kltReadCounts(bhip_klt* k, const int** out) {
+	bhip_ctx* ctx = k->ctx;
+	BHIP_TRY(k->pinned.reserve(ctx, (size_t)k->batch * 32));
+	BHIP_HIP(ctx, hipMemcpyAsync(k->pinned.p, k->tab.v.nAct, (size_t)k->batch * 16, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	*out = k->pinned.as<int>();
+	return BHIP_OK;
+}
+
+static int kltProcess(bhip_klt* k, const float* dev_frames, long long imageStride, int stride) {
+	bhip_ctx* ctx = k->ctx;
+	BHIP_TRY(bhip_pyramid_dev_f32(ctx, k->kernel.data(), (int)k->kernel.size(), k->scales, k->L, dev_frames, imageStride, stride, k->W, k->H, k->batch,
+								  k->pyr.as<float>()));
+	for (int l = 0; l < k->L; l++)   // PyramidOps.gradient with FactoryDerivative.sobel: BorderType.EXTENDED
+		BHIP_TRY(bhip_launch_gradient(ctx, 0, k->pyr.as<float>() + k->offs[l], k->dims[2 * l], k->dims[2 * l], k->dims[2 * l + 1], k->dx.as<float>() + k->offs[l],
+									  k->dy.as<float>() + k->offs[l], k->dims[2 * l], 2, k->batch, k->total, k->total));
+	k->haveFrame = true;
+	const KltPyr P = k->view();
+	BHIP_TRY(bhip_launch_klt_begin(ctx, k->tab.v));
+	BHIP_TRY(bhip_launch_klt_track(ctx, P, k->tab.v, k->cfg, k->ub));
+	BHIP_TRY(bhip_launch_klt_describe(ctx, P, k->tab.v, k->cfg, 0, nullptr, k->ub));
+	return bhip_launch_klt_compact(ctx, k->tab.v, 0);
+}
+
+// spawnTracks from candidate lists on the device (dev_xy [batch][xyCap] (x,y) int16 pairs in layer-0 pixels, dev_n [batch], each <= xyCap)
+static int kltSpawnFrom(bhip_klt* k, const int16_t* dev_xy, int xyCap, const int* dev_n) {
+	bhip_ctx* ctx = k->ctx;
+	BHIP_TRY(k->pinned.reserve(ctx, (size_t)k->batch * 32));
+	int* h = k->pinned.as<int>();
+	BHIP_HIP(ctx, hipMemcpyAsync(h, k->tab.v.nAct, (size_t)k->batch * 16, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(h + 4 * k->batch, dev_n, (size_t)k->batch * 4, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	const int B = k->batch;
+	int need = 0, maxCand = 0, ub = 0;
+	for (int b = 0; b < B; b++) {
+		const int c = h[4 * B + b];
+		if (c > xyCap) return bhip_fail(ctx, BHIP_ERR_CAPACITY, "candidate list overflowed");
+		need = std::max(need, c - h[3 * B + b]);
+		maxCand = std::max(maxCand, c);
+		ub = std::max(ub, h[b] + c);
+	}
+	if (need > 0) BHIP_TRY(kltGrow(k, (k->tab.v.cap + std::max(need, k->tab.v.cap / 2) + 255) & ~255));
+	const float scale0 = (float)(double)k->scales[0];
+	BHIP_TRY(bhip_launch_klt_spawn_place(ctx, k->tab.v, dev_xy, xyCap, dev_n, scale0, maxCand));
+	BHIP_TRY(bhip_launch_klt_describe(ctx, k->view(), k->tab.v, k->cfg, 1, dev_n, maxCand));
+	BHIP_TRY(bhip_launch_klt_spawn_commit(ctx, k->tab.v, dev_n));
+	k->ub = std::max(k->ub, ub);
+	return BHIP_OK;
+}
+
+#define CHECK_KLT(k)                    \
+	if (!(k)) return BHIP_ERR_INVALID;  \
+	bhip_ctx* ctx = (k)->ctx;           \
+	CHECK_CTX(ctx)
+
+// a one-layer, one-sequence table for the stage-level calls: n tracks at xy, all active
+static int kltStageTable(bhip_ctx* ctx, KltTable& tab, int radius, const float* xy, int n) {
+	BHIP_TRY(tab.alloc(ctx, 1, std::max(n, 1), 1, radius));
+	BHIP_TRY(bhip_launch_klt_init(ctx, tab.v, 0));
+	std::vector<int> act(n);
+	std::vector<float> x(n), y(n);
+	for (int i = 0; i < n; i++) { act[i] = i; x[i] = xy[2 * i]; y[i] = xy[2 * i + 1]; }
+	BHIP_HIP(ctx, hipMemcpyAsync(tab.v.act, act.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(tab.v.x, x.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(tab.v.y, y.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(tab.v.nAct, &n, 4, hipMemcpyHostToDevice, ctx->stream));
+	return bhip_ctx_synchronize(ctx);   // the host vectors leave scope
+}
+static KltPyr kltStagePyr(const float* img, const float* dx, const float* dy, int width, int height) {
+	KltPyr P{};
+	P.img = img; P.dx = dx; P.dy = dy;
+	P.w[0] = width; P.h[0] = height; P.stride[0] = width; P.scale[0] = 1.0f;
+	P.numLayers = 1; P.frameW = width; P.frameH = height;
+	return P;
+}
+
+extern "C" {
+
+int bhip_klt_create(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int templateRadius, const int* scales, int numLayers, int detectRadius, float detectThreshold,
+					int detectBorder, int width, int height, int batch, bhip_klt** out) {
+	if (out) *out = nullptr;
+	if (!kltRangeOk(templateRadius, numLayers)) return BHIP_ERR_UNSUPPORTED;   // templateRadius 1..7, numLayers 1..8; nothing is touched, not even ctx
+	HandleRegistry& R = registry();
+	std::lock_guard<std::mutex> lock(R.m);
+	if (!ctx || !R.ctxs.count(ctx)) return BHIP_ERR_INVALID;
+	if (!out) return bhip_fail(ctx, BHIP_ERR_INVALID, "null output");
+	if (cfg && cfg->maxIterations < 1) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "maxIterations must be >= 1");
+	if (!scales || width <= 0 || height <= 0 || batch <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad tracker arguments");
+	CHECK_CTX(ctx);
+	std::unique_ptr<bhip_klt> k(new (std::nothrow) bhip_klt());
+	if (!k) return bhip_fail(ctx, BHIP_ERR_NOMEM, "out of host memory");
+	k->ctx = ctx;
+	if (cfg) k->cfg = *cfg; else bhip_klt_cfg_default(&k->cfg);
+	k->r = templateRadius; k->L = numLayers; k->W = width; k->H = height; k->batch = batch;
+	k->detectRadius = detectRadius; k->detectThreshold = detectThreshold; k->detectBorder = detectBorder;
+	for (int l = 0; l < numLayers; l++) k->scales[l] = scales[l];
+	if (bhip_pyramid_layout(width, height, scales, numLayers, k->dims, k->offs, &k->total) != BHIP_OK) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad pyramid scales");
+	for (int l = 1; l < numLayers; l++)
+		if (scales[l] / scales[l - 1] <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Skip must be >= 1");
+	k->kernel = bhip_gaussian1d_f32(-1, 2);
+	const size_t bytes = (size_t)k->total * batch * 4;
+	BHIP_TRY(k->pyr.reserve(ctx, bytes));
+	BHIP_TRY(k->dx.reserve(ctx, bytes));
+	BHIP_TRY(k->dy.reserve(ctx, bytes));
+	BHIP_TRY(k->tab.alloc(ctx, batch, 1024, numLayers, templateRadius));
+	BHIP_TRY(bhip_launch_klt_init(ctx, k->tab.v, 0));
+	BHIP_TRY(bhip_ctx_synchronize(ctx));
+	R.klts.insert(k.get());
+	*out = k.release();
+	return BHIP_OK;
+}
+
+int bhip_klt_destroy(bhip_klt* k) {
+	if (!k) return BHIP_OK;
+	HandleRegistry& R = registry();
+	std::lock_guard<std::mutex> lock(R.m);
+	if (R.exiting) return BHIP_OK;
+	if (!R.klts.count(k)) return BHIP_ERR_INVALID;
+	R.klts.erase(k);
+	kltReleaseDevice(k);
+	delete k;
+	return BHIP_OK;
+}
+
+int bhip_klt_process_dev_f32(bhip_klt* k, const float* dev_frames, long long imageStride, int stride) {
+	CHECK_KLT(k);
+	if (!dev_frames || stride < k->W) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image batch");
+	return kltProcess(k, dev_frames, imageStride, stride);
+}
+
+int bhip_klt_process_f32(bhip_klt* k, const float* const* img, const int* startIndex, const int* stride) {
+	CHECK_KLT(k);
+	if (!img) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image batch");
+	const long long px = (long long)k->W * k->H;
+	BHIP_TRY(k->frames.reserve(ctx, (size_t)px * 4 * k->batch));
+	for (int b = 0; b < k->batch; b++) {
+		if (!img[b] || (stride ? stride[b] : k->W) < k->W) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image (null or stride < width)");
+		BHIP_TRY(upload(ctx, k->frames.as<float>() + b * px, k->W, img[b], startIndex ? startIndex[b] : 0, stride ? stride[b] : k->W, k->W, k->H, ctx->stream));
+	}
+	BHIP_TRY(kltProcess(k, k->frames.as<float>(), px, k->W));
+	return bhip_ctx_synchronize(ctx);   // the caller's frames have been consumed
+}
+
+int bhip_klt_spawn(bhip_klt* k, int maxFeatures) {
+	CHECK_KLT(k);
+	if (!k->haveFrame) return bhip_fail(ctx, BHIP_ERR_INVALID, "spawnTracks before the first process()");
+	if (maxFeatures > 0) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "maxFeatures > 0 (SelectNBestFeatures) is a host call: use bhip_klt_spawn_points");
+	const int w0 = k->dims[0], h0 = k->dims[1];
+	const long long px = (long long)w0 * h0;
+	BHIP_TRY(k->intensity.reserve(ctx, (size_t)px * 4 * k->batch));
+	float* inten = k->intensity.as<float>();
+	BHIP_TRY(cornerImpl(ctx, false, false, 0, 1, 0.0f, k->dx.as<float>() + k->offs[0], k->dy.as<float>() + k->offs[0], k->total, w0, w0, h0, k->batch, inten, px, w0));
+	BHIP_TRY(bhip_launch_klt_mark_exclude(ctx, k->tab.v, (float)(double)k->scales[0], inten, px, w0, w0, h0, k->ub));
+	const int step = k->detectRadius + 1;
+	const int rw = std::max(w0 - 2 * k->detectBorder, 0), rh = std::max(h0 - 2 * k->detectBorder, 0);
+	const int cap = step > 0 ? std::max(1, ((rw + step - 1) / step) * ((rh + step - 1) / step)) : 1;   // one maximum per block at most
+	BHIP_TRY(k->candXY.reserve(ctx, (size_t)cap * 4 * k->batch));
+	BHIP_TRY(k->candN.reserve(ctx, (size_t)k->batch * 4));
+	BHIP_TRY(nonmaxDevice(ctx, inten, px, w0, w0, h0, k->batch, k->detectRadius, k->detectThreshold, k->detectBorder, k->candXY.as<int16_t>(), cap,
+						  k->candN.as<int>()));
+	return kltSpawnFrom(k, k->candXY.as<int16_t>(), cap, k->candN.as<int>());
+}
+
+int bhip_klt_spawn_points(bhip_klt* k, const int16_t* xy, const int* count, int capacity) {
+	CHECK_KLT(k);
+	if (!k->haveFrame) return bhip_fail(ctx, BHIP_ERR_INVALID, "spawnTracks before the first process()");
+	if (!count || capacity < 0 || (capacity > 0 && !xy)) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad candidate lists");
+	for (int b = 0; b < k->batch; b++)
+		if (count[b] < 0 || count[b] > capacity) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad candidate count");
+	BHIP_TRY(k->candXY.reserve(ctx, (size_t)std::max(capacity, 1) * 4 * k->batch));
+	BHIP_TRY(k->candN.reserve(ctx, (size_t)k->batch * 4));
+	if (capacity > 0) BHIP_HIP(ctx, hipMemcpyAsync(k->candXY.p, xy, (size_t)capacity * 4 * k->batch, hipMemcpyHostToDevice, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(k->candN.p, count, (size_t)k->batch * 4, hipMemcpyHostToDevice, ctx->stream));
+	BHIP_TRY(kltSpawnFrom(k, k->candXY.as<int16_t>(), std::max(capacity, 1), k->candN.as<int>()));
+	return bhip_ctx_synchronize(ctx);
+}
+
+int bhip_klt_add_tracks(bhip_klt* k, const int* seq, const double* xy, int n, uint8_t* ok) {
+	CHECK_KLT(k);
+	if (!k->haveFrame) return bhip_fail(ctx, BHIP_ERR_INVALID, "addTrack before the first process()");
+	if (n < 0 || (n > 0 && (!seq || !xy || !ok))) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad track list");
+	if (n == 0) return BHIP_OK;
+	const int* h = nullptr;
+	BHIP_TRY(kltReadCounts(k, &h));
+	std::vector<int> want(k->batch, 0);
+	int need = 0;
+	for (int i = 0; i < n; i++)
+		if (seq[i] >= 0 && seq[i] < k->batch) need = std::max(need, ++want[seq[i]] - h[3 * k->batch + seq[i]]);
+	if (need > 0) BHIP_TRY(kltGrow(k, (k->tab.v.cap + std::max(need, k->tab.v.cap / 2) + 255) & ~255));
+	// stage: [xy 16n | seq 4n | list 4n | ok n]
+	BHIP_TRY(k->stage.reserve(ctx, (size_t)n * 25 + 16));
+	char* st = (char*)k->stage.p;
+	double* dxy = (double*)st;
+	int* dseq = (int*)(st + (size_t)n * 16);
+	int* dlist = dseq + n;
+	unsigned char* dok = (unsigned char*)(dlist + n);
+	BHIP_HIP(ctx, hipMemcpyAsync(dxy, xy, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(dseq, seq, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+	BHIP_TRY(bhip_launch_klt_add(ctx, k->tab.v, dseq, dxy, n, k->W, k->H, dok, dlist));
+	BHIP_TRY(bhip_launch_klt_describe(ctx, k->view(), k->tab.v, k->cfg, 3, dlist, n));   // tracker.setDescription(t): the result is not looked at
+	BHIP_HIP(ctx, hipMemcpyAsync(ok, dok, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+	k->ub += *std::max_element(want.begin(), want.end());
+	return bhip_ctx_synchronize(ctx);
+}
+
+int bhip_klt_drop_tracks(bhip_klt* k, const int* seq, const long long* featureId, int n, uint8_t* ok) {
+	CHECK_KLT(k);
+	if (n < 0 || (n > 0 && (!seq || !featureId))) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad track list");
+	if (n == 0) return BHIP_OK;
+	// stage: [featureId 8n | seq 4n | ok n]
+	BHIP_TRY(k->stage.reserve(ctx, (size_t)n * 13 + 16));
+	char* st = (char*)k->stage.p;
+	long long* did = (long long*)st;
+	int* dseq = (int*)(st + (size_t)n * 8);
+	unsigned char* dok = (unsigned char*)(dseq + n);
+	BHIP_HIP(ctx, hipMemcpyAsync(did, featureId, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(dseq, seq, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+	BHIP_TRY(bhip_launch_klt_match_drop(ctx, k->tab.v, dseq, did, n, dok, k->ub));
+	BHIP_TRY(bhip_launch_klt_compact(ctx, k->tab.v, 1));
+	if (ok) BHIP_HIP(ctx, hipMemcpyAsync(ok, dok, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
+}
+
+int bhip_klt_drop_all(bhip_klt* k) {
+	CHECK_KLT(k);
+	k->ub = 0;
+	return bhip_launch_klt_drop_all(ctx, k->tab.v, 0);
+}
+
+int bhip_klt_reset(bhip_klt* k) {
+	CHECK_KLT(k);
+	k->ub = 0;
+	return bhip_launch_klt_drop_all(ctx, k->tab.v, 1);
+}
+
+int bhip_klt_counts(bhip_klt* k, int* active, int* spawned, int* dropped) {
+	CHECK_KLT(k);
+	const int* h = nullptr;
+	BHIP_TRY(kltReadCounts(k, &h));
+	const int B = k->batch;
+	k->ub = 0;
+	for (int b = 0; b < B; b++) {
+		k->ub = std::max(k->ub, h[b]);
+		if (active) active[b] = h[b];
+		if (dropped) dropped[b] = h[B + b];
+		if (spawned) spawned[b] = h[2 * B + b];
+	}
+	return BHIP_OK;
+}
+
+int bhip_klt_fetch(bhip_klt* k, int which, int seq, long long* featureId, float* xy, int* fault, float* error) {
+	CHECK_KLT(k);
+	if (which < 0 || which > 2 || seq < 0 || seq >= k->batch) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad list selector");
+	const int* h = nullptr;
+	BHIP_TRY(kltReadCounts(k, &h));
+	const int n = h[(which == 0 ? 0 : which == 1 ? 2 : 1) * k->batch + seq];
+	if (n == 0) return BHIP_OK;
+	// stage: [featureId 8n | xy 8n | fault 4n | error 4n]
+	BHIP_TRY(k->stage.reserve(ctx, (size_t)n * 24));
+	char* st = (char*)k->stage.p;
+	long long* did = (long long*)st;
+	float* dxy = (float*)(st + (size_t)n * 8);
+	int* df = (int*)(st + (size_t)n * 16);
+	float* de = (float*)(st + (size_t)n * 20);
+	BHIP_TRY(bhip_launch_klt_gather(ctx, k->tab.v, which, seq, n, did, dxy, df, de));
+	if (featureId) BHIP_HIP(ctx, hipMemcpyAsync(featureId, did, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+	if (xy) BHIP_HIP(ctx, hipMemcpyAsync(xy, dxy, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+	if (fault) BHIP_HIP(ctx, hipMemcpyAsync(fault, df, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+	if (error) BHIP_HIP(ctx, hipMemcpyAsync(error, de, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
+}
+
+int bhip_klt_stats(bhip_klt* k, long long* tracks, long long* iterations, long long* borderIterations) {
+	CHECK_KLT(k);
+	BHIP_TRY(k->stage.reserve(ctx, 32));
+	BHIP_TRY(k->pinned.reserve(ctx, (size_t)k->batch * 32));
+	BHIP_HIP(ctx, hipMemsetAsync(k->stage.p, 0, 24, ctx->stream));
+	BHIP_TRY(bhip_launch_klt_stats(ctx, k->tab.v, k->stage.as<unsigned long long>()));
+	BHIP_HIP(ctx, hipMemcpyAsync(k->pinned.p, k->stage.p, 24, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	const long long* h = k->pinned.as<long long>();
+	if (tracks) *tracks = h[0];
+	if (iterations) *iterations = h[1];
+	if (borderIterations) *borderIterations = h[2];
+	return BHIP_OK;
+}
+
+int bhip_klt_fetch_layer(bhip_klt* k, int seq, int layer, int which, float* out) {
+	CHECK_KLT(k);
+	if (!k->haveFrame) return bhip_fail(ctx, BHIP_ERR_INVALID, "no frame processed");
+	if (seq < 0 || seq >= k->batch || layer < 0 || layer >= k->L || which < 0 || which > 2 || !out) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad layer selector");
+	const float* src = (which == 0 ? k->pyr : which == 1 ? k->dx : k->dy).as<float>() + (long long)seq * k->total + k->offs[layer];
+	BHIP_HIP(ctx, hipMemcpyAsync(out, src, (size_t)k->dims[2 * layer] * k->dims[2 * layer + 1] * 4, hipMemcpyDeviceToHost, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
+}
+
+int bhip_klt_dev_view(bhip_klt* k, const int** dev_activeSlots, const int** dev_activeCount, const float** dev_x, const float** dev_y,
+					  const long long** dev_featureId, const float** dev_pyramid, const float** dev_derivX, const float** dev_derivY, int* slotsPerSequence,
+					  long long* floatsPerFrame) {
+	CHECK_KLT(k);
+	const KltTab& T = k->tab.v;
+	if (dev_activeSlots) *dev_activeSlots = T.act;
+	if (dev_activeCount) *dev_activeCount = T.nAct;
+	if (dev_x) *dev_x = T.x;
+	if (dev_y) *dev_y = T.y;
+	if (dev_featureId) *dev_featureId = T.id;
+	if (dev_pyramid) *dev_pyramid = k->pyr.as<float>();
+	if (dev_derivX) *dev_derivX = k->dx.as<float>();
+	if (dev_derivY) *dev_derivY = k->dy.as<float>();
+	if (slotsPerSequence) *slotsPerSequence = T.cap;
+	if (floatsPerFrame) *floatsPerFrame = k->total;
+	return BHIP_OK;
+}
+
+int bhip_klt_set_description_f32(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const float* image, int imgStart, int imgStride, const float* derivX,
+								 const float* derivY, int dStart, int dStride, int width, int height, const float* xy, int n, float* desc, float* descX,
+								 float* descY, float* G, uint8_t* ok) {
+	if (!kltRangeOk(radius, 1)) return BHIP_ERR_UNSUPPORTED;   // templateRadius 1..7; nothing is written
+	CHECK_CTX(ctx);
+	CHECK_IMG(ctx, image, imgStride, width, height, 1);
+	CHECK_IMG(ctx, derivX, dStride, width, height, 1);
+	CHECK_IMG(ctx, derivY, dStride, width, height, 1);
+	if (n < 0 || (n > 0 && (!xy || !desc || !descX || !descY || !G || !ok))) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad feature list");
+	if (n == 0) return BHIP_OK;
+	bhip_klt_cfg c;
+	if (cfg) c = *cfg; else bhip_klt_cfg_default(&c);
+	CtxScratch* sc = scratchOf(ctx);
+	const size_t bytes = (size_t)width * height * 4;
+	BHIP_TRY(sc->in0.reserve(ctx, bytes));
+	BHIP_TRY(sc->in1.reserve(ctx, bytes));
+	BHIP_TRY(sc->tmp0.reserve(ctx, bytes));
+	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, image, imgStart, imgStride, width, height, ctx->stream));
+	BHIP_TRY(upload(ctx, sc->in1.as<float>(), width, derivX, dStart, dStride, width, height, ctx->stream));
+	BHIP_TRY(upload(ctx, sc->tmp0.as<float>(), width, derivY, dStart, dStride, width, height, ctx->stream));
+	KltTable tab;
+	BHIP_TRY(kltStageTable(ctx, tab, radius, xy, n));
+	BHIP_TRY(bhip_launch_klt_describe(ctx, kltStagePyr(sc->in0.as<float>(), sc->in1.as<float>(), sc->tmp0.as<float>(), width, height), tab.v, c, 2, nullptr, n));
+	const int len = tab.v.len;
+	std::vector<float> t((size_t)n * 3 * len), g((size_t)3 * n);
+	std::vector<int> keep(n), fault(n);
+	BHIP_HIP(ctx, hipMemcpyAsync(t.data(), tab.v.tmpl, t.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(g.data(), tab.v.gxx, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(g.data() + n, tab.v.gyy, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(g.data() + 2 * n, tab.v.gxy, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(keep.data(), tab.v.keep, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(fault.data(), tab.v.fault, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_TRY(bhip_ctx_synchronize(ctx));
+	for (int i = 0; i < n; i++) {
+		memcpy(desc + (size_t)i * len, t.data() + ((size_t)i * 3 + 0) * len, (size_t)len * 4);
+		memcpy(descX + (size_t)i * len, t.data() + ((size_t)i * 3 + 1) * len, (size_t)len * 4);
+		memcpy(descY + (size_t)i * len, t.data() + ((size_t)i * 3 + 2) * len, (size_t)len * 4);
+		G[3 * i] = g[i]; G[3 * i + 1] = g[n + i]; G[3 * i + 2] = g[2 * n + i];
+		ok[i] = fault[i] == BHIP_KLT_REFERENCE_THROWS ? 2 : keep[i] ? 1 : 0;
+	}
+	return BHIP_OK;
+}
+
+int bhip_klt_track_f32(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const float* image, int imgStart, int imgStride, int width, int height,
+					   const float* desc, const float* descX, const float* descY, const float* G, float* xy, int n, int* fault, float* error) {
+	if (!kltRangeOk(radius, 1)) return BHIP_ERR_UNSUPPORTED;   // templateRadius 1..7; nothing is written
+	CHECK_CTX(ctx);
+	bhip_klt_cfg c;
+	if (cfg) c = *cfg; else bhip_klt_cfg_default(&c);
+	if (c.maxIterations < 1) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "maxIterations must be >= 1");
+	CHECK_IMG(ctx, image, imgStride, width, height, 1);
+	if (n < 0 || (n > 0 && (!xy || !desc || !descX || !descY || !G || !fault || !error))) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad feature list");
+	if (n == 0) return BHIP_OK;
+	CtxScratch* sc = scratchOf(ctx);
+	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
+	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, image, imgStart, imgStride, width, height, ctx->stream));
+	KltTable tab;
+	BHIP_TRY(kltStageTable(ctx, tab, radius, xy, n));
+	const int len = tab.v.len;
+	std::vector<float> t((size_t)n * 3 * len), g((size_t)3 * n), pos((size_t)2 * n);
+	for (int i = 0; i < n; i++) {
+		memcpy(t.data() + ((size_t)i * 3 + 0) * len, desc + (size_t)i * len, (size_t)len * 4);
+		memcpy(t.data() + ((size_t)i * 3 + 1) * len, descX + (size_t)i * len, (size_t)len * 4);
+		memcpy(t.data() + ((size_t)i * 3 + 2) * len, descY + (size_t)i * len, (size_t)len * 4);
+		g[i] = G[3 * i]; g[n + i] = G[3 * i + 1]; g[2 * n + i] = G[3 * i + 2];
+	}
+	BHIP_HIP(ctx, hipMemcpyAsync(tab.v.tmpl, t.data(), t.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(tab.v.gxx, g.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(tab.v.gyy, g.data() + n, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(tab.v.gxy, g.data() + 2 * n, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+	BHIP_TRY(bhip_launch_klt_track(ctx, kltStagePyr(sc->in0.as<float>(), nullptr, nullptr, width, height), tab.v, c, n));
+	BHIP_HIP(ctx, hipMemcpyAsync(pos.data(), tab.v.lx, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(pos.data() + n, tab.v.ly, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(fault, tab.v.fault, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(error, tab.v.err, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_TRY(bhip_ctx_synchronize(ctx));
+	for (int i = 0; i < n; i++) { xy[2 * i] = pos[i]; xy[2 * i + 1] = pos[n + i]; }
+	return BHIP_OK;
 }
 
 }  // extern "C"

@@ -293,3 +293,56 @@ int bhip_launch_nonmax_blocks(bhip_ctx* ctx, const float* img, long long imageSt
 int bhip_launch_blocks_to_xy(bhip_ctx* ctx, const unsigned int* bitmap, const unsigned int* wordPrefix, int bitmapWords, const unsigned short* posInBlock,
 							 int nbx, int nby, int batch, int radius, int border, int16_t* xy, int cap);
 
+// ---------------- pyramid KLT tracker (klt.hip) ----------------
+#define BHIP_KLT_MAX_LAYERS 8
+#define BHIP_KLT_MAX_RADIUS 7
+#define BHIP_KLT_MAX_LEN ((2 * BHIP_KLT_MAX_RADIUS + 1) * (2 * BHIP_KLT_MAX_RADIUS + 1))
+
+// image pyramid + derivative pyramids of `batch` frames: layer l of frame b starts at base + b * frameStride + off[l], rows stride[l] floats apart
+struct KltPyr {
+	const float* img;
+	const float* dx;   // nullptr when only tracking (PyramidKltTracker.setImage(image))
+	const float* dy;
+	long long frameStride;
+	long long off[BHIP_KLT_MAX_LAYERS];
+	int w[BHIP_KLT_MAX_LAYERS], h[BHIP_KLT_MAX_LAYERS], stride[BHIP_KLT_MAX_LAYERS];
+	float scale[BHIP_KLT_MAX_LAYERS];   // (float)image.getScale(layer)
+	int numLayers;
+	int frameW, frameH;                 // the input frame (PointTrackerKltPyramid's image.isInBounds)
+};
+
+// Track table of one tracker object.  Sequence b owns slots [0, cap); slot s of sequence b is entry g = b * cap + s of every per-track array
+// (structure of arrays: the fields of neighbouring tracks are contiguous).  Lists hold slot numbers, in the reference's list order.
+struct KltTab {
+	int cap, batch, L, r, len;
+	int *act, *drp, *spw, *freeL;          // [batch][cap]: active / dropped / spawned tracks, unused slots
+	int *nAct, *nDrp, *nSpw, *nFree;       // [batch]
+	long long* total;                      // [batch] totalFeatures
+	long long* id;                         // featureId
+	float *x, *y;                          // PyramidKltFeature.x,y == PointTrack position
+	float *tx, *ty;                        // position found by track(), committed to x,y when the track survives the frame
+	float* err;                            // KltTracker.getError() of the last layer whose error was computed
+	int* fault;                            // KltTrackFault ordinal of the last track()
+	int* keep;
+	int* iters;                            // Lucas-Kanade iterations of the last track() | border-form iterations << 16 (bench figures)
+	float *lx, *ly, *gxx, *gxy, *gyy;      // [L][batch * cap]: KltFeature x, y, Gxx, Gxy, Gyy of every layer
+	float* tmpl;                           // [g][L][3][len]: desc, derivX, derivY (desc = NaN where the patch left the image)
+};
+
+int bhip_launch_klt_init(bhip_ctx* ctx, KltTab T, int firstSlot);   // slots firstSlot .. cap-1 of every sequence join its unused list (firstSlot 0: a fresh table)
+int bhip_launch_klt_begin(bhip_ctx* ctx, KltTab T);                 // process(): dropped.clear() (their slots become unused), spawned.clear()
+int bhip_launch_klt_track(bhip_ctx* ctx, KltPyr P, KltTab T, bhip_klt_cfg cfg, int maxActive);
+// mode 0: process() -- tracks whose fault is SUCCESS and whose new centre is inside the frame are described at (tx,ty); keep = survives
+// mode 1: the `count[b]` newest entries of sequence b's unused list are described at their x,y (spawnTracks); keep = the reference did not throw
+// mode 3: the table entries count[0 .. maxCount) are described at their x,y (addTrack; entries < 0 are skipped)
+// mode 2: every active track is described at its x,y (stage-level calls); keep = setDescription's result
+int bhip_launch_klt_describe(bhip_ctx* ctx, KltPyr P, KltTab T, bhip_klt_cfg cfg, int mode, const int* count, int maxCount);
+int bhip_launch_klt_compact(bhip_ctx* ctx, KltTab T, int toUnused);   // active := kept tracks in order; the others go to dropped (or straight to unused)
+int bhip_launch_klt_mark_exclude(bhip_ctx* ctx, KltTab T, float scale0, float* intensity, long long imageStride, int stride, int w, int h, int maxActive);
+int bhip_launch_klt_spawn_place(bhip_ctx* ctx, KltTab T, const int16_t* xy, int xyCap, const int* count, float scale0, int maxCount);
+int bhip_launch_klt_spawn_commit(bhip_ctx* ctx, KltTab T, const int* count);
+int bhip_launch_klt_add(bhip_ctx* ctx, KltTab T, const int* seq, const double* xy, int n, int frameW, int frameH, unsigned char* ok, int* list);
+int bhip_launch_klt_match_drop(bhip_ctx* ctx, KltTab T, const int* seq, const long long* id, int n, unsigned char* ok, int maxActive);
+int bhip_launch_klt_drop_all(bhip_ctx* ctx, KltTab T, int resetTotal);
+int bhip_launch_klt_stats(bhip_ctx* ctx, KltTab T, unsigned long long* out);   // out[3] += tracks, iterations, border-form iterations of the last process()
+int bhip_launch_klt_gather(bhip_ctx* ctx, KltTab T, int which, int seq, int n, long long* id, float* xy, int* fault, float* err);

@@ -1202,7 +1202,7 @@ struct GradParams {
 	float* dy;
 	long long inImageStride, outImageStride;   // floats between the images of a batch
 	int inStride, outStride, width, height;
-	int border;  // 0: frame untouched, 1: ImageBorderValue(0)
+	int border;  // 0: frame untouched, 1: ImageBorderValue(0), 2: BorderType.EXTENDED (Sobel only)
 };
 
 __device__ __forceinline__ float at0(const GradParams& P, const float* img, int x, int y) {
@@ -1230,12 +1230,20 @@ __device__ __forceinline__ bool gradOne(const float a[3][3], int x, int y, int W
 		const float kx[9] = {-0.25f, 0, 0.25f, -0.5f, 0, 0.5f, -0.25f, 0, 0.25f};
 		const float ky[9] = {-0.25f, -0.5f, -0.25f, 0, 0, 0, 0.25f, 0.5f, 0.25f};
 		float tx = 0, ty = 0;
+		// border 2 = BorderType.EXTENDED (BorderIndex1D_Extend): an index outside the image is clamped, and the clamped pixel of a frame
+		// pixel's neighbourhood is always one of the nine values at hand
+		const int r0 = (border == 2 && y == 0) ? 1 : 0, r2 = (border == 2 && y == H - 1) ? 1 : 2;
+		const int c0 = (border == 2 && x == 0) ? 1 : 0, c2 = (border == 2 && x == W - 1) ? 1 : 2;
 #pragma unroll
 		for (int i = 0; i < 3; i++)
 #pragma unroll
 			for (int j = 0; j < 3; j++) {
-				tx += a[i][j] * kx[i * 3 + j];
-				ty += a[i][j] * ky[i * 3 + j];
+				const int ii = i == 0 ? r0 : i == 2 ? r2 : 1, jj = j == 0 ? c0 : j == 2 ? c2 : 1;
+				const float v = (ii == 0 ? (jj == 0 ? a[0][0] : jj == 1 ? a[0][1] : a[0][2])
+								 : ii == 1 ? (jj == 0 ? a[1][0] : jj == 1 ? a[1][1] : a[1][2])
+										   : (jj == 0 ? a[2][0] : jj == 1 ? a[2][1] : a[2][2]));
+				tx += v * kx[i * 3 + j];
+				ty += v * ky[i * 3 + j];
 			}
 		dx = tx; dy = ty;
 		return true;

@@ -12,6 +12,7 @@ Names follow the reference classes the host-buffer forms in boofcv_amd/api.py mi
   DeviceImageOps.pyramid        PyramidDiscreteSampleBlur.process                   I:alg/transform/pyramid/PyramidDiscreteSampleBlur.java:88-118
   DeviceImageOps.cornerIntensity  GradientCornerIntensity.process                   F:alg/feature/detect/intensity/impl/ImplSsdCorner_F32.java:62-196
   DeviceImageOps.brief          DescribePointBrief.process                          F:alg/feature/describe/DescribePointBrief.java:73-89
+  DeviceKltTracker              PointTrackerKltPyramid, batched over sequences      main/boofcv-geo/.../abst/feature/tracker/PointTrackerKltPyramid.java:139-348
 """
 import ctypes as C
 
@@ -77,7 +78,8 @@ class DeviceImageOps:
         return out
 
     def _grad(self, fn, src, border, dx, dy):
-        """border: None = frame untouched (as the reference with a null border), 0 = ImageBorderValue(0).  float32 -> float32, uint8 -> int16."""
+        """border: None = frame untouched (as the reference with a null border), 0 = ImageBorderValue(0), "EXTENDED" = BorderType.EXTENDED (Sobel on
+        float32 only).  float32 -> float32, uint8 -> int16."""
         fn_f32, fn_u8 = fn
         u8 = src.dtype == torch.uint8
         fn, dt = (fn_u8, torch.int16) if u8 else (fn_f32, torch.float32)
@@ -94,7 +96,7 @@ class DeviceImageOps:
         yp, ois2, ors2, _, _, _ = _geom(dy, dt)
         if (ois, ors) != (ois2, ors2):
             raise IllegalArgumentException("derivX and derivY must share their layout")
-        _check(self.ctx, fn(self.ctx._h, ip, iis, irs, W, H, B, xp, yp, ois, ors, 0 if border is None else 1))
+        _check(self.ctx, fn(self.ctx._h, ip, iis, irs, W, H, B, xp, yp, ois, ors, 0 if border is None else 2 if border == "EXTENDED" else 1))
         return dx, dy
 
     def sobel(self, src, border=0, dx=None, dy=None):
@@ -181,4 +183,123 @@ class DeviceImageOps:
         _check(self.ctx, self.L.bhip_brief_dev_f32(self.ctx._h, ip, iis, irs, W, H, B, int(radius), len(cp), sp.ctypes.data_as(_lib._i32p),
                                                  cp.ctypes.data_as(_lib._i32p), C.c_void_p(xy.data_ptr()), st.ctypes.data_as(_lib._ip),
                                                  C.c_void_p(out.data_ptr())))
+        return out
+
+
+class DeviceKltTracker:
+    """PointTrackerKltPyramid (G:abst/feature/tracker/PointTrackerKltPyramid.java:139-348, as FactoryPointTracker.klt builds it) for B independent
+    GrayF32 sequences at once, on one bhip_klt: process(frames) takes a [B,H,W] CUDA tensor and queues pyramid, Sobel (EXTENDED border), tracking,
+    re-description and the list update on the context's stream without a host synchronisation; spawn() detects Shi-Tomasi corners
+    (radius 1, unweighted) with the strict non-max extractor (detectRadius, detectThreshold, detectBorder) and starts tracks on them
+    (maxFeatures <= 0).  Sequence b's results equal those of a single-sequence tracker fed with frames[b]."""
+
+    def __init__(self, scales, templateRadius, config=None, detectRadius=1, detectThreshold=0.0, ctx=None, detectBorder=None, device=0):
+        from .api import KltConfig
+        self.ctx = ctx or Context(device, stream=torch.cuda.current_stream(device).cuda_stream)
+        self.L = _lib.load()
+        self.scales = [int(s) for s in scales]
+        self.templateRadius = int(templateRadius)
+        self.config = config or KltConfig()
+        self.detectRadius, self.detectThreshold = int(detectRadius), float(detectThreshold)
+        # FactoryDetectPoint.createGeneral + GeneralFeatureDetector: ignoreBorder + radius, at least the Shi-Tomasi window radius (1)
+        self.detectBorder = max(self.detectRadius, 1) if detectBorder is None else int(detectBorder)
+        self._h = None
+        self._shape = None
+        self.ctx._children.add(self)
+
+    def close(self):
+        if self._h:
+            self.L.bhip_klt_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _need(self):
+        if not self._h:
+            raise IllegalArgumentException("process() has not been called")
+
+    def process(self, frames):
+        ptr, imageStride, stride, W, H, B = _geom(frames)
+        if self._shape != (W, H, B) or not self._h:
+            self.close()
+            h = C.c_void_p()
+            cfg = self.config._c()
+            sc = (C.c_int * len(self.scales))(*self.scales)
+            _check(self.ctx, self.L.bhip_klt_create(self.ctx._h, C.byref(cfg), self.templateRadius, sc, len(self.scales), self.detectRadius, self.detectThreshold,
+                                                    self.detectBorder, W, H, B, C.byref(h)))
+            self._h, self._shape = h, (W, H, B)
+        _check(self.ctx, self.L.bhip_klt_process_dev_f32(self._h, ptr, imageStride, stride))
+
+    def spawn(self):
+        self._need()
+        _check(self.ctx, self.L.bhip_klt_spawn(self._h, -1))
+
+    def addTracks(self, seq, xy):
+        """addTrack(x, y) on sequence seq[i] for every i, in order -> uint8 [n] (0 where the reference returns null)"""
+        self._need()
+        seq = np.ascontiguousarray(seq, np.int32)
+        xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+        ok = np.zeros(len(seq), np.uint8)
+        _check(self.ctx, self.L.bhip_klt_add_tracks(self._h, seq.ctypes.data_as(_lib._ip), xy.ctypes.data_as(_lib._dp), len(seq), ok.ctypes.data_as(_lib._u8p)))
+        return ok
+
+    def dropTracks(self, seq, featureId):
+        self._need()
+        seq = np.ascontiguousarray(seq, np.int32)
+        ids = np.ascontiguousarray(featureId, np.int64)
+        ok = np.zeros(len(seq), np.uint8)
+        _check(self.ctx, self.L.bhip_klt_drop_tracks(self._h, seq.ctypes.data_as(_lib._ip), ids.ctypes.data_as(_lib._llp), len(seq), ok.ctypes.data_as(_lib._u8p)))
+        return ok
+
+    def dropAllTracks(self):
+        self._need()
+        _check(self.ctx, self.L.bhip_klt_drop_all(self._h))
+
+    def reset(self):
+        self._need()
+        _check(self.ctx, self.L.bhip_klt_reset(self._h))
+
+    def counts(self):
+        """-> (active, spawned, dropped) int32 [B] each"""
+        self._need()
+        B = self._shape[2]
+        out = [np.zeros(B, np.int32) for _ in range(3)]
+        _check(self.ctx, self.L.bhip_klt_counts(self._h, *[o.ctypes.data_as(_lib._ip) for o in out]))
+        return tuple(out)
+
+    def stats(self):
+        """-> (tracks, iterations, borderIterations) of the last process() over all sequences"""
+        self._need()
+        v = [C.c_longlong() for _ in range(3)]
+        _check(self.ctx, self.L.bhip_klt_stats(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def _fetch(self, which, seq):
+        from .api import _klt_fetch
+        self._need()
+        ids, xy, fault, err = _klt_fetch(self.ctx, self._h, which, int(seq), self._shape[2])
+        return dict(featureId=ids, xy=xy, fault=fault, error=err)
+
+    def active(self, seq):
+        """tracks of getActiveTracks() of sequence seq, in list order: dict(featureId, xy, fault, error)"""
+        return self._fetch(0, seq)
+
+    def spawned(self, seq):
+        return self._fetch(1, seq)
+
+    def dropped(self, seq):
+        return self._fetch(2, seq)
+
+    def layer(self, seq, layer, which=0):
+        """layer of the image pyramid (which 0) / derivX (1) / derivY (2) of sequence seq, as a host array"""
+        self._need()
+        sc = np.asarray(self.scales, dtype=np.int32)
+        dims = np.zeros(2 * len(sc), dtype=np.int32)
+        self.L.bhip_pyramid_layout(self._shape[0], self._shape[1], sc.ctypes.data_as(_lib._ip), len(sc), dims.ctypes.data_as(_lib._ip), None, None)
+        out = np.zeros((int(dims[2 * layer + 1]), int(dims[2 * layer])), np.float32)
+        _check(self.ctx, self.L.bhip_klt_fetch_layer(self._h, int(seq), int(layer), int(which), out.ctypes.data_as(_lib._fp)))
         return out

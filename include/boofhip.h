@@ -21,7 +21,8 @@
  *  - pointers named dev_* are device (HBM) addresses on the ctx's device; every other pointer is host memory;
  *  - there is no CPU fallback inside the library: without a usable GPU bhip_ctx_create fails;
  *  - handles may be destroyed in any order and more than once: bhip_ctx_destroy releases the device side of every bhip_surf created on
- *    that context (they become inert: every call on them returns BHIP_ERR_INVALID, bhip_surf_destroy then only frees the shell), a
+ *    that context (they become inert: every call on them returns BHIP_ERR_INVALID, bhip_surf_destroy then only frees the shell; the same
+ *    holds for bhip_klt and bhip_klt_destroy), a
  *    pointer that is not a live handle is refused with BHIP_ERR_INVALID, and once the process is exiting the destroy calls do nothing
  *    (a finaliser that runs after the HIP runtime has shut down is harmless);
  *  - a context must not be destroyed while another thread is inside a call on it or on an object created on it.
@@ -46,6 +47,7 @@ typedef enum {
 
 typedef struct bhip_ctx bhip_ctx;
 typedef struct bhip_surf bhip_surf;
+typedef struct bhip_klt bhip_klt;   /* pyramid KLT point tracker; same handle rules as bhip_surf */
 
 /* ---- configuration structs: same field names and defaults as the reference's Config* classes ---- */
 
@@ -83,7 +85,27 @@ typedef struct {
 	int sampleWidth;            /* 6 */
 } bhip_ori_cfg;
 
+/* F:alg/tracker/klt/KltConfig.java:32-49 */
+typedef struct {
+	int forbiddenBorder;    /* 0; not used by the reference either */
+	float maxPerPixelError; /* 25 */
+	int maxIterations;      /* 15 */
+	float minDeterminant;   /* 0.001f */
+	float minPositionDelta; /* 0.01f */
+} bhip_klt_cfg;
+
+/* F:alg/tracker/klt/KltTrackFault.java:28-44 (ordinals).  BHIP_KLT_REFERENCE_THROWS: the position is one of the float round-off cases at the image
+ * border where KltTracker.computeSubImageBounds / BilinearRectangle_F32.region throw IllegalArgumentException (in Java the exception leaves
+ * PointTrackerKltPyramid.process); the library never reads outside the image, gives the track this fault and drops it. */
+#define BHIP_KLT_SUCCESS 0
+#define BHIP_KLT_DRIFTED 1
+#define BHIP_KLT_OUT_OF_BOUNDS 2
+#define BHIP_KLT_FAILED 3
+#define BHIP_KLT_LARGE_ERROR 4
+#define BHIP_KLT_REFERENCE_THROWS 5
+
 void bhip_fh_cfg_default(bhip_fh_cfg* c);
+void bhip_klt_cfg_default(bhip_klt_cfg* c);
 void bhip_surf_cfg_default(bhip_surf_cfg* c);
 void bhip_ori_cfg_default(bhip_ori_cfg* c, int stable);
 
@@ -277,7 +299,10 @@ int bhip_mean_f32(bhip_ctx* ctx, const float* in, int inStart, int inStride, int
 int bhip_median_f32(bhip_ctx* ctx, const float* in, int inStart, int inStride, int width, int height, int radius, float* out, int outStart,
 					int outStride);
 /* GradientSobel.process(GrayF32,derivX,derivY,border) (I:alg/filter/derivative/GradientSobel.java:158-173);
- * border: 0 = null (frame untouched), 1 = ImageBorderValue(0) */
+ * border: 0 = null (frame untouched), 1 = ImageBorderValue(0), 2 = BorderType.EXTENDED (BoofDefaults.DERIV_BORDER_TYPE, what
+ * FactoryDerivative.sobel passes: I:abst/filter/derivative/ImageGradient_SB.java:39-66): every frame pixel is kernelDerivX/Y_F32 on the
+ * index-clamped image, summed as ConvolveJustBorder_General_SB.convolve does (I:alg/filter/convolve/border/ConvolveJustBorder_General_SB.java:110-174).
+ * bhip_three_f32 and the GrayU8 gradients answer BHIP_ERR_UNSUPPORTED to 2. */
 int bhip_sobel_f32(bhip_ctx* ctx, const float* in, int inStart, int inStride, int width, int height, float* dx, float* dy, int outStart,
 				   int outStride, int border);
 /* GradientThree.process(GrayF32,...) -> GradientThree_Standard.process (I:alg/filter/derivative/impl/GradientThree_Standard.java:40-62) */
@@ -412,6 +437,66 @@ int bhip_corner_intensity_weighted_dev_f32(bhip_ctx* ctx, int kind, int radius, 
  * `start` is a host array of batch+1 entries); point p's words go to dev_out[p * ceil(numPoints/32) ...] */
 int bhip_brief_dev_f32(bhip_ctx* ctx, const float* dev_img, long long imageStride, int stride, int width, int height, int batch, int radius, int numPoints,
 					   const int32_t* samplePoints, const int32_t* compare, const double* dev_xy, const int* start, int32_t* dev_out);
+
+/* ---- pyramid KLT point tracker: FactoryPointTracker.klt(PkltConfig, ConfigGeneralDetector, GrayF32, GrayF32) -> PointTrackerKltPyramid
+ *      (G:factory/feature/tracker/FactoryPointTracker.java:120-145,534-541; G:abst/feature/tracker/PointTrackerKltPyramid.java:139-348;
+ *       F:alg/tracker/klt/PyramidKltTracker.java:58-151; F:alg/tracker/klt/KltTracker.java:147-495; I:alg/interpolate/impl/BilinearRectangle_F32.java:64-172;
+ *       G: = main/boofcv-geo/src/main/java/boofcv/).  One object tracks `batch` independent image sequences of one shape; batch = 1 is the
+ *      reference object.  Pyramid = FactoryPyramid.discreteGaussian(scales, -1, 2), gradient = GradientSobel with BorderType.EXTENDED, corners =
+ *      Shi-Tomasi radius 1 unweighted + strict NonMaxBlock(detectRadius, detectThreshold, detectBorder), all on the device.  Every value is the
+ *      single-threaded Java arithmetic bit for bit.  Deviations: BHIP_KLT_REFERENCE_THROWS (above); positions are reported as the float
+ *      PyramidKltFeature.x,y (PointTrack holds the same numbers as doubles, and the caller's doubles after addTrack); a track added by
+ *      bhip_klt_add_tracks has featureId -1 (the reference leaves whatever the recycled PointTrack held); a track that process() drops after a
+ *      successful track() (centre outside the frame, or setDescription false) keeps fault BHIP_KLT_SUCCESS.  templateRadius 1..7, numLayers 1..8,
+ *      maxIterations >= 1, otherwise BHIP_ERR_UNSUPPORTED. ---- */
+int bhip_klt_create(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int templateRadius, const int* scales, int numLayers, int detectRadius, float detectThreshold,
+					int detectBorder, int width, int height, int batch, bhip_klt** out);
+int bhip_klt_destroy(bhip_klt* k);
+/* process(image) for every sequence: frame b starts at dev_frames + b * imageStride, rows `stride` floats apart.  Pyramid, gradient, track,
+ * re-describe and the list update are queued on the ctx stream without a host synchronisation. */
+int bhip_klt_process_dev_f32(bhip_klt* k, const float* dev_frames, long long imageStride, int stride);
+/* the same for host frames (one pointer per sequence) */
+int bhip_klt_process_f32(bhip_klt* k, const float* const* img, const int* startIndex, const int* stride);
+/* spawnTracks() for every sequence with ConfigGeneralDetector.maxFeatures <= 0; maxFeatures > 0 (SelectNBestFeatures) is BHIP_ERR_UNSUPPORTED here.
+ * New tracks follow the block-raster order of bhip_nonmax_block_dev_f32.  One small count read-back. */
+int bhip_klt_spawn(bhip_klt* k, int maxFeatures);
+/* the second half of spawnTracks() for corners the caller found itself (GeneralFeatureDetector with maxFeatures > 0 composed from
+ * bhip_klt_fetch_layer, the corner entry points and bhip_select_nbest_f32): sequence b gets count[b] candidates, xy[(b * capacity + i) * 2] in
+ * layer-0 pixels, in detector order */
+int bhip_klt_spawn_points(bhip_klt* k, const int16_t* xy, const int* count, int capacity);
+/* addTrack(x, y) on sequence seq[i], in call order; ok[i] = 0 where the reference returns null */
+int bhip_klt_add_tracks(bhip_klt* k, const int* seq, const double* xy, int n, uint8_t* ok);
+/* dropTrack of the active track with that featureId (the first one in list order); ok (may be NULL): the reference's boolean */
+int bhip_klt_drop_tracks(bhip_klt* k, const int* seq, const long long* featureId, int n, uint8_t* ok);
+int bhip_klt_drop_all(bhip_klt* k);
+int bhip_klt_reset(bhip_klt* k);
+/* sizes of getActiveTracks / getNewTracks / getDroppedTracks of every sequence ([batch] each; any pointer may be NULL) */
+int bhip_klt_counts(bhip_klt* k, int* active, int* spawned, int* dropped);
+/* one list of sequence seq (which: 0 active, 1 spawned, 2 dropped) in the reference's list order: featureId[n], xy[2n], fault[n] (last
+ * track() result), error[n] (KltTracker.getError() of the last layer of this track whose error was computed).  Any pointer may be NULL. */
+int bhip_klt_fetch(bhip_klt* k, int which, int seq, long long* featureId, float* xy, int* fault, float* error);
+/* figures of the last process() over all sequences: tracks that went through track(), Lucas-Kanade iterations they took, and how many of those
+ * took the border form (computeGandE_border) */
+int bhip_klt_stats(bhip_klt* k, long long* tracks, long long* iterations, long long* borderIterations);
+/* layer `layer` of sequence seq of the last process(): which 0 = image pyramid, 1 = derivX, 2 = derivY; dense, bhip_pyramid_layout's dims */
+int bhip_klt_fetch_layer(bhip_klt* k, int seq, int layer, int which, float* out);
+/* for callers that stay on the device: sequence b's active slots are dev_activeSlots[b * slotsPerSequence + i], i < dev_activeCount[b]; slot s of
+ * sequence b is entry b * slotsPerSequence + s of dev_x / dev_y / dev_featureId.  Layer l of frame b of the pyramid / derivative buffers starts at
+ * b * floatsPerFrame + offsets[l] of bhip_pyramid_layout.  Valid until the next spawn or add (the table may regrow). */
+int bhip_klt_dev_view(bhip_klt* k, const int** dev_activeSlots, const int** dev_activeCount, const float** dev_x, const float** dev_y,
+					  const long long** dev_featureId, const float** dev_pyramid, const float** dev_derivX, const float** dev_derivY, int* slotsPerSequence,
+					  long long* floatsPerFrame);
+/* stage level, host buffers, one image: KltTracker.setDescription (:147-240) for n features of radius `radius` at xy[2n] on (image, derivX, derivY) of
+ * one shape; image and derivatives each with their own startIndex / stride.  desc / derivX / derivY templates [n][(2r+1)^2] (desc = NaN outside the
+ * image; the derivative templates read 0 there, the reference leaves them stale), G[3n] = Gxx, Gyy, Gxy, ok[n] = the boolean
+ * (2 = BHIP_KLT_REFERENCE_THROWS). */
+int bhip_klt_set_description_f32(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const float* image, int imgStart, int imgStride, const float* derivX,
+								 const float* derivY, int dStart, int dStride, int width, int height, const float* xy, int n, float* desc, float* descX,
+								 float* descY, float* G, uint8_t* ok);
+/* KltTracker.track (:251-325): xy[2n] in / out (moved also when a fault is returned, as in the reference), fault[n], error[n] (written where
+ * computeError ran: SUCCESS and LARGE_ERROR) */
+int bhip_klt_track_f32(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const float* image, int imgStart, int imgStride, int width, int height,
+					   const float* desc, const float* descX, const float* descY, const float* G, float* xy, int n, int* fault, float* error);
 
 #ifdef __cplusplus
 }
