@@ -152,10 +152,23 @@ SIGNATURES = {
     "bhip_klt_counts": (_i, [_vp, _ip, _ip, _ip]),
     "bhip_klt_fetch": (_i, [_vp, _i, _i, _llp, _fp, _ip, _fp]),
     "bhip_klt_stats": (_i, [_vp, _llp, _llp, _llp]),
+    "bhip_klt_fetch_templates": (_i, [_vp, _i, _i, _i, _fp, _fp]),
     "bhip_klt_fetch_layer": (_i, [_vp, _i, _i, _i, _fp]),
     "bhip_klt_dev_view": (_i, [_vp, P(_vp), P(_vp), P(_vp), P(_vp), P(_vp), P(_vp), P(_vp), P(_vp), _ip, _llp]),
     "bhip_klt_set_description_f32": (_i, [_vp, P(KltCfg), _i, _fp, _i, _i, _fp, _fp, _i, _i, _i, _i, _fp, _i, _fp, _fp, _fp, _fp, _u8p]),
     "bhip_klt_track_f32": (_i, [_vp, P(KltCfg), _i, _fp, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _i, _ip, _fp]),
+    "bhip_conv_down_norm_h_u8": (_i, [_vp, _i32p, _i, _u8p, _i, _i, _i, _i, _u8p, _i, _i, _i, _i, _i]),
+    "bhip_conv_down_norm_v_u8": (_i, [_vp, _i32p, _i, _u8p, _i, _i, _i, _i, _u8p, _i, _i, _i, _i, _i]),
+    "bhip_pyramid_u8": (_i, [_vp, _i32p, _i, _ip, _i, _u8p, _i, _i, _i, _i, _u8p]),
+    "bhip_pyramid_dev_u8": (_i, [_vp, _i32p, _i, _ip, _i, _vp, _ll, _i, _i, _i, _i, _vp]),
+    "bhip_klt_create_u8": (_i, [_vp, P(KltCfg), _i, _ip, _i, _i, _f, _i, _i, _i, _i, P(_vp)]),
+    "bhip_klt_process_dev_u8": (_i, [_vp, _vp, _ll, _i]),
+    "bhip_klt_process_u8": (_i, [_vp, P(_u8p), _ip, _ip]),
+    "bhip_klt_fetch_layer_u8": (_i, [_vp, _i, _i, _u8p]),
+    "bhip_klt_fetch_layer_s16": (_i, [_vp, _i, _i, _i, _i16p]),
+    "bhip_klt_dev_view_u8": (_i, [_vp, P(_vp), P(_vp), P(_vp), P(_vp), P(_vp), P(_vp), P(_vp), P(_vp), _ip, _llp]),
+    "bhip_klt_set_description_u8": (_i, [_vp, P(KltCfg), _i, _u8p, _i, _i, _i16p, _i16p, _i, _i, _i, _i, _fp, _i, _fp, _fp, _fp, _fp, _u8p]),
+    "bhip_klt_track_u8": (_i, [_vp, P(KltCfg), _i, _u8p, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _i, _ip, _fp]),
 }
 
 _lib = None

@@ -1597,32 +1597,49 @@ class FactoryKernelGaussian:
         return out
 
 
+def _s32_taps(kernel):
+    """Kernel1D_S32 taps: the int32 array FactoryKernelGaussian.gaussian1D_S32 returns, or anything with such a .data"""
+    return np.ascontiguousarray(getattr(kernel, "data", kernel), dtype=np.int32)
+
+
 class ConvolveImageDownNormalized:
-    """I:alg/filter/convolve/ConvolveImageDownNormalized.java:53-86 (the NORMALIZED ConvolveDown of the discrete pyramid)"""
+    """I:alg/filter/convolve/ConvolveImageDownNormalized.java:53-86 (Kernel1D_F32, GrayF32), :109-137 (Kernel1D_S32, GrayU8 -> GrayI8): the
+    NORMALIZED ConvolveDown of the discrete pyramid"""
 
     @staticmethod
-    def _run(fn, kernel, image, dest, skip, ctx):
+    def _run(axis, kernel, image, dest, skip, ctx):
         ctx = _ctx(ctx)
-        rc = fn(ctx._h, kernel.data.ctypes.data_as(_lib._fp), kernel.width, image._p(), image.startIndex, image.stride, image.width, image.height,
+        L = _lib.load()
+        if isinstance(image, GrayU8):
+            if not isinstance(dest, GrayU8):
+                raise IllegalArgumentException("a GrayU8 image is down-convolved into a GrayU8 (GrayI8) image")
+            taps = _s32_taps(kernel)
+            fn, kp, kw = getattr(L, "bhip_conv_down_norm_%s_u8" % axis), taps.ctypes.data_as(_lib._i32p), len(taps)
+        elif isinstance(image, GrayF32):
+            fn, kp, kw = getattr(L, "bhip_conv_down_norm_%s_f32" % axis), kernel.data.ctypes.data_as(_lib._fp), kernel.width
+        else:
+            raise RuntimeError("only GrayF32 and GrayU8 images are implemented on the GPU (use the Java path)")
+        rc = fn(ctx._h, kp, kw, image._p(), image.startIndex, image.stride, image.width, image.height,
                 dest._p(), dest.startIndex, dest.stride, dest.width, dest.height, int(skip))
         _check(ctx, rc)
 
     @staticmethod
     def horizontal(kernel, image, dest, skip, ctx=None):
-        ConvolveImageDownNormalized._run(_lib.load().bhip_conv_down_norm_h_f32, kernel, image, dest, skip, ctx)
+        ConvolveImageDownNormalized._run("h", kernel, image, dest, skip, ctx)
 
     @staticmethod
     def vertical(kernel, image, dest, skip, ctx=None):
-        ConvolveImageDownNormalized._run(_lib.load().bhip_conv_down_norm_v_f32, kernel, image, dest, skip, ctx)
+        ConvolveImageDownNormalized._run("v", kernel, image, dest, skip, ctx)
 
 
 class PyramidDiscreteSampleBlur:
     """I:alg/transform/pyramid/PyramidDiscreteSampleBlur.java:48-126: layer i = layer i-1 blurred with the (border-normalised) kernel and
     sub-sampled by scale[i]/scale[i-1]; layer 0 = the input when scale[0] == 1."""
 
-    def __init__(self, kernel, sigma, saveOriginalReference, scaleFactors, ctx=None):
+    def __init__(self, kernel, sigma, saveOriginalReference, scaleFactors, ctx=None, imageType=None):
         self.ctx = _ctx(ctx)
         self.kernel = kernel
+        self.imageType = GrayF32 if imageType is None else imageType   # GrayF32 (Kernel1D_F32) or GrayU8 (Kernel1D_S32)
         self.saveOriginalReference = bool(saveOriginalReference)
         self.scale = [int(s) for s in scaleFactors]
         # ImagePyramidBase.checkScales (T:struct/pyramid/ImagePyramidBase.java:100-112)
@@ -1659,9 +1676,17 @@ class PyramidDiscreteSampleBlur:
         if L.bhip_pyramid_layout(input.width, input.height, sc.ctypes.data_as(_lib._ip), n, dims.ctypes.data_as(_lib._ip),
                                  offs.ctypes.data_as(_lib._llp), C.byref(total)) != 0:
             raise IllegalArgumentException("bad pyramid scales")
-        packed = np.zeros(total.value, dtype=np.float32)
-        rc = L.bhip_pyramid_f32(self.ctx._h, self.kernel.data.ctypes.data_as(_lib._fp), self.kernel.width, sc.ctypes.data_as(_lib._ip), n, input._p(),
-                                input.startIndex, input.stride, input.width, input.height, packed.ctypes.data_as(_lib._fp))
+        if not isinstance(input, self.imageType):
+            raise IllegalArgumentException("this pyramid was built for %s images" % self.imageType.__name__)
+        if self.imageType is GrayU8:
+            taps = _s32_taps(self.kernel)
+            packed = np.zeros(total.value, dtype=np.uint8)
+            rc = L.bhip_pyramid_u8(self.ctx._h, taps.ctypes.data_as(_lib._i32p), len(taps), sc.ctypes.data_as(_lib._ip), n, input._p(),
+                                   input.startIndex, input.stride, input.width, input.height, packed.ctypes.data_as(_lib._u8p))
+        else:
+            packed = np.zeros(total.value, dtype=np.float32)
+            rc = L.bhip_pyramid_f32(self.ctx._h, self.kernel.data.ctypes.data_as(_lib._fp), self.kernel.width, sc.ctypes.data_as(_lib._ip), n, input._p(),
+                                    input.startIndex, input.stride, input.width, input.height, packed.ctypes.data_as(_lib._fp))
         _check(self.ctx, rc)
         self.layers = []
         for i in range(n):
@@ -1669,7 +1694,7 @@ class PyramidDiscreteSampleBlur:
             if i == 0 and self.scale[0] == 1 and self.saveOriginalReference:
                 self.layers.append(input)  # setFirstLayer(input)
             else:
-                self.layers.append(GrayF32(w, h, packed[offs[i]:offs[i] + w * h]))
+                self.layers.append(self.imageType(w, h, packed[offs[i]:offs[i] + w * h]))
         return self
 
     def getLayer(self, i):
@@ -1684,10 +1709,19 @@ class PyramidDiscreteSampleBlur:
 
 class FactoryPyramid:
     @staticmethod
-    def discreteGaussian(scaleFactors, sigma, radius, saveOriginalReference=False, ctx=None):
-        """I:factory/transform/pyramid/FactoryPyramid.java:53-61"""
-        kernel = FactoryKernelGaussian.gaussian1D_F32(sigma, radius)
-        return PyramidDiscreteSampleBlur(kernel, sigma, saveOriginalReference, scaleFactors, ctx)
+    def discreteGaussian(scaleFactors, sigma, radius, saveOriginalReference=False, ctx=None, imageType=None):
+        """I:factory/transform/pyramid/FactoryPyramid.java:53-61: FactoryKernelGaussian.gaussian(FactoryKernel.getKernelType(imageType, 1), sigma,
+        radius) -- Kernel1D_F32 for GrayF32 (the default), Kernel1D_S32 for GrayU8"""
+        imageType = GrayF32 if imageType is None else imageType
+        if imageType is GrayU8:
+            if sigma > 0:
+                raise RuntimeError("the integer Gaussian kernel is built from its radius only on the GPU (sigma = -1)")
+            kernel = FactoryKernelGaussian.gaussian1D_S32(radius)
+        elif imageType is GrayF32:
+            kernel = FactoryKernelGaussian.gaussian1D_F32(sigma, radius)
+        else:
+            raise RuntimeError("only GrayF32 and GrayU8 pyramids are implemented on the GPU (use the Java path)")
+        return PyramidDiscreteSampleBlur(kernel, sigma, saveOriginalReference, scaleFactors, ctx, imageType)
 
 
 @dataclass
@@ -1754,7 +1788,7 @@ class _Gradient:
 
     @classmethod
     def process(cls, orig, derivX, derivY, border=None, ctx=None):
-        """border: None = null (frame untouched), 0 = ImageBorderValue(0), BorderType.EXTENDED (GradientSobel on GrayF32 only: what
+        """border: None = null (frame untouched), 0 = ImageBorderValue(0), BorderType.EXTENDED (GradientSobel only: what
         FactoryDerivative.sobel uses).  GrayF32 -> GrayF32, or GrayU8 -> GrayS16."""
         ctx = _ctx(ctx)
         extended = border is BorderType.EXTENDED
@@ -1893,7 +1927,8 @@ class KltFeature:
 
 class KltTracker:
     """F:alg/tracker/klt/KltTracker.java:147-495 with BilinearRectangle_F32 for the image and the derivatives, on the stage-level entry points
-    bhip_klt_set_description_f32 / bhip_klt_track_f32.  Where the reference throws "Region is outside of the image" this raises
+    bhip_klt_set_description_f32 / bhip_klt_track_f32 -- or, for a GrayU8 image with GrayS16 derivatives, BilinearRectangle_U8 / _S16 on
+    bhip_klt_set_description_u8 / bhip_klt_track_u8.  Where the reference throws "Region is outside of the image" this raises
     IllegalArgumentException."""
 
     def __init__(self, config=None, ctx=None):
@@ -1906,6 +1941,10 @@ class KltTracker:
         for d in (derivX, derivY):
             if d is not None and (d.width != image.width or d.height != image.height):
                 raise IllegalArgumentException("Image shapes do not match")   # InputSanityCheck.checkSameShape
+        derivType = GrayS16 if isinstance(image, GrayU8) else GrayF32
+        if not isinstance(image, (GrayF32, GrayU8)) or any(d is not None and not isinstance(d, derivType) for d in (derivX, derivY)):
+            raise RuntimeError("only GrayF32 images with GrayF32 derivatives and GrayU8 images with GrayS16 derivatives are tracked on the GPU "
+                               "(use the Java path)")
         self.image, self.derivX, self.derivY = image, derivX, derivY
 
     unsafe_setImage = setImage
@@ -1931,10 +1970,12 @@ class KltTracker:
         ok = np.zeros(n, np.uint8)
         cfg = self.config._c()
         im = self.image
-        _check(self.ctx, _lib.load().bhip_klt_set_description_f32(self.ctx._h, C.byref(cfg), int(radius), im._p(), im.startIndex, im.stride, self.derivX._p(),
-                                                                 self.derivY._p(), self.derivX.startIndex, self.derivX.stride, im.width, im.height,
-                                                                 xy.ctypes.data_as(_lib._fp), n, d.ctypes.data_as(_lib._fp), dx.ctypes.data_as(_lib._fp),
-                                                                 dy.ctypes.data_as(_lib._fp), G.ctypes.data_as(_lib._fp), ok.ctypes.data_as(_lib._u8p)))
+        L = _lib.load()
+        fn = L.bhip_klt_set_description_u8 if isinstance(im, GrayU8) else L.bhip_klt_set_description_f32
+        _check(self.ctx, fn(self.ctx._h, C.byref(cfg), int(radius), im._p(), im.startIndex, im.stride, self.derivX._p(),
+                            self.derivY._p(), self.derivX.startIndex, self.derivX.stride, im.width, im.height,
+                            xy.ctypes.data_as(_lib._fp), n, d.ctypes.data_as(_lib._fp), dx.ctypes.data_as(_lib._fp),
+                            dy.ctypes.data_as(_lib._fp), G.ctypes.data_as(_lib._fp), ok.ctypes.data_as(_lib._u8p)))
         return d, dx, dy, G, ok
 
     def trackAll(self, xy, radius, desc, derivX, derivY, G):
@@ -1947,10 +1988,12 @@ class KltTracker:
         cfg = self.config._c()
         im = self.image
         _check_extent(im.width, im.height, im.startIndex, im.stride, im.data.size)
-        _check(self.ctx, _lib.load().bhip_klt_track_f32(self.ctx._h, C.byref(cfg), int(radius), im._p(), im.startIndex, im.stride, im.width, im.height,
-                                                       desc.ctypes.data_as(_lib._fp), derivX.ctypes.data_as(_lib._fp), derivY.ctypes.data_as(_lib._fp),
-                                                       G.ctypes.data_as(_lib._fp), xy.ctypes.data_as(_lib._fp), n, fault.ctypes.data_as(_lib._ip),
-                                                       err.ctypes.data_as(_lib._fp)))
+        L = _lib.load()
+        fn = L.bhip_klt_track_u8 if isinstance(im, GrayU8) else L.bhip_klt_track_f32
+        _check(self.ctx, fn(self.ctx._h, C.byref(cfg), int(radius), im._p(), im.startIndex, im.stride, im.width, im.height,
+                            desc.ctypes.data_as(_lib._fp), derivX.ctypes.data_as(_lib._fp), derivY.ctypes.data_as(_lib._fp),
+                            G.ctypes.data_as(_lib._fp), xy.ctypes.data_as(_lib._fp), n, fault.ctypes.data_as(_lib._ip),
+                            err.ctypes.data_as(_lib._fp)))
         return xy, fault, err
 
     def setDescription(self, feature):
@@ -2043,13 +2086,15 @@ class PyramidKltTracker:
 
 class PointTrackerKltPyramid:
     """G:abst/feature/tracker/PointTrackerKltPyramid.java:139-348 as FactoryPointTracker.klt builds it (Shi-Tomasi radius 1 unweighted, Sobel with
-    BorderType.EXTENDED, discreteGaussian(scaling, -1, 2), bilinear interpolation) over one bhip_klt with batch = 1: pyramid, gradient, tracking,
+    BorderType.EXTENDED, discreteGaussian(scaling, -1, 2), bilinear interpolation; imageType GrayF32 with GrayF32 derivatives, or GrayU8 with
+    GrayS16 derivatives on bhip_klt_create_u8 / bhip_klt_process_u8) over one bhip_klt with batch = 1: pyramid, gradient, tracking,
     re-description, corner detection and the track lists all stay on the device.  Differences from the Java object: the lists are returned as
     fresh PointTrack objects (positions are the float PyramidKltFeature.x,y; cookie / description are not kept between calls), dropTrack finds
     its track by featureId, addTrack gives featureId -1, and a track at a position where the reference throws is dropped (fault 5)."""
 
-    def __init__(self, config, templateRadius, scaling, configExtract, ctx=None, detectBorder=None):
+    def __init__(self, config, templateRadius, scaling, configExtract, ctx=None, detectBorder=None, imageType=None):
         self.ctx = _ctx(ctx)
+        self.imageType = GrayF32 if imageType is None else imageType   # GrayF32 (GrayF32 derivatives) or GrayU8 (GrayS16 derivatives)
         self.config = config or KltConfig()
         self.templateRadius = int(templateRadius)
         self.scaling = [int(s) for s in scaling]
@@ -2069,8 +2114,9 @@ class PointTrackerKltPyramid:
         h = C.c_void_p()
         cfg = self.config._c()
         sc = (C.c_int * len(self.scaling))(*self.scaling)
-        _check(self.ctx, L.bhip_klt_create(self.ctx._h, C.byref(cfg), self.templateRadius, sc, len(self.scaling), int(self.configExtract.radius),
-                                           float(self.configExtract.threshold), int(self.detectBorder), width, height, 1, C.byref(h)))
+        create = L.bhip_klt_create_u8 if self.imageType is GrayU8 else L.bhip_klt_create
+        _check(self.ctx, create(self.ctx._h, C.byref(cfg), self.templateRadius, sc, len(self.scaling), int(self.configExtract.radius),
+                                float(self.configExtract.threshold), int(self.detectBorder), width, height, 1, C.byref(h)))
         self._h, self._shape = h, (width, height)
 
     def close(self):
@@ -2090,13 +2136,19 @@ class PointTrackerKltPyramid:
             raise IllegalArgumentException("process() has not been called")
 
     def process(self, image):
-        if not isinstance(image, GrayF32):
-            raise RuntimeError("only GrayF32 sequences are tracked on the GPU (use the Java path)")
+        if not isinstance(image, (GrayF32, GrayU8)):
+            raise RuntimeError("only GrayF32 and GrayU8 sequences are tracked on the GPU (use the Java path)")
+        if not isinstance(image, self.imageType):
+            raise IllegalArgumentException("this tracker was built for %s images, not %s" % (self.imageType.__name__, type(image).__name__))
         _check_extent(image.width, image.height, image.startIndex, image.stride, image.data.size)
         if self._shape != (image.width, image.height) or not self._h:
             self._create(image.width, image.height)
-        ptr = (C.POINTER(C.c_float) * 1)(image._p())
-        _check(self.ctx, _lib.load().bhip_klt_process_f32(self._h, ptr, (C.c_int * 1)(image.startIndex), (C.c_int * 1)(image.stride)))
+        L = _lib.load()
+        start, stride = (C.c_int * 1)(image.startIndex), (C.c_int * 1)(image.stride)
+        if self.imageType is GrayU8:
+            _check(self.ctx, L.bhip_klt_process_u8(self._h, (_lib._u8p * 1)(image._p()), start, stride))
+        else:
+            _check(self.ctx, L.bhip_klt_process_f32(self._h, (C.POINTER(C.c_float) * 1)(image._p()), start, stride))
 
     def getLayer(self, layer, which=0):
         """layer of the image pyramid (which = 0) or of derivX / derivY (1 / 2) of the last process()"""
@@ -2104,7 +2156,16 @@ class PointTrackerKltPyramid:
         sc = np.asarray(self.scaling, dtype=np.int32)
         dims = np.zeros(2 * len(sc), dtype=np.int32)
         _lib.load().bhip_pyramid_layout(self._shape[0], self._shape[1], sc.ctypes.data_as(_lib._ip), len(sc), dims.ctypes.data_as(_lib._ip), None, None)
-        out = GrayF32(int(dims[2 * layer]), int(dims[2 * layer + 1]))
+        w, h = int(dims[2 * layer]), int(dims[2 * layer + 1])
+        if self.imageType is GrayU8:   # the GrayU8 pyramid, GrayS16 derivatives
+            if which == 0:
+                out = GrayU8(w, h)
+                _check(self.ctx, _lib.load().bhip_klt_fetch_layer_u8(self._h, 0, int(layer), out._p()))
+            else:
+                out = GrayS16(w, h)
+                _check(self.ctx, _lib.load().bhip_klt_fetch_layer_s16(self._h, 0, int(layer), int(which), out._p()))
+            return out
+        out = GrayF32(w, h)
         _check(self.ctx, _lib.load().bhip_klt_fetch_layer(self._h, 0, int(layer), int(which), out._p()))
         return out
 
@@ -2119,7 +2180,8 @@ class PointTrackerKltPyramid:
         scale0 = np.float32(self.scaling[0])
         exclude = [Point2D_I16(int(np.float32(t.x) / scale0), int(np.float32(t.y) / scale0)) for t in self.getActiveTracks()]
         cfg = ConfigExtract(self.configExtract.radius, self.configExtract.threshold, self.detectBorder)
-        det = GeneralFeatureDetector(FactoryIntensityPointAlg.shiTomasi(1, False, GrayF32, ctx=self.ctx), FactoryFeatureExtractor.nonmax(cfg, self.ctx))
+        derivType = GrayS16 if self.imageType is GrayU8 else GrayF32
+        det = GeneralFeatureDetector(FactoryIntensityPointAlg.shiTomasi(1, False, derivType, ctx=self.ctx), FactoryFeatureExtractor.nonmax(cfg, self.ctx))
         det.setMaxFeatures(maxFeatures)
         det.setExcludeMaximum(exclude)
         det.process(self.getLayer(0, 0), self.getLayer(0, 1), self.getLayer(0, 2))
@@ -2189,10 +2251,12 @@ class FactoryPointTracker:
     def klt(config, configExtract=None, featureRadius=None, imageType=GrayF32, derivType=None, ctx=None):
         """klt(int[] scaling, ConfigGeneralDetector, int featureRadius, imageType, derivType) or klt(PkltConfig, ConfigGeneralDetector, imageType,
         derivType): the first argument decides"""
-        if imageType is not GrayF32 or derivType not in (None, GrayF32):
-            raise RuntimeError("only GrayF32 sequences are tracked on the GPU (use the Java path)")
+        # derivType None = GImageDerivativeOps.getDerivativeType(imageType): GrayF32 for GrayF32, GrayS16 for GrayU8
+        if not ((imageType is GrayF32 and derivType in (None, GrayF32)) or (imageType is GrayU8 and derivType in (None, GrayS16))):
+            raise RuntimeError("only GrayF32 sequences (GrayF32 derivatives) and GrayU8 sequences (GrayS16 derivatives) are tracked on the GPU "
+                               "(use the Java path)")
         if config is None:
             config = PkltConfig()
         if not isinstance(config, PkltConfig):
             config = PkltConfig(featureRadius, config)
-        return PointTrackerKltPyramid(config.config, config.templateRadius, config.pyramidScaling, configExtract, ctx)
+        return PointTrackerKltPyramid(config.config, config.templateRadius, config.pyramidScaling, configExtract, ctx, imageType=imageType)

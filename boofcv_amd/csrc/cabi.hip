@@ -1544,7 +1544,7 @@ static int gradHost(bhip_ctx* ctx, int kind, const TI* in, int inStart, int inSt
 	CHECK_IMG(ctx, in, inStride, width, height, 1);
 	CHECK_IMG(ctx, dx, outStride, width, height, 1);
 	CHECK_IMG(ctx, dy, outStride, width, height, 1);
-	if (border != 0 && border != 1 && !(border == 2 && kind == 0 && sizeof(TI) == 4))   // 2 = BorderType.EXTENDED: GradientSobel on GrayF32 only
+	if (border != 0 && border != 1 && !(border == 2 && kind == 0))   // 2 = BorderType.EXTENDED: GradientSobel only
 		return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "border policy not supported on the GPU");
 	CtxScratch* sc = scratchOf(ctx);
 	const int pitch = sizeof(TI) == 4 ? pitch4(width) : width;
@@ -1569,7 +1569,7 @@ static int gradDev(bhip_ctx* ctx, int kind, const TI* dev_in, long long inImageS
 	CHECK_IMG(ctx, dev_in, inStride, width, height, batch);
 	CHECK_IMG(ctx, dev_dx, outStride, width, height, batch);
 	CHECK_IMG(ctx, dev_dy, outStride, width, height, batch);
-	if (border != 0 && border != 1 && !(border == 2 && kind == 0 && sizeof(TI) == 4))   // 2 = BorderType.EXTENDED: GradientSobel on GrayF32 only
+	if (border != 0 && border != 1 && !(border == 2 && kind == 0))   // 2 = BorderType.EXTENDED: GradientSobel only
 		return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "border policy not supported on the GPU");
 	return gradImpl(ctx, kind, dev_in, inImageStride, inStride, width, height, batch, dev_dx, dev_dy, outImageStride, outStride, border);
 }
@@ -1699,6 +1699,32 @@ int bhip_conv_down_norm_v_f32(bhip_ctx* ctx, const float* kernel, int kw, const 
 	return convDownHost(ctx, true, kernel, kw, in, inStart, inStride, width, height, out, outStart, outStride, outWidth, outHeight, skip);
 }
 
+static int convDownHostU8(bhip_ctx* ctx, bool vertical, const int32_t* kernel, int kw, const uint8_t* in, int inStart, int inStride, int width, int height,
+						  uint8_t* out, int outStart, int outStride, int outWidth, int outHeight, int skip) {
+	CHECK_CTX(ctx);
+	CHECK_IMG(ctx, in, inStride, width, height, 1);
+	CHECK_IMG(ctx, out, outStride, outWidth, outHeight, 1);
+	if (!kernel) return bhip_fail(ctx, BHIP_ERR_INVALID, "null kernel");
+	CtxScratch* sc = scratchOf(ctx);
+	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height));
+	BHIP_TRY(sc->out0.reserve(ctx, (size_t)outWidth * outHeight));
+	BHIP_TRY(upload(ctx, sc->in0.as<uint8_t>(), width, in, inStart, inStride, width, height, ctx->stream));
+	// pixels the reference does not write keep the caller's values
+	BHIP_TRY(upload(ctx, sc->out0.as<uint8_t>(), outWidth, (const uint8_t*)out, outStart, outStride, outWidth, outHeight, ctx->stream));
+	BHIP_TRY(bhip_launch_conv_down_u8(ctx, vertical, kernel, kw, sc->in0.as<uint8_t>(), 0, width, width, height, sc->out0.as<uint8_t>(), 0, outWidth, outWidth,
+									  outHeight, skip, 1));
+	BHIP_TRY(download(ctx, out, outStart, outStride, (const uint8_t*)sc->out0.as<uint8_t>(), outWidth, outWidth, outHeight, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
+}
+int bhip_conv_down_norm_h_u8(bhip_ctx* ctx, const int32_t* kernel, int kw, const uint8_t* in, int inStart, int inStride, int width, int height, uint8_t* out,
+							 int outStart, int outStride, int outWidth, int outHeight, int skip) {
+	return convDownHostU8(ctx, false, kernel, kw, in, inStart, inStride, width, height, out, outStart, outStride, outWidth, outHeight, skip);
+}
+int bhip_conv_down_norm_v_u8(bhip_ctx* ctx, const int32_t* kernel, int kw, const uint8_t* in, int inStart, int inStride, int width, int height, uint8_t* out,
+							 int outStart, int outStride, int outWidth, int outHeight, int skip) {
+	return convDownHostU8(ctx, true, kernel, kw, in, inStart, inStride, width, height, out, outStart, outStride, outWidth, outHeight, skip);
+}
+
 // FactoryKernelGaussian.gaussian(Kernel1D_F32.class, sigma, radius) (I:factory/filter/kernel/FactoryKernelGaussian.java:120-153)
 int bhip_gaussian_kernel1d_f32(double sigma, int radius, float* out, int capacity) {
 	if (sigma <= 0 && radius <= 0) return -1;
@@ -1782,6 +1808,87 @@ int bhip_pyramid_dev_f32(bhip_ctx* ctx, const float* kernel, int kw, const int* 
 		prev = layer; prevImageStride = total; prevStride = lw; pw = lw; ph = lh;
 	}
 	return BHIP_OK;
+}
+
+}  // extern "C"
+
+// PyramidDiscreteSampleBlur<GrayU8>.process on `batch` device frames (see bhip_pyramid_dev_f32 for `temp` and the zero-filled layers).
+// layer0Present: the caller has already put the frames into layer 0 (scale[0] == 1), so no copy is made.
+static int pyramidU8Impl(bhip_ctx* ctx, const int32_t* kernel, int kw, const int* scales, int n, const uint8_t* dev_in, long long inImageStride, int inStride,
+						 int width, int height, int batch, uint8_t* dev_out, bool layer0Present) {
+	if (n > 32) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "more than 32 layers");
+	int dims[64];
+	long long offs[32], total = 0;
+	if (bhip_pyramid_layout(width, height, scales, n, dims, offs, &total) != BHIP_OK) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad pyramid scales");
+	for (int i = 1; i < n; i++)
+		if (scales[i] / scales[i - 1] <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Skip must be >= 1");
+	CtxScratch* sc = scratchOf(ctx);
+	const bool copy0 = scales[0] == 1;
+	// freshly created layers are zero; layer 0 at scale 1 is written (or already there) as a whole
+	const long long clearFrom = copy0 ? (n > 1 ? offs[1] : total) : 0;
+	if (total > clearFrom)
+		BHIP_HIP(ctx, hipMemset2DAsync(dev_out + clearFrom, (size_t)total, 0, (size_t)(total - clearFrom), (size_t)batch, ctx->stream));
+	long long tempCap = 0;
+	{
+		int pw0 = width, ph0 = height;
+		for (int i = 0; i < n; i++) {
+			if (!(i == 0 && copy0)) {
+				const int skip = i == 0 ? scales[0] : scales[i] / scales[i - 1];
+				tempCap = std::max(tempCap, (long long)(pw0 / skip) * ph0);
+			}
+			pw0 = dims[2 * i]; ph0 = dims[2 * i + 1];
+		}
+	}
+	if (tempCap > 0) {
+		BHIP_TRY(sc->ipTmp.reserve(ctx, (size_t)tempCap * batch));
+		BHIP_HIP(ctx, hipMemsetAsync(sc->ipTmp.p, 0, (size_t)tempCap * batch, ctx->stream));
+	}
+	const uint8_t* prev = dev_in;
+	long long prevImageStride = inImageStride;
+	int prevStride = inStride, pw = width, ph = height;
+	for (int i = 0; i < n; i++) {
+		uint8_t* layer = dev_out + offs[i];
+		const int lw = dims[2 * i], lh = dims[2 * i + 1];
+		if (i == 0 && copy0) {
+			if (!layer0Present) {
+				ProfScope prof(ctx, "pyramid_copy_u8", 2.0 * width * height * batch);
+				BHIP_TRY(bhip_launch_copy_images_u8(ctx, dev_in, inImageStride, inStride, layer, total, lw, width, height, batch));
+			}
+		} else {
+			const int skip = i == 0 ? scales[0] : scales[i] / scales[i - 1];
+			const int tw = pw / skip;
+			uint8_t* tmp = sc->ipTmp.as<uint8_t>();
+			BHIP_TRY(bhip_launch_conv_down_u8(ctx, false, kernel, kw, prev, prevImageStride, prevStride, pw, ph, tmp, tempCap, tw, tw, ph, skip, batch));
+			BHIP_TRY(bhip_launch_conv_down_u8(ctx, true, kernel, kw, tmp, tempCap, tw, tw, ph, layer, total, lw, lw, lh, skip, batch));
+		}
+		prev = layer; prevImageStride = total; prevStride = lw; pw = lw; ph = lh;
+	}
+	return BHIP_OK;
+}
+
+extern "C" {
+
+int bhip_pyramid_dev_u8(bhip_ctx* ctx, const int32_t* kernel, int kw, const int* scales, int n, const uint8_t* dev_in, long long inImageStride, int inStride,
+						int width, int height, int batch, uint8_t* dev_out) {
+	CHECK_CTX(ctx);
+	if (!kernel || !scales || !dev_in || !dev_out || batch <= 0 || width <= 0 || height <= 0 || inStride < width) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad pyramid arguments");
+	return pyramidU8Impl(ctx, kernel, kw, scales, n, dev_in, inImageStride, inStride, width, height, batch, dev_out, false);
+}
+
+int bhip_pyramid_u8(bhip_ctx* ctx, const int32_t* kernel, int kw, const int* scales, int n, const uint8_t* in, int inStart, int inStride, int width, int height,
+					uint8_t* out) {
+	CHECK_CTX(ctx);
+	CHECK_IMG(ctx, in, inStride, width, height, 1);
+	if (!out || !kernel || !scales) return bhip_fail(ctx, BHIP_ERR_INVALID, "null buffer");
+	long long total = 0;
+	if (bhip_pyramid_layout(width, height, scales, n, nullptr, nullptr, &total) != BHIP_OK) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad pyramid scales");
+	CtxScratch* sc = scratchOf(ctx);
+	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height));
+	BHIP_TRY(sc->out0.reserve(ctx, (size_t)total));
+	BHIP_TRY(upload(ctx, sc->in0.as<uint8_t>(), width, in, inStart, inStride, width, height, ctx->stream));
+	BHIP_TRY(pyramidU8Impl(ctx, kernel, kw, scales, n, sc->in0.as<uint8_t>(), (long long)width * height, width, width, height, 1, sc->out0.as<uint8_t>(), false));
+	BHIP_HIP(ctx, hipMemcpyAsync(out, sc->out0.p, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
 }
 
 int bhip_pyramid_f32(bhip_ctx* ctx, const float* kernel, int kw, const int* scales, int n, const float* in, int inStart, int inStride, int width,
@@ -2098,11 +2205,15 @@ struct bhip_klt : KltDevice {
 	int detectRadius = 0, detectBorder = 0;
 	float detectThreshold = 0;
 	std::vector<float> kernel;   // FactoryPyramid.discreteGaussian(scales, -1, 2)
+	std::vector<int32_t> kernelS32;   // the same for a GrayU8 tracker: Kernel1D_S32 [1,4,7,4,1]
+	bool u8 = false;             // GrayU8 frames with GrayS16 derivatives (bhip_klt_create_u8); pyr holds bytes, dx / dy shorts
 	bool haveFrame = false;
 	int ub = 0;                  // no sequence has more active tracks than this (exact after a spawn or bhip_klt_counts)
-	KltPyr view() const {
-		KltPyr P{};
-		P.img = pyr.as<float>(); P.dx = dx.as<float>(); P.dy = dy.as<float>();
+	KltPyr view() const { return viewT<float, float>(); }
+	template <class TI, class TD>
+	KltPyrT<TI, TD> viewT() const {
+		KltPyrT<TI, TD> P{};
+		P.img = pyr.as<TI>(); P.dx = dx.as<TD>(); P.dy = dy.as<TD>();
 		P.frameStride = total;
 		for (int l = 0; l < L; l++) { P.off[l] = offs[l]; P.w[l] = dims[2 * l]; P.h[l] = dims[2 * l + 1]; P.stride[l] = dims[2 * l]; P.scale[l] = (float)(double)scales[l]; }
 		P.numLayers = L; P.frameW = W; P.frameH = H;
@@ -2157,6 +2268,23 @@ static int kltReadCounts(bhip_klt* k, const int** out) {
 	return BHIP_OK;
 }
 
+// setDescription of the tracks `mode` selects (bhip_launch_klt_describe) on the tracker's own pixel types
+static int kltDescribe(bhip_klt* k, int mode, const int* count, int maxCount) {
+	if (k->u8) return bhip_launch_klt_describe(k->ctx, k->viewT<uint8_t, int16_t>(), k->tab.v, k->cfg, mode, count, maxCount);
+	return bhip_launch_klt_describe(k->ctx, k->view(), k->tab.v, k->cfg, mode, count, maxCount);
+}
+
+// process() once the pyramid and its gradient are in place
+static int kltTrackFrame(bhip_klt* k) {
+	bhip_ctx* ctx = k->ctx;
+	k->haveFrame = true;
+	BHIP_TRY(bhip_launch_klt_begin(ctx, k->tab.v));
+	if (k->u8) BHIP_TRY(bhip_launch_klt_track(ctx, k->viewT<uint8_t, int16_t>(), k->tab.v, k->cfg, k->ub));
+	else BHIP_TRY(bhip_launch_klt_track(ctx, k->view(), k->tab.v, k->cfg, k->ub));
+	BHIP_TRY(kltDescribe(k, 0, nullptr, k->ub));
+	return bhip_launch_klt_compact(ctx, k->tab.v, 0);
+}
+
 static int kltProcess(bhip_klt* k, const float* dev_frames, long long imageStride, int stride) {
 	bhip_ctx* ctx = k->ctx;
 	BHIP_TRY(bhip_pyramid_dev_f32(ctx, k->kernel.data(), (int)k->kernel.size(), k->scales, k->L, dev_frames, imageStride, stride, k->W, k->H, k->batch,
@@ -2164,12 +2292,21 @@ static int kltProcess(bhip_klt* k, const float* dev_frames, long long imageStrid
 	for (int l = 0; l < k->L; l++)   // PyramidOps.gradient with FactoryDerivative.sobel: BorderType.EXTENDED
 		BHIP_TRY(bhip_launch_gradient(ctx, 0, k->pyr.as<float>() + k->offs[l], k->dims[2 * l], k->dims[2 * l], k->dims[2 * l + 1], k->dx.as<float>() + k->offs[l],
 									  k->dy.as<float>() + k->offs[l], k->dims[2 * l], 2, k->batch, k->total, k->total));
-	k->haveFrame = true;
-	const KltPyr P = k->view();
-	BHIP_TRY(bhip_launch_klt_begin(ctx, k->tab.v));
-	BHIP_TRY(bhip_launch_klt_track(ctx, P, k->tab.v, k->cfg, k->ub));
-	BHIP_TRY(bhip_launch_klt_describe(ctx, P, k->tab.v, k->cfg, 0, nullptr, k->ub));
-	return bhip_launch_klt_compact(ctx, k->tab.v, 0);
+	return kltTrackFrame(k);
+}
+
+// GrayU8 frames: PyramidDiscreteSampleBlur<GrayU8> ([1,4,7,4,1] / 17), GradientSobel(GrayU8, GrayS16, GrayS16) with BorderType.EXTENDED.
+// dev_frames == nullptr: the frames are already in layer 0 of the pyramid (host frames are uploaded straight into it when scale[0] == 1)
+static int kltProcessU8(bhip_klt* k, const uint8_t* dev_frames, long long imageStride, int stride) {
+	bhip_ctx* ctx = k->ctx;
+	uint8_t* pyr = k->pyr.as<uint8_t>();
+	const bool inPlace = dev_frames == nullptr;
+	BHIP_TRY(pyramidU8Impl(ctx, k->kernelS32.data(), (int)k->kernelS32.size(), k->scales, k->L, inPlace ? pyr : dev_frames, inPlace ? k->total : imageStride,
+						   inPlace ? k->W : stride, k->W, k->H, k->batch, pyr, inPlace));
+	for (int l = 0; l < k->L; l++)
+		BHIP_TRY(bhip_launch_gradient_u8(ctx, 0, pyr + k->offs[l], k->total, k->dims[2 * l], k->dims[2 * l], k->dims[2 * l + 1], k->batch,
+										 k->dx.as<int16_t>() + k->offs[l], k->dy.as<int16_t>() + k->offs[l], k->total, k->dims[2 * l], 2));
+	return kltTrackFrame(k);
 }
 
 // spawnTracks from candidate lists on the device (dev_xy [batch][xyCap] (x,y) int16 pairs in layer-0 pixels, dev_n [batch], each <= xyCap)
@@ -2192,7 +2329,7 @@ static int kltSpawnFrom(bhip_klt* k, const int16_t* dev_xy, int xyCap, const int
 	if (need > 0) BHIP_TRY(kltGrow(k, (k->tab.v.cap + std::max(need, k->tab.v.cap / 2) + 255) & ~255));
 	const float scale0 = (float)(double)k->scales[0];
 	BHIP_TRY(bhip_launch_klt_spawn_place(ctx, k->tab.v, dev_xy, xyCap, dev_n, scale0, maxCand));
-	BHIP_TRY(bhip_launch_klt_describe(ctx, k->view(), k->tab.v, k->cfg, 1, dev_n, maxCand));
+	BHIP_TRY(kltDescribe(k, 1, dev_n, maxCand));
 	BHIP_TRY(bhip_launch_klt_spawn_commit(ctx, k->tab.v, dev_n));
 	k->ub = std::max(k->ub, ub);
 	return BHIP_OK;
@@ -2216,18 +2353,17 @@ static int kltStageTable(bhip_ctx* ctx, KltTable& tab, int radius, const float* 
 	BHIP_HIP(ctx, hipMemcpyAsync(tab.v.nAct, &n, 4, hipMemcpyHostToDevice, ctx->stream));
 	return bhip_ctx_synchronize(ctx);   // the host vectors leave scope
 }
-static KltPyr kltStagePyr(const float* img, const float* dx, const float* dy, int width, int height) {
-	KltPyr P{};
+template <class TI, class TD>
+static KltPyrT<TI, TD> kltStagePyr(const TI* img, const TD* dx, const TD* dy, int width, int height) {
+	KltPyrT<TI, TD> P{};
 	P.img = img; P.dx = dx; P.dy = dy;
 	P.w[0] = width; P.h[0] = height; P.stride[0] = width; P.scale[0] = 1.0f;
 	P.numLayers = 1; P.frameW = width; P.frameH = height;
 	return P;
 }
 
-extern "C" {
-
-int bhip_klt_create(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int templateRadius, const int* scales, int numLayers, int detectRadius, float detectThreshold,
-					int detectBorder, int width, int height, int batch, bhip_klt** out) {
+static int kltCreate(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int templateRadius, const int* scales, int numLayers, int detectRadius, float detectThreshold,
+					 int detectBorder, int width, int height, int batch, bool u8, bhip_klt** out) {
 	if (out) *out = nullptr;
 	if (!kltRangeOk(templateRadius, numLayers)) return BHIP_ERR_UNSUPPORTED;   // templateRadius 1..7, numLayers 1..8; nothing is touched, not even ctx
 	HandleRegistry& R = registry();
@@ -2247,17 +2383,30 @@ int bhip_klt_create(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int templateRadius, 
 	if (bhip_pyramid_layout(width, height, scales, numLayers, k->dims, k->offs, &k->total) != BHIP_OK) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad pyramid scales");
 	for (int l = 1; l < numLayers; l++)
 		if (scales[l] / scales[l - 1] <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Skip must be >= 1");
-	k->kernel = bhip_gaussian1d_f32(-1, 2);
-	const size_t bytes = (size_t)k->total * batch * 4;
-	BHIP_TRY(k->pyr.reserve(ctx, bytes));
-	BHIP_TRY(k->dx.reserve(ctx, bytes));
-	BHIP_TRY(k->dy.reserve(ctx, bytes));
+	k->u8 = u8;
+	if (u8) k->kernelS32 = bhip_gaussian1d_s32(2);
+	else k->kernel = bhip_gaussian1d_f32(-1, 2);
+	const size_t elems = (size_t)k->total * batch;
+	BHIP_TRY(k->pyr.reserve(ctx, elems * (u8 ? 1 : 4)));
+	BHIP_TRY(k->dx.reserve(ctx, elems * (u8 ? 2 : 4)));
+	BHIP_TRY(k->dy.reserve(ctx, elems * (u8 ? 2 : 4)));
 	BHIP_TRY(k->tab.alloc(ctx, batch, 1024, numLayers, templateRadius));
 	BHIP_TRY(bhip_launch_klt_init(ctx, k->tab.v, 0));
 	BHIP_TRY(bhip_ctx_synchronize(ctx));
 	R.klts.insert(k.get());
 	*out = k.release();
 	return BHIP_OK;
+}
+
+extern "C" {
+
+int bhip_klt_create(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int templateRadius, const int* scales, int numLayers, int detectRadius, float detectThreshold,
+					int detectBorder, int width, int height, int batch, bhip_klt** out) {
+	return kltCreate(ctx, cfg, templateRadius, scales, numLayers, detectRadius, detectThreshold, detectBorder, width, height, batch, false, out);
+}
+int bhip_klt_create_u8(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int templateRadius, const int* scales, int numLayers, int detectRadius, float detectThreshold,
+					   int detectBorder, int width, int height, int batch, bhip_klt** out) {
+	return kltCreate(ctx, cfg, templateRadius, scales, numLayers, detectRadius, detectThreshold, detectBorder, width, height, batch, true, out);
 }
 
 int bhip_klt_destroy(bhip_klt* k) {
@@ -2272,14 +2421,43 @@ int bhip_klt_destroy(bhip_klt* k) {
 	return BHIP_OK;
 }
 
+#define CHECK_KLT_TYPE(k, wantU8) \
+	if ((k)->u8 != (wantU8)) return bhip_fail(ctx, BHIP_ERR_INVALID, (k)->u8 ? "this tracker was created for GrayU8 frames" : "this tracker was created for GrayF32 frames")
+
 int bhip_klt_process_dev_f32(bhip_klt* k, const float* dev_frames, long long imageStride, int stride) {
 	CHECK_KLT(k);
+	CHECK_KLT_TYPE(k, false);
 	if (!dev_frames || stride < k->W) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image batch");
 	return kltProcess(k, dev_frames, imageStride, stride);
 }
 
+int bhip_klt_process_dev_u8(bhip_klt* k, const uint8_t* dev_frames, long long imageStride, int stride) {
+	CHECK_KLT(k);
+	CHECK_KLT_TYPE(k, true);
+	if (!dev_frames || stride < k->W) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image batch");
+	return kltProcessU8(k, dev_frames, imageStride, stride);
+}
+
+int bhip_klt_process_u8(bhip_klt* k, const uint8_t* const* img, const int* startIndex, const int* stride) {
+	CHECK_KLT(k);
+	CHECK_KLT_TYPE(k, true);
+	if (!img) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image batch");
+	for (int b = 0; b < k->batch; b++)
+		if (!img[b] || (stride ? stride[b] : k->W) < k->W) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image (null or stride < width)");
+	// scale[0] == 1: layer 0 is the frame itself, so it is uploaded to where the pyramid keeps it; otherwise to a staging block
+	const bool inPlace = k->scales[0] == 1;
+	const long long px = (long long)k->W * k->H, frameStride = inPlace ? k->total : px;
+	if (!inPlace) BHIP_TRY(k->frames.reserve(ctx, (size_t)px * k->batch));
+	uint8_t* dst = inPlace ? k->pyr.as<uint8_t>() : k->frames.as<uint8_t>();
+	for (int b = 0; b < k->batch; b++)
+		BHIP_TRY(upload(ctx, dst + b * frameStride, k->W, img[b], startIndex ? startIndex[b] : 0, stride ? stride[b] : k->W, k->W, k->H, ctx->stream));
+	BHIP_TRY(kltProcessU8(k, inPlace ? nullptr : dst, px, k->W));
+	return bhip_ctx_synchronize(ctx);   // the caller's frames have been consumed
+}
+
 int bhip_klt_process_f32(bhip_klt* k, const float* const* img, const int* startIndex, const int* stride) {
 	CHECK_KLT(k);
+	CHECK_KLT_TYPE(k, false);
 	if (!img) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image batch");
 	const long long px = (long long)k->W * k->H;
 	BHIP_TRY(k->frames.reserve(ctx, (size_t)px * 4 * k->batch));
@@ -2299,7 +2477,9 @@ int bhip_klt_spawn(bhip_klt* k, int maxFeatures) {
 	const long long px = (long long)w0 * h0;
 	BHIP_TRY(k->intensity.reserve(ctx, (size_t)px * 4 * k->batch));
 	float* inten = k->intensity.as<float>();
-	BHIP_TRY(cornerImpl(ctx, false, false, 0, 1, 0.0f, k->dx.as<float>() + k->offs[0], k->dy.as<float>() + k->offs[0], k->total, w0, w0, h0, k->batch, inten, px, w0));
+	// FactoryIntensityPointAlg.shiTomasi(1, false, derivType): ImplSsdCorner_F32, or ImplSsdCorner_S16 on the GrayS16 derivatives of a GrayU8 tracker
+	if (k->u8) BHIP_TRY(cornerImpl(ctx, true, false, 0, 1, 0.0f, k->dx.as<int16_t>() + k->offs[0], k->dy.as<int16_t>() + k->offs[0], k->total, w0, w0, h0, k->batch, inten, px, w0));
+	else BHIP_TRY(cornerImpl(ctx, false, false, 0, 1, 0.0f, k->dx.as<float>() + k->offs[0], k->dy.as<float>() + k->offs[0], k->total, w0, w0, h0, k->batch, inten, px, w0));
 	BHIP_TRY(bhip_launch_klt_mark_exclude(ctx, k->tab.v, (float)(double)k->scales[0], inten, px, w0, w0, h0, k->ub));
 	const int step = k->detectRadius + 1;
 	const int rw = std::max(w0 - 2 * k->detectBorder, 0), rh = std::max(h0 - 2 * k->detectBorder, 0);
@@ -2347,7 +2527,7 @@ int bhip_klt_add_tracks(bhip_klt* k, const int* seq, const double* xy, int n, ui
 	BHIP_HIP(ctx, hipMemcpyAsync(dxy, xy, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
 	BHIP_HIP(ctx, hipMemcpyAsync(dseq, seq, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
 	BHIP_TRY(bhip_launch_klt_add(ctx, k->tab.v, dseq, dxy, n, k->W, k->H, dok, dlist));
-	BHIP_TRY(bhip_launch_klt_describe(ctx, k->view(), k->tab.v, k->cfg, 3, dlist, n));   // tracker.setDescription(t): the result is not looked at
+	BHIP_TRY(kltDescribe(k, 3, dlist, n));   // tracker.setDescription(t): the result is not looked at
 	BHIP_HIP(ctx, hipMemcpyAsync(ok, dok, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
 	k->ub += *std::max_element(want.begin(), want.end());
 	return bhip_ctx_synchronize(ctx);
@@ -2420,6 +2600,24 @@ int bhip_klt_fetch(bhip_klt* k, int which, int seq, long long* featureId, float*
 	return bhip_ctx_synchronize(ctx);
 }
 
+int bhip_klt_fetch_templates(bhip_klt* k, int which, int seq, int layer, float* tmpl, float* G) {
+	CHECK_KLT(k);
+	if (which < 0 || which > 2 || seq < 0 || seq >= k->batch || layer < 0 || layer >= k->L) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad list selector");
+	const int* h = nullptr;
+	BHIP_TRY(kltReadCounts(k, &h));
+	const int n = h[(which == 0 ? 0 : which == 1 ? 2 : 1) * k->batch + seq];
+	if (n == 0) return BHIP_OK;
+	// stage: [templates 3 len n floats | G 3n floats]
+	const size_t nt = (size_t)n * 3 * k->tab.v.len;
+	BHIP_TRY(k->stage.reserve(ctx, (nt + (size_t)3 * n) * 4));
+	float* dt = k->stage.as<float>();
+	float* dg = dt + nt;
+	BHIP_TRY(bhip_launch_klt_gather_templates(ctx, k->tab.v, which, seq, layer, n, dt, dg));
+	if (tmpl) BHIP_HIP(ctx, hipMemcpyAsync(tmpl, dt, nt * 4, hipMemcpyDeviceToHost, ctx->stream));
+	if (G) BHIP_HIP(ctx, hipMemcpyAsync(G, dg, (size_t)3 * n * 4, hipMemcpyDeviceToHost, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
+}
+
 int bhip_klt_stats(bhip_klt* k, long long* tracks, long long* iterations, long long* borderIterations) {
 	CHECK_KLT(k);
 	BHIP_TRY(k->stage.reserve(ctx, 32));
@@ -2437,6 +2635,7 @@ int bhip_klt_stats(bhip_klt* k, long long* tracks, long long* iterations, long l
 
 int bhip_klt_fetch_layer(bhip_klt* k, int seq, int layer, int which, float* out) {
 	CHECK_KLT(k);
+	CHECK_KLT_TYPE(k, false);
 	if (!k->haveFrame) return bhip_fail(ctx, BHIP_ERR_INVALID, "no frame processed");
 	if (seq < 0 || seq >= k->batch || layer < 0 || layer >= k->L || which < 0 || which > 2 || !out) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad layer selector");
 	const float* src = (which == 0 ? k->pyr : which == 1 ? k->dx : k->dy).as<float>() + (long long)seq * k->total + k->offs[layer];
@@ -2444,10 +2643,50 @@ int bhip_klt_fetch_layer(bhip_klt* k, int seq, int layer, int which, float* out)
 	return bhip_ctx_synchronize(ctx);
 }
 
+int bhip_klt_fetch_layer_u8(bhip_klt* k, int seq, int layer, uint8_t* out) {
+	CHECK_KLT(k);
+	CHECK_KLT_TYPE(k, true);
+	if (!k->haveFrame) return bhip_fail(ctx, BHIP_ERR_INVALID, "no frame processed");
+	if (seq < 0 || seq >= k->batch || layer < 0 || layer >= k->L || !out) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad layer selector");
+	const uint8_t* src = k->pyr.as<uint8_t>() + (long long)seq * k->total + k->offs[layer];
+	BHIP_HIP(ctx, hipMemcpyAsync(out, src, (size_t)k->dims[2 * layer] * k->dims[2 * layer + 1], hipMemcpyDeviceToHost, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
+}
+
+int bhip_klt_fetch_layer_s16(bhip_klt* k, int seq, int layer, int which, int16_t* out) {
+	CHECK_KLT(k);
+	CHECK_KLT_TYPE(k, true);
+	if (!k->haveFrame) return bhip_fail(ctx, BHIP_ERR_INVALID, "no frame processed");
+	if (seq < 0 || seq >= k->batch || layer < 0 || layer >= k->L || which < 1 || which > 2 || !out) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad layer selector");
+	const int16_t* src = (which == 1 ? k->dx : k->dy).as<int16_t>() + (long long)seq * k->total + k->offs[layer];
+	BHIP_HIP(ctx, hipMemcpyAsync(out, src, (size_t)k->dims[2 * layer] * k->dims[2 * layer + 1] * 2, hipMemcpyDeviceToHost, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
+}
+
+int bhip_klt_dev_view_u8(bhip_klt* k, const int** dev_activeSlots, const int** dev_activeCount, const float** dev_x, const float** dev_y,
+						 const long long** dev_featureId, const uint8_t** dev_pyramid, const int16_t** dev_derivX, const int16_t** dev_derivY, int* slotsPerSequence,
+						 long long* elementsPerFrame) {
+	CHECK_KLT(k);
+	CHECK_KLT_TYPE(k, true);
+	const KltTab& T = k->tab.v;
+	if (dev_activeSlots) *dev_activeSlots = T.act;
+	if (dev_activeCount) *dev_activeCount = T.nAct;
+	if (dev_x) *dev_x = T.x;
+	if (dev_y) *dev_y = T.y;
+	if (dev_featureId) *dev_featureId = T.id;
+	if (dev_pyramid) *dev_pyramid = k->pyr.as<uint8_t>();
+	if (dev_derivX) *dev_derivX = k->dx.as<int16_t>();
+	if (dev_derivY) *dev_derivY = k->dy.as<int16_t>();
+	if (slotsPerSequence) *slotsPerSequence = T.cap;
+	if (elementsPerFrame) *elementsPerFrame = k->total;
+	return BHIP_OK;
+}
+
 int bhip_klt_dev_view(bhip_klt* k, const int** dev_activeSlots, const int** dev_activeCount, const float** dev_x, const float** dev_y,
 					  const long long** dev_featureId, const float** dev_pyramid, const float** dev_derivX, const float** dev_derivY, int* slotsPerSequence,
 					  long long* floatsPerFrame) {
 	CHECK_KLT(k);
+	CHECK_KLT_TYPE(k, false);
 	const KltTab& T = k->tab.v;
 	if (dev_activeSlots) *dev_activeSlots = T.act;
 	if (dev_activeCount) *dev_activeCount = T.nAct;
@@ -2462,9 +2701,12 @@ int bhip_klt_dev_view(bhip_klt* k, const int** dev_activeSlots, const int** dev_
 	return BHIP_OK;
 }
 
-int bhip_klt_set_description_f32(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const float* image, int imgStart, int imgStride, const float* derivX,
-								 const float* derivY, int dStart, int dStride, int width, int height, const float* xy, int n, float* desc, float* descX,
-								 float* descY, float* G, uint8_t* ok) {
+}  // extern "C"
+
+template <class TI, class TD>
+static int kltSetDescriptionStage(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const TI* image, int imgStart, int imgStride, const TD* derivX,
+								  const TD* derivY, int dStart, int dStride, int width, int height, const float* xy, int n, float* desc, float* descX,
+								  float* descY, float* G, uint8_t* ok) {
 	if (!kltRangeOk(radius, 1)) return BHIP_ERR_UNSUPPORTED;   // templateRadius 1..7; nothing is written
 	CHECK_CTX(ctx);
 	CHECK_IMG(ctx, image, imgStride, width, height, 1);
@@ -2475,16 +2717,16 @@ int bhip_klt_set_description_f32(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int rad
 	bhip_klt_cfg c;
 	if (cfg) c = *cfg; else bhip_klt_cfg_default(&c);
 	CtxScratch* sc = scratchOf(ctx);
-	const size_t bytes = (size_t)width * height * 4;
-	BHIP_TRY(sc->in0.reserve(ctx, bytes));
-	BHIP_TRY(sc->in1.reserve(ctx, bytes));
-	BHIP_TRY(sc->tmp0.reserve(ctx, bytes));
-	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, image, imgStart, imgStride, width, height, ctx->stream));
-	BHIP_TRY(upload(ctx, sc->in1.as<float>(), width, derivX, dStart, dStride, width, height, ctx->stream));
-	BHIP_TRY(upload(ctx, sc->tmp0.as<float>(), width, derivY, dStart, dStride, width, height, ctx->stream));
+	const size_t px = (size_t)width * height;
+	BHIP_TRY(sc->in0.reserve(ctx, px * sizeof(TI)));
+	BHIP_TRY(sc->in1.reserve(ctx, px * sizeof(TD)));
+	BHIP_TRY(sc->tmp0.reserve(ctx, px * sizeof(TD)));
+	BHIP_TRY(upload(ctx, sc->in0.as<TI>(), width, image, imgStart, imgStride, width, height, ctx->stream));
+	BHIP_TRY(upload(ctx, sc->in1.as<TD>(), width, derivX, dStart, dStride, width, height, ctx->stream));
+	BHIP_TRY(upload(ctx, sc->tmp0.as<TD>(), width, derivY, dStart, dStride, width, height, ctx->stream));
 	KltTable tab;
 	BHIP_TRY(kltStageTable(ctx, tab, radius, xy, n));
-	BHIP_TRY(bhip_launch_klt_describe(ctx, kltStagePyr(sc->in0.as<float>(), sc->in1.as<float>(), sc->tmp0.as<float>(), width, height), tab.v, c, 2, nullptr, n));
+	BHIP_TRY(bhip_launch_klt_describe(ctx, kltStagePyr<TI, TD>(sc->in0.as<TI>(), sc->in1.as<TD>(), sc->tmp0.as<TD>(), width, height), tab.v, c, 2, nullptr, n));
 	const int len = tab.v.len;
 	std::vector<float> t((size_t)n * 3 * len), g((size_t)3 * n);
 	std::vector<int> keep(n), fault(n);
@@ -2505,8 +2747,9 @@ int bhip_klt_set_description_f32(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int rad
 	return BHIP_OK;
 }
 
-int bhip_klt_track_f32(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const float* image, int imgStart, int imgStride, int width, int height,
-					   const float* desc, const float* descX, const float* descY, const float* G, float* xy, int n, int* fault, float* error) {
+template <class TI, class TD>
+static int kltTrackStage(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const TI* image, int imgStart, int imgStride, int width, int height,
+						 const float* desc, const float* descX, const float* descY, const float* G, float* xy, int n, int* fault, float* error) {
 	if (!kltRangeOk(radius, 1)) return BHIP_ERR_UNSUPPORTED;   // templateRadius 1..7; nothing is written
 	CHECK_CTX(ctx);
 	bhip_klt_cfg c;
@@ -2516,8 +2759,8 @@ int bhip_klt_track_f32(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const
 	if (n < 0 || (n > 0 && (!xy || !desc || !descX || !descY || !G || !fault || !error))) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad feature list");
 	if (n == 0) return BHIP_OK;
 	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
-	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, image, imgStart, imgStride, width, height, ctx->stream));
+	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * sizeof(TI)));
+	BHIP_TRY(upload(ctx, sc->in0.as<TI>(), width, image, imgStart, imgStride, width, height, ctx->stream));
 	KltTable tab;
 	BHIP_TRY(kltStageTable(ctx, tab, radius, xy, n));
 	const int len = tab.v.len;
@@ -2532,7 +2775,7 @@ int bhip_klt_track_f32(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const
 	BHIP_HIP(ctx, hipMemcpyAsync(tab.v.gxx, g.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
 	BHIP_HIP(ctx, hipMemcpyAsync(tab.v.gyy, g.data() + n, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
 	BHIP_HIP(ctx, hipMemcpyAsync(tab.v.gxy, g.data() + 2 * n, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-	BHIP_TRY(bhip_launch_klt_track(ctx, kltStagePyr(sc->in0.as<float>(), nullptr, nullptr, width, height), tab.v, c, n));
+	BHIP_TRY(bhip_launch_klt_track(ctx, kltStagePyr<TI, TD>(sc->in0.as<TI>(), nullptr, nullptr, width, height), tab.v, c, n));
 	BHIP_HIP(ctx, hipMemcpyAsync(pos.data(), tab.v.lx, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
 	BHIP_HIP(ctx, hipMemcpyAsync(pos.data() + n, tab.v.ly, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
 	BHIP_HIP(ctx, hipMemcpyAsync(fault, tab.v.fault, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -2540,6 +2783,29 @@ int bhip_klt_track_f32(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const
 	BHIP_TRY(bhip_ctx_synchronize(ctx));
 	for (int i = 0; i < n; i++) { xy[2 * i] = pos[i]; xy[2 * i + 1] = pos[n + i]; }
 	return BHIP_OK;
+}
+
+extern "C" {
+
+int bhip_klt_set_description_f32(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const float* image, int imgStart, int imgStride, const float* derivX,
+								 const float* derivY, int dStart, int dStride, int width, int height, const float* xy, int n, float* desc, float* descX,
+								 float* descY, float* G, uint8_t* ok) {
+	return kltSetDescriptionStage<float, float>(ctx, cfg, radius, image, imgStart, imgStride, derivX, derivY, dStart, dStride, width, height, xy, n, desc, descX,
+												descY, G, ok);
+}
+int bhip_klt_set_description_u8(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const uint8_t* image, int imgStart, int imgStride, const int16_t* derivX,
+								const int16_t* derivY, int dStart, int dStride, int width, int height, const float* xy, int n, float* desc, float* descX,
+								float* descY, float* G, uint8_t* ok) {
+	return kltSetDescriptionStage<uint8_t, int16_t>(ctx, cfg, radius, image, imgStart, imgStride, derivX, derivY, dStart, dStride, width, height, xy, n, desc,
+													descX, descY, G, ok);
+}
+int bhip_klt_track_f32(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const float* image, int imgStart, int imgStride, int width, int height,
+					   const float* desc, const float* descX, const float* descY, const float* G, float* xy, int n, int* fault, float* error) {
+	return kltTrackStage<float, float>(ctx, cfg, radius, image, imgStart, imgStride, width, height, desc, descX, descY, G, xy, n, fault, error);
+}
+int bhip_klt_track_u8(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const uint8_t* image, int imgStart, int imgStride, int width, int height,
+					  const float* desc, const float* descX, const float* descY, const float* G, float* xy, int n, int* fault, float* error) {
+	return kltTrackStage<uint8_t, int16_t>(ctx, cfg, radius, image, imgStart, imgStride, width, height, desc, descX, descY, G, xy, n, fault, error);
 }
 
 }  // extern "C"

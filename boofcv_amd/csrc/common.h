@@ -274,6 +274,11 @@ int bhip_launch_gradient(bhip_ctx* ctx, int kind, const float* in, int inStride,
 // fused Gaussian-weighted corner intensity on F32 or S16 derivatives.  Element strides throughout.
 int bhip_launch_gradient_u8(bhip_ctx* ctx, int kind, const uint8_t* in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dx,
 							int16_t* dy, long long outImageStride, int outStride, int border);
+// ConvolveImageDownNormalized.horizontal / vertical (Kernel1D_S32, GrayU8, GrayI8, skip): the integer pyramid's layer step; element strides
+int bhip_launch_conv_down_u8(bhip_ctx* ctx, bool vertical, const int32_t* kernel, int kw, const uint8_t* in, long long inImageStride, int inStride, int width,
+							 int height, uint8_t* out, long long outImageStride, int outStride, int outWidth, int outHeight, int skip, int batch);
+int bhip_launch_copy_images_u8(bhip_ctx* ctx, const uint8_t* in, long long inImageStride, int inStride, uint8_t* out, long long outImageStride, int outStride,
+							   int width, int height, int batch);
 size_t bhip_corner_box_s16_scratch(int radius, int width, int height, int batch);   // bytes of `scratch` bhip_launch_corner_box_s16 needs (0: none)
 int bhip_launch_corner_box_s16(bhip_ctx* ctx, int kind, int radius, float kappa, const int16_t* dx, const int16_t* dy, long long dImageStride, int dStride,
 							   int width, int height, int batch, float* intensity, long long iImageStride, int iStride, void* scratch);
@@ -298,11 +303,13 @@ int bhip_launch_blocks_to_xy(bhip_ctx* ctx, const unsigned int* bitmap, const un
 #define BHIP_KLT_MAX_RADIUS 7
 #define BHIP_KLT_MAX_LEN ((2 * BHIP_KLT_MAX_RADIUS + 1) * (2 * BHIP_KLT_MAX_RADIUS + 1))
 
-// image pyramid + derivative pyramids of `batch` frames: layer l of frame b starts at base + b * frameStride + off[l], rows stride[l] floats apart
-struct KltPyr {
-	const float* img;
-	const float* dx;   // nullptr when only tracking (PyramidKltTracker.setImage(image))
-	const float* dy;
+// image pyramid + derivative pyramids of `batch` frames: layer l of frame b starts at base + b * frameStride + off[l], rows stride[l] elements apart.
+// TI / TD: pixel types of the image and of its derivatives -- GrayF32 / GrayF32 or GrayU8 / GrayS16
+template <class TI, class TD>
+struct KltPyrT {
+	const TI* img;
+	const TD* dx;   // nullptr when only tracking (PyramidKltTracker.setImage(image))
+	const TD* dy;
 	long long frameStride;
 	long long off[BHIP_KLT_MAX_LAYERS];
 	int w[BHIP_KLT_MAX_LAYERS], h[BHIP_KLT_MAX_LAYERS], stride[BHIP_KLT_MAX_LAYERS];
@@ -310,6 +317,8 @@ struct KltPyr {
 	int numLayers;
 	int frameW, frameH;                 // the input frame (PointTrackerKltPyramid's image.isInBounds)
 };
+using KltPyr = KltPyrT<float, float>;
+using KltPyrU8 = KltPyrT<uint8_t, int16_t>;
 
 // Track table of one tracker object.  Sequence b owns slots [0, cap); slot s of sequence b is entry g = b * cap + s of every per-track array
 // (structure of arrays: the fields of neighbouring tracks are contiguous).  Lists hold slot numbers, in the reference's list order.
@@ -337,6 +346,8 @@ int bhip_launch_klt_track(bhip_ctx* ctx, KltPyr P, KltTab T, bhip_klt_cfg cfg, i
 // mode 3: the table entries count[0 .. maxCount) are described at their x,y (addTrack; entries < 0 are skipped)
 // mode 2: every active track is described at its x,y (stage-level calls); keep = setDescription's result
 int bhip_launch_klt_describe(bhip_ctx* ctx, KltPyr P, KltTab T, bhip_klt_cfg cfg, int mode, const int* count, int maxCount);
+int bhip_launch_klt_track(bhip_ctx* ctx, KltPyrU8 P, KltTab T, bhip_klt_cfg cfg, int maxActive);
+int bhip_launch_klt_describe(bhip_ctx* ctx, KltPyrU8 P, KltTab T, bhip_klt_cfg cfg, int mode, const int* count, int maxCount);
 int bhip_launch_klt_compact(bhip_ctx* ctx, KltTab T, int toUnused);   // active := kept tracks in order; the others go to dropped (or straight to unused)
 int bhip_launch_klt_mark_exclude(bhip_ctx* ctx, KltTab T, float scale0, float* intensity, long long imageStride, int stride, int w, int h, int maxActive);
 int bhip_launch_klt_spawn_place(bhip_ctx* ctx, KltTab T, const int16_t* xy, int xyCap, const int* count, float scale0, int maxCount);
@@ -346,3 +357,4 @@ int bhip_launch_klt_match_drop(bhip_ctx* ctx, KltTab T, const int* seq, const lo
 int bhip_launch_klt_drop_all(bhip_ctx* ctx, KltTab T, int resetTotal);
 int bhip_launch_klt_stats(bhip_ctx* ctx, KltTab T, unsigned long long* out);   // out[3] += tracks, iterations, border-form iterations of the last process()
 int bhip_launch_klt_gather(bhip_ctx* ctx, KltTab T, int which, int seq, int n, long long* id, float* xy, int* fault, float* err);
+int bhip_launch_klt_gather_templates(bhip_ctx* ctx, KltTab T, int which, int seq, int layer, int n, float* tmpl, float* G);

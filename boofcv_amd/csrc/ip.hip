@@ -1954,6 +1954,8 @@ int bhip_launch_integral_u8(bhip_ctx* ctx, const unsigned char* in, long long in
 //   border: DerivativeHelperFunctions.processBorderHorizontal/Vertical with kernelDeriv_I32
 // The arithmetic is integer, so the interior expression and every border form give the same value: the 3x3 (3-tap) formula on the image
 // padded with 0.  With border 1 every pixel is written, with border 0 only the interior (frame untouched).  Results fit in a short.
+// Border 2 (Sobel only) is BorderType.EXTENDED -- ImageBorder1D_S32 with BorderIndex1D_Extend (I:core/image/border/BorderIndex1D_Extend.java):
+// the same nine-tap sum on the index-clamped image; every pixel is written.
 struct GradU8Params {
 	const uint8_t* in;
 	int16_t* dx;
@@ -1965,23 +1967,28 @@ struct GradU8Params {
 struct GradRowU8 { int v[6]; };   // columns x-1 .. x+4 of one row (0 outside the image)
 __device__ __forceinline__ GradRowU8 gradU8LoadRow(const GradU8Params& P, const uint8_t* img, int x, int y, int lane) {
 	GradRowU8 r;
+	const bool ext = P.border == 2;   // outside pixels read the nearest pixel of the image instead of 0
 	if (y < 0 || y >= P.height) {
+		if (!ext) {
 #pragma unroll
-		for (int i = 0; i < 6; i++) r.v[i] = 0;
-		return r;
+			for (int i = 0; i < 6; i++) r.v[i] = 0;
+			return r;
+		}
+		y = y < 0 ? 0 : P.height - 1;
 	}
 	const uint8_t* row = img + (long long)y * P.inStride;
+	const int last = P.width - 1;
 	int c[4];
 	if (x + 3 < P.width && (reinterpret_cast<uintptr_t>(row + x) & 3) == 0) {
 		const unsigned w = *reinterpret_cast<const unsigned*>(row + x);
 		c[0] = w & 255; c[1] = (w >> 8) & 255; c[2] = (w >> 16) & 255; c[3] = w >> 24;
 	} else {
 #pragma unroll
-		for (int j = 0; j < 4; j++) c[j] = x + j < P.width ? row[x + j] : 0;
+		for (int j = 0; j < 4; j++) c[j] = x + j < P.width ? row[x + j] : ext ? row[last] : 0;
 	}
 	int left = __shfl_up(c[3], 1, 64), right = __shfl_down(c[0], 1, 64);
-	if (lane == 0) left = (x - 1 >= 0 && x - 1 < P.width) ? row[x - 1] : 0;
-	if (lane == 63) right = (x + 4 < P.width) ? row[x + 4] : 0;
+	if (lane == 0) left = x - 1 < 0 ? (ext ? row[0] : 0) : x - 1 < P.width ? row[x - 1] : ext ? row[last] : 0;
+	if (lane == 63) right = x + 4 < P.width ? row[x + 4] : ext ? row[last] : 0;
 	r.v[0] = left; r.v[1] = c[0]; r.v[2] = c[1]; r.v[3] = c[2]; r.v[4] = c[3]; r.v[5] = right;
 	return r;
 }
@@ -2047,6 +2054,207 @@ int bhip_launch_gradient_u8(bhip_ctx* ctx, int kind, const uint8_t* in, long lon
 	dim3 grid((width + 255) / 256, (height + 4 * GR_ROWS - 1) / (4 * GR_ROWS), batch);
 	if (kind == 0) hipLaunchKernelGGL(k_grad_u8<0>, grid, dim3(256), 0, ctx->stream, P);
 	else hipLaunchKernelGGL(k_grad_u8<1>, grid, dim3(256), 0, ctx->stream, P);
+	BHIP_HIP(ctx, hipGetLastError());
+	return BHIP_OK;
+}
+
+// ---------------- GrayU8 down-sampling convolution (integer pyramid layer step) ----------------
+// ConvolveImageDownNormalized.horizontal/vertical(Kernel1D_S32, GrayU8, GrayI8, skip)   I:alg/filter/convolve/ConvolveImageDownNormalized.java:109-137
+//   interior  I:alg/filter/convolve/down/ConvolveDownNoBorderStandard.java:329-394 == ConvolveDownNoBorderUnrolled_U8_I8_Div:
+//             (byte)((total + divisor/2) / divisor), divisor = kernel.computeSum()
+//   border    I:alg/filter/convolve/down/ConvolveDownNormalized_JustBorder.java:262-358: (byte)((total + weight/2) / weight) over the taps inside
+//   naive     I:alg/filter/convolve/down/ConvolveDownNormalizedNaive.java:133-187 (kernel.width >= image.width, in the vertical call too)
+// The position classes along the filtered axis are those of k_conv_down (same UtilDownConvolve ranges).  All three forms are one integer
+// expression: the interior's divisor is the weight of the full tap range.  Plain int division (Java's, truncating) for any S32 kernel.
+struct ConvDownU8Params {
+	const uint8_t* in;
+	uint8_t* out;
+	long long inImageStride, outImageStride;
+	int inStride, outStride, width, height;   // input size
+	int skip, kw, radius, naive;
+	int offset, offsetRem, maxSide, offsetEnd, sideTrunc;   // along the filtered axis
+	int k[BHIP_MAX_TAPS];
+};
+// taps [k0, k1] around `centre` of output D along an axis of `side` pixels; false: the reference does not write this output
+__device__ __forceinline__ bool downU8Range(const ConvDownU8Params& P, int D, int side, int& centre, int& k0, int& k1) {
+	const int r = P.radius;
+	centre = D * P.skip;
+	if (P.naive) {
+		k0 = max(-r, -centre);
+		k1 = min(r, side - 1 - centre);
+	} else if (centre >= P.offsetEnd && centre < P.sideTrunc) {
+		k0 = -r;
+		k1 = min(r, side - centre - 1);
+	} else if (centre < P.offset) {
+		k0 = -centre;
+		k1 = r;
+	} else {
+		centre += P.offsetRem;
+		if (centre > P.maxSide) return false;
+		k0 = -r; k1 = r;
+	}
+	return true;
+}
+__device__ __forceinline__ unsigned downU8Round(int total, int weight) { return weight != 0 ? (unsigned)((total + weight / 2) / weight) & 255u : 0u; }
+__device__ __forceinline__ void downU8Store(uint8_t* dst, const unsigned (&v)[4], const bool (&wr)[4]) {
+	if (wr[0] && wr[1] && wr[2] && wr[3] && (reinterpret_cast<uintptr_t>(dst) & 3) == 0)
+		*reinterpret_cast<unsigned*>(dst) = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
+	else {
+#pragma unroll
+		for (int j = 0; j < 4; j++)
+			if (wr[j]) dst[j] = (uint8_t)v[j];
+	}
+}
+// a thread owns four neighbouring outputs of one row, stored as one dword where the row end and the alignment allow
+__global__ __launch_bounds__(256) void k_conv_down_h_u8(ConvDownU8Params P) {
+	const int outW = P.width / P.skip;
+	const int ox = (blockIdx.x * 256 + threadIdx.x) * 4;
+	if (ox >= outW) return;
+	const uint8_t* row = P.in + (long long)blockIdx.z * P.inImageStride + (long long)blockIdx.y * P.inStride;
+	unsigned v[4];
+	bool wr[4];
+	// the usual layer step (skip 2, radius <= 2) away from the row ends: the four outputs are centred on input columns 2 ox + {0, 2, 4, 6}
+	// and read columns 2 ox - 2 .. 2 ox + 8, which are four dwords from 2 ox - 4 when the row is dword aligned
+	const int c0 = 2 * ox;
+	if (P.skip == 2 && P.radius <= 2 && !P.naive && ox + 3 < outW && c0 - 4 >= 0 && c0 + 12 <= P.width && c0 >= P.offset && c0 + 6 <= P.maxSide &&
+		(reinterpret_cast<uintptr_t>(row + c0) & 3) == 0) {
+		const uint4 q = make_uint4(*reinterpret_cast<const unsigned*>(row + c0 - 4), *reinterpret_cast<const unsigned*>(row + c0),
+								   *reinterpret_cast<const unsigned*>(row + c0 + 4), *reinterpret_cast<const unsigned*>(row + c0 + 8));
+		const unsigned w[4] = {q.x, q.y, q.z, q.w};
+		int b[16];   // b[i] = input column c0 - 4 + i
+#pragma unroll
+		for (int i = 0; i < 16; i++) b[i] = (w[i >> 2] >> (8 * (i & 3))) & 255;
+		int kk[5], weight = 0;   // the kernel centred in five taps (zeros around a narrower one): every register index below is a constant
+#pragma unroll
+		for (int i = 0; i < 5; i++) {
+			const int t = i - 2 + P.radius;
+			kk[i] = t >= 0 && t < P.kw ? P.k[t] : 0;
+			weight += kk[i];
+		}
+#pragma unroll
+		for (int j = 0; j < 4; j++) {
+			int total = 0;
+#pragma unroll
+			for (int i = 0; i < 5; i++) total += b[2 + 2 * j + i] * kk[i];
+			v[j] = downU8Round(total, weight);
+			wr[j] = true;
+		}
+		downU8Store(P.out + (long long)blockIdx.z * P.outImageStride + (long long)blockIdx.y * P.outStride + ox, v, wr);
+		return;
+	}
+#pragma unroll
+	for (int j = 0; j < 4; j++) {
+		int centre, k0, k1;
+		v[j] = 0;
+		wr[j] = ox + j < outW && downU8Range(P, ox + j, P.width, centre, k0, k1);
+		if (!wr[j]) continue;
+		int total = 0, weight = 0;
+		for (int k = k0; k <= k1; k++) {
+			const int w = P.k[k + P.radius];
+			weight += w;
+			total += row[centre + k] * w;
+		}
+		v[j] = downU8Round(total, weight);
+	}
+	downU8Store(P.out + (long long)blockIdx.z * P.outImageStride + (long long)blockIdx.y * P.outStride + ox, v, wr);
+}
+// a thread owns four neighbouring columns of one output row: every tap row is one dword load where aligned
+__global__ __launch_bounds__(256) void k_conv_down_v_u8(ConvDownU8Params P) {
+	const int x = (blockIdx.x * 256 + threadIdx.x) * 4, oy = blockIdx.y;
+	if (x >= P.width) return;
+	int centre, k0, k1;
+	if (!downU8Range(P, oy, P.height, centre, k0, k1)) return;   // uniform over the grid row
+	const uint8_t* src = P.in + (long long)blockIdx.z * P.inImageStride + (long long)centre * P.inStride + x;
+	const bool full4 = x + 3 < P.width;
+	int total[4] = {0, 0, 0, 0}, weight = 0;
+	for (int k = k0; k <= k1; k++) {
+		const int w = P.k[k + P.radius];
+		const uint8_t* s = src + (long long)k * P.inStride;
+		weight += w;
+		if (full4 && (reinterpret_cast<uintptr_t>(s) & 3) == 0) {
+			const unsigned q = *reinterpret_cast<const unsigned*>(s);
+			total[0] += (int)(q & 255) * w; total[1] += (int)((q >> 8) & 255) * w; total[2] += (int)((q >> 16) & 255) * w; total[3] += (int)(q >> 24) * w;
+		} else {
+#pragma unroll
+			for (int j = 0; j < 4; j++)
+				if (x + j < P.width) total[j] += s[j] * w;
+		}
+	}
+	unsigned v[4];
+	bool wr[4];
+#pragma unroll
+	for (int j = 0; j < 4; j++) { v[j] = downU8Round(total[j], weight); wr[j] = x + j < P.width; }
+	downU8Store(P.out + (long long)blockIdx.z * P.outImageStride + (long long)oy * P.outStride + x, v, wr);
+}
+
+// ---- batched GrayU8 image copy (layer 0 of the integer pyramid at scale 1).  A thread moves 16 bytes; the views a caller hands over start
+// anywhere, so both sides are accessed without an alignment assumption (memcpy of a uint4: gfx950 global memory takes unaligned vector
+// accesses).
+__global__ __launch_bounds__(256) void k_copy_images_u8(const uint8_t* __restrict__ in, long long inImageStride, int inStride, uint8_t* __restrict__ out,
+														  long long outImageStride, int outStride, int width, int height) {
+	const int x = (blockIdx.x * 256 + threadIdx.x) * 16;
+	if (x >= width) return;
+	const uint8_t* src = in + (long long)blockIdx.z * inImageStride + x;
+	uint8_t* dst = out + (long long)blockIdx.z * outImageStride + x;
+	for (int y = blockIdx.y; y < height; y += gridDim.y) {
+		const uint8_t* s = src + (long long)y * inStride;
+		uint8_t* d = dst + (long long)y * outStride;
+		if (x + 15 < width) {
+			uint4 v;
+			__builtin_memcpy(&v, s, 16);
+			__builtin_memcpy(d, &v, 16);
+		} else
+			for (int q = 0; q < 16 && x + q < width; q++) d[q] = s[q];
+	}
+}
+int bhip_launch_copy_images_u8(bhip_ctx* ctx, const uint8_t* in, long long inImageStride, int inStride, uint8_t* out, long long outImageStride, int outStride,
+							   int width, int height, int batch) {
+	if (width <= 0 || height <= 0 || batch <= 0) return BHIP_OK;
+	dim3 grid((width + 4095) / 4096, std::min(height, 512), batch);
+	hipLaunchKernelGGL(k_copy_images_u8, grid, dim3(256), 0, ctx->stream, in, inImageStride, inStride, out, outImageStride, outStride, width, height);
+	BHIP_HIP(ctx, hipGetLastError());
+	return BHIP_OK;
+}
+
+int bhip_launch_conv_down_u8(bhip_ctx* ctx, bool vertical, const int32_t* kernel, int kw, const uint8_t* in, long long inImageStride, int inStride, int width,
+							 int height, uint8_t* out, long long outImageStride, int outStride, int outWidth, int outHeight, int skip, int batch) {
+	if (kw <= 0 || kw > BHIP_MAX_TAPS) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "kernel width not supported");
+	// ConvolveImageDownNoBorder.checkParameters* (I:alg/filter/convolve/ConvolveImageDownNoBorder.java:160-186), as bhip_launch_conv_down
+	if (skip <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Skip must be >= 1");
+	if (outWidth < width / skip) return bhip_fail(ctx, BHIP_ERR_INVALID, "Output width is too small");
+	if (outHeight < height / skip) return bhip_fail(ctx, BHIP_ERR_INVALID, "Output height is too small");
+	if (vertical && outWidth < width) return bhip_fail(ctx, BHIP_ERR_INVALID, "Output width is too small");
+	if (!vertical && outHeight < height) return bhip_fail(ctx, BHIP_ERR_INVALID, "Output height is too small");
+	ConvDownU8Params P;
+	P.in = in; P.out = out; P.inImageStride = inImageStride; P.outImageStride = outImageStride; P.inStride = inStride; P.outStride = outStride;
+	P.width = width; P.height = height; P.skip = skip; P.kw = kw; P.radius = kw / 2;
+	long long sum = 0;
+	for (int i = 0; i < kw; i++) { P.k[i] = kernel[i]; sum += kernel[i]; }
+	if (sum == 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "/ by zero (the kernel sums to 0)");
+	const int r = P.radius;
+	const int side = vertical ? height : width;
+	P.naive = kw >= width ? 1 : 0;   // sic: the vertical form tests the image WIDTH as well
+	P.offset = downOffset(skip, r);
+	P.offsetRem = P.offset % skip;
+	P.maxSide = downMaxSide(side, skip, r);
+	P.offsetEnd = P.maxSide + skip;
+	P.sideTrunc = side - side % skip;
+	if (!P.naive) {
+		if (kw % 2 != 1) return bhip_fail(ctx, BHIP_ERR_INVALID, "Non symmetric odd kernels not supported");
+		bool ok = true;   // every loop of the reference stays inside the image along the filtered axis (see bhip_launch_conv_down)
+		if (P.offset <= P.maxSide) ok = ok && P.offset - r >= 0;
+		const int lastLeft = ((P.offset - 1) / skip) * skip;
+		ok = ok && lastLeft + r < side;
+		if (P.offsetEnd < P.sideTrunc) ok = ok && P.offsetEnd - r >= 0;
+		if (!ok) return bhip_fail(ctx, BHIP_ERR_INVALID, "kernel does not fit the image along the filtered axis");
+	}
+	const int gw = vertical ? width : width / skip;
+	const int gh = vertical ? height / skip : height;
+	if (gw <= 0 || gh <= 0 || batch <= 0) return BHIP_OK;
+	ProfScope prof(ctx, vertical ? "k_conv_down_v_u8" : "k_conv_down_h_u8", 1.0 * batch * ((double)width * height + (double)gw * gh));
+	const dim3 grid((gw + 1023) / 1024, gh, batch);
+	if (vertical) hipLaunchKernelGGL(k_conv_down_v_u8, grid, dim3(256), 0, ctx->stream, P);
+	else hipLaunchKernelGGL(k_conv_down_h_u8, grid, dim3(256), 0, ctx->stream, P);
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
 }

@@ -1,6 +1,6 @@
-// Pyramid KLT point tracker: PyramidKltTracker / KltTracker / BilinearRectangle_F32 and the list logic of PointTrackerKltPyramid.
+// Pyramid KLT point tracker: PyramidKltTracker / KltTracker / BilinearRectangle_F32 / _U8 / _S16 and the list logic of PointTrackerKltPyramid.
 //   F:alg/tracker/klt/KltTracker.java:147-495, PyramidKltTracker.java:58-151
-//   I:alg/interpolate/impl/BilinearRectangle_F32.java:64-172
+//   I:alg/interpolate/impl/BilinearRectangle_F32.java:64-172, BilinearRectangle_U8.java:65-173, BilinearRectangle_S16.java:66-168
 //   G:abst/feature/tracker/PointTrackerKltPyramid.java:139-348   (G: = main/boofcv-geo/src/main/java/boofcv/)
 //
 // Shape: one wave per track.  The iteration count, the inside / border choice and every fault test are then uniform over the wave; the 64
@@ -12,6 +12,10 @@
 // The one deliberate deviation: where computeSubImageBounds / region throw IllegalArgumentException for a float round-off position at the
 // border (the exception leaves process() in Java), the track gets the fault BHIP_KLT_REFERENCE_THROWS and is dropped; no kernel reads
 // outside the image.
+//
+// Pixel types: the kernels are templates over the image and derivative types, <float, float> and <uint8_t, int16_t>.  BilinearRectangle_U8 /
+// _S16 are the F32 expression on the four taps converted to float (& 0xFF, sign-extended), every such integer is exact in fp32, so the
+// integer instantiation performs the fp32 operations of the float one on float copies of the same arrays.
 #include "common.h"
 #include <cfloat>
 #include <cmath>
@@ -58,8 +62,9 @@ __device__ __forceinline__ KltRegion kltRegion(float tlx, float tly, int w, int 
 }
 // output pixel (j, i) of region(); the image border cases are handleBorder :128-172 as written (including the bottom-only corner, which
 // reads row regHeight of the image and mixes with by / ay)
-__device__ __forceinline__ float kltRegionAt(const KltRegion& R, const float* p, int stride, int j, int i) {
-	const float* q = p + (long long)(R.yt + i) * stride + R.xt + j;
+template <class T>
+__device__ __forceinline__ float kltRegionAt(const KltRegion& R, const T* p, int stride, int j, int i) {
+	const T* q = p + (long long)(R.yt + i) * stride + R.xt + j;
 	if (j < R.regW && i < R.regH) {
 		const float XY = q[0], xY = q[1], Xy = q[stride], xy = q[stride + 1];
 		return R.a0 * XY + R.a1 * xY + R.a2 * xy + R.a3 * Xy;
@@ -125,7 +130,8 @@ __device__ __forceinline__ void kltChains(KltShared& S, int lane, int nsum, int 
 
 // KltTracker.setDescription :147-240 for one layer by one wave.  Writes the templates to tD / tX / tY (global) and leaves them in S.
 // Returns 1 / 0 (the reference's boolean) or -1 where the reference throws.
-__device__ int kltDescribeLayer(const float* img, const float* dxI, const float* dyI, int stride, int W, int H, int r, const bhip_klt_cfg& cfg, float x,
+template <class TI, class TD>
+__device__ int kltDescribeLayer(const TI* img, const TD* dxI, const TD* dyI, int stride, int W, int H, int r, const bhip_klt_cfg& cfg, float x,
 								float y, float* tD, float* tX, float* tY, float& Gxx, float& Gxy, float& Gyy, KltShared& S, int lane) {
 	const int wF = 2 * r + 1, len = wF * wF;
 	const KltBounds Bd(r, W, H);
@@ -168,7 +174,8 @@ __device__ int kltDescribeLayer(const float* img, const float* dxI, const float*
 }
 
 // PyramidKltTracker.setDescription :58-71 at (fx, fy) for the track of table entry g
-__device__ int kltDescribeTrack(const KltPyr& P, const KltTab& T, const bhip_klt_cfg& cfg, int b, int g, float fx, float fy, KltShared& S, int lane) {
+template <class TI, class TD>
+__device__ int kltDescribeTrack(const KltPyrT<TI, TD>& P, const KltTab& T, const bhip_klt_cfg& cfg, int b, int g, float fx, float fy, KltShared& S, int lane) {
 	const long long n = (long long)T.batch * T.cap;
 	for (int l = 0; l < P.numLayers; l++) {
 		const float scale = P.scale[l];
@@ -188,7 +195,8 @@ __device__ int kltDescribeTrack(const KltPyr& P, const KltTab& T, const bhip_klt
 }
 
 // KltTracker.track :251-325 on one layer; the template is in S (D, X, Y, pXX, pYY, pXY).  x, y move even when a fault is returned.
-__device__ int kltTrackLayer(const float* img, int stride, int W, int H, int r, const bhip_klt_cfg& cfg, float& x, float& y, float sGxx, float sGxy,
+template <class TI>
+__device__ int kltTrackLayer(const TI* img, int stride, int W, int H, int r, const bhip_klt_cfg& cfg, float& x, float& y, float sGxx, float sGxy,
 							 float sGyy, float& error, int& iters, KltShared& S, int lane) {
 	const int wF = 2 * r + 1, len = wF * wF;
 	const KltBounds Bd(r, W, H);
@@ -270,7 +278,8 @@ __device__ int kltTrackLayer(const float* img, int stride, int W, int H, int r, 
 }
 
 // PyramidKltTracker.track :113-151 for every active track: fault, error and the new position (tx, ty; feature.x,y stay as they were)
-__global__ __launch_bounds__(64) void k_klt_track(KltPyr P, KltTab T, bhip_klt_cfg cfg) {
+template <class TI, class TD>
+__global__ __launch_bounds__(64) void k_klt_track(KltPyrT<TI, TD> P, KltTab T, bhip_klt_cfg cfg) {
 	__shared__ KltShared S;
 	const int b = blockIdx.y, lane = threadIdx.x;
 	if ((int)blockIdx.x >= T.nAct[b]) return;
@@ -306,7 +315,8 @@ __global__ __launch_bounds__(64) void k_klt_track(KltPyr P, KltTab T, bhip_klt_c
 	}
 }
 
-__global__ __launch_bounds__(64) void k_klt_describe(KltPyr P, KltTab T, bhip_klt_cfg cfg, int mode, const int* count) {
+template <class TI, class TD>
+__global__ __launch_bounds__(64) void k_klt_describe(KltPyrT<TI, TD> P, KltTab T, bhip_klt_cfg cfg, int mode, const int* count) {
 	__shared__ KltShared S;
 	const int lane = threadIdx.x;
 	int b = blockIdx.y, g;
@@ -522,6 +532,18 @@ __global__ void k_klt_gather(KltTab T, int which, int b, int n, long long* id, f
 	err[i] = T.err[g];
 }
 
+// templates and G of one layer of the tracks of one list, in list order: tmpl [n][3][len] (desc, derivX, derivY), G [n][3] (Gxx, Gyy, Gxy)
+__global__ __launch_bounds__(64) void k_klt_gather_templates(KltTab T, int which, int b, int layer, int n, float* tmpl, float* G) {
+	const int i = blockIdx.x;
+	if (i >= n) return;
+	const int* list = which == 0 ? T.act : which == 1 ? T.spw : T.drp;
+	const int g = b * T.cap + list[b * T.cap + i];
+	const long long N = (long long)T.batch * T.cap;
+	const float* t = T.tmpl + ((long long)g * T.L + layer) * 3 * T.len;
+	for (int e = threadIdx.x; e < 3 * T.len; e += 64) tmpl[(long long)i * 3 * T.len + e] = t[e];
+	if (threadIdx.x == 0) { G[3 * i] = T.gxx[layer * N + g]; G[3 * i + 1] = T.gyy[layer * N + g]; G[3 * i + 2] = T.gxy[layer * N + g]; }
+}
+
 // tracks, iterations and border-form iterations of the last process() over all sequences (its tracks are now in active or dropped)
 __global__ __launch_bounds__(256) void k_klt_stats(KltTab T, unsigned long long* out) {
 	const int b = blockIdx.x, na = T.nAct[b], nd = T.nDrp[b];
@@ -550,13 +572,25 @@ int bhip_launch_klt_begin(bhip_ctx* ctx, KltTab T) {
 int bhip_launch_klt_track(bhip_ctx* ctx, KltPyr P, KltTab T, bhip_klt_cfg cfg, int maxActive) {
 	if (maxActive <= 0) return BHIP_OK;
 	ProfScope prof(ctx, "k_klt_track");
-	hipLaunchKernelGGL(k_klt_track, dim3(maxActive, T.batch), dim3(64), 0, ctx->stream, P, T, cfg);
+	hipLaunchKernelGGL((k_klt_track<float, float>), dim3(maxActive, T.batch), dim3(64), 0, ctx->stream, P, T, cfg);
+	KLT_DONE(ctx);
+}
+int bhip_launch_klt_track(bhip_ctx* ctx, KltPyrU8 P, KltTab T, bhip_klt_cfg cfg, int maxActive) {
+	if (maxActive <= 0) return BHIP_OK;
+	ProfScope prof(ctx, "k_klt_track_u8");
+	hipLaunchKernelGGL((k_klt_track<uint8_t, int16_t>), dim3(maxActive, T.batch), dim3(64), 0, ctx->stream, P, T, cfg);
 	KLT_DONE(ctx);
 }
 int bhip_launch_klt_describe(bhip_ctx* ctx, KltPyr P, KltTab T, bhip_klt_cfg cfg, int mode, const int* count, int maxCount) {
 	if (maxCount <= 0) return BHIP_OK;
 	ProfScope prof(ctx, "k_klt_describe");
-	hipLaunchKernelGGL(k_klt_describe, dim3(maxCount, mode == 3 ? 1 : T.batch), dim3(64), 0, ctx->stream, P, T, cfg, mode, count);
+	hipLaunchKernelGGL((k_klt_describe<float, float>), dim3(maxCount, mode == 3 ? 1 : T.batch), dim3(64), 0, ctx->stream, P, T, cfg, mode, count);
+	KLT_DONE(ctx);
+}
+int bhip_launch_klt_describe(bhip_ctx* ctx, KltPyrU8 P, KltTab T, bhip_klt_cfg cfg, int mode, const int* count, int maxCount) {
+	if (maxCount <= 0) return BHIP_OK;
+	ProfScope prof(ctx, "k_klt_describe_u8");
+	hipLaunchKernelGGL((k_klt_describe<uint8_t, int16_t>), dim3(maxCount, mode == 3 ? 1 : T.batch), dim3(64), 0, ctx->stream, P, T, cfg, mode, count);
 	KLT_DONE(ctx);
 }
 int bhip_launch_klt_compact(bhip_ctx* ctx, KltTab T, int toUnused) {
@@ -593,6 +627,11 @@ int bhip_launch_klt_drop_all(bhip_ctx* ctx, KltTab T, int resetTotal) {
 }
 int bhip_launch_klt_stats(bhip_ctx* ctx, KltTab T, unsigned long long* out) {
 	hipLaunchKernelGGL(k_klt_stats, dim3(T.batch), dim3(256), 0, ctx->stream, T, out);
+	KLT_DONE(ctx);
+}
+int bhip_launch_klt_gather_templates(bhip_ctx* ctx, KltTab T, int which, int seq, int layer, int n, float* tmpl, float* G) {
+	if (n <= 0) return BHIP_OK;
+	hipLaunchKernelGGL(k_klt_gather_templates, dim3(n), dim3(64), 0, ctx->stream, T, which, seq, layer, n, tmpl, G);
 	KLT_DONE(ctx);
 }
 int bhip_launch_klt_gather(bhip_ctx* ctx, KltTab T, int which, int seq, int n, long long* id, float* xy, int* fault, float* err) {

@@ -78,8 +78,8 @@ class DeviceImageOps:
         return out
 
     def _grad(self, fn, src, border, dx, dy):
-        """border: None = frame untouched (as the reference with a null border), 0 = ImageBorderValue(0), "EXTENDED" = BorderType.EXTENDED (Sobel on
-        float32 only).  float32 -> float32, uint8 -> int16."""
+        """border: None = frame untouched (as the reference with a null border), 0 = ImageBorderValue(0), "EXTENDED" = BorderType.EXTENDED (Sobel
+        only).  float32 -> float32, uint8 -> int16."""
         fn_f32, fn_u8 = fn
         u8 = src.dtype == torch.uint8
         fn, dt = (fn_u8, torch.int16) if u8 else (fn_f32, torch.float32)
@@ -160,14 +160,20 @@ class DeviceImageOps:
         return dims.reshape(-1, 2), offs, total.value
 
     def pyramid(self, kernel, scales, src):
-        """-> list of [B, h_i, w_i] layer views into one packed [B, total] tensor"""
-        k = np.ascontiguousarray(kernel, np.float32)
+        """-> list of [B, h_i, w_i] layer views into one packed [B, total] tensor.  float32 frames with a Kernel1D_F32, or uint8 frames with a
+        Kernel1D_S32 (PyramidDiscreteSampleBlur<GrayU8>)"""
+        u8 = src.dtype == torch.uint8
+        k = np.ascontiguousarray(kernel, np.int32 if u8 else np.float32)
         s = np.ascontiguousarray(scales, np.int32)
-        ip, iis, irs, W, H, B = _geom(src)
+        ip, iis, irs, W, H, B = _geom(src, torch.uint8 if u8 else torch.float32)
         dims, offs, total = self.pyramidLayout(W, H, s)
-        out = torch.empty((B, total), dtype=torch.float32, device=src.device)
-        _check(self.ctx, self.L.bhip_pyramid_dev_f32(self.ctx._h, k.ctypes.data_as(_lib._fp), len(k), s.ctypes.data_as(_lib._ip), len(s), ip, iis, irs, W, H, B,
-                                                   C.c_void_p(out.data_ptr())))
+        out = torch.empty((B, total), dtype=src.dtype if u8 else torch.float32, device=src.device)
+        if u8:
+            _check(self.ctx, self.L.bhip_pyramid_dev_u8(self.ctx._h, k.ctypes.data_as(_lib._i32p), len(k), s.ctypes.data_as(_lib._ip), len(s), ip, iis, irs, W, H, B,
+                                                      C.c_void_p(out.data_ptr())))
+        else:
+            _check(self.ctx, self.L.bhip_pyramid_dev_f32(self.ctx._h, k.ctypes.data_as(_lib._fp), len(k), s.ctypes.data_as(_lib._ip), len(s), ip, iis, irs, W, H, B,
+                                                       C.c_void_p(out.data_ptr())))
         return [out[:, int(offs[i]):int(offs[i]) + int(dims[i][0]) * int(dims[i][1])].view(B, int(dims[i][1]), int(dims[i][0])) for i in range(len(s))]
 
     def brief(self, img, radius, samplePoints, compare, xy, start):
@@ -188,7 +194,8 @@ class DeviceImageOps:
 
 class DeviceKltTracker:
     """PointTrackerKltPyramid (G:abst/feature/tracker/PointTrackerKltPyramid.java:139-348, as FactoryPointTracker.klt builds it) for B independent
-    GrayF32 sequences at once, on one bhip_klt: process(frames) takes a [B,H,W] CUDA tensor and queues pyramid, Sobel (EXTENDED border), tracking,
+    GrayF32 or GrayU8 sequences at once, on one bhip_klt: process(frames) takes a [B,H,W] float32 or uint8 CUDA tensor (the first call decides; a
+    uint8 tracker has a uint8 pyramid and int16 derivatives) and queues pyramid, Sobel (EXTENDED border), tracking,
     re-description and the list update on the context's stream without a host synchronisation; spawn() detects Shi-Tomasi corners
     (radius 1, unweighted) with the strict non-max extractor (detectRadius, detectThreshold, detectBorder) and starts tracks on them
     (maxFeatures <= 0).  Sequence b's results equal those of a single-sequence tracker fed with frames[b]."""
@@ -205,6 +212,7 @@ class DeviceKltTracker:
         self.detectBorder = max(self.detectRadius, 1) if detectBorder is None else int(detectBorder)
         self._h = None
         self._shape = None
+        self._dtype = None
         self.ctx._children.add(self)
 
     def close(self):
@@ -223,16 +231,21 @@ class DeviceKltTracker:
             raise IllegalArgumentException("process() has not been called")
 
     def process(self, frames):
-        ptr, imageStride, stride, W, H, B = _geom(frames)
+        u8 = frames.dtype == torch.uint8
+        dtype = torch.uint8 if u8 else torch.float32
+        if self._dtype is not None and dtype != self._dtype:
+            raise IllegalArgumentException("this tracker has been fed %s frames" % str(self._dtype).replace("torch.", ""))
+        ptr, imageStride, stride, W, H, B = _geom(frames, dtype)
         if self._shape != (W, H, B) or not self._h:
             self.close()
             h = C.c_void_p()
             cfg = self.config._c()
             sc = (C.c_int * len(self.scales))(*self.scales)
-            _check(self.ctx, self.L.bhip_klt_create(self.ctx._h, C.byref(cfg), self.templateRadius, sc, len(self.scales), self.detectRadius, self.detectThreshold,
-                                                    self.detectBorder, W, H, B, C.byref(h)))
-            self._h, self._shape = h, (W, H, B)
-        _check(self.ctx, self.L.bhip_klt_process_dev_f32(self._h, ptr, imageStride, stride))
+            create = self.L.bhip_klt_create_u8 if u8 else self.L.bhip_klt_create
+            _check(self.ctx, create(self.ctx._h, C.byref(cfg), self.templateRadius, sc, len(self.scales), self.detectRadius, self.detectThreshold,
+                                    self.detectBorder, W, H, B, C.byref(h)))
+            self._h, self._shape, self._dtype = h, (W, H, B), dtype
+        _check(self.ctx, (self.L.bhip_klt_process_dev_u8 if u8 else self.L.bhip_klt_process_dev_f32)(self._h, ptr, imageStride, stride))
 
     def spawn(self):
         self._need()
@@ -294,12 +307,32 @@ class DeviceKltTracker:
     def dropped(self, seq):
         return self._fetch(2, seq)
 
+    def templates(self, seq, layer, which=0):
+        """PyramidKltFeature.desc[layer] of every track of a list (which: 0 active, 1 spawned, 2 dropped) of sequence seq, in list order
+        -> (templates float32 [n][3][(2r+1)^2] = desc, derivX, derivY; G float32 [n][3] = Gxx, Gyy, Gxy)"""
+        self._need()
+        n = int(self.counts()[(0, 1, 2)[which]][seq])
+        ln = (2 * self.templateRadius + 1) ** 2
+        t, G = np.zeros((n, 3, ln), np.float32), np.zeros((n, 3), np.float32)
+        if n:
+            _check(self.ctx, self.L.bhip_klt_fetch_templates(self._h, int(which), int(seq), int(layer), t.ctypes.data_as(_lib._fp), G.ctypes.data_as(_lib._fp)))
+        return t, G
+
     def layer(self, seq, layer, which=0):
         """layer of the image pyramid (which 0) / derivX (1) / derivY (2) of sequence seq, as a host array"""
         self._need()
         sc = np.asarray(self.scales, dtype=np.int32)
         dims = np.zeros(2 * len(sc), dtype=np.int32)
         self.L.bhip_pyramid_layout(self._shape[0], self._shape[1], sc.ctypes.data_as(_lib._ip), len(sc), dims.ctypes.data_as(_lib._ip), None, None)
-        out = np.zeros((int(dims[2 * layer + 1]), int(dims[2 * layer])), np.float32)
+        shape = (int(dims[2 * layer + 1]), int(dims[2 * layer]))
+        if self._dtype == torch.uint8:   # uint8 image pyramid, int16 derivatives
+            if which == 0:
+                out = np.zeros(shape, np.uint8)
+                _check(self.ctx, self.L.bhip_klt_fetch_layer_u8(self._h, int(seq), int(layer), out.ctypes.data_as(_lib._u8p)))
+            else:
+                out = np.zeros(shape, np.int16)
+                _check(self.ctx, self.L.bhip_klt_fetch_layer_s16(self._h, int(seq), int(layer), int(which), out.ctypes.data_as(_lib._i16p)))
+            return out
+        out = np.zeros(shape, np.float32)
         _check(self.ctx, self.L.bhip_klt_fetch_layer(self._h, int(seq), int(layer), int(which), out.ctypes.data_as(_lib._fp)))
         return out

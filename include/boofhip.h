@@ -302,7 +302,7 @@ int bhip_median_f32(bhip_ctx* ctx, const float* in, int inStart, int inStride, i
  * border: 0 = null (frame untouched), 1 = ImageBorderValue(0), 2 = BorderType.EXTENDED (BoofDefaults.DERIV_BORDER_TYPE, what
  * FactoryDerivative.sobel passes: I:abst/filter/derivative/ImageGradient_SB.java:39-66): every frame pixel is kernelDerivX/Y_F32 on the
  * index-clamped image, summed as ConvolveJustBorder_General_SB.convolve does (I:alg/filter/convolve/border/ConvolveJustBorder_General_SB.java:110-174).
- * bhip_three_f32 and the GrayU8 gradients answer BHIP_ERR_UNSUPPORTED to 2. */
+ * bhip_sobel_u8_s16 accepts 2 as well (see there); the three-tap gradients of both types answer BHIP_ERR_UNSUPPORTED to 2. */
 int bhip_sobel_f32(bhip_ctx* ctx, const float* in, int inStart, int inStride, int width, int height, float* dx, float* dy, int outStart,
 				   int outStride, int border);
 /* GradientThree.process(GrayF32,...) -> GradientThree_Standard.process (I:alg/filter/derivative/impl/GradientThree_Standard.java:40-62) */
@@ -331,6 +331,23 @@ int bhip_pyramid_f32(bhip_ctx* ctx, const float* kernel, int kernelWidth, const 
 					 int inStride, int width, int height, float* out);
 int bhip_pyramid_dev_f32(bhip_ctx* ctx, const float* kernel, int kernelWidth, const int* scales, int numLayers, const float* dev_in,
 						 long long inImageStride, int inStride, int width, int height, int batch, float* dev_out);
+/* The same on GrayU8: ConvolveImageDownNormalized.horizontal/vertical(Kernel1D_S32, GrayU8, GrayI8, skip)
+ * (I:alg/filter/convolve/ConvolveImageDownNormalized.java:109-137).  Interior (byte)((total + divisor/2) / divisor) with divisor =
+ * kernel.computeSum() (ConvolveDownNoBorderStandard.java:329-394, ConvolveDownNoBorderUnrolled_U8_I8_Div), border (byte)((total + weight/2) / weight)
+ * over the taps inside the image (ConvolveDownNormalized_JustBorder.java:262-358), naive form when kernelWidth >= width
+ * (ConvolveDownNormalizedNaive.java:133-187); Java's truncating int division for any S32 kernel.  BHIP_ERR_INVALID where the reference throws
+ * (also a kernel that sums to 0: ArithmeticException). */
+int bhip_conv_down_norm_h_u8(bhip_ctx* ctx, const int32_t* kernel, int kernelWidth, const uint8_t* in, int inStart, int inStride, int width, int height,
+							 uint8_t* out, int outStart, int outStride, int outWidth, int outHeight, int skip);
+int bhip_conv_down_norm_v_u8(bhip_ctx* ctx, const int32_t* kernel, int kernelWidth, const uint8_t* in, int inStart, int inStride, int width, int height,
+							 uint8_t* out, int outStart, int outStride, int outWidth, int outHeight, int skip);
+/* PyramidDiscreteSampleBlur<GrayU8> (I:alg/transform/pyramid/PyramidDiscreteSampleBlur.java:67-124): bhip_pyramid_f32 / bhip_pyramid_dev_f32 on
+ * bytes, with the layout of bhip_pyramid_layout counted in elements.  The kernel is FactoryKernelGaussian.gaussian(Kernel1D_S32, -1, radius)
+ * (bhip_gaussian_kernel1d_s32), built by the caller; the image between the two passes of a layer is a GrayU8. */
+int bhip_pyramid_u8(bhip_ctx* ctx, const int32_t* kernel, int kernelWidth, const int* scales, int numLayers, const uint8_t* in, int inStart,
+					int inStride, int width, int height, uint8_t* out);
+int bhip_pyramid_dev_u8(bhip_ctx* ctx, const int32_t* kernel, int kernelWidth, const int* scales, int numLayers, const uint8_t* dev_in,
+						long long inImageStride, int inStride, int width, int height, int batch, uint8_t* dev_out);
 /* FactoryIntensityPointAlg.shiTomasi(radius, false, GrayF32) / harris(radius, kappa, false, GrayF32)
  * (F:factory/feature/detect/intensity/FactoryIntensityPointAlg.java:91-160) -> GradientCornerIntensity.process(derivX, derivY, intensity)
  * = ImplSsdCorner_F32 (F:alg/feature/detect/intensity/impl/ImplSsdCorner_F32.java:62-196, ImplSsdCornerBox.java:36-51) with
@@ -343,8 +360,9 @@ int bhip_corner_intensity_f32(bhip_ctx* ctx, int kind, int radius, float kappa, 
 /* GrayU8 -> GrayS16 gradients: GradientSobel.process(GrayU8, GrayS16, GrayS16, border) (I:alg/filter/derivative/GradientSobel.java:110-124 ->
  * impl/GradientSobel_Outer.java:76- process_sub) and GradientThree.process(GrayU8, ...) (I:alg/filter/derivative/GradientThree.java:86-101 ->
  * impl/GradientThree_Standard.java:67-88).  Integer arithmetic stored as (short).  border: 0 = null (frame untouched), 1 = ImageBorderValue(0)
- * (ConvolveJustBorder_General_SB with kernelDerivX/Y_I32, DerivativeHelperFunctions.processBorderHorizontal/Vertical with kernelDeriv_I32).
- * dx and dy share outStart / outStride. */
+ * (ConvolveJustBorder_General_SB with kernelDerivX/Y_I32, DerivativeHelperFunctions.processBorderHorizontal/Vertical with kernelDeriv_I32),
+ * 2 (bhip_sobel_u8_s16 only) = BorderType.EXTENDED, ImageBorder1D_S32 over BorderIndex1D_Extend: the nine-tap kernelDerivX/Y_I32 sum on the
+ * index-clamped image, what FactoryDerivative.sobel(GrayU8, GrayS16) passes.  dx and dy share outStart / outStride. */
 int bhip_sobel_u8_s16(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, int16_t* dx, int16_t* dy, int outStart,
 					  int outStride, int border);
 int bhip_three_u8_s16(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, int16_t* dx, int16_t* dy, int outStart,
@@ -475,6 +493,10 @@ int bhip_klt_counts(bhip_klt* k, int* active, int* spawned, int* dropped);
 /* one list of sequence seq (which: 0 active, 1 spawned, 2 dropped) in the reference's list order: featureId[n], xy[2n], fault[n] (last
  * track() result), error[n] (KltTracker.getError() of the last layer of this track whose error was computed).  Any pointer may be NULL. */
 int bhip_klt_fetch(bhip_klt* k, int which, int seq, long long* featureId, float* xy, int* fault, float* error);
+/* what PyramidKltFeature.desc[layer] holds for the tracks of one list of sequence seq, in list order: tmpl[n][3][(2r+1)^2] = KltFeature.desc,
+ * derivX, derivY (F:alg/tracker/klt/KltFeature.java; desc = NaN outside the image, the derivative templates 0 there), G[n][3] = Gxx, Gyy, Gxy.
+ * Either pointer may be NULL.  For tests and for callers that re-use descriptions; either pixel type. */
+int bhip_klt_fetch_templates(bhip_klt* k, int which, int seq, int layer, float* tmpl, float* G);
 /* figures of the last process() over all sequences: tracks that went through track(), Lucas-Kanade iterations they took, and how many of those
  * took the border form (computeGandE_border) */
 int bhip_klt_stats(bhip_klt* k, long long* tracks, long long* iterations, long long* borderIterations);
@@ -497,6 +519,36 @@ int bhip_klt_set_description_f32(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int rad
  * computeError ran: SUCCESS and LARGE_ERROR) */
 int bhip_klt_track_f32(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const float* image, int imgStart, int imgStride, int width, int height,
 					   const float* desc, const float* descX, const float* descY, const float* G, float* xy, int n, int* fault, float* error);
+
+/* ---- the same tracker on GrayU8 frames: FactoryPointTracker.klt(PkltConfig, ConfigGeneralDetector, GrayU8, GrayS16)
+ *      (G:factory/feature/tracker/FactoryPointTracker.java:120-145; derivType = GImageDerivativeOps.getDerivativeType(GrayU8) = GrayS16).
+ *      Pyramid = PyramidDiscreteSampleBlur<GrayU8> with Kernel1D_S32 [1,4,7,4,1] (bhip_pyramid_dev_u8), gradient = GradientSobel.process(GrayU8,
+ *      GrayS16, GrayS16, EXTENDED) (I:alg/filter/derivative/GradientSobel.java:110-124), interpolation = BilinearRectangle_U8 / _S16
+ *      (I:alg/interpolate/impl/BilinearRectangle_U8.java:65-173, BilinearRectangle_S16.java:66-168: the F32 expression on taps converted to
+ *      float), corners = ImplSsdCorner_S16 + ShiTomasiCorner_S32 (bhip_corner_intensity_dev_s16).  KltTracker / PyramidKltTracker and the lists
+ *      are type independent, so spawn, spawn_points, add, drop, counts, fetch, stats, reset and destroy are the calls above on either kind of
+ *      handle.  A handle answers BHIP_ERR_INVALID to the process / fetch_layer / dev_view calls of the other pixel type. ---- */
+int bhip_klt_create_u8(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int templateRadius, const int* scales, int numLayers, int detectRadius, float detectThreshold,
+					   int detectBorder, int width, int height, int batch, bhip_klt** out);
+/* process(GrayU8) for every sequence: strides in bytes (= elements).  The frames are copied into layer 0, so dev_frames may be reused once the
+ * call has been queued on the stream. */
+int bhip_klt_process_dev_u8(bhip_klt* k, const uint8_t* dev_frames, long long imageStride, int stride);
+/* the same for host frames (one pointer per sequence); with scale[0] == 1 they are uploaded straight into layer 0 */
+int bhip_klt_process_u8(bhip_klt* k, const uint8_t* const* img, const int* startIndex, const int* stride);
+/* layer `layer` of sequence seq of the last process(): the GrayU8 image pyramid, and derivX (which 1) / derivY (which 2) as GrayS16 */
+int bhip_klt_fetch_layer_u8(bhip_klt* k, int seq, int layer, uint8_t* out);
+int bhip_klt_fetch_layer_s16(bhip_klt* k, int seq, int layer, int which, int16_t* out);
+/* bhip_klt_dev_view for a GrayU8 tracker: layer l of frame b starts at b * elementsPerFrame + offsets[l] elements of each buffer */
+int bhip_klt_dev_view_u8(bhip_klt* k, const int** dev_activeSlots, const int** dev_activeCount, const float** dev_x, const float** dev_y,
+						 const long long** dev_featureId, const uint8_t** dev_pyramid, const int16_t** dev_derivX, const int16_t** dev_derivY,
+						 int* slotsPerSequence, long long* elementsPerFrame);
+/* bhip_klt_set_description_f32 / bhip_klt_track_f32 on a GrayU8 image with GrayS16 derivatives (KltTracker<GrayU8, GrayS16> with
+ * BilinearRectangle_U8 / _S16); templates, G, positions, faults and errors are float as there */
+int bhip_klt_set_description_u8(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const uint8_t* image, int imgStart, int imgStride, const int16_t* derivX,
+								const int16_t* derivY, int dStart, int dStride, int width, int height, const float* xy, int n, float* desc, float* descX,
+								float* descY, float* G, uint8_t* ok);
+int bhip_klt_track_u8(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const uint8_t* image, int imgStart, int imgStride, int width, int height,
+					  const float* desc, const float* descX, const float* descY, const float* G, float* xy, int n, int* fault, float* error);
 
 #ifdef __cplusplus
 }

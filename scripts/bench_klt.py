@@ -6,8 +6,13 @@ a sequence is the 1920x1080 window of its scene moved by whole pixels, so the tr
 spawned on the first frame (Shi-Tomasi radius 1, strict non-max of --detect-radius, threshold 1); every timed step is one process() of the 64
 next frames.  Reported per step: ctx-profiler ms split into pyramid, gradient, track, re-describe and compaction, the wall time between HIP events,
 tracks per second, the mean Lucas-Kanade iteration count per track and the share of SUCCESS tracks that lie within 0.25 px of the true motion.
-One JSON line per run, printed and appended to --out (default profiles/bench_klt.jsonl)."""
+One JSON line per run, printed and appended to --out (default profiles/bench_klt.jsonl).
+
+--image-type u8 runs the same scenes rounded to bytes through the GrayU8 tracker (uint8 pyramid, int16 Sobel); the line then carries "imageType".
+--host-steps N adds N process() calls from page-locked host frames (bhip_klt_process_f32 / _u8: upload, step, synchronise) and reports
+"host_steps_per_second" / "host_frames_per_second", the figure a caller with a camera stream sees."""
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -19,7 +24,32 @@ sys.path.insert(0, ROOT)
 from boofcv_amd.device import DeviceImageOps, DeviceKltTracker  # noqa: E402
 
 B, W, H, MARGIN = 64, 1920, 1080, 64
-GROUPS = (("track", ("k_klt_track",)), ("redescribe", ("k_klt_describe",)), ("compaction", ("k_klt_compact",)), ("gradient", ("k_sobel",)))
+GROUPS = (("track", ("k_klt_track", "k_klt_track_u8")), ("redescribe", ("k_klt_describe", "k_klt_describe_u8")), ("compaction", ("k_klt_compact",)),
+          ("gradient", ("k_sobel", "k_sobel_u8")))
+
+
+def host_steps(ops, trk, frame, n, u8):
+    """n process() calls from page-locked host frames on a tracker of the same configuration -> steps per second (wall clock, each call synchronises)"""
+    import time
+    from boofcv_amd import _lib
+    L = ops.L
+    h = C.c_void_p()
+    cfg = trk.config._c()
+    sc = (C.c_int * 3)(1, 2, 4)
+    create, process = (L.bhip_klt_create_u8, L.bhip_klt_process_u8) if u8 else (L.bhip_klt_create, L.bhip_klt_process_f32)
+    assert create(ops.ctx._h, C.byref(cfg), 2, sc, 3, trk.detectRadius, trk.detectThreshold, trk.detectBorder, W, H, B, C.byref(h)) == 0
+    pinned = [frame(k).contiguous().cpu().pin_memory() for k in (0, 1)]
+    elem = C.c_uint8 if u8 else C.c_float
+    ptrs = [(C.POINTER(elem) * B)(*[C.cast(p[b].data_ptr(), C.POINTER(elem)) for b in range(B)]) for p in pinned]
+    assert process(h, ptrs[0], None, None) == 0
+    assert L.bhip_klt_spawn(h, -1) == 0
+    assert process(h, ptrs[1], None, None) == 0
+    t0 = time.perf_counter()
+    for k in range(n):
+        assert process(h, ptrs[k % 2], None, None) == 0
+    dt = time.perf_counter() - t0
+    L.bhip_klt_destroy(h)
+    return n / dt
 
 
 def main():
@@ -28,12 +58,18 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_klt.jsonl"))
+    ap.add_argument("--image-type", choices=("f32", "u8"), default="f32", help="f32: GrayF32 frames; u8: the same scenes rounded to bytes, GrayU8 tracker")
+    ap.add_argument("--host-steps", type=int, default=0, help="also time this many process() calls from page-locked host frames")
     a = ap.parse_args()
+    u8 = a.image_type == "u8"
 
     ops = DeviceImageOps(device=0)
     gen = torch.Generator(device="cuda").manual_seed(11)
     scene = ops.gaussian(torch.rand((B, H + MARGIN, W + MARGIN), device="cuda", generator=gen) * 255, -1, 3)
     ops.ctx.synchronize()
+    if u8:
+        scene = scene.round().clamp(0, 255).to(torch.uint8)
+        torch.cuda.synchronize()
     trk = DeviceKltTracker([1, 2, 4], 2, None, detectRadius=a.detect_radius, detectThreshold=1.0, ctx=ops.ctx)
 
     # the window walks one pixel right and down per frame and turns round before it leaves the scene
@@ -106,6 +142,12 @@ def main():
            "tracks_per_second": round(mean_tracks / (wall * 1e-3)), "tracks_per_second_tracking_kernels": round(mean_tracks / (tracking * 1e-3)) if tracking > 0 else None,
            "mean_iterations_per_track": round(iters / max(n_tracked, 1), 3), "border_iteration_share": round(border / max(iters, 1), 4),
            "alive_checked": alive, "within_quarter_pixel": round(near / max(alive, 1), 4)}
+    if u8:
+        out["imageType"] = "u8"
+    if a.host_steps > 0:
+        sps = host_steps(ops, trk, frame, a.host_steps, u8)
+        out["host_steps_per_second"] = round(sps, 2)
+        out["host_frames_per_second"] = round(sps * B, 1)
     line = json.dumps(out)
     print(line, flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
