@@ -9,31 +9,6 @@
 #include <mutex>
 #include <unordered_set>
 
-// launchers defined in the other translation units
-int bhip_launch_describe_ex(bhip_ctx* ctx, ImgView ii, const KeyPoint* kps, int cap, const int* imageStart, int batch, int singleImage, long long total,
-							SurfTables t, const double* anglesIn, double* angles, double* desc, uint8_t* white, const int* perm = nullptr, const DescPlanar* planar = nullptr);
-int bhip_launch_kp_spatial_order(bhip_ctx* ctx, const KeyPoint* kps, int cap, const int* start, int batch, int maxCount, int W, int H, int* hist, int* perm);
-int bhip_assoc_phase1_l2(bhip_ctx* ctx, const double* src, int nsLocal, int srcBegin, const double* dst, int nd, int dof, double maxErr, int sqrtScore,
-						 int* pairs, double* fit, void* colTop, DevBuf& work);
-int bhip_assoc_phase1_ham(bhip_ctx* ctx, const int32_t* src, int nsLocal, int srcBegin, const int32_t* dst, int nd, int words, double maxErr, int* pairs,
-						  double* fit, void* colTop, DevBuf& work);
-int bhip_assoc_phase2(bhip_ctx* ctx, const void* colAll, int nranks, int nd, int nsLocal, int srcBegin, int* pairs, double* fit);
-int bhip_assoc_coltop_size();
-int bhip_assoc_hamming_batched(bhip_ctx* ctx, const int32_t* src, const int32_t* dst, int words, int count, const long long* srcOff, const int* ns,
-							   const long long* dstOff, const int* nd, double maxErr, int backwards, int* pairs, double* fit, DevBuf& work);
-int bhip_launch_integral_u8(bhip_ctx* ctx, const unsigned char* in, long long inImageStride, int inStride, int* out, long long outImageStride, int outStride,
-							int width, int height, int batch);
-
-int bhip_assoc_l2_mfma_batched(bhip_ctx* ctx, AssocMfmaWork& W, const double* dev_src, const double* dev_dst, int count, const long long* srcOff,
-								 const int* ns, const long long* dstOff, const int* nd, double maxErr, int backwards, int* dev_pairs, double* dev_fit,
-								 int* usedMfma);
-
-bool bhip_fused_plan(int skip, int nlevels, const int* sizes, int radius, int* TX, int* TY, int* ldsBytes);
-bool bhip_fused_is_fixed(int skip, int nlevels, const int* sizes, int radius);
-int bhip_launch_detect_fused(bhip_ctx* ctx, ImgView ii, int batch, int skip, int nlevels, const int* sizes, int nmid, const DetectLevelParams* mids,
-							 const int* midLevels, int radius, float threshold, unsigned int* bitmap, int bitmapWords, KeyPoint* cand, int* candCount,
-							 int cap, const FusedExport* exp, bool intTaps = false);
-
 // Per-context scratch that the stateless entry points reuse (freed with the context).  The staging slots belong to the host-buffer export
 // that is running: the caller's views it uploads, the results it downloads, its own working buffers.  Code on device pointers (the
 // implementations behind the _dev exports, which host exports run on their staged copies) uses only the device-side slots, so nothing a
@@ -174,10 +149,19 @@ int bhip_host_free(void* host_mem) {
 		BHIP_HIP((ctx), hipSetDevice((ctx)->device));    \
 	} while (0)
 
-// `batch` images (a host view is one) of w x h elements, rows `stride` elements apart
-#define CHECK_IMG(ctx, p, stride, w, h, batch)                                                                                       \
-	do {                                                                                                                             \
-		if (!(p) || (w) <= 0 || (h) <= 0 || (batch) <= 0 || (stride) < (w)) return bhip_fail((ctx), BHIP_ERR_INVALID, "bad image"); \
+// a caller's host image: width x height elements, rows `stride` elements apart, the first at data[start]
+template <class T>
+struct HostImg {
+	T* data;
+	int start, stride, width, height;
+	static constexpr int batch = 1;
+};
+
+// v: a HostImg or a DevImg
+#define CHECK_IMG(ctx, v)                                                                                         \
+	do {                                                                                                          \
+		if (!(v).data || (v).width <= 0 || (v).height <= 0 || (v).batch <= 0 || (v).stride < (v).width)          \
+			return bhip_fail((ctx), BHIP_ERR_INVALID, "bad image");                                               \
 	} while (0)
 
 // Host view (rows `stride` elements apart from `start`) to / from a device image with rows `pitch` elements apart, enqueued on `st`.  Two
@@ -194,6 +178,43 @@ static int download(bhip_ctx* ctx, T* out, int start, int stride, const T* dev, 
 	if (pitch == w && stride == w) BHIP_HIP(ctx, hipMemcpyAsync(out + start, dev, sizeof(T) * w * h, hipMemcpyDeviceToHost, st));
 	else BHIP_HIP(ctx, hipMemcpy2DAsync(out + start, sizeof(T) * stride, dev, sizeof(T) * pitch, sizeof(T) * w, h, hipMemcpyDeviceToHost, st));
 	return BHIP_OK;
+}
+
+// Staging of a host-buffer export (see CtxScratch): stageIn reserves `slot` for one image shaped like `h` with rows `pitch` elements apart,
+// uploads h into it unless `copy` is false (an output the implementation writes as a whole) and hands back the device view; stageOut
+// enqueues the download.  The export synchronizes once after its last stageOut.
+template <class T>
+static int stageIn(bhip_ctx* ctx, DevBuf& slot, HostImg<T> h, int pitch, DevImg<std::remove_const_t<T>>& dev, bool copy = true) {
+	using E = std::remove_const_t<T>;
+	BHIP_TRY(slot.reserve(ctx, (size_t)pitch * h.height * sizeof(E)));
+	dev = bhip_img_over<E>(slot, pitch, h.width, h.height, 1);
+	return copy ? upload<E>(ctx, dev.data, pitch, h.data, h.start, h.stride, h.width, h.height, ctx->stream) : BHIP_OK;
+}
+template <class T>
+static int stageOut(bhip_ctx* ctx, HostImg<T> h, DevImg<T> dev) {
+	return download<T>(ctx, h.data, h.start, h.stride, dev.data, dev.stride, h.width, h.height, ctx->stream);
+}
+// pitch4(w): device rows 16-byte aligned so that the tiled ip kernels apply
+static inline int pitch4(int w) { return (w + 3) & ~3; }
+
+// The usual host export: one input view, one output view.  After the context and image checks and the export's own argument check
+// (argError: its message, nullptr when it passed) `in` is staged into in0 and `out` into out0 -- rows pitch4(width) apart when `pitched`,
+// dense otherwise; `out` is uploaded too when `keepOut`, i.e. when the operation leaves some pixels as the caller had them -- then
+// run(din, dout), the download and the synchronize.  When run fails, nothing is downloaded.
+template <class TI, class TO, class Run>
+static int hostInOut(bhip_ctx* ctx, HostImg<const TI> in, HostImg<TO> out, bool pitched, bool keepOut, const char* argError, Run run) {
+	CHECK_CTX(ctx);
+	CHECK_IMG(ctx, in);
+	CHECK_IMG(ctx, out);
+	if (argError) return bhip_fail(ctx, BHIP_ERR_INVALID, argError);
+	CtxScratch* sc = scratchOf(ctx);
+	DevImg<TI> din;
+	DevImg<TO> dout;
+	BHIP_TRY(stageIn(ctx, sc->in0, in, pitched ? pitch4(in.width) : in.width, din));
+	BHIP_TRY(stageIn(ctx, sc->out0, out, pitched ? pitch4(out.width) : out.width, dout, keepOut));
+	BHIP_TRY(run(din, dout));
+	BHIP_TRY(stageOut(ctx, out, dout));
+	return bhip_ctx_synchronize(ctx);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -580,7 +601,8 @@ static int surfRun(bhip_surf* s, ImgView in, int batch, int planarBands = 0, boo
 	}
 	s->W = W; s->H = H; s->batch = batch;
 	ImgViewW iiW{iiBase, (long long)W * H, W, W, H};
-	if (u8) BHIP_TRY(bhip_launch_integral_u8(ctx, (const unsigned char*)in.data, (long long)W * H, W, (int*)iiBase, (long long)W * H, W, W, H, nImages));
+	const DevImg<const uint8_t> inU8{(const uint8_t*)in.data, (long long)W * H, W, W, H, nImages};   // what `in` stands for when u8 is set
+	if (u8) BHIP_TRY(bhip_launch_integral_u8(ctx, inU8, DevImg<int32_t>{(int32_t*)iiBase, (long long)W * H, W, W, H, nImages}));
 	else BHIP_TRY(bhip_launch_integral(ctx, in, iiW, nImages));
 	ImgView ii{iiBase, (long long)W * H, W, W, H};
 	s->iiView = ii;
@@ -617,9 +639,12 @@ static int surfRun(bhip_surf* s, ImgView in, int batch, int planarBands = 0, boo
 			BHIP_HIP(ctx, hipMemsetAsync(s->whiteBuf.p, 0, (size_t)total, ctx->stream));
 			int maxCount = 0;
 			for (int c : s->det.counts) maxCount = std::max(maxCount, c);
-			BHIP_TRY(bhip_launch_brief(ctx, in.data, u8 ? W : in.stride, W, H, s->briefRadius, s->briefPoints, s->briefSample(), s->briefCompare(),
-									   (const double*)s->det.sorted.p, (int)total, s->wordsBuf.as<int>(), u8, batch, u8 ? (long long)W * H : in.imageStride,
-									   s->startBuf.as<int>(), maxCount, (int)(sizeof(KeyPoint) / 8), (long long)s->det.cap * (long long)(sizeof(KeyPoint) / 8), s->briefPatch));
+			auto brief = [&](auto img) {
+				return bhip_launch_brief(ctx, img, s->briefRadius, s->briefPoints, s->briefSample(), s->briefCompare(), (const double*)s->det.sorted.p, (int)total,
+										 s->wordsBuf.as<int>(), s->startBuf.as<int>(), maxCount, (int)(sizeof(KeyPoint) / 8),
+										 (long long)s->det.cap * (long long)(sizeof(KeyPoint) / 8), s->briefPatch);
+			};
+			BHIP_TRY(u8 ? brief(inU8) : brief(DevImg<const float>{in.data, in.imageStride, in.stride, W, H, batch}));
 		}
 		BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
 		s->haveResult = true;
@@ -1121,39 +1146,31 @@ int bhip_surf_describe_points(bhip_surf* s, int image, const double* xy_scale, i
 // ---------------------------------------------------------------------------------------------------------------
 // stage-level entry points (host buffers in / out)
 // ---------------------------------------------------------------------------------------------------------------
-// pitch4(w): device rows 16-byte aligned so that the tiled ip kernels apply
-static inline int pitch4(int w) { return (w + 3) & ~3; }
-
 int bhip_integral_f32(bhip_ctx* ctx, const float* in, int inStart, int inStride, int width, int height, float* out, int outStart, int outStride) {
-	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, in, inStride, width, height, 1);
-	CHECK_IMG(ctx, out, outStride, width, height, 1);
-	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
-	BHIP_TRY(sc->out0.reserve(ctx, (size_t)width * height * 4));
-	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, in, inStart, inStride, width, height, ctx->stream));
-	ImgView iv{sc->in0.as<float>(), (long long)width * height, width, width, height};
-	ImgViewW ov{sc->out0.as<float>(), (long long)width * height, width, width, height};
-	BHIP_TRY(bhip_launch_integral(ctx, iv, ov, 1));
-	BHIP_TRY(download(ctx, out, outStart, outStride, sc->out0.as<float>(), width, width, height, ctx->stream));
-	return bhip_ctx_synchronize(ctx);
+	return hostInOut<float, float>(ctx, {in, inStart, inStride, width, height}, {out, outStart, outStride, width, height}, false, false, nullptr, [&](auto din, auto dout) {
+		ImgView iv{din.data, din.imageStride, width, width, height};
+		ImgViewW ov{dout.data, dout.imageStride, width, width, height};
+		return bhip_launch_integral(ctx, iv, ov, 1);
+	});
 }
 
 int bhip_hessian_f32(bhip_ctx* ctx, const float* ii, int iiStart, int iiStride, int width, int height, int skip, int size, float* intensity,
 					 int outStart, int outStride) {
+	const HostImg<const float> hin{ii, iiStart, iiStride, width, height};
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, ii, iiStride, width, height, 1);
+	CHECK_IMG(ctx, hin);
 	if (skip < 1 || size < 3) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad skip/size");
 	const int w = width / skip, h = height / skip;
 	if (w <= 0 || h <= 0) return BHIP_OK;
-	CHECK_IMG(ctx, intensity, outStride, w, h, 1);
+	const HostImg<float> hout{intensity, outStart, outStride, w, h};
+	CHECK_IMG(ctx, hout);
 	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
-	BHIP_TRY(sc->out0.reserve(ctx, (size_t)w * h * 4));
-	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, ii, iiStart, iiStride, width, height, ctx->stream));
-	ImgView iv{sc->in0.as<float>(), (long long)width * height, width, width, height};
-	BHIP_TRY(bhip_launch_hessian(ctx, iv, 1, skip, 1, &size, sc->out0.as<float>(), (long long)w * h, (long long)w * h, w));
-	BHIP_TRY(download(ctx, intensity, outStart, outStride, sc->out0.as<float>(), w, w, h, ctx->stream));
+	DevImg<float> din, dout;
+	BHIP_TRY(stageIn(ctx, sc->in0, hin, width, din));
+	BHIP_TRY(stageIn(ctx, sc->out0, hout, w, dout, false));
+	ImgView iv{din.data, din.imageStride, width, width, height};
+	BHIP_TRY(bhip_launch_hessian(ctx, iv, 1, skip, 1, &size, dout.data, (long long)w * h, (long long)w * h, w));
+	BHIP_TRY(stageOut(ctx, hout, dout));
 	return bhip_ctx_synchronize(ctx);
 }
 
@@ -1186,23 +1203,24 @@ static int nonmaxDevice(bhip_ctx* ctx, const float* dev_intensity, long long ima
 int bhip_nonmax_block_dev_f32(bhip_ctx* ctx, const float* dev_intensity, long long imageStride, int stride, int width, int height, int batch, int radius,
 							  float threshold, int border, int16_t* dev_xy, int cap, int* dev_n) {
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, dev_intensity, stride, width, height, batch);
+	CHECK_IMG(ctx, (DevImg<const float>{dev_intensity, imageStride, stride, width, height, batch}));
 	if (!dev_n || cap < 0 || (cap > 0 && !dev_xy)) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad output");
 	return nonmaxDevice(ctx, dev_intensity, imageStride, stride, width, height, batch, radius, threshold, border, dev_xy, cap, dev_n);
 }
 
 int bhip_nonmax_block_f32(bhip_ctx* ctx, const float* intensity, int start, int stride, int width, int height, int radius, float threshold,
 						  int border, int16_t* xy, int cap, int* n) {
+	const HostImg<const float> hin{intensity, start, stride, width, height};
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, intensity, stride, width, height, 1);
+	CHECK_IMG(ctx, hin);
 	if (!n || cap < 0 || (cap > 0 && !xy)) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad output");
 	*n = 0;
 	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
+	DevImg<float> din;
+	BHIP_TRY(stageIn(ctx, sc->in0, hin, width, din));
 	BHIP_TRY(sc->out0.reserve(ctx, (size_t)std::max(cap, 1) * 4));
 	BHIP_TRY(sc->out1.reserve(ctx, 16));
-	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, intensity, start, stride, width, height, ctx->stream));
-	BHIP_TRY(nonmaxDevice(ctx, sc->in0.as<float>(), 0, width, width, height, 1, radius, threshold, border, sc->out0.as<int16_t>(), cap, sc->out1.as<int>()));
+	BHIP_TRY(nonmaxDevice(ctx, din.data, 0, width, width, height, 1, radius, threshold, border, sc->out0.as<int16_t>(), cap, sc->out1.as<int>()));
 	BHIP_HIP(ctx, hipMemcpyAsync(ctx->hostScratch.p, sc->out1.p, 4, hipMemcpyDeviceToHost, ctx->stream));
 	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the count decides how much of the list to copy
 	*n = ctx->hostScratch.as<int>()[0];
@@ -1214,8 +1232,9 @@ int bhip_nonmax_block_f32(bhip_ctx* ctx, const float* intensity, int start, int 
 
 int bhip_select_nbest_f32(bhip_ctx* ctx, const float* intensity, int start, int stride, int width, int height, const int16_t* xy, int n, int target,
 						  int positive, int16_t* out_xy, int* out_n) {
+	const HostImg<const float> hin{intensity, start, stride, width, height};
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, intensity, stride, width, height, 1);
+	CHECK_IMG(ctx, hin);
 	if (n < 0 || !out_n || (n > 0 && (!xy || !out_xy))) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad corner list");
 	for (int i = 0; i < n; i++)
 		if (xy[2 * i] < 0 || xy[2 * i] >= width || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= height)
@@ -1229,14 +1248,14 @@ int bhip_select_nbest_f32(bhip_ctx* ctx, const float* intensity, int start, int 
 	*out_n = 0;
 	if (target <= 0) return BHIP_OK;   // n > target, nothing to keep (QuickSelect with k = 0 is never reached with a positive N in the reference)
 	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
+	DevImg<float> din;
+	BHIP_TRY(stageIn(ctx, sc->in0, hin, width, din));
 	BHIP_TRY(sc->in1.reserve(ctx, (size_t)n * 4));
 	BHIP_TRY(sc->tmp0.reserve(ctx, (size_t)n * 4));
 	BHIP_TRY(sc->tmp1.reserve(ctx, (size_t)n * 4));
 	BHIP_TRY(sc->out0.reserve(ctx, (size_t)target * 4));
-	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, intensity, start, stride, width, height, ctx->stream));
 	BHIP_HIP(ctx, hipMemcpyAsync(sc->in1.p, xy, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-	BHIP_TRY(bhip_launch_select_nbest_xy(ctx, sc->in0.as<float>(), width, sc->in1.as<int16_t>(), n, target, positive != 0, sc->tmp0.as<float>(),
+	BHIP_TRY(bhip_launch_select_nbest_xy(ctx, din.data, width, sc->in1.as<int16_t>(), n, target, positive != 0, sc->tmp0.as<float>(),
 										 sc->tmp1.as<int>(), sc->out0.as<int16_t>()));
 	BHIP_HIP(ctx, hipMemcpyAsync(out_xy, sc->out0.p, (size_t)target * 4, hipMemcpyDeviceToHost, ctx->stream));
 	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1247,16 +1266,17 @@ int bhip_select_nbest_f32(bhip_ctx* ctx, const float* intensity, int start, int 
 // FastHessianFeatureDetector.detect(integral): intTaps = the integral image holds int32 (GrayS32, from a GrayU8 frame) instead of float
 static int fhDetect(bhip_ctx* ctx, const bhip_fh_cfg* cfg, const void* ii, bool intTaps, int iiStart, int iiStride, int width, int height,
 					double* xy_scale, int cap, int* n) {
+	const HostImg<const float> hin{(const float*)ii, iiStart, iiStride, width, height};   // 32-bit words either way
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, ii, iiStride, width, height, 1);
+	CHECK_IMG(ctx, hin);
 	if (!n || cap < 0 || (cap > 0 && !xy_scale)) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad output");
 	*n = 0;
 	FhDetector det;
 	det.intTaps = intTaps;
 	if (cfg) det.cfg = *cfg; else bhip_fh_cfg_default(&det.cfg);
 	CtxScratch* sc = scratchOf(ctx);
-	int status = sc->in0.reserve(ctx, (size_t)width * height * 4);
-	if (status == BHIP_OK) status = upload(ctx, sc->in0.as<float>(), width, (const float*)ii, iiStart, iiStride, width, height, ctx->stream);   // 32-bit words either way
+	DevImg<float> din;
+	int status = stageIn(ctx, sc->in0, hin, width, din);
 	if (status == BHIP_OK) status = det.prepare(ctx, width, height, 1);
 	ImgView iv{sc->in0.as<float>(), (long long)width * height, width, width, height};
 	if (status == BHIP_OK) status = det.run(ctx, iv);
@@ -1454,275 +1474,303 @@ int bhip_assoc_shard_phase2(bhip_ctx* ctx, const void* dev_colTopAll, int nranks
 
 // ---------------------------------------------------------------------------------------------------------------
 // boofcv-ip front end.  Most operations have a host-buffer export (the caller's image view) and a device-batched _dev export (BASELINE
-// config 5: pyramid -> gradient -> NMS -> SURF on a 4K stream without leaving HBM).  Both run one implementation (xxxImpl) on device
-// images: `batch` of them imageStride elements apart, rows `stride` elements apart, asynchronous on the ctx stream.  The _dev export calls
-// it after its argument checks.  The host export checks, stages the view (rows pitch4(width) apart where the tiled kernels apply, dense
-// otherwise), calls it with batch 1, downloads and synchronizes; when the implementation fails, nothing is downloaded.
+// config 5: pyramid -> gradient -> NMS -> SURF on a 4K stream without leaving HBM).  Both run one implementation -- an ip.hip launcher or
+// an xxxImpl around several -- on DevImg views of device images, asynchronous on the ctx stream.  The _dev export wraps the caller's
+// pointers into views and calls it after its argument checks.  The host export checks its HostImg views, stages them (stageIn / hostInOut:
+// rows pitch4(width) apart where the tiled kernels apply, dense otherwise), calls it with batch 1, downloads and synchronizes; when the
+// implementation fails, nothing is downloaded.
 // ---------------------------------------------------------------------------------------------------------------
 }  // extern "C"
 
-static int convImpl(bhip_ctx* ctx, bool vertical, bool normalized, const float* kernel, int kw, int koff, const float* in, long long inImageStride,
-					int inStride, int width, int height, int batch, float* out, long long outImageStride, int outStride) {
-	return bhip_launch_conv(ctx, vertical, normalized, kernel, kw, koff, in, inStride, width, height, out, outStride, batch, inImageStride, outImageStride);
-}
-
 // BlurImageOps.gaussian: one fused pass, or a horizontal pass into the library's `storage` and a vertical pass into `out`
-static int gaussianImpl(bhip_ctx* ctx, double sigma, int radius, const float* in, long long inImageStride, int inStride, int width, int height, int batch,
-						float* out, long long outImageStride, int outStride) {
+static int gaussianImpl(bhip_ctx* ctx, double sigma, int radius, DevImg<const float> in, DevImg<float> out) {
 	std::vector<float> k = bhip_gaussian1d_f32(sigma, radius);
 	const int kw = (int)k.size(), koff = kw / 2;
 	bool fused = false;
-	BHIP_TRY(bhip_launch_blur_fused(ctx, k.data(), kw, in, inStride, width, height, out, outStride, batch, inImageStride, outImageStride, &fused));
+	BHIP_TRY(bhip_launch_blur_fused(ctx, k.data(), kw, in, out, &fused));
 	if (fused) return BHIP_OK;
-	const int pitch = pitch4(width);
-	const long long tmpImage = (long long)pitch * height;
-	DevBuf& tmp = scratchOf(ctx)->ipTmp;
-	BHIP_TRY(tmp.reserve(ctx, (size_t)tmpImage * 4 * batch));
-	BHIP_TRY(bhip_launch_conv(ctx, false, true, k.data(), kw, koff, in, inStride, width, height, tmp.as<float>(), pitch, batch, inImageStride, tmpImage));
-	return bhip_launch_conv(ctx, true, true, k.data(), kw, koff, tmp.as<float>(), pitch, width, height, out, outStride, batch, tmpImage, outImageStride);
+	const int pitch = pitch4(in.width);
+	DevBuf& buf = scratchOf(ctx)->ipTmp;
+	BHIP_TRY(buf.reserve(ctx, (size_t)pitch * in.height * 4 * in.batch));
+	const DevImg<float> tmp = bhip_img_over<float>(buf, pitch, in.width, in.height, in.batch);
+	BHIP_TRY(bhip_launch_conv(ctx, false, true, k.data(), kw, koff, in, tmp));
+	return bhip_launch_conv(ctx, true, true, k.data(), kw, koff, tmp, out);
 }
 
-// GradientSobel / GradientThree (kind 0 / 1): GrayF32 -> GrayF32, GrayU8 -> GrayS16
-static int gradImpl(bhip_ctx* ctx, int kind, const float* in, long long inImageStride, int inStride, int width, int height, int batch, float* dx, float* dy,
-					long long outImageStride, int outStride, int border) {
-	return bhip_launch_gradient(ctx, kind, in, inStride, width, height, dx, dy, outStride, border, batch, inImageStride, outImageStride);
-}
-static int gradImpl(bhip_ctx* ctx, int kind, const uint8_t* in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dx,
-					int16_t* dy, long long outImageStride, int outStride, int border) {
-	return bhip_launch_gradient_u8(ctx, kind, in, inImageStride, inStride, width, height, batch, dx, dy, outImageStride, outStride, border);
-}
-
-// GradientCornerIntensity.process (FactoryIntensityPointAlg.shiTomasi / harris) on GrayF32 or GrayS16 (s16) derivatives: box window
+// GradientCornerIntensity.process (FactoryIntensityPointAlg.shiTomasi / harris) on GrayF32 or GrayS16 derivatives (T): box window
 // (ImplSsdCornerBox, ImplSsdCorner_S16) or Gaussian-weighted window (ImplSsdCornerWeighted_F32 / _S16)
-static int cornerImpl(bhip_ctx* ctx, bool s16, bool weighted, int kind, int radius, float kappa, const void* dx, const void* dy, long long dImageStride,
-					  int dStride, int width, int height, int batch, float* intensity, long long iImageStride, int iStride) {
-	if (weighted)
-		return bhip_launch_corner_weighted(ctx, s16, kind, radius, kappa, dx, dy, dImageStride, dStride, width, height, batch, intensity, iImageStride, iStride);
+template <class T>
+static int cornerImpl(bhip_ctx* ctx, bool weighted, int kind, int radius, float kappa, DevImg<const T> dx, DevImg<const T> dy, DevImg<float> intensity) {
+	if (weighted) return bhip_launch_corner_weighted(ctx, kind, radius, kappa, dx, dy, intensity);
+	const int width = dx.width, height = dx.height, batch = dx.batch;
 	DevBuf& tmp = scratchOf(ctx)->ipTmp;
-	if (s16) {
+	if constexpr (std::is_same_v<T, int16_t>) {
 		if (radius >= 0 && 2 * radius + 1 <= width && 2 * radius + 1 <= height) {
 			const size_t bytes = bhip_corner_box_s16_scratch(radius, width, height, batch);
 			if (bytes) BHIP_TRY(tmp.reserve(ctx, bytes));
 		}
-		return bhip_launch_corner_box_s16(ctx, kind, radius, kappa, (const int16_t*)dx, (const int16_t*)dy, dImageStride, dStride, width, height, batch,
-										  intensity, iImageStride, iStride, tmp.p);
+		return bhip_launch_corner_box_s16(ctx, kind, radius, kappa, dx, dy, intensity, tmp.p);
+	} else {
+		BHIP_TRY(tmp.reserve(ctx, (size_t)width * height * 4 * 3 * batch));
+		// ImageMiscOps.fillBorder(intensity, 0, radius): clear every image, the interior is overwritten
+		for (int b = 0; b < batch; b++)
+			BHIP_HIP(ctx, hipMemset2DAsync(intensity.data + b * intensity.imageStride, (size_t)intensity.stride * 4, 0, (size_t)width * 4, (size_t)height, ctx->stream));
+		return bhip_launch_corner_intensity(ctx, kind, radius, kappa, dx, dy, intensity, tmp.as<float>());
 	}
-	const size_t px = (size_t)width * height;
-	BHIP_TRY(tmp.reserve(ctx, px * 4 * 3 * batch));
-	// ImageMiscOps.fillBorder(intensity, 0, radius): clear every image, the interior is overwritten
-	for (int b = 0; b < batch; b++)
-		BHIP_HIP(ctx, hipMemset2DAsync(intensity + b * iImageStride, (size_t)iStride * 4, 0, (size_t)width * 4, (size_t)height, ctx->stream));
-	float* h = tmp.as<float>();
-	return bhip_launch_corner_intensity(ctx, kind, radius, kappa, (const float*)dx, (const float*)dy, dStride, width, height, h, h + px, h + 2 * px, intensity,
-										iStride, batch, dImageStride, (long long)px * 3, iImageStride);
 }
 
 // DescribePointBrief.process: the points of image b are xy[start[b] .. start[b+1]) (host prefix, batch+1 entries, at most maxCount per
 // image), or with start == nullptr the n points of one image; words of point p at out[p * ceil(numPoints/32)].  The first nSample sample
 // points are uploaded and decide between the LDS-patch and the gather kernel.
-static int briefImpl(bhip_ctx* ctx, bool u8, const void* img, long long imageStride, int stride, int width, int height, int batch, int radius, int numPoints,
-					 const int32_t* samplePoints, int nSample, const int32_t* compare, const double* xy, const int* start, int n, int maxCount, int32_t* out) {
+template <class T>
+static int briefImpl(bhip_ctx* ctx, DevImg<const T> img, int radius, int numPoints, const int32_t* samplePoints, int nSample, const int32_t* compare,
+					 const double* xy, const int* start, int n, int maxCount, int32_t* out) {
 	const size_t nS = (size_t)nSample * 2, nC = (size_t)numPoints * 2;
 	DevBuf& tab = scratchOf(ctx)->ipKernel;
-	BHIP_TRY(tab.reserve(ctx, (nS + nC + (start ? batch + 1 : 0)) * 4));
+	BHIP_TRY(tab.reserve(ctx, (nS + nC + (start ? img.batch + 1 : 0)) * 4));
 	int* dSample = tab.as<int>();
 	int* dCompare = dSample + nS;
 	int* dStart = start ? dCompare + nC : nullptr;
 	BHIP_HIP(ctx, hipMemcpyAsync(dSample, samplePoints, nS * 4, hipMemcpyHostToDevice, ctx->stream));
 	BHIP_HIP(ctx, hipMemcpyAsync(dCompare, compare, nC * 4, hipMemcpyHostToDevice, ctx->stream));
-	if (start) BHIP_HIP(ctx, hipMemcpyAsync(dStart, start, (size_t)(batch + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-	return bhip_launch_brief(ctx, (const float*)img, stride, width, height, radius, numPoints, dSample, dCompare, xy, n, out, u8, batch, imageStride, dStart,
-							 maxCount, 2, 0, briefPatchOk(samplePoints, nSample, radius));
+	if (start) BHIP_HIP(ctx, hipMemcpyAsync(dStart, start, (size_t)(img.batch + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+	return bhip_launch_brief(ctx, img, radius, numPoints, dSample, dCompare, xy, n, out, dStart, maxCount, 2, 0, briefPatchOk(samplePoints, nSample, radius));
 }
+
+static bool gradBorderOk(int kind, int border) { return border == 0 || border == 1 || (border == 2 && kind == 0); }   // 2 = BorderType.EXTENDED: GradientSobel only
 
 // host forms: GrayF32 gradients re-pitch rows to pitch4 (the streaming kernels), GrayU8 ones stay dense; without a border policy the frame
 // keeps the caller's values, so dx and dy are staged too
 template <class TI, class TO>
-static int gradHost(bhip_ctx* ctx, int kind, const TI* in, int inStart, int inStride, int width, int height, TO* dx, TO* dy, int outStart, int outStride,
-					int border) {
+static int gradHost(bhip_ctx* ctx, int kind, HostImg<const TI> in, HostImg<TO> dx, HostImg<TO> dy, int border) {
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, in, inStride, width, height, 1);
-	CHECK_IMG(ctx, dx, outStride, width, height, 1);
-	CHECK_IMG(ctx, dy, outStride, width, height, 1);
-	if (border != 0 && border != 1 && !(border == 2 && kind == 0))   // 2 = BorderType.EXTENDED: GradientSobel only
-		return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "border policy not supported on the GPU");
+	CHECK_IMG(ctx, in);
+	CHECK_IMG(ctx, dx);
+	CHECK_IMG(ctx, dy);
+	if (!gradBorderOk(kind, border)) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "border policy not supported on the GPU");
 	CtxScratch* sc = scratchOf(ctx);
-	const int pitch = sizeof(TI) == 4 ? pitch4(width) : width;
-	const long long img = (long long)pitch * height;
-	BHIP_TRY(sc->in0.reserve(ctx, img * sizeof(TI)));
-	BHIP_TRY(sc->out0.reserve(ctx, img * sizeof(TO)));
-	BHIP_TRY(sc->out1.reserve(ctx, img * sizeof(TO)));
-	TI* din = sc->in0.as<TI>();
-	TO *ddx = sc->out0.as<TO>(), *ddy = sc->out1.as<TO>();
-	BHIP_TRY(upload(ctx, din, pitch, in, inStart, inStride, width, height, ctx->stream));
-	BHIP_TRY(upload(ctx, ddx, pitch, dx, outStart, outStride, width, height, ctx->stream));
-	BHIP_TRY(upload(ctx, ddy, pitch, dy, outStart, outStride, width, height, ctx->stream));
-	BHIP_TRY(gradImpl(ctx, kind, din, img, pitch, width, height, 1, ddx, ddy, img, pitch, border));
-	BHIP_TRY(download(ctx, dx, outStart, outStride, ddx, pitch, width, height, ctx->stream));
-	BHIP_TRY(download(ctx, dy, outStart, outStride, ddy, pitch, width, height, ctx->stream));
+	const int pitch = sizeof(TI) == 4 ? pitch4(in.width) : in.width;
+	DevImg<TI> din;
+	DevImg<TO> ddx, ddy;
+	BHIP_TRY(stageIn(ctx, sc->in0, in, pitch, din));
+	BHIP_TRY(stageIn(ctx, sc->out0, dx, pitch, ddx));
+	BHIP_TRY(stageIn(ctx, sc->out1, dy, pitch, ddy));
+	BHIP_TRY(bhip_launch_gradient(ctx, kind, din, ddx, ddy, border));
+	BHIP_TRY(stageOut(ctx, dx, ddx));
+	BHIP_TRY(stageOut(ctx, dy, ddy));
 	return bhip_ctx_synchronize(ctx);
 }
 template <class TI, class TO>
-static int gradDev(bhip_ctx* ctx, int kind, const TI* dev_in, long long inImageStride, int inStride, int width, int height, int batch, TO* dev_dx, TO* dev_dy,
-				   long long outImageStride, int outStride, int border) {
+static int gradDev(bhip_ctx* ctx, int kind, DevImg<const TI> in, DevImg<TO> dx, DevImg<TO> dy, int border) {
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, dev_in, inStride, width, height, batch);
-	CHECK_IMG(ctx, dev_dx, outStride, width, height, batch);
-	CHECK_IMG(ctx, dev_dy, outStride, width, height, batch);
-	if (border != 0 && border != 1 && !(border == 2 && kind == 0))   // 2 = BorderType.EXTENDED: GradientSobel only
-		return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "border policy not supported on the GPU");
-	return gradImpl(ctx, kind, dev_in, inImageStride, inStride, width, height, batch, dev_dx, dev_dy, outImageStride, outStride, border);
+	CHECK_IMG(ctx, in);
+	CHECK_IMG(ctx, dx);
+	CHECK_IMG(ctx, dy);
+	if (!gradBorderOk(kind, border)) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "border policy not supported on the GPU");
+	return bhip_launch_gradient(ctx, kind, in, dx, dy, border);
 }
 
 // host forms of the corner intensity: dense derivatives (T = float or int16_t)
 template <class T>
-static int cornerHost(bhip_ctx* ctx, bool weighted, int kind, int radius, float kappa, const T* dx, const T* dy, int dStart, int dStride, int width, int height,
-					  float* intensity, int iStart, int iStride) {
+static int cornerHost(bhip_ctx* ctx, bool weighted, int kind, int radius, float kappa, HostImg<const T> dx, HostImg<const T> dy, HostImg<float> intensity) {
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, dx, dStride, width, height, 1);
-	CHECK_IMG(ctx, dy, dStride, width, height, 1);
-	CHECK_IMG(ctx, intensity, iStride, width, height, 1);
+	CHECK_IMG(ctx, dx);
+	CHECK_IMG(ctx, dy);
+	CHECK_IMG(ctx, intensity);
 	CtxScratch* sc = scratchOf(ctx);
-	const long long px = (long long)width * height;
-	BHIP_TRY(sc->in0.reserve(ctx, px * sizeof(T)));
-	BHIP_TRY(sc->in1.reserve(ctx, px * sizeof(T)));
-	BHIP_TRY(sc->out0.reserve(ctx, px * 4));
-	BHIP_TRY(upload(ctx, sc->in0.as<T>(), width, dx, dStart, dStride, width, height, ctx->stream));
-	BHIP_TRY(upload(ctx, sc->in1.as<T>(), width, dy, dStart, dStride, width, height, ctx->stream));
-	BHIP_TRY(cornerImpl(ctx, sizeof(T) == 2, weighted, kind, radius, kappa, sc->in0.p, sc->in1.p, px, width, width, height, 1, sc->out0.as<float>(), px, width));
-	BHIP_TRY(download(ctx, intensity, iStart, iStride, sc->out0.as<float>(), width, width, height, ctx->stream));
+	DevImg<T> ddx, ddy;
+	DevImg<float> dout;
+	BHIP_TRY(stageIn(ctx, sc->in0, dx, dx.width, ddx));
+	BHIP_TRY(stageIn(ctx, sc->in1, dy, dx.width, ddy));
+	BHIP_TRY(stageIn(ctx, sc->out0, intensity, dx.width, dout, false));
+	BHIP_TRY(cornerImpl<T>(ctx, weighted, kind, radius, kappa, ddx, ddy, dout));
+	BHIP_TRY(stageOut(ctx, intensity, dout));
 	return bhip_ctx_synchronize(ctx);
 }
-static int cornerDev(bhip_ctx* ctx, bool s16, bool weighted, int kind, int radius, float kappa, const void* dev_dx, const void* dev_dy, long long dImageStride,
-					 int dStride, int width, int height, int batch, float* dev_intensity, long long iImageStride, int iStride) {
+template <class T>
+static int cornerDev(bhip_ctx* ctx, bool weighted, int kind, int radius, float kappa, DevImg<const T> dx, DevImg<const T> dy, DevImg<float> intensity) {
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, dev_dx, dStride, width, height, batch);
-	CHECK_IMG(ctx, dev_dy, dStride, width, height, batch);
-	CHECK_IMG(ctx, dev_intensity, iStride, width, height, batch);
-	return cornerImpl(ctx, s16, weighted, kind, radius, kappa, dev_dx, dev_dy, dImageStride, dStride, width, height, batch, dev_intensity, iImageStride, iStride);
+	CHECK_IMG(ctx, dx);
+	CHECK_IMG(ctx, dy);
+	CHECK_IMG(ctx, intensity);
+	return cornerImpl<T>(ctx, weighted, kind, radius, kappa, dx, dy, intensity);
 }
 
 // bhip_brief_f32 / bhip_brief_u8 after their checks: the view staged dense, the n points as given
 template <class T>
-static int briefHost(bhip_ctx* ctx, const T* img, int start, int stride, int width, int height, int radius, int numPoints, const int32_t* samplePoints,
-					 int nSample, const int32_t* compare, const double* xy, int n, int32_t* out) {
+static int briefHost(bhip_ctx* ctx, HostImg<const T> img, int radius, int numPoints, const int32_t* samplePoints, int nSample, const int32_t* compare,
+					 const double* xy, int n, int32_t* out) {
 	CtxScratch* sc = scratchOf(ctx);
 	const size_t words = (numPoints + 31) / 32;
-	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * sizeof(T)));
+	DevImg<T> dimg;
+	BHIP_TRY(stageIn(ctx, sc->in0, img, img.width, dimg));
 	BHIP_TRY(sc->in1.reserve(ctx, (size_t)n * 16));
 	BHIP_TRY(sc->out0.reserve(ctx, (size_t)n * words * 4));
-	BHIP_TRY(upload(ctx, sc->in0.as<T>(), width, img, start, stride, width, height, ctx->stream));
 	BHIP_HIP(ctx, hipMemcpyAsync(sc->in1.p, xy, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-	BHIP_TRY(briefImpl(ctx, sizeof(T) == 1, sc->in0.p, (long long)width * height, width, width, height, 1, radius, numPoints, samplePoints, nSample, compare,
-					   sc->in1.as<double>(), nullptr, n, 0, sc->out0.as<int32_t>()));
+	BHIP_TRY(briefImpl<T>(ctx, dimg, radius, numPoints, samplePoints, nSample, compare, sc->in1.as<double>(), nullptr, n, 0, sc->out0.as<int32_t>()));
 	BHIP_HIP(ctx, hipMemcpyAsync(out, sc->out0.p, (size_t)n * words * 4, hipMemcpyDeviceToHost, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
+}
+
+static int convHost(bhip_ctx* ctx, bool vertical, bool normalized, const float* kernel, int kw, int koff, HostImg<const float> in, HostImg<float> out) {
+	// the no-border variants leave the frame of `out` untouched: it starts from the caller's pixels
+	return hostInOut<float, float>(ctx, in, out, true, true, kernel ? nullptr : "null kernel",
+								   [&](auto din, auto dout) { return bhip_launch_conv(ctx, vertical, normalized, kernel, kw, koff, din, dout); });
+}
+static int convDev(bhip_ctx* ctx, bool vertical, bool normalized, const float* kernel, int kw, int koff, DevImg<const float> in, DevImg<float> out) {
+	CHECK_CTX(ctx);
+	CHECK_IMG(ctx, in);
+	CHECK_IMG(ctx, out);
+	if (!kernel) return bhip_fail(ctx, BHIP_ERR_INVALID, "null kernel");
+	return bhip_launch_conv(ctx, vertical, normalized, kernel, kw, koff, in, out);
+}
+
+// ConvolveImageDownNormalized on a host view: Kernel1D_F32 on GrayF32 or Kernel1D_S32 on GrayU8, dense on the device; pixels the reference
+// does not write keep the caller's values
+template <class K, class T>
+static int convDownHost(bhip_ctx* ctx, bool vertical, const K* kernel, int kw, HostImg<const T> in, HostImg<T> out, int skip) {
+	return hostInOut<T, T>(ctx, in, out, false, true, kernel ? nullptr : "null kernel",
+						   [&](auto din, auto dout) { return bhip_launch_conv_down(ctx, vertical, kernel, kw, din, dout, skip); });
+}
+
+// PyramidDiscreteSampleBlur<T>.process on `batch` device frames: GrayF32 with a Kernel1D_F32, GrayU8 with a Kernel1D_S32; `out` holds the
+// layers of frame b from out + b * total (bhip_pyramid_layout).  The two pixel types differ where PyrTraits says so and nowhere else.
+// layer0Present (GrayU8 only): the caller has already put the frames into layer 0 (scale[0] == 1), so no copy is made.
+template <class T> struct PyrTraits;
+template <> struct PyrTraits<float> {
+	using Kernel = float;
+	static constexpr bool fusedLayer = true;    // bhip_launch_pyr_layer_fused is tried before the two passes
+	static constexpr bool clearLayer0 = true;   // the whole output is cleared, layer 0 at scale 1 included
+	static constexpr const char* copyTag = "pyramid_copy";
+	static constexpr double copyBytes = 8.0;    // per pixel
+};
+template <> struct PyrTraits<uint8_t> {
+	using Kernel = int32_t;
+	static constexpr bool fusedLayer = false;
+	static constexpr bool clearLayer0 = false;  // layer 0 at scale 1 is written (or already there) as a whole
+	static constexpr const char* copyTag = "pyramid_copy_u8";
+	static constexpr double copyBytes = 2.0;
+};
+template <class T>
+static int pyramidImpl(bhip_ctx* ctx, const typename PyrTraits<T>::Kernel* kernel, int kw, const int* scales, int n, DevImg<const T> in, T* out,
+					   bool layer0Present = false) {
+	using Tr = PyrTraits<T>;
+	const int width = in.width, height = in.height, batch = in.batch;
+	if (n > 32) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "more than 32 layers");
+	int dims[64];
+	long long offs[32], total = 0;
+	if (bhip_pyramid_layout(width, height, scales, n, dims, offs, &total) != BHIP_OK) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad pyramid scales");
+	for (int i = 1; i < n; i++)
+		if (scales[i] / scales[i - 1] <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Skip must be >= 1");
+	CtxScratch* sc = scratchOf(ctx);
+	const bool copy0 = scales[0] == 1;
+	// freshly created layers are zero (pixels outside floor(prev/skip) are never written)
+	if (Tr::clearLayer0) {
+		BHIP_HIP(ctx, hipMemsetAsync(out, 0, (size_t)total * batch * sizeof(T), ctx->stream));
+	} else {
+		const long long clearFrom = copy0 ? (n > 1 ? offs[1] : total) : 0;
+		if (total > clearFrom)
+			BHIP_HIP(ctx, hipMemset2DAsync(out + clearFrom, (size_t)total * sizeof(T), 0, (size_t)(total - clearFrom) * sizeof(T), (size_t)batch, ctx->stream));
+	}
+	// `temp` of the reference is one grow-only image shared by all layers: zero when first allocated, afterwards it keeps the
+	// previous layer's values wherever the off-grid skip>=3 case leaves a column unwritten.  Same here: one dense region per
+	// frame, sized for the first convolved layer, cleared once per call (= first process() of a fresh pyramid object).
+	long long tempCap = 0;
+	{
+		int pw0 = width, ph0 = height;
+		for (int i = 0; i < n; i++) {
+			if (!(i == 0 && copy0)) {
+				const int skip = i == 0 ? scales[0] : scales[i] / scales[i - 1];
+				tempCap = std::max(tempCap, (long long)(pw0 / skip) * ph0);
+			}
+			pw0 = dims[2 * i]; ph0 = dims[2 * i + 1];
+		}
+	}
+	if (tempCap > 0) {
+		BHIP_TRY(sc->ipTmp.reserve(ctx, (size_t)tempCap * sizeof(T) * batch));
+		BHIP_HIP(ctx, hipMemsetAsync(sc->ipTmp.p, 0, (size_t)tempCap * sizeof(T) * batch, ctx->stream));
+	}
+	DevImg<const T> prev = in;
+	for (int i = 0; i < n; i++) {
+		const DevImg<T> layer = bhip_pyr_layer(out, total, dims, offs, i, batch);
+		if (i == 0 && copy0) {
+			if (!layer0Present) {
+				ProfScope prof(ctx, Tr::copyTag, Tr::copyBytes * width * height * batch);
+				BHIP_TRY(bhip_launch_copy_images(ctx, in, layer));
+			}
+		} else {
+			const int skip = i == 0 ? scales[0] : scales[i] / scales[i - 1];
+			const int tw = prev.width / skip;   // 0 when the layer below is narrower than the step: both passes then write nothing and the (ceil-sized) layer stays zero, as in the reference
+			bool fused = false;
+			if constexpr (Tr::fusedLayer) BHIP_TRY(bhip_launch_pyr_layer_fused(ctx, kernel, kw, prev, layer, skip, &fused));
+			if (!fused) {
+				const DevImg<T> tmp{sc->ipTmp.as<T>(), tempCap, tw, tw, prev.height, batch};
+				BHIP_TRY(bhip_launch_conv_down(ctx, false, kernel, kw, prev, tmp, skip));
+				BHIP_TRY(bhip_launch_conv_down(ctx, true, kernel, kw, tmp, layer, skip));
+			}
+		}
+		prev = layer;
+	}
+	return BHIP_OK;
+}
+
+// host pyramid: the view staged dense, all layers downloaded as one block
+template <class T>
+static int pyramidHost(bhip_ctx* ctx, const typename PyrTraits<T>::Kernel* kernel, int kw, const int* scales, int n, HostImg<const T> in, T* out) {
+	CHECK_CTX(ctx);
+	CHECK_IMG(ctx, in);
+	if (!out || !kernel || !scales) return bhip_fail(ctx, BHIP_ERR_INVALID, "null buffer");
+	long long total = 0;
+	if (bhip_pyramid_layout(in.width, in.height, scales, n, nullptr, nullptr, &total) != BHIP_OK) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad pyramid scales");
+	CtxScratch* sc = scratchOf(ctx);
+	DevImg<T> din;
+	BHIP_TRY(stageIn(ctx, sc->in0, in, in.width, din));
+	BHIP_TRY(sc->out0.reserve(ctx, (size_t)total * sizeof(T)));
+	BHIP_TRY(pyramidImpl<T>(ctx, kernel, kw, scales, n, din, sc->out0.as<T>()));
+	BHIP_HIP(ctx, hipMemcpyAsync(out, sc->out0.p, (size_t)total * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
 	return bhip_ctx_synchronize(ctx);
 }
 
 extern "C" {
 
-static int convHost(bhip_ctx* ctx, bool vertical, bool normalized, const float* kernel, int kw, int koff, const float* in, int inStart, int inStride,
-					int width, int height, float* out, int outStart, int outStride) {
-	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, in, inStride, width, height, 1);
-	CHECK_IMG(ctx, out, outStride, width, height, 1);
-	if (!kernel) return bhip_fail(ctx, BHIP_ERR_INVALID, "null kernel");
-	CtxScratch* sc = scratchOf(ctx);
-	const int pitch = pitch4(width);
-	const long long img = (long long)pitch * height;
-	BHIP_TRY(sc->in0.reserve(ctx, img * 4));
-	BHIP_TRY(sc->out0.reserve(ctx, img * 4));
-	BHIP_TRY(upload(ctx, sc->in0.as<float>(), pitch, in, inStart, inStride, width, height, ctx->stream));
-	// the no-border variants leave the frame of `out` untouched: start from the caller's pixels
-	BHIP_TRY(upload(ctx, sc->out0.as<float>(), pitch, out, outStart, outStride, width, height, ctx->stream));
-	BHIP_TRY(convImpl(ctx, vertical, normalized, kernel, kw, koff, sc->in0.as<float>(), img, pitch, width, height, 1, sc->out0.as<float>(), img, pitch));
-	BHIP_TRY(download(ctx, out, outStart, outStride, sc->out0.as<float>(), pitch, width, height, ctx->stream));
-	return bhip_ctx_synchronize(ctx);
-}
 int bhip_conv_h_f32(bhip_ctx* ctx, const float* kernel, int kw, int koff, const float* in, int inStart, int inStride, int width, int height, float* out,
 					int outStart, int outStride) {
-	return convHost(ctx, false, false, kernel, kw, koff, in, inStart, inStride, width, height, out, outStart, outStride);
+	return convHost(ctx, false, false, kernel, kw, koff, {in, inStart, inStride, width, height}, {out, outStart, outStride, width, height});
 }
 int bhip_conv_v_f32(bhip_ctx* ctx, const float* kernel, int kw, int koff, const float* in, int inStart, int inStride, int width, int height, float* out,
 					int outStart, int outStride) {
-	return convHost(ctx, true, false, kernel, kw, koff, in, inStart, inStride, width, height, out, outStart, outStride);
+	return convHost(ctx, true, false, kernel, kw, koff, {in, inStart, inStride, width, height}, {out, outStart, outStride, width, height});
 }
 int bhip_conv_norm_h_f32(bhip_ctx* ctx, const float* kernel, int kw, int koff, const float* in, int inStart, int inStride, int width, int height,
 						 float* out, int outStart, int outStride) {
-	return convHost(ctx, false, true, kernel, kw, koff, in, inStart, inStride, width, height, out, outStart, outStride);
+	return convHost(ctx, false, true, kernel, kw, koff, {in, inStart, inStride, width, height}, {out, outStart, outStride, width, height});
 }
 int bhip_conv_norm_v_f32(bhip_ctx* ctx, const float* kernel, int kw, int koff, const float* in, int inStart, int inStride, int width, int height,
 						 float* out, int outStart, int outStride) {
-	return convHost(ctx, true, true, kernel, kw, koff, in, inStart, inStride, width, height, out, outStart, outStride);
+	return convHost(ctx, true, true, kernel, kw, koff, {in, inStart, inStride, width, height}, {out, outStart, outStride, width, height});
 }
 
 int bhip_gaussian_f32(bhip_ctx* ctx, const float* in, int inStart, int inStride, int width, int height, double sigma, int radius, float* out,
 					  int outStart, int outStride) {
-	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, in, inStride, width, height, 1);
-	CHECK_IMG(ctx, out, outStride, width, height, 1);
-	if (sigma <= 0 && radius <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Sigma must be > 0");
-	CtxScratch* sc = scratchOf(ctx);
-	const int pitch = pitch4(width);
-	const long long img = (long long)pitch * height;
-	BHIP_TRY(sc->in0.reserve(ctx, img * 4));
-	BHIP_TRY(sc->out0.reserve(ctx, img * 4));
-	BHIP_TRY(upload(ctx, sc->in0.as<float>(), pitch, in, inStart, inStride, width, height, ctx->stream));
-	BHIP_TRY(gaussianImpl(ctx, sigma, radius, sc->in0.as<float>(), img, pitch, width, height, 1, sc->out0.as<float>(), img, pitch));
-	BHIP_TRY(download(ctx, out, outStart, outStride, sc->out0.as<float>(), pitch, width, height, ctx->stream));
-	return bhip_ctx_synchronize(ctx);
+	return hostInOut<float, float>(ctx, {in, inStart, inStride, width, height}, {out, outStart, outStride, width, height}, true, false,
+								   sigma <= 0 && radius <= 0 ? "Sigma must be > 0" : nullptr, [&](auto din, auto dout) { return gaussianImpl(ctx, sigma, radius, din, dout); });
 }
 
-static int convDownHost(bhip_ctx* ctx, bool vertical, const float* kernel, int kw, const float* in, int inStart, int inStride, int width, int height,
-						float* out, int outStart, int outStride, int outWidth, int outHeight, int skip) {
-	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, in, inStride, width, height, 1);
-	CHECK_IMG(ctx, out, outStride, outWidth, outHeight, 1);
-	if (!kernel) return bhip_fail(ctx, BHIP_ERR_INVALID, "null kernel");
-	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
-	BHIP_TRY(sc->out0.reserve(ctx, (size_t)outWidth * outHeight * 4));
-	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, in, inStart, inStride, width, height, ctx->stream));
-	// pixels the reference does not write keep the caller's values
-	BHIP_TRY(upload(ctx, sc->out0.as<float>(), outWidth, out, outStart, outStride, outWidth, outHeight, ctx->stream));
-	BHIP_TRY(bhip_launch_conv_down(ctx, vertical, kernel, kw, sc->in0.as<float>(), 0, width, width, height, sc->out0.as<float>(), 0, outWidth, outWidth,
-								   outHeight, skip, 1));
-	BHIP_TRY(download(ctx, out, outStart, outStride, sc->out0.as<float>(), outWidth, outWidth, outHeight, ctx->stream));
-	return bhip_ctx_synchronize(ctx);
-}
 int bhip_conv_down_norm_h_f32(bhip_ctx* ctx, const float* kernel, int kw, const float* in, int inStart, int inStride, int width, int height, float* out,
 							  int outStart, int outStride, int outWidth, int outHeight, int skip) {
-	return convDownHost(ctx, false, kernel, kw, in, inStart, inStride, width, height, out, outStart, outStride, outWidth, outHeight, skip);
+	return convDownHost<float, float>(ctx, false, kernel, kw, {in, inStart, inStride, width, height}, {out, outStart, outStride, outWidth, outHeight}, skip);
 }
 int bhip_conv_down_norm_v_f32(bhip_ctx* ctx, const float* kernel, int kw, const float* in, int inStart, int inStride, int width, int height, float* out,
 							  int outStart, int outStride, int outWidth, int outHeight, int skip) {
-	return convDownHost(ctx, true, kernel, kw, in, inStart, inStride, width, height, out, outStart, outStride, outWidth, outHeight, skip);
-}
-
-static int convDownHostU8(bhip_ctx* ctx, bool vertical, const int32_t* kernel, int kw, const uint8_t* in, int inStart, int inStride, int width, int height,
-						  uint8_t* out, int outStart, int outStride, int outWidth, int outHeight, int skip) {
-	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, in, inStride, width, height, 1);
-	CHECK_IMG(ctx, out, outStride, outWidth, outHeight, 1);
-	if (!kernel) return bhip_fail(ctx, BHIP_ERR_INVALID, "null kernel");
-	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height));
-	BHIP_TRY(sc->out0.reserve(ctx, (size_t)outWidth * outHeight));
-	BHIP_TRY(upload(ctx, sc->in0.as<uint8_t>(), width, in, inStart, inStride, width, height, ctx->stream));
-	// pixels the reference does not write keep the caller's values
-	BHIP_TRY(upload(ctx, sc->out0.as<uint8_t>(), outWidth, (const uint8_t*)out, outStart, outStride, outWidth, outHeight, ctx->stream));
-	BHIP_TRY(bhip_launch_conv_down_u8(ctx, vertical, kernel, kw, sc->in0.as<uint8_t>(), 0, width, width, height, sc->out0.as<uint8_t>(), 0, outWidth, outWidth,
-									  outHeight, skip, 1));
-	BHIP_TRY(download(ctx, out, outStart, outStride, (const uint8_t*)sc->out0.as<uint8_t>(), outWidth, outWidth, outHeight, ctx->stream));
-	return bhip_ctx_synchronize(ctx);
+	return convDownHost<float, float>(ctx, true, kernel, kw, {in, inStart, inStride, width, height}, {out, outStart, outStride, outWidth, outHeight}, skip);
 }
 int bhip_conv_down_norm_h_u8(bhip_ctx* ctx, const int32_t* kernel, int kw, const uint8_t* in, int inStart, int inStride, int width, int height, uint8_t* out,
 							 int outStart, int outStride, int outWidth, int outHeight, int skip) {
-	return convDownHostU8(ctx, false, kernel, kw, in, inStart, inStride, width, height, out, outStart, outStride, outWidth, outHeight, skip);
+	return convDownHost<int32_t, uint8_t>(ctx, false, kernel, kw, {in, inStart, inStride, width, height}, {out, outStart, outStride, outWidth, outHeight}, skip);
 }
 int bhip_conv_down_norm_v_u8(bhip_ctx* ctx, const int32_t* kernel, int kw, const uint8_t* in, int inStart, int inStride, int width, int height, uint8_t* out,
 							 int outStart, int outStride, int outWidth, int outHeight, int skip) {
-	return convDownHostU8(ctx, true, kernel, kw, in, inStart, inStride, width, height, out, outStart, outStride, outWidth, outHeight, skip);
+	return convDownHost<int32_t, uint8_t>(ctx, true, kernel, kw, {in, inStart, inStride, width, height}, {out, outStart, outStride, outWidth, outHeight}, skip);
 }
 
 // FactoryKernelGaussian.gaussian(Kernel1D_F32.class, sigma, radius) (I:factory/filter/kernel/FactoryKernelGaussian.java:120-153)
@@ -1732,6 +1780,27 @@ int bhip_gaussian_kernel1d_f32(double sigma, int radius, float* out, int capacit
 	if (!out || (int)k.size() > capacity) return -(int)k.size();
 	for (size_t i = 0; i < k.size(); i++) out[i] = k[i];
 	return (int)k.size();
+}
+
+int bhip_pyramid_dev_f32(bhip_ctx* ctx, const float* kernel, int kw, const int* scales, int n, const float* dev_in, long long inImageStride, int inStride,
+						 int width, int height, int batch, float* dev_out) {
+	CHECK_CTX(ctx);
+	if (!kernel || !dev_in || !dev_out || batch <= 0 || inStride < width) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad pyramid arguments");
+	return pyramidImpl<float>(ctx, kernel, kw, scales, n, {dev_in, inImageStride, inStride, width, height, batch}, dev_out);
+}
+int bhip_pyramid_dev_u8(bhip_ctx* ctx, const int32_t* kernel, int kw, const int* scales, int n, const uint8_t* dev_in, long long inImageStride, int inStride,
+						int width, int height, int batch, uint8_t* dev_out) {
+	CHECK_CTX(ctx);
+	if (!kernel || !scales || !dev_in || !dev_out || batch <= 0 || width <= 0 || height <= 0 || inStride < width) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad pyramid arguments");
+	return pyramidImpl<uint8_t>(ctx, kernel, kw, scales, n, {dev_in, inImageStride, inStride, width, height, batch}, dev_out);
+}
+int bhip_pyramid_u8(bhip_ctx* ctx, const int32_t* kernel, int kw, const int* scales, int n, const uint8_t* in, int inStart, int inStride, int width, int height,
+					uint8_t* out) {
+	return pyramidHost<uint8_t>(ctx, kernel, kw, scales, n, {in, inStart, inStride, width, height}, out);
+}
+int bhip_pyramid_f32(bhip_ctx* ctx, const float* kernel, int kw, const int* scales, int n, const float* in, int inStart, int inStride, int width,
+					 int height, float* out) {
+	return pyramidHost<float>(ctx, kernel, kw, scales, n, {in, inStart, inStride, width, height}, out);
 }
 
 // PyramidDiscreteSampleBlur: layer geometry (ImagePyramidBase.initialize) + scale checks (ImagePyramidBase.checkScales)
@@ -1754,232 +1823,59 @@ int bhip_pyramid_layout(int width, int height, const int* scales, int n, int* di
 	return BHIP_OK;
 }
 
-int bhip_pyramid_dev_f32(bhip_ctx* ctx, const float* kernel, int kw, const int* scales, int n, const float* dev_in, long long inImageStride, int inStride,
-						 int width, int height, int batch, float* dev_out) {
-	CHECK_CTX(ctx);
-	if (!kernel || !dev_in || !dev_out || batch <= 0 || inStride < width) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad pyramid arguments");
-	if (n > 32) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "more than 32 layers");
-	int dims[64];
-	long long offs[32], total = 0;
-	if (bhip_pyramid_layout(width, height, scales, n, dims, offs, &total) != BHIP_OK) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad pyramid scales");
-	for (int i = 1; i < n; i++)
-		if (scales[i] / scales[i - 1] <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Skip must be >= 1");
-	CtxScratch* sc = scratchOf(ctx);
-	// freshly created layers are zero (pixels outside floor(prev/skip) are never written)
-	BHIP_HIP(ctx, hipMemsetAsync(dev_out, 0, (size_t)total * batch * 4, ctx->stream));
-	// `temp` of the reference is one grow-only image shared by all layers: zero when first allocated, afterwards it keeps the
-	// previous layer's values wherever the off-grid skip>=3 case leaves a column unwritten.  Same here: one dense region per
-	// frame, sized for the first convolved layer, cleared once per call (= first process() of a fresh pyramid object).
-	long long tempCap = 0;
-	{
-		int pw0 = width, ph0 = height;
-		for (int i = 0; i < n; i++) {
-			if (!(i == 0 && scales[0] == 1)) {
-				const int skip = i == 0 ? scales[0] : scales[i] / scales[i - 1];
-				tempCap = std::max(tempCap, (long long)(pw0 / skip) * ph0);
-			}
-			pw0 = dims[2 * i]; ph0 = dims[2 * i + 1];
-		}
-	}
-	if (tempCap > 0) {
-		BHIP_TRY(sc->ipTmp.reserve(ctx, (size_t)tempCap * 4 * batch));
-		BHIP_HIP(ctx, hipMemsetAsync(sc->ipTmp.p, 0, (size_t)tempCap * 4 * batch, ctx->stream));
-	}
-	const float* prev = dev_in;
-	long long prevImageStride = inImageStride;
-	int prevStride = inStride, pw = width, ph = height;
-	for (int i = 0; i < n; i++) {
-		float* layer = dev_out + offs[i];
-		const int lw = dims[2 * i], lh = dims[2 * i + 1];
-		if (i == 0 && scales[0] == 1) {
-			ProfScope prof(ctx, "pyramid_copy", 8.0 * width * height * batch);
-			BHIP_TRY(bhip_launch_copy_images(ctx, dev_in, inImageStride, inStride, layer, total, lw, width, height, batch));
-		} else {
-			const int skip = i == 0 ? scales[0] : scales[i] / scales[i - 1];
-			const int tw = pw / skip;   // 0 when the layer below is narrower than the step: both passes then write nothing and the (ceil-sized) layer stays zero, as in the reference
-			bool fused = false;
-			BHIP_TRY(bhip_launch_pyr_layer_fused(ctx, kernel, kw, prev, prevImageStride, prevStride, pw, ph, layer, total, lw, skip, batch, &fused));
-			if (!fused) {
-				BHIP_TRY(bhip_launch_conv_down(ctx, false, kernel, kw, prev, prevImageStride, prevStride, pw, ph, sc->ipTmp.as<float>(), tempCap, tw, tw, ph, skip,
-											   batch));
-				BHIP_TRY(bhip_launch_conv_down(ctx, true, kernel, kw, sc->ipTmp.as<float>(), tempCap, tw, tw, ph, layer, total, lw, lw, lh, skip, batch));
-			}
-		}
-		prev = layer; prevImageStride = total; prevStride = lw; pw = lw; ph = lh;
-	}
-	return BHIP_OK;
-}
-
-}  // extern "C"
-
-// PyramidDiscreteSampleBlur<GrayU8>.process on `batch` device frames (see bhip_pyramid_dev_f32 for `temp` and the zero-filled layers).
-// layer0Present: the caller has already put the frames into layer 0 (scale[0] == 1), so no copy is made.
-static int pyramidU8Impl(bhip_ctx* ctx, const int32_t* kernel, int kw, const int* scales, int n, const uint8_t* dev_in, long long inImageStride, int inStride,
-						 int width, int height, int batch, uint8_t* dev_out, bool layer0Present) {
-	if (n > 32) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "more than 32 layers");
-	int dims[64];
-	long long offs[32], total = 0;
-	if (bhip_pyramid_layout(width, height, scales, n, dims, offs, &total) != BHIP_OK) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad pyramid scales");
-	for (int i = 1; i < n; i++)
-		if (scales[i] / scales[i - 1] <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Skip must be >= 1");
-	CtxScratch* sc = scratchOf(ctx);
-	const bool copy0 = scales[0] == 1;
-	// freshly created layers are zero; layer 0 at scale 1 is written (or already there) as a whole
-	const long long clearFrom = copy0 ? (n > 1 ? offs[1] : total) : 0;
-	if (total > clearFrom)
-		BHIP_HIP(ctx, hipMemset2DAsync(dev_out + clearFrom, (size_t)total, 0, (size_t)(total - clearFrom), (size_t)batch, ctx->stream));
-	long long tempCap = 0;
-	{
-		int pw0 = width, ph0 = height;
-		for (int i = 0; i < n; i++) {
-			if (!(i == 0 && copy0)) {
-				const int skip = i == 0 ? scales[0] : scales[i] / scales[i - 1];
-				tempCap = std::max(tempCap, (long long)(pw0 / skip) * ph0);
-			}
-			pw0 = dims[2 * i]; ph0 = dims[2 * i + 1];
-		}
-	}
-	if (tempCap > 0) {
-		BHIP_TRY(sc->ipTmp.reserve(ctx, (size_t)tempCap * batch));
-		BHIP_HIP(ctx, hipMemsetAsync(sc->ipTmp.p, 0, (size_t)tempCap * batch, ctx->stream));
-	}
-	const uint8_t* prev = dev_in;
-	long long prevImageStride = inImageStride;
-	int prevStride = inStride, pw = width, ph = height;
-	for (int i = 0; i < n; i++) {
-		uint8_t* layer = dev_out + offs[i];
-		const int lw = dims[2 * i], lh = dims[2 * i + 1];
-		if (i == 0 && copy0) {
-			if (!layer0Present) {
-				ProfScope prof(ctx, "pyramid_copy_u8", 2.0 * width * height * batch);
-				BHIP_TRY(bhip_launch_copy_images_u8(ctx, dev_in, inImageStride, inStride, layer, total, lw, width, height, batch));
-			}
-		} else {
-			const int skip = i == 0 ? scales[0] : scales[i] / scales[i - 1];
-			const int tw = pw / skip;
-			uint8_t* tmp = sc->ipTmp.as<uint8_t>();
-			BHIP_TRY(bhip_launch_conv_down_u8(ctx, false, kernel, kw, prev, prevImageStride, prevStride, pw, ph, tmp, tempCap, tw, tw, ph, skip, batch));
-			BHIP_TRY(bhip_launch_conv_down_u8(ctx, true, kernel, kw, tmp, tempCap, tw, tw, ph, layer, total, lw, lw, lh, skip, batch));
-		}
-		prev = layer; prevImageStride = total; prevStride = lw; pw = lw; ph = lh;
-	}
-	return BHIP_OK;
-}
-
-extern "C" {
-
-int bhip_pyramid_dev_u8(bhip_ctx* ctx, const int32_t* kernel, int kw, const int* scales, int n, const uint8_t* dev_in, long long inImageStride, int inStride,
-						int width, int height, int batch, uint8_t* dev_out) {
-	CHECK_CTX(ctx);
-	if (!kernel || !scales || !dev_in || !dev_out || batch <= 0 || width <= 0 || height <= 0 || inStride < width) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad pyramid arguments");
-	return pyramidU8Impl(ctx, kernel, kw, scales, n, dev_in, inImageStride, inStride, width, height, batch, dev_out, false);
-}
-
-int bhip_pyramid_u8(bhip_ctx* ctx, const int32_t* kernel, int kw, const int* scales, int n, const uint8_t* in, int inStart, int inStride, int width, int height,
-					uint8_t* out) {
-	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, in, inStride, width, height, 1);
-	if (!out || !kernel || !scales) return bhip_fail(ctx, BHIP_ERR_INVALID, "null buffer");
-	long long total = 0;
-	if (bhip_pyramid_layout(width, height, scales, n, nullptr, nullptr, &total) != BHIP_OK) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad pyramid scales");
-	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height));
-	BHIP_TRY(sc->out0.reserve(ctx, (size_t)total));
-	BHIP_TRY(upload(ctx, sc->in0.as<uint8_t>(), width, in, inStart, inStride, width, height, ctx->stream));
-	BHIP_TRY(pyramidU8Impl(ctx, kernel, kw, scales, n, sc->in0.as<uint8_t>(), (long long)width * height, width, width, height, 1, sc->out0.as<uint8_t>(), false));
-	BHIP_HIP(ctx, hipMemcpyAsync(out, sc->out0.p, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
-	return bhip_ctx_synchronize(ctx);
-}
-
-int bhip_pyramid_f32(bhip_ctx* ctx, const float* kernel, int kw, const int* scales, int n, const float* in, int inStart, int inStride, int width,
-					 int height, float* out) {
-	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, in, inStride, width, height, 1);
-	if (!out || !kernel || !scales) return bhip_fail(ctx, BHIP_ERR_INVALID, "null buffer");
-	long long total = 0;
-	if (bhip_pyramid_layout(width, height, scales, n, nullptr, nullptr, &total) != BHIP_OK) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad pyramid scales");
-	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
-	BHIP_TRY(sc->out0.reserve(ctx, (size_t)total * 4));
-	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, in, inStart, inStride, width, height, ctx->stream));
-	BHIP_TRY(bhip_pyramid_dev_f32(ctx, kernel, kw, scales, n, sc->in0.as<float>(), (long long)width * height, width, width, height, 1, sc->out0.as<float>()));
-	BHIP_HIP(ctx, hipMemcpyAsync(out, sc->out0.p, (size_t)total * 4, hipMemcpyDeviceToHost, ctx->stream));
-	return bhip_ctx_synchronize(ctx);
-}
-
 int bhip_conv2d_f32(bhip_ctx* ctx, const float* kernel, int kw, int koff, const float* in, int inStart, int inStride, int width, int height, float* out,
 					int outStart, int outStride) {
-	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, in, inStride, width, height, 1);
-	CHECK_IMG(ctx, out, outStride, width, height, 1);
-	if (!kernel) return bhip_fail(ctx, BHIP_ERR_INVALID, "null kernel");
-	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
-	BHIP_TRY(sc->out0.reserve(ctx, (size_t)width * height * 4));
-	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, in, inStart, inStride, width, height, ctx->stream));
-	BHIP_TRY(upload(ctx, sc->out0.as<float>(), width, out, outStart, outStride, width, height, ctx->stream));   // the frame keeps the caller's pixels
-	BHIP_TRY(bhip_launch_conv2d(ctx, kernel, kw, koff, sc->in0.as<float>(), width, width, height, sc->out0.as<float>(), width));
-	BHIP_TRY(download(ctx, out, outStart, outStride, sc->out0.as<float>(), width, width, height, ctx->stream));
-	return bhip_ctx_synchronize(ctx);
+	// the frame keeps the caller's pixels
+	return hostInOut<float, float>(ctx, {in, inStart, inStride, width, height}, {out, outStart, outStride, width, height}, false, true, kernel ? nullptr : "null kernel",
+								   [&](auto din, auto dout) { return bhip_launch_conv2d(ctx, kernel, kw, koff, din, dout); });
 }
 int bhip_mean_f32(bhip_ctx* ctx, const float* in, int inStart, int inStride, int width, int height, int radiusX, int radiusY, float* out, int outStart,
 				  int outStride) {
-	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, in, inStride, width, height, 1);
-	CHECK_IMG(ctx, out, outStride, width, height, 1);
-	if (radiusX <= 0 || radiusY <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Radius must be > 0");
-	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
-	BHIP_TRY(sc->tmp0.reserve(ctx, (size_t)width * height * 4));
-	BHIP_TRY(sc->out0.reserve(ctx, (size_t)width * height * 4));
-	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, in, inStart, inStride, width, height, ctx->stream));
-	BHIP_TRY(bhip_launch_mean(ctx, false, sc->in0.as<float>(), sc->tmp0.as<float>(), width, height, radiusX));
-	BHIP_TRY(bhip_launch_mean(ctx, true, sc->tmp0.as<float>(), sc->out0.as<float>(), width, height, radiusY));
-	BHIP_TRY(download(ctx, out, outStart, outStride, sc->out0.as<float>(), width, width, height, ctx->stream));
-	return bhip_ctx_synchronize(ctx);
+	return hostInOut<float, float>(ctx, {in, inStart, inStride, width, height}, {out, outStart, outStride, width, height}, false, false,
+								   radiusX <= 0 || radiusY <= 0 ? "Radius must be > 0" : nullptr, [&](auto din, DevImg<float> dout) {
+		DevBuf& buf = scratchOf(ctx)->tmp0;   // the horizontal pass's result
+		BHIP_TRY(buf.reserve(ctx, (size_t)width * height * 4));
+		const DevImg<float> dtmp = bhip_img_over<float>(buf, width, width, height, 1);
+		BHIP_TRY(bhip_launch_mean(ctx, false, din, dtmp, radiusX));
+		return bhip_launch_mean(ctx, true, dtmp, dout, radiusY);
+	});
 }
 int bhip_median_f32(bhip_ctx* ctx, const float* in, int inStart, int inStride, int width, int height, int radius, float* out, int outStart, int outStride) {
-	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, in, inStride, width, height, 1);
-	CHECK_IMG(ctx, out, outStride, width, height, 1);
-	if (radius <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Radius must be > 0");
-	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
-	BHIP_TRY(sc->out0.reserve(ctx, (size_t)width * height * 4));
-	BHIP_TRY(upload(ctx, sc->in0.as<float>(), width, in, inStart, inStride, width, height, ctx->stream));
-	BHIP_TRY(bhip_launch_median(ctx, sc->in0.as<float>(), width, sc->out0.as<float>(), width, width, height, radius));
-	BHIP_TRY(download(ctx, out, outStart, outStride, sc->out0.as<float>(), width, width, height, ctx->stream));
-	return bhip_ctx_synchronize(ctx);
+	return hostInOut<float, float>(ctx, {in, inStart, inStride, width, height}, {out, outStart, outStride, width, height}, false, false,
+								   radius <= 0 ? "Radius must be > 0" : nullptr, [&](auto din, auto dout) { return bhip_launch_median(ctx, din, dout, radius); });
 }
 
 int bhip_sobel_f32(bhip_ctx* ctx, const float* in, int inStart, int inStride, int width, int height, float* dx, float* dy, int outStart, int outStride,
 				   int border) {
-	return gradHost(ctx, 0, in, inStart, inStride, width, height, dx, dy, outStart, outStride, border);
+	return gradHost<float, float>(ctx, 0, {in, inStart, inStride, width, height}, {dx, outStart, outStride, width, height}, {dy, outStart, outStride, width, height}, border);
 }
 int bhip_three_f32(bhip_ctx* ctx, const float* in, int inStart, int inStride, int width, int height, float* dx, float* dy, int outStart, int outStride,
 				   int border) {
-	return gradHost(ctx, 1, in, inStart, inStride, width, height, dx, dy, outStart, outStride, border);
+	return gradHost<float, float>(ctx, 1, {in, inStart, inStride, width, height}, {dx, outStart, outStride, width, height}, {dy, outStart, outStride, width, height}, border);
 }
 int bhip_sobel_u8_s16(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, int16_t* dx, int16_t* dy, int outStart,
 					  int outStride, int border) {
-	return gradHost(ctx, 0, in, inStart, inStride, width, height, dx, dy, outStart, outStride, border);
+	return gradHost<uint8_t, int16_t>(ctx, 0, {in, inStart, inStride, width, height}, {dx, outStart, outStride, width, height}, {dy, outStart, outStride, width, height}, border);
 }
 int bhip_three_u8_s16(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, int16_t* dx, int16_t* dy, int outStart,
 					  int outStride, int border) {
-	return gradHost(ctx, 1, in, inStart, inStride, width, height, dx, dy, outStart, outStride, border);
+	return gradHost<uint8_t, int16_t>(ctx, 1, {in, inStart, inStride, width, height}, {dx, outStart, outStride, width, height}, {dy, outStart, outStride, width, height}, border);
 }
 
 int bhip_corner_intensity_f32(bhip_ctx* ctx, int kind, int radius, float kappa, const float* derivX, const float* derivY, int dStart, int dStride, int width,
 							  int height, float* intensity, int iStart, int iStride) {
-	return cornerHost(ctx, false, kind, radius, kappa, derivX, derivY, dStart, dStride, width, height, intensity, iStart, iStride);
+	return cornerHost<float>(ctx, false, kind, radius, kappa, {derivX, dStart, dStride, width, height}, {derivY, dStart, dStride, width, height},
+							 {intensity, iStart, iStride, width, height});
 }
 int bhip_corner_intensity_s16(bhip_ctx* ctx, int kind, int radius, float kappa, int weighted, const int16_t* derivX, const int16_t* derivY, int dStart,
 							  int dStride, int width, int height, float* intensity, int iStart, int iStride) {
-	return cornerHost(ctx, weighted != 0, kind, radius, kappa, derivX, derivY, dStart, dStride, width, height, intensity, iStart, iStride);
+	return cornerHost<int16_t>(ctx, weighted != 0, kind, radius, kappa, {derivX, dStart, dStride, width, height}, {derivY, dStart, dStride, width, height},
+							   {intensity, iStart, iStride, width, height});
 }
 int bhip_corner_intensity_weighted_f32(bhip_ctx* ctx, int kind, int radius, float kappa, const float* derivX, const float* derivY, int dStart, int dStride,
 									   int width, int height, float* intensity, int iStart, int iStride) {
-	return cornerHost(ctx, true, kind, radius, kappa, derivX, derivY, dStart, dStride, width, height, intensity, iStart, iStride);
+	return cornerHost<float>(ctx, true, kind, radius, kappa, {derivX, dStart, dStride, width, height}, {derivY, dStart, dStride, width, height},
+							 {intensity, iStart, iStride, width, height});
 }
 int bhip_gaussian_kernel1d_s32(int radius, int32_t* out, int capacity) {
 	if (radius <= 0) return -1;
@@ -1991,16 +1887,8 @@ int bhip_gaussian_kernel1d_s32(int radius, int32_t* out, int capacity) {
 
 // ---- integer image variants, stage level ----
 int bhip_integral_u8_s32(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, int32_t* out, int outStart, int outStride) {
-	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, in, inStride, width, height, 1);
-	CHECK_IMG(ctx, out, outStride, width, height, 1);
-	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height));
-	BHIP_TRY(sc->out0.reserve(ctx, (size_t)width * height * 4));
-	BHIP_TRY(upload(ctx, sc->in0.as<uint8_t>(), width, in, inStart, inStride, width, height, ctx->stream));
-	BHIP_TRY(bhip_launch_integral_u8(ctx, sc->in0.as<unsigned char>(), 0, width, sc->out0.as<int>(), 0, width, width, height, 1));
-	BHIP_TRY(download(ctx, out, outStart, outStride, sc->out0.as<int32_t>(), width, width, height, ctx->stream));
-	return bhip_ctx_synchronize(ctx);
+	return hostInOut<uint8_t, int32_t>(ctx, {in, inStart, inStride, width, height}, {out, outStart, outStride, width, height}, false, false, nullptr,
+									   [&](auto din, auto dout) { return bhip_launch_integral_u8(ctx, din, dout); });
 }
 int bhip_hessian_s32(bhip_ctx* ctx, const int32_t* ii, int iiStart, int iiStride, int width, int height, int skip, int size, float* out, int outStart,
 					 int outStride) {
@@ -2009,13 +1897,14 @@ int bhip_hessian_s32(bhip_ctx* ctx, const int32_t* ii, int iiStart, int iiStride
 	if (skip < 1 || size < 3) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad skip / size");
 	const int w = width / skip, h = height / skip;
 	if (w <= 0 || h <= 0 || outStride < w) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad intensity image");
+	const HostImg<float> hout{out, outStart, outStride, w, h};
 	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * 4));
-	BHIP_TRY(sc->out0.reserve(ctx, (size_t)w * h * 4));
-	BHIP_TRY(upload(ctx, sc->in0.as<int32_t>(), width, ii, iiStart, iiStride, width, height, ctx->stream));
-	ImgView iv{sc->in0.as<float>(), (long long)width * height, width, width, height};   // 32-bit words either way
-	BHIP_TRY(bhip_launch_hessian(ctx, iv, 1, skip, 1, &size, sc->out0.as<float>(), (long long)w * h, (long long)w * h, w, nullptr, true));
-	BHIP_TRY(download(ctx, out, outStart, outStride, sc->out0.as<float>(), w, w, h, ctx->stream));
+	DevImg<float> din, dout;
+	BHIP_TRY(stageIn(ctx, sc->in0, HostImg<const float>{(const float*)ii, iiStart, iiStride, width, height}, width, din));   // 32-bit words either way
+	BHIP_TRY(stageIn(ctx, sc->out0, hout, w, dout, false));
+	ImgView iv{din.data, din.imageStride, width, width, height};
+	BHIP_TRY(bhip_launch_hessian(ctx, iv, 1, skip, 1, &size, dout.data, (long long)w * h, (long long)w * h, w, nullptr, true));
+	BHIP_TRY(stageOut(ctx, hout, dout));
 	return bhip_ctx_synchronize(ctx);
 }
 
@@ -2023,107 +1912,112 @@ int bhip_hessian_s32(bhip_ctx* ctx, const int32_t* ii, int iiStart, int iiStride
 // numPoints sample points; bhip_brief_u8 and bhip_brief_dev_f32 accept any non-negative index and use maxIdx + 1 points.
 int bhip_brief_u8(bhip_ctx* ctx, const uint8_t* img, int start, int stride, int width, int height, int radius, int numPoints, const int32_t* samplePoints,
 				  const int32_t* compare, const double* xy, int n, int32_t* out) {
+	const HostImg<const uint8_t> himg{img, start, stride, width, height};
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, img, stride, width, height, 1);
+	CHECK_IMG(ctx, himg);
 	if (numPoints <= 0 || !samplePoints || !compare || n < 0 || (n > 0 && (!xy || !out))) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad BRIEF arguments");
 	if (n == 0) return BHIP_OK;
 	int maxIdx = 0;
 	for (int i = 0; i < 2 * numPoints; i++) { if (compare[i] < 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "negative sample index"); maxIdx = std::max(maxIdx, compare[i]); }
-	return briefHost(ctx, img, start, stride, width, height, radius, numPoints, samplePoints, maxIdx + 1, compare, xy, n, out);
+	return briefHost(ctx, himg, radius, numPoints, samplePoints, maxIdx + 1, compare, xy, n, out);
 }
 
 int bhip_brief_f32(bhip_ctx* ctx, const float* img, int start, int stride, int width, int height, int radius, int numPoints,
 				   const int32_t* samplePoints, const int32_t* compare, const double* xy, int n, int32_t* out) {
+	const HostImg<const float> himg{img, start, stride, width, height};
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, img, stride, width, height, 1);
+	CHECK_IMG(ctx, himg);
 	if (numPoints <= 0 || !samplePoints || !compare || n < 0 || (n > 0 && (!xy || !out))) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad BRIEF arguments");
 	if (n == 0) return BHIP_OK;
 	for (int i = 0; i < 2 * numPoints; i++)
 		if (compare[i] < 0 || compare[i] >= numPoints) return bhip_fail(ctx, BHIP_ERR_INVALID, "pair index outside the sample point list");
-	return briefHost(ctx, img, start, stride, width, height, radius, numPoints, samplePoints, numPoints, compare, xy, n, out);
+	return briefHost(ctx, himg, radius, numPoints, samplePoints, numPoints, compare, xy, n, out);
 }
 
 // ---- device-batched forms ----
-static int convDev(bhip_ctx* ctx, bool vertical, bool normalized, const float* kernel, int kw, int koff, const float* dev_in, long long inImageStride,
-				   int inStride, int width, int height, int batch, float* dev_out, long long outImageStride, int outStride) {
-	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, dev_in, inStride, width, height, batch);
-	CHECK_IMG(ctx, dev_out, outStride, width, height, batch);
-	if (!kernel) return bhip_fail(ctx, BHIP_ERR_INVALID, "null kernel");
-	return convImpl(ctx, vertical, normalized, kernel, kw, koff, dev_in, inImageStride, inStride, width, height, batch, dev_out, outImageStride, outStride);
-}
 int bhip_conv_h_dev_f32(bhip_ctx* ctx, const float* kernel, int kw, int koff, const float* dev_in, long long inImageStride, int inStride, int width, int height,
 						int batch, float* dev_out, long long outImageStride, int outStride) {
-	return convDev(ctx, false, false, kernel, kw, koff, dev_in, inImageStride, inStride, width, height, batch, dev_out, outImageStride, outStride);
+	return convDev(ctx, false, false, kernel, kw, koff, {dev_in, inImageStride, inStride, width, height, batch}, {dev_out, outImageStride, outStride, width, height, batch});
 }
 int bhip_conv_v_dev_f32(bhip_ctx* ctx, const float* kernel, int kw, int koff, const float* dev_in, long long inImageStride, int inStride, int width, int height,
 						int batch, float* dev_out, long long outImageStride, int outStride) {
-	return convDev(ctx, true, false, kernel, kw, koff, dev_in, inImageStride, inStride, width, height, batch, dev_out, outImageStride, outStride);
+	return convDev(ctx, true, false, kernel, kw, koff, {dev_in, inImageStride, inStride, width, height, batch}, {dev_out, outImageStride, outStride, width, height, batch});
 }
 int bhip_conv_norm_h_dev_f32(bhip_ctx* ctx, const float* kernel, int kw, int koff, const float* dev_in, long long inImageStride, int inStride, int width,
 							 int height, int batch, float* dev_out, long long outImageStride, int outStride) {
-	return convDev(ctx, false, true, kernel, kw, koff, dev_in, inImageStride, inStride, width, height, batch, dev_out, outImageStride, outStride);
+	return convDev(ctx, false, true, kernel, kw, koff, {dev_in, inImageStride, inStride, width, height, batch}, {dev_out, outImageStride, outStride, width, height, batch});
 }
 int bhip_conv_norm_v_dev_f32(bhip_ctx* ctx, const float* kernel, int kw, int koff, const float* dev_in, long long inImageStride, int inStride, int width,
 							 int height, int batch, float* dev_out, long long outImageStride, int outStride) {
-	return convDev(ctx, true, true, kernel, kw, koff, dev_in, inImageStride, inStride, width, height, batch, dev_out, outImageStride, outStride);
+	return convDev(ctx, true, true, kernel, kw, koff, {dev_in, inImageStride, inStride, width, height, batch}, {dev_out, outImageStride, outStride, width, height, batch});
 }
 
 int bhip_gaussian_dev_f32(bhip_ctx* ctx, const float* dev_in, long long inImageStride, int inStride, int width, int height, int batch, double sigma, int radius,
 						  float* dev_out, long long outImageStride, int outStride) {
+	const DevImg<const float> in{dev_in, inImageStride, inStride, width, height, batch};
+	const DevImg<float> out{dev_out, outImageStride, outStride, width, height, batch};
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, dev_in, inStride, width, height, batch);
-	CHECK_IMG(ctx, dev_out, outStride, width, height, batch);
+	CHECK_IMG(ctx, in);
+	CHECK_IMG(ctx, out);
 	if (sigma <= 0 && radius <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Sigma must be > 0");
-	return gaussianImpl(ctx, sigma, radius, dev_in, inImageStride, inStride, width, height, batch, dev_out, outImageStride, outStride);
+	return gaussianImpl(ctx, sigma, radius, in, out);
 }
 
 int bhip_sobel_dev_f32(bhip_ctx* ctx, const float* dev_in, long long inImageStride, int inStride, int width, int height, int batch, float* dev_dx, float* dev_dy,
 					   long long outImageStride, int outStride, int border) {
-	return gradDev(ctx, 0, dev_in, inImageStride, inStride, width, height, batch, dev_dx, dev_dy, outImageStride, outStride, border);
+	return gradDev<float, float>(ctx, 0, {dev_in, inImageStride, inStride, width, height, batch}, {dev_dx, outImageStride, outStride, width, height, batch},
+								 {dev_dy, outImageStride, outStride, width, height, batch}, border);
 }
 int bhip_three_dev_f32(bhip_ctx* ctx, const float* dev_in, long long inImageStride, int inStride, int width, int height, int batch, float* dev_dx, float* dev_dy,
 					   long long outImageStride, int outStride, int border) {
-	return gradDev(ctx, 1, dev_in, inImageStride, inStride, width, height, batch, dev_dx, dev_dy, outImageStride, outStride, border);
+	return gradDev<float, float>(ctx, 1, {dev_in, inImageStride, inStride, width, height, batch}, {dev_dx, outImageStride, outStride, width, height, batch},
+								 {dev_dy, outImageStride, outStride, width, height, batch}, border);
 }
 int bhip_sobel_dev_u8_s16(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dev_dx,
 						  int16_t* dev_dy, long long outImageStride, int outStride, int border) {
-	return gradDev(ctx, 0, dev_in, inImageStride, inStride, width, height, batch, dev_dx, dev_dy, outImageStride, outStride, border);
+	return gradDev<uint8_t, int16_t>(ctx, 0, {dev_in, inImageStride, inStride, width, height, batch}, {dev_dx, outImageStride, outStride, width, height, batch},
+									 {dev_dy, outImageStride, outStride, width, height, batch}, border);
 }
 int bhip_three_dev_u8_s16(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dev_dx,
 						  int16_t* dev_dy, long long outImageStride, int outStride, int border) {
-	return gradDev(ctx, 1, dev_in, inImageStride, inStride, width, height, batch, dev_dx, dev_dy, outImageStride, outStride, border);
+	return gradDev<uint8_t, int16_t>(ctx, 1, {dev_in, inImageStride, inStride, width, height, batch}, {dev_dx, outImageStride, outStride, width, height, batch},
+									 {dev_dy, outImageStride, outStride, width, height, batch}, border);
 }
 
 int bhip_gradient_intensity_dev_f32(bhip_ctx* ctx, int kind, const float* dev_dx, const float* dev_dy, long long dImageStride, int dStride, int width, int height,
 									int batch, float* dev_out, long long outImageStride, int outStride) {
+	const DevImg<const float> dx{dev_dx, dImageStride, dStride, width, height, batch}, dy{dev_dy, dImageStride, dStride, width, height, batch};
+	const DevImg<float> out{dev_out, outImageStride, outStride, width, height, batch};
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, dev_dx, dStride, width, height, batch);
-	CHECK_IMG(ctx, dev_dy, dStride, width, height, batch);
-	CHECK_IMG(ctx, dev_out, outStride, width, height, batch);
-	return bhip_launch_grad_intensity(ctx, kind, dev_dx, dev_dy, dImageStride, dStride, dev_out, outImageStride, outStride, width, height, batch);
+	CHECK_IMG(ctx, dx);
+	CHECK_IMG(ctx, dy);
+	CHECK_IMG(ctx, out);
+	return bhip_launch_grad_intensity(ctx, kind, dx, dy, out);
 }
 
 int bhip_corner_intensity_dev_f32(bhip_ctx* ctx, int kind, int radius, float kappa, const float* dev_dx, const float* dev_dy, long long dImageStride, int dStride,
 								  int width, int height, int batch, float* dev_intensity, long long iImageStride, int iStride) {
-	return cornerDev(ctx, false, false, kind, radius, kappa, dev_dx, dev_dy, dImageStride, dStride, width, height, batch, dev_intensity, iImageStride, iStride);
+	return cornerDev<float>(ctx, false, kind, radius, kappa, {dev_dx, dImageStride, dStride, width, height, batch}, {dev_dy, dImageStride, dStride, width, height, batch},
+							{dev_intensity, iImageStride, iStride, width, height, batch});
 }
 int bhip_corner_intensity_dev_s16(bhip_ctx* ctx, int kind, int radius, float kappa, int weighted, const int16_t* dev_dx, const int16_t* dev_dy,
 								  long long dImageStride, int dStride, int width, int height, int batch, float* dev_intensity, long long iImageStride, int iStride) {
-	return cornerDev(ctx, true, weighted != 0, kind, radius, kappa, dev_dx, dev_dy, dImageStride, dStride, width, height, batch, dev_intensity, iImageStride,
-					 iStride);
+	return cornerDev<int16_t>(ctx, weighted != 0, kind, radius, kappa, {dev_dx, dImageStride, dStride, width, height, batch},
+							  {dev_dy, dImageStride, dStride, width, height, batch}, {dev_intensity, iImageStride, iStride, width, height, batch});
 }
 int bhip_corner_intensity_weighted_dev_f32(bhip_ctx* ctx, int kind, int radius, float kappa, const float* dev_dx, const float* dev_dy, long long dImageStride,
 										   int dStride, int width, int height, int batch, float* dev_intensity, long long iImageStride, int iStride) {
-	return cornerDev(ctx, false, true, kind, radius, kappa, dev_dx, dev_dy, dImageStride, dStride, width, height, batch, dev_intensity, iImageStride, iStride);
+	return cornerDev<float>(ctx, true, kind, radius, kappa, {dev_dx, dImageStride, dStride, width, height, batch}, {dev_dy, dImageStride, dStride, width, height, batch},
+							{dev_intensity, iImageStride, iStride, width, height, batch});
 }
 
 // DescribePointBrief.process over a batch: the points of image b are dev_xy[start[b] .. start[b+1]) (host prefix `start`, batch+1 entries);
 // words of point p at dev_out[p * ceil(numPoints/32)]
 int bhip_brief_dev_f32(bhip_ctx* ctx, const float* dev_img, long long imageStride, int stride, int width, int height, int batch, int radius, int numPoints,
 					   const int32_t* samplePoints, const int32_t* compare, const double* dev_xy, const int* start, int32_t* dev_out) {
+	const DevImg<const float> img{dev_img, imageStride, stride, width, height, batch};
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, dev_img, stride, width, height, batch);
+	CHECK_IMG(ctx, img);
 	if (numPoints <= 0 || !samplePoints || !compare || !start) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad BRIEF arguments");
 	int maxCount = 0;
 	for (int b = 0; b < batch; b++) {
@@ -2135,8 +2029,7 @@ int bhip_brief_dev_f32(bhip_ctx* ctx, const float* dev_img, long long imageStrid
 	if (!dev_xy || !dev_out) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad BRIEF arguments");
 	int maxIdx = 0;
 	for (int i = 0; i < 2 * numPoints; i++) { if (compare[i] < 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "negative sample index"); maxIdx = std::max(maxIdx, compare[i]); }
-	BHIP_TRY(briefImpl(ctx, false, dev_img, imageStride, stride, width, height, batch, radius, numPoints, samplePoints, maxIdx + 1, compare, dev_xy, start, n,
-					   maxCount, dev_out));
+	BHIP_TRY(briefImpl<float>(ctx, img, radius, numPoints, samplePoints, maxIdx + 1, compare, dev_xy, start, n, maxCount, dev_out));
 	return bhip_ctx_synchronize(ctx);   // the host tables were handed to async copies
 }
 
@@ -2188,6 +2081,16 @@ struct KltTable {
 };
 }  // namespace
 
+// the pixel types a tracker runs on: image / derivative (KltPyrT)
+template <class TI_, class TD_>
+struct KltTypes {
+	using TI = TI_;
+	using TD = TD_;
+	static constexpr bool u8 = std::is_same_v<TI_, uint8_t>;
+};
+using KltF32 = KltTypes<float, float>;      // bhip_klt_create: GrayF32 frames and derivatives
+using KltU8 = KltTypes<uint8_t, int16_t>;   // bhip_klt_create_u8: GrayU8 frames, GrayS16 derivatives
+
 // everything a tracker holds on its context's device; dropped as a whole like SurfDevice
 struct KltDevice {
 	KltTable tab;
@@ -2209,11 +2112,16 @@ struct bhip_klt : KltDevice {
 	bool u8 = false;             // GrayU8 frames with GrayS16 derivatives (bhip_klt_create_u8); pyr holds bytes, dx / dy shorts
 	bool haveFrame = false;
 	int ub = 0;                  // no sequence has more active tracks than this (exact after a spawn or bhip_klt_counts)
-	KltPyr view() const { return viewT<float, float>(); }
-	template <class TI, class TD>
-	KltPyrT<TI, TD> viewT() const {
-		KltPyrT<TI, TD> P{};
-		P.img = pyr.as<TI>(); P.dx = dx.as<TD>(); P.dy = dy.as<TD>();
+	// f(KltF32{}) or f(KltU8{}): the one place that turns `u8` into types
+	template <class F>
+	int withTypes(F f) const { return u8 ? f(KltU8{}) : f(KltF32{}); }
+	// layer l of every frame in the image (which 0), dx (1) or dy (2) pyramid
+	template <class T>
+	DevImg<T> layer(int which, int l) const { return bhip_pyr_layer((which == 0 ? pyr : which == 1 ? dx : dy).as<T>(), total, dims, offs, l, batch); }
+	template <class Px>
+	KltPyrT<typename Px::TI, typename Px::TD> view() const {
+		KltPyrT<typename Px::TI, typename Px::TD> P{};
+		P.img = pyr.as<typename Px::TI>(); P.dx = dx.as<typename Px::TD>(); P.dy = dy.as<typename Px::TD>();
 		P.frameStride = total;
 		for (int l = 0; l < L; l++) { P.off[l] = offs[l]; P.w[l] = dims[2 * l]; P.h[l] = dims[2 * l + 1]; P.stride[l] = dims[2 * l]; P.scale[l] = (float)(double)scales[l]; }
 		P.numLayers = L; P.frameW = W; P.frameH = H;
@@ -2270,8 +2178,7 @@ static int kltReadCounts(bhip_klt* k, const int** out) {
 
 // setDescription of the tracks `mode` selects (bhip_launch_klt_describe) on the tracker's own pixel types
 static int kltDescribe(bhip_klt* k, int mode, const int* count, int maxCount) {
-	if (k->u8) return bhip_launch_klt_describe(k->ctx, k->viewT<uint8_t, int16_t>(), k->tab.v, k->cfg, mode, count, maxCount);
-	return bhip_launch_klt_describe(k->ctx, k->view(), k->tab.v, k->cfg, mode, count, maxCount);
+	return k->withTypes([&](auto px) { return bhip_launch_klt_describe(k->ctx, k->view<decltype(px)>(), k->tab.v, k->cfg, mode, count, maxCount); });
 }
 
 // process() once the pyramid and its gradient are in place
@@ -2279,33 +2186,22 @@ static int kltTrackFrame(bhip_klt* k) {
 	bhip_ctx* ctx = k->ctx;
 	k->haveFrame = true;
 	BHIP_TRY(bhip_launch_klt_begin(ctx, k->tab.v));
-	if (k->u8) BHIP_TRY(bhip_launch_klt_track(ctx, k->viewT<uint8_t, int16_t>(), k->tab.v, k->cfg, k->ub));
-	else BHIP_TRY(bhip_launch_klt_track(ctx, k->view(), k->tab.v, k->cfg, k->ub));
+	BHIP_TRY(k->withTypes([&](auto px) { return bhip_launch_klt_track(ctx, k->view<decltype(px)>(), k->tab.v, k->cfg, k->ub); }));
 	BHIP_TRY(kltDescribe(k, 0, nullptr, k->ub));
 	return bhip_launch_klt_compact(ctx, k->tab.v, 0);
 }
 
-static int kltProcess(bhip_klt* k, const float* dev_frames, long long imageStride, int stride) {
+// process() on device frames: PyramidDiscreteSampleBlur (GrayF32: FactoryPyramid.discreteGaussian's kernel, GrayU8: [1,4,7,4,1] / 17), then
+// PyramidOps.gradient with FactoryDerivative.sobel -- BorderType.EXTENDED; GrayU8 -> GrayS16 -- then the tracking.
+// inLayer0: the frames are already in layer 0 of the pyramid, which `frames` views
+template <class Px>
+static int kltProcess(bhip_klt* k, DevImg<const typename Px::TI> frames, bool inLayer0) {
+	using TI = typename Px::TI;
+	using TD = typename Px::TD;
 	bhip_ctx* ctx = k->ctx;
-	BHIP_TRY(bhip_pyramid_dev_f32(ctx, k->kernel.data(), (int)k->kernel.size(), k->scales, k->L, dev_frames, imageStride, stride, k->W, k->H, k->batch,
-								  k->pyr.as<float>()));
-	for (int l = 0; l < k->L; l++)   // PyramidOps.gradient with FactoryDerivative.sobel: BorderType.EXTENDED
-		BHIP_TRY(bhip_launch_gradient(ctx, 0, k->pyr.as<float>() + k->offs[l], k->dims[2 * l], k->dims[2 * l], k->dims[2 * l + 1], k->dx.as<float>() + k->offs[l],
-									  k->dy.as<float>() + k->offs[l], k->dims[2 * l], 2, k->batch, k->total, k->total));
-	return kltTrackFrame(k);
-}
-
-// GrayU8 frames: PyramidDiscreteSampleBlur<GrayU8> ([1,4,7,4,1] / 17), GradientSobel(GrayU8, GrayS16, GrayS16) with BorderType.EXTENDED.
-// dev_frames == nullptr: the frames are already in layer 0 of the pyramid (host frames are uploaded straight into it when scale[0] == 1)
-static int kltProcessU8(bhip_klt* k, const uint8_t* dev_frames, long long imageStride, int stride) {
-	bhip_ctx* ctx = k->ctx;
-	uint8_t* pyr = k->pyr.as<uint8_t>();
-	const bool inPlace = dev_frames == nullptr;
-	BHIP_TRY(pyramidU8Impl(ctx, k->kernelS32.data(), (int)k->kernelS32.size(), k->scales, k->L, inPlace ? pyr : dev_frames, inPlace ? k->total : imageStride,
-						   inPlace ? k->W : stride, k->W, k->H, k->batch, pyr, inPlace));
-	for (int l = 0; l < k->L; l++)
-		BHIP_TRY(bhip_launch_gradient_u8(ctx, 0, pyr + k->offs[l], k->total, k->dims[2 * l], k->dims[2 * l], k->dims[2 * l + 1], k->batch,
-										 k->dx.as<int16_t>() + k->offs[l], k->dy.as<int16_t>() + k->offs[l], k->total, k->dims[2 * l], 2));
+	if constexpr (Px::u8) BHIP_TRY(pyramidImpl<TI>(ctx, k->kernelS32.data(), (int)k->kernelS32.size(), k->scales, k->L, frames, k->pyr.as<TI>(), inLayer0));
+	else BHIP_TRY(pyramidImpl<TI>(ctx, k->kernel.data(), (int)k->kernel.size(), k->scales, k->L, frames, k->pyr.as<TI>(), inLayer0));
+	for (int l = 0; l < k->L; l++) BHIP_TRY(bhip_launch_gradient(ctx, 0, k->layer<const TI>(0, l), k->layer<TD>(1, l), k->layer<TD>(2, l), 2));
 	return kltTrackFrame(k);
 }
 
@@ -2339,6 +2235,8 @@ static int kltSpawnFrom(bhip_klt* k, const int16_t* dev_xy, int xyCap, const int
 	if (!(k)) return BHIP_ERR_INVALID;  \
 	bhip_ctx* ctx = (k)->ctx;           \
 	CHECK_CTX(ctx)
+#define CHECK_KLT_TYPE(k, wantU8) \
+	if ((k)->u8 != (wantU8)) return bhip_fail(ctx, BHIP_ERR_INVALID, (k)->u8 ? "this tracker was created for GrayU8 frames" : "this tracker was created for GrayF32 frames")
 
 // a one-layer, one-sequence table for the stage-level calls: n tracks at xy, all active
 static int kltStageTable(bhip_ctx* ctx, KltTable& tab, int radius, const float* xy, int n) {
@@ -2360,6 +2258,65 @@ static KltPyrT<TI, TD> kltStagePyr(const TI* img, const TD* dx, const TD* dy, in
 	P.w[0] = width; P.h[0] = height; P.stride[0] = width; P.scale[0] = 1.0f;
 	P.numLayers = 1; P.frameW = width; P.frameH = height;
 	return P;
+}
+
+template <class Px>
+static int kltProcessDev(bhip_klt* k, const typename Px::TI* dev_frames, long long imageStride, int stride) {
+	CHECK_KLT(k);
+	CHECK_KLT_TYPE(k, Px::u8);
+	if (!dev_frames || stride < k->W) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image batch");
+	return kltProcess<Px>(k, {dev_frames, imageStride, stride, k->W, k->H, k->batch}, false);
+}
+
+template <class Px>
+static int kltProcessHost(bhip_klt* k, const typename Px::TI* const* img, const int* startIndex, const int* stride) {
+	using TI = typename Px::TI;
+	CHECK_KLT(k);
+	CHECK_KLT_TYPE(k, Px::u8);
+	if (!img) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image batch");
+	for (int b = 0; b < k->batch; b++)
+		if (!img[b] || (stride ? stride[b] : k->W) < k->W) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image (null or stride < width)");
+	// A GrayU8 tracker whose layer 0 is the frame itself (scale[0] == 1) takes the frames straight into the pyramid; every other tracker
+	// stages them in `frames`.
+	const bool uploadToLayer0 = Px::u8 && k->scales[0] == 1;
+	if (!uploadToLayer0) BHIP_TRY(k->frames.reserve(ctx, (size_t)k->W * k->H * sizeof(TI) * k->batch));
+	const DevImg<TI> dst = uploadToLayer0 ? k->layer<TI>(0, 0) : bhip_img_over<TI>(k->frames, k->W, k->W, k->H, k->batch);
+	for (int b = 0; b < k->batch; b++)
+		BHIP_TRY(upload<TI>(ctx, dst.data + b * dst.imageStride, k->W, img[b], startIndex ? startIndex[b] : 0, stride ? stride[b] : k->W, k->W, k->H, ctx->stream));
+	BHIP_TRY(kltProcess<Px>(k, dst, uploadToLayer0));
+	return bhip_ctx_synchronize(ctx);   // the caller's frames have been consumed
+}
+
+// bhip_klt_fetch_layer*: layer `layer` of sequence seq from the image (which 0), dx (1) or dy (2) pyramid, as T; which >= whichMin
+template <class T>
+static int kltFetchLayer(bhip_klt* k, int seq, int layer, int which, int whichMin, T* out) {
+	CHECK_KLT(k);
+	CHECK_KLT_TYPE(k, (!std::is_same_v<T, float>));
+	if (!k->haveFrame) return bhip_fail(ctx, BHIP_ERR_INVALID, "no frame processed");
+	if (seq < 0 || seq >= k->batch || layer < 0 || layer >= k->L || which < whichMin || which > 2 || !out) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad layer selector");
+	const DevImg<const T> v = k->layer<const T>(which, layer);
+	BHIP_HIP(ctx, hipMemcpyAsync(out, v.data + seq * v.imageStride, (size_t)v.width * v.height * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+	return bhip_ctx_synchronize(ctx);
+}
+
+template <class Px>
+static int kltDevView(bhip_klt* k, const int** dev_activeSlots, const int** dev_activeCount, const float** dev_x, const float** dev_y,
+					  const long long** dev_featureId, const typename Px::TI** dev_pyramid, const typename Px::TD** dev_derivX, const typename Px::TD** dev_derivY,
+					  int* slotsPerSequence, long long* elementsPerFrame) {
+	CHECK_KLT(k);
+	CHECK_KLT_TYPE(k, Px::u8);
+	const KltTab& T = k->tab.v;
+	if (dev_activeSlots) *dev_activeSlots = T.act;
+	if (dev_activeCount) *dev_activeCount = T.nAct;
+	if (dev_x) *dev_x = T.x;
+	if (dev_y) *dev_y = T.y;
+	if (dev_featureId) *dev_featureId = T.id;
+	if (dev_pyramid) *dev_pyramid = k->pyr.as<typename Px::TI>();
+	if (dev_derivX) *dev_derivX = k->dx.as<typename Px::TD>();
+	if (dev_derivY) *dev_derivY = k->dy.as<typename Px::TD>();
+	if (slotsPerSequence) *slotsPerSequence = T.cap;
+	if (elementsPerFrame) *elementsPerFrame = k->total;
+	return BHIP_OK;
 }
 
 static int kltCreate(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int templateRadius, const int* scales, int numLayers, int detectRadius, float detectThreshold,
@@ -2421,52 +2378,17 @@ int bhip_klt_destroy(bhip_klt* k) {
 	return BHIP_OK;
 }
 
-#define CHECK_KLT_TYPE(k, wantU8) \
-	if ((k)->u8 != (wantU8)) return bhip_fail(ctx, BHIP_ERR_INVALID, (k)->u8 ? "this tracker was created for GrayU8 frames" : "this tracker was created for GrayF32 frames")
-
 int bhip_klt_process_dev_f32(bhip_klt* k, const float* dev_frames, long long imageStride, int stride) {
-	CHECK_KLT(k);
-	CHECK_KLT_TYPE(k, false);
-	if (!dev_frames || stride < k->W) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image batch");
-	return kltProcess(k, dev_frames, imageStride, stride);
+	return kltProcessDev<KltF32>(k, dev_frames, imageStride, stride);
 }
-
 int bhip_klt_process_dev_u8(bhip_klt* k, const uint8_t* dev_frames, long long imageStride, int stride) {
-	CHECK_KLT(k);
-	CHECK_KLT_TYPE(k, true);
-	if (!dev_frames || stride < k->W) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image batch");
-	return kltProcessU8(k, dev_frames, imageStride, stride);
+	return kltProcessDev<KltU8>(k, dev_frames, imageStride, stride);
 }
-
 int bhip_klt_process_u8(bhip_klt* k, const uint8_t* const* img, const int* startIndex, const int* stride) {
-	CHECK_KLT(k);
-	CHECK_KLT_TYPE(k, true);
-	if (!img) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image batch");
-	for (int b = 0; b < k->batch; b++)
-		if (!img[b] || (stride ? stride[b] : k->W) < k->W) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image (null or stride < width)");
-	// scale[0] == 1: layer 0 is the frame itself, so it is uploaded to where the pyramid keeps it; otherwise to a staging block
-	const bool inPlace = k->scales[0] == 1;
-	const long long px = (long long)k->W * k->H, frameStride = inPlace ? k->total : px;
-	if (!inPlace) BHIP_TRY(k->frames.reserve(ctx, (size_t)px * k->batch));
-	uint8_t* dst = inPlace ? k->pyr.as<uint8_t>() : k->frames.as<uint8_t>();
-	for (int b = 0; b < k->batch; b++)
-		BHIP_TRY(upload(ctx, dst + b * frameStride, k->W, img[b], startIndex ? startIndex[b] : 0, stride ? stride[b] : k->W, k->W, k->H, ctx->stream));
-	BHIP_TRY(kltProcessU8(k, inPlace ? nullptr : dst, px, k->W));
-	return bhip_ctx_synchronize(ctx);   // the caller's frames have been consumed
+	return kltProcessHost<KltU8>(k, img, startIndex, stride);
 }
-
 int bhip_klt_process_f32(bhip_klt* k, const float* const* img, const int* startIndex, const int* stride) {
-	CHECK_KLT(k);
-	CHECK_KLT_TYPE(k, false);
-	if (!img) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image batch");
-	const long long px = (long long)k->W * k->H;
-	BHIP_TRY(k->frames.reserve(ctx, (size_t)px * 4 * k->batch));
-	for (int b = 0; b < k->batch; b++) {
-		if (!img[b] || (stride ? stride[b] : k->W) < k->W) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image (null or stride < width)");
-		BHIP_TRY(upload(ctx, k->frames.as<float>() + b * px, k->W, img[b], startIndex ? startIndex[b] : 0, stride ? stride[b] : k->W, k->W, k->H, ctx->stream));
-	}
-	BHIP_TRY(kltProcess(k, k->frames.as<float>(), px, k->W));
-	return bhip_ctx_synchronize(ctx);   // the caller's frames have been consumed
+	return kltProcessHost<KltF32>(k, img, startIndex, stride);
 }
 
 int bhip_klt_spawn(bhip_klt* k, int maxFeatures) {
@@ -2478,8 +2400,10 @@ int bhip_klt_spawn(bhip_klt* k, int maxFeatures) {
 	BHIP_TRY(k->intensity.reserve(ctx, (size_t)px * 4 * k->batch));
 	float* inten = k->intensity.as<float>();
 	// FactoryIntensityPointAlg.shiTomasi(1, false, derivType): ImplSsdCorner_F32, or ImplSsdCorner_S16 on the GrayS16 derivatives of a GrayU8 tracker
-	if (k->u8) BHIP_TRY(cornerImpl(ctx, true, false, 0, 1, 0.0f, k->dx.as<int16_t>() + k->offs[0], k->dy.as<int16_t>() + k->offs[0], k->total, w0, w0, h0, k->batch, inten, px, w0));
-	else BHIP_TRY(cornerImpl(ctx, false, false, 0, 1, 0.0f, k->dx.as<float>() + k->offs[0], k->dy.as<float>() + k->offs[0], k->total, w0, w0, h0, k->batch, inten, px, w0));
+	BHIP_TRY(k->withTypes([&](auto t) {
+		using TD = typename decltype(t)::TD;
+		return cornerImpl<TD>(ctx, false, 0, 1, 0.0f, k->layer<const TD>(1, 0), k->layer<const TD>(2, 0), bhip_img_over<float>(k->intensity, w0, w0, h0, k->batch));
+	}));
 	BHIP_TRY(bhip_launch_klt_mark_exclude(ctx, k->tab.v, (float)(double)k->scales[0], inten, px, w0, w0, h0, k->ub));
 	const int step = k->detectRadius + 1;
 	const int rw = std::max(w0 - 2 * k->detectBorder, 0), rh = std::max(h0 - 2 * k->detectBorder, 0);
@@ -2633,72 +2557,19 @@ int bhip_klt_stats(bhip_klt* k, long long* tracks, long long* iterations, long l
 	return BHIP_OK;
 }
 
-int bhip_klt_fetch_layer(bhip_klt* k, int seq, int layer, int which, float* out) {
-	CHECK_KLT(k);
-	CHECK_KLT_TYPE(k, false);
-	if (!k->haveFrame) return bhip_fail(ctx, BHIP_ERR_INVALID, "no frame processed");
-	if (seq < 0 || seq >= k->batch || layer < 0 || layer >= k->L || which < 0 || which > 2 || !out) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad layer selector");
-	const float* src = (which == 0 ? k->pyr : which == 1 ? k->dx : k->dy).as<float>() + (long long)seq * k->total + k->offs[layer];
-	BHIP_HIP(ctx, hipMemcpyAsync(out, src, (size_t)k->dims[2 * layer] * k->dims[2 * layer + 1] * 4, hipMemcpyDeviceToHost, ctx->stream));
-	return bhip_ctx_synchronize(ctx);
-}
-
-int bhip_klt_fetch_layer_u8(bhip_klt* k, int seq, int layer, uint8_t* out) {
-	CHECK_KLT(k);
-	CHECK_KLT_TYPE(k, true);
-	if (!k->haveFrame) return bhip_fail(ctx, BHIP_ERR_INVALID, "no frame processed");
-	if (seq < 0 || seq >= k->batch || layer < 0 || layer >= k->L || !out) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad layer selector");
-	const uint8_t* src = k->pyr.as<uint8_t>() + (long long)seq * k->total + k->offs[layer];
-	BHIP_HIP(ctx, hipMemcpyAsync(out, src, (size_t)k->dims[2 * layer] * k->dims[2 * layer + 1], hipMemcpyDeviceToHost, ctx->stream));
-	return bhip_ctx_synchronize(ctx);
-}
-
-int bhip_klt_fetch_layer_s16(bhip_klt* k, int seq, int layer, int which, int16_t* out) {
-	CHECK_KLT(k);
-	CHECK_KLT_TYPE(k, true);
-	if (!k->haveFrame) return bhip_fail(ctx, BHIP_ERR_INVALID, "no frame processed");
-	if (seq < 0 || seq >= k->batch || layer < 0 || layer >= k->L || which < 1 || which > 2 || !out) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad layer selector");
-	const int16_t* src = (which == 1 ? k->dx : k->dy).as<int16_t>() + (long long)seq * k->total + k->offs[layer];
-	BHIP_HIP(ctx, hipMemcpyAsync(out, src, (size_t)k->dims[2 * layer] * k->dims[2 * layer + 1] * 2, hipMemcpyDeviceToHost, ctx->stream));
-	return bhip_ctx_synchronize(ctx);
-}
+int bhip_klt_fetch_layer(bhip_klt* k, int seq, int layer, int which, float* out) { return kltFetchLayer(k, seq, layer, which, 0, out); }
+int bhip_klt_fetch_layer_u8(bhip_klt* k, int seq, int layer, uint8_t* out) { return kltFetchLayer(k, seq, layer, 0, 0, out); }
+int bhip_klt_fetch_layer_s16(bhip_klt* k, int seq, int layer, int which, int16_t* out) { return kltFetchLayer(k, seq, layer, which, 1, out); }
 
 int bhip_klt_dev_view_u8(bhip_klt* k, const int** dev_activeSlots, const int** dev_activeCount, const float** dev_x, const float** dev_y,
 						 const long long** dev_featureId, const uint8_t** dev_pyramid, const int16_t** dev_derivX, const int16_t** dev_derivY, int* slotsPerSequence,
 						 long long* elementsPerFrame) {
-	CHECK_KLT(k);
-	CHECK_KLT_TYPE(k, true);
-	const KltTab& T = k->tab.v;
-	if (dev_activeSlots) *dev_activeSlots = T.act;
-	if (dev_activeCount) *dev_activeCount = T.nAct;
-	if (dev_x) *dev_x = T.x;
-	if (dev_y) *dev_y = T.y;
-	if (dev_featureId) *dev_featureId = T.id;
-	if (dev_pyramid) *dev_pyramid = k->pyr.as<uint8_t>();
-	if (dev_derivX) *dev_derivX = k->dx.as<int16_t>();
-	if (dev_derivY) *dev_derivY = k->dy.as<int16_t>();
-	if (slotsPerSequence) *slotsPerSequence = T.cap;
-	if (elementsPerFrame) *elementsPerFrame = k->total;
-	return BHIP_OK;
+	return kltDevView<KltU8>(k, dev_activeSlots, dev_activeCount, dev_x, dev_y, dev_featureId, dev_pyramid, dev_derivX, dev_derivY, slotsPerSequence, elementsPerFrame);
 }
-
 int bhip_klt_dev_view(bhip_klt* k, const int** dev_activeSlots, const int** dev_activeCount, const float** dev_x, const float** dev_y,
 					  const long long** dev_featureId, const float** dev_pyramid, const float** dev_derivX, const float** dev_derivY, int* slotsPerSequence,
 					  long long* floatsPerFrame) {
-	CHECK_KLT(k);
-	CHECK_KLT_TYPE(k, false);
-	const KltTab& T = k->tab.v;
-	if (dev_activeSlots) *dev_activeSlots = T.act;
-	if (dev_activeCount) *dev_activeCount = T.nAct;
-	if (dev_x) *dev_x = T.x;
-	if (dev_y) *dev_y = T.y;
-	if (dev_featureId) *dev_featureId = T.id;
-	if (dev_pyramid) *dev_pyramid = k->pyr.as<float>();
-	if (dev_derivX) *dev_derivX = k->dx.as<float>();
-	if (dev_derivY) *dev_derivY = k->dy.as<float>();
-	if (slotsPerSequence) *slotsPerSequence = T.cap;
-	if (floatsPerFrame) *floatsPerFrame = k->total;
-	return BHIP_OK;
+	return kltDevView<KltF32>(k, dev_activeSlots, dev_activeCount, dev_x, dev_y, dev_featureId, dev_pyramid, dev_derivX, dev_derivY, slotsPerSequence, floatsPerFrame);
 }
 
 }  // extern "C"
@@ -2708,25 +2579,25 @@ static int kltSetDescriptionStage(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int ra
 								  const TD* derivY, int dStart, int dStride, int width, int height, const float* xy, int n, float* desc, float* descX,
 								  float* descY, float* G, uint8_t* ok) {
 	if (!kltRangeOk(radius, 1)) return BHIP_ERR_UNSUPPORTED;   // templateRadius 1..7; nothing is written
+	const HostImg<const TI> himg{image, imgStart, imgStride, width, height};
+	const HostImg<const TD> hdx{derivX, dStart, dStride, width, height}, hdy{derivY, dStart, dStride, width, height};
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, image, imgStride, width, height, 1);
-	CHECK_IMG(ctx, derivX, dStride, width, height, 1);
-	CHECK_IMG(ctx, derivY, dStride, width, height, 1);
+	CHECK_IMG(ctx, himg);
+	CHECK_IMG(ctx, hdx);
+	CHECK_IMG(ctx, hdy);
 	if (n < 0 || (n > 0 && (!xy || !desc || !descX || !descY || !G || !ok))) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad feature list");
 	if (n == 0) return BHIP_OK;
 	bhip_klt_cfg c;
 	if (cfg) c = *cfg; else bhip_klt_cfg_default(&c);
 	CtxScratch* sc = scratchOf(ctx);
-	const size_t px = (size_t)width * height;
-	BHIP_TRY(sc->in0.reserve(ctx, px * sizeof(TI)));
-	BHIP_TRY(sc->in1.reserve(ctx, px * sizeof(TD)));
-	BHIP_TRY(sc->tmp0.reserve(ctx, px * sizeof(TD)));
-	BHIP_TRY(upload(ctx, sc->in0.as<TI>(), width, image, imgStart, imgStride, width, height, ctx->stream));
-	BHIP_TRY(upload(ctx, sc->in1.as<TD>(), width, derivX, dStart, dStride, width, height, ctx->stream));
-	BHIP_TRY(upload(ctx, sc->tmp0.as<TD>(), width, derivY, dStart, dStride, width, height, ctx->stream));
+	DevImg<TI> dimg;
+	DevImg<TD> ddx, ddy;
+	BHIP_TRY(stageIn(ctx, sc->in0, himg, width, dimg));
+	BHIP_TRY(stageIn(ctx, sc->in1, hdx, width, ddx));
+	BHIP_TRY(stageIn(ctx, sc->tmp0, hdy, width, ddy));
 	KltTable tab;
 	BHIP_TRY(kltStageTable(ctx, tab, radius, xy, n));
-	BHIP_TRY(bhip_launch_klt_describe(ctx, kltStagePyr<TI, TD>(sc->in0.as<TI>(), sc->in1.as<TD>(), sc->tmp0.as<TD>(), width, height), tab.v, c, 2, nullptr, n));
+	BHIP_TRY(bhip_launch_klt_describe(ctx, kltStagePyr<TI, TD>(dimg.data, ddx.data, ddy.data, width, height), tab.v, c, 2, nullptr, n));
 	const int len = tab.v.len;
 	std::vector<float> t((size_t)n * 3 * len), g((size_t)3 * n);
 	std::vector<int> keep(n), fault(n);
@@ -2755,12 +2626,13 @@ static int kltTrackStage(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, con
 	bhip_klt_cfg c;
 	if (cfg) c = *cfg; else bhip_klt_cfg_default(&c);
 	if (c.maxIterations < 1) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "maxIterations must be >= 1");
-	CHECK_IMG(ctx, image, imgStride, width, height, 1);
+	const HostImg<const TI> himg{image, imgStart, imgStride, width, height};
+	CHECK_IMG(ctx, himg);
 	if (n < 0 || (n > 0 && (!xy || !desc || !descX || !descY || !G || !fault || !error))) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad feature list");
 	if (n == 0) return BHIP_OK;
 	CtxScratch* sc = scratchOf(ctx);
-	BHIP_TRY(sc->in0.reserve(ctx, (size_t)width * height * sizeof(TI)));
-	BHIP_TRY(upload(ctx, sc->in0.as<TI>(), width, image, imgStart, imgStride, width, height, ctx->stream));
+	DevImg<TI> dimg;
+	BHIP_TRY(stageIn(ctx, sc->in0, himg, width, dimg));
 	KltTable tab;
 	BHIP_TRY(kltStageTable(ctx, tab, radius, xy, n));
 	const int len = tab.v.len;
@@ -2775,7 +2647,7 @@ static int kltTrackStage(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, con
 	BHIP_HIP(ctx, hipMemcpyAsync(tab.v.gxx, g.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
 	BHIP_HIP(ctx, hipMemcpyAsync(tab.v.gyy, g.data() + n, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
 	BHIP_HIP(ctx, hipMemcpyAsync(tab.v.gxy, g.data() + 2 * n, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-	BHIP_TRY(bhip_launch_klt_track(ctx, kltStagePyr<TI, TD>(sc->in0.as<TI>(), nullptr, nullptr, width, height), tab.v, c, n));
+	BHIP_TRY(bhip_launch_klt_track(ctx, kltStagePyr<TI, TD>(dimg.data, nullptr, nullptr, width, height), tab.v, c, n));
 	BHIP_HIP(ctx, hipMemcpyAsync(pos.data(), tab.v.lx, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
 	BHIP_HIP(ctx, hipMemcpyAsync(pos.data() + n, tab.v.ly, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
 	BHIP_HIP(ctx, hipMemcpyAsync(fault, tab.v.fault, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));

@@ -150,6 +150,27 @@ struct ImgViewW {
 	int width, height;
 };
 
+// ---------------- typed view of a device image batch, passed between host functions ----------------
+// `batch` images of width x height elements, imageStride elements apart, rows `stride` elements apart (all strides in elements of T).
+// DevImg<const T> is the input form.  Host side only: the launchers unpack a view into their kernel's ImgView / *Params arguments.
+template <class T>
+struct DevImg {
+	T* data;
+	long long imageStride;
+	int stride, width, height, batch;
+	operator DevImg<const T>() const { return {data, imageStride, stride, width, height, batch}; }
+};
+// `batch` images with rows `pitch` elements apart, packed from the start of `buf`
+template <class T>
+static inline DevImg<T> bhip_img_over(const DevBuf& buf, int pitch, int width, int height, int batch) {
+	return {buf.as<T>(), (long long)pitch * height, pitch, width, height, batch};
+}
+// layer l of a pyramid batch laid out by bhip_pyramid_layout (dims, offs; `total` elements per frame): dense rows
+template <class T>
+static inline DevImg<T> bhip_pyr_layer(T* base, long long total, const int* dims, const long long* offs, int l, int batch) {
+	return {base + offs[l], total, dims[2 * l], dims[2 * l], dims[2 * l + 1], batch};
+}
+
 // ---------------- detector structures ----------------
 #define BHIP_MAX_OCTAVES 8
 #define BHIP_MAX_LEVELS 8
@@ -211,9 +232,6 @@ int bhip_launch_hessian(bhip_ctx* ctx, ImgView ii, int batch, int skip, int nlev
 						long long imageStrideOut, int outStride, const HessLevelSource* from = nullptr, bool intTaps = false,
 						unsigned int skipMask = 0);   // skipMask: levels this launch does not produce
 
-int bhip_launch_copy_images(bhip_ctx* ctx, const float* in, long long inImageStride, int inStride, float* out, long long outImageStride, int outStride,
-							int width, int height, int batch);
-
 // describe-kernel options beyond the grey float default (see DescParams): colour SURF bands (nBands > 0), the orientation's object
 // radius factor, integer taps (GrayS32 integral images)
 struct DescPlanar {
@@ -252,46 +270,68 @@ int bhip_launch_assoc_l2(bhip_ctx* ctx, const double* src, int ns, const double*
 int bhip_launch_assoc_hamming(bhip_ctx* ctx, const int32_t* src, int ns, const int32_t* dst, int nd, int words, double maxErr, int backwards,
 							  int* pairs, double* fit, DevBuf& work);
 
-// ---------------- boofcv-ip front end (ip.hip); device images, `batch` of them imageStride floats apart ----------------
-int bhip_launch_conv(bhip_ctx* ctx, bool vertical, bool normalized, const float* kernel, int kw, int koff, const float* in, int inStride, int width,
-					 int height, float* out, int outStride, int batch = 1, long long inImageStride = 0, long long outImageStride = 0);
-int bhip_launch_blur_fused(bhip_ctx* ctx, const float* kernel, int kw, const float* in, int inStride, int width, int height, float* out, int outStride, int batch,
-						   long long inImageStride, long long outImageStride, bool* done);
-int bhip_launch_pyr_layer_fused(bhip_ctx* ctx, const float* kernel, int kw, const float* in, long long inImageStride, int inStride, int width, int height,
-								float* out, long long outImageStride, int outStride, int skip, int batch, bool* done);
-int bhip_launch_conv_down(bhip_ctx* ctx, bool vertical, const float* kernel, int kw, const float* in, long long inImageStride, int inStride, int width,
-						  int height, float* out, long long outImageStride, int outStride, int outWidth, int outHeight, int skip, int batch);
+// describe.hip, detect.hip, associate.hip, assoc_mfma.hip, detect_fused.hip: what only the C ABI layer calls
+int bhip_launch_describe_ex(bhip_ctx* ctx, ImgView ii, const KeyPoint* kps, int cap, const int* imageStart, int batch, int singleImage, long long total,
+							SurfTables t, const double* anglesIn, double* angles, double* desc, uint8_t* white, const int* perm = nullptr, const DescPlanar* planar = nullptr);
+int bhip_launch_kp_spatial_order(bhip_ctx* ctx, const KeyPoint* kps, int cap, const int* start, int batch, int maxCount, int W, int H, int* hist, int* perm);
+int bhip_assoc_phase1_l2(bhip_ctx* ctx, const double* src, int nsLocal, int srcBegin, const double* dst, int nd, int dof, double maxErr, int sqrtScore,
+						 int* pairs, double* fit, void* colTop, DevBuf& work);
+int bhip_assoc_phase1_ham(bhip_ctx* ctx, const int32_t* src, int nsLocal, int srcBegin, const int32_t* dst, int nd, int words, double maxErr, int* pairs,
+						  double* fit, void* colTop, DevBuf& work);
+int bhip_assoc_phase2(bhip_ctx* ctx, const void* colAll, int nranks, int nd, int nsLocal, int srcBegin, int* pairs, double* fit);
+int bhip_assoc_coltop_size();
+int bhip_assoc_hamming_batched(bhip_ctx* ctx, const int32_t* src, const int32_t* dst, int words, int count, const long long* srcOff, const int* ns,
+							   const long long* dstOff, const int* nd, double maxErr, int backwards, int* pairs, double* fit, DevBuf& work);
+
+int bhip_assoc_l2_mfma_batched(bhip_ctx* ctx, AssocMfmaWork& W, const double* dev_src, const double* dev_dst, int count, const long long* srcOff,
+								 const int* ns, const long long* dstOff, const int* nd, double maxErr, int backwards, int* dev_pairs, double* dev_fit,
+								 int* usedMfma);
+
+bool bhip_fused_plan(int skip, int nlevels, const int* sizes, int radius, int* TX, int* TY, int* ldsBytes);
+bool bhip_fused_is_fixed(int skip, int nlevels, const int* sizes, int radius);
+int bhip_launch_detect_fused(bhip_ctx* ctx, ImgView ii, int batch, int skip, int nlevels, const int* sizes, int nmid, const DetectLevelParams* mids,
+							 const int* midLevels, int radius, float threshold, unsigned int* bitmap, int bitmapWords, KeyPoint* cand, int* candCount,
+							 int cap, const FusedExport* exp, bool intTaps = false);
+
+// ---------------- boofcv-ip front end (ip.hip) ----------------
+// Images arrive as DevImg views.  Where the images of a call share one shape, width, height and batch are read from the first view; dx / dy
+// pairs share one layout.
+int bhip_launch_conv(bhip_ctx* ctx, bool vertical, bool normalized, const float* kernel, int kw, int koff, DevImg<const float> in, DevImg<float> out);
+int bhip_launch_blur_fused(bhip_ctx* ctx, const float* kernel, int kw, DevImg<const float> in, DevImg<float> out, bool* done);
+int bhip_launch_pyr_layer_fused(bhip_ctx* ctx, const float* kernel, int kw, DevImg<const float> in, DevImg<float> out, int skip, bool* done);
+// ConvolveImageDownNormalized.horizontal / vertical: Kernel1D_F32 on GrayF32, or Kernel1D_S32 on GrayU8 -> GrayI8 (the integer pyramid's layer step)
+int bhip_launch_conv_down(bhip_ctx* ctx, bool vertical, const float* kernel, int kw, DevImg<const float> in, DevImg<float> out, int skip);
+int bhip_launch_conv_down(bhip_ctx* ctx, bool vertical, const int32_t* kernel, int kw, DevImg<const uint8_t> in, DevImg<uint8_t> out, int skip);
+int bhip_launch_copy_images(bhip_ctx* ctx, DevImg<const float> in, DevImg<float> out);
+int bhip_launch_copy_images(bhip_ctx* ctx, DevImg<const uint8_t> in, DevImg<uint8_t> out);
 int bhip_launch_planar_average(bhip_ctx* ctx, const float* bands, long long bandStride, int numBands, long long n, float* out);
-int bhip_launch_corner_intensity(bhip_ctx* ctx, int kind, int radius, float kappa, const float* dx, const float* dy, int dStride, int width, int height,
-								 float* hXX, float* hXY, float* hYY, float* intensity, int iStride, int batch = 1, long long dImageStride = 0,
-								 long long hImageStride = 0, long long iImageStride = 0);
-int bhip_launch_conv2d(bhip_ctx* ctx, const float* kernel, int kw, int koff, const float* in, int inStride, int width, int height, float* out, int outStride);
-int bhip_launch_mean(bhip_ctx* ctx, bool vertical, const float* in, float* out, int width, int height, int radius);
-int bhip_launch_median(bhip_ctx* ctx, const float* in, int inStride, float* out, int outStride, int width, int height, int radius);
-int bhip_launch_gradient(bhip_ctx* ctx, int kind, const float* in, int inStride, int width, int height, float* dx, float* dy, int outStride, int border,
-						 int batch = 1, long long inImageStride = 0, long long outImageStride = 0);
-// integer gradient + corner path (ip.hip): GrayU8 -> GrayS16 gradients (kind 0 Sobel, 1 three-tap), fused S16 box corner intensity,
-// fused Gaussian-weighted corner intensity on F32 or S16 derivatives.  Element strides throughout.
-int bhip_launch_gradient_u8(bhip_ctx* ctx, int kind, const uint8_t* in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dx,
-							int16_t* dy, long long outImageStride, int outStride, int border);
-// ConvolveImageDownNormalized.horizontal / vertical (Kernel1D_S32, GrayU8, GrayI8, skip): the integer pyramid's layer step; element strides
-int bhip_launch_conv_down_u8(bhip_ctx* ctx, bool vertical, const int32_t* kernel, int kw, const uint8_t* in, long long inImageStride, int inStride, int width,
-							 int height, uint8_t* out, long long outImageStride, int outStride, int outWidth, int outHeight, int skip, int batch);
-int bhip_launch_copy_images_u8(bhip_ctx* ctx, const uint8_t* in, long long inImageStride, int inStride, uint8_t* out, long long outImageStride, int outStride,
-							   int width, int height, int batch);
-size_t bhip_corner_box_s16_scratch(int radius, int width, int height, int batch);   // bytes of `scratch` bhip_launch_corner_box_s16 needs (0: none)
-int bhip_launch_corner_box_s16(bhip_ctx* ctx, int kind, int radius, float kappa, const int16_t* dx, const int16_t* dy, long long dImageStride, int dStride,
-							   int width, int height, int batch, float* intensity, long long iImageStride, int iStride, void* scratch);
+// GradientSobel / GradientThree (kind 0 / 1): GrayF32 -> GrayF32, GrayU8 -> GrayS16
+int bhip_launch_gradient(bhip_ctx* ctx, int kind, DevImg<const float> in, DevImg<float> dx, DevImg<float> dy, int border);
+int bhip_launch_gradient(bhip_ctx* ctx, int kind, DevImg<const uint8_t> in, DevImg<int16_t> dx, DevImg<int16_t> dy, int border);
+int bhip_launch_grad_intensity(bhip_ctx* ctx, int kind, DevImg<const float> dx, DevImg<const float> dy, DevImg<float> out);
+// box-window corner intensity.  F32: `scratch` holds three dense width x height float planes per image.  S16: fused, or through `scratch`
+// (bhip_corner_box_s16_scratch bytes, 0: none) when the radius is beyond the fused block.
+int bhip_launch_corner_intensity(bhip_ctx* ctx, int kind, int radius, float kappa, DevImg<const float> dx, DevImg<const float> dy, DevImg<float> intensity,
+								 float* scratch);
+size_t bhip_corner_box_s16_scratch(int radius, int width, int height, int batch);
+int bhip_launch_corner_box_s16(bhip_ctx* ctx, int kind, int radius, float kappa, DevImg<const int16_t> dx, DevImg<const int16_t> dy, DevImg<float> intensity,
+							   void* scratch);
+// fused Gaussian-weighted corner intensity on F32 (ImplSsdCornerWeighted_F32) or S16 (ImplSsdCornerWeighted_S16) derivatives
 int bhip_corner_weighted_max_radius();
-int bhip_launch_corner_weighted(bhip_ctx* ctx, bool s16, int kind, int radius, float kappa, const void* dx, const void* dy, long long dImageStride, int dStride,
-								int width, int height, int batch, float* intensity, long long iImageStride, int iStride);
-int bhip_launch_grad_intensity(bhip_ctx* ctx, int kind, const float* dx, const float* dy, long long dImageStride, int dStride, float* out,
-							   long long oImageStride, int oStride, int width, int height, int batch);
-int bhip_launch_brief(bhip_ctx* ctx, const float* img, int stride, int width, int height, int radius, int numPoints, const int* samplePoints,
-					  const int* compare, const double* xy, int n, int* out, bool u8 = false, int batch = 1, long long imageStride = 0,
-					  const int* start = nullptr, int maxCount = 0, int xyStride = 2, long long xyImageStride = 0, bool patchOk = false);
+int bhip_launch_corner_weighted(bhip_ctx* ctx, int kind, int radius, float kappa, DevImg<const float> dx, DevImg<const float> dy, DevImg<float> intensity);
+int bhip_launch_corner_weighted(bhip_ctx* ctx, int kind, int radius, float kappa, DevImg<const int16_t> dx, DevImg<const int16_t> dy, DevImg<float> intensity);
+// start == nullptr: n points on image 0.  Otherwise img.batch images and the device prefix `start` (batch + 1); maxCount = largest per-image count.
 // patchOk: every sample point of the definition lies within [-radius, radius]^2 (checked on the host where the table is at hand), so the
 // LDS-patch kernel may be used; otherwise the gather kernel runs
+int bhip_launch_brief(bhip_ctx* ctx, DevImg<const float> img, int radius, int numPoints, const int* samplePoints, const int* compare, const double* xy, int n,
+					  int* out, const int* start, int maxCount, int xyStride, long long xyImageStride, bool patchOk);
+int bhip_launch_brief(bhip_ctx* ctx, DevImg<const uint8_t> img, int radius, int numPoints, const int* samplePoints, const int* compare, const double* xy, int n,
+					  int* out, const int* start, int maxCount, int xyStride, long long xyImageStride, bool patchOk);
+// single images (batch 1)
+int bhip_launch_conv2d(bhip_ctx* ctx, const float* kernel, int kw, int koff, DevImg<const float> in, DevImg<float> out);
+int bhip_launch_mean(bhip_ctx* ctx, bool vertical, DevImg<const float> in, DevImg<float> out, int radius);   // one direction of the mean blur
+int bhip_launch_median(bhip_ctx* ctx, DevImg<const float> in, DevImg<float> out, int radius);
+int bhip_launch_integral_u8(bhip_ctx* ctx, DevImg<const uint8_t> in, DevImg<int32_t> out);   // IntegralImageOps.transform(GrayU8, GrayS32)
 // stand-alone strict block NMS over a batch (detect.hip): bitmap of accepted blocks + the pixel's position inside its block
 int bhip_launch_nonmax_blocks(bhip_ctx* ctx, const float* img, long long imageStride, int stride, int w, int h, int batch, int radius, float threshold, int border,
 							  unsigned int* bitmap, int bitmapWords, unsigned short* posInBlock, int nbx, int nby);

@@ -651,13 +651,17 @@ static void setNormalizedMode(ConvParams& P, int extent) {
 	}
 }
 
-int bhip_launch_conv(bhip_ctx* ctx, bool vertical, bool normalized, const float* kernel, int kw, int koff, const float* in, int inStride, int width,
-					 int height, float* out, int outStride, int batch, long long inImageStride, long long outImageStride) {
+// both sides of a launch allow 16-byte vector accesses: base, row stride and image stride
+template <class T>
+static bool vec4(DevImg<T> v) { return aligned16(v.data) && v.stride % 4 == 0 && v.imageStride % 4 == 0; }
+
+int bhip_launch_conv(bhip_ctx* ctx, bool vertical, bool normalized, const float* kernel, int kw, int koff, DevImg<const float> in, DevImg<float> out) {
+	const int width = in.width, height = in.height, batch = in.batch;
 	if (kw <= 0 || kw > BHIP_MAX_TAPS || koff < 0 || koff >= kw) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "kernel width not supported");
 	if (width <= 0 || height <= 0 || batch <= 0) return BHIP_OK;
 	ConvParams P;
-	P.in = in; P.out = out; P.inStride = inStride; P.outStride = outStride; P.width = width; P.height = height; P.kw = kw; P.koff = koff;
-	P.inImageStride = inImageStride; P.outImageStride = outImageStride;
+	P.in = in.data; P.out = out.data; P.inStride = in.stride; P.outStride = out.stride; P.width = width; P.height = height; P.kw = kw; P.koff = koff;
+	P.inImageStride = in.imageStride; P.outImageStride = out.imageStride;
 	for (int i = 0; i < kw; i++) P.k[i] = kernel[i];
 	P.unrolled = (koff == kw / 2 && kw % 2 == 1 && (kw == 3 || kw == 5 || kw == 7 || kw == 9 || kw == 11)) ? 1 : 0;
 	P.mode = 0;
@@ -665,8 +669,7 @@ int bhip_launch_conv(bhip_ctx* ctx, bool vertical, bool normalized, const float*
 	if (normalized) setNormalizedMode(P, vertical ? height : width);
 	ProfScope prof(ctx, vertical ? "k_conv_v" : "k_conv_h", 8.0 * width * height * batch);
 	// tiled forms need 16-byte aligned rows on both sides; the naive form (kernel wider than the image) stays on the general kernel
-	const bool tiled = P.mode != 2 && aligned16(in) && aligned16(out) && inStride % 4 == 0 && outStride % 4 == 0 && inImageStride % 4 == 0 &&
-					   outImageStride % 4 == 0 && kw <= 97;
+	const bool tiled = P.mode != 2 && vec4(in) && vec4(out) && kw <= 97;
 	if (!tiled) {
 		dim3 grid((width + 255) / 256, height, batch);
 		if (vertical) hipLaunchKernelGGL(k_conv<true>, grid, dim3(256), 0, ctx->stream, P);
@@ -715,17 +718,17 @@ int bhip_launch_conv(bhip_ctx* ctx, bool vertical, bool normalized, const float*
 
 // BlurImageOps.gaussian in one pass; returns *done = false when the shape / kernel is outside what the fused kernel covers (the caller
 // then runs the two separable passes)
-int bhip_launch_blur_fused(bhip_ctx* ctx, const float* kernel, int kw, const float* in, int inStride, int width, int height, float* out, int outStride, int batch,
-						   long long inImageStride, long long outImageStride, bool* done) {
+int bhip_launch_blur_fused(bhip_ctx* ctx, const float* kernel, int kw, DevImg<const float> in, DevImg<float> out, bool* done) {
+	const int width = in.width, height = in.height, batch = in.batch;
 	*done = false;
 	if (width <= 0 || height <= 0 || batch <= 0) { *done = true; return BHIP_OK; }
 	const bool unrolled = kw == 3 || kw == 5 || kw == 7 || kw == 9 || kw == 11;
 	if (!unrolled || kw >= width || kw >= height) return BHIP_OK;   // standard-form widths and the naive form (kernel wider than the image)
-	if (!(aligned16(in) && aligned16(out) && inStride % 4 == 0 && outStride % 4 == 0 && inImageStride % 4 == 0 && outImageStride % 4 == 0)) return BHIP_OK;
+	if (!(vec4(in) && vec4(out))) return BHIP_OK;
 	if (bhip_env_flag("BHIP_BLUR_TWO_PASS")) return BHIP_OK;        // parity cross-check of the two forms
 	ConvParams P;
-	P.in = in; P.out = out; P.inStride = inStride; P.outStride = outStride; P.width = width; P.height = height; P.kw = kw; P.koff = kw / 2;
-	P.inImageStride = inImageStride; P.outImageStride = outImageStride;
+	P.in = in.data; P.out = out.data; P.inStride = in.stride; P.outStride = out.stride; P.width = width; P.height = height; P.kw = kw; P.koff = kw / 2;
+	P.inImageStride = in.imageStride; P.outImageStride = out.imageStride;
 	for (int i = 0; i < kw; i++) P.k[i] = kernel[i];
 	P.unrolled = 1; P.mode = 1; P.borderOnly = 0;
 	{
@@ -962,24 +965,31 @@ static int downMaxSide(int sideLength, int skip, int radius) {
 }
 static int downOffset(int skip, int radius) { return radius <= skip ? skip : radius + radius % skip; }
 
-int bhip_launch_conv_down(bhip_ctx* ctx, bool vertical, const float* kernel, int kw, const float* in, long long inImageStride, int inStride, int width,
-						  int height, float* out, long long outImageStride, int outStride, int outWidth, int outHeight, int skip, int batch) {
+// What the two down-sampling launchers share: ConvolveImageDownNoBorder.checkParameters*, the view and the taps unpacked into the kernel's
+// params struct (ConvDownParams / ConvDownU8Params), the position classes along the filtered axis, and the test that every loop of the
+// reference stays inside the image.
+template <class Params, class K, class T>
+static int convDownSetup(bhip_ctx* ctx, bool vertical, const K* kernel, int kw, DevImg<const T> in, DevImg<T> out, int skip, Params& P) {
+	const int width = in.width, height = in.height;
 	if (kw <= 0 || kw > BHIP_MAX_TAPS) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "kernel width not supported");
 	// ConvolveImageDownNoBorder.checkParameters* (I:alg/filter/convolve/ConvolveImageDownNoBorder.java:160-186)
 	if (skip <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Skip must be >= 1");
-	if (outWidth < width / skip) return bhip_fail(ctx, BHIP_ERR_INVALID, "Output width is too small");
-	if (outHeight < height / skip) return bhip_fail(ctx, BHIP_ERR_INVALID, "Output height is too small");
+	if (out.width < width / skip) return bhip_fail(ctx, BHIP_ERR_INVALID, "Output width is too small");
+	if (out.height < height / skip) return bhip_fail(ctx, BHIP_ERR_INVALID, "Output height is too small");
 	// checkParametersH/V on the no-border path; on the naive path GrayF32.set would throw ImageAccessException for the same shapes
-	if (vertical && outWidth < width) return bhip_fail(ctx, BHIP_ERR_INVALID, "Output width is too small");
-	if (!vertical && outHeight < height) return bhip_fail(ctx, BHIP_ERR_INVALID, "Output height is too small");
-	ConvDownParams P;
-	P.in = in; P.out = out; P.inImageStride = inImageStride; P.outImageStride = outImageStride; P.inStride = inStride; P.outStride = outStride;
+	if (vertical && out.width < width) return bhip_fail(ctx, BHIP_ERR_INVALID, "Output width is too small");
+	if (!vertical && out.height < height) return bhip_fail(ctx, BHIP_ERR_INVALID, "Output height is too small");
+	P.in = in.data; P.out = out.data; P.inImageStride = in.imageStride; P.outImageStride = out.imageStride; P.inStride = in.stride; P.outStride = out.stride;
 	P.width = width; P.height = height; P.skip = skip; P.kw = kw; P.radius = kw / 2;
 	for (int i = 0; i < kw; i++) P.k[i] = kernel[i];
+	if constexpr (std::is_integral_v<K>) {   // the integer form divides by the kernel's sum
+		long long sum = 0;
+		for (int i = 0; i < kw; i++) sum += kernel[i];
+		if (sum == 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "/ by zero (the kernel sums to 0)");
+	}
 	const int r = P.radius;
 	const int side = vertical ? height : width;
 	P.naive = kw >= width ? 1 : 0;   // sic: the vertical form tests the image WIDTH as well
-	P.unrolled = (kw % 2 == 1 && (kw == 3 || kw == 5 || kw == 7 || kw == 9 || kw == 11)) ? 1 : 0;
 	P.offset = downOffset(skip, r);
 	P.offsetRem = P.offset % skip;
 	P.maxSide = downMaxSide(side, skip, r);
@@ -996,6 +1006,14 @@ int bhip_launch_conv_down(bhip_ctx* ctx, bool vertical, const float* kernel, int
 		if (P.offsetEnd < P.sideTrunc) ok = ok && P.offsetEnd - r >= 0;
 		if (!ok) return bhip_fail(ctx, BHIP_ERR_INVALID, "kernel does not fit the image along the filtered axis");
 	}
+	return BHIP_OK;
+}
+
+int bhip_launch_conv_down(bhip_ctx* ctx, bool vertical, const float* kernel, int kw, DevImg<const float> in, DevImg<float> out, int skip) {
+	const int width = in.width, height = in.height, batch = in.batch;
+	ConvDownParams P;
+	BHIP_TRY(convDownSetup(ctx, vertical, kernel, kw, in, out, skip, P));
+	P.unrolled = (kw % 2 == 1 && (kw == 3 || kw == 5 || kw == 7 || kw == 9 || kw == 11)) ? 1 : 0;
 	const int gw = vertical ? width : width / skip;
 	const int gh = vertical ? height / skip : height;
 	if (gw <= 0 || gh <= 0 || batch <= 0) return BHIP_OK;
@@ -1003,8 +1021,7 @@ int bhip_launch_conv_down(bhip_ctx* ctx, bool vertical, const float* kernel, int
 	dim3 grid((gw + 255) / 256, gh, batch);
 	P.skipInterior = 0;
 	// skip 2, unrolled widths 3 / 5, 16-byte aligned rows: the interior goes through the streaming kernels, the general kernel adds the borders
-	const bool stream = !P.naive && skip == 2 && P.unrolled && (kw == 3 || kw == 5) && P.offsetRem == 0 && aligned16(in) && aligned16(out) &&
-						inStride % 4 == 0 && inImageStride % 4 == 0 && outStride % 4 == 0 && outImageStride % 4 == 0;
+	const bool stream = !P.naive && skip == 2 && P.unrolled && (kw == 3 || kw == 5) && P.offsetRem == 0 && vec4(in) && vec4(out);
 	if (stream) {
 		if (vertical) {
 			dim3 g((width + 255) / 256, (gh + 4 * CD_ROWS_V - 1) / (4 * CD_ROWS_V), batch);
@@ -1146,18 +1163,17 @@ __global__ __launch_bounds__(256) void k_copy_images(const float* __restrict__ i
 	}
 }
 // *done = false: the shape / kernel is outside what the fused layer kernel covers (the caller runs the two passes through `temp`)
-int bhip_launch_pyr_layer_fused(bhip_ctx* ctx, const float* kernel, int kw, const float* in, long long inImageStride, int inStride, int width, int height,
-								float* out, long long outImageStride, int outStride, int skip, int batch, bool* done) {
+int bhip_launch_pyr_layer_fused(bhip_ctx* ctx, const float* kernel, int kw, DevImg<const float> in, DevImg<float> out, int skip, bool* done) {
+	const int width = in.width, height = in.height, batch = in.batch;
 	*done = false;
 	if (skip != 2 || !(kw == 3 || kw == 5) || batch <= 0) return BHIP_OK;
 	const int r = kw / 2;
 	if (kw >= width / 2 || kw >= height) return BHIP_OK;        // naive forms (the reference's vertical pass tests the width of `temp`, width / 2)
 	if (width / 2 <= 0 || height / 2 <= 0) return BHIP_OK;
-	if (!(aligned16(in) && inStride % 4 == 0 && inImageStride % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0 && outStride % 2 == 0 && outImageStride % 2 == 0))
-		return BHIP_OK;
+	if (!(vec4(in) && (reinterpret_cast<uintptr_t>(out.data) & 7) == 0 && out.stride % 2 == 0 && out.imageStride % 2 == 0)) return BHIP_OK;
 	if (bhip_env_flag("BHIP_PYRAMID_TWO_PASS")) return BHIP_OK;  // parity cross-check of the two forms
 	PyrLayerParams P;
-	P.in = in; P.out = out; P.inImageStride = inImageStride; P.outImageStride = outImageStride; P.inStride = inStride; P.outStride = outStride;
+	P.in = in.data; P.out = out.data; P.inImageStride = in.imageStride; P.outImageStride = out.imageStride; P.inStride = in.stride; P.outStride = out.stride;
 	P.width = width; P.height = height;
 	for (int i = 0; i < kw; i++) P.k[i] = kernel[i];
 	for (int axis = 0; axis < 2; axis++) {
@@ -1185,12 +1201,12 @@ int bhip_launch_pyr_layer_fused(bhip_ctx* ctx, const float* kernel, int kw, cons
 	return BHIP_OK;
 }
 
-int bhip_launch_copy_images(bhip_ctx* ctx, const float* in, long long inImageStride, int inStride, float* out, long long outImageStride, int outStride,
-							int width, int height, int batch) {
-	if (width <= 0 || height <= 0 || batch <= 0) return BHIP_OK;
-	const int vec = aligned16(in) && aligned16(out) && inStride % 4 == 0 && outStride % 4 == 0 && inImageStride % 4 == 0 && outImageStride % 4 == 0;
-	dim3 grid((width + 1023) / 1024, std::min(height, 256), batch);
-	hipLaunchKernelGGL(k_copy_images, grid, dim3(256), 0, ctx->stream, in, inImageStride, inStride, out, outImageStride, outStride, width, height, vec);
+int bhip_launch_copy_images(bhip_ctx* ctx, DevImg<const float> in, DevImg<float> out) {
+	if (in.width <= 0 || in.height <= 0 || in.batch <= 0) return BHIP_OK;
+	const int vec = vec4(in) && vec4(out);
+	dim3 grid((in.width + 1023) / 1024, std::min(in.height, 256), in.batch);
+	hipLaunchKernelGGL(k_copy_images, grid, dim3(256), 0, ctx->stream, in.data, in.imageStride, in.stride, out.data, out.imageStride, out.stride, in.width,
+					   in.height, vec);
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
 }
@@ -1353,13 +1369,17 @@ __global__ __launch_bounds__(256) void k_grad_stream(GradParams P) {
 	}
 }
 
-int bhip_launch_gradient(bhip_ctx* ctx, int kind, const float* in, int inStride, int width, int height, float* dx, float* dy, int outStride, int border,
-						 int batch, long long inImageStride, long long outImageStride) {
+// dx and dy of one gradient (or one corner intensity) are addressed with one row stride and one image stride
+template <class T>
+static bool sameLayout(DevImg<T> a, DevImg<T> b) { return a.stride == b.stride && a.imageStride == b.imageStride; }
+
+int bhip_launch_gradient(bhip_ctx* ctx, int kind, DevImg<const float> in, DevImg<float> dx, DevImg<float> dy, int border) {
+	const int width = in.width, height = in.height, batch = in.batch;
 	if (width <= 0 || height <= 0 || batch <= 0) return BHIP_OK;
-	GradParams P{in, dx, dy, inImageStride, outImageStride, inStride, outStride, width, height, border};
+	if (!sameLayout(dx, dy)) return bhip_fail(ctx, BHIP_ERR_INVALID, "dx and dy must share one layout");
+	GradParams P{in.data, dx.data, dy.data, in.imageStride, dx.imageStride, in.stride, dx.stride, width, height, border};
 	ProfScope prof(ctx, kind == 0 ? "k_sobel" : "k_three", 12.0 * width * height * batch);
-	const bool stream = aligned16(in) && aligned16(dx) && aligned16(dy) && inStride % 4 == 0 && outStride % 4 == 0 && inImageStride % 4 == 0 &&
-						outImageStride % 4 == 0;
+	const bool stream = vec4(in) && vec4(dx) && aligned16(dy.data);
 	if (stream) {
 		dim3 grid((width + 255) / 256, (height + 4 * GR_ROWS - 1) / (4 * GR_ROWS), batch);
 		if (kind == 0) hipLaunchKernelGGL(k_grad_stream<0>, grid, dim3(256), 0, ctx->stream, P);
@@ -1388,13 +1408,14 @@ __global__ __launch_bounds__(256) void k_grad_intensity(const float* __restrict_
 	else r = a * a + b * b;
 	out[(long long)blockIdx.z * oImageStride + (long long)y * oStride + x] = r;
 }
-int bhip_launch_grad_intensity(bhip_ctx* ctx, int kind, const float* dx, const float* dy, long long dImageStride, int dStride, float* out,
-							   long long oImageStride, int oStride, int width, int height, int batch) {
+int bhip_launch_grad_intensity(bhip_ctx* ctx, int kind, DevImg<const float> dx, DevImg<const float> dy, DevImg<float> out) {
+	const int width = dx.width, height = dx.height, batch = dx.batch;
 	if (kind < 0 || kind > 2) return bhip_fail(ctx, BHIP_ERR_INVALID, "unknown gradient intensity");
 	if (width <= 0 || height <= 0 || batch <= 0) return BHIP_OK;
+	if (!sameLayout(dx, dy)) return bhip_fail(ctx, BHIP_ERR_INVALID, "dx and dy must share one layout");
 	ProfScope prof(ctx, "k_grad_intensity", 12.0 * width * height * batch);
-	hipLaunchKernelGGL(k_grad_intensity, dim3((width + 255) / 256, height, batch), dim3(256), 0, ctx->stream, dx, dy, dImageStride, dStride, out, oImageStride,
-					   oStride, width, height, kind);
+	hipLaunchKernelGGL(k_grad_intensity, dim3((width + 255) / 256, height, batch), dim3(256), 0, ctx->stream, dx.data, dy.data, dx.imageStride, dx.stride, out.data,
+					   out.imageStride, out.stride, width, height, kind);
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
 }
@@ -1539,11 +1560,15 @@ __global__ __launch_bounds__(256) void k_brief_patch(BriefParams P) {
 }
 
 // start == nullptr: n points on one image.  Otherwise `batch` images and device prefix `start` (batch+1); maxCount = largest per-image count.
-int bhip_launch_brief(bhip_ctx* ctx, const float* img, int stride, int width, int height, int radius, int numPoints, const int* samplePoints,
-					  const int* compare, const double* xy, int n, int* out, bool u8, int batch, long long imageStride, const int* start, int maxCount,
-					  int xyStride, long long xyImageStride, bool patchOk) {
+// T: float or unsigned char pixels (BriefParams carries the base as const float* either way; the kernel instantiation reads it as T)
+template <class T>
+static int launchBrief(bhip_ctx* ctx, DevImg<const T> img, int radius, int numPoints, const int* samplePoints, const int* compare, const double* xy, int n,
+					   int* out, const int* start, int maxCount, int xyStride, long long xyImageStride, bool patchOk) {
 	if (n <= 0) return BHIP_OK;
-	BriefParams P{img, imageStride, stride, width, height, radius, numPoints, (numPoints + 31) / 32, n, samplePoints, compare, xy, out, start, xyStride, xyImageStride};
+	constexpr bool u8 = std::is_same_v<T, uint8_t>;
+	const int batch = img.batch;
+	BriefParams P{reinterpret_cast<const float*>(img.data), img.imageStride, img.stride, img.width, img.height, radius, numPoints, (numPoints + 31) / 32, n,
+				  samplePoints, compare, xy, out, start, xyStride, xyImageStride};
 	const long long total = (long long)(start ? maxCount : n) * P.words;
 	if (total <= 0) return BHIP_OK;
 	dim3 grid((unsigned)((total + 255) / 256), start ? batch : 1);
@@ -1559,6 +1584,14 @@ int bhip_launch_brief(bhip_ctx* ctx, const float* img, int stride, int width, in
 	else hipLaunchKernelGGL(k_brief<float>, grid, dim3(256), 0, ctx->stream, P);
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
+}
+int bhip_launch_brief(bhip_ctx* ctx, DevImg<const float> img, int radius, int numPoints, const int* samplePoints, const int* compare, const double* xy, int n,
+					  int* out, const int* start, int maxCount, int xyStride, long long xyImageStride, bool patchOk) {
+	return launchBrief(ctx, img, radius, numPoints, samplePoints, compare, xy, n, out, start, maxCount, xyStride, xyImageStride, patchOk);
+}
+int bhip_launch_brief(bhip_ctx* ctx, DevImg<const uint8_t> img, int radius, int numPoints, const int* samplePoints, const int* compare, const double* xy, int n,
+					  int* out, const int* start, int maxCount, int xyStride, long long xyImageStride, bool patchOk) {
+	return launchBrief(ctx, img, radius, numPoints, samplePoints, compare, xy, n, out, start, maxCount, xyStride, xyImageStride, patchOk);
 }
 
 
@@ -1698,15 +1731,18 @@ __global__ __launch_bounds__(256) void k_corner_cols(CornerParams P) {
 	}
 }
 
-// intensity must be zero along its border of `radius` pixels: the caller clears the whole image first.  hXX/hXY/hYY: dense width x height
-// planes per image, hImageStride floats apart.
-int bhip_launch_corner_intensity(bhip_ctx* ctx, int kind, int radius, float kappa, const float* dx, const float* dy, int dStride, int width, int height,
-								 float* hXX, float* hXY, float* hYY, float* intensity, int iStride, int batch, long long dImageStride, long long hImageStride,
-								 long long iImageStride) {
+// intensity must be zero along its border of `radius` pixels: the caller clears the whole image first.  scratch: the row sums XX, XY, YY
+// as three dense width x height planes per image.
+int bhip_launch_corner_intensity(bhip_ctx* ctx, int kind, int radius, float kappa, DevImg<const float> dx, DevImg<const float> dy, DevImg<float> intensity,
+								 float* scratch) {
+	const int width = dx.width, height = dx.height, batch = dx.batch;
 	if (kind != 0 && kind != 1) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "corner score not supported");
 	if (radius < 0 || 2 * radius + 1 > width || 2 * radius + 1 > height) return bhip_fail(ctx, BHIP_ERR_INVALID, "window larger than the image");
 	if (batch <= 0) return BHIP_OK;
-	CornerParams P{dx, dy, dImageStride, hImageStride, iImageStride, dStride, width, height, radius, hXX, hXY, hYY, intensity, iStride, kind, kappa};
+	if (!sameLayout(dx, dy)) return bhip_fail(ctx, BHIP_ERR_INVALID, "dx and dy must share one layout");
+	const long long px = (long long)width * height;
+	CornerParams P{dx.data, dy.data, dx.imageStride, px * 3, intensity.imageStride, dx.stride, width, height, radius, scratch, scratch + px, scratch + 2 * px,
+				   intensity.data, intensity.stride, kind, kappa};
 	{
 		ProfScope prof(ctx, "k_corner_rows", 4.0 * width * height * 5 * batch);
 		hipLaunchKernelGGL(k_corner_rows, dim3((height + 63) / 64, batch), dim3(64), 0, ctx->stream, P);
@@ -1749,10 +1785,11 @@ __global__ __launch_bounds__(256) void k_conv2d(Conv2DParams P) {
 	}
 	P.out[(long long)y * P.outStride + x] = total;
 }
-int bhip_launch_conv2d(bhip_ctx* ctx, const float* kernel, int kw, int koff, const float* in, int inStride, int width, int height, float* out, int outStride) {
+int bhip_launch_conv2d(bhip_ctx* ctx, const float* kernel, int kw, int koff, DevImg<const float> in, DevImg<float> out) {
+	const int width = in.width, height = in.height;
 	if (kw <= 0 || kw * kw > BHIP_MAX_TAPS2D || koff < 0 || koff >= kw) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "kernel width not supported");
 	Conv2DParams P;
-	P.in = in; P.out = out; P.inStride = inStride; P.outStride = outStride; P.width = width; P.height = height; P.kw = kw; P.koff = koff;
+	P.in = in.data; P.out = out.data; P.inStride = in.stride; P.outStride = out.stride; P.width = width; P.height = height; P.kw = kw; P.koff = koff;
 	P.unrolled = (koff == kw / 2 && kw % 2 == 1 && (kw == 3 || kw == 5 || kw == 7 || kw == 9 || kw == 11)) ? 1 : 0;
 	for (int i = 0; i < kw * kw; i++) P.k[i] = kernel[i];
 	ProfScope prof(ctx, "k_conv2d", 8.0 * width * height);
@@ -1817,19 +1854,20 @@ __global__ __launch_bounds__(256) void k_mean_cols(const float* __restrict__ in,
 		out[(long long)y * outStride + x] = total / divisor;
 	}
 }
-// one direction of the mean blur: dense in / out of the same shape
-int bhip_launch_mean(bhip_ctx* ctx, bool vertical, const float* in, float* out, int width, int height, int radius) {
+// one direction of the mean blur: in / out of the same shape
+int bhip_launch_mean(bhip_ctx* ctx, bool vertical, DevImg<const float> in, DevImg<float> out, int radius) {
+	const int width = in.width, height = in.height;
 	const int kw = 2 * radius + 1;
 	if (kw > BHIP_MAX_TAPS) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "mean radius not supported");
 	float ker[BHIP_MAX_TAPS];
 	const float val = 1.0f / (float)kw;   // FactoryKernel.table1D_F32(radius, true)
 	for (int i = 0; i < kw; i++) ker[i] = val;
 	const int extent = vertical ? height : width;
-	if (kw > extent) return bhip_launch_conv(ctx, vertical, true, ker, kw, radius, in, width, width, height, out, width);   // ConvolveImageNormalized
+	if (kw > extent) return bhip_launch_conv(ctx, vertical, true, ker, kw, radius, in, out);   // ConvolveImageNormalized
 	// border first (k_conv mode 3), then the interior chains
 	{
 		ConvParams P;
-		P.in = in; P.out = out; P.inStride = width; P.outStride = width; P.width = width; P.height = height; P.kw = kw; P.koff = radius;
+		P.in = in.data; P.out = out.data; P.inStride = in.stride; P.outStride = out.stride; P.width = width; P.height = height; P.kw = kw; P.koff = radius;
 		P.inImageStride = 0; P.outImageStride = 0; P.borderOnly = 0;
 		for (int i = 0; i < kw; i++) P.k[i] = ker[i];
 		P.unrolled = 0; P.mode = 3;
@@ -1838,8 +1876,8 @@ int bhip_launch_mean(bhip_ctx* ctx, bool vertical, const float* in, float* out, 
 		else hipLaunchKernelGGL(k_conv<false>, grid, dim3(256), 0, ctx->stream, P);
 	}
 	ProfScope prof(ctx, vertical ? "k_mean_cols" : "k_mean_rows", 8.0 * width * height);
-	if (vertical) hipLaunchKernelGGL(k_mean_cols, dim3((width + 255) / 256), dim3(256), 0, ctx->stream, in, width, out, width, width, height, radius);
-	else hipLaunchKernelGGL(k_mean_rows, dim3((height + 63) / 64), dim3(64), 0, ctx->stream, in, width, out, width, width, height, radius);
+	if (vertical) hipLaunchKernelGGL(k_mean_cols, dim3((width + 255) / 256), dim3(256), 0, ctx->stream, in.data, in.stride, out.data, out.stride, width, height, radius);
+	else hipLaunchKernelGGL(k_mean_rows, dim3((height + 63) / 64), dim3(64), 0, ctx->stream, in.data, in.stride, out.data, out.stride, width, height, radius);
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
 }
@@ -1879,12 +1917,13 @@ __global__ __launch_bounds__(MED_T * MED_T) void k_median(const float* __restric
 		}
 	out[(long long)y * outStride + x] = result;
 }
-int bhip_launch_median(bhip_ctx* ctx, const float* in, int inStride, float* out, int outStride, int width, int height, int radius) {
+int bhip_launch_median(bhip_ctx* ctx, DevImg<const float> in, DevImg<float> out, int radius) {
+	const int width = in.width, height = in.height;
 	if (radius > 8) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "median radius > 8 is not supported on the GPU");
 	const int TW = MED_T + 2 * radius;
 	ProfScope prof(ctx, "k_median", 8.0 * width * height);
-	hipLaunchKernelGGL(k_median, dim3((width + MED_T - 1) / MED_T, (height + MED_T - 1) / MED_T), dim3(MED_T, MED_T), (size_t)TW * TW * 4, ctx->stream, in, inStride, out,
-					   outStride, width, height, radius);
+	hipLaunchKernelGGL(k_median, dim3((width + MED_T - 1) / MED_T, (height + MED_T - 1) / MED_T), dim3(MED_T, MED_T), (size_t)TW * TW * 4, ctx->stream, in.data, in.stride,
+					   out.data, out.stride, width, height, radius);
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
 }
@@ -1931,17 +1970,17 @@ __global__ __launch_bounds__(256) void k_integral_cols_s32(int* __restrict__ io,
 		p[(long long)y * stride + x] = total;
 	}
 }
-int bhip_launch_integral_u8(bhip_ctx* ctx, const unsigned char* in, long long inImageStride, int inStride, int* out, long long outImageStride, int outStride,
-							int width, int height, int batch) {
+int bhip_launch_integral_u8(bhip_ctx* ctx, DevImg<const uint8_t> in, DevImg<int32_t> out) {
+	const int width = in.width, height = in.height, batch = in.batch;
 	if (width <= 0 || height <= 0 || batch <= 0) return BHIP_OK;
 	{
 		ProfScope prof(ctx, "k_integral_rows_u8", 5.0 * width * height * batch);
-		hipLaunchKernelGGL(k_integral_rows_u8, dim3((height + 3) / 4, batch), dim3(256), 0, ctx->stream, in, inImageStride, inStride, out, outImageStride, outStride,
-						   width, height);
+		hipLaunchKernelGGL(k_integral_rows_u8, dim3((height + 3) / 4, batch), dim3(256), 0, ctx->stream, in.data, in.imageStride, in.stride, out.data, out.imageStride,
+						   out.stride, width, height);
 	}
 	{
 		ProfScope prof(ctx, "k_integral_cols_s32", 8.0 * width * height * batch);
-		hipLaunchKernelGGL(k_integral_cols_s32, dim3((width + 255) / 256, batch), dim3(256), 0, ctx->stream, out, outImageStride, outStride, width, height);
+		hipLaunchKernelGGL(k_integral_cols_s32, dim3((width + 255) / 256, batch), dim3(256), 0, ctx->stream, out.data, out.imageStride, out.stride, width, height);
 	}
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
@@ -2046,10 +2085,11 @@ __global__ __launch_bounds__(256) void k_grad_u8(GradU8Params P) {
 	}
 }
 
-int bhip_launch_gradient_u8(bhip_ctx* ctx, int kind, const uint8_t* in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dx,
-							int16_t* dy, long long outImageStride, int outStride, int border) {
+int bhip_launch_gradient(bhip_ctx* ctx, int kind, DevImg<const uint8_t> in, DevImg<int16_t> dx, DevImg<int16_t> dy, int border) {
+	const int width = in.width, height = in.height, batch = in.batch;
 	if (width <= 0 || height <= 0 || batch <= 0) return BHIP_OK;
-	GradU8Params P{in, dx, dy, inImageStride, outImageStride, inStride, outStride, width, height, border};
+	if (!sameLayout(dx, dy)) return bhip_fail(ctx, BHIP_ERR_INVALID, "dx and dy must share one layout");
+	GradU8Params P{in.data, dx.data, dy.data, in.imageStride, dx.imageStride, in.stride, dx.stride, width, height, border};
 	ProfScope prof(ctx, kind == 0 ? "k_sobel_u8" : "k_three_u8", 5.0 * width * height * batch);
 	dim3 grid((width + 255) / 256, (height + 4 * GR_ROWS - 1) / (4 * GR_ROWS), batch);
 	if (kind == 0) hipLaunchKernelGGL(k_grad_u8<0>, grid, dim3(256), 0, ctx->stream, P);
@@ -2207,47 +2247,19 @@ __global__ __launch_bounds__(256) void k_copy_images_u8(const uint8_t* __restric
 			for (int q = 0; q < 16 && x + q < width; q++) d[q] = s[q];
 	}
 }
-int bhip_launch_copy_images_u8(bhip_ctx* ctx, const uint8_t* in, long long inImageStride, int inStride, uint8_t* out, long long outImageStride, int outStride,
-							   int width, int height, int batch) {
-	if (width <= 0 || height <= 0 || batch <= 0) return BHIP_OK;
-	dim3 grid((width + 4095) / 4096, std::min(height, 512), batch);
-	hipLaunchKernelGGL(k_copy_images_u8, grid, dim3(256), 0, ctx->stream, in, inImageStride, inStride, out, outImageStride, outStride, width, height);
+int bhip_launch_copy_images(bhip_ctx* ctx, DevImg<const uint8_t> in, DevImg<uint8_t> out) {
+	if (in.width <= 0 || in.height <= 0 || in.batch <= 0) return BHIP_OK;
+	dim3 grid((in.width + 4095) / 4096, std::min(in.height, 512), in.batch);
+	hipLaunchKernelGGL(k_copy_images_u8, grid, dim3(256), 0, ctx->stream, in.data, in.imageStride, in.stride, out.data, out.imageStride, out.stride, in.width,
+					   in.height);
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
 }
 
-int bhip_launch_conv_down_u8(bhip_ctx* ctx, bool vertical, const int32_t* kernel, int kw, const uint8_t* in, long long inImageStride, int inStride, int width,
-							 int height, uint8_t* out, long long outImageStride, int outStride, int outWidth, int outHeight, int skip, int batch) {
-	if (kw <= 0 || kw > BHIP_MAX_TAPS) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "kernel width not supported");
-	// ConvolveImageDownNoBorder.checkParameters* (I:alg/filter/convolve/ConvolveImageDownNoBorder.java:160-186), as bhip_launch_conv_down
-	if (skip <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Skip must be >= 1");
-	if (outWidth < width / skip) return bhip_fail(ctx, BHIP_ERR_INVALID, "Output width is too small");
-	if (outHeight < height / skip) return bhip_fail(ctx, BHIP_ERR_INVALID, "Output height is too small");
-	if (vertical && outWidth < width) return bhip_fail(ctx, BHIP_ERR_INVALID, "Output width is too small");
-	if (!vertical && outHeight < height) return bhip_fail(ctx, BHIP_ERR_INVALID, "Output height is too small");
+int bhip_launch_conv_down(bhip_ctx* ctx, bool vertical, const int32_t* kernel, int kw, DevImg<const uint8_t> in, DevImg<uint8_t> out, int skip) {
+	const int width = in.width, height = in.height, batch = in.batch;
 	ConvDownU8Params P;
-	P.in = in; P.out = out; P.inImageStride = inImageStride; P.outImageStride = outImageStride; P.inStride = inStride; P.outStride = outStride;
-	P.width = width; P.height = height; P.skip = skip; P.kw = kw; P.radius = kw / 2;
-	long long sum = 0;
-	for (int i = 0; i < kw; i++) { P.k[i] = kernel[i]; sum += kernel[i]; }
-	if (sum == 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "/ by zero (the kernel sums to 0)");
-	const int r = P.radius;
-	const int side = vertical ? height : width;
-	P.naive = kw >= width ? 1 : 0;   // sic: the vertical form tests the image WIDTH as well
-	P.offset = downOffset(skip, r);
-	P.offsetRem = P.offset % skip;
-	P.maxSide = downMaxSide(side, skip, r);
-	P.offsetEnd = P.maxSide + skip;
-	P.sideTrunc = side - side % skip;
-	if (!P.naive) {
-		if (kw % 2 != 1) return bhip_fail(ctx, BHIP_ERR_INVALID, "Non symmetric odd kernels not supported");
-		bool ok = true;   // every loop of the reference stays inside the image along the filtered axis (see bhip_launch_conv_down)
-		if (P.offset <= P.maxSide) ok = ok && P.offset - r >= 0;
-		const int lastLeft = ((P.offset - 1) / skip) * skip;
-		ok = ok && lastLeft + r < side;
-		if (P.offsetEnd < P.sideTrunc) ok = ok && P.offsetEnd - r >= 0;
-		if (!ok) return bhip_fail(ctx, BHIP_ERR_INVALID, "kernel does not fit the image along the filtered axis");
-	}
+	BHIP_TRY(convDownSetup(ctx, vertical, kernel, kw, in, out, skip, P));
 	const int gw = vertical ? width : width / skip;
 	const int gh = vertical ? height / skip : height;
 	if (gw <= 0 || gh <= 0 || batch <= 0) return BHIP_OK;
@@ -2395,12 +2407,14 @@ __global__ __launch_bounds__(256) void k_corner_cols_s16(CornerS16Params P, cons
 size_t bhip_corner_box_s16_scratch(int radius, int width, int height, int batch) {
 	return cornerBoxLds(radius) <= 65536 ? 0 : (size_t)3 * width * height * 4 * batch;
 }
-int bhip_launch_corner_box_s16(bhip_ctx* ctx, int kind, int radius, float kappa, const int16_t* dx, const int16_t* dy, long long dImageStride, int dStride,
-							   int width, int height, int batch, float* intensity, long long iImageStride, int iStride, void* scratch) {
+int bhip_launch_corner_box_s16(bhip_ctx* ctx, int kind, int radius, float kappa, DevImg<const int16_t> dx, DevImg<const int16_t> dy, DevImg<float> intensity,
+							   void* scratch) {
+	const int width = dx.width, height = dx.height, batch = dx.batch;
 	if (kind != 0 && kind != 1) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "corner score not supported");
 	if (radius < 0 || 2 * radius + 1 > width || 2 * radius + 1 > height) return bhip_fail(ctx, BHIP_ERR_INVALID, "window larger than the image");
 	if (batch <= 0) return BHIP_OK;
-	CornerS16Params P{dx, dy, dImageStride, iImageStride, dStride, width, height, radius, intensity, iStride, kind, kappa};
+	if (!sameLayout(dx, dy)) return bhip_fail(ctx, BHIP_ERR_INVALID, "dx and dy must share one layout");
+	CornerS16Params P{dx.data, dy.data, dx.imageStride, intensity.imageStride, dx.stride, width, height, radius, intensity.data, intensity.stride, kind, kappa};
 	const size_t lds = cornerBoxLds(radius);
 	if (lds <= 65536) {
 		const int bx = (width + CB_TX - 1) / CB_TX, by = (height + CB_TY - 1) / CB_TY;
@@ -2415,7 +2429,8 @@ int bhip_launch_corner_box_s16(bhip_ctx* ctx, int kind, int radius, float kappa,
 	const long long px = (long long)width * height;
 	uint32_t* h = static_cast<uint32_t*>(scratch);
 	for (int b = 0; b < batch; b++)
-		BHIP_HIP(ctx, hipMemset2DAsync(intensity + (long long)b * iImageStride, (size_t)iStride * 4, 0, (size_t)width * 4, (size_t)height, ctx->stream));
+		BHIP_HIP(ctx, hipMemset2DAsync(intensity.data + (long long)b * intensity.imageStride, (size_t)intensity.stride * 4, 0, (size_t)width * 4, (size_t)height,
+									   ctx->stream));
 	{
 		ProfScope prof(ctx, "k_corner_rows_s16", (4.0 + 12.0) * px * batch);
 		hipLaunchKernelGGL(k_corner_rows_s16, dim3((height + 63) / 64, batch), dim3(64), 0, ctx->stream, P, h, h + px, h + 2 * px, px * 3);
@@ -2554,16 +2569,19 @@ __global__ __launch_bounds__(256) void k_corner_weighted(CornerWParams Q, ConvPa
 
 int bhip_corner_weighted_max_radius() { return CW_MAX_RADIUS; }
 
-// s16: derivatives are int16_t (ImplSsdCornerWeighted_S16), else float (ImplSsdCornerWeighted_F32).  radius must be 1 .. CW_MAX_RADIUS.
-int bhip_launch_corner_weighted(bhip_ctx* ctx, bool s16, int kind, int radius, float kappa, const void* dx, const void* dy, long long dImageStride, int dStride,
-								int width, int height, int batch, float* intensity, long long iImageStride, int iStride) {
+// T: the derivatives are int16_t (ImplSsdCornerWeighted_S16) or float (ImplSsdCornerWeighted_F32).  radius must be 1 .. CW_MAX_RADIUS.
+template <class T>
+static int launchCornerWeighted(bhip_ctx* ctx, int kind, int radius, float kappa, DevImg<const T> dx, DevImg<const T> dy, DevImg<float> intensity) {
+	constexpr bool s16 = std::is_same_v<T, int16_t>;
+	const int width = dx.width, height = dx.height, batch = dx.batch;
 	if (kind != 0 && kind != 1) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "corner score not supported");
 	if (radius <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Radius must be > 0");
 	if (radius > CW_MAX_RADIUS) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "weighted corner radius above the supported limit");
 	if (width <= 0 || height <= 0 || batch <= 0) return BHIP_OK;
+	if (!sameLayout(dx, dy)) return bhip_fail(ctx, BHIP_ERR_INVALID, "dx and dy must share one layout");
 	CornerWParams Q{};
-	Q.dx = dx; Q.dy = dy; Q.dImageStride = dImageStride; Q.iImageStride = iImageStride; Q.dStride = dStride; Q.width = width; Q.height = height;
-	Q.radius = radius; Q.intensity = intensity; Q.iStride = iStride; Q.kind = kind; Q.kappa = kappa;
+	Q.dx = dx.data; Q.dy = dy.data; Q.dImageStride = dx.imageStride; Q.iImageStride = intensity.imageStride; Q.dStride = dx.stride; Q.width = width; Q.height = height;
+	Q.radius = radius; Q.intensity = intensity.data; Q.iStride = intensity.stride; Q.kind = kind; Q.kappa = kappa;
 	const int kw = 2 * radius + 1;
 	ConvParams Ph{}, Pv{};
 	if (s16) {
@@ -2589,4 +2607,10 @@ int bhip_launch_corner_weighted(bhip_ctx* ctx, bool s16, int kind, int radius, f
 	else hipLaunchKernelGGL(k_corner_weighted<false>, dim3(bx, by, batch), dim3(256), lds, ctx->stream, Q, Ph, Pv);
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
+}
+int bhip_launch_corner_weighted(bhip_ctx* ctx, int kind, int radius, float kappa, DevImg<const float> dx, DevImg<const float> dy, DevImg<float> intensity) {
+	return launchCornerWeighted(ctx, kind, radius, kappa, dx, dy, intensity);
+}
+int bhip_launch_corner_weighted(bhip_ctx* ctx, int kind, int radius, float kappa, DevImg<const int16_t> dx, DevImg<const int16_t> dy, DevImg<float> intensity) {
+	return launchCornerWeighted(ctx, kind, radius, kappa, dx, dy, intensity);
 }
