@@ -22,15 +22,6 @@
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
-struct HamColTop {   // must match ColTop of associate.hip
-	double min1, min2;
-	int idx1, pad;
-};
-struct HamRowBest {  // must match RowBest of associate.hip
-	double best;
-	int idx, pad;
-};
-
 // one thread per (row, word): 32 bits -> 32 bytes of {0,1}; one thread per row for the popcount
 __global__ __launch_bounds__(256) void k_ham_expand(const int* __restrict__ D, long long rows, int words, unsigned char* __restrict__ bytes, int* __restrict__ pop) {
 	const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -57,8 +48,8 @@ __global__ __launch_bounds__(256) void k_ham_expand(const int* __restrict__ D, l
 // bound by L2 traffic, 16 KB per 16 MFMAs).  The tile is stored as [k-step][lane half][column] 16-byte chunks with a pitch of 33 chunks:
 // fragment reads are contiguous across lanes, staging writes spread over the banks.  Next tile's chunks are fetched into registers
 // before the MFMAs of the current one (double buffer).
-//   COLMODE = false: U = sources, V = destinations -> HamRowBest partial out[split][u]
-//   COLMODE = true : U = destinations, V = sources -> HamColTop partial out[split][u], idx = vBase + v
+//   COLMODE = false: U = sources, V = destinations -> RowBest partial out[split][u]
+//   COLMODE = true : U = destinations, V = sources -> ColTop partial out[split][u], idx = vBase + v
 template <int WORDS, bool COLMODE>
 __global__ __launch_bounds__(256, 2) void k_ham_mfma(const unsigned char* __restrict__ Ub, const int* __restrict__ Up, int nU, const unsigned char* __restrict__ Vb,
 													  const int* __restrict__ Vp, int nV, int vPerSplit, int vBase, double maxErr, void* __restrict__ outRaw) {
@@ -167,14 +158,14 @@ __global__ __launch_bounds__(256, 2) void k_ham_mfma(const unsigned char* __rest
 			const int u = uT + (g & 3) + 8 * (g >> 2) + 4 * h;
 			if (u >= nU) continue;
 			if (!COLMODE) {
-				HamRowBest* out = (HamRowBest*)outRaw + (long long)split * nU + u;
+				RowBest* out = (RowBest*)outRaw + (long long)split * nU + u;
 				const double fit = (double)(k1[g] >> 16);
 				const bool hit = k1[g] != 0xFFFFFFFFu && fit <= maxErr;
 				out->best = hit ? fit : maxErr;
 				out->idx = hit ? v0 + (int)(0xFFFFu - (k1[g] & 0xFFFFu)) : -1;
 				out->pad = 0;
 			} else {
-				HamColTop* out = (HamColTop*)outRaw + (long long)split * nU + u;
+				ColTop* out = (ColTop*)outRaw + (long long)split * nU + u;
 				const bool any = k1[g] != 0xFFFFFFFFu;
 				out->min1 = any ? (double)(k1[g] >> 16) : INFINITY;
 				out->min2 = m2[g] != 0xFFFF ? (double)m2[g] : INFINITY;

@@ -17,22 +17,7 @@
 #include <cmath>
 #include <algorithm>
 
-struct ColTop {
-	double min1, min2;
-	int idx1, pad;
-};
-struct RowBest {
-	double best;
-	int idx, pad;
-};
-
 #define VT 64  // vectors of the streamed set per LDS tile
-
-// int8 MFMA Hamming path (assoc_ham_mfma.hip)
-int bhip_ham_expand(bhip_ctx* ctx, const int* D, long long rows, int words, unsigned char* bytes, int* pop);
-int bhip_ham_mfma_splits(int nU, int nV);
-int bhip_ham_mfma_scan(bhip_ctx* ctx, bool colMode, const unsigned char* Ub, const int* Up, int nU, const unsigned char* Vb, const int* Vp, int nV, int words,
-						 int vBase, double maxErr, void* partial, int splits);
 
 template <int DOF>
 struct L2Scorer {

@@ -241,7 +241,7 @@ struct FhOctavePlan {
 struct FhDetector {
 	bhip_fh_cfg cfg;
 	int W = 0, H = 0, batch = 0, cap = 0;
-	bool intTaps = false;   // the integral image holds int32 (GrayS32, from a GrayU8 frame) instead of float
+	bool plannedInt = false;   // the plan is for GrayS32 integral images (from GrayU8 frames; integer taps) instead of GrayF32 ones
 	std::vector<FhOctavePlan> plan;
 	int bitmapWords = 0;
 	DevBuf inten, bitmap, prefix, cand, sorted, count, selKey, selIdx, selLevels;
@@ -305,7 +305,7 @@ struct FhDetector {
 			// N-best selection needs every level's NMS list and intensity images in memory: stand-alone kernels
 			o.fused = !unfusedOnly() && !nBest() && !o.mids.empty() && bhip_fused_plan(o.skip, o.nlevels, o.sizes, cfg.extractRadius, &ftx, &fty, &flds);
 			o.fixed = o.fused && bhip_fused_is_fixed(o.skip, o.nlevels, o.sizes, cfg.extractRadius);
-			if (intTaps && !o.fixed) o.fused = false;   // integer taps: compile-time-geometry fused kernel or the stand-alone kernels
+			if (plannedInt && !o.fixed) o.fused = false;   // integer taps: compile-time-geometry fused kernel or the stand-alone kernels
 			o.nexport = 0;
 			for (int i = 0; i < BHIP_MAX_LEVELS; i++) { o.shareFrom[i] = -1; o.exportSlot[i] = -1; o.onDemand[i] = false; }
 		}
@@ -343,9 +343,11 @@ struct FhDetector {
 		}
 	}
 
-	bool plannedInt = false;
+	// T: element type of the integral images that run() will be given (float or int32_t)
+	template <class T>
 	int prepare(bhip_ctx* ctx, int width, int height, int batch_) {
-		if (width != W || height != H || plannedInt != intTaps) { BHIP_TRY(makePlan(ctx, width, height)); planExecution(); plannedInt = intTaps; }
+		constexpr bool isInt = std::is_same<T, int32_t>::value;
+		if (width != W || height != H || plannedInt != isInt) { BHIP_TRY(makePlan(ctx, width, height)); plannedInt = isInt; planExecution(); }
 		W = width; H = height; batch = batch_;
 		if (cap == 0) cap = 8192;
 		return allocate(ctx);
@@ -376,8 +378,11 @@ struct FhDetector {
 		return BHIP_OK;
 	}
 
-	// ii: dense integral images.  Leaves the ordered key points in `sorted` ([image][cap]) and their counts in `counts`.
-	int run(bhip_ctx* ctx, ImgView ii) {
+	// level l of the intensity planes of stand-alone octave o
+	DevImg<float> level(const FhOctavePlan& o, int l) const { return {inten.as<float>() + o.intenOff + (size_t)l * o.w * o.h, o.intenImageStride, o.w, o.w, o.h, batch}; }
+	// ii: the dense integral images prepare<T>() planned for.  Leaves the ordered key points in `sorted` ([image][cap]) and their counts in `counts`.
+	template <class T>
+	int run(bhip_ctx* ctx, DevImg<const T> ii) {
 		for (int attempt = 0; attempt < 8; attempt++) {
 			BHIP_HIP(ctx, hipMemsetAsync(bitmap.p, 0, (size_t)bitmapWords * 4 * batch, ctx->stream));
 			BHIP_HIP(ctx, hipMemsetAsync(count.p, 0, (size_t)batch * 4 * 2, ctx->stream));
@@ -395,40 +400,34 @@ struct FhDetector {
 						const FhOctavePlan& c = plan[k + 1];
 						ex.n = o.nexport;
 						for (int j = 0; j < o.nlevels; j++) if (o.exportSlot[j] >= 0) ex.level[o.exportSlot[j]] = j;
-						ex.out = inten.as<float>() + c.intenOff; ex.w = c.w; ex.h = c.h; ex.imageStride = c.intenImageStride;
+						ex.out = level(c, 0).data; ex.w = c.w; ex.h = c.h; ex.imageStride = c.intenImageStride;
 						for (int i = 0; i < c.nlevels; i++) {
 							const int j = c.shareFrom[i];
 							if (j >= 0 && o.exportSlot[j] >= 0) ex.slotOffset[o.exportSlot[j]] = (long long)i * c.w * c.h;
 						}
 					}
-					BHIP_TRY(bhip_launch_detect_fused(ctx, ii, batch, o.skip, o.nlevels, o.sizes, (int)o.mids.size(), mp, ml, cfg.extractRadius,
+					BHIP_TRY(bhip_launch_detect_fused(ctx, ii, o.skip, o.nlevels, o.sizes, (int)o.mids.size(), mp, ml, cfg.extractRadius,
 													  cfg.detectThreshold, bitmap.as<unsigned int>(), bitmapWords, cand.as<KeyPoint>(), count.as<int>(), cap,
-													  ex.n > 0 ? &ex : nullptr, intTaps));
+													  ex.n > 0 ? &ex : nullptr));
 					continue;
 				}
-				const long long levelStride = (long long)o.w * o.h;
-				const long long imageStride = o.intenImageStride;
-				float* base = inten.as<float>() + o.intenOff;
 				HessLevelSource from[BHIP_MAX_LEVELS];
 				for (int i = 0; i < o.nlevels; i++) {
 					from[i] = HessLevelSource{nullptr, 0, 0, 1, 0};
 					const int j = o.shareFrom[i];
 					if (j < 0 || k == 0) continue;
 					const FhOctavePlan& p = plan[k - 1];
-					if (p.fused) from[i] = HessLevelSource{base + (size_t)i * levelStride, imageStride, o.w, 1, 1};   // written in place by the fused octave
-					else from[i] = HessLevelSource{inten.as<float>() + p.intenOff + (size_t)j * p.w * p.h, p.intenImageStride, p.w, 2, 0};
+					if (p.fused) from[i] = HessLevelSource{level(o, i).data, o.intenImageStride, o.w, 1, 1};   // written in place by the fused octave
+					else from[i] = HessLevelSource{level(p, j).data, p.intenImageStride, p.w, 2, 0};
 				}
 				unsigned int skipMask = 0;
 				for (int i = 0; i < o.nlevels; i++)
 					if (o.onDemand[i]) skipMask |= 1u << i;
-				BHIP_TRY(bhip_launch_hessian(ctx, ii, batch, o.skip, o.nlevels, o.sizes, base, levelStride, imageStride, o.w, from, intTaps, skipMask));
-				for (auto& m : o.mids) {
-					const float* lower = o.onDemand[m.level - 1] ? nullptr : base + (m.level - 1) * levelStride;
-					const float* upper = o.onDemand[m.level + 1] ? nullptr : base + (m.level + 1) * levelStride;
-					BHIP_TRY(bhip_launch_nms_scalespace(ctx, lower, base + m.level * levelStride, upper, imageStride, o.w, batch, m.p, cfg.extractRadius,
-														cfg.detectThreshold, bitmap.as<unsigned int>(), bitmapWords, cand.as<KeyPoint>(), count.as<int>(), cap,
-														nBest(), &ii, intTaps));
-				}
+				BHIP_TRY(bhip_launch_hessian(ctx, ii, o.skip, o.nlevels, o.sizes, level(o, 0), (long long)o.w * o.h, from, skipMask));
+				auto held = [&](int l) { DevImg<const float> v = level(o, l); if (o.onDemand[l]) v.data = nullptr; return v; };   // nullptr: not in memory
+				for (auto& m : o.mids)
+					BHIP_TRY(bhip_launch_nms_scalespace(ctx, held(m.level - 1), level(o, m.level), held(m.level + 1), m.p, cfg.extractRadius, cfg.detectThreshold,
+														bitmap.as<unsigned int>(), bitmapWords, cand.as<KeyPoint>(), count.as<int>(), cap, nBest(), ii));
 			}
 			BHIP_TRY(bhip_launch_word_prefix(ctx, bitmap.as<unsigned int>(), bitmapWords, batch, prefix.as<unsigned int>(), count.as<int>() + batch));
 			counts.resize(batch);
@@ -463,17 +462,13 @@ struct FhDetector {
 		int* levelStart = selLevels.as<int>();
 		int* levelCount = levelStart + (size_t)std::max(nlv, 1) * batch;
 		int li = 0;
-		for (auto& o : plan) {
-			const long long levelStride = (long long)o.w * o.h;
-			const float* base = inten.as<float>() + o.intenOff;
+		for (auto& o : plan)
 			for (auto& m : o.mids) {
-				BHIP_TRY(bhip_launch_select_nbest(ctx, base + (m.level - 1) * levelStride, base + m.level * levelStride, base + (m.level + 1) * levelStride,
-												  o.intenImageStride, o.w, batch, m.p, cfg.extractRadius, cfg.maxFeaturesPerScale, bitmap.as<unsigned int>(),
-												  prefix.as<unsigned int>(), bitmapWords, sorted.as<KeyPoint>(), cap, selKey.as<float>(), selIdx.as<int>(),
-												  cand.as<KeyPoint>(), levelStart, levelCount, li, nlv));
+				BHIP_TRY(bhip_launch_select_nbest(ctx, level(o, m.level - 1), level(o, m.level), level(o, m.level + 1), m.p, cfg.extractRadius,
+												  cfg.maxFeaturesPerScale, bitmap.as<unsigned int>(), prefix.as<unsigned int>(), bitmapWords, sorted.as<KeyPoint>(),
+												  cap, selKey.as<float>(), selIdx.as<int>(), cand.as<KeyPoint>(), levelStart, levelCount, li, nlv));
 				li++;
 			}
-		}
 		BHIP_TRY(bhip_launch_compact_levels(ctx, cand.as<KeyPoint>(), cap, levelStart, levelCount, nlv, batch, sorted.as<KeyPoint>(), count.as<int>()));
 		BHIP_HIP(ctx, hipMemcpyAsync(counts.data(), count.p, (size_t)batch * 4, hipMemcpyDeviceToHost, ctx->stream));
 		BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -509,12 +504,15 @@ struct bhip_surf : SurfDevice {
 	std::vector<int> starts;  // batch+1
 	int W = 0, H = 0, batch = 0;
 	bool haveResult = false;
-	ImgView iiView;
+	bool iiInt = false;        // the integral images of the last detect (iiBuf, [batch][H][W]; see withIntegral) are GrayS32, from GrayU8 frames, not GrayF32
 	int planarBands = 0;       // > 0: the last detect was colour SURF on that many bands (descriptor = planarBands * dof values)
-	DescPlanar planar{};
-	bool descOptions = false;  // the last detect needs `planar` passed to the describe kernel (colour bands and / or integer taps)
 	int dofOut() const { return tables.dof * (planarBands > 0 ? planarBands : 1); }
-	float* extII = nullptr;    // worker only: where the integral images of the current chunk go (a slice of the owner's iiBuf)
+	// colour SURF: the bands' integral images follow the grey one in iiBuf
+	DescPlanar planar() const {
+		const long long px = (long long)W * H;
+		return planarBands > 0 ? DescPlanar{iiBuf.as<float>() + px, px * (1 + planarBands), px, planarBands} : DescPlanar{};
+	}
+	const DevBuf* iiOwner = nullptr; int iiFirst = 0;   // worker only: the current chunk's integral images go into the owner's iiBuf, from image iiFirst on
 	// describe = BRIEF (DetectDescribeFusion(fastHessian, null, brief), bhip_surf_create_brief): no orientation / SURF stage; every detected
 	// point gets its TupleDesc_B words from the input frame itself
 	bool brief = false;
@@ -524,6 +522,20 @@ struct bhip_surf : SurfDevice {
 	const int* briefCompare() const { return briefSample() + briefCompareOff; }
 	size_t briefCompareOff = 0;
 };
+
+// The one place where the stored integral images' element type becomes a static type again: f(DevImg<const float>) or f(DevImg<const int32_t>)
+template <class F>
+static int withIntegral(const bhip_surf* s, F f) {
+	return s->iiInt ? f(bhip_img_over<const int32_t>(s->iiBuf, s->W, s->W, s->H, s->batch)) : f(bhip_img_over<const float>(s->iiBuf, s->W, s->W, s->H, s->batch));
+}
+// frame type -> integral image type (GIntegralImageOps.getIntegralType): GrayF32 -> GrayF32, GrayU8 -> GrayS32 (every stage then runs on integer taps)
+template <class T> struct SurfTraits;
+template <> struct SurfTraits<float> { using II = float; };
+template <> struct SurfTraits<uint8_t> { using II = int32_t; };
+constexpr int GREY = 0;   // surfRun's `bands` for single-band frames (otherwise the band count of one colour frame)
+// SYNCHRONIZED: host-frame callers get their frames (and the upload buffer) back only after a final synchronize.  QUEUED: the caller's device-
+// resident batch (bhip_surf_detect_dev_f32) -- the call may return with the describe kernels still queued on the context's stream (its contract)
+enum class SurfReturn { SYNCHRONIZED, QUEUED };
 
 static int buildTables(bhip_surf* s) {
 	bhip_ctx* ctx = s->ctx;
@@ -583,33 +595,24 @@ static int buildTables(bhip_surf* s) {
 	return BHIP_OK;
 }
 
-// planarBands > 0: `in` holds [1 + planarBands] images -- the band average first, then the bands (colour SURF, one frame)
-// u8: `in.data` points at dense 8-bit frames ([batch][H][W] bytes); the integral images are then GrayS32 and every stage runs on integer taps
-// deviceInput: the frames are the caller's device-resident batch (bhip_surf_detect_dev_f32) -- the call may return while the describe kernels
-// are still queued on the context's stream (its documented contract); host-frame callers get their frames back only after a final synchronize
-static int surfRun(bhip_surf* s, ImgView in, int batch, int planarBands = 0, bool u8 = false, bool deviceInput = false) {
+// in: a batch of GrayF32 or GrayU8 (dense) frames, bands == GREY; or, bands > 0, one colour frame as [1 + bands] GrayF32 images -- the band
+// average first, then the bands
+template <class T>
+static int surfRun(bhip_surf* s, DevImg<const T> in, int bands, SurfReturn ret) {
+	using II = typename SurfTraits<T>::II;
 	bhip_ctx* ctx = s->ctx;
-	const int W = in.width, H = in.height;
+	const int W = in.width, H = in.height, batch = bands > 0 ? 1 : in.batch;
+	const long long px = (long long)W * H;
 	s->haveResult = false;
-	s->det.intTaps = u8;
-	BHIP_TRY(s->det.prepare(ctx, W, H, batch));
-	const int nImages = planarBands > 0 ? 1 + planarBands : batch;
-	float* iiBase = s->extII;
-	if (!iiBase) {
-		BHIP_TRY(s->iiBuf.reserve(ctx, (size_t)W * H * 4 * nImages));
-		iiBase = s->iiBuf.as<float>();
-	}
+	BHIP_TRY(s->det.prepare<II>(ctx, W, H, batch));
+	if (!s->iiOwner) BHIP_TRY(s->iiBuf.reserve(ctx, (size_t)px * 4 * in.batch));
+	II* iiBase = s->iiOwner ? s->iiOwner->as<II>() + px * s->iiFirst : s->iiBuf.as<II>();
 	s->W = W; s->H = H; s->batch = batch;
-	ImgViewW iiW{iiBase, (long long)W * H, W, W, H};
-	const DevImg<const uint8_t> inU8{(const uint8_t*)in.data, (long long)W * H, W, W, H, nImages};   // what `in` stands for when u8 is set
-	if (u8) BHIP_TRY(bhip_launch_integral_u8(ctx, inU8, DevImg<int32_t>{(int32_t*)iiBase, (long long)W * H, W, W, H, nImages}));
-	else BHIP_TRY(bhip_launch_integral(ctx, in, iiW, nImages));
-	ImgView ii{iiBase, (long long)W * H, W, W, H};
-	s->iiView = ii;
-	s->planarBands = planarBands;
-	s->planar = DescPlanar{iiBase + (long long)W * H, (long long)W * H * (1 + planarBands), (long long)W * H, planarBands,
-						   planarBands > 0 ? 1.0 : 2.0, u8};
-	s->descOptions = planarBands > 0 || u8;
+	s->iiInt = std::is_same<II, int32_t>::value; s->planarBands = bands;
+	const DevImg<II> iiAll{iiBase, px, W, W, H, in.batch};
+	if constexpr (std::is_same<T, uint8_t>::value) BHIP_TRY(bhip_launch_integral_u8(ctx, in, iiAll));
+	else BHIP_TRY(bhip_launch_integral(ctx, in, iiAll));
+	const DevImg<const II> ii{iiBase, px, W, W, H, batch};
 	BHIP_TRY(s->det.run(ctx, ii));
 	// exclusive prefix of counts -> start of every image in the compact result arrays
 	s->starts.assign(batch + 1, 0);
@@ -630,7 +633,7 @@ static int surfRun(bhip_surf* s, ImgView in, int batch, int planarBands = 0, boo
 		// describe = WrapDescribeBrief (process always returns true, so every detected point is kept, in detector order):
 		// yaw = detector.getOrientation(i) = 0 (WrapFHtoInterestPoint.java:77-79); DescribePointBrief.process samples the frame handed to
 		// setImage (:71-75,86-88 -- the blurred copy it makes is never read)
-		if (planarBands > 0) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "BRIEF runs on single-band frames");
+		if (bands > 0) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "BRIEF runs on single-band frames");
 		BHIP_TRY(s->angBuf.reserve(ctx, (size_t)std::max<long long>(total, 1) * 8));
 		BHIP_TRY(s->whiteBuf.reserve(ctx, (size_t)std::max<long long>(total, 1)));
 		BHIP_TRY(s->wordsBuf.reserve(ctx, (size_t)std::max<long long>(total, 1) * 4 * s->briefWords));
@@ -639,12 +642,9 @@ static int surfRun(bhip_surf* s, ImgView in, int batch, int planarBands = 0, boo
 			BHIP_HIP(ctx, hipMemsetAsync(s->whiteBuf.p, 0, (size_t)total, ctx->stream));
 			int maxCount = 0;
 			for (int c : s->det.counts) maxCount = std::max(maxCount, c);
-			auto brief = [&](auto img) {
-				return bhip_launch_brief(ctx, img, s->briefRadius, s->briefPoints, s->briefSample(), s->briefCompare(), (const double*)s->det.sorted.p, (int)total,
-										 s->wordsBuf.as<int>(), s->startBuf.as<int>(), maxCount, (int)(sizeof(KeyPoint) / 8),
-										 (long long)s->det.cap * (long long)(sizeof(KeyPoint) / 8), s->briefPatch);
-			};
-			BHIP_TRY(u8 ? brief(inU8) : brief(DevImg<const float>{in.data, in.imageStride, in.stride, W, H, batch}));
+			BHIP_TRY(bhip_launch_brief(ctx, in, s->briefRadius, s->briefPoints, s->briefSample(), s->briefCompare(), (const double*)s->det.sorted.p, (int)total,
+									   s->wordsBuf.as<int>(), s->startBuf.as<int>(), maxCount, (int)(sizeof(KeyPoint) / 8),
+									   (long long)s->det.cap * (long long)(sizeof(KeyPoint) / 8), s->briefPatch));
 		}
 		BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
 		s->haveResult = true;
@@ -672,11 +672,11 @@ static int surfRun(bhip_surf* s, ImgView in, int batch, int planarBands = 0, boo
 			perm = s->permBuf.as<int>();
 		}
 	}
-	BHIP_TRY(bhip_launch_describe_ex(ctx, ii, s->det.sorted.as<KeyPoint>(), s->det.cap, s->startBuf.as<int>(), batch, 0, total, s->tables, nullptr,
-									 s->angBuf.as<double>(), s->descBuf.as<double>(), s->whiteBuf.as<uint8_t>(), perm, s->descOptions ? &s->planar : nullptr));
+	BHIP_TRY(bhip_launch_describe_ex(ctx, ii, s->det.sorted.as<KeyPoint>(), s->det.cap, s->startBuf.as<int>(), 0, total, s->tables, nullptr,
+									 s->angBuf.as<double>(), s->descBuf.as<double>(), s->whiteBuf.as<uint8_t>(), perm, s->planar()));
 	// host-frame callers may reuse their frames (and the upload buffer) as soon as the call returns; a device-resident batch was consumed before
 	// the detector's count read-back, so its call returns with the describe kernels still in flight (stream order covers every later use)
-	if (!deviceInput) BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (ret == SurfReturn::SYNCHRONIZED) BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	s->haveResult = true;
 	return BHIP_OK;
 }
@@ -699,10 +699,11 @@ static int growKeep(bhip_ctx* ctx, DevBuf& b, size_t bytes, size_t keep) {
 
 // Host frames -> device in chunks on the copy stream, each chunk detected + described by the worker object as soon as it has arrived;
 // results are appended to the owner's arrays, which end up exactly as one surfRun over the whole batch leaves them.
-// upload(i, dst, stream) enqueues the copy of frame i.  Returns BHIP_OK with *done = false when the batch has to go through the plain
-// path (small batch, or a key-point list outgrew the owner's capacity half way).
-template <class Upload>
-static int surfRunChunked(bhip_surf* s, int width, int height, int batch, size_t imgBytes, bool u8, Upload upload, bool* done) {
+// upload(i, dst, stream) enqueues the copy of frame i (T: the frames' element type).  Returns BHIP_OK with *done = false when the batch has
+// to go through the plain path (small batch, or a key-point list outgrew the owner's capacity half way).
+template <class T, class Upload>
+static int surfRunChunked(bhip_surf* s, int width, int height, int batch, Upload upload, bool* done) {
+	using II = typename SurfTraits<T>::II;
 	bhip_ctx* ctx = s->ctx;
 	*done = false;
 	int chunk = SURF_CHUNK;
@@ -721,8 +722,7 @@ static int surfRunChunked(bhip_surf* s, int width, int height, int batch, size_t
 	bhip_surf* w = s->worker.get();
 	const size_t px = (size_t)width * height;
 	s->haveResult = false;
-	s->det.intTaps = u8;
-	BHIP_TRY(s->det.prepare(ctx, width, height, batch));
+	BHIP_TRY(s->det.prepare<II>(ctx, width, height, batch));
 	BHIP_TRY(s->iiBuf.reserve(ctx, px * 4 * batch));
 	// everything queued on the compute stream so far (an earlier batch may still read inBuf) precedes the first upload
 	const int nchunks = (batch + chunk - 1) / chunk;
@@ -736,7 +736,7 @@ static int surfRunChunked(bhip_surf* s, int width, int height, int batch, size_t
 	int status = BHIP_OK;
 	for (int c = 0; c < nchunks && status == BHIP_OK; c++) {
 		const int a = c * chunk, n = std::min(chunk, batch - a);
-		for (int i = a; i < a + n && status == BHIP_OK; i++) status = upload(i, (char*)s->inBuf.p + imgBytes * i, s->copyStream);
+		for (int i = a; i < a + n && status == BHIP_OK; i++) status = upload(i, s->inBuf.as<T>() + px * i, s->copyStream);
 		if (status == BHIP_OK && (hipEventCreateWithFlags(&arrived[c].h, hipEventDisableTiming) != hipSuccess || hipEventRecord(arrived[c], s->copyStream) != hipSuccess))
 			status = bhip_fail(ctx, BHIP_ERR_HIP, "event");
 	}
@@ -748,9 +748,8 @@ static int surfRunChunked(bhip_surf* s, int width, int height, int batch, size_t
 	for (int c = 0; c < nchunks && status == BHIP_OK && fits; c++) {
 		const int a = c * chunk, n = std::min(chunk, batch - a);
 		if (hipStreamWaitEvent(ctx->stream, arrived[c], 0) != hipSuccess) { status = bhip_fail(ctx, BHIP_ERR_HIP, "wait"); break; }
-		w->extII = s->iiBuf.as<float>() + px * a;
-		ImgView in{(const float*)((const char*)s->inBuf.p + imgBytes * a), (long long)px, width, width, height};   // u8: only pointer and shape are used
-		status = surfRun(w, in, n, 0, u8);
+		w->iiOwner = &s->iiBuf; w->iiFirst = a;
+		status = surfRun(w, DevImg<const T>{s->inBuf.as<T>() + px * a, (long long)px, width, width, height, n}, GREY, SurfReturn::SYNCHRONIZED);
 		if (status != BHIP_OK) break;
 		int maxCount = 0;
 		for (int i = 0; i < n; i++) maxCount = std::max(maxCount, w->det.counts[i]);
@@ -779,21 +778,18 @@ static int surfRunChunked(bhip_surf* s, int width, int height, int batch, size_t
 	// every upload has to be over before the caller's frames may change (and before the plain path re-uses inBuf)
 	(void)hipStreamSynchronize(s->copyStream);
 	(void)hipStreamSynchronize(ctx->stream);
-	w->extII = nullptr;
+	w->iiOwner = nullptr;
 	if (status != BHIP_OK) return status;
 	if (!fits) {
 		// the frames are all on the device: run the whole batch the plain way (its detector grows the key-point capacity as needed)
-		ImgView in{s->inBuf.as<float>(), (long long)px, width, width, height};
 		*done = true;
-		return surfRun(s, in, batch, 0, u8);
+		return surfRun(s, bhip_img_over<const T>(s->inBuf, width, width, height, batch), GREY, SurfReturn::SYNCHRONIZED);
 	}
 	if (total > 0x7fffffffLL) return bhip_fail(ctx, BHIP_ERR_CAPACITY, "more than 2^31 key points in one batch");
 	s->det.total = total;
 	s->W = width; s->H = height; s->batch = batch;
-	s->iiView = ImgView{s->iiBuf.as<float>(), (long long)px, width, width, height};
+	s->iiInt = std::is_same<II, int32_t>::value;
 	s->planarBands = 0;
-	s->planar = DescPlanar{s->iiBuf.as<float>() + (long long)px, (long long)px, (long long)px, 0, 2.0, u8};
-	s->descOptions = u8;
 	BHIP_TRY(s->startBuf.reserve(ctx, (size_t)(batch + 1) * 4));
 	BHIP_HIP(ctx, hipMemcpyAsync(s->startBuf.p, s->starts.data(), (size_t)(batch + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
 	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -846,20 +842,18 @@ static int surfDetectHost(bhip_surf* s, const T* const* img, const int* startInd
 	bhip_ctx* ctx = s->ctx;
 	CHECK_CTX(ctx);
 	if (!img || width <= 0 || height <= 0 || batch <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image batch");
-	const bool u8 = sizeof(T) == 1;
-	const size_t imgBytes = (size_t)width * height * sizeof(T);
-	BHIP_TRY(s->inBuf.reserve(ctx, imgBytes * batch));
+	const size_t px = (size_t)width * height;
+	BHIP_TRY(s->inBuf.reserve(ctx, px * sizeof(T) * batch));
 	for (int i = 0; i < batch; i++)
 		if (!img[i] || (stride ? stride[i] : width) < width) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image (null or stride < width)");
-	auto put = [&](int i, void* dst, hipStream_t st) {
-		return upload(ctx, (T*)dst, width, img[i], startIndex ? startIndex[i] : 0, stride ? stride[i] : width, width, height, st);
+	auto put = [&](int i, T* dst, hipStream_t st) {
+		return upload(ctx, dst, width, img[i], startIndex ? startIndex[i] : 0, stride ? stride[i] : width, width, height, st);
 	};
 	bool done = false;
-	BHIP_TRY(surfRunChunked(s, width, height, batch, imgBytes, u8, put, &done));
+	BHIP_TRY(surfRunChunked<T>(s, width, height, batch, put, &done));
 	if (done) return BHIP_OK;
-	for (int i = 0; i < batch; i++) BHIP_TRY(put(i, (char*)s->inBuf.p + imgBytes * i, ctx->stream));
-	ImgView in{s->inBuf.as<float>(), (long long)width * height, width, width, height};   // u8: only the pointer and the shape are used
-	return surfRun(s, in, batch, 0, u8);
+	for (int i = 0; i < batch; i++) BHIP_TRY(put(i, s->inBuf.as<T>() + px * i, ctx->stream));
+	return surfRun(s, bhip_img_over<const T>(s->inBuf, width, width, height, batch), GREY, SurfReturn::SYNCHRONIZED);
 }
 
 // AssociateDescription over the descriptors still resident from the last detect of `s`: checks the problem table of
@@ -894,6 +888,59 @@ static int assocSurf(bhip_surf* s, int count, const int* srcImage, const int* ds
 	BHIP_HIP(ctx, hipMemcpyAsync(pairs, sc->out0.p, (size_t)total * 4, hipMemcpyDeviceToHost, ctx->stream));
 	BHIP_HIP(ctx, hipMemcpyAsync(fit, sc->out1.p, (size_t)total * 8, hipMemcpyDeviceToHost, ctx->stream));
 	return bhip_ctx_synchronize(ctx);
+}
+
+// bhip_hessian_f32 (T = float) and bhip_hessian_s32 (T = int32_t).  Their argument checks differ (not harmonised): S32 refuses a null or too
+// narrow output and an intensity image without pixels, F32 checks the output only after an empty intensity image has returned BHIP_OK
+template <class T>
+static int hessianHost(bhip_ctx* ctx, HostImg<const T> hin, int skip, int size, float* intensity, int outStart, int outStride) {
+	constexpr bool s32 = std::is_same<T, int32_t>::value;
+	CHECK_CTX(ctx);
+	CHECK_IMG(ctx, hin);
+	if (s32 && !intensity) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image");
+	if (skip < 1 || size < 3) return bhip_fail(ctx, BHIP_ERR_INVALID, s32 ? "bad skip / size" : "bad skip/size");
+	const int w = hin.width / skip, h = hin.height / skip;
+	if (s32 && (w <= 0 || h <= 0 || outStride < w)) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad intensity image");
+	if (w <= 0 || h <= 0) return BHIP_OK;
+	const HostImg<float> hout{intensity, outStart, outStride, w, h};
+	CHECK_IMG(ctx, hout);
+	CtxScratch* sc = scratchOf(ctx);
+	DevImg<T> din;
+	DevImg<float> dout;
+	BHIP_TRY(stageIn(ctx, sc->in0, hin, hin.width, din));
+	BHIP_TRY(stageIn(ctx, sc->out0, hout, w, dout, false));
+	BHIP_TRY(bhip_launch_hessian(ctx, DevImg<const T>(din), skip, 1, &size, dout, (long long)w * h, nullptr, 0));
+	BHIP_TRY(stageOut(ctx, hout, dout));
+	return bhip_ctx_synchronize(ctx);
+}
+
+// FastHessianFeatureDetector.detect(integral) on a GrayF32 (T = float) or a GrayS32 (T = int32_t, from a GrayU8 frame) integral image
+template <class T>
+static int fhDetect(bhip_ctx* ctx, const bhip_fh_cfg* cfg, HostImg<const T> hin, double* xy_scale, int cap, int* n) {
+	CHECK_CTX(ctx);
+	CHECK_IMG(ctx, hin);
+	if (!n || cap < 0 || (cap > 0 && !xy_scale)) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad output");
+	*n = 0;
+	FhDetector det;
+	if (cfg) det.cfg = *cfg; else bhip_fh_cfg_default(&det.cfg);
+	CtxScratch* sc = scratchOf(ctx);
+	DevImg<T> din;
+	int status = stageIn(ctx, sc->in0, hin, hin.width, din);
+	if (status == BHIP_OK) status = det.prepare<T>(ctx, hin.width, hin.height, 1);
+	if (status == BHIP_OK) status = det.run(ctx, DevImg<const T>(din));
+	if (status == BHIP_OK) {
+		*n = det.counts[0];
+		const int ncopy = std::min(*n, cap);
+		if (ncopy > 0) {
+			std::vector<KeyPoint> kps(ncopy);
+			hipError_t e = hipMemcpyAsync(kps.data(), det.sorted.p, (size_t)ncopy * sizeof(KeyPoint), hipMemcpyDeviceToHost, ctx->stream);
+			if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+			if (e != hipSuccess) status = bhip_fail(ctx, BHIP_ERR_HIP, hipGetErrorString(e));
+			else for (int i = 0; i < ncopy; i++) { xy_scale[3 * i] = kps[i].x; xy_scale[3 * i + 1] = kps[i].y; xy_scale[3 * i + 2] = kps[i].scale; }
+		}
+	}
+	(void)hipStreamSynchronize(ctx->stream);   // det's buffers are freed on return
+	return status;
 }
 
 extern "C" {
@@ -931,8 +978,7 @@ int bhip_surf_detect_dev_f32(bhip_surf* s, const float* dev_images, long long im
 	bhip_ctx* ctx = s->ctx;
 	CHECK_CTX(ctx);
 	if (!dev_images || width <= 0 || height <= 0 || batch <= 0 || stride < width) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image batch");
-	ImgView in{dev_images, imageStride, stride, width, height};
-	return surfRun(s, in, batch, 0, false, true);
+	return surfRun(s, DevImg<const float>{dev_images, imageStride, stride, width, height, batch}, GREY, SurfReturn::QUEUED);
 }
 
 int bhip_surf_detect_f32(bhip_surf* s, const float* const* img, const int* startIndex, const int* stride, int width, int height, int batch) {
@@ -956,8 +1002,7 @@ int bhip_surf_detect_planar_f32(bhip_surf* s, const float* const* bands, int num
 		BHIP_TRY(upload(ctx, s->inBuf.as<float>() + px * (1 + b), width, bands[b], startIndex, stride, width, height, ctx->stream));
 	}
 	BHIP_TRY(bhip_launch_planar_average(ctx, s->inBuf.as<float>() + px, (long long)px, numBands, (long long)px, s->inBuf.as<float>()));
-	ImgView in{s->inBuf.as<float>(), (long long)px, width, width, height};
-	return surfRun(s, in, 1, numBands);
+	return surfRun(s, bhip_img_over<const float>(s->inBuf, width, width, height, 1 + numBands), numBands, SurfReturn::SYNCHRONIZED);
 }
 
 // FactoryDetectDescribe.surfStable / surfFast on GrayU8 frames (integral type GrayS32, GIntegralImageOps.getIntegralType): same results
@@ -1134,8 +1179,10 @@ int bhip_surf_describe_points(bhip_surf* s, int image, const double* xy_scale, i
 	BHIP_TRY(s->tmpDesc.reserve(ctx, (size_t)n * 8 * dof));
 	BHIP_TRY(s->tmpWhite.reserve(ctx, (size_t)n));
 	BHIP_HIP(ctx, hipMemcpyAsync(s->tmpKp.p, kps.data(), (size_t)n * sizeof(KeyPoint), hipMemcpyHostToDevice, ctx->stream));
-	BHIP_TRY(bhip_launch_describe_ex(ctx, s->iiView, s->tmpKp.as<KeyPoint>(), 0, nullptr, s->batch, image, n, s->tables, nullptr, s->tmpAng.as<double>(),
-									 s->tmpDesc.as<double>(), s->tmpWhite.as<uint8_t>(), nullptr, s->descOptions ? &s->planar : nullptr));
+	BHIP_TRY(withIntegral(s, [&](auto ii) {
+		return bhip_launch_describe_ex(ctx, ii, s->tmpKp.as<KeyPoint>(), 0, nullptr, image, n, s->tables, nullptr, s->tmpAng.as<double>(),
+									   s->tmpDesc.as<double>(), s->tmpWhite.as<uint8_t>(), nullptr, s->planar());
+	}));
 	if (angle) BHIP_HIP(ctx, hipMemcpyAsync(angle, s->tmpAng.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
 	if (white) BHIP_HIP(ctx, hipMemcpyAsync(white, s->tmpWhite.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
 	if (desc) BHIP_HIP(ctx, hipMemcpyAsync(desc, s->tmpDesc.p, (size_t)n * 8 * dof, hipMemcpyDeviceToHost, ctx->stream));
@@ -1148,36 +1195,19 @@ int bhip_surf_describe_points(bhip_surf* s, int image, const double* xy_scale, i
 // ---------------------------------------------------------------------------------------------------------------
 int bhip_integral_f32(bhip_ctx* ctx, const float* in, int inStart, int inStride, int width, int height, float* out, int outStart, int outStride) {
 	return hostInOut<float, float>(ctx, {in, inStart, inStride, width, height}, {out, outStart, outStride, width, height}, false, false, nullptr, [&](auto din, auto dout) {
-		ImgView iv{din.data, din.imageStride, width, width, height};
-		ImgViewW ov{dout.data, dout.imageStride, width, width, height};
-		return bhip_launch_integral(ctx, iv, ov, 1);
+		return bhip_launch_integral(ctx, din, dout);
 	});
 }
 
 int bhip_hessian_f32(bhip_ctx* ctx, const float* ii, int iiStart, int iiStride, int width, int height, int skip, int size, float* intensity,
 					 int outStart, int outStride) {
-	const HostImg<const float> hin{ii, iiStart, iiStride, width, height};
-	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, hin);
-	if (skip < 1 || size < 3) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad skip/size");
-	const int w = width / skip, h = height / skip;
-	if (w <= 0 || h <= 0) return BHIP_OK;
-	const HostImg<float> hout{intensity, outStart, outStride, w, h};
-	CHECK_IMG(ctx, hout);
-	CtxScratch* sc = scratchOf(ctx);
-	DevImg<float> din, dout;
-	BHIP_TRY(stageIn(ctx, sc->in0, hin, width, din));
-	BHIP_TRY(stageIn(ctx, sc->out0, hout, w, dout, false));
-	ImgView iv{din.data, din.imageStride, width, width, height};
-	BHIP_TRY(bhip_launch_hessian(ctx, iv, 1, skip, 1, &size, dout.data, (long long)w * h, (long long)w * h, w));
-	BHIP_TRY(stageOut(ctx, hout, dout));
-	return bhip_ctx_synchronize(ctx);
+	return hessianHost<float>(ctx, {ii, iiStart, iiStride, width, height}, skip, size, intensity, outStart, outStride);
 }
 
-// strict block NMS of `batch` dense device images: lists into dev_xy ([batch][cap] (x,y) int16 pairs, block-raster order), counts into
+// strict block NMS of a batch of device images: lists into dev_xy ([batch][cap] (x,y) int16 pairs, block-raster order), counts into
 // dev_n[batch] (a count may exceed cap: only the first cap pairs are written)
-static int nonmaxDevice(bhip_ctx* ctx, const float* dev_intensity, long long imageStride, int stride, int width, int height, int batch, int radius,
-						float threshold, int border, int16_t* dev_xy, int cap, int* dev_n) {
+static int nonmaxDevice(bhip_ctx* ctx, DevImg<const float> img, int radius, float threshold, int border, int16_t* dev_xy, int cap, int* dev_n) {
+	const int width = img.width, height = img.height, batch = img.batch;
 	if (radius < 1) return bhip_fail(ctx, BHIP_ERR_INVALID, "Search radius must be >= 1");
 	if (border < 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Ignore border must be >= 0 ");
 	if (width >= 32768 || height >= 32768) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "image too large for Point2D_I16");
@@ -1192,8 +1222,7 @@ static int nonmaxDevice(bhip_ctx* ctx, const float* dev_intensity, long long ima
 	BHIP_TRY(sc->nmsPrefix.reserve(ctx, (size_t)words * 4 * batch));
 	BHIP_TRY(sc->nmsPos.reserve(ctx, (size_t)nbx * nby * 2 * batch));
 	BHIP_HIP(ctx, hipMemsetAsync(sc->nmsBitmap.p, 0, (size_t)words * 4 * batch, ctx->stream));
-	BHIP_TRY(bhip_launch_nonmax_blocks(ctx, dev_intensity, imageStride, stride, width, height, batch, radius, threshold, border, sc->nmsBitmap.as<unsigned int>(),
-									   words, sc->nmsPos.as<unsigned short>(), nbx, nby));
+	BHIP_TRY(bhip_launch_nonmax_blocks(ctx, img, radius, threshold, border, sc->nmsBitmap.as<unsigned int>(), words, sc->nmsPos.as<unsigned short>(), nbx, nby));
 	BHIP_TRY(bhip_launch_word_prefix(ctx, sc->nmsBitmap.as<unsigned int>(), words, batch, sc->nmsPrefix.as<unsigned int>(), dev_n));
 	BHIP_TRY(bhip_launch_blocks_to_xy(ctx, sc->nmsBitmap.as<unsigned int>(), sc->nmsPrefix.as<unsigned int>(), words, sc->nmsPos.as<unsigned short>(), nbx, nby,
 									  batch, radius, border, dev_xy, cap));
@@ -1203,9 +1232,10 @@ static int nonmaxDevice(bhip_ctx* ctx, const float* dev_intensity, long long ima
 int bhip_nonmax_block_dev_f32(bhip_ctx* ctx, const float* dev_intensity, long long imageStride, int stride, int width, int height, int batch, int radius,
 							  float threshold, int border, int16_t* dev_xy, int cap, int* dev_n) {
 	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, (DevImg<const float>{dev_intensity, imageStride, stride, width, height, batch}));
+	const DevImg<const float> img{dev_intensity, imageStride, stride, width, height, batch};
+	CHECK_IMG(ctx, img);
 	if (!dev_n || cap < 0 || (cap > 0 && !dev_xy)) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad output");
-	return nonmaxDevice(ctx, dev_intensity, imageStride, stride, width, height, batch, radius, threshold, border, dev_xy, cap, dev_n);
+	return nonmaxDevice(ctx, img, radius, threshold, border, dev_xy, cap, dev_n);
 }
 
 int bhip_nonmax_block_f32(bhip_ctx* ctx, const float* intensity, int start, int stride, int width, int height, int radius, float threshold,
@@ -1220,7 +1250,7 @@ int bhip_nonmax_block_f32(bhip_ctx* ctx, const float* intensity, int start, int 
 	BHIP_TRY(stageIn(ctx, sc->in0, hin, width, din));
 	BHIP_TRY(sc->out0.reserve(ctx, (size_t)std::max(cap, 1) * 4));
 	BHIP_TRY(sc->out1.reserve(ctx, 16));
-	BHIP_TRY(nonmaxDevice(ctx, din.data, 0, width, width, height, 1, radius, threshold, border, sc->out0.as<int16_t>(), cap, sc->out1.as<int>()));
+	BHIP_TRY(nonmaxDevice(ctx, din, radius, threshold, border, sc->out0.as<int16_t>(), cap, sc->out1.as<int>()));
 	BHIP_HIP(ctx, hipMemcpyAsync(ctx->hostScratch.p, sc->out1.p, 4, hipMemcpyDeviceToHost, ctx->stream));
 	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the count decides how much of the list to copy
 	*n = ctx->hostScratch.as<int>()[0];
@@ -1255,7 +1285,7 @@ int bhip_select_nbest_f32(bhip_ctx* ctx, const float* intensity, int start, int 
 	BHIP_TRY(sc->tmp1.reserve(ctx, (size_t)n * 4));
 	BHIP_TRY(sc->out0.reserve(ctx, (size_t)target * 4));
 	BHIP_HIP(ctx, hipMemcpyAsync(sc->in1.p, xy, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-	BHIP_TRY(bhip_launch_select_nbest_xy(ctx, din.data, width, sc->in1.as<int16_t>(), n, target, positive != 0, sc->tmp0.as<float>(),
+	BHIP_TRY(bhip_launch_select_nbest_xy(ctx, din, sc->in1.as<int16_t>(), n, target, positive != 0, sc->tmp0.as<float>(),
 										 sc->tmp1.as<int>(), sc->out0.as<int16_t>()));
 	BHIP_HIP(ctx, hipMemcpyAsync(out_xy, sc->out0.p, (size_t)target * 4, hipMemcpyDeviceToHost, ctx->stream));
 	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1263,44 +1293,13 @@ int bhip_select_nbest_f32(bhip_ctx* ctx, const float* intensity, int start, int 
 	return BHIP_OK;
 }
 
-// FastHessianFeatureDetector.detect(integral): intTaps = the integral image holds int32 (GrayS32, from a GrayU8 frame) instead of float
-static int fhDetect(bhip_ctx* ctx, const bhip_fh_cfg* cfg, const void* ii, bool intTaps, int iiStart, int iiStride, int width, int height,
-					double* xy_scale, int cap, int* n) {
-	const HostImg<const float> hin{(const float*)ii, iiStart, iiStride, width, height};   // 32-bit words either way
-	CHECK_CTX(ctx);
-	CHECK_IMG(ctx, hin);
-	if (!n || cap < 0 || (cap > 0 && !xy_scale)) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad output");
-	*n = 0;
-	FhDetector det;
-	det.intTaps = intTaps;
-	if (cfg) det.cfg = *cfg; else bhip_fh_cfg_default(&det.cfg);
-	CtxScratch* sc = scratchOf(ctx);
-	DevImg<float> din;
-	int status = stageIn(ctx, sc->in0, hin, width, din);
-	if (status == BHIP_OK) status = det.prepare(ctx, width, height, 1);
-	ImgView iv{sc->in0.as<float>(), (long long)width * height, width, width, height};
-	if (status == BHIP_OK) status = det.run(ctx, iv);
-	if (status == BHIP_OK) {
-		*n = det.counts[0];
-		const int ncopy = std::min(*n, cap);
-		if (ncopy > 0) {
-			std::vector<KeyPoint> kps(ncopy);
-			hipError_t e = hipMemcpyAsync(kps.data(), det.sorted.p, (size_t)ncopy * sizeof(KeyPoint), hipMemcpyDeviceToHost, ctx->stream);
-			if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-			if (e != hipSuccess) status = bhip_fail(ctx, BHIP_ERR_HIP, hipGetErrorString(e));
-			else for (int i = 0; i < ncopy; i++) { xy_scale[3 * i] = kps[i].x; xy_scale[3 * i + 1] = kps[i].y; xy_scale[3 * i + 2] = kps[i].scale; }
-		}
-	}
-	(void)hipStreamSynchronize(ctx->stream);   // det's buffers are freed on return
-	return status;
-}
 int bhip_fh_detect_f32(bhip_ctx* ctx, const bhip_fh_cfg* cfg, const float* ii, int iiStart, int iiStride, int width, int height, double* xy_scale,
 					   int cap, int* n) {
-	return fhDetect(ctx, cfg, ii, false, iiStart, iiStride, width, height, xy_scale, cap, n);
+	return fhDetect<float>(ctx, cfg, {ii, iiStart, iiStride, width, height}, xy_scale, cap, n);
 }
 int bhip_fh_detect_s32(bhip_ctx* ctx, const bhip_fh_cfg* cfg, const int32_t* ii, int iiStart, int iiStride, int width, int height, double* xy_scale,
 					   int cap, int* n) {
-	return fhDetect(ctx, cfg, ii, true, iiStart, iiStride, width, height, xy_scale, cap, n);
+	return fhDetect<int32_t>(ctx, cfg, {ii, iiStart, iiStride, width, height}, xy_scale, cap, n);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1892,20 +1891,7 @@ int bhip_integral_u8_s32(bhip_ctx* ctx, const uint8_t* in, int inStart, int inSt
 }
 int bhip_hessian_s32(bhip_ctx* ctx, const int32_t* ii, int iiStart, int iiStride, int width, int height, int skip, int size, float* out, int outStart,
 					 int outStride) {
-	CHECK_CTX(ctx);
-	if (!ii || !out || width <= 0 || height <= 0 || iiStride < width) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image");
-	if (skip < 1 || size < 3) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad skip / size");
-	const int w = width / skip, h = height / skip;
-	if (w <= 0 || h <= 0 || outStride < w) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad intensity image");
-	const HostImg<float> hout{out, outStart, outStride, w, h};
-	CtxScratch* sc = scratchOf(ctx);
-	DevImg<float> din, dout;
-	BHIP_TRY(stageIn(ctx, sc->in0, HostImg<const float>{(const float*)ii, iiStart, iiStride, width, height}, width, din));   // 32-bit words either way
-	BHIP_TRY(stageIn(ctx, sc->out0, hout, w, dout, false));
-	ImgView iv{din.data, din.imageStride, width, width, height};
-	BHIP_TRY(bhip_launch_hessian(ctx, iv, 1, skip, 1, &size, dout.data, (long long)w * h, (long long)w * h, w, nullptr, true));
-	BHIP_TRY(stageOut(ctx, hout, dout));
-	return bhip_ctx_synchronize(ctx);
+	return hessianHost<int32_t>(ctx, {ii, iiStart, iiStride, width, height}, skip, size, out, outStart, outStride);
 }
 
 // The BRIEF exports differ in what they accept (not harmonised): bhip_brief_f32 rejects a pair index >= numPoints and decides the kernel over
@@ -2398,20 +2384,19 @@ int bhip_klt_spawn(bhip_klt* k, int maxFeatures) {
 	const int w0 = k->dims[0], h0 = k->dims[1];
 	const long long px = (long long)w0 * h0;
 	BHIP_TRY(k->intensity.reserve(ctx, (size_t)px * 4 * k->batch));
-	float* inten = k->intensity.as<float>();
+	const DevImg<float> inten = bhip_img_over<float>(k->intensity, w0, w0, h0, k->batch);
 	// FactoryIntensityPointAlg.shiTomasi(1, false, derivType): ImplSsdCorner_F32, or ImplSsdCorner_S16 on the GrayS16 derivatives of a GrayU8 tracker
 	BHIP_TRY(k->withTypes([&](auto t) {
 		using TD = typename decltype(t)::TD;
-		return cornerImpl<TD>(ctx, false, 0, 1, 0.0f, k->layer<const TD>(1, 0), k->layer<const TD>(2, 0), bhip_img_over<float>(k->intensity, w0, w0, h0, k->batch));
+		return cornerImpl<TD>(ctx, false, 0, 1, 0.0f, k->layer<const TD>(1, 0), k->layer<const TD>(2, 0), inten);
 	}));
-	BHIP_TRY(bhip_launch_klt_mark_exclude(ctx, k->tab.v, (float)(double)k->scales[0], inten, px, w0, w0, h0, k->ub));
+	BHIP_TRY(bhip_launch_klt_mark_exclude(ctx, k->tab.v, (float)(double)k->scales[0], inten, k->ub));
 	const int step = k->detectRadius + 1;
 	const int rw = std::max(w0 - 2 * k->detectBorder, 0), rh = std::max(h0 - 2 * k->detectBorder, 0);
 	const int cap = step > 0 ? std::max(1, ((rw + step - 1) / step) * ((rh + step - 1) / step)) : 1;   // one maximum per block at most
 	BHIP_TRY(k->candXY.reserve(ctx, (size_t)cap * 4 * k->batch));
 	BHIP_TRY(k->candN.reserve(ctx, (size_t)k->batch * 4));
-	BHIP_TRY(nonmaxDevice(ctx, inten, px, w0, w0, h0, k->batch, k->detectRadius, k->detectThreshold, k->detectBorder, k->candXY.as<int16_t>(), cap,
-						  k->candN.as<int>()));
+	BHIP_TRY(nonmaxDevice(ctx, inten, k->detectRadius, k->detectThreshold, k->detectBorder, k->candXY.as<int16_t>(), cap, k->candN.as<int>()));
 	return kltSpawnFrom(k, k->candXY.as<int16_t>(), cap, k->candN.as<int>());
 }
 

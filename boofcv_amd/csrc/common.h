@@ -6,6 +6,7 @@
 #include <cstring>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include <new>
 #include <utility>
@@ -137,6 +138,7 @@ struct AssocMfmaWork {
 };
 
 // ---------------- image view passed to kernels ----------------
+// Kernel-argument types only (they are in kernel signatures and *Params structs); `data` is typed float whatever the 32-bit element type is
 struct ImgView {
 	const float* data;   // base of image 0 (already offset by startIndex)
 	long long imageStride;  // floats between images of a batch
@@ -160,6 +162,12 @@ struct DevImg {
 	int stride, width, height, batch;
 	operator DevImg<const T>() const { return {data, imageStride, stride, width, height, batch}; }
 };
+// a launcher's kernel argument for a view of 32-bit elements (float, or the int32 of a GrayS32 integral image)
+template <class T>
+static inline ImgView bhip_kernel_view(DevImg<const T> v) {
+	static_assert(sizeof(T) == 4, "ImgView carries 32-bit elements");
+	return {reinterpret_cast<const float*>(v.data), v.imageStride, v.stride, v.width, v.height};
+}
 // `batch` images with rows `pitch` elements apart, packed from the start of `buf`
 template <class T>
 static inline DevImg<T> bhip_img_over(const DevBuf& buf, int pitch, int width, int height, int batch) {
@@ -210,7 +218,9 @@ std::vector<float> bhip_gaussian1d_f32(double sigma, int radius);           // F
 std::vector<int32_t> bhip_gaussian1d_s32(int radius);                       // FactoryKernelGaussian.gaussian(Kernel1D_S32,-1,radius)
 
 // ---------------- kernel launchers (defined in the .hip files) ----------------
-int bhip_launch_integral(bhip_ctx* ctx, ImgView in, ImgViewW out, int batch);
+// An integral image is GrayF32 (from GrayF32 frames) or GrayS32 (from GrayU8 frames): the launchers that read one are templates over its
+// element type T = float / int32_t (instantiated for these two where they are defined), which picks the kernel instantiation.
+int bhip_launch_integral(bhip_ctx* ctx, DevImg<const float> in, DevImg<float> out);
 // levels a fused octave writes out for the next octave (every second pixel, next octave's [image][slot][h][w] layout)
 struct FusedExport {
 	int n;
@@ -228,18 +238,16 @@ struct HessLevelSource {
 	int step;                // 1: src already has this octave's layout, 2: take every second pixel
 	int inPlace;             // src IS this level's output plane (the producer wrote it there): only the pixels that must be recomputed are touched
 };
-int bhip_launch_hessian(bhip_ctx* ctx, ImgView ii, int batch, int skip, int nlevels, const int* sizes, float* intensity, long long levelStride,
-						long long imageStrideOut, int outStride, const HessLevelSource* from = nullptr, bool intTaps = false,
-						unsigned int skipMask = 0);   // skipMask: levels this launch does not produce
+// level0: the octave's intensity planes, level l `levelStride` floats on; from == nullptr: all computed; skipMask: levels this launch does not produce
+template <class T>
+int bhip_launch_hessian(bhip_ctx* ctx, DevImg<const T> ii, int skip, int nlevels, const int* sizes, DevImg<float> level0, long long levelStride,
+						const HessLevelSource* from, unsigned int skipMask);
 
-// describe-kernel options beyond the grey float default (see DescParams): colour SURF bands (nBands > 0), the orientation's object
-// radius factor, integer taps (GrayS32 integral images)
+// colour SURF (see DescParams): the band integral images the descriptor is built from.  nBands == 0: grey SURF, nothing else is read
 struct DescPlanar {
-	const float* data;               // band integral images, [image][band][H][W]
+	const float* data;               // [image][band][H][W]
 	long long imageStride, bandStride;
 	int nBands;
-	double oriRadiusFactor;
-	bool intTaps;
 };
 struct DetectLevelParams {
 	int skip, w, h;              // intensity image size
@@ -248,38 +256,47 @@ struct DetectLevelParams {
 	int nbx, nby;                // blocks in the NMS region
 	unsigned int bitBase;        // first bit of this (octave,level) in the per-image bitmap
 };
-int bhip_launch_nms_scalespace(bhip_ctx* ctx, const float* lower, const float* mid, const float* upper, long long imageStride, int stride, int batch,
-							   DetectLevelParams p, int radius, float threshold, unsigned int* bitmap, int bitmapWords, KeyPoint* cand, int* candCount,
-							   int cap, bool listOnly = false, const ImgView* ii = nullptr, bool intTaps = false);   // lower / upper == nullptr: evaluated on demand from *ii
-int bhip_launch_select_nbest(bhip_ctx* ctx, const float* lower, const float* mid, const float* upper, long long imageStride, int stride, int batch,
-							 DetectLevelParams p, int radius, int target, const unsigned int* bitmap, const unsigned int* prefix, int bitmapWords,
-							 const KeyPoint* nms, int cap, float* keyBuf, int* idxBuf, KeyPoint* out, int* levelStart, int* levelCount, int levelIndex, int nlv);
-int bhip_launch_select_nbest_xy(bhip_ctx* ctx, const float* img, int stride, const int16_t* xy, int n, int target, bool positive, float* key, int* idx,
-								int16_t* out);
+// lower / mid / upper: three levels of one octave (one layout).  lower.data / upper.data == nullptr: that level is evaluated on demand from ii
+template <class T>
+int bhip_launch_nms_scalespace(bhip_ctx* ctx, DevImg<const float> lower, DevImg<const float> mid, DevImg<const float> upper, DetectLevelParams p, int radius,
+							   float threshold, unsigned int* bitmap, int bitmapWords, KeyPoint* cand, int* candCount, int cap, bool listOnly,
+							   DevImg<const T> ii);
+int bhip_launch_select_nbest(bhip_ctx* ctx, DevImg<const float> lower, DevImg<const float> mid, DevImg<const float> upper, DetectLevelParams p, int radius,
+							 int target, const unsigned int* bitmap, const unsigned int* prefix, int bitmapWords, const KeyPoint* nms, int cap, float* keyBuf,
+							 int* idxBuf, KeyPoint* out, int* levelStart, int* levelCount, int levelIndex, int nlv);
+int bhip_launch_select_nbest_xy(bhip_ctx* ctx, DevImg<const float> img, const int16_t* xy, int n, int target, bool positive, float* key, int* idx, int16_t* out);
 int bhip_launch_compact_levels(bhip_ctx* ctx, const KeyPoint* src, int cap, const int* levelStart, const int* levelCount, int nlv, int batch, KeyPoint* dst,
 							   int* totals);
 int bhip_launch_rank_scatter(bhip_ctx* ctx, const unsigned int* bitmap, int bitmapWords, unsigned int* wordPrefix, const KeyPoint* cand,
 							 const int* candCount, int cap, int batch, KeyPoint* sorted);
 int bhip_launch_word_prefix(bhip_ctx* ctx, const unsigned int* bitmap, int bitmapWords, int batch, unsigned int* wordPrefix, int* totals);
 
-int bhip_launch_describe(bhip_ctx* ctx, ImgView ii, const KeyPoint* kps, const int* kpImage /*may be null: use imageOfBlock*/, long long total,
-						 const int* imageStart /*batch+1 prefix of counts*/, int batch, SurfTables t, double* angles, double* desc, uint8_t* white);
-
-int bhip_launch_assoc_l2(bhip_ctx* ctx, const double* src, int ns, const double* dst, int nd, int dof, double maxErr, int backwards, int sqrtScore,
-						 int* pairs, double* fit, DevBuf& work);
-int bhip_launch_assoc_hamming(bhip_ctx* ctx, const int32_t* src, int ns, const int32_t* dst, int nd, int words, double maxErr, int backwards,
-							  int* pairs, double* fit, DevBuf& work);
-
 // describe.hip, detect.hip, associate.hip, assoc_mfma.hip, detect_fused.hip: what only the C ABI layer calls
-int bhip_launch_describe_ex(bhip_ctx* ctx, ImgView ii, const KeyPoint* kps, int cap, const int* imageStart, int batch, int singleImage, long long total,
-							SurfTables t, const double* anglesIn, double* angles, double* desc, uint8_t* white, const int* perm = nullptr, const DescPlanar* planar = nullptr);
+// ii: the grey integral images of the batch.  imageStart == nullptr: kps is a flat list for image `singleImage`; perm: optional processing order
+template <class T>
+int bhip_launch_describe_ex(bhip_ctx* ctx, DevImg<const T> ii, const KeyPoint* kps, int cap, const int* imageStart, int singleImage, long long total,
+							SurfTables t, const double* anglesIn, double* angles, double* desc, uint8_t* white, const int* perm, DescPlanar planar);
 int bhip_launch_kp_spatial_order(bhip_ctx* ctx, const KeyPoint* kps, int cap, const int* start, int batch, int maxCount, int W, int H, int* hist, int* perm);
+// per-split partial records of the association scans (associate.hip's VALU kernels and assoc_ham_mfma.hip write the same ones)
+struct ColTop {
+	double min1, min2;
+	int idx1, pad;
+};
+struct RowBest {
+	double best;
+	int idx, pad;
+};
 int bhip_assoc_phase1_l2(bhip_ctx* ctx, const double* src, int nsLocal, int srcBegin, const double* dst, int nd, int dof, double maxErr, int sqrtScore,
 						 int* pairs, double* fit, void* colTop, DevBuf& work);
 int bhip_assoc_phase1_ham(bhip_ctx* ctx, const int32_t* src, int nsLocal, int srcBegin, const int32_t* dst, int nd, int words, double maxErr, int* pairs,
 						  double* fit, void* colTop, DevBuf& work);
 int bhip_assoc_phase2(bhip_ctx* ctx, const void* colAll, int nranks, int nd, int nsLocal, int srcBegin, int* pairs, double* fit);
 int bhip_assoc_coltop_size();
+// int8 MFMA Hamming path (assoc_ham_mfma.hip), called by associate.hip
+int bhip_ham_expand(bhip_ctx* ctx, const int* D, long long rows, int words, unsigned char* bytes, int* pop);
+int bhip_ham_mfma_splits(int nU, int nV);
+int bhip_ham_mfma_scan(bhip_ctx* ctx, bool colMode, const unsigned char* Ub, const int* Up, int nU, const unsigned char* Vb, const int* Vp, int nV, int words,
+						 int vBase, double maxErr, void* partial, int splits);
 int bhip_assoc_hamming_batched(bhip_ctx* ctx, const int32_t* src, const int32_t* dst, int words, int count, const long long* srcOff, const int* ns,
 							   const long long* dstOff, const int* nd, double maxErr, int backwards, int* pairs, double* fit, DevBuf& work);
 
@@ -289,9 +306,10 @@ int bhip_assoc_l2_mfma_batched(bhip_ctx* ctx, AssocMfmaWork& W, const double* de
 
 bool bhip_fused_plan(int skip, int nlevels, const int* sizes, int radius, int* TX, int* TY, int* ldsBytes);
 bool bhip_fused_is_fixed(int skip, int nlevels, const int* sizes, int radius);
-int bhip_launch_detect_fused(bhip_ctx* ctx, ImgView ii, int batch, int skip, int nlevels, const int* sizes, int nmid, const DetectLevelParams* mids,
+template <class T>
+int bhip_launch_detect_fused(bhip_ctx* ctx, DevImg<const T> ii, int skip, int nlevels, const int* sizes, int nmid, const DetectLevelParams* mids,
 							 const int* midLevels, int radius, float threshold, unsigned int* bitmap, int bitmapWords, KeyPoint* cand, int* candCount,
-							 int cap, const FusedExport* exp, bool intTaps = false);
+							 int cap, const FusedExport* exp);
 
 // ---------------- boofcv-ip front end (ip.hip) ----------------
 // Images arrive as DevImg views.  Where the images of a call share one shape, width, height and batch are read from the first view; dx / dy
@@ -333,8 +351,8 @@ int bhip_launch_mean(bhip_ctx* ctx, bool vertical, DevImg<const float> in, DevIm
 int bhip_launch_median(bhip_ctx* ctx, DevImg<const float> in, DevImg<float> out, int radius);
 int bhip_launch_integral_u8(bhip_ctx* ctx, DevImg<const uint8_t> in, DevImg<int32_t> out);   // IntegralImageOps.transform(GrayU8, GrayS32)
 // stand-alone strict block NMS over a batch (detect.hip): bitmap of accepted blocks + the pixel's position inside its block
-int bhip_launch_nonmax_blocks(bhip_ctx* ctx, const float* img, long long imageStride, int stride, int w, int h, int batch, int radius, float threshold, int border,
-							  unsigned int* bitmap, int bitmapWords, unsigned short* posInBlock, int nbx, int nby);
+int bhip_launch_nonmax_blocks(bhip_ctx* ctx, DevImg<const float> img, int radius, float threshold, int border, unsigned int* bitmap, int bitmapWords,
+							  unsigned short* posInBlock, int nbx, int nby);
 int bhip_launch_blocks_to_xy(bhip_ctx* ctx, const unsigned int* bitmap, const unsigned int* wordPrefix, int bitmapWords, const unsigned short* posInBlock,
 							 int nbx, int nby, int batch, int radius, int border, int16_t* xy, int cap);
 
@@ -389,7 +407,7 @@ int bhip_launch_klt_describe(bhip_ctx* ctx, KltPyr P, KltTab T, bhip_klt_cfg cfg
 int bhip_launch_klt_track(bhip_ctx* ctx, KltPyrU8 P, KltTab T, bhip_klt_cfg cfg, int maxActive);
 int bhip_launch_klt_describe(bhip_ctx* ctx, KltPyrU8 P, KltTab T, bhip_klt_cfg cfg, int mode, const int* count, int maxCount);
 int bhip_launch_klt_compact(bhip_ctx* ctx, KltTab T, int toUnused);   // active := kept tracks in order; the others go to dropped (or straight to unused)
-int bhip_launch_klt_mark_exclude(bhip_ctx* ctx, KltTab T, float scale0, float* intensity, long long imageStride, int stride, int w, int h, int maxActive);
+int bhip_launch_klt_mark_exclude(bhip_ctx* ctx, KltTab T, float scale0, DevImg<float> intensity, int maxActive);
 int bhip_launch_klt_spawn_place(bhip_ctx* ctx, KltTab T, const int16_t* xy, int xyCap, const int* count, float scale0, int maxCount);
 int bhip_launch_klt_spawn_commit(bhip_ctx* ctx, KltTab T, const int* count);
 int bhip_launch_klt_add(bhip_ctx* ctx, KltTab T, const int* seq, const double* xy, int n, int frameW, int frameH, unsigned char* ok, int* list);

@@ -1274,20 +1274,19 @@ int bhip_describe_lds_bytes(const SurfTables& t, int nBands) {
 	return (b + 15) & ~15;
 }
 
-int bhip_launch_describe_ex(bhip_ctx* ctx, ImgView ii, const KeyPoint* kps, int cap, const int* imageStart, int batch, int singleImage, long long total,
-							SurfTables t, const double* anglesIn, double* angles, double* desc, uint8_t* white, const int* perm, const DescPlanar* planar) {
+template <class T>
+int bhip_launch_describe_ex(bhip_ctx* ctx, DevImg<const T> ii, const KeyPoint* kps, int cap, const int* imageStart, int singleImage, long long total,
+							SurfTables t, const double* anglesIn, double* angles, double* desc, uint8_t* white, const int* perm, DescPlanar planar) {
 	if (total <= 0) return BHIP_OK;
 	DescParams P;
-	P.ii = ii; P.kps = kps; P.cap = cap; P.imageStart = imageStart; P.batch = batch; P.singleImage = singleImage; P.total = total; P.t = t;
+	P.ii = bhip_kernel_view(ii); P.kps = kps; P.cap = cap; P.imageStart = imageStart; P.batch = ii.batch; P.singleImage = singleImage; P.total = total; P.t = t;
 	P.anglesIn = anglesIn; P.angles = angles; P.desc = desc; P.white = white; P.perm = perm;
-	P.bandData = nullptr; P.bandImageStride = P.bandStride = 0; P.nBands = 0; P.oriRadiusFactor = 2.0;
-	if (planar) {
-		if (planar->nBands > 0) {
-			if (!planar->data) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad planar description request");
-			P.bandData = planar->data; P.bandImageStride = planar->imageStride; P.bandStride = planar->bandStride; P.nBands = planar->nBands;
-		}
-		P.oriRadiusFactor = planar->oriRadiusFactor;
+	P.bandData = nullptr; P.bandImageStride = P.bandStride = 0; P.nBands = 0;
+	if (planar.nBands > 0) {
+		if (!planar.data) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad planar description request");
+		P.bandData = planar.data; P.bandImageStride = planar.imageStride; P.bandStride = planar.bandStride; P.nBands = planar.nBands;
 	}
+	P.oriRadiusFactor = planar.nBands > 0 ? 1.0 : 2.0;
 	P.ldsPerWave = bhip_describe_lds_bytes(t, P.nBands);
 	P.stamps = nullptr;
 	P.serialOnly = bhip_env_flag("BHIP_DESCRIBE_SERIAL") ? 1 : 0;   // parity cross-checks of the two window sweeps / the two sort keys
@@ -1304,7 +1303,7 @@ int bhip_launch_describe_ex(bhip_ctx* ctx, ImgView ii, const KeyPoint* kps, int 
 	if ((long long)ii.stride * ii.height > 0x3fffffffLL || ii.stride >= (1 << 17)) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "integral image too large for 32-bit tap offsets");
 #ifdef BHIP_EXPERIMENTS
 	const char* stampPath = getenv("BHIP_DESCRIBE_STAMPS");
-	if (stampPath && total > 1000 && !(planar && planar->intTaps)) {
+	if (stampPath && total > 1000 && std::is_same<T, float>::value) {
 		// diagnostic build: phase shares of the describe kernel (never a quoted run time)
 		unsigned long long* dev = nullptr;
 		if (hipMalloc(&dev, (size_t)total * 128) == hipSuccess) {
@@ -1357,7 +1356,8 @@ int bhip_launch_describe_ex(bhip_ctx* ctx, ImgView ii, const KeyPoint* kps, int 
 #endif
 		// default configurations get compile-time sizes (CFG 1 / 2); anything else runs the generic instantiations
 		const bool cfgStable = bhip_describe_default_cfg(t) == 1, cfgFast = bhip_describe_default_cfg(t) == 2;
-		const bool ints = planar && planar->intTaps;   // GrayS32 integral image(s)
+		// (both tap types are named whatever T is: the kernels keep their places in the code object)
+		constexpr bool ints = std::is_same<T, int32_t>::value;   // GrayS32 integral image(s)
 		const void* fn;
 		if (cfgStable) fn = ints ? (const void*)k_describe<false, 5, 9, int, 1> : (const void*)k_describe<false, 5, 9, float, 1>;
 		else if (cfgFast) fn = ints ? (const void*)k_describe<false, 3, 5, int, 2> : (const void*)k_describe<false, 3, 5, float, 2>;
@@ -1410,3 +1410,5 @@ int bhip_launch_describe_ex(bhip_ctx* ctx, ImgView ii, const KeyPoint* kps, int 
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
 }
+template int bhip_launch_describe_ex(bhip_ctx*, DevImg<const float>, const KeyPoint*, int, const int*, int, long long, SurfTables, const double*, double*, double*,  uint8_t*, const int*, DescPlanar);
+template int bhip_launch_describe_ex(bhip_ctx*, DevImg<const int32_t>, const KeyPoint*, int, const int*, int, long long, SurfTables, const double*, double*, double*,  uint8_t*, const int*, DescPlanar);

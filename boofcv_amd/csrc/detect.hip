@@ -264,20 +264,22 @@ __global__ __launch_bounds__(256) void k_nms_scalespace(NmsParams P) {
 	}
 }
 
-int bhip_launch_nms_scalespace(bhip_ctx* ctx, const float* lower, const float* mid, const float* upper, long long imageStride, int stride, int batch,
-							   DetectLevelParams p, int radius, float threshold, unsigned int* bitmap, int bitmapWords, KeyPoint* cand, int* candCount,
-							   int cap, bool listOnly, const ImgView* ii, bool intTaps) {
+template <class T>
+int bhip_launch_nms_scalespace(bhip_ctx* ctx, DevImg<const float> lower, DevImg<const float> mid, DevImg<const float> upper, DetectLevelParams p, int radius,
+							   float threshold, unsigned int* bitmap, int bitmapWords, KeyPoint* cand, int* candCount, int cap, bool listOnly,
+							   DevImg<const T> ii) {
 	const int rw = p.w - 2 * p.border, rh = p.h - 2 * p.border;
 	if (rw <= 0 || rh <= 0) return BHIP_OK;
-	NmsParams P{lower, mid, upper, imageStride, stride, p, radius, threshold, bitmap, bitmapWords, cand, candCount, cap, listOnly ? 1 : 0, {}};
+	const int batch = mid.batch;
+	NmsParams P{lower.data, mid.data, upper.data, mid.imageStride, mid.stride, p, radius, threshold, bitmap, bitmapWords, cand, candCount, cap, listOnly ? 1 : 0, {}};
 	P.virt.lower.on = P.virt.upper.on = 0;
-	P.virt.intTaps = intTaps ? 1 : 0;
-	if (!lower || !upper) {
+	P.virt.intTaps = std::is_same<T, int32_t>::value ? 1 : 0;
+	if (!lower.data || !upper.data) {
 		// an outer level that was not computed: evaluated on demand from the integral image
-		if (!ii || listOnly) return bhip_fail(ctx, BHIP_ERR_INVALID, "a level that is not in memory needs the integral image");
-		P.virt.ii = *ii;
-		if (!lower) { P.virt.lower.on = 1; P.virt.lower.L = bhipMakeHessLevel(p.sizeLower, p.skip); }
-		if (!upper) { P.virt.upper.on = 1; P.virt.upper.L = bhipMakeHessLevel(p.sizeUpper, p.skip); }
+		if (!ii.data || listOnly) return bhip_fail(ctx, BHIP_ERR_INVALID, "a level that is not in memory needs the integral image");
+		P.virt.ii = bhip_kernel_view(ii);
+		if (!lower.data) { P.virt.lower.on = 1; P.virt.lower.L = bhipMakeHessLevel(p.sizeLower, p.skip); }
+		if (!upper.data) { P.virt.upper.on = 1; P.virt.upper.L = bhipMakeHessLevel(p.sizeUpper, p.skip); }
 	}
 	dim3 grid((rw + 255) / 256, (rh + NMS_ROWS - 1) / NMS_ROWS, batch);
 	{
@@ -287,6 +289,10 @@ int bhip_launch_nms_scalespace(bhip_ctx* ctx, const float* lower, const float* m
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
 }
+template int bhip_launch_nms_scalespace(bhip_ctx*, DevImg<const float>, DevImg<const float>, DevImg<const float>, DetectLevelParams, int, float, unsigned int*, int,
+										KeyPoint*, int*, int, bool, DevImg<const float>);
+template int bhip_launch_nms_scalespace(bhip_ctx*, DevImg<const float>, DevImg<const float>, DevImg<const float>, DetectLevelParams, int, float, unsigned int*, int,
+										KeyPoint*, int*, int, bool, DevImg<const int32_t>);
 
 // ---- exclusive prefix of per-word popcounts: one workgroup per image ----
 __global__ __launch_bounds__(1024) void k_word_prefix(const unsigned int* __restrict__ bitmap, int words, unsigned int* __restrict__ prefix, int* __restrict__ totals) {
@@ -493,15 +499,15 @@ __global__ __launch_bounds__(64) void k_compact_levels(const KeyPoint* __restric
 	if (lane == 0) totals[img] = off;
 }
 
-int bhip_launch_select_nbest(bhip_ctx* ctx, const float* lower, const float* mid, const float* upper, long long imageStride, int stride, int batch,
-							 DetectLevelParams p, int radius, int target, const unsigned int* bitmap, const unsigned int* prefix, int bitmapWords,
-							 const KeyPoint* nms, int cap, float* keyBuf, int* idxBuf, KeyPoint* out, int* levelStart, int* levelCount, int levelIndex, int nlv) {
-	if (batch <= 0) return BHIP_OK;
-	SelectParams P{lower, mid, upper, imageStride, stride, p, radius, target, bitmap, prefix, bitmapWords, nms, cap, keyBuf, idxBuf, out, levelStart, levelCount,
-				   levelIndex, nlv};
+int bhip_launch_select_nbest(bhip_ctx* ctx, DevImg<const float> lower, DevImg<const float> mid, DevImg<const float> upper, DetectLevelParams p, int radius,
+							 int target, const unsigned int* bitmap, const unsigned int* prefix, int bitmapWords, const KeyPoint* nms, int cap, float* keyBuf,
+							 int* idxBuf, KeyPoint* out, int* levelStart, int* levelCount, int levelIndex, int nlv) {
+	if (mid.batch <= 0) return BHIP_OK;
+	SelectParams P{lower.data, mid.data, upper.data, mid.imageStride, mid.stride, p, radius, target, bitmap, prefix, bitmapWords, nms, cap, keyBuf, idxBuf, out,
+				   levelStart, levelCount, levelIndex, nlv};
 	{
 		ProfScope ps(ctx, "k_select_nbest");
-		hipLaunchKernelGGL(k_select_nbest, dim3(batch), dim3(64), 0, ctx->stream, P);
+		hipLaunchKernelGGL(k_select_nbest, dim3(mid.batch), dim3(64), 0, ctx->stream, P);
 	}
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
@@ -539,9 +545,8 @@ __global__ __launch_bounds__(64) void k_select_nbest_xy(const float* __restrict_
 	}
 }
 
-int bhip_launch_select_nbest_xy(bhip_ctx* ctx, const float* img, int stride, const int16_t* xy, int n, int target, bool positive, float* key, int* idx,
-								int16_t* out) {
-	hipLaunchKernelGGL(k_select_nbest_xy, dim3(1), dim3(64), 0, ctx->stream, img, stride, xy, n, target, positive ? 1 : 0, key, idx, out);
+int bhip_launch_select_nbest_xy(bhip_ctx* ctx, DevImg<const float> img, const int16_t* xy, int n, int target, bool positive, float* key, int* idx, int16_t* out) {
+	hipLaunchKernelGGL(k_select_nbest_xy, dim3(1), dim3(64), 0, ctx->stream, img.data, img.stride, xy, n, target, positive ? 1 : 0, key, idx, out);
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
 }
@@ -606,12 +611,13 @@ __global__ __launch_bounds__(256) void k_nonmax_blocks(NonmaxParams P) {
 	}
 }
 
-int bhip_launch_nonmax_blocks(bhip_ctx* ctx, const float* img, long long imageStride, int stride, int w, int h, int batch, int radius, float threshold, int border,
-							  unsigned int* bitmap, int bitmapWords, unsigned short* posInBlock, int nbx, int nby) {
+int bhip_launch_nonmax_blocks(bhip_ctx* ctx, DevImg<const float> img, int radius, float threshold, int border, unsigned int* bitmap, int bitmapWords,
+							  unsigned short* posInBlock, int nbx, int nby) {
+	const int w = img.width, h = img.height, batch = img.batch;
 	const int rw = w - 2 * border, rh = h - 2 * border;
 	if (rw <= 0 || rh <= 0 || batch <= 0) return BHIP_OK;
 	if (radius > 254) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "NMS radius too large");
-	NonmaxParams P{img, imageStride, stride, w, h, radius, border, nbx, bitmapWords, threshold, bitmap, posInBlock, (long long)nbx * nby};
+	NonmaxParams P{img.data, img.imageStride, img.stride, w, h, radius, border, nbx, bitmapWords, threshold, bitmap, posInBlock, (long long)nbx * nby};
 	dim3 grid((rw + 255) / 256, (rh + NMS_ROWS - 1) / NMS_ROWS, batch);
 	{
 		ProfScope ps(ctx, "k_nonmax_blocks", 4.0 * w * h * batch);

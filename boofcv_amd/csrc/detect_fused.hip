@@ -820,13 +820,16 @@ bool bhip_fused_is_fixed(int skip, int nlevels, const int* sizes, int radius) {
 	return (skip == 1 && sizes[0] == 9 && step == 6) || (skip == 2 && sizes[0] == 15 && step == 12);
 }
 
-int bhip_launch_detect_fused(bhip_ctx* ctx, ImgView ii, int batch, int skip, int nlevels, const int* sizes, int nmid, const DetectLevelParams* mids,
+template <class T>
+int bhip_launch_detect_fused(bhip_ctx* ctx, DevImg<const T> ii, int skip, int nlevels, const int* sizes, int nmid, const DetectLevelParams* mids,
 							 const int* midLevels, int radius, float threshold, unsigned int* bitmap, int bitmapWords, KeyPoint* cand, int* candCount,
-							 int cap, const FusedExport* exp, bool intTaps) {
+							 int cap, const FusedExport* exp) {
 	FusedParams P;
 	int TX, TY, lds;
 	if (!bhip_fused_plan(skip, nlevels, sizes, radius, &TX, &TY, &lds)) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "octave does not fit the fused tile");
-	P.ii = ii; P.skip = skip; P.w = ii.width / skip; P.h = ii.height / skip; P.nlevels = nlevels;
+	const int batch = ii.batch;
+	constexpr bool ints = std::is_same<T, int32_t>::value;   // (both tap types are named below whatever T is: the kernels keep their places in the code object)
+	P.ii = bhip_kernel_view(ii); P.skip = skip; P.w = ii.width / skip; P.h = ii.height / skip; P.nlevels = nlevels;
 	if (P.w <= 0 || P.h <= 0 || nmid <= 0) return BHIP_OK;
 	int rFmax = 0;
 	for (int i = 0; i < nlevels; i++) {
@@ -882,7 +885,7 @@ int bhip_launch_detect_fused(bhip_ctx* ctx, ImgView ii, int batch, int skip, int
 		if (nt > 0x7ffffff0LL) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "batch too large for one fused-octave launch");             \
 		dim3 g((unsigned)(((nt + 7) >> 3) << 3));                                                                                      \
 		const size_t ldsB = (size_t)G::ldsFloats * 4;                                                                                  \
-		if (intTaps) {                                                                                                                 \
+		if (ints) {                                                                                                                    \
 			if (ldsB > 65536) BHIP_HIP(ctx, hipFuncSetAttribute((const void*)k_detect_fused_fixed<int, SK, S0, ST, 4, 2, ITWV, TYV, NTV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsB)); \
 			hipLaunchKernelGGL((k_detect_fused_fixed<int, SK, S0, ST, 4, 2, ITWV, TYV, NTV>), g, dim3(NTV), ldsB, ctx->stream, P);      \
 		} else {                                                                                                                       \
@@ -917,7 +920,7 @@ int bhip_launch_detect_fused(bhip_ctx* ctx, ImgView ii, int batch, int skip, int
 #undef LAUNCH_FIXED
 		}
 		if (!launched) {
-			if (intTaps) return bhip_fail(ctx, BHIP_ERR_INVALID, "integer taps need the fixed-geometry fused kernel");
+			if (ints) return bhip_fail(ctx, BHIP_ERR_INVALID, "integer taps need the fixed-geometry fused kernel");
 			if (P.nexp > 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "level export needs the fixed-geometry fused kernel");
 			hipLaunchKernelGGL(k_detect_fused, grid, dim3(256), (size_t)lds, ctx->stream, P);
 		}
@@ -925,3 +928,5 @@ int bhip_launch_detect_fused(bhip_ctx* ctx, ImgView ii, int batch, int skip, int
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
 }
+template int bhip_launch_detect_fused(bhip_ctx*, DevImg<const int32_t>, int, int, const int*, int, const DetectLevelParams*, const int*, int, float, unsigned int*, int,   KeyPoint*, int*, int, const FusedExport*);
+template int bhip_launch_detect_fused(bhip_ctx*, DevImg<const float>, int, int, const int*, int, const DetectLevelParams*, const int*, int, float, unsigned int*, int,   KeyPoint*, int*, int, const FusedExport*);

@@ -53,19 +53,18 @@ __global__ __launch_bounds__(256) void k_hessian(HessParams P) {
 		hessianCompute<T>(d, P.ii.stride, P.ii.width, P.ii.height, L, P.skip, P.w, P.h, x, y);
 }
 
-int bhip_launch_hessian(bhip_ctx* ctx, ImgView ii, int batch, int skip, int nlevels, const int* sizes, float* intensity, long long levelStride,
-						long long imageStrideOut, int outStride, const HessLevelSource* from, bool intTaps, unsigned int skipMask) {
+template <class T>
+int bhip_launch_hessian(bhip_ctx* ctx, DevImg<const T> ii, int skip, int nlevels, const int* sizes, DevImg<float> level0, long long levelStride,
+						const HessLevelSource* from, unsigned int skipMask) {
 	if (nlevels > BHIP_MAX_LEVELS) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "too many scales per octave");
+	const int batch = ii.batch;
 	HessParams P;
-	P.ii = ii;
+	P.ii = bhip_kernel_view(ii);
 	P.skip = skip;
 	P.w = ii.width / skip;
 	P.h = ii.height / skip;
 	P.nlevels = nlevels;
-	P.out = intensity;
-	P.levelStride = levelStride;
-	P.imageStrideOut = imageStrideOut;
-	P.outStride = outStride;
+	P.out = level0.data; P.levelStride = levelStride; P.imageStrideOut = level0.imageStride; P.outStride = level0.stride;
 	for (int i = 0; i < nlevels; i++) {
 		P.lv[i] = bhipMakeHessLevel(sizes[i], skip);
 		P.from[i] = from ? from[i] : HessLevelSource{nullptr, 0, 0, 1, 0};
@@ -86,9 +85,10 @@ int bhip_launch_hessian(bhip_ctx* ctx, ImgView ii, int batch, int skip, int nlev
 		// algorithmic bytes: the integral image once + every level's intensity written once
 		const double bytes = 4.0 * ii.width * ii.height * batch + 4.0 * P.nrun * (double)P.w * P.h * batch;
 		ProfScope ps(ctx, skip == 1 ? "k_hessian_skip1" : "k_hessian_skipN", bytes);
-		if (intTaps) hipLaunchKernelGGL(k_hessian<int>, grid, dim3(256), 0, ctx->stream, P);
-		else hipLaunchKernelGGL(k_hessian<float>, grid, dim3(256), 0, ctx->stream, P);
+		hipLaunchKernelGGL(k_hessian<T>, grid, dim3(256), 0, ctx->stream, P);
 	}
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
 }
+template int bhip_launch_hessian(bhip_ctx*, DevImg<const int32_t>, int, int, const int*, DevImg<float>, long long, const HessLevelSource*, unsigned int);
+template int bhip_launch_hessian(bhip_ctx*, DevImg<const float>, int, int, const int*, DevImg<float>, long long, const HessLevelSource*, unsigned int);

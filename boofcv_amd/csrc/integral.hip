@@ -327,7 +327,10 @@ static int fusedBandHeight(int H) {
 	return best;
 }
 
-int bhip_launch_integral(bhip_ctx* ctx, ImgView in, ImgViewW out, int batch) {
+int bhip_launch_integral(bhip_ctx* ctx, DevImg<const float> src, DevImg<float> dst) {
+	const ImgView in = bhip_kernel_view(src);
+	const ImgViewW out{dst.data, dst.imageStride, dst.stride, dst.width, dst.height};
+	const int batch = src.batch;
 	if (in.width <= 0 || in.height <= 0 || batch <= 0) return BHIP_OK;
 	const bool twoPass = bhip_env_flag("BHIP_INTEGRAL_TWO_PASS");   // parity cross-check of the two integral plans
 	// one workgroup per image only fills the chip with a large batch; small batches keep the two streaming passes

@@ -598,9 +598,10 @@ int bhip_launch_klt_compact(bhip_ctx* ctx, KltTab T, int toUnused) {
 	hipLaunchKernelGGL(k_klt_compact, dim3(T.batch), dim3(256), 0, ctx->stream, T, toUnused);
 	KLT_DONE(ctx);
 }
-int bhip_launch_klt_mark_exclude(bhip_ctx* ctx, KltTab T, float scale0, float* intensity, long long imageStride, int stride, int w, int h, int maxActive) {
+int bhip_launch_klt_mark_exclude(bhip_ctx* ctx, KltTab T, float scale0, DevImg<float> intensity, int maxActive) {
 	if (maxActive <= 0) return BHIP_OK;
-	hipLaunchKernelGGL(k_klt_mark_exclude, dim3((maxActive + 255) / 256, T.batch), dim3(256), 0, ctx->stream, T, scale0, intensity, imageStride, stride, w, h);
+	hipLaunchKernelGGL(k_klt_mark_exclude, dim3((maxActive + 255) / 256, T.batch), dim3(256), 0, ctx->stream, T, scale0, intensity.data, intensity.imageStride,
+					   intensity.stride, intensity.width, intensity.height);
 	KLT_DONE(ctx);
 }
 int bhip_launch_klt_spawn_place(bhip_ctx* ctx, KltTab T, const int16_t* xy, int xyCap, const int* count, float scale0, int maxCount) {

@@ -1389,3 +1389,38 @@ def test_chunked_host_batch_equals_plain(api, orc, tmp_path, u8):
         rp = ref.fetch()
         s0, s1 = int(base[4][3]), int(base[4][4])
         assert np.array_equal(base[0][s0:s1], rp[0]) and np.array_equal(base[2][s0:s1], rp[2])
+
+
+@pytest.mark.parametrize("batch", [3, 130])
+@pytest.mark.parametrize("kind", ["surfStable", "brief"])
+def test_detect_device_padded_rows_equals_dense_host_batch(api, orc, kind, batch):
+    """bhip_surf_detect_dev_f32 on a device batch whose rows and images are padded (160x120 frames, row stride 176, image stride 176*125,
+    every padding element 1e6) gives, array for array, what detectBatch gives on the same frames as dense host images -- for a surfStable
+    object and for Fast-Hessian + BRIEF (key points and words; BRIEF samples the strided frames themselves).  130 frames are above the
+    single-pass integral kernel's batch threshold (128), so that kernel reads the strided input too."""
+    torch = pytest.importorskip("torch")
+    w, h, stride, rows = 160, 120, 176, 125
+    base = [orc.noise_image(w, h, 234 + k) for k in range(5)]
+    idx = [k % 5 for k in range(batch)]
+
+    def make(ctx=None):
+        if kind == "surfStable":
+            return api.FactoryDetectDescribe.surfStable(None, None, None, api.GrayF32, ctx=ctx)
+        brief = api.FactoryDescribeRegionPoint.brief(None, api.GrayF32, ctx=ctx)
+        return api.FactoryDetectDescribe.fuseTogether(api.FactoryInterestPoint.fastHessian(None), None, brief, ctx=ctx)
+
+    host = make()
+    host.detectBatch([G(api, base[k]) for k in idx])
+    want = host.fetchAll()
+    padded = np.full((batch, rows, stride), 1e6, dtype=np.float32)
+    for b, k in enumerate(idx):
+        padded[b, :h, :w] = base[k].array()
+    frames = torch.from_numpy(padded).cuda()
+    ctx = api.Context(0, stream=torch.cuda.current_stream(0).cuda_stream)
+    dev = make(ctx)
+    dev.detectDevice(frames.data_ptr(), stride * rows, stride, w, h, batch)
+    got = dev.fetchAll()
+    assert len(got) == len(want) and want[-1][-1] > 20 * batch
+    for k, (a, b) in enumerate(zip(got, want)):
+        assert np.array_equal(a, b), (kind, batch, k)
+    dev.close(); ctx.close()
