@@ -84,6 +84,9 @@ SIGNATURES = {
     "bhip_integral_f32": (_i, [_vp, _fp, _i, _i, _i, _i, _fp, _i, _i]),
     "bhip_hessian_f32": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _i, _fp, _i, _i]),
     "bhip_nonmax_block_f32": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _f, _i, _i16p, _i, _ip]),
+    "bhip_nonmax_block_minmax_f32": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _f, _f, _i, _i, _i, _i16p, _ip, _i16p, _ip, _i]),
+    "bhip_fast_u8": (_i, [_vp, _u8p, _i, _i, _i, _i, _i, _i, _d, _fp, _i, _i, _i16p, _ip, _i16p, _ip, _i]),
+    "bhip_fast_f32": (_i, [_vp, _fp, _i, _i, _i, _i, _f, _i, _d, _fp, _i, _i, _i16p, _ip, _i16p, _ip, _i]),
     "bhip_select_nbest_f32": (_i, [_vp, _fp, _i, _i, _i, _i, _i16p, _i, _i, _i, _i16p, _ip]),
     "bhip_fh_detect_f32": (_i, [_vp, P(FhCfg), _fp, _i, _i, _i, _i, _dp, _i, _ip]),
     "bhip_assoc_l2_f64": (_i, [_vp, _dp, _i, _dp, _i, _i, _d, _i, _i, _ip, _dp]),
@@ -132,6 +135,9 @@ SIGNATURES = {
     "bhip_three_dev_f32": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _vp, _vp, _ll, _i, _i]),
     "bhip_gradient_intensity_dev_f32": (_i, [_vp, _i, _vp, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i]),
     "bhip_nonmax_block_dev_f32": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _i, _vp, _i, _vp]),
+    "bhip_nonmax_block_minmax_dev_f32": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _i]),
+    "bhip_fast_dev_u8": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _d, _vp, _ll, _i, _vp, _vp, _vp, _vp, _i]),
+    "bhip_fast_dev_f32": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _f, _i, _d, _vp, _ll, _i, _vp, _vp, _vp, _vp, _i]),
     "bhip_corner_intensity_dev_f32": (_i, [_vp, _i, _i, _f, _vp, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i]),
     "bhip_sobel_dev_u8_s16": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _vp, _vp, _ll, _i, _i]),
     "bhip_three_dev_u8_s16": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _vp, _vp, _ll, _i, _i]),

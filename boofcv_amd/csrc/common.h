@@ -355,6 +355,21 @@ int bhip_launch_nonmax_blocks(bhip_ctx* ctx, DevImg<const float> img, int radius
 							  unsigned short* posInBlock, int nbx, int nby);
 int bhip_launch_blocks_to_xy(bhip_ctx* ctx, const unsigned int* bitmap, const unsigned int* wordPrefix, int bitmapWords, const unsigned short* posInBlock,
 							 int nbx, int nby, int batch, int radius, int border, int16_t* xy, int cap);
+// the minima half (NonMaxBlockSearchStrict.Min): same outputs as bhip_launch_nonmax_blocks, into buffers of its own
+int bhip_launch_nonmin_blocks(bhip_ctx* ctx, DevImg<const float> img, int radius, float threshold, int border, unsigned int* bitmap, int bitmapWords,
+							  unsigned short* posInBlock, int nbx, int nby);
+
+// ---------------- FAST corner detector (fast.hip) ----------------
+template <class T> struct FastTol;   // ImplFastHelper_U8 / _F32: the type of pixelTol and of the pixel arithmetic
+template <> struct FastTol<uint8_t> { using type = int; };
+template <> struct FastTol<float> { using type = float; };
+size_t bhip_fast_scratch(int width, int height, int batch);   // bytes of device scratch one bhip_launch_fast call needs
+// FastCornerDetector.process(image, intensity) on every frame of a batch (inten.data == nullptr: process(image)).  maxFeatures: the
+// reference's (int)(maxFeaturesFraction * width * height).  Frame b's dark / bright corners go to xyLow / xyHigh[b * cap ...] in raster
+// order, their numbers to nLow / nHigh[b] (they may exceed cap: only the first cap pairs are written)
+template <class T>
+int bhip_launch_fast(bhip_ctx* ctx, DevImg<const T> img, typename FastTol<T>::type tol, int minContinuous, int maxFeatures, DevImg<float> inten, void* scratch,
+					 int16_t* xyLow, int* nLow, int16_t* xyHigh, int* nHigh, int cap);
 
 // ---------------- pyramid KLT tracker (klt.hip) ----------------
 #define BHIP_KLT_MAX_LAYERS 8

@@ -17,9 +17,15 @@
 
 // strict-maximum test of NonMaxBlockSearchStrict.Max for pixel (x,y) with value v.  The window is read without early exits so the
 // loads are independent (a branch per load turns the window into a chain of dependent memory round trips).
-template <int RT>   // RT > 0: compile-time radius, fully unrolled; RT == 0: run-time radius r
+// MIN: NonMaxBlockSearchStrict.Min's test, the mirror image -- v <= thresholdMin, v != -Float.MAX_VALUE, no other window pixel <= v, and
+// +INFINITY outside the image.  The pixels are compared as they are loaded (a negation behind each guarded load would make the loads wait
+// for one another).
+template <bool MIN> __device__ __forceinline__ bool nmsBeats(float a, float b) { return MIN ? a <= b : a >= b; }   // a keeps b from being the strict extremum
+template <bool MIN> __device__ __forceinline__ float nmsPad() { return MIN ? INFINITY : -INFINITY; }
+template <bool MIN> __device__ __forceinline__ float nmsMarker() { return MIN ? -FLT_MAX : FLT_MAX; }
+template <int RT, bool MIN = false>   // RT > 0: compile-time radius, fully unrolled; RT == 0: run-time radius r
 __device__ __forceinline__ bool strictLocalMax(const float* __restrict__ img, int stride, int w, int h, int x, int y, int r, float v, float thr) {
-	if (!(v >= thr) || v == FLT_MAX) return false;
+	if (!nmsBeats<MIN>(v, thr) || v == nmsMarker<MIN>()) return false;
 	bool isMax = true;
 	if (RT > 0) {
 		float nb[(2 * RT + 1) * (2 * RT + 1)];
@@ -29,17 +35,17 @@ __device__ __forceinline__ bool strictLocalMax(const float* __restrict__ img, in
 			for (int i = -RT; i <= RT; i++) {
 				const int xx = x + i, yy = y + j;
 				const bool in = xx >= 0 && xx < w && yy >= 0 && yy < h && !(i == 0 && j == 0);
-				nb[(j + RT) * (2 * RT + 1) + i + RT] = in ? img[(long long)yy * stride + xx] : -INFINITY;
+				nb[(j + RT) * (2 * RT + 1) + i + RT] = in ? img[(long long)yy * stride + xx] : nmsPad<MIN>();
 			}
 #pragma unroll
 		for (int k = 0; k < (2 * RT + 1) * (2 * RT + 1); k++)
-			if (nb[k] >= v) isMax = false;
+			if (nmsBeats<MIN>(nb[k], v)) isMax = false;
 	} else {
 		const int x0 = max(x - r, 0), x1 = min(x + r, w - 1), y0 = max(y - r, 0), y1 = min(y + r, h - 1);
 		for (int j = y0; j <= y1; j++) {
 			const float* row = img + (long long)j * stride;
 			for (int i = x0; i <= x1; i++)
-				if (row[i] >= v && !(i == x && j == y)) isMax = false;
+				if (nmsBeats<MIN>(row[i], v) && !(i == x && j == y)) isMax = false;
 		}
 	}
 	return isMax;
@@ -564,6 +570,7 @@ struct NonmaxParams {
 	unsigned short* posInBlock;    // [batch][nbx*nby]
 	long long blocksPerImage;
 };
+template <bool MIN>   // MIN: minima, P.threshold is thresholdMin (see strictLocalMax)
 __global__ __launch_bounds__(256) void k_nonmax_blocks(NonmaxParams P) {
 	const int b = P.border, w = P.w, h = P.h, r = P.radius, stride = P.stride;
 	const int x = b + blockIdx.x * blockDim.x + threadIdx.x;
@@ -573,14 +580,14 @@ __global__ __launch_bounds__(256) void k_nonmax_blocks(NonmaxParams P) {
 #pragma unroll
 	for (int k = 0; k < NMS_ROWS + 2; k++) {
 		const int yy = yBase - 1 + k;
-		col[k] = (yy >= 0 && yy < h && x < w - b) ? img[(long long)yy * stride + x] : -INFINITY;
+		col[k] = (yy >= 0 && yy < h && x < w - b) ? img[(long long)yy * stride + x] : nmsPad<MIN>();
 	}
 #pragma unroll
 	for (int k = 0; k < NMS_ROWS; k++) {
 		const int yy = yBase + k;
 		const bool rowIn = yy < h && x < w - b;
-		lf[k] = (rowIn && x >= 1) ? img[(long long)yy * stride + x - 1] : -INFINITY;
-		rt[k] = (rowIn && x + 1 < w) ? img[(long long)yy * stride + x + 1] : -INFINITY;
+		lf[k] = (rowIn && x >= 1) ? img[(long long)yy * stride + x - 1] : nmsPad<MIN>();
+		rt[k] = (rowIn && x + 1 < w) ? img[(long long)yy * stride + x + 1] : nmsPad<MIN>();
 	}
 	__shared__ int candList[256 * NMS_ROWS];
 	__shared__ int candCount;
@@ -591,7 +598,8 @@ __global__ __launch_bounds__(256) void k_nonmax_blocks(NonmaxParams P) {
 		for (int k = 0; k < NMS_ROWS; k++) {
 			const int y = yBase + k;
 			const float val = col[k + 1];
-			const bool pass = y < h - b && val >= P.threshold && val != FLT_MAX && !(lf[k] >= val || rt[k] >= val || col[k] >= val || col[k + 2] >= val);
+			const bool pass = y < h - b && nmsBeats<MIN>(val, P.threshold) && val != nmsMarker<MIN>() &&
+							  !(nmsBeats<MIN>(lf[k], val) || nmsBeats<MIN>(rt[k], val) || nmsBeats<MIN>(col[k], val) || nmsBeats<MIN>(col[k + 2], val));
 			if (pass) candList[atomicAdd(&candCount, 1)] = (k << 16) | (int)threadIdx.x;
 		}
 	}
@@ -603,7 +611,8 @@ __global__ __launch_bounds__(256) void k_nonmax_blocks(NonmaxParams P) {
 		const int cx = b + blockIdx.x * blockDim.x + (code & 0xFFFF);
 		const int cy = yBase + (code >> 16);
 		const float val = img[(long long)cy * stride + cx];
-		if (!(r == 2 ? strictLocalMax<2>(img, stride, w, h, cx, cy, r, val, P.threshold) : strictLocalMax<0>(img, stride, w, h, cx, cy, r, val, P.threshold))) continue;
+		if (!(r == 2 ? strictLocalMax<2, MIN>(img, stride, w, h, cx, cy, r, val, P.threshold) : strictLocalMax<0, MIN>(img, stride, w, h, cx, cy, r, val, P.threshold)))
+			continue;
 		const int bx = (cx - b) / step, by = (cy - b) / step;
 		const unsigned int bit = (unsigned)by * (unsigned)P.nbx + (unsigned)bx;
 		atomicOr(&P.bitmap[(long long)blockIdx.z * P.bitmapWords + (bit >> 5)], 1u << (bit & 31));
@@ -611,7 +620,8 @@ __global__ __launch_bounds__(256) void k_nonmax_blocks(NonmaxParams P) {
 	}
 }
 
-int bhip_launch_nonmax_blocks(bhip_ctx* ctx, DevImg<const float> img, int radius, float threshold, int border, unsigned int* bitmap, int bitmapWords,
+template <bool MIN>
+static int launchNonmaxBlocks(bhip_ctx* ctx, DevImg<const float> img, int radius, float threshold, int border, unsigned int* bitmap, int bitmapWords,
 							  unsigned short* posInBlock, int nbx, int nby) {
 	const int w = img.width, h = img.height, batch = img.batch;
 	const int rw = w - 2 * border, rh = h - 2 * border;
@@ -620,11 +630,19 @@ int bhip_launch_nonmax_blocks(bhip_ctx* ctx, DevImg<const float> img, int radius
 	NonmaxParams P{img.data, img.imageStride, img.stride, w, h, radius, border, nbx, bitmapWords, threshold, bitmap, posInBlock, (long long)nbx * nby};
 	dim3 grid((rw + 255) / 256, (rh + NMS_ROWS - 1) / NMS_ROWS, batch);
 	{
-		ProfScope ps(ctx, "k_nonmax_blocks", 4.0 * w * h * batch);
-		hipLaunchKernelGGL(k_nonmax_blocks, grid, dim3(256), 0, ctx->stream, P);
+		ProfScope ps(ctx, MIN ? "k_nonmin_blocks" : "k_nonmax_blocks", 4.0 * w * h * batch);
+		hipLaunchKernelGGL(k_nonmax_blocks<MIN>, grid, dim3(256), 0, ctx->stream, P);
 	}
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
+}
+int bhip_launch_nonmax_blocks(bhip_ctx* ctx, DevImg<const float> img, int radius, float threshold, int border, unsigned int* bitmap, int bitmapWords,
+							  unsigned short* posInBlock, int nbx, int nby) {
+	return launchNonmaxBlocks<false>(ctx, img, radius, threshold, border, bitmap, bitmapWords, posInBlock, nbx, nby);
+}
+int bhip_launch_nonmin_blocks(bhip_ctx* ctx, DevImg<const float> img, int radius, float threshold, int border, unsigned int* bitmap, int bitmapWords,
+							  unsigned short* posInBlock, int nbx, int nby) {
+	return launchNonmaxBlocks<true>(ctx, img, radius, threshold, border, bitmap, bitmapWords, posInBlock, nbx, nby);
 }
 
 // one thread per bitmap word: every set bit (= accepted block, ascending = block-raster order) writes (x,y) at its rank

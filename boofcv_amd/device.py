@@ -9,6 +9,8 @@ Names follow the reference classes the host-buffer forms in boofcv_amd/api.py mi
   DeviceImageOps.sobel / three  GradientSobel / GradientThree .process              I:alg/filter/derivative/GradientSobel.java:110-124,158-173
   DeviceImageOps.intensity      GradientToEdgeFeatures.intensityE / intensityAbs    F:alg/feature/detect/edge/GradientToEdgeFeatures.java:61-95
   DeviceImageOps.nonmax         NonMaxBlock.process (strict)                        F:alg/feature/detect/extract/NonMaxBlock.java:69-94
+  DeviceImageOps.nonmaxMinMax   NonMaxBlockSearchStrict.Min / .Max / .MinMax        F:alg/feature/detect/extract/NonMaxBlockSearchStrict.java:56-248
+  DeviceImageOps.fast           FastCornerDetector.process                          F:alg/feature/detect/intensity/FastCornerDetector.java:123-189
   DeviceImageOps.pyramid        PyramidDiscreteSampleBlur.process                   I:alg/transform/pyramid/PyramidDiscreteSampleBlur.java:88-118
   DeviceImageOps.cornerIntensity  GradientCornerIntensity.process                   F:alg/feature/detect/intensity/impl/ImplSsdCorner_F32.java:62-196
   DeviceImageOps.brief          DescribePointBrief.process                          F:alg/feature/describe/DescribePointBrief.java:73-89
@@ -127,6 +129,47 @@ class DeviceImageOps:
         _check(self.ctx, self.L.bhip_nonmax_block_dev_f32(self.ctx._h, ip, iis, irs, W, H, B, int(radius), float(threshold), int(border),
                                                         C.c_void_p(xy.data_ptr()), cap, C.c_void_p(n.data_ptr())))
         return xy, n
+
+    def nonmaxMinMax(self, intensity, radius, thresholdMin, thresholdMax, border, detectMin=True, detectMax=True, cap=None):
+        """NonMaxBlockSearchStrict.Min / .Max / .MinMax -> (xyMin int16 [B, cap, 2], nMin int32 [B], xyMax, nMax) on the device, each list in
+        block-raster order; a side that is not detected has counts of 0"""
+        ip, iis, irs, W, H, B = _geom(intensity)
+        if cap is None:
+            step = radius + 1
+            cap = max(1, ((max(W - 2 * border, 0) + step - 1) // step) * ((max(H - 2 * border, 0) + step - 1) // step))
+        xyMin, xyMax = (torch.empty((B, cap, 2), dtype=torch.int16, device=intensity.device) for _ in range(2))
+        nMin, nMax = (torch.empty((B,), dtype=torch.int32, device=intensity.device) for _ in range(2))
+        _check(self.ctx, self.L.bhip_nonmax_block_minmax_dev_f32(self.ctx._h, ip, iis, irs, W, H, B, int(radius), float(thresholdMin), float(thresholdMax),
+                                                               int(border), 1 if detectMin else 0, 1 if detectMax else 0, C.c_void_p(xyMin.data_ptr()),
+                                                               C.c_void_p(nMin.data_ptr()), C.c_void_p(xyMax.data_ptr()), C.c_void_p(nMax.data_ptr()), cap))
+        return xyMin, nMin, xyMax, nMax
+
+    def fast(self, src, pixelTol, minContinuous, maxFeaturesFraction=0.1, intensity=True, cap=None):
+        """FastCornerDetector.process on uint8 or float32 frames -> (intensity float32 [B, H, W] | None, xyLow int16 [B, cap, 2], nLow int32 [B],
+        xyHigh, nHigh): dark and bright corners in raster order.  intensity: True allocates it, False / None is process(image), a float32
+        tensor (any row stride) is written in place.  A count may exceed cap; only the first cap pairs are written."""
+        u8 = src.dtype == torch.uint8
+        ip, iis, irs, W, H, B = _geom(src, torch.uint8 if u8 else torch.float32)
+        inten = None
+        if intensity is True:
+            inten = torch.empty((B, H, W), dtype=torch.float32, device=src.device)
+        elif intensity is not None and intensity is not False:
+            inten = intensity
+        op, ois, ors = None, 0, 0
+        if inten is not None:
+            op, ois, ors, W2, H2, B2 = _geom(inten)
+            if (W, H, B) != (W2, H2, B2):
+                raise IllegalArgumentException("input and intensity shapes differ")
+        if cap is None:
+            # the detector stops after the row that reaches the limit, so a list is never longer than the limit plus that row
+            cap = max(1, min(max(W - 6, 0) * max(H - 6, 0), int(maxFeaturesFraction * W * H) + W))
+        xyLow, xyHigh = (torch.empty((B, cap, 2), dtype=torch.int16, device=src.device) for _ in range(2))
+        nLow, nHigh = (torch.empty((B,), dtype=torch.int32, device=src.device) for _ in range(2))
+        fn = self.L.bhip_fast_dev_u8 if u8 else self.L.bhip_fast_dev_f32
+        _check(self.ctx, fn(self.ctx._h, ip, iis, irs, W, H, B, int(pixelTol) if u8 else float(pixelTol), int(minContinuous), float(maxFeaturesFraction), op, ois,
+                            ors, C.c_void_p(xyLow.data_ptr()), C.c_void_p(nLow.data_ptr()), C.c_void_p(xyHigh.data_ptr()), C.c_void_p(nHigh.data_ptr()),
+                            cap))
+        return inten, xyLow, nLow, xyHigh, nHigh
 
     def cornerIntensity(self, kind, radius, kappa, dx, dy, out=None, weighted=False):
         """kind: 0 Shi-Tomasi, 1 Harris.  float32 derivatives: ImplSsdCorner_F32 / ImplSsdCornerWeighted_F32; int16 derivatives:

@@ -217,6 +217,35 @@ int bhip_hessian_f32(bhip_ctx* ctx, const float* ii, int iiStart, int iiStride, 
  * Writes up to cap (x,y) int16 pairs in block-raster order (the USE_CONCURRENT=false order); *n is the number found. */
 int bhip_nonmax_block_f32(bhip_ctx* ctx, const float* intensity, int start, int stride, int width, int height, int radius, float threshold,
 						  int border, int16_t* xy, int cap, int* n);
+/* NonMaxBlock.process with NonMaxBlockSearchStrict.Min / .Max / .MinMax (F:alg/feature/detect/extract/NonMaxBlock.java:69-94,
+ * NonMaxBlockSearchStrict.java:56-79 Max, :97-139 Min, :141-194 MinMax, checkLocalMax / checkLocalMin :196-248), the extractor
+ * FactoryFeatureExtractor.nonmax builds for a strict ConfigExtract with detectMinimums and / or detectMaximums.  A minimum is the first
+ * smallest value of its (radius+1)^2 block, <= thresholdMin, != -Float.MAX_VALUE and strictly below every other pixel of its clipped
+ * (2*radius+1)^2 window.  The factory sets thresholdMin = -config.threshold; here the two thresholds are separate, as in the wrapper.
+ * Each list is written in block-raster order, up to cap pairs; *nMin / *nMax are the numbers found (0 for a side that is not detected).
+ * The candidate lists of the interface are not used (NonMaxBlock ignores them). */
+int bhip_nonmax_block_minmax_f32(bhip_ctx* ctx, const float* intensity, int start, int stride, int width, int height, int radius, float thresholdMin,
+								 float thresholdMax, int border, int detectMin, int detectMax, int16_t* xyMin, int* nMin, int16_t* xyMax, int* nMax, int cap);
+/* FastCornerDetector.process(image, intensity) (F:alg/feature/detect/intensity/FastCornerDetector.java:123-156; intensity == NULL:
+ * process(image), :161-189) with the helper FactoryIntensityPointAlg.fast(pixelTol, minContinuous, GrayU8 / GrayF32) builds
+ * (F:factory/feature/detect/intensity/FactoryIntensityPointAlg.java).  Circle: DiscretizedCircle.imageOffsets(3, stride)
+ * (I:misc/DiscretizedCircle.java:39-77), 16 pixels.  Class: ImplFastCorner{9..12}_{U8,F32}.checkPixel, evaluated as the rule its decision
+ * tree searches (GenericFastCorner.compareToNaiveDetection): minContinuous cyclically contiguous ring pixels all > centre + pixelTol
+ * (bright, "high") or all < centre - pixelTol (dark, "low").  Score: ImplFastHelper_U8 / _F32.scoreLower / scoreUpper (:47-81): the sum of
+ * the ring pixels beyond the bound minus centre * count; the F32 helper's sum is an `int` that truncates toward zero after every addition
+ * (Java's (int): saturating, NaN -> 0), so the sign of an F32 score does not tell the polarity.
+ * Rows 3 .. height-4 and columns 3 .. width-4 in raster order; after each row the detector stops once low + high >=
+ * (int)(maxFeaturesFraction * width * height) (that row is kept whole).  xyLow / xyHigh receive up to cap (x,y) pairs each in raster order,
+ * *nLow / *nHigh the numbers found (they may exceed cap).  width < 7 or height < 7: empty lists, zero intensity.
+ * Validation: minContinuous 9..12 (ConfigFastCorner.checkValidity, F:abst/feature/detect/interest/ConfigFastCorner.java:31-64),
+ * 0 < maxFeaturesFraction <= 1 (setMaxFeaturesFraction :195-199); otherwise BHIP_ERR_INVALID and nothing is written.
+ * Deviations: a negative pixelTol is BHIP_ERR_INVALID (the trees define nothing sensible there); the intensity view is written as a whole,
+ * 0 in the 3-pixel border and in the rows after an early stop, where the reference leaves what an earlier frame put there (its border is
+ * 0 because BaseGeneralFeatureIntensity.init zeroes on a size change) -- the result of a freshly constructed reference detector. */
+int bhip_fast_u8(bhip_ctx* ctx, const uint8_t* image, int start, int stride, int width, int height, int pixelTol, int minContinuous, double maxFeaturesFraction,
+				 float* intensity, int iStart, int iStride, int16_t* xyLow, int* nLow, int16_t* xyHigh, int* nHigh, int cap);
+int bhip_fast_f32(bhip_ctx* ctx, const float* image, int start, int stride, int width, int height, float pixelTol, int minContinuous, double maxFeaturesFraction,
+				  float* intensity, int iStart, int iStride, int16_t* xyLow, int* nLow, int16_t* xyHigh, int* nHigh, int cap);
 /* SelectNBestFeatures.process(intensity, corners, positive) + getBestCorners() (F:alg/feature/detect/extract/SelectNBestFeatures.java:51-97):
  * n <= target copies the list; otherwise keys = -intensity (positive) or +intensity and org.ddogleg.sorting.QuickSelect.selectIndex(keys,
  * target, n, indexes) decides which `target` corners are kept and in which order.  ddogleg is not part of the reference tree: the routine
@@ -438,6 +467,20 @@ int bhip_gradient_intensity_dev_f32(bhip_ctx* ctx, int kind, const float* dev_dx
  * only the first cap pairs are written) */
 int bhip_nonmax_block_dev_f32(bhip_ctx* ctx, const float* dev_intensity, long long imageStride, int stride, int width, int height, int batch, int radius,
 							  float threshold, int border, int16_t* dev_xy, int cap, int* dev_n);
+/* bhip_nonmax_block_minmax_f32 on every image of a batch: image b's lists go to dev_xyMin / dev_xyMax[b*cap ...], their lengths to dev_nMin /
+ * dev_nMax[b] (a length may exceed cap; only the first cap pairs are written).  No host synchronisation. */
+int bhip_nonmax_block_minmax_dev_f32(bhip_ctx* ctx, const float* dev_intensity, long long imageStride, int stride, int width, int height, int batch, int radius,
+									 float thresholdMin, float thresholdMax, int border, int detectMin, int detectMax, int16_t* dev_xyMin, int* dev_nMin,
+									 int16_t* dev_xyMax, int* dev_nMax, int cap);
+/* bhip_fast_u8 / bhip_fast_f32 on a batch of device frames (strides in elements; any byte alignment of a GrayU8 view).  dev_intensity == NULL:
+ * process(image).  Frame b writes dev_xyLow / dev_xyHigh[b*cap ...] and dev_nLow / dev_nHigh[b]; a count may exceed cap, only the first cap
+ * pairs are written.  Classification, row counts with the early stop, and the ordered lists are queued without a host synchronisation. */
+int bhip_fast_dev_u8(bhip_ctx* ctx, const uint8_t* dev_img, long long imageStride, int stride, int width, int height, int batch, int pixelTol, int minContinuous,
+					 double maxFeaturesFraction, float* dev_intensity, long long iImageStride, int iStride, int16_t* dev_xyLow, int* dev_nLow, int16_t* dev_xyHigh,
+					 int* dev_nHigh, int cap);
+int bhip_fast_dev_f32(bhip_ctx* ctx, const float* dev_img, long long imageStride, int stride, int width, int height, int batch, float pixelTol, int minContinuous,
+					  double maxFeaturesFraction, float* dev_intensity, long long iImageStride, int iStride, int16_t* dev_xyLow, int* dev_nLow, int16_t* dev_xyHigh,
+					  int* dev_nHigh, int cap);
 /* GradientCornerIntensity.process (see bhip_corner_intensity_f32) on a batch; derivX / derivY share dImageStride / dStride */
 int bhip_corner_intensity_dev_f32(bhip_ctx* ctx, int kind, int radius, float kappa, const float* dev_dx, const float* dev_dy, long long dImageStride,
 								  int dStride, int width, int height, int batch, float* dev_intensity, long long iImageStride, int iStride);

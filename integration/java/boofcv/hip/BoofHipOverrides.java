@@ -81,41 +81,58 @@ public final class BoofHipOverrides {
 			long ctx = BoofHipContext.get();
 			BoofHip.check(ctx, BoofHip.gaussianF32(ctx, in.data, in.startIndex, in.stride, in.width, in.height, sigmaX, radiusX, out.data, out.startIndex, out.stride));
 		};
-		// FactoryFeatureExtractor.nonmax(ConfigExtract): strict maxima only (relaxed rule / minima / candidate lists stay on the Java path)
+		// FactoryFeatureExtractor.nonmax(ConfigExtract): the strict Max / Min / MinMax searches (relaxed rule / candidate lists stay on the Java path)
 		BOverrideFactoryFeatureExtractor.nonmax = (ConfigExtract config) -> {
 			config.checkValidity();
-			if (!config.useStrictRule || config.detectMinimums || !config.detectMaximums) throw declined();
+			if (!config.useStrictRule) throw declined();
 			return new NonMaxHip(config);
 		};
 	}
 
-	/** NonMaxSuppression over bhip_nonmax_block_f32 (NonMaxBlock.process with the strict search, block-raster order). */
+	/** NonMaxSuppression over bhip_nonmax_block_f32 / bhip_nonmax_block_minmax_f32 (NonMaxBlock.process with the strict Max / Min / MinMax search,
+	 *  block-raster order).  As in FactoryFeatureExtractor.nonmax, a config without maximums gets the Min search and thresholdMin starts at -threshold. */
 	static final class NonMaxHip implements NonMaxSuppression {
-		private int radius, border; private float threshold;
-		private short[] xy = new short[0];
-		private final int[] n = new int[1];
-		NonMaxHip(ConfigExtract c) { radius = c.radius; border = c.ignoreBorder; threshold = c.threshold; }
+		private int radius, border; private float thresholdMax, thresholdMin;
+		private final boolean detectMin, detectMax;
+		private short[] xyMin = new short[0], xyMax = new short[0];
+		private final int[] nMin = new int[1], nMax = new int[1];
+		NonMaxHip(ConfigExtract c) {
+			radius = c.radius; border = c.ignoreBorder; thresholdMax = c.threshold; thresholdMin = -c.threshold;
+			detectMax = c.detectMaximums; detectMin = c.detectMinimums || !c.detectMaximums;
+		}
 
 		@Override public void process(GrayF32 intensity, QueueCorner candidateMin, QueueCorner candidateMax, QueueCorner foundMin, QueueCorner foundMax) {
 			long ctx = BoofHipContext.get();
 			int step = radius + 1;
 			int cap = Math.max(1, ((intensity.width - 2*border + step - 1)/step)*((intensity.height - 2*border + step - 1)/step));
-			if (xy.length < 2*cap) xy = new short[2*cap];
-			BoofHip.check(ctx, BoofHip.nonmaxBlockF32(ctx, intensity.data, intensity.startIndex, intensity.stride, intensity.width, intensity.height, radius, threshold,
-					border, xy, cap, n));
-			foundMax.reset();
-			for (int i = 0; i < n[0]; i++) foundMax.add(xy[2*i], xy[2*i + 1]);
+			if (xyMax.length < 2*cap) xyMax = new short[2*cap];
+			if (detectMin && xyMin.length < 2*cap) xyMin = new short[2*cap];
+			nMin[0] = nMax[0] = 0;
+			if (detectMin)
+				BoofHip.check(ctx, BoofHip.nonmaxBlockMinmaxF32(ctx, intensity.data, intensity.startIndex, intensity.stride, intensity.width, intensity.height, radius,
+						thresholdMin, thresholdMax, border, 1, detectMax ? 1 : 0, xyMin, nMin, xyMax, nMax, cap));
+			else
+				BoofHip.check(ctx, BoofHip.nonmaxBlockF32(ctx, intensity.data, intensity.startIndex, intensity.stride, intensity.width, intensity.height, radius,
+						thresholdMax, border, xyMax, cap, nMax));
+			if (foundMin != null) {   // NonMaxBlock.process resets the lists it is given
+				foundMin.reset();
+				for (int i = 0; i < nMin[0]; i++) foundMin.add(xyMin[2*i], xyMin[2*i + 1]);
+			}
+			if (foundMax != null) {
+				foundMax.reset();
+				for (int i = 0; i < nMax[0]; i++) foundMax.add(xyMax[2*i], xyMax[2*i + 1]);
+			}
 		}
 		@Override public boolean getUsesCandidates() { return false; }
-		@Override public float getThresholdMinimum() { return -threshold; }
-		@Override public float getThresholdMaximum() { return threshold; }
-		@Override public void setThresholdMinimum(float t) {}
-		@Override public void setThresholdMaximum(float t) { threshold = t; }
+		@Override public float getThresholdMinimum() { return thresholdMin; }
+		@Override public float getThresholdMaximum() { return thresholdMax; }
+		@Override public void setThresholdMinimum(float t) { thresholdMin = t; }
+		@Override public void setThresholdMaximum(float t) { thresholdMax = t; }
 		@Override public void setIgnoreBorder(int b) { border = b; }
 		@Override public int getIgnoreBorder() { return border; }
 		@Override public void setSearchRadius(int r) { radius = r; }
 		@Override public int getSearchRadius() { return radius; }
-		@Override public boolean canDetectMaximums() { return true; }
-		@Override public boolean canDetectMinimums() { return false; }
+		@Override public boolean canDetectMaximums() { return detectMax; }
+		@Override public boolean canDetectMinimums() { return detectMin; }
 	}
 }
