@@ -36,6 +36,8 @@ def _geom(t, dtype=torch.float32):
     B, H, W = t.shape
     if W > 1 and t.stride(2) != 1:
         raise IllegalArgumentException("the last dimension must be contiguous")
+    if (B > 1 and t.stride(0) < 0) or (H > 1 and t.stride(1) < 0):
+        raise IllegalArgumentException("strides must not be negative")
     return C.c_void_p(t.data_ptr()), (t.stride(0) if B > 1 else H * t.stride(1)), t.stride(1) if H > 1 else max(W, t.stride(1)), W, H, B
 
 
