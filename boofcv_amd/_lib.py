@@ -38,6 +38,11 @@ class KltCfg(C.Structure):
                 ("minPositionDelta", C.c_float)]
 
 
+class DisparityBmCfg(C.Structure):
+    _fields_ = [("minDisparity", C.c_int), ("rangeDisparity", C.c_int), ("regionRadiusX", C.c_int), ("regionRadiusY", C.c_int),
+                ("maxPerPixelError", C.c_double), ("validateRtoL", C.c_int), ("texture", C.c_double)]
+
+
 # KltTrackFault ordinals (+ the library's own code for positions where the reference throws)
 BHIP_KLT_SUCCESS, BHIP_KLT_DRIFTED, BHIP_KLT_OUT_OF_BOUNDS, BHIP_KLT_FAILED, BHIP_KLT_LARGE_ERROR, BHIP_KLT_REFERENCE_THROWS = range(6)
 
@@ -49,6 +54,7 @@ _fp, _dp, _ip, _u8p, _i16p, _i32p, _llp = P(C.c_float), P(C.c_double), P(C.c_int
 SIGNATURES = {
     "bhip_fh_cfg_default": (None, [P(FhCfg)]),
     "bhip_surf_cfg_default": (None, [P(SurfCfg)]),
+    "bhip_disparity_bm_cfg_default": (None, [P(DisparityBmCfg)]),
     "bhip_ori_cfg_default": (None, [P(OriCfg), _i]),
     "bhip_ctx_create": (_i, [_i, P(_vp)]),
     "bhip_ctx_create_on_stream": (_i, [_i, _vp, P(_vp)]),
@@ -87,6 +93,8 @@ SIGNATURES = {
     "bhip_nonmax_block_minmax_f32": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _f, _f, _i, _i, _i, _i16p, _ip, _i16p, _ip, _i]),
     "bhip_fast_u8": (_i, [_vp, _u8p, _i, _i, _i, _i, _i, _i, _d, _fp, _i, _i, _i16p, _ip, _i16p, _ip, _i]),
     "bhip_fast_f32": (_i, [_vp, _fp, _i, _i, _i, _i, _f, _i, _d, _fp, _i, _i, _i16p, _ip, _i16p, _ip, _i]),
+    "bhip_disparity_bm_u8_u8": (_i, [_vp, P(DisparityBmCfg), _u8p, _i, _i, _u8p, _i, _i, _i, _i, _u8p, _i, _i]),
+    "bhip_disparity_bm_u8_f32": (_i, [_vp, P(DisparityBmCfg), _u8p, _i, _i, _u8p, _i, _i, _i, _i, _fp, _i, _i]),
     "bhip_select_nbest_f32": (_i, [_vp, _fp, _i, _i, _i, _i, _i16p, _i, _i, _i, _i16p, _ip]),
     "bhip_fh_detect_f32": (_i, [_vp, P(FhCfg), _fp, _i, _i, _i, _i, _dp, _i, _ip]),
     "bhip_assoc_l2_f64": (_i, [_vp, _dp, _i, _dp, _i, _i, _d, _i, _i, _ip, _dp]),
@@ -138,6 +146,8 @@ SIGNATURES = {
     "bhip_nonmax_block_minmax_dev_f32": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _i, _f, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _i]),
     "bhip_fast_dev_u8": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _d, _vp, _ll, _i, _vp, _vp, _vp, _vp, _i]),
     "bhip_fast_dev_f32": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _f, _i, _d, _vp, _ll, _i, _vp, _vp, _vp, _vp, _i]),
+    "bhip_disparity_bm_dev_u8_u8": (_i, [_vp, P(DisparityBmCfg), _vp, _ll, _i, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i]),
+    "bhip_disparity_bm_dev_u8_f32": (_i, [_vp, P(DisparityBmCfg), _vp, _ll, _i, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i]),
     "bhip_corner_intensity_dev_f32": (_i, [_vp, _i, _i, _f, _vp, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i]),
     "bhip_sobel_dev_u8_s16": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _vp, _vp, _ll, _i, _i]),
     "bhip_three_dev_u8_s16": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _vp, _vp, _ll, _i, _i]),

@@ -15,7 +15,7 @@
 // host export calls can overwrite what it staged.
 struct CtxScratch {
 	DevBuf in0, in1, out0, out1, tmp0, tmp1;                                 // staging
-	DevBuf work, assocCol, nmsBitmap, nmsPrefix, nmsPos, ipTmp, ipKernel, fast;   // device side
+	DevBuf work, assocCol, nmsBitmap, nmsPrefix, nmsPos, ipTmp, ipKernel, fast, disparity;   // device side
 	AssocMfmaWork mfma;
 	int assocExactOnly = -1;  // BHIP_ASSOC_EXACT=1 forces the exact VALU association kernels (parity cross-check)
 };
@@ -61,6 +61,9 @@ void bhip_fh_cfg_default(bhip_fh_cfg* c) {
 }
 void bhip_klt_cfg_default(bhip_klt_cfg* c) {
 	c->forbiddenBorder = 0; c->maxPerPixelError = 25; c->maxIterations = 15; c->minDeterminant = 0.001f; c->minPositionDelta = 0.01f;
+}
+void bhip_disparity_bm_cfg_default(bhip_disparity_bm_cfg* c) {
+	c->minDisparity = 0; c->rangeDisparity = 100; c->regionRadiusX = 3; c->regionRadiusY = 3; c->maxPerPixelError = 0; c->validateRtoL = 1; c->texture = 0.15;
 }
 void bhip_surf_cfg_default(bhip_surf_cfg* c) {
 	c->widthLargeGrid = 4; c->widthSubRegion = 5; c->widthSample = 3; c->weightSigma = 4.5; c->overLap = 2; c->sigmaLargeGrid = 2.5;
@@ -1398,6 +1401,105 @@ int bhip_fast_dev_f32(bhip_ctx* ctx, const float* dev_img, long long imageStride
 					  int* dev_nHigh, int cap) {
 	return fastDev<float>(ctx, dev_img, imageStride, stride, width, height, batch, pixelTol, minContinuous, maxFeaturesFraction, dev_intensity, iImageStride, iStride,
 						  dev_xyLow, dev_nLow, dev_xyHigh, dev_nHigh, cap);
+}
+
+// ---- dense stereo disparity (disparity.hip): StereoDisparity.process of FactoryStereoDisparity.blockMatch, SAD on GrayU8 pairs ----
+extern "C++" {
+// Java's (int) of a double: NaN -> 0, saturating
+static int javaDoubleToInt(double v) {
+	if (v != v) return 0;
+	if (v >= 2147483647.0) return 2147483647;
+	if (v <= -2147483648.0) return -2147483647 - 1;
+	return (int)v;
+}
+
+// the checks of ConfigDisparityBM.checkValidity, DisparityBlockMatchRowFormat.process and SelectDisparityWithChecksWta.configure, then the
+// kernel's limits; fills the selector's parameters
+template <class OutT>
+static int disparityParams(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int width, int height, DispBmParams& p) {
+	bhip_disparity_bm_cfg c;
+	if (cfg) c = *cfg; else bhip_disparity_bm_cfg_default(&c);
+	if (c.minDisparity < 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "miDisparity < 0");
+	if (c.rangeDisparity < 1) return bhip_fail(ctx, BHIP_ERR_INVALID, "rangeDisparity < 1");
+	if (c.regionRadiusX < 0 || c.regionRadiusY < 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "region radius < 0");
+	const long long maxD = (long long)c.minDisparity + c.rangeDisparity;
+	if (maxD > (long long)width - 2LL * c.regionRadiusX)
+		return bhip_fail(ctx, BHIP_ERR_INVALID, "The maximum disparity is too large for this image size: max size " + std::to_string((long long)width - 2LL * c.regionRadiusX));
+	if ((long long)height < 2LL * c.regionRadiusY + 1) return bhip_fail(ctx, BHIP_ERR_INVALID, "the image is lower than the region");
+	if (sizeof(OutT) == 1 && c.rangeDisparity + 1LL > 254)
+		return bhip_fail(ctx, BHIP_ERR_INVALID, "Max range exceeds maximum value in disparity image. v=" + std::to_string(c.rangeDisparity + 1LL));
+	if (c.regionRadiusX > BHIP_DISP_MAX_RADIUS || c.regionRadiusY > BHIP_DISP_MAX_RADIUS || c.rangeDisparity > BHIP_DISP_MAX_RANGE)
+		return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "block matching on the GPU: region radius <= 7, rangeDisparity <= 256");
+	const int rw = 2 * c.regionRadiusX + 1, rh = 2 * c.regionRadiusY + 1;
+	const int maxError = javaDoubleToInt((rw * rh) * c.maxPerPixelError);   // FactoryStereoDisparity.java:75,79
+	p.minD = c.minDisparity; p.range = c.rangeDisparity; p.rx = c.regionRadiusX; p.ry = c.regionRadiusY;
+	p.maxError = maxError <= 0 ? 2147483647 : maxError;                     // SelectDisparityWithChecksWta.java:83
+	p.rtolTol = c.validateRtoL;
+	p.textureThr = javaDoubleToInt(10000 * c.texture);                      // SelectErrorWithChecks_S32.setTexture
+	return BHIP_OK;
+}
+
+template <class OutT>
+static int disparityDevice(bhip_ctx* ctx, const DispBmParams& p, DevImg<const uint8_t> left, DevImg<const uint8_t> right, DevImg<OutT> disp) {
+	DevBuf& scratch = scratchOf(ctx)->disparity;
+	BHIP_TRY(scratch.reserve(ctx, bhip_disparity_scratch(left.width, left.height, left.batch)));
+	return bhip_launch_disparity_bm<OutT>(ctx, left, right, p, scratch.as<uint8_t>(), disp);
+}
+
+template <class OutT>
+static int disparityDev(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* dev_left, long long lImageStride, int lStride, const uint8_t* dev_right,
+						long long rImageStride, int rStride, int width, int height, int batch, OutT* dev_disp, long long dImageStride, int dStride) {
+	CHECK_CTX(ctx);
+	const DevImg<const uint8_t> left{dev_left, lImageStride, lStride, width, height, batch}, right{dev_right, rImageStride, rStride, width, height, batch};
+	const DevImg<OutT> disp{dev_disp, dImageStride, dStride, width, height, batch};
+	CHECK_IMG(ctx, left);
+	CHECK_IMG(ctx, right);
+	CHECK_IMG(ctx, disp);
+	DispBmParams p;
+	BHIP_TRY(disparityParams<OutT>(ctx, cfg, width, height, p));
+	return disparityDevice<OutT>(ctx, p, left, right, disp);
+}
+
+template <class OutT>
+static int disparityHost(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* left, int lStart, int lStride, const uint8_t* right, int rStart, int rStride,
+						 int width, int height, OutT* disp, int dStart, int dStride) {
+	const HostImg<const uint8_t> hl{left, lStart, lStride, width, height}, hr{right, rStart, rStride, width, height};
+	const HostImg<OutT> hd{disp, dStart, dStride, width, height};
+	CHECK_CTX(ctx);
+	CHECK_IMG(ctx, hl);
+	CHECK_IMG(ctx, hr);
+	CHECK_IMG(ctx, hd);
+	DispBmParams p;
+	BHIP_TRY(disparityParams<OutT>(ctx, cfg, width, height, p));
+	CtxScratch* sc = scratchOf(ctx);
+	DevImg<uint8_t> dl, dr;
+	DevImg<OutT> dd;
+	BHIP_TRY(stageIn(ctx, sc->in0, hl, width, dl));
+	BHIP_TRY(stageIn(ctx, sc->in1, hr, width, dr));
+	BHIP_TRY(stageIn(ctx, sc->out0, hd, width, dd, false));
+	BHIP_TRY(disparityDevice<OutT>(ctx, p, dl, dr, dd));
+	BHIP_TRY(stageOut(ctx, hd, dd));
+	return bhip_ctx_synchronize(ctx);
+}
+}  // extern "C++"
+
+int bhip_disparity_bm_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* left, int lStart, int lStride, const uint8_t* right, int rStart,
+							int rStride, int width, int height, uint8_t* disp, int dStart, int dStride) {
+	return disparityHost<uint8_t>(ctx, cfg, left, lStart, lStride, right, rStart, rStride, width, height, disp, dStart, dStride);
+}
+int bhip_disparity_bm_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* left, int lStart, int lStride, const uint8_t* right, int rStart,
+							 int rStride, int width, int height, float* disp, int dStart, int dStride) {
+	return disparityHost<float>(ctx, cfg, left, lStart, lStride, right, rStart, rStride, width, height, disp, dStart, dStride);
+}
+int bhip_disparity_bm_dev_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* dev_left, long long lImageStride, int lStride,
+								const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, uint8_t* dev_disp,
+								long long dImageStride, int dStride) {
+	return disparityDev<uint8_t>(ctx, cfg, dev_left, lImageStride, lStride, dev_right, rImageStride, rStride, width, height, batch, dev_disp, dImageStride, dStride);
+}
+int bhip_disparity_bm_dev_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* dev_left, long long lImageStride, int lStride,
+								 const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, float* dev_disp,
+								 long long dImageStride, int dStride) {
+	return disparityDev<float>(ctx, cfg, dev_left, lImageStride, lStride, dev_right, rImageStride, rStride, width, height, batch, dev_disp, dImageStride, dStride);
 }
 
 int bhip_select_nbest_f32(bhip_ctx* ctx, const float* intensity, int start, int stride, int width, int height, const int16_t* xy, int n, int target,

@@ -371,6 +371,20 @@ template <class T>
 int bhip_launch_fast(bhip_ctx* ctx, DevImg<const T> img, typename FastTol<T>::type tol, int minContinuous, int maxFeatures, DevImg<float> inten, void* scratch,
 					 int16_t* xyLow, int* nLow, int16_t* xyHigh, int* nHigh, int cap);
 
+// ---------------- dense stereo disparity, SAD block matching (disparity.hip) ----------------
+#define BHIP_DISP_MAX_RADIUS 7    // regionRadiusX / regionRadiusY the kernel's staged rows hold
+#define BHIP_DISP_MAX_RANGE 256   // rangeDisparity the kernel's cost slab holds
+// ConfigDisparityBM as the selector sees it: maxError = Integer.MAX_VALUE when the test is off, rtolTol < 0 and textureThr <= 0 likewise
+struct DispBmParams {
+	int minD, range, rx, ry;
+	int maxError, rtolTol, textureThr;
+};
+size_t bhip_disparity_scratch(int width, int height, int batch);   // bytes of device scratch one bhip_launch_disparity_bm call needs
+// DisparityScoreBM_S32 + SelectErrorWithChecks_S32.DispU8 (OutT = uint8_t) / SelectErrorSubpixel.S32_F32 (OutT = float) on every pair of a
+// batch; the whole output view is written (rangeDisparity where the reference writes nothing).  The caller has validated c against the image.
+template <class OutT>
+int bhip_launch_disparity_bm(bhip_ctx* ctx, DevImg<const uint8_t> left, DevImg<const uint8_t> right, const DispBmParams& c, uint8_t* scratch, DevImg<OutT> out);
+
 // ---------------- pyramid KLT tracker (klt.hip) ----------------
 #define BHIP_KLT_MAX_LAYERS 8
 #define BHIP_KLT_MAX_RADIUS 7

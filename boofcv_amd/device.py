@@ -11,6 +11,7 @@ Names follow the reference classes the host-buffer forms in boofcv_amd/api.py mi
   DeviceImageOps.nonmax         NonMaxBlock.process (strict)                        F:alg/feature/detect/extract/NonMaxBlock.java:69-94
   DeviceImageOps.nonmaxMinMax   NonMaxBlockSearchStrict.Min / .Max / .MinMax        F:alg/feature/detect/extract/NonMaxBlockSearchStrict.java:56-248
   DeviceImageOps.fast           FastCornerDetector.process                          F:alg/feature/detect/intensity/FastCornerDetector.java:123-189
+  DeviceImageOps.disparityBM    StereoDisparity.process (blockMatch, SAD, GrayU8)   F:factory/feature/disparity/FactoryStereoDisparity.java:62-144
   DeviceImageOps.pyramid        PyramidDiscreteSampleBlur.process                   I:alg/transform/pyramid/PyramidDiscreteSampleBlur.java:88-118
   DeviceImageOps.cornerIntensity  GradientCornerIntensity.process                   F:alg/feature/detect/intensity/impl/ImplSsdCorner_F32.java:62-196
   DeviceImageOps.brief          DescribePointBrief.process                          F:alg/feature/describe/DescribePointBrief.java:73-89
@@ -172,6 +173,24 @@ class DeviceImageOps:
                             ors, C.c_void_p(xyLow.data_ptr()), C.c_void_p(nLow.data_ptr()), C.c_void_p(xyHigh.data_ptr()), C.c_void_p(nHigh.data_ptr()),
                             cap))
         return inten, xyLow, nLow, xyHigh, nHigh
+
+    def disparityBM(self, left, right, config=None, subpixel=True, out=None):
+        """StereoDisparity.process of FactoryStereoDisparity.blockMatch (SAD) on uint8 pairs [B,H,W] -> the disparity [B,H,W]: float32 when subpixel,
+        uint8 otherwise (config.subpixel is not read; `out`, any row / image stride, is written in place and as a whole).  config: a
+        ConfigDisparityBM, None = the reference defaults."""
+        lp, lis, lrs, W, H, B = _geom(left, torch.uint8)
+        rp, ris, rrs, W2, H2, B2 = _geom(right, torch.uint8)
+        if (W, H, B) != (W2, H2, B2):
+            raise IllegalArgumentException("Image shapes do not match")
+        dt = torch.float32 if subpixel else torch.uint8
+        if out is None:
+            out = torch.empty((B, H, W), dtype=dt, device=left.device)
+        op, ois, ors, W3, H3, B3 = _geom(out, dt)
+        if (W, H, B) != (W3, H3, B3):
+            raise IllegalArgumentException("input and disparity shapes differ")
+        fn = self.L.bhip_disparity_bm_dev_u8_f32 if subpixel else self.L.bhip_disparity_bm_dev_u8_u8
+        _check(self.ctx, fn(self.ctx._h, C.byref(config._c()) if config is not None else None, lp, lis, lrs, rp, ris, rrs, W, H, B, op, ois, ors))
+        return out
 
     def cornerIntensity(self, kind, radius, kappa, dx, dy, out=None, weighted=False):
         """kind: 0 Shi-Tomasi, 1 Harris.  float32 derivatives: ImplSsdCorner_F32 / ImplSsdCornerWeighted_F32; int16 derivatives:

@@ -94,6 +94,17 @@ typedef struct {
 	float minPositionDelta; /* 0.01f */
 } bhip_klt_cfg;
 
+/* F:factory/feature/disparity/ConfigDisparityBM.java:31-87 (errorType = SAD; subpixel is the choice between the _u8 and _f32 entry points) */
+typedef struct {
+	int minDisparity;        /* 0; must be >= 0 */
+	int rangeDisparity;      /* 100; must be >= 1 */
+	int regionRadiusX;       /* 3 */
+	int regionRadiusY;       /* 3 */
+	double maxPerPixelError; /* 0: the test is off (any value whose (int)(regionWidth*regionHeight*maxPerPixelError) is <= 0) */
+	int validateRtoL;        /* 1; < 0: off */
+	double texture;          /* 0.15; off when (int)(10000*texture) <= 0 */
+} bhip_disparity_bm_cfg;
+
 /* F:alg/tracker/klt/KltTrackFault.java:28-44 (ordinals).  BHIP_KLT_REFERENCE_THROWS: the position is one of the float round-off cases at the image
  * border where KltTracker.computeSubImageBounds / BilinearRectangle_F32.region throw IllegalArgumentException (in Java the exception leaves
  * PointTrackerKltPyramid.process); the library never reads outside the image, gives the track this fault and drops it. */
@@ -106,6 +117,7 @@ typedef struct {
 
 void bhip_fh_cfg_default(bhip_fh_cfg* c);
 void bhip_klt_cfg_default(bhip_klt_cfg* c);
+void bhip_disparity_bm_cfg_default(bhip_disparity_bm_cfg* c);
 void bhip_surf_cfg_default(bhip_surf_cfg* c);
 void bhip_ori_cfg_default(bhip_ori_cfg* c, int stable);
 
@@ -246,6 +258,41 @@ int bhip_fast_u8(bhip_ctx* ctx, const uint8_t* image, int start, int stride, int
 				 float* intensity, int iStart, int iStride, int16_t* xyLow, int* nLow, int16_t* xyHigh, int* nHigh, int cap);
 int bhip_fast_f32(bhip_ctx* ctx, const float* image, int start, int stride, int width, int height, float pixelTol, int minContinuous, double maxFeaturesFraction,
 				  float* intensity, int iStart, int iStride, int16_t* xyLow, int* nLow, int16_t* xyHigh, int* nHigh, int cap);
+/* StereoDisparity.process(left, right) of FactoryStereoDisparity.blockMatch(ConfigDisparityBM, GrayU8.class, GrayU8.class | GrayF32.class) with
+ * errorType = SAD (F:factory/feature/disparity/FactoryStereoDisparity.java:62-144,203-240): WrapDisparityBlockMatchRowFormat / WrapBaseBlockMatch
+ * (F:abst/feature/disparity/WrapBaseBlockMatch.java:42-85) over DisparityScoreBM_S32 (F:alg/feature/disparity/block/score/DisparityScoreBM_S32.java:73-205)
+ * with BlockRowScoreSad.U8 (block/BlockRowScore.java:96-138, BlockRowScoreSad.java:53-67) and the selector SelectErrorWithChecks_S32.DispU8
+ * (block/select/SelectErrorWithChecks_S32.java:60-162,172-190; bhip_disparity_bm_u8_u8, subpixel = false) or SelectErrorSubpixel.S32_F32
+ * (block/select/SelectErrorSubpixel.java:46-75; bhip_disparity_bm_u8_f32, subpixel = true).  cfg == NULL: the reference defaults.
+ * With maxD = minDisparity + rangeDisparity, rw = 2*regionRadiusX+1, rh = 2*regionRadiusY+1, inv = rangeDisparity + 1:
+ *   cost    for a row y in [ry, H-ry), a left block that starts at column c in [minDisparity, W-rw] and i in [0, lm), lm = min(c - minDisparity + 1,
+ *           rangeDisparity) (maxDisparityAtColumnL2R): C(y,c,i) = sum over dy = -ry..ry, j < rw of |L[y+dy][c+j] - R[y+dy][c-minDisparity-i+j]|, an int
+ *           (the reference's running sums are exact in integers).  The result goes to pixel (c + rx, y).
+ *   best    the first i with the smallest cost (strict <), sBest its cost.
+ *   error   maxError = (int)((rw*rh)*maxPerPixelError) in double; <= 0 turns the test off; sBest > maxError gives inv.
+ *   R to L  only when not rejected and validateRtoL >= 0: k = c - best - minDisparity, n = min(W-rw, k+maxD) - k - minDisparity, rBest = the first
+ *           minimum of C(y, k+minDisparity+j, j) over j = 0, then 1 <= j < n; |rBest - best| > validateRtoL gives inv.  As written in the reference,
+ *           a search that the image clips leaves out the j whose left block would start at column W-rw.
+ *   texture only when (int)(10000*texture) = thr > 0, not rejected and lm >= 3: second = the smallest C(y,c,i) over i in [0,best-1) and [best+2,lm),
+ *           Integer.MAX_VALUE when there is none; 10000*(second-sBest) <= thr*sBest gives inv, both products Java ints that wrap (lm == 3 and
+ *           best == 1: the wrapped product is negative and the pixel is rejected).
+ *   store   U8: (byte)value.  F32: value <= 0 or value >= lm-1 (inv included) stores (float)value, otherwise value + (float)(c0-c2) /
+ *           (float)(2*(c0-2*c1+c2)) with c0, c1, c2 the costs at value-1, value, value+1: one correctly rounded fp32 division and one fp32 addition.
+ *   rest    rows < ry and >= H-ry, columns < rx+minDisparity and >= W-rx hold rangeDisparity, WrapBaseBlockMatch.getInvalidValue(), with which
+ *           the wrapper fills a new disparity image -- not inv.  (TestWrapDisparityBlockMatchRowFormat.borderSetToInvalid asserts a value
+ *           > rangeDisparity there and contradicts the main code, which is what is followed.)
+ * Validation, BHIP_ERR_INVALID and nothing is written: minDisparity < 0, rangeDisparity < 1 (ConfigDisparityBM.checkValidity), a negative radius,
+ * maxD > W - 2*regionRadiusX (DisparityBlockMatchRowFormat.process throws RuntimeException), an output of type U8 with inv > 254
+ * (SelectDisparityWithChecksWta.configure), H < rh.
+ * Deviations: H < rh is refused, where the reference indexes outside the image; the disparity view is written as a whole on every call,
+ * rangeDisparity outside the region above, where the reference leaves what an earlier pair put there -- the result of a freshly constructed
+ * reference object.
+ * Limits: regionRadiusX, regionRadiusY <= 7 and rangeDisparity <= 256 (<= 253 for U8, by the validation); beyond them BHIP_ERR_UNSUPPORTED and
+ * nothing is written.  blockMatchBest5, CENSUS, NCC, SGM and the GrayF32 / GrayU16 / GrayS16 inputs have no entry point. */
+int bhip_disparity_bm_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* left, int lStart, int lStride, const uint8_t* right, int rStart,
+							int rStride, int width, int height, uint8_t* disp, int dStart, int dStride);
+int bhip_disparity_bm_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* left, int lStart, int lStride, const uint8_t* right, int rStart,
+							 int rStride, int width, int height, float* disp, int dStart, int dStride);
 /* SelectNBestFeatures.process(intensity, corners, positive) + getBestCorners() (F:alg/feature/detect/extract/SelectNBestFeatures.java:51-97):
  * n <= target copies the list; otherwise keys = -intensity (positive) or +intensity and org.ddogleg.sorting.QuickSelect.selectIndex(keys,
  * target, n, indexes) decides which `target` corners are kept and in which order.  ddogleg is not part of the reference tree: the routine
@@ -481,6 +528,16 @@ int bhip_fast_dev_u8(bhip_ctx* ctx, const uint8_t* dev_img, long long imageStrid
 int bhip_fast_dev_f32(bhip_ctx* ctx, const float* dev_img, long long imageStride, int stride, int width, int height, int batch, float pixelTol, int minContinuous,
 					  double maxFeaturesFraction, float* dev_intensity, long long iImageStride, int iStride, int16_t* dev_xyLow, int* dev_nLow, int16_t* dev_xyHigh,
 					  int* dev_nHigh, int cap);
+/* bhip_disparity_bm_u8_u8 / bhip_disparity_bm_u8_f32 on a batch of device pairs (strides in elements; any byte alignment of a GrayU8 view): pair b is
+ * dev_left + b*lImageStride, dev_right + b*rImageStride and writes dev_disp + b*dImageStride, the whole width x height view and nothing outside it.
+ * Cost and selection run in two launches (right-to-left minima into one byte per pixel of context scratch, then selection) without a host
+ * synchronisation. */
+int bhip_disparity_bm_dev_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* dev_left, long long lImageStride, int lStride,
+								const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, uint8_t* dev_disp,
+								long long dImageStride, int dStride);
+int bhip_disparity_bm_dev_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* dev_left, long long lImageStride, int lStride,
+								 const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, float* dev_disp,
+								 long long dImageStride, int dStride);
 /* GradientCornerIntensity.process (see bhip_corner_intensity_f32) on a batch; derivX / derivY share dImageStride / dStride */
 int bhip_corner_intensity_dev_f32(bhip_ctx* ctx, int kind, int radius, float kappa, const float* dev_dx, const float* dev_dy, long long dImageStride,
 								  int dStride, int width, int height, int batch, float* dev_intensity, long long iImageStride, int iStride);
