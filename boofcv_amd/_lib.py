@@ -46,6 +46,11 @@ class DisparityBmCfg(C.Structure):
 # KltTrackFault ordinals (+ the library's own code for positions where the reference throws)
 BHIP_KLT_SUCCESS, BHIP_KLT_DRIFTED, BHIP_KLT_OUT_OF_BOUNDS, BHIP_KLT_FAILED, BHIP_KLT_LARGE_ERROR, BHIP_KLT_REFERENCE_THROWS = range(6)
 
+# InterpolationType / BorderType ordinals and the coordinate models of bhip_distort_*
+BHIP_INTERP_NEAREST_NEIGHBOR, BHIP_INTERP_BILINEAR, BHIP_INTERP_BICUBIC, BHIP_INTERP_POLYNOMIAL4 = range(4)
+BHIP_BORDER_SKIP, BHIP_BORDER_EXTENDED, BHIP_BORDER_NORMALIZED, BHIP_BORDER_REFLECT, BHIP_BORDER_WRAP, BHIP_BORDER_ZERO = range(6)
+BHIP_DISTORT_AFFINE, BHIP_DISTORT_HOMOGRAPHY = 1, 2
+
 P = C.POINTER
 _vp, _i, _f, _d, _ll = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_longlong
 _fp, _dp, _ip, _u8p, _i16p, _i32p, _llp = P(C.c_float), P(C.c_double), P(C.c_int), P(C.c_uint8), P(C.c_int16), P(C.c_int32), P(C.c_longlong)
@@ -95,6 +100,10 @@ SIGNATURES = {
     "bhip_fast_f32": (_i, [_vp, _fp, _i, _i, _i, _i, _f, _i, _d, _fp, _i, _i, _i16p, _ip, _i16p, _ip, _i]),
     "bhip_disparity_bm_u8_u8": (_i, [_vp, P(DisparityBmCfg), _u8p, _i, _i, _u8p, _i, _i, _i, _i, _u8p, _i, _i]),
     "bhip_disparity_bm_u8_f32": (_i, [_vp, P(DisparityBmCfg), _u8p, _i, _i, _u8p, _i, _i, _i, _i, _fp, _i, _i]),
+    "bhip_distort_map_u8": (_i, [_vp, _u8p, _i, _i, _i, _i, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _u8p, _i, _i, _u8p, _i, _i]),
+    "bhip_distort_map_f32": (_i, [_vp, _fp, _i, _i, _i, _i, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _fp, _i, _i, _u8p, _i, _i]),
+    "bhip_distort_model_u8": (_i, [_vp, _u8p, _i, _i, _i, _i, _i, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _u8p, _i, _i, _u8p, _i, _i]),
+    "bhip_distort_model_f32": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _fp, _i, _i, _u8p, _i, _i]),
     "bhip_select_nbest_f32": (_i, [_vp, _fp, _i, _i, _i, _i, _i16p, _i, _i, _i, _i16p, _ip]),
     "bhip_fh_detect_f32": (_i, [_vp, P(FhCfg), _fp, _i, _i, _i, _i, _dp, _i, _ip]),
     "bhip_assoc_l2_f64": (_i, [_vp, _dp, _i, _dp, _i, _i, _d, _i, _i, _ip, _dp]),
@@ -148,6 +157,11 @@ SIGNATURES = {
     "bhip_fast_dev_f32": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _f, _i, _d, _vp, _ll, _i, _vp, _vp, _vp, _vp, _i]),
     "bhip_disparity_bm_dev_u8_u8": (_i, [_vp, P(DisparityBmCfg), _vp, _ll, _i, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i]),
     "bhip_disparity_bm_dev_u8_f32": (_i, [_vp, P(DisparityBmCfg), _vp, _ll, _i, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i]),
+    "bhip_distort_map_dev_u8": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _ll, _i, _vp, _ll, _i]),
+    "bhip_distort_map_dev_f32": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _ll, _i, _vp, _ll, _i]),
+    "bhip_distort_model_dev_u8": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _i, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _ll, _i, _vp, _ll, _i]),
+    "bhip_distort_model_dev_f32": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _i, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _ll, _i, _vp, _ll, _i]),
+    "bhip_distort_build_map": (_i, [_vp, _i, _fp, _i, _i, _vp]),
     "bhip_corner_intensity_dev_f32": (_i, [_vp, _i, _i, _f, _vp, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i]),
     "bhip_sobel_dev_u8_s16": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _vp, _vp, _ll, _i, _i]),
     "bhip_three_dev_u8_s16": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _vp, _vp, _ll, _i, _i]),

@@ -15,7 +15,7 @@
 // host export calls can overwrite what it staged.
 struct CtxScratch {
 	DevBuf in0, in1, out0, out1, tmp0, tmp1;                                 // staging
-	DevBuf work, assocCol, nmsBitmap, nmsPrefix, nmsPos, ipTmp, ipKernel, fast, disparity;   // device side
+	DevBuf work, assocCol, nmsBitmap, nmsPrefix, nmsPos, ipTmp, ipKernel, fast, disparity, distortMap;   // device side
 	AssocMfmaWork mfma;
 	int assocExactOnly = -1;  // BHIP_ASSOC_EXACT=1 forces the exact VALU association kernels (parity cross-check)
 };
@@ -1500,6 +1500,120 @@ int bhip_disparity_bm_dev_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg
 								 const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, float* dev_disp,
 								 long long dImageStride, int dStride) {
 	return disparityDev<float>(ctx, cfg, dev_left, lImageStride, lStride, dev_right, rImageStride, rStride, width, height, batch, dev_disp, dImageStride, dStride);
+}
+
+// ---- image remap (distort.hip): ImageDistort.apply of FactoryDistort.distortSB, GrayU8 / GrayF32, NEAREST_NEIGHBOR / BILINEAR, ZERO / EXTENDED ----
+extern "C++" {
+// the checks every form shares: what is refused (include/boofhip.h), before anything is staged or launched
+static int distortCheck(bhip_ctx* ctx, const DistortCoords& co, int dw, int dh, const DistortCrop& crop, int interp, int border) {
+	if (co.model == 0 ? !co.map : ((co.model != BHIP_DISTORT_AFFINE && co.model != BHIP_DISTORT_HOMOGRAPHY) || !co.coeff))
+		return bhip_fail(ctx, BHIP_ERR_INVALID, "distort: no map, or no such model");
+	if (co.mapImageStride < 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "distort: negative map stride");
+	if (crop.x0 < 0 || crop.y0 < 0 || crop.x0 > crop.x1 || crop.y0 > crop.y1 || crop.x1 > dw || crop.y1 > dh)
+		return bhip_fail(ctx, BHIP_ERR_INVALID, "distort: the crop is not inside the destination");
+	if (interp != BHIP_INTERP_NEAREST_NEIGHBOR && interp != BHIP_INTERP_BILINEAR)
+		return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "distort on the GPU: NEAREST_NEIGHBOR or BILINEAR interpolation");
+	if (border != BHIP_BORDER_ZERO && border != BHIP_BORDER_EXTENDED) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "distort on the GPU: ZERO or EXTENDED border");
+	return BHIP_OK;
+}
+
+template <class T>
+static int distortDev(bhip_ctx* ctx, const T* dev_src, long long sImageStride, int sStride, int sw, int sh, int batch, const DistortCoords& co, int dw, int dh,
+					  const DistortCrop& crop, int interp, int border, int renderAll, T* dev_dst, long long dImageStride, int dStride, uint8_t* dev_mask,
+					  long long mImageStride, int mStride) {
+	CHECK_CTX(ctx);
+	const DevImg<const T> src{dev_src, sImageStride, sStride, sw, sh, batch};
+	const DevImg<T> dst{dev_dst, dImageStride, dStride, dw, dh, batch};
+	DevImg<uint8_t> mask{nullptr, 0, 0, dw, dh, batch};
+	CHECK_IMG(ctx, src);
+	CHECK_IMG(ctx, dst);
+	if (dev_mask) {
+		mask = {dev_mask, mImageStride, mStride, dw, dh, batch};
+		CHECK_IMG(ctx, mask);
+	}
+	BHIP_TRY(distortCheck(ctx, co, dw, dh, crop, interp, border));
+	return bhip_launch_distort<T>(ctx, src, co, crop, interp, border, renderAll, dst, mask);
+}
+
+template <class T>
+static int distortHost(bhip_ctx* ctx, const T* src, int sStart, int sStride, int sw, int sh, DistortCoords co, int dw, int dh, const DistortCrop& crop, int interp,
+					   int border, int renderAll, T* dst, int dStart, int dStride, uint8_t* mask, int mStart, int mStride) {
+	const HostImg<const T> hs{src, sStart, sStride, sw, sh};
+	const HostImg<T> hd{dst, dStart, dStride, dw, dh};
+	const HostImg<uint8_t> hm{mask, mStart, mStride, dw, dh};
+	CHECK_CTX(ctx);
+	CHECK_IMG(ctx, hs);
+	CHECK_IMG(ctx, hd);
+	if (mask) CHECK_IMG(ctx, hm);
+	BHIP_TRY(distortCheck(ctx, co, dw, dh, crop, interp, border));
+	CtxScratch* sc = scratchOf(ctx);
+	DevImg<T> ds, dd;
+	DevImg<uint8_t> dm{nullptr, 0, 0, dw, dh, 1};
+	// the destination is written as a whole only when every pixel is rendered; the mask whenever the crop is the whole image
+	const bool whole = crop.x0 == 0 && crop.y0 == 0 && crop.x1 == dw && crop.y1 == dh;
+	BHIP_TRY(stageIn(ctx, sc->in0, hs, sw, ds));
+	if (co.model == 0) {   // co.map is the caller's host map
+		BHIP_TRY(sc->distortMap.reserve(ctx, (size_t)dw * dh * 8));
+		BHIP_HIP(ctx, hipMemcpyAsync(sc->distortMap.as<float>(), co.map, (size_t)dw * dh * 8, hipMemcpyHostToDevice, ctx->stream));
+		co.map = sc->distortMap.as<float>();
+	}
+	BHIP_TRY(stageIn(ctx, sc->out0, hd, dw, dd, !(whole && renderAll)));
+	if (mask) BHIP_TRY(stageIn(ctx, sc->out1, hm, dw, dm, !whole));
+	BHIP_TRY(bhip_launch_distort<T>(ctx, ds, co, crop, interp, border, renderAll, dd, dm));
+	BHIP_TRY(stageOut(ctx, hd, dd));
+	if (mask) BHIP_TRY(stageOut(ctx, hm, dm));
+	return bhip_ctx_synchronize(ctx);
+}
+}  // extern "C++"
+
+int bhip_distort_map_u8(bhip_ctx* ctx, const uint8_t* src, int sStart, int sStride, int sw, int sh, const float* map, int dw, int dh, int x0, int y0, int x1,
+						int y1, int interp, int border, int renderAll, uint8_t* dst, int dStart, int dStride, uint8_t* mask, int mStart, int mStride) {
+	return distortHost<uint8_t>(ctx, src, sStart, sStride, sw, sh, {0, map, 0, nullptr}, dw, dh, {x0, y0, x1, y1}, interp, border, renderAll, dst, dStart, dStride, mask, mStart, mStride);
+}
+int bhip_distort_map_f32(bhip_ctx* ctx, const float* src, int sStart, int sStride, int sw, int sh, const float* map, int dw, int dh, int x0, int y0, int x1,
+						 int y1, int interp, int border, int renderAll, float* dst, int dStart, int dStride, uint8_t* mask, int mStart, int mStride) {
+	return distortHost<float>(ctx, src, sStart, sStride, sw, sh, {0, map, 0, nullptr}, dw, dh, {x0, y0, x1, y1}, interp, border, renderAll, dst, dStart, dStride, mask, mStart, mStride);
+}
+// a model of 0 would select the map form: it is no model
+int bhip_distort_model_u8(bhip_ctx* ctx, const uint8_t* src, int sStart, int sStride, int sw, int sh, int model, const float* coeff, int dw, int dh, int x0, int y0,
+						  int x1, int y1, int interp, int border, int renderAll, uint8_t* dst, int dStart, int dStride, uint8_t* mask, int mStart, int mStride) {
+	return distortHost<uint8_t>(ctx, src, sStart, sStride, sw, sh, {model ? model : -1, nullptr, 0, coeff}, dw, dh, {x0, y0, x1, y1}, interp, border, renderAll, dst,
+								dStart, dStride, mask, mStart, mStride);
+}
+int bhip_distort_model_f32(bhip_ctx* ctx, const float* src, int sStart, int sStride, int sw, int sh, int model, const float* coeff, int dw, int dh, int x0, int y0,
+						   int x1, int y1, int interp, int border, int renderAll, float* dst, int dStart, int dStride, uint8_t* mask, int mStart, int mStride) {
+	return distortHost<float>(ctx, src, sStart, sStride, sw, sh, {model ? model : -1, nullptr, 0, coeff}, dw, dh, {x0, y0, x1, y1}, interp, border, renderAll, dst,
+							  dStart, dStride, mask, mStart, mStride);
+}
+int bhip_distort_map_dev_u8(bhip_ctx* ctx, const uint8_t* dev_src, long long sImageStride, int sStride, int sw, int sh, int batch, const float* dev_map,
+							long long mapImageStride, int dw, int dh, int x0, int y0, int x1, int y1, int interp, int border, int renderAll, uint8_t* dev_dst,
+							long long dImageStride, int dStride, uint8_t* dev_mask, long long mImageStride, int mStride) {
+	return distortDev<uint8_t>(ctx, dev_src, sImageStride, sStride, sw, sh, batch, {0, dev_map, mapImageStride, nullptr}, dw, dh, {x0, y0, x1, y1}, interp, border,
+							   renderAll, dev_dst, dImageStride, dStride, dev_mask, mImageStride, mStride);
+}
+int bhip_distort_map_dev_f32(bhip_ctx* ctx, const float* dev_src, long long sImageStride, int sStride, int sw, int sh, int batch, const float* dev_map,
+							 long long mapImageStride, int dw, int dh, int x0, int y0, int x1, int y1, int interp, int border, int renderAll, float* dev_dst,
+							 long long dImageStride, int dStride, uint8_t* dev_mask, long long mImageStride, int mStride) {
+	return distortDev<float>(ctx, dev_src, sImageStride, sStride, sw, sh, batch, {0, dev_map, mapImageStride, nullptr}, dw, dh, {x0, y0, x1, y1}, interp, border,
+							 renderAll, dev_dst, dImageStride, dStride, dev_mask, mImageStride, mStride);
+}
+int bhip_distort_model_dev_u8(bhip_ctx* ctx, const uint8_t* dev_src, long long sImageStride, int sStride, int sw, int sh, int batch, int model, const float* coeff,
+							  int dw, int dh, int x0, int y0, int x1, int y1, int interp, int border, int renderAll, uint8_t* dev_dst, long long dImageStride,
+							  int dStride, uint8_t* dev_mask, long long mImageStride, int mStride) {
+	return distortDev<uint8_t>(ctx, dev_src, sImageStride, sStride, sw, sh, batch, {model ? model : -1, nullptr, 0, coeff}, dw, dh, {x0, y0, x1, y1}, interp, border,
+							   renderAll, dev_dst, dImageStride, dStride, dev_mask, mImageStride, mStride);
+}
+int bhip_distort_model_dev_f32(bhip_ctx* ctx, const float* dev_src, long long sImageStride, int sStride, int sw, int sh, int batch, int model, const float* coeff,
+							   int dw, int dh, int x0, int y0, int x1, int y1, int interp, int border, int renderAll, float* dev_dst, long long dImageStride,
+							   int dStride, uint8_t* dev_mask, long long mImageStride, int mStride) {
+	return distortDev<float>(ctx, dev_src, sImageStride, sStride, sw, sh, batch, {model ? model : -1, nullptr, 0, coeff}, dw, dh, {x0, y0, x1, y1}, interp, border,
+							 renderAll, dev_dst, dImageStride, dStride, dev_mask, mImageStride, mStride);
+}
+int bhip_distort_build_map(bhip_ctx* ctx, int model, const float* coeff, int dw, int dh, float* dev_map) {
+	CHECK_CTX(ctx);
+	if ((model != BHIP_DISTORT_AFFINE && model != BHIP_DISTORT_HOMOGRAPHY) || !coeff || !dev_map || dw <= 0 || dh <= 0)
+		return bhip_fail(ctx, BHIP_ERR_INVALID, "bhip_distort_build_map: no such model, or no coefficients / map / size");
+	return bhip_launch_distort_build_map(ctx, model, coeff, dw, dh, dev_map);
 }
 
 int bhip_select_nbest_f32(bhip_ctx* ctx, const float* intensity, int start, int stride, int width, int height, const int16_t* xy, int n, int target,

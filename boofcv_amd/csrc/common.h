@@ -385,6 +385,26 @@ size_t bhip_disparity_scratch(int width, int height, int batch);   // bytes of d
 template <class OutT>
 int bhip_launch_disparity_bm(bhip_ctx* ctx, DevImg<const uint8_t> left, DevImg<const uint8_t> right, const DispBmParams& c, uint8_t* scratch, DevImg<OutT> out);
 
+// ---------------- image remap, ImageDistort (distort.hip) ----------------
+// where the source coordinates of a destination pixel come from: model == 0, a device map of (x, y) pairs, dw*dh per image and mapImageStride
+// floats from one image's map to the next (0: one map for the batch); otherwise BHIP_DISTORT_AFFINE / _HOMOGRAPHY with 6 / 9 coefficients
+struct DistortCoords {
+	int model;
+	const float* map;
+	long long mapImageStride;
+	const float* coeff;   // host memory
+};
+struct DistortCrop {
+	int x0, y0, x1, y1;
+};
+// ImageDistortBasic_SB / ImageDistortCache_SB apply on every image of a batch: the pixels of the crop of dst (assigned or skipped as renderAll
+// says) and, when mask.data is not null, of the mask.  The caller has validated interp, border, the crop against dst and mask against dst.
+template <class T>
+int bhip_launch_distort(bhip_ctx* ctx, DevImg<const T> src, const DistortCoords& co, const DistortCrop& crop, int interp, int border, int renderAll, DevImg<T> dst,
+						DevImg<uint8_t> mask);
+// the map of a model, dw x dh entries, into device memory
+int bhip_launch_distort_build_map(bhip_ctx* ctx, int model, const float* coeff, int dw, int dh, float* map);
+
 // ---------------- pyramid KLT tracker (klt.hip) ----------------
 #define BHIP_KLT_MAX_LAYERS 8
 #define BHIP_KLT_MAX_RADIUS 7

@@ -12,6 +12,7 @@ Names follow the reference classes the host-buffer forms in boofcv_amd/api.py mi
   DeviceImageOps.nonmaxMinMax   NonMaxBlockSearchStrict.Min / .Max / .MinMax        F:alg/feature/detect/extract/NonMaxBlockSearchStrict.java:56-248
   DeviceImageOps.fast           FastCornerDetector.process                          F:alg/feature/detect/intensity/FastCornerDetector.java:123-189
   DeviceImageOps.disparityBM    StereoDisparity.process (blockMatch, SAD, GrayU8)   F:factory/feature/disparity/FactoryStereoDisparity.java:62-144
+  DeviceImageOps.distort        ImageDistort.apply (distortSB, GrayU8 / GrayF32)    I:alg/distort/ImageDistortBasic_SB.java:56-135, ImageDistortCache_SB.java:76-206
   DeviceImageOps.pyramid        PyramidDiscreteSampleBlur.process                   I:alg/transform/pyramid/PyramidDiscreteSampleBlur.java:88-118
   DeviceImageOps.cornerIntensity  GradientCornerIntensity.process                   F:alg/feature/detect/intensity/impl/ImplSsdCorner_F32.java:62-196
   DeviceImageOps.brief          DescribePointBrief.process                          F:alg/feature/describe/DescribePointBrief.java:73-89
@@ -190,6 +191,69 @@ class DeviceImageOps:
             raise IllegalArgumentException("input and disparity shapes differ")
         fn = self.L.bhip_disparity_bm_dev_u8_f32 if subpixel else self.L.bhip_disparity_bm_dev_u8_u8
         _check(self.ctx, fn(self.ctx._h, C.byref(config._c()) if config is not None else None, lp, lis, lrs, rp, ris, rrs, W, H, B, op, ois, ors))
+        return out
+
+    def distortBuildMap(self, model, coeff, dw, dh, out=None):
+        """bhip_distort_build_map: the [dh,dw,2] float32 map of an affine (model 1, six coefficients) or homography (model 2, nine) model"""
+        coeff = np.ascontiguousarray(coeff, np.float32).reshape(-1)
+        if out is None:
+            out = torch.empty((int(dh), int(dw), 2), dtype=torch.float32, device=self.device)
+        if out.dtype != torch.float32 or tuple(out.shape) != (int(dh), int(dw), 2) or not out.is_contiguous() or not out.is_cuda:
+            raise IllegalArgumentException("the map is a contiguous [dh,dw,2] float32 CUDA tensor")
+        if coeff.size != {1: 6, 2: 9}.get(int(model), -1):
+            raise IllegalArgumentException("model 1 (affine) takes 6 coefficients, model 2 (homography) 9")
+        _check(self.ctx, self.L.bhip_distort_build_map(self.ctx._h, int(model), coeff.ctypes.data_as(_lib._fp), int(dw), int(dh), C.c_void_p(out.data_ptr())))
+        return out
+
+    def distort(self, src, map=None, model=None, coeff=None, interp=_lib.BHIP_INTERP_BILINEAR, border=_lib.BHIP_BORDER_EXTENDED, renderAll=True, out=None,
+                mask=None, crop=None, shape=None):
+        """ImageDistort.apply on [B,H,W] uint8 / float32 frames of any row / image stride -> `out` of the same type, [B,dh,dw].  The source
+        coordinates come from `map`, a contiguous [dh,dw,2] (shared by the batch) or [B,dh,dw,2] float32 tensor of (x, y) pairs, or from
+        `model` (1 affine, 2 homography) with `coeff`, evaluated in the kernel; then the destination size is out's, or `shape` = (dh, dw), or the
+        source's.  interp / border: the BHIP_INTERP_* / BHIP_BORDER_* codes.  renderAll = False leaves the pixels whose source lies outside the
+        image as they are in `out`.  mask: a [B,dh,dw] uint8 tensor, written 1 / 0.  crop = (x0, y0, x1, y1).  src, out and mask must not overlap."""
+        dt = src.dtype
+        if dt not in (torch.uint8, torch.float32):
+            raise RuntimeError("only uint8 and float32 frames are distorted on the GPU (use the Java path)")
+        sp, sis, srs, sw, sh, B = _geom(src, dt)
+        if (map is None) == (model is None):
+            raise IllegalArgumentException("give a map or a model")
+        if map is not None:
+            if map.dtype != torch.float32 or not map.is_cuda or map.dim() not in (3, 4) or map.shape[-1] != 2 or not map.is_contiguous():
+                raise IllegalArgumentException("the map is a contiguous [dh,dw,2] or [B,dh,dw,2] float32 CUDA tensor")
+            if map.dim() == 4 and map.shape[0] != B:
+                raise IllegalArgumentException("one map, or one per image")
+            dh, dw = int(map.shape[-3]), int(map.shape[-2])
+            mis = 2 * dh * dw if map.dim() == 4 else 0
+        elif out is not None:
+            dh, dw = int(out.shape[-2]), int(out.shape[-1])
+        else:
+            dh, dw = (sh, sw) if shape is None else (int(shape[0]), int(shape[1]))
+        if out is None:
+            if not renderAll or crop is not None:
+                out = torch.zeros((B, dh, dw), dtype=dt, device=src.device)
+                torch.cuda.current_stream(src.device).synchronize()   # the fill runs on torch's stream: order it before the kernel
+            else:
+                out = torch.empty((B, dh, dw), dtype=dt, device=src.device)
+        op, ois, ors, W2, H2, B2 = _geom(out, dt)
+        if (W2, H2, B2) != (dw, dh, B):
+            raise IllegalArgumentException("the destination has the map's size and the source's batch")
+        mp, mis2, mrs = None, 0, 0
+        if mask is not None:
+            mp, mis2, mrs, W3, H3, B3 = _geom(mask, torch.uint8)
+            if (W3, H3, B3) != (dw, dh, B):
+                raise IllegalArgumentException("the mask has the destination's shape")
+        x0, y0, x1, y1 = (0, 0, dw, dh) if crop is None else (int(v) for v in crop)
+        tail = (dw, dh, x0, y0, x1, y1, int(interp), int(border), 1 if renderAll else 0, op, ois, ors, mp, mis2, mrs)
+        if map is not None:
+            fn = self.L.bhip_distort_map_dev_u8 if dt == torch.uint8 else self.L.bhip_distort_map_dev_f32
+            _check(self.ctx, fn(self.ctx._h, sp, sis, srs, sw, sh, B, C.c_void_p(map.data_ptr()), mis, *tail))
+        else:
+            coeff = np.ascontiguousarray(coeff, np.float32).reshape(-1)
+            if coeff.size != {1: 6, 2: 9}.get(int(model), -1):
+                raise IllegalArgumentException("model 1 (affine) takes 6 coefficients, model 2 (homography) 9")
+            fn = self.L.bhip_distort_model_dev_u8 if dt == torch.uint8 else self.L.bhip_distort_model_dev_f32
+            _check(self.ctx, fn(self.ctx._h, sp, sis, srs, sw, sh, B, int(model), coeff.ctypes.data_as(_lib._fp), *tail))
         return out
 
     def cornerIntensity(self, kind, radius, kappa, dx, dy, out=None, weighted=False):

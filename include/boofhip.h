@@ -293,6 +293,53 @@ int bhip_disparity_bm_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, con
 							int rStride, int width, int height, uint8_t* disp, int dStart, int dStride);
 int bhip_disparity_bm_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* left, int lStart, int lStride, const uint8_t* right, int rStart,
 							 int rStride, int width, int height, float* disp, int dStart, int dStride);
+/* ---- image remap: ImageDistort<T,T>, GrayU8 -> GrayU8 and GrayF32 -> GrayF32 (distort.hip) ---- */
+typedef enum { BHIP_INTERP_NEAREST_NEIGHBOR = 0, BHIP_INTERP_BILINEAR = 1, BHIP_INTERP_BICUBIC = 2, BHIP_INTERP_POLYNOMIAL4 = 3 } bhip_interp;   /* InterpolationType ordinals */
+typedef enum { BHIP_BORDER_SKIP = 0, BHIP_BORDER_EXTENDED = 1, BHIP_BORDER_NORMALIZED = 2, BHIP_BORDER_REFLECT = 3, BHIP_BORDER_WRAP = 4, BHIP_BORDER_ZERO = 5 } bhip_border;   /* BorderType ordinals */
+typedef enum { BHIP_DISTORT_AFFINE = 1, BHIP_DISTORT_HOMOGRAPHY = 2 } bhip_distort_model;
+/* ImageDistort.apply(src, dst), apply(src, dst, mask) and apply(src, dst, x0, y0, x1, y1) of FactoryDistort.distortSB(cached, interp, type)
+ * (I:factory/distort/FactoryDistort.java:96-122; callers I:alg/distort/DistortImageOps.java:70-145) with interp from
+ * FactoryInterpolation.createPixelS(0, 255, NEAREST_NEIGHBOR | BILINEAR, ZERO | EXTENDED, type): ImageDistortCache_SB
+ * (I:alg/distort/ImageDistortCache_SB.java:76-206) on a map the caller has filled with its PixelTransform, which is also what
+ * ImageDistortBasic_SB (I:alg/distort/ImageDistortBasic_SB.java:56-135) computes with that transform.  Single-threaded reference results, bit
+ * for bit (the library is built with -ffp-contract=off).
+ * For every destination pixel (x, y) of the crop [x0,x1) x [y0,y1), with a source of sw x sh and (sx, sy) = map[y*dw + x]:
+ *   inside   sx >= 0 && sx <= sw-1 && sy >= 0 && sy <= sh-1 (the int bounds converted to float).
+ *   render   renderAll != 0: dst = assign(get(sx, sy)) for every pixel.  renderAll == 0 (what BorderType.SKIP becomes in
+ *            DistortImageOps.distortSingle and RectifyImageOps.rectifyImage, with border EXTENDED): only the inside pixels are assigned, every
+ *            other pixel of dst keeps what it held.
+ *   mask     when not NULL, 1 for an inside pixel and 0 otherwise, for every pixel of the crop in both render modes.
+ *   get      BILINEAR (ImplBilinearPixel_U8.java:48-90, ImplBilinearPixel_F32.java:48-90): when !(sx < 0 || sy < 0 || sx > sw-2 || sy > sh-2),
+ *            xt = (int)sx, yt = (int)sy, ax = sx - xt, ay = sy - yt and the taps are pixels; otherwise xf = (float)floor(sx), xt = (int)xf,
+ *            ax = sx - xf (same in y) and the taps come from the border.  val = (1-ax)*(1-ay)*p(xt,yt); val += ax*(1-ay)*p(xt+1,yt);
+ *            val += ax*ay*p(xt+1,yt+1); val += (1-ax)*ay*p(xt,yt+1); each product left to right, in float.
+ *            NEAREST_NEIGHBOR (NearestNeighborPixel_U8.java:56-72, NearestNeighborPixel_F32.java:56-72): pixel ((int)sx, (int)sy) when
+ *            !(sx < 0 || sy < 0 || sx > sw-1 || sy > sh-1), otherwise the border at ((int)floor(sx), (int)floor(sy)).
+ *   border   ZERO (ImageBorderValue, value 0): the pixel when in bounds, else 0.  EXTENDED (BorderIndex1D_Extend): each coordinate clamped
+ *            to [0, n-1].
+ *   assign   AssignPixelValue_SB.java:31-59: GrayF32 stores the float; GrayU8 stores (byte)value, Java's float -> int (toward zero, saturating,
+ *            NaN -> 0) and then the low eight bits.
+ * Domain: coordinates are finite with |v| <= 2^30.  For NaN, infinities and anything larger nothing outside the source view is read and
+ * nothing outside the crop is written; the values stored for such pixels are unspecified.
+ * Deviations: (1) ImageDistortCache_SB.renderAll indexes its map with the destination's array index (map[indexDst], :143), which is only
+ * right for a destination with startIndex = 0 and stride = width; the library indexes the map by y*dw + x for every destination layout --
+ * the same result for a dense destination, and what ImageDistortBasic_SB computes.  (2) Source and destination (and mask) must not overlap;
+ * this is not detected.
+ * BHIP_ERR_UNSUPPORTED and nothing is written: interp other than NEAREST_NEIGHBOR or BILINEAR; border other than ZERO or EXTENDED (REFLECT
+ * and WRAP index outside the array in the reference for far coordinates, NORMALIZED is a different class).
+ * BHIP_ERR_INVALID and nothing is written: an empty source or destination, a crop that is not inside the destination (0 <= x0 <= x1 <= dw,
+ * 0 <= y0 <= y1 <= dh), a NULL map.
+ * Host form: one image; map is dw*dh interleaved (x, y) float pairs in host memory; mask may be NULL (mStart, mStride then unread). */
+int bhip_distort_map_u8(bhip_ctx* ctx, const uint8_t* src, int sStart, int sStride, int sw, int sh, const float* map, int dw, int dh, int x0, int y0, int x1,
+						int y1, int interp, int border, int renderAll, uint8_t* dst, int dStart, int dStride, uint8_t* mask, int mStart, int mStride);
+int bhip_distort_map_f32(bhip_ctx* ctx, const float* src, int sStart, int sStride, int sw, int sh, const float* map, int dw, int dh, int x0, int y0, int x1,
+						 int y1, int interp, int border, int renderAll, float* dst, int dStart, int dStride, uint8_t* mask, int mStart, int mStride);
+/* The host form with the coordinates computed from a model instead of read from a map: see bhip_distort_model_dev_u8 for the models, their
+ * formulas and what they claim. */
+int bhip_distort_model_u8(bhip_ctx* ctx, const uint8_t* src, int sStart, int sStride, int sw, int sh, int model, const float* coeff, int dw, int dh, int x0, int y0,
+						  int x1, int y1, int interp, int border, int renderAll, uint8_t* dst, int dStart, int dStride, uint8_t* mask, int mStart, int mStride);
+int bhip_distort_model_f32(bhip_ctx* ctx, const float* src, int sStart, int sStride, int sw, int sh, int model, const float* coeff, int dw, int dh, int x0, int y0,
+						   int x1, int y1, int interp, int border, int renderAll, float* dst, int dStart, int dStride, uint8_t* mask, int mStart, int mStride);
 /* SelectNBestFeatures.process(intensity, corners, positive) + getBestCorners() (F:alg/feature/detect/extract/SelectNBestFeatures.java:51-97):
  * n <= target copies the list; otherwise keys = -intensity (positive) or +intensity and org.ddogleg.sorting.QuickSelect.selectIndex(keys,
  * target, n, indexes) decides which `target` corners are kept and in which order.  ddogleg is not part of the reference tree: the routine
@@ -538,6 +585,35 @@ int bhip_disparity_bm_dev_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg,
 int bhip_disparity_bm_dev_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* dev_left, long long lImageStride, int lStride,
 								 const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, float* dev_disp,
 								 long long dImageStride, int dStride);
+/* bhip_distort_map_u8 / _f32 on a batch of device images (strides in elements; any byte alignment of a GrayU8 view): image b reads
+ * dev_src + b*sImageStride (sw x sh) and the map dev_map + b*mapImageStride (dw*dh interleaved float (x, y) pairs, dense; mapImageStride in
+ * floats, 0 = one map shared by the batch, the usual case of one map per camera), and writes the crop of dev_dst + b*dImageStride (dw x dh)
+ * and, when dev_mask is not NULL, of dev_mask + b*mImageStride.  One launch, no host synchronisation. */
+int bhip_distort_map_dev_u8(bhip_ctx* ctx, const uint8_t* dev_src, long long sImageStride, int sStride, int sw, int sh, int batch, const float* dev_map,
+							long long mapImageStride, int dw, int dh, int x0, int y0, int x1, int y1, int interp, int border, int renderAll, uint8_t* dev_dst,
+							long long dImageStride, int dStride, uint8_t* dev_mask, long long mImageStride, int mStride);
+int bhip_distort_map_dev_f32(bhip_ctx* ctx, const float* dev_src, long long sImageStride, int sStride, int sw, int sh, int batch, const float* dev_map,
+							 long long mapImageStride, int dw, int dh, int x0, int y0, int x1, int y1, int interp, int border, int renderAll, float* dev_dst,
+							 long long dImageStride, int dStride, uint8_t* dev_mask, long long mImageStride, int mStride);
+/* The same with the coordinates computed in the kernel from `coeff` (host memory, passed by value to the kernel) instead of read from a map:
+ * ImageDistortBasic_SB with PixelTransformAffine_F32 / PixelTransformHomography_F32 (I:alg/distort/PixelTransformAffine_F32.java,
+ * PixelTransformHomography_F32.java).  With x, y converted from int to float first and every sum left to right, in float:
+ *   BHIP_DISTORT_AFFINE      coeff = a11 a12 a21 a22 tx ty:     sx = tx + a11*x + a12*y,  sy = ty + a21*x + a22*y
+ *   BHIP_DISTORT_HOMOGRAPHY  coeff = a11 .. a33, row-major:    z = a31*x + a32*y + a33,  sx = (a11*x + a12*y + a13)/z,  sy = (a21*x + a22*y + a23)/z
+ *                            (correctly rounded divisions)
+ * These formulas are the library's definition.  They restate georegression's AffinePointOps_F32.transform and HomographyPointOps_F32.transform,
+ * whose source is not part of the reference tree, so their order of operations is unconfirmed: a Java caller who needs bit equality with
+ * ImageDistortBasic_SB fills a map with its own transform and uses the map form.  The result is, bit for bit, the map form on the map
+ * bhip_distort_build_map writes.  BHIP_ERR_INVALID: a model other than the two, a NULL coeff. */
+int bhip_distort_model_dev_u8(bhip_ctx* ctx, const uint8_t* dev_src, long long sImageStride, int sStride, int sw, int sh, int batch, int model, const float* coeff,
+							  int dw, int dh, int x0, int y0, int x1, int y1, int interp, int border, int renderAll, uint8_t* dev_dst, long long dImageStride,
+							  int dStride, uint8_t* dev_mask, long long mImageStride, int mStride);
+int bhip_distort_model_dev_f32(bhip_ctx* ctx, const float* dev_src, long long sImageStride, int sStride, int sw, int sh, int batch, int model, const float* coeff,
+							   int dw, int dh, int x0, int y0, int x1, int y1, int interp, int border, int renderAll, float* dev_dst, long long dImageStride,
+							   int dStride, uint8_t* dev_mask, long long mImageStride, int mStride);
+/* The map of a model: dev_map[2*(y*dw + x)], [.. + 1] = (sx, sy) of the formulas above for 0 <= x < dw, 0 <= y < dh (what
+ * ImageDistortCache_SB.init, I:alg/distort/ImageDistortCache_SB.java:111-134, computes on the host).  No host synchronisation. */
+int bhip_distort_build_map(bhip_ctx* ctx, int model, const float* coeff, int dw, int dh, float* dev_map);
 /* GradientCornerIntensity.process (see bhip_corner_intensity_f32) on a batch; derivX / derivY share dImageStride / dStride */
 int bhip_corner_intensity_dev_f32(bhip_ctx* ctx, int kind, int radius, float kappa, const float* dev_dx, const float* dev_dy, long long dImageStride,
 								  int dStride, int width, int height, int batch, float* dev_intensity, long long iImageStride, int iStride);
