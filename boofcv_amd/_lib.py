@@ -43,6 +43,25 @@ class DisparityBmCfg(C.Structure):
                 ("maxPerPixelError", C.c_double), ("validateRtoL", C.c_int), ("texture", C.c_double)]
 
 
+class BgBasicCfg(C.Structure):
+    _fields_ = [("learnRate", C.c_float), ("threshold", C.c_float), ("unknownValue", C.c_int)]
+
+
+class BgGaussianCfg(C.Structure):
+    _fields_ = [("learnRate", C.c_float), ("threshold", C.c_float), ("initialVariance", C.c_float), ("minimumDifference", C.c_float),
+                ("unknownValue", C.c_int)]
+
+
+class BgGmmCfg(C.Structure):
+    _fields_ = [("learningPeriod", C.c_float), ("initialVariance", C.c_float), ("decayCoefient", C.c_float), ("maxDistance", C.c_float),
+                ("numberOfGaussian", C.c_int), ("significantWeight", C.c_float), ("unknownValue", C.c_int)]
+
+
+# bhip_bg_algorithm, bhip_image_family, bhip_pixel_type
+BHIP_BG_BASIC, BHIP_BG_GAUSSIAN, BHIP_BG_GMM = range(3)
+BHIP_IMAGE_GRAY, BHIP_IMAGE_PLANAR, BHIP_IMAGE_INTERLEAVED = range(3)
+BHIP_PIXEL_U8, BHIP_PIXEL_F32 = range(2)
+
 # KltTrackFault ordinals (+ the library's own code for positions where the reference throws)
 BHIP_KLT_SUCCESS, BHIP_KLT_DRIFTED, BHIP_KLT_OUT_OF_BOUNDS, BHIP_KLT_FAILED, BHIP_KLT_LARGE_ERROR, BHIP_KLT_REFERENCE_THROWS = range(6)
 
@@ -199,6 +218,34 @@ SIGNATURES = {
     "bhip_klt_dev_view_u8": (_i, [_vp, P(_vp), P(_vp), P(_vp), P(_vp), P(_vp), P(_vp), P(_vp), P(_vp), _ip, _llp]),
     "bhip_klt_set_description_u8": (_i, [_vp, P(KltCfg), _i, _u8p, _i, _i, _i16p, _i16p, _i, _i, _i, _i, _fp, _i, _fp, _fp, _fp, _fp, _u8p]),
     "bhip_klt_track_u8": (_i, [_vp, P(KltCfg), _i, _u8p, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _i, _ip, _fp]),
+    "bhip_bg_basic_cfg_default": (None, [P(BgBasicCfg)]),
+    "bhip_bg_gaussian_cfg_default": (None, [P(BgGaussianCfg)]),
+    "bhip_bg_gmm_cfg_default": (None, [P(BgGmmCfg)]),
+    "bhip_bg_create_basic": (_i, [_vp, P(BgBasicCfg), _i, _i, _i, _i, _i, _i, P(_vp)]),
+    "bhip_bg_create_gaussian": (_i, [_vp, P(BgGaussianCfg), _i, _i, _i, _i, _i, _i, P(_vp)]),
+    "bhip_bg_create_gmm": (_i, [_vp, P(BgGmmCfg), _i, _i, _i, _i, _i, _i, P(_vp)]),
+    "bhip_bg_destroy": (_i, [_vp]),
+    "bhip_bg_reset": (_i, [_vp, _i]),
+    "bhip_bg_set_unknown_value": (_i, [_vp, _i]),
+    "bhip_bg_set_common_unknown_value": (_i, [_vp, _i]),
+    "bhip_bg_set_threshold": (_i, [_vp, _f]),
+    "bhip_bg_set_learn_rate": (_i, [_vp, _f]),
+    "bhip_bg_set_initial_variance": (_i, [_vp, _f]),
+    "bhip_bg_set_minimum_difference": (_i, [_vp, _f]),
+    "bhip_bg_set_learning_period": (_i, [_vp, _f]),
+    "bhip_bg_set_significant_weight": (_i, [_vp, _f]),
+    "bhip_bg_set_max_distance": (_i, [_vp, _f]),
+    "bhip_bg_update_dev_u8": (_i, [_vp, _vp, _ll, _ll, _ll, _i, _i, _vp, _ll, _ll, _i]),
+    "bhip_bg_update_dev_f32": (_i, [_vp, _vp, _ll, _ll, _ll, _i, _i, _vp, _ll, _ll, _i]),
+    "bhip_bg_segment_dev_u8": (_i, [_vp, _vp, _ll, _ll, _i, _vp, _ll, _i]),
+    "bhip_bg_segment_dev_f32": (_i, [_vp, _vp, _ll, _ll, _i, _vp, _ll, _i]),
+    "bhip_bg_update_u8": (_i, [_vp, _u8p, _ll, _ll, _ll, _ll, _i, _i, _u8p, _ll, _ll, _ll, _i]),
+    "bhip_bg_update_f32": (_i, [_vp, _fp, _ll, _ll, _ll, _ll, _i, _i, _u8p, _ll, _ll, _ll, _i]),
+    "bhip_bg_segment_u8": (_i, [_vp, _u8p, _ll, _ll, _ll, _i, _u8p, _ll, _ll, _i]),
+    "bhip_bg_segment_f32": (_i, [_vp, _fp, _ll, _ll, _ll, _i, _u8p, _ll, _ll, _i]),
+    "bhip_bg_model_floats": (_i, [_vp, _llp]),
+    "bhip_bg_fetch_model": (_i, [_vp, _i, _fp]),
+    "bhip_bg_store_model": (_i, [_vp, _i, _fp]),
 }
 
 _lib = None

@@ -405,6 +405,36 @@ int bhip_launch_distort(bhip_ctx* ctx, DevImg<const T> src, const DistortCoords&
 // the map of a model, dw x dh entries, into device memory
 int bhip_launch_distort_build_map(bhip_ctx* ctx, int model, const float* coeff, int dw, int dh, float* map);
 
+// ---------------- stationary background models (background.hip) ----------------
+#define BHIP_BG_MAX_BANDS 4
+#define BHIP_BG_MAX_GAUSSIANS 8   // the mixture is a register array of this many slots at most
+// what a bhip_bg was created for.  bands: 0 = a single-band Gray image (the reference's *_SB classes), 1..4 = a Planar image of that many bands
+// (*_PL / *_MB); maxGaussians: GMM only
+struct BgShape {
+	int alg, bands, maxGaussians, width, height, streams;
+};
+// the fields of the three Java classes (those the algorithm does not have are unused)
+struct BgConfig {
+	float learnRate, threshold, initialVariance, minimumDifference;          // Basic / Gaussian
+	float learningPeriod, decay, maxDistance, significantWeight;             // GMM (and initialVariance)
+	int unknownValue;
+};
+// frames or masks of a batch of streams: element (stream, frame, band, y, x) at data[stream * streamStride + frame * frameStride +
+// band * bandStride + y * stride + x]
+template <class T>
+struct BgFrames {
+	T* data;
+	long long streamStride, frameStride, bandStride;
+	int stride, numFrames;
+};
+int bhip_bg_components(const BgShape& sh);   // float planes of one stream's model
+double bhip_bg_bytes(const BgShape& sh, int pixelBytes, int numFrames, bool masks, bool segment);   // HBM bytes of one launch
+// segment == false: updateBackground(frame_t[, mask_t]) for t = 0 .. numFrames-1 on every stream (m.data == nullptr: no masks).
+// segment == true: segment(frame, mask) with the one frame of every stream.  state: device [streams][2] = {initialised, GMM common.unknownValue}
+template <class T>
+int bhip_launch_background(bhip_ctx* ctx, const BgShape& sh, const BgConfig& cfg, const BgFrames<const T>& f, const BgFrames<uint8_t>& m, float* model,
+						   const int* state, bool segment);
+
 // ---------------- pyramid KLT tracker (klt.hip) ----------------
 #define BHIP_KLT_MAX_LAYERS 8
 #define BHIP_KLT_MAX_RADIUS 7

@@ -17,6 +17,7 @@ Names follow the reference classes the host-buffer forms in boofcv_amd/api.py mi
   DeviceImageOps.cornerIntensity  GradientCornerIntensity.process                   F:alg/feature/detect/intensity/impl/ImplSsdCorner_F32.java:62-196
   DeviceImageOps.brief          DescribePointBrief.process                          F:alg/feature/describe/DescribePointBrief.java:73-89
   DeviceKltTracker              PointTrackerKltPyramid, batched over sequences      main/boofcv-geo/.../abst/feature/tracker/PointTrackerKltPyramid.java:139-348
+  DeviceBackgroundModel         BackgroundStationaryBasic / Gaussian / Gmm, batched over streams   F:alg/background/stationary/*.java
 """
 import ctypes as C
 
@@ -464,3 +465,162 @@ class DeviceKltTracker:
         out = np.zeros(shape, np.float32)
         _check(self.ctx, self.L.bhip_klt_fetch_layer(self._h, int(seq), int(layer), int(which), out.ctypes.data_as(_lib._fp)))
         return out
+
+
+class DeviceBackgroundModel:
+    """FactoryBackgroundModel.stationaryBasic / stationaryGaussian / stationaryGmm for S independent camera streams at once, on one bhip_bg
+    (F:factory/background/FactoryBackgroundModel.java:47-64,112-141,193-225; stream s is one Java object).
+
+    algorithm   "basic", "gaussian" or "gmm", with config a ConfigBackgroundBasic / ConfigBackgroundGaussian / ConfigBackgroundGmm (None: the
+                GMM defaults); the factory's rules hold (stationaryBasic does not forward config.unknownValue)
+    dtype       torch.uint8 or torch.float32
+    bands       0: Gray frames [S,T,H,W]; 1..4: Planar frames [S,T,B,H,W]
+    update()    updateBackground(frame_t[, mask_t]) for the T frames of every stream in one launch that keeps each pixel's model in registers;
+                masks: None, True (allocated) or a uint8 [S,T,H,W] tensor -> the masks
+    segment()   segment(frame, mask) with frames [S,(B,)H,W] -> uint8 [S,H,W]
+    Frames and masks may be strided views (unit stride along x).  The handle is created at the first call, for its stream count and frame size."""
+    ALGORITHMS = ("basic", "gaussian", "gmm")
+
+    def __init__(self, algorithm, config=None, dtype=torch.uint8, bands=0, ctx=None, device=0):
+        from . import api
+        if algorithm not in self.ALGORITHMS:
+            raise IllegalArgumentException("algorithm must be one of %s" % (self.ALGORITHMS,))
+        if dtype not in (torch.uint8, torch.float32):
+            raise RuntimeError("only uint8 and float32 frames are implemented on the GPU (use the Java path)")
+        if config is None and algorithm == "gmm":
+            config = api.ConfigBackgroundGmm()
+        elif config is None:
+            raise IllegalArgumentException("ConfigBackgroundBasic / ConfigBackgroundGaussian: threshold has no default")
+        else:
+            config.checkValidity()
+        self.ctx = ctx or Context(device, stream=torch.cuda.current_stream(device).cuda_stream)
+        self.L = _lib.load()
+        self.device = torch.device("cuda", self.ctx.device)
+        self.algorithm, self.config, self.dtype, self.bands = algorithm, config, dtype, int(bands)
+        self._h = None
+        self._shape = None          # (S, H, W)
+        self._unknown = None if algorithm == "basic" else config.unknownValue
+        self.ctx._children.add(self)
+
+    def close(self):
+        if self._h:
+            self.L.bhip_bg_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _create(self, S, H, W):
+        if self._h:
+            if self._shape != (S, H, W):
+                raise IllegalArgumentException("this model was created for %d streams of %d x %d frames" % (self._shape[0], self._shape[2], self._shape[1]))
+            return
+        c = self.config
+        family = _lib.BHIP_IMAGE_PLANAR if self.bands else _lib.BHIP_IMAGE_GRAY
+        pixel = _lib.BHIP_PIXEL_U8 if self.dtype == torch.uint8 else _lib.BHIP_PIXEL_F32
+        h = C.c_void_p()
+        if self.algorithm == "basic":
+            cfg = _lib.BgBasicCfg(c.learnRate, c.threshold, c.unknownValue)
+            st = self.L.bhip_bg_create_basic(self.ctx._h, C.byref(cfg), family, pixel, self.bands, W, H, S, C.byref(h))
+        elif self.algorithm == "gaussian":
+            cfg = _lib.BgGaussianCfg(c.learnRate, c.threshold, c.initialVariance, c.minimumDifference, c.unknownValue)
+            st = self.L.bhip_bg_create_gaussian(self.ctx._h, C.byref(cfg), family, pixel, self.bands, W, H, S, C.byref(h))
+        else:
+            cfg = _lib.BgGmmCfg(c.learningPeriod, c.initialVariance, c.decayCoefient, c.maxDistance, c.numberOfGaussian, c.significantWeight, c.unknownValue)
+            st = self.L.bhip_bg_create_gmm(self.ctx._h, C.byref(cfg), family, pixel, self.bands, W, H, S, C.byref(h))
+        _check(self.ctx, st)
+        self._h, self._shape = h, (S, H, W)
+        if self.algorithm == "basic" and self._unknown is not None:
+            _check(self.ctx, self.L.bhip_bg_set_unknown_value(self._h, self._unknown))
+
+    def setUnknownValue(self, unknownValue):
+        if unknownValue < 0 or unknownValue > 255:
+            raise IllegalArgumentException("out of range. 0 to 255")
+        self._unknown = int(unknownValue)
+        if self._h:
+            _check(self.ctx, self.L.bhip_bg_set_unknown_value(self._h, self._unknown))
+
+    def set(self, name, value):
+        """a setter of the Java class on every stream: threshold, learn_rate, initial_variance, minimum_difference, learning_period,
+        significant_weight, max_distance"""
+        if not self._h:
+            raise IllegalArgumentException("the model is created by the first update() or segment()")
+        _check(self.ctx, getattr(self.L, "bhip_bg_set_" + name)(self._h, float(value)))
+
+    def _frames(self, t, lead, what):
+        """t: [S, (T,) (B,) H, W] with `lead` leading dimensions -> (ptr, strides of the leading dimensions + band, row stride, sizes)"""
+        nd = lead + (1 if self.bands else 0) + 2
+        if t.dim() != nd or t.dtype != self.dtype or not t.is_cuda:
+            raise IllegalArgumentException("%s: expected a %d-dimensional %s CUDA tensor" % (what, nd, str(self.dtype).replace("torch.", "")))
+        if self.bands and t.shape[lead] != self.bands:
+            raise IllegalArgumentException("%s: expected %d bands" % (what, self.bands))
+        if t.shape[-1] > 1 and t.stride(-1) != 1:
+            raise IllegalArgumentException("the last dimension must be contiguous")
+        if any(t.shape[i] > 1 and t.stride(i) < 0 for i in range(nd)):
+            raise IllegalArgumentException("strides must not be negative")
+        W = t.shape[-1]
+        row = t.stride(-2) if t.shape[-2] > 1 else max(W, t.stride(-2))
+        band = t.stride(lead) if self.bands else 0
+        return C.c_void_p(t.data_ptr()), [t.stride(i) for i in range(lead)], band, row
+
+    def _masks(self, m, shape, what):
+        if m.dtype != torch.uint8 or not m.is_cuda or tuple(m.shape) != tuple(shape):
+            raise IllegalArgumentException("%s: expected a uint8 CUDA tensor of shape %s" % (what, tuple(shape)))
+        if m.shape[-1] > 1 and m.stride(-1) != 1:
+            raise IllegalArgumentException("the last dimension must be contiguous")
+        W = m.shape[-1]
+        return C.c_void_p(m.data_ptr()), [m.stride(i) for i in range(m.dim() - 2)], (m.stride(-2) if m.shape[-2] > 1 else max(W, m.stride(-2)))
+
+    def update(self, frames, masks=None):
+        ptr, (ss, fs), band, row = self._frames(frames, 2, "frames")
+        S, T, H, W = frames.shape[0], frames.shape[1], frames.shape[-2], frames.shape[-1]
+        self._create(S, H, W)
+        if masks is True:
+            masks = torch.empty((S, T, H, W), dtype=torch.uint8, device=frames.device)
+        mp, mss, mfs, mrow = None, 0, 0, 0
+        if masks is not None:
+            mp, (mss, mfs), mrow = self._masks(masks, (S, T, H, W), "masks")
+        fn = self.L.bhip_bg_update_dev_u8 if self.dtype == torch.uint8 else self.L.bhip_bg_update_dev_f32
+        _check(self.ctx, fn(self._h, ptr, ss, fs, band, row, T, mp, mss, mfs, mrow))
+        return masks
+
+    def segment(self, frames, out=None):
+        ptr, (ss,), band, row = self._frames(frames, 1, "frames")
+        S, H, W = frames.shape[0], frames.shape[-2], frames.shape[-1]
+        self._create(S, H, W)
+        if out is None:
+            out = torch.empty((S, H, W), dtype=torch.uint8, device=frames.device)
+        mp, (mss,), mrow = self._masks(out, (S, H, W), "out")
+        fn = self.L.bhip_bg_segment_dev_u8 if self.dtype == torch.uint8 else self.L.bhip_bg_segment_dev_f32
+        _check(self.ctx, fn(self._h, ptr, ss, band, row, mp, mss, mrow))
+        return out
+
+    def reset(self, stream=None):
+        if self._h:
+            _check(self.ctx, self.L.bhip_bg_reset(self._h, -1 if stream is None else int(stream)))
+
+    def model(self, stream):
+        """the model of one stream in the reference's layout (include/boofhip.h, bhip_bg_fetch_model), as a float32 NumPy array:
+        Basic [bands][H][W], Gaussian [2*bands][H][W], GMM [H][W*modelStride]"""
+        if not self._h:
+            raise IllegalArgumentException("the model is created by the first update() or segment()")
+        n = C.c_longlong()
+        _check(self.ctx, self.L.bhip_bg_model_floats(self._h, C.byref(n)))
+        out = np.zeros(n.value, np.float32)
+        _check(self.ctx, self.L.bhip_bg_fetch_model(self._h, int(stream), out.ctypes.data_as(_lib._fp)))
+        _, H, W = self._shape
+        return out.reshape(H, -1) if self.algorithm == "gmm" else out.reshape(-1, H, W)
+
+    def storeModel(self, stream, model):
+        """the inverse of model(): installs a model (the stream counts as initialised afterwards)"""
+        if not self._h:
+            raise IllegalArgumentException("the model is created by the first update() or segment()")
+        n = C.c_longlong()
+        _check(self.ctx, self.L.bhip_bg_model_floats(self._h, C.byref(n)))
+        a = np.ascontiguousarray(model, np.float32).reshape(-1)
+        if a.size != n.value:
+            raise IllegalArgumentException("the model of a stream has %d floats" % n.value)
+        _check(self.ctx, self.L.bhip_bg_store_model(self._h, int(stream), a.ctypes.data_as(_lib._fp)))

@@ -22,7 +22,7 @@
  *  - there is no CPU fallback inside the library: without a usable GPU bhip_ctx_create fails;
  *  - handles may be destroyed in any order and more than once: bhip_ctx_destroy releases the device side of every bhip_surf created on
  *    that context (they become inert: every call on them returns BHIP_ERR_INVALID, bhip_surf_destroy then only frees the shell; the same
- *    holds for bhip_klt and bhip_klt_destroy), a
+ *    holds for bhip_klt and bhip_klt_destroy, bhip_bg and bhip_bg_destroy), a
  *    pointer that is not a live handle is refused with BHIP_ERR_INVALID, and once the process is exiting the destroy calls do nothing
  *    (a finaliser that runs after the HIP runtime has shut down is harmless);
  *  - a context must not be destroyed while another thread is inside a call on it or on an object created on it.
@@ -48,6 +48,7 @@ typedef enum {
 typedef struct bhip_ctx bhip_ctx;
 typedef struct bhip_surf bhip_surf;
 typedef struct bhip_klt bhip_klt;   /* pyramid KLT point tracker; same handle rules as bhip_surf */
+typedef struct bhip_bg bhip_bg;     /* stationary background models of a batch of streams; same handle rules as bhip_surf */
 
 /* ---- configuration structs: same field names and defaults as the reference's Config* classes ---- */
 
@@ -725,6 +726,126 @@ int bhip_klt_set_description_u8(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radi
 								float* descY, float* G, uint8_t* ok);
 int bhip_klt_track_u8(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const uint8_t* image, int imgStart, int imgStride, int width, int height,
 					  const float* desc, const float* descX, const float* descY, const float* G, float* xy, int n, int* fault, float* error);
+
+/* ---- stationary background models: FactoryBackgroundModel.stationaryBasic / stationaryGaussian / stationaryGmm (background.hip) ----
+ * BackgroundStationaryBasic_SB / _PL      F:alg/background/stationary/BackgroundStationaryBasic_SB.java:58-123, BackgroundStationaryBasic_PL.java:66-142
+ * BackgroundStationaryGaussian_SB / _PL   F:alg/background/stationary/BackgroundStationaryGaussian_SB.java:58-142, BackgroundStationaryGaussian_PL.java:72-180
+ * BackgroundStationaryGmm_SB / _MB        F:alg/background/stationary/BackgroundStationaryGmm.java:48-78, BackgroundStationaryGmm_SB.java:50-100,
+ *                                         BackgroundStationaryGmm_MB.java:54-105, F:alg/background/BackgroundGmmCommon.java:78-375
+ * factory and configs                     F:factory/background/FactoryBackgroundModel.java:47-64,112-141,193-225, ConfigBackground*.java
+ *
+ * A bhip_bg holds `streams` independent models of one algorithm for frames of one type and shape, resident on the device: stream s is one
+ * Java object.  Frames are GrayU8 / GrayF32 (family GRAY, bands ignored: the *_SB classes) or Planar<GrayU8> / Planar<GrayF32> of 1..4 bands
+ * (family PLANAR: the *_PL / *_MB classes, also for one band).  Model planes and masks equal the single-threaded Java results bit for bit:
+ * plain IEEE fp32 evaluated left to right without fused multiply-add, the one double accumulator of Basic_PL.segment, denormal variances kept
+ * (ConfigBackgroundGaussian.initialVariance is Float.MIN_VALUE), 0/0 = NaN and x/0 = +Inf in Gaussian.segment as in Java.
+ *
+ * Rules taken from the reference:
+ *  - updateBackground(frame, mask) is update, then segment, for Basic and Gaussian (F:alg/background/BackgroundModelStationary.java:48-51);
+ *    GMM writes updateMixture's return value;
+ *  - a stream's first Basic / Gaussian update after creation or bhip_bg_reset initialises it (GConvertImage.convert; Gaussian: the variance
+ *    planes are filled with initialVariance); a GMM stream starts from the zeroed model; an uninitialised stream segments to unknownValue;
+ *  - BackgroundStationaryGaussian tests `background.width == 1` for "not initialised", so a Gaussian model of width 1 never leaves that state:
+ *    every update initialises it again and every mask is unknownValue.  Reproduced;
+ *  - BackgroundGmmCommon.unknownValue is refreshed only inside segment(): a GMM update that creates a pixel's first Gaussian writes the
+ *    unknown value that the stream's last segment() on an initialised model installed, 0 before any.  Kept per stream, untouched by
+ *    bhip_bg_reset (the Java object keeps it too);
+ *  - bhip_bg_create_* is the factory call: config.checkValidity(), the constructor and the factory's setters.  stationaryBasic does not forward
+ *    config.unknownValue (it stays 0 until bhip_bg_set_unknown_value); stationaryGmm installs the config's maxDistance (3) and
+ *    significantWeight (0.01f) over the constructor's 3*3 and min(0.2f, 100/learningPeriod).  The setters validate nothing, as in Java, except
+ *    bhip_bg_set_unknown_value (0..255).
+ * Deviations and limits:
+ *  - width, height and the stream count are fixed at creation; the reference's re-initialisation when the frame size changes and its
+ *    InputSanityCheck exceptions belong to the caller (the Python and Java classes create a new handle);
+ *  - a mask is written, never reshaped; frames and masks must not overlap;
+ *  - BHIP_ERR_UNSUPPORTED: numberOfGaussian > 8 (1..8 are compiled: the mixture lives in registers), more than 4 bands, family INTERLEAVED,
+ *    pixel types other than U8 / F32;
+ *  - BHIP_ERR_INVALID, nothing written: what checkValidity and the constructors reject (learnRate outside [0,1], threshold <= 0,
+ *    initialVariance <= 0, minimumDifference < 0, learningPeriod <= 0, decayCoefient < 0, numberOfGaussian outside 1..255, an unknownValue
+ *    outside 0..255 as in BackgroundModel.setUnknownValue), a NULL Basic or
+ *    Gaussian config (threshold has no default), bands outside 1.. for PLANAR, sizes < 1, a view with stride < width, numFrames < 1, a call of
+ *    the other pixel type, a setter the algorithm does not have, a stream index out of range. */
+typedef enum { BHIP_BG_BASIC = 0, BHIP_BG_GAUSSIAN = 1, BHIP_BG_GMM = 2 } bhip_bg_algorithm;
+typedef enum { BHIP_IMAGE_GRAY = 0, BHIP_IMAGE_PLANAR = 1, BHIP_IMAGE_INTERLEAVED = 2 } bhip_image_family;   /* ImageType.Family */
+typedef enum { BHIP_PIXEL_U8 = 0, BHIP_PIXEL_F32 = 1 } bhip_pixel_type;
+/* F:factory/background/ConfigBackgroundBasic.java */
+typedef struct {
+	float learnRate;      /* 0.05f */
+	float threshold;      /* no default in Java: 0 here, which bhip_bg_create_basic refuses */
+	int unknownValue;     /* 0; not forwarded by stationaryBasic */
+} bhip_bg_basic_cfg;
+/* F:factory/background/ConfigBackgroundGaussian.java */
+typedef struct {
+	float learnRate;          /* 0.05f */
+	float threshold;          /* no default in Java: 0 here, which bhip_bg_create_gaussian refuses */
+	float initialVariance;    /* Float.MIN_VALUE, the smallest denormal */
+	float minimumDifference;  /* 0 */
+	int unknownValue;         /* 0 */
+} bhip_bg_gaussian_cfg;
+/* F:factory/background/ConfigBackgroundGmm.java */
+typedef struct {
+	float learningPeriod;     /* 1000 */
+	float initialVariance;    /* 400 */
+	float decayCoefient;      /* 0.005f */
+	float maxDistance;        /* 3 */
+	int numberOfGaussian;     /* 5 */
+	float significantWeight;  /* 0.01f */
+	int unknownValue;         /* 0 */
+} bhip_bg_gmm_cfg;
+void bhip_bg_basic_cfg_default(bhip_bg_basic_cfg* c);
+void bhip_bg_gaussian_cfg_default(bhip_bg_gaussian_cfg* c);
+void bhip_bg_gmm_cfg_default(bhip_bg_gmm_cfg* c);
+/* family / pixelType: bhip_image_family / bhip_pixel_type; bands: the Planar image's, ignored for GRAY.  cfg NULL: the defaults (GMM only) */
+int bhip_bg_create_basic(bhip_ctx* ctx, const bhip_bg_basic_cfg* cfg, int family, int pixelType, int bands, int width, int height, int streams, bhip_bg** out);
+int bhip_bg_create_gaussian(bhip_ctx* ctx, const bhip_bg_gaussian_cfg* cfg, int family, int pixelType, int bands, int width, int height, int streams, bhip_bg** out);
+int bhip_bg_create_gmm(bhip_ctx* ctx, const bhip_bg_gmm_cfg* cfg, int family, int pixelType, int bands, int width, int height, int streams, bhip_bg** out);
+int bhip_bg_destroy(bhip_bg* bg);
+/* BackgroundModel.reset() of stream `stream`, or of every stream when stream < 0 */
+int bhip_bg_reset(bhip_bg* bg, int stream);
+/* BackgroundModel.setUnknownValue and the setters of BackgroundAlgorithmBasic / BackgroundAlgorithmGaussian / BackgroundAlgorithmGmm, for
+ * every stream.  setLearningPeriod: learningRate = 1.0f / period */
+int bhip_bg_set_unknown_value(bhip_bg* bg, int unknownValue);
+int bhip_bg_set_threshold(bhip_bg* bg, float threshold);                   /* Basic, Gaussian */
+int bhip_bg_set_learn_rate(bhip_bg* bg, float learnRate);                  /* Basic, Gaussian */
+int bhip_bg_set_initial_variance(bhip_bg* bg, float initialVariance);      /* Gaussian, GMM */
+int bhip_bg_set_minimum_difference(bhip_bg* bg, float minimumDifference);  /* Gaussian */
+int bhip_bg_set_learning_period(bhip_bg* bg, float period);                /* GMM */
+int bhip_bg_set_significant_weight(bhip_bg* bg, float significantWeight);  /* GMM */
+int bhip_bg_set_max_distance(bhip_bg* bg, float maxDistance);              /* GMM */
+/* GMM: installs BackgroundGmmCommon.unknownValue of every stream, as a segment() on an initialised model would.  For a caller that replaces a
+ * handle (another frame size) and has to carry the Java object's stale value over */
+int bhip_bg_set_common_unknown_value(bhip_bg* bg, int unknownValue);
+/* updateBackground(frame_t) (dev_masks NULL) or updateBackground(frame_t, mask_t) for t = 0 .. numFrames-1, in order, on every stream, in one
+ * launch that keeps each pixel's model in registers.  Pixel (x, y) of band b of frame t of stream s is
+ * dev_frames[s*streamStride + t*frameStride + b*bandStride + y*stride + x], mask pixel dev_masks[s*mStreamStride + t*mFrameStride + y*mStride + x]
+ * (strides in elements, any byte alignment).  No host synchronisation. */
+int bhip_bg_update_dev_u8(bhip_bg* bg, const uint8_t* dev_frames, long long streamStride, long long frameStride, long long bandStride, int stride, int numFrames,
+						  uint8_t* dev_masks, long long mStreamStride, long long mFrameStride, int mStride);
+int bhip_bg_update_dev_f32(bhip_bg* bg, const float* dev_frames, long long streamStride, long long frameStride, long long bandStride, int stride, int numFrames,
+						   uint8_t* dev_masks, long long mStreamStride, long long mFrameStride, int mStride);
+/* segment(frame, mask) with one frame per stream; the model is not changed */
+int bhip_bg_segment_dev_u8(bhip_bg* bg, const uint8_t* dev_frames, long long streamStride, long long bandStride, int stride, uint8_t* dev_masks,
+						   long long mStreamStride, int mStride);
+int bhip_bg_segment_dev_f32(bhip_bg* bg, const float* dev_frames, long long streamStride, long long bandStride, int stride, uint8_t* dev_masks,
+							long long mStreamStride, int mStride);
+/* the same on host buffers (the first element at frames[start] / masks[mStart]): staged, run through the _dev forms, synchronised */
+int bhip_bg_update_u8(bhip_bg* bg, const uint8_t* frames, long long start, long long streamStride, long long frameStride, long long bandStride, int stride,
+					  int numFrames, uint8_t* masks, long long mStart, long long mStreamStride, long long mFrameStride, int mStride);
+int bhip_bg_update_f32(bhip_bg* bg, const float* frames, long long start, long long streamStride, long long frameStride, long long bandStride, int stride,
+					   int numFrames, uint8_t* masks, long long mStart, long long mStreamStride, long long mFrameStride, int mStride);
+int bhip_bg_segment_u8(bhip_bg* bg, const uint8_t* frames, long long start, long long streamStride, long long bandStride, int stride, uint8_t* masks,
+					   long long mStart, long long mStreamStride, int mStride);
+int bhip_bg_segment_f32(bhip_bg* bg, const float* frames, long long start, long long streamStride, long long bandStride, int stride, uint8_t* masks,
+						long long mStart, long long mStreamStride, int mStride);
+/* The model of one stream in the reference's layout, width*height*components floats (bhip_bg_model_floats):
+ *   Basic     `bands` GrayF32 planes [band][y][x]                     (getBackground())
+ *   Gaussian  Planar<GrayF32>(2*bands): plane 2b the mean, 2b+1 the variance of band b
+ *   GMM       common.model.data[y][x*modelStride + g*(2+bands) + k], k = 0 weight, 1 variance, 2.. the means; modelStride = numberOfGaussian*(2+bands)
+ * BHIP_ERR_INVALID when the stream is not initialised (the reference's model is then 0 x 0 or 1 x 1).  bhip_bg_store_model is the inverse and
+ * leaves the stream initialised. */
+int bhip_bg_model_floats(bhip_bg* bg, long long* floats);
+int bhip_bg_fetch_model(bhip_bg* bg, int stream, float* model);
+int bhip_bg_store_model(bhip_bg* bg, int stream, const float* model);
 
 #ifdef __cplusplus
 }
