@@ -5,10 +5,14 @@
 //   -> hessianInner   ...:132-213  (32 integral-image taps per pixel)
 //   box kernels       I:alg/transform/ii/DerivativeIntegralImage.java:102-158
 //   block_zero        I:alg/transform/ii/impl/ImplIntegralImageOps.java:195-214, convolveSparse :172-183
-// Every pixel of every level of one octave is one thread; all levels of the octave share one launch so the integral image
-// is pulled through L2 once per octave.  fp32, no FMA contraction (-ffp-contract=off), expressions in the reference's order.
+// Two plans, equally exact.  Gather (k_hessian): every pixel of every level of one octave is one thread that fetches its taps itself.
+// Staged rows (k_hessian_rows, octaves with a power-of-two step >= 4): the inner pixels of a computed level take their taps from LDS, where
+// a workgroup has put the ten image rows of one output row with coalesced loads; the border pixels and the shared levels' pixels that
+// must be recomputed or copied go through the gather form in a compact launch (k_hessian_frame).  BHIP_DETECT_GATHER=1 forces the gather
+// plan.  fp32, no FMA contraction (-ffp-contract=off), expressions in the reference's order.
 // Bound: HBM (+L2 gather).  Algorithmic bytes per octave: 4P (ii read) + levels * 4P/skip^2 (intensity write).
 #include "hessian_dev.h"
+#include <algorithm>
 
 struct HessParams {
 	ImgView ii;
@@ -23,13 +27,9 @@ struct HessParams {
 	int srcW, srcH;
 };
 
+// one output pixel of one level, gather form: computed, copied from the octave below, or left as the producing octave wrote it
 template <class T>
-__global__ __launch_bounds__(256) void k_hessian(HessParams P) {
-	const int x = blockIdx.x * blockDim.x + threadIdx.x;
-	const int y = blockIdx.y;
-	const int img = blockIdx.z / P.nrun;
-	const int level = P.runLevel[blockIdx.z - img * P.nrun];
-	if (x >= P.w) return;
+__device__ __forceinline__ void hessianPixel(const HessParams& P, int img, int level, int x, int y) {
 	const HessLevel L = P.lv[level];
 	if (P.from[level].src) {
 		// Same kernel size one octave down.  A response depends on the pixel and the kernel size, and on which of the reference's two
@@ -51,6 +51,235 @@ __global__ __launch_bounds__(256) void k_hessian(HessParams P) {
 	const T* __restrict__ d = (const T*)P.ii.data + (long long)img * P.ii.imageStride;
 	P.out[(long long)img * P.imageStrideOut + (long long)level * P.levelStride + (long long)y * P.outStride + x] =
 		hessianCompute<T>(d, P.ii.stride, P.ii.width, P.ii.height, L, P.skip, P.w, P.h, x, y);
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void k_hessian(HessParams P) {
+	const int x = blockIdx.x * blockDim.x + threadIdx.x;
+	const int y = blockIdx.y;
+	const int img = blockIdx.z / P.nrun;
+	const int level = P.runLevel[blockIdx.z - img * P.nrun];
+	if (x >= P.w) return;
+	hessianPixel<T>(P, img, level, x, y);
+}
+
+// ---------------- staged-rows plan ----------------
+#define BHIP_HESS_ROWS 10   // image rows the 32 taps of hessianInner lie in: 2 (Dxx) + 4 (Dyy) + 4 (Dxy)
+// words staged per group of row r: the Dxx and Dxy rows carry four taps, the Dyy rows two
+__host__ __device__ constexpr int hessRowWords(int r) { return r >= 2 && r < 6 ? 2 : 4; }
+
+// The pixels of a run level the frame launch leaves out: the rectangle [x0, x1) x [y0, y1) (empty: none).  The others are numbered
+// row by row: the rows above it, the rows below it, then the columns left and right of it.
+struct HessFrame {
+	int x0, x1, y0, y1;
+	int count;
+};
+struct HessFrameParams {
+	HessFrame fr[BHIP_MAX_LEVELS];   // by run index
+};
+
+template <class T>
+__global__ __launch_bounds__(256) void k_hessian_frame(HessParams P, HessFrameParams F) {
+	const int img = blockIdx.y / P.nrun;
+	const int run = blockIdx.y - img * P.nrun;
+	const HessFrame f = F.fr[run];
+	int idx = blockIdx.x * blockDim.x + threadIdx.x;
+	if (idx >= f.count) return;
+	const int above = f.y0 * P.w, below = (P.h - f.y1) * P.w;
+	int x, y;
+	if (idx < above + below) {
+		y = idx / P.w;
+		x = idx - y * P.w;
+		if (idx >= above) y += f.y1 - f.y0;
+	} else {
+		idx -= above + below;
+		const int side = P.w - (f.x1 - f.x0);
+		y = idx / side;
+		x = idx - y * side;
+		y += f.y0;
+		if (x >= f.x0) x += f.x1 - f.x0;
+	}
+	hessianPixel<T>(P, img, P.runLevel[run], x, y);
+}
+
+// How one computed level is staged.  An x-tile of TX outputs of output row y reads image rows y * skip + dy[r]; of row r it needs, for
+// output i, the columns c0 + skip * i + (tap offsets), c0 = the tile's first tap column.  The columns are grouped by `skip`: group q of row
+// r starts at column c0 + dc[r] + skip * q and its first hessRowWords(r) columns are staged: the run the column phases of the row's taps
+// span (at a step of 4 the runs of a four-tap row join up to the whole row segment), element e into plane e of the row:
+// lds[base[r] + e * G + q].  So the loads of neighbouring lanes are neighbouring 16- or 8-byte runs, and tap j of output i is
+// lds[tap[j] + i]: neighbouring lanes, neighbouring banks.
+struct HessRowLevel {
+	int level;
+	int x0, nx, y0, ny;   // the inner region, in output pixels
+	int TX, ntiles, G;
+	float norm;
+	int dy[BHIP_HESS_ROWS], dc[BHIP_HESS_ROWS], base[BHIP_HESS_ROWS];
+	int tap[32];          // xx(r, k): 4 r + k; yy(k, s): 8 + 2 k + s; xy(r, c): 16 + 4 r + c
+};
+struct HessRowParams {
+	ImgView ii;
+	int skip, batch, nlv;
+	int ymin, nrows;        // output rows any staged level has inner pixels in
+	int tilesPerRow;        // sum of the levels' ntiles
+	int blocksPerImage;     // nrows * tilesPerRow
+	float* out;
+	long long levelStride, imageStrideOut;
+	int outStride;
+	HessRowLevel lv[BHIP_MAX_LEVELS];
+};
+
+template <class T>
+struct HessTapsLds {
+	const T* lds;   // + the output's index in its tile
+	const int* tap;
+	__device__ __forceinline__ T xx(int r, int k) const { return lds[tap[4 * r + k]]; }
+	__device__ __forceinline__ T yy(int k, int s) const { return lds[tap[8 + 2 * k + s]]; }
+	__device__ __forceinline__ T xy(int r, int c) const { return lds[tap[16 + 4 * r + c]]; }
+};
+
+typedef unsigned int hess_u2 __attribute__((ext_vector_type(2), aligned(4)));
+typedef unsigned int hess_u4 __attribute__((ext_vector_type(4), aligned(4)));
+
+// One workgroup = one image, one staged level, one output row, one x-tile.  Block b runs on XCD b % 8 (blocks are dealt round-robin): it
+// takes image (b / 8 / blocksPerImage) * 8 + b % 8, so an XCD works through whole images, and within an image the blocks go row by row, so
+// the rows an XCD has in flight are a band of the image that fits its L2 and each tap row is fetched from memory once.
+template <class T>
+__global__ __launch_bounds__(256) void k_hessian_rows(HessRowParams P) {
+	extern __shared__ __attribute__((aligned(16))) unsigned int hessLds[];
+	const int slot = blockIdx.x >> 3;
+	const int img = (slot / P.blocksPerImage) * 8 + (blockIdx.x & 7);
+	if (img >= P.batch) return;
+	const int within = slot % P.blocksPerImage;
+	const int y = P.ymin + within / P.tilesPerRow;
+	int tile = within % P.tilesPerRow, li = 0;
+	while (li < P.nlv - 1 && tile >= P.lv[li].ntiles) { tile -= P.lv[li].ntiles; li++; }
+	const HessRowLevel& L = P.lv[li];
+	if (y < L.y0 || y >= L.y0 + L.ny) return;
+	const int first = tile * L.TX;                 // first output of the tile, counted from the first inner column
+	const int n = min(L.TX, L.nx - first);         // outputs of this tile
+	const int W = P.ii.width;
+	const unsigned int* __restrict__ d = (const unsigned int*)P.ii.data + (long long)img * P.ii.imageStride;
+
+	// stage: wave k takes groups 64 k .. 64 k + 63 of every row (a row has at most 256 groups), all its loads in flight before the first
+	// is written to LDS; a run is one load where it lies inside its image row, and goes word by word at the row's ends (nothing outside
+	// [0, W) of the row is touched)
+	const int q = threadIdx.x;
+	if (q < n + L.G - L.TX) {   // the groups the tile's n outputs reach
+		unsigned int v[BHIP_HESS_ROWS][4];
+#pragma unroll
+		for (int r = 0; r < BHIP_HESS_ROWS; r++) {
+			const int rw = hessRowWords(r);
+			const int Y = y * P.skip + L.dy[r];                       // inside the image for every inner pixel
+			const int c = first * P.skip + L.dc[r] + P.skip * q;      // dc counts from the first inner output's first tap column
+			const unsigned int* __restrict__ src = d + (long long)Y * P.ii.stride + c;
+			if (c >= 0 && c + rw <= W) {
+				if (rw == 4) { const hess_u4 t = *(const hess_u4*)src; v[r][0] = t.x; v[r][1] = t.y; v[r][2] = t.z; v[r][3] = t.w; }
+				else { const hess_u2 t = *(const hess_u2*)src; v[r][0] = t.x; v[r][1] = t.y; }
+			} else {
+#pragma unroll
+				for (int e = 0; e < rw; e++) v[r][e] = c + e >= 0 && c + e < W ? src[e] : 0;
+			}
+		}
+#pragma unroll
+		for (int r = 0; r < BHIP_HESS_ROWS; r++) {
+			unsigned int* dst = hessLds + L.base[r] + q;
+#pragma unroll
+			for (int e = 0; e < hessRowWords(r); e++) dst[e * L.G] = v[r][e];
+		}
+	}
+	__syncthreads();
+
+	const int i = threadIdx.x;
+	if (i >= n) return;
+	float Dxx, Dyy, Dxy;
+	hessianInnerExpr<T>(HessTapsLds<T>{(const T*)hessLds + i, L.tap}, Dxx, Dyy, Dxy);
+	P.out[(long long)img * P.imageStrideOut + (long long)L.level * P.levelStride + (long long)y * P.outStride + L.x0 + first + i] =
+		hessianDeterminant(Dxx, Dyy, Dxy, L.norm);
+}
+
+// Plans the staged-rows form of a launch: which levels are staged and how (R), and which pixels are left to the gather form (F).  False:
+// the launch stays with the gather plan (a step that is not a power of two or below 4, taps whose column phases span more than the
+// 16- or 8-byte run of their row, a kernel so wide that a tile would hold fewer than 64 outputs, no computed level with inner pixels).
+static bool hessPlanRows(const HessParams& P, int batch, HessRowParams& R, HessFrameParams& F, int* ldsBytes) {
+	const int skip = P.skip;
+	if (skip < 4 || (skip & (skip - 1)) != 0) return false;
+	R.ii = P.ii; R.skip = skip; R.batch = batch; R.nlv = 0;
+	R.out = P.out; R.levelStride = P.levelStride; R.imageStrideOut = P.imageStrideOut; R.outStride = P.outStride;
+	R.tilesPerRow = 0;
+	int ymin = P.h, ymax = 0, ldsWords = 0;
+	for (int run = 0; run < P.nrun; run++) {
+		const int level = P.runLevel[run];
+		const HessLevel& L = P.lv[level];
+		HessFrame& f = F.fr[run];
+		f = HessFrame{0, 0, 0, 0, P.w * P.h};
+		// the inner region; for a level the octave below wrote in place, the part of it that octave evaluated with the inner form too
+		int x0 = L.border, x1 = P.w - L.border, y0 = L.border, y1 = P.h - L.border;
+		const HessLevelSource& S = P.from[level];
+		if (S.src) {
+			if (!S.inPlace) continue;   // every pixel is copied or computed
+			const int bp = P.srcBorder[level];
+			x0 = std::max(x0, (bp + 1) / 2); x1 = std::min(x1, (P.srcW - bp + 1) / 2);
+			y0 = std::max(y0, (bp + 1) / 2); y1 = std::min(y1, (P.srcH - bp + 1) / 2);
+		}
+		if (x1 <= x0 || y1 <= y0) continue;
+		if (S.src) {   // nothing to do inside
+			f = HessFrame{x0, x1, y0, y1, P.w * P.h - (x1 - x0) * (y1 - y0)};
+			continue;
+		}
+		HessRowLevel& V = R.lv[R.nlv];
+		V.level = level; V.x0 = x0; V.nx = x1 - x0; V.y0 = y0; V.ny = y1 - y0; V.norm = L.norm;
+		// tap columns relative to the output's first tap column, row by row
+		int off[BHIP_HESS_ROWS][4], nt[BHIP_HESS_ROWS];
+		for (int r = 0; r < 2; r++) {
+			V.dy[r] = -L.rS - 1 + r * L.bL; nt[r] = 4;
+			for (int k = 0; k < 4; k++) off[r][k] = k * L.bS;
+		}
+		for (int k = 0; k < 4; k++) {
+			V.dy[2 + k] = -L.rF - 1 + k * L.bS; nt[2 + k] = 2;
+			for (int s = 0; s < 2; s++) off[2 + k][s] = L.rF - L.rS + s * L.bL;
+		}
+		for (int r = 0; r < 4; r++) {
+			V.dy[6 + r] = -L.bS - 1 + hessXyOffset(r, L.bS); nt[6 + r] = 4;
+			for (int c = 0; c < 4; c++) off[6 + r][c] = L.rF - L.bS + hessXyOffset(c, L.bS);
+		}
+		int plane[BHIP_HESS_ROWS][4], grp[BHIP_HESS_ROWS][4], maxGroup = 0;
+		bool ok = true;
+		for (int r = 0; r < BHIP_HESS_ROWS; r++) {
+			// a group starts at the row's first tap, so a tap's plane is its distance from that tap modulo the step (the offsets ascend).  A
+			// pattern whose planes do not fit the row's run (the default sizes give 0..3 and 0..1) is not rotated: the launch stays with the gather
+			V.dc[r] = L.lost + off[r][0];
+			for (int k = 0; k < nt[r]; k++) {
+				const int rel = off[r][k] - off[r][0];
+				plane[r][k] = rel % skip;
+				grp[r][k] = rel / skip;
+				maxGroup = std::max(maxGroup, grp[r][k]);
+				if (plane[r][k] >= hessRowWords(r)) ok = false;
+			}
+		}
+		// tile width: the groups of a row (outputs + the groups the farthest tap reaches over) fill whole waves of 64 loads
+		const int txCap = 256 - (maxGroup + 1);
+		if (!ok || txCap < 64) return false;
+		V.ntiles = (V.nx + txCap - 1) / txCap;
+		V.TX = (V.nx + V.ntiles - 1) / V.ntiles;
+		V.G = V.TX + maxGroup + 1;
+		int words = 0;
+		for (int r = 0; r < BHIP_HESS_ROWS; r++) { V.base[r] = words; words += hessRowWords(r) * V.G; }
+		for (int j = 0; j < 32; j++) {
+			const int r = j < 8 ? j / 4 : j < 16 ? 2 + (j - 8) / 2 : 6 + (j - 16) / 4;
+			const int k = j < 8 ? j % 4 : j < 16 ? (j - 8) % 2 : (j - 16) % 4;
+			V.tap[j] = V.base[r] + plane[r][k] * V.G + grp[r][k];
+		}
+		ldsWords = std::max(ldsWords, words);
+		f = HessFrame{x0, x1, y0, y1, P.w * P.h - (x1 - x0) * (y1 - y0)};
+		ymin = std::min(ymin, y0); ymax = std::max(ymax, y1);
+		R.tilesPerRow += V.ntiles;
+		R.nlv++;
+	}
+	if (R.nlv == 0) return false;
+	R.ymin = ymin; R.nrows = ymax - ymin;
+	R.blocksPerImage = R.nrows * R.tilesPerRow;
+	*ldsBytes = ldsWords * 4;   // at most 32 KiB: 32 planes of G <= 256 words, so five workgroups fit a CU's LDS
+	return true;
 }
 
 template <class T>
@@ -80,12 +309,24 @@ int bhip_launch_hessian(bhip_ctx* ctx, DevImg<const T> ii, int skip, int nlevels
 	for (int i = 0; i < nlevels; i++)
 		if (!(skipMask & (1u << i))) P.runLevel[P.nrun++] = i;
 	if (P.w <= 0 || P.h <= 0 || P.nrun == 0) return BHIP_OK;
-	dim3 grid((P.w + 255) / 256, P.h, batch * P.nrun);
-	{
-		// algorithmic bytes: the integral image once + every level's intensity written once
-		const double bytes = 4.0 * ii.width * ii.height * batch + 4.0 * P.nrun * (double)P.w * P.h * batch;
+	// algorithmic bytes: the integral image once + every level's intensity written once
+	const double bytes = 4.0 * ii.width * ii.height * batch + 4.0 * P.nrun * (double)P.w * P.h * batch;
+	HessRowParams R;
+	HessFrameParams F;
+	int ldsBytes = 0;
+	if (bhip_env_flag("BHIP_DETECT_GATHER") || !hessPlanRows(P, batch, R, F, &ldsBytes)) {   // BHIP_DETECT_GATHER: parity cross-check of the two plans
+		dim3 grid((P.w + 255) / 256, P.h, batch * P.nrun);
 		ProfScope ps(ctx, skip == 1 ? "k_hessian_skip1" : "k_hessian_skipN", bytes);
 		hipLaunchKernelGGL(k_hessian<T>, grid, dim3(256), 0, ctx->stream, P);
+	} else {
+		int maxCount = 0;
+		for (int i = 0; i < P.nrun; i++) maxCount = std::max(maxCount, F.fr[i].count);
+		if (maxCount > 0) {
+			ProfScope ps(ctx, "k_hessian_frame");
+			hipLaunchKernelGGL(k_hessian_frame<T>, dim3((maxCount + 255) / 256, batch * P.nrun), dim3(256), 0, ctx->stream, P, F);
+		}
+		ProfScope ps(ctx, "k_hessian_rows", bytes);
+		hipLaunchKernelGGL(k_hessian_rows<T>, dim3(8 * ((batch + 7) / 8) * R.blocksPerImage), dim3(256), ldsBytes, ctx->stream, R);
 	}
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;

@@ -32,6 +32,48 @@ __device__ __forceinline__ T block_zero(const T* __restrict__ d, int stride, int
 	return br - tr - bl + tl;
 }
 
+// The 32 taps of hessianInner, by box: xx(r, k) = row r (top, bottom) and column k * blockSmall of the Dxx lobes; yy(k, s) = row k * blockSmall
+// and side s (left, right) of the Dyy lobes; xy(r, c) = row r (y1..y4) and column c (0, blockSmall, blockSmall + 1, 2 * blockSmall + 1) of the Dxy
+// quadrants.  One expression for every tap source (global memory here, LDS in k_hessian_rows): the order of the sums, the T(3) products and
+// the conversions are the reference's.
+template <class T, class Taps>
+__device__ __forceinline__ void hessianInnerExpr(const Taps& t, float& Dxx, float& Dyy, float& Dxy) {
+	Dxx = (float)(t.xx(1, 3) - t.xx(0, 3) - t.xx(1, 0) + t.xx(0, 0));
+	Dxx -= (float)(T(3) * (t.xx(1, 2) - t.xx(0, 2) - t.xx(1, 1) + t.xx(0, 1)));
+
+	Dyy = (float)(t.yy(3, 1) - t.yy(3, 0) - t.yy(0, 1) + t.yy(0, 0));
+	Dyy -= (float)(T(3) * (t.yy(2, 1) - t.yy(2, 0) - t.yy(1, 1) + t.yy(1, 0)));
+
+	Dxy = (float)(t.xy(1, 1) - t.xy(0, 1) - t.xy(1, 0) + t.xy(0, 0));
+	Dxy -= (float)(t.xy(1, 3) - t.xy(0, 3) - t.xy(1, 2) + t.xy(0, 2));
+	Dxy += (float)(t.xy(3, 3) - t.xy(2, 3) - t.xy(3, 2) + t.xy(2, 2));
+	Dxy -= (float)(t.xy(3, 1) - t.xy(2, 1) - t.xy(3, 0) + t.xy(2, 0));
+}
+
+__device__ __forceinline__ float hessianDeterminant(float Dxx, float Dyy, float Dxy, float norm) {
+	Dxx *= norm;
+	Dxy *= norm;
+	Dyy *= norm;
+	return Dxx * Dyy - 0.81f * Dxy * Dxy;
+}
+
+// rows and columns of the Dxy quadrants relative to (y1, first column): 0, bS, bS + 1, 2 bS + 1
+__host__ __device__ __forceinline__ int hessXyOffset(int i, int bS) { return i == 0 ? 0 : i == 1 ? bS : i == 2 ? bS + 1 : 2 * bS + 1; }
+
+// taps of the output pixel whose first tap column is `col` (row yy of the image), gathered from the integral image d
+template <class T>
+struct HessTapsGlobal {
+	const T* __restrict__ d;
+	long long top, l, y1, stride;
+	int bS, bL;
+	__device__ __forceinline__ HessTapsGlobal(const T* __restrict__ d_, int stride_, const HessLevel& L, int yy, int col)
+		: d(d_), top((long long)(yy - L.rS - 1) * stride_ + col), l((long long)(yy - L.rF - 1) * stride_ + (L.rF - L.rS) + col),
+		  y1((long long)(yy - L.bS - 1) * stride_ + (L.rF - L.bS) + col), stride(stride_), bS(L.bS), bL(L.bL) {}
+	__device__ __forceinline__ T xx(int r, int k) const { return d[top + (long long)(r * bL) * stride + k * bS]; }
+	__device__ __forceinline__ T yy(int k, int s) const { return d[l + (long long)(k * bS) * stride + s * bL]; }
+	__device__ __forceinline__ T xy(int r, int c) const { return d[y1 + (long long)hessXyOffset(r, bS) * stride + hessXyOffset(c, bS)]; }
+};
+
 // det(Hessian) of output pixel (x, y) of a level with geometry L on the octave lattice `skip` (w x h outputs): hessianInner inside the
 // level's border, the clamped border form outside.  d = integral image of this frame.
 template <class T>
@@ -42,27 +84,7 @@ __device__ __forceinline__ float hessianCompute(const T* __restrict__ d, int str
 	if (inner) {
 		// hessianInner: the first inner column sits at offset `lost`, then +skip per output pixel
 		const int col = L.lost + (x - L.border) * skip;
-		const long long top = (long long)(yy - L.rS - 1) * stride + col;
-		const long long bot = top + (long long)L.bL * stride;
-		const int bS = L.bS;
-		Dxx = (float)(d[bot + 3 * bS] - d[top + 3 * bS] - d[bot] + d[top]);
-		Dxx -= (float)(T(3) * (d[bot + 2 * bS] - d[top + 2 * bS] - d[bot + bS] + d[top + bS]));
-
-		const long long l = (long long)(yy - L.rF - 1) * stride + (L.rF - L.rS) + col;
-		const long long r = l + L.bL;
-		const long long ro1 = (long long)bS * stride;
-		Dyy = (float)(d[r + 3 * ro1] - d[l + 3 * ro1] - d[r] + d[l]);
-		Dyy -= (float)(T(3) * (d[r + 2 * ro1] - d[l + 2 * ro1] - d[r + ro1] + d[l + ro1]));
-
-		const long long y1 = (long long)(yy - bS - 1) * stride + (L.rF - bS) + col;
-		const long long y2 = y1 + ro1;
-		const long long y3 = y2 + stride;
-		const long long y4 = y3 + ro1;
-		const int x3 = bS + 1, x4 = x3 + bS;
-		Dxy = (float)(d[y2 + bS] - d[y1 + bS] - d[y2] + d[y1]);
-		Dxy -= (float)(d[y2 + x4] - d[y1 + x4] - d[y2 + x3] + d[y1 + x3]);
-		Dxy += (float)(d[y4 + x4] - d[y3 + x4] - d[y4 + x3] + d[y3 + x3]);
-		Dxy -= (float)(d[y4 + bS] - d[y3 + bS] - d[y4] + d[y3]);
+		hessianInnerExpr<T>(HessTapsGlobal<T>(d, stride, L, yy, col), Dxx, Dyy, Dxy);
 	} else {
 		// computeHessian via convolveSparse: ret = 0; ret += block_zero(...) * scale, block by block (float scales for GrayF32, int for GrayS32)
 		T ret = 0;
@@ -81,10 +103,7 @@ __device__ __forceinline__ float hessianCompute(const T* __restrict__ d, int str
 		ret += block_zero<T>(d, stride, W, H, xx - b - 1, yy, xx - 1, yy + b) * T(-1);
 		Dxy = (float)ret;
 	}
-	Dxx *= L.norm;
-	Dxy *= L.norm;
-	Dyy *= L.norm;
-	return Dxx * Dyy - 0.81f * Dxy * Dxy;
+	return hessianDeterminant(Dxx, Dyy, Dxy, L.norm);
 }
 
 static inline HessLevel bhipMakeHessLevel(int size, int skip) {
