@@ -69,6 +69,9 @@ BHIP_KLT_SUCCESS, BHIP_KLT_DRIFTED, BHIP_KLT_OUT_OF_BOUNDS, BHIP_KLT_FAILED, BHI
 BHIP_INTERP_NEAREST_NEIGHBOR, BHIP_INTERP_BILINEAR, BHIP_INTERP_BICUBIC, BHIP_INTERP_POLYNOMIAL4 = range(4)
 BHIP_BORDER_SKIP, BHIP_BORDER_EXTENDED, BHIP_BORDER_NORMALIZED, BHIP_BORDER_REFLECT, BHIP_BORDER_WRAP, BHIP_BORDER_ZERO = range(6)
 BHIP_DISTORT_AFFINE, BHIP_DISTORT_HOMOGRAPHY = 1, 2
+# TemplateScoreType ordinals
+BHIP_TEMPLATE_SAD, BHIP_TEMPLATE_SSE, BHIP_TEMPLATE_NCC, BHIP_TEMPLATE_CORRELATION = range(4)
+BHIP_TEMPLATE_MAX_WIDTH, BHIP_TEMPLATE_MAX_CANDIDATES = 160, 65536
 
 P = C.POINTER
 _vp, _i, _f, _d, _ll = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_longlong
@@ -124,6 +127,9 @@ SIGNATURES = {
     "bhip_distort_model_u8": (_i, [_vp, _u8p, _i, _i, _i, _i, _i, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _u8p, _i, _i, _u8p, _i, _i]),
     "bhip_distort_model_f32": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _fp, _i, _i, _u8p, _i, _i]),
     "bhip_select_nbest_f32": (_i, [_vp, _fp, _i, _i, _i, _i, _i16p, _i, _i, _i, _i16p, _ip]),
+    "bhip_template_intensity_u8": (_i, [_vp, _i, _u8p, _i, _i, _i, _i, _u8p, _i, _i, _i, _i, _u8p, _i, _i, _i, _i, _fp, _i, _i]),
+    "bhip_template_intensity_f32": (_i, [_vp, _i, _fp, _i, _i, _i, _i, _fp, _i, _i, _i, _i, _fp, _i, _i, _i, _i, _fp, _i, _i]),
+    "bhip_template_select_f32": (_i, [_vp, _fp, _i, _i, _i, _i, _i16p, _i, _i, _i, _i16p, _fp, _ip]),
     "bhip_fh_detect_f32": (_i, [_vp, P(FhCfg), _fp, _i, _i, _i, _i, _dp, _i, _ip]),
     "bhip_assoc_l2_f64": (_i, [_vp, _dp, _i, _dp, _i, _i, _d, _i, _i, _ip, _dp]),
     "bhip_assoc_hamming": (_i, [_vp, _i32p, _i, _i32p, _i, _i, _d, _i, _ip, _dp]),
@@ -176,6 +182,9 @@ SIGNATURES = {
     "bhip_fast_dev_f32": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _f, _i, _d, _vp, _ll, _i, _vp, _vp, _vp, _vp, _i]),
     "bhip_disparity_bm_dev_u8_u8": (_i, [_vp, P(DisparityBmCfg), _vp, _ll, _i, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i]),
     "bhip_disparity_bm_dev_u8_f32": (_i, [_vp, P(DisparityBmCfg), _vp, _ll, _i, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i]),
+    "bhip_template_intensity_dev_u8": (_i, [_vp, _i, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i, _i, _i, _vp, _ll, _i, _i, _i, _vp, _ll, _i]),
+    "bhip_template_intensity_dev_f32": (_i, [_vp, _i, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i, _i, _i, _vp, _ll, _i, _i, _i, _vp, _ll, _i]),
+    "bhip_template_select_dev_f32": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "bhip_distort_map_dev_u8": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _ll, _i, _vp, _ll, _i]),
     "bhip_distort_map_dev_f32": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _ll, _i, _vp, _ll, _i]),
     "bhip_distort_model_dev_u8": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _i, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _ll, _i, _vp, _ll, _i]),

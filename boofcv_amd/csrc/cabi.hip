@@ -15,7 +15,7 @@
 // host export calls can overwrite what it staged.
 struct CtxScratch {
 	DevBuf in0, in1, out0, out1, tmp0, tmp1;                                 // staging
-	DevBuf work, assocCol, nmsBitmap, nmsPrefix, nmsPos, ipTmp, ipKernel, fast, disparity, distortMap;   // device side
+	DevBuf work, assocCol, nmsBitmap, nmsPrefix, nmsPos, ipTmp, ipKernel, fast, disparity, distortMap, templ;   // device side
 	AssocMfmaWork mfma;
 	int assocExactOnly = -1;  // BHIP_ASSOC_EXACT=1 forces the exact VALU association kernels (parity cross-check)
 };
@@ -1625,6 +1625,148 @@ int bhip_distort_build_map(bhip_ctx* ctx, int model, const float* coeff, int dw,
 	if ((model != BHIP_DISTORT_AFFINE && model != BHIP_DISTORT_HOMOGRAPHY) || !coeff || !dev_map || dw <= 0 || dh <= 0)
 		return bhip_fail(ctx, BHIP_ERR_INVALID, "bhip_distort_build_map: no such model, or no coefficients / map / size");
 	return bhip_launch_distort_build_map(ctx, model, coeff, dw, dh, dev_map);
+}
+
+// ---- template matching (template.hip, k_template_select in detect.hip): TemplateMatchingIntensity.process and the selection of TemplateMatching.process ----
+extern "C++" {
+// the checks the reference leaves to an array index exception, then the kernel's limit
+template <class T>
+static int templateCheck(bhip_ctx* ctx, int score, DevImg<const T> img, DevImg<const T> tpl, DevImg<const T> mask) {
+	if (score == BHIP_TEMPLATE_CORRELATION) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "TemplateCorrelationFFT is not implemented on the GPU (use the Java path)");
+	if (score < BHIP_TEMPLATE_SAD || score > BHIP_TEMPLATE_CORRELATION) return bhip_fail(ctx, BHIP_ERR_INVALID, "Unknown");
+	if (tpl.width > img.width || tpl.height > img.height) return bhip_fail(ctx, BHIP_ERR_INVALID, "the template is larger than the image");
+	if (mask.data && (mask.width != tpl.width || mask.height != tpl.height)) return bhip_fail(ctx, BHIP_ERR_INVALID, "the mask must have the template's size");
+	if (tpl.width > BHIP_TEMPLATE_MAX_WIDTH)
+		return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "template matching on the GPU: template width <= " + std::to_string(BHIP_TEMPLATE_MAX_WIDTH) + " (use the Java path)");
+	return BHIP_OK;
+}
+
+template <class T>
+static int templateDevice(bhip_ctx* ctx, int score, DevImg<const T> img, DevImg<const T> tpl, DevImg<const T> mask, DevImg<float> out) {
+	DevBuf& stats = scratchOf(ctx)->templ;
+	BHIP_TRY(stats.reserve(ctx, bhip_template_scratch(img.batch)));
+	return bhip_launch_template_intensity<T>(ctx, score, img, tpl, mask, stats.as<float>(), out);
+}
+
+template <class T>
+static int templateDev(bhip_ctx* ctx, int score, const T* dev_image, long long iImageStride, int iStride, int width, int height, int batch, const T* dev_templ,
+					   long long tImageStride, int tStride, int tWidth, int tHeight, const T* dev_mask, long long mImageStride, int mStride, int mWidth, int mHeight,
+					   float* dev_intensity, long long oImageStride, int oStride) {
+	CHECK_CTX(ctx);
+	const DevImg<const T> img{dev_image, iImageStride, iStride, width, height, batch}, tpl{dev_templ, tImageStride, tStride, tWidth, tHeight, batch};
+	const DevImg<const T> mask{dev_mask, mImageStride, mStride, mWidth, mHeight, batch};
+	const DevImg<float> out{dev_intensity, oImageStride, oStride, width, height, batch};
+	CHECK_IMG(ctx, img);
+	CHECK_IMG(ctx, tpl);
+	if (dev_mask) CHECK_IMG(ctx, mask);
+	CHECK_IMG(ctx, out);
+	if (tImageStride < 0 || mImageStride < 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad image");
+	BHIP_TRY(templateCheck<T>(ctx, score, img, tpl, mask));
+	return templateDevice<T>(ctx, score, img, tpl, mask, out);
+}
+
+template <class T>
+static int templateHost(bhip_ctx* ctx, int score, const T* image, int iStart, int iStride, int width, int height, const T* templ, int tStart, int tStride, int tWidth,
+						int tHeight, const T* mask, int mStart, int mStride, int mWidth, int mHeight, float* intensity, int oStart, int oStride) {
+	const HostImg<const T> hi{image, iStart, iStride, width, height}, ht{templ, tStart, tStride, tWidth, tHeight}, hm{mask, mStart, mStride, mWidth, mHeight};
+	const HostImg<float> ho{intensity, oStart, oStride, width, height};
+	CHECK_CTX(ctx);
+	CHECK_IMG(ctx, hi);
+	CHECK_IMG(ctx, ht);
+	if (mask) CHECK_IMG(ctx, hm);
+	CHECK_IMG(ctx, ho);
+	BHIP_TRY(templateCheck<T>(ctx, score, {image, 0, iStride, width, height, 1}, {templ, 0, tStride, tWidth, tHeight, 1}, {mask, 0, mStride, mWidth, mHeight, 1}));
+	CtxScratch* sc = scratchOf(ctx);
+	DevImg<T> di, dt, dm{nullptr, 0, 0, tWidth, tHeight, 1};
+	DevImg<float> dout;
+	BHIP_TRY(stageIn(ctx, sc->in0, hi, width, di));
+	BHIP_TRY(stageIn(ctx, sc->in1, ht, tWidth, dt));
+	if (mask) BHIP_TRY(stageIn(ctx, sc->tmp0, hm, mWidth, dm));
+	BHIP_TRY(stageIn(ctx, sc->out0, ho, width, dout, false));
+	BHIP_TRY(templateDevice<T>(ctx, score, di, dt, dm, dout));
+	BHIP_TRY(stageOut(ctx, ho, dout));
+	return bhip_ctx_synchronize(ctx);
+}
+
+// selection scratch: [batch][cap] keys and indexes (the slot of the NCC statistics, which no kernel still in flight on another stream reads:
+// everything runs on the context's stream)
+static int templateSelectDevice(bhip_ctx* ctx, DevImg<const float> img, const int16_t* dev_xy, const int* dev_n, int cap, int maxMatches, bool maximize,
+								int16_t* dev_out_xy, float* dev_out_score, int* dev_out_n) {
+	if (cap > BHIP_TEMPLATE_MAX_CANDIDATES)
+		return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "template matching on the GPU: at most " + std::to_string(BHIP_TEMPLATE_MAX_CANDIDATES) + " candidates per image");
+	DevBuf& work = scratchOf(ctx)->templ;
+	const size_t per = (size_t)std::max(cap, 1) * img.batch;
+	BHIP_TRY(work.reserve(ctx, per * 8));
+	float* key = work.as<float>();
+	return bhip_launch_template_select(ctx, img, dev_xy, dev_n, cap, maxMatches, maximize, key, (int*)(key + per), dev_out_xy, dev_out_score, dev_out_n);
+}
+}  // extern "C++"
+
+int bhip_template_intensity_u8(bhip_ctx* ctx, int score, const uint8_t* image, int iStart, int iStride, int width, int height, const uint8_t* templ, int tStart,
+							   int tStride, int tWidth, int tHeight, const uint8_t* mask, int mStart, int mStride, int mWidth, int mHeight, float* intensity, int oStart,
+							   int oStride) {
+	return templateHost<uint8_t>(ctx, score, image, iStart, iStride, width, height, templ, tStart, tStride, tWidth, tHeight, mask, mStart, mStride, mWidth, mHeight,
+								 intensity, oStart, oStride);
+}
+int bhip_template_intensity_f32(bhip_ctx* ctx, int score, const float* image, int iStart, int iStride, int width, int height, const float* templ, int tStart,
+								int tStride, int tWidth, int tHeight, const float* mask, int mStart, int mStride, int mWidth, int mHeight, float* intensity, int oStart,
+								int oStride) {
+	return templateHost<float>(ctx, score, image, iStart, iStride, width, height, templ, tStart, tStride, tWidth, tHeight, mask, mStart, mStride, mWidth, mHeight,
+							   intensity, oStart, oStride);
+}
+int bhip_template_intensity_dev_u8(bhip_ctx* ctx, int score, const uint8_t* dev_image, long long iImageStride, int iStride, int width, int height, int batch,
+								   const uint8_t* dev_templ, long long tImageStride, int tStride, int tWidth, int tHeight, const uint8_t* dev_mask,
+								   long long mImageStride, int mStride, int mWidth, int mHeight, float* dev_intensity, long long oImageStride, int oStride) {
+	return templateDev<uint8_t>(ctx, score, dev_image, iImageStride, iStride, width, height, batch, dev_templ, tImageStride, tStride, tWidth, tHeight, dev_mask,
+								mImageStride, mStride, mWidth, mHeight, dev_intensity, oImageStride, oStride);
+}
+int bhip_template_intensity_dev_f32(bhip_ctx* ctx, int score, const float* dev_image, long long iImageStride, int iStride, int width, int height, int batch,
+									const float* dev_templ, long long tImageStride, int tStride, int tWidth, int tHeight, const float* dev_mask,
+									long long mImageStride, int mStride, int mWidth, int mHeight, float* dev_intensity, long long oImageStride, int oStride) {
+	return templateDev<float>(ctx, score, dev_image, iImageStride, iStride, width, height, batch, dev_templ, tImageStride, tStride, tWidth, tHeight, dev_mask,
+							  mImageStride, mStride, mWidth, mHeight, dev_intensity, oImageStride, oStride);
+}
+
+int bhip_template_select_dev_f32(bhip_ctx* ctx, const float* dev_intensity, long long imageStride, int stride, int width, int height, int batch,
+								 const int16_t* dev_xy, const int* dev_n, int cap, int maxMatches, int maximize, int16_t* dev_out_xy, float* dev_out_score,
+								 int* dev_out_n) {
+	CHECK_CTX(ctx);
+	const DevImg<const float> img{dev_intensity, imageStride, stride, width, height, batch};
+	CHECK_IMG(ctx, img);
+	if (cap < 0 || maxMatches < 0 || !dev_n || !dev_out_n || (cap > 0 && !dev_xy) || (maxMatches > 0 && (!dev_out_xy || !dev_out_score)))
+		return bhip_fail(ctx, BHIP_ERR_INVALID, "bad candidate list");
+	return templateSelectDevice(ctx, img, dev_xy, dev_n, cap, maxMatches, maximize != 0, dev_out_xy, dev_out_score, dev_out_n);
+}
+
+int bhip_template_select_f32(bhip_ctx* ctx, const float* intensity, int start, int stride, int width, int height, const int16_t* xy, int n, int maxMatches,
+							 int maximize, int16_t* out_xy, float* out_score, int* out_n) {
+	const HostImg<const float> hin{intensity, start, stride, width, height};
+	CHECK_CTX(ctx);
+	CHECK_IMG(ctx, hin);
+	if (n < 0 || maxMatches < 0 || !out_n || (n > 0 && !xy) || (std::min(n, maxMatches) > 0 && (!out_xy || !out_score)))
+		return bhip_fail(ctx, BHIP_ERR_INVALID, "bad candidate list");
+	for (int i = 0; i < n; i++)
+		if (xy[2 * i] < 0 || xy[2 * i] >= width || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= height)
+			return bhip_fail(ctx, BHIP_ERR_INVALID, "candidate outside the intensity image");   // GrayF32.get would throw ImageAccessException
+	if (n > BHIP_TEMPLATE_MAX_CANDIDATES)
+		return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "template matching on the GPU: at most " + std::to_string(BHIP_TEMPLATE_MAX_CANDIDATES) + " candidates per image");
+	const int N = std::min(n, maxMatches);
+	*out_n = 0;
+	if (N == 0) return BHIP_OK;   // no candidates or nothing asked for: no matches
+	CtxScratch* sc = scratchOf(ctx);
+	DevImg<float> din;
+	BHIP_TRY(stageIn(ctx, sc->in0, hin, width, din));
+	BHIP_TRY(sc->in1.reserve(ctx, (size_t)n * 4));
+	BHIP_TRY(sc->out0.reserve(ctx, (size_t)N * 4));
+	BHIP_TRY(sc->out1.reserve(ctx, (size_t)N * 4 + 16));
+	BHIP_HIP(ctx, hipMemcpyAsync(sc->in1.p, xy, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+	int* dcount = (int*)(sc->out1.as<char>() + (size_t)N * 4);
+	BHIP_TRY(templateSelectDevice(ctx, din, sc->in1.as<int16_t>(), nullptr, n, N, maximize != 0, sc->out0.as<int16_t>(), sc->out1.as<float>(), dcount));
+	BHIP_HIP(ctx, hipMemcpyAsync(out_xy, sc->out0.p, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_HIP(ctx, hipMemcpyAsync(out_score, sc->out1.p, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	*out_n = N;
+	return BHIP_OK;
 }
 
 int bhip_select_nbest_f32(bhip_ctx* ctx, const float* intensity, int start, int stride, int width, int height, const int16_t* xy, int n, int target,

@@ -435,6 +435,17 @@ template <class T>
 int bhip_launch_background(bhip_ctx* ctx, const BgShape& sh, const BgConfig& cfg, const BgFrames<const T>& f, const BgFrames<uint8_t>& m, float* model,
 						   const int* state, bool segment);
 
+// ---------------- template matching (template.hip; the match selection is in detect.hip next to the N-best selection) ----------------
+size_t bhip_template_scratch(int batch);   // bytes of device scratch (the NCC template statistics) one bhip_launch_template_intensity call needs
+// TemplateIntensityImage.process on every image of a batch, T = uint8_t / float; tpl.imageStride / mask.imageStride 0: shared by the batch,
+// mask.data == nullptr: no mask.  The whole output view is written.  The caller has validated the sizes (tpl.width <= BHIP_TEMPLATE_MAX_WIDTH).
+template <class T>
+int bhip_launch_template_intensity(bhip_ctx* ctx, int score, DevImg<const T> img, DevImg<const T> tpl, DevImg<const T> mask, float* stats, DevImg<float> out);
+// TemplateMatching.process after the extractor: image b selects from xy[b*cap ...], the first min(n[b], cap) pairs (n == nullptr: cap of them);
+// key / idx: [batch][cap] work arrays
+int bhip_launch_template_select(bhip_ctx* ctx, DevImg<const float> img, const int16_t* xy, const int* n, int cap, int maxMatches, bool maximize, float* key,
+								int* idx, int16_t* outXY, float* outScore, int* outN);
+
 // ---------------- pyramid KLT tracker (klt.hip) ----------------
 #define BHIP_KLT_MAX_LAYERS 8
 #define BHIP_KLT_MAX_RADIUS 7

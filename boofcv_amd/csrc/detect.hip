@@ -557,6 +557,65 @@ int bhip_launch_select_nbest_xy(bhip_ctx* ctx, DevImg<const float> img, const in
 	return BHIP_OK;
 }
 
+// TemplateMatching.process after the extractor (F:alg/feature/detect/template/TemplateMatching.java:141-172), one wave per image: scores =
+// -/+ intensity(x,y), the sequential QuickSelect with k = N = min(maxMatches, n) (also when N == n), then match i = candidate idx[i] with
+// that candidate's score, -scores[idx[i]] of the scores as they were before the routine permuted its copy (TestTemplateMatching pins that)
+struct TemplateSelectParams {
+	const float* img;
+	long long imageStride;
+	int stride, w, h;
+	const int16_t* xy;
+	const int* n;
+	int cap, maxMatches, maximize;
+	float* key;
+	int* idx;
+	int16_t* outXY;
+	float* outScore;
+	int* outN;
+};
+__global__ __launch_bounds__(64) void k_template_select(TemplateSelectParams P) {
+	const int lane = threadIdx.x;
+	const long long b = blockIdx.x;
+	const int n = P.n ? min(max(P.n[b], 0), P.cap) : P.cap;
+	const int N = min(P.maxMatches, n);
+	const float* img = P.img + b * P.imageStride;
+	const int16_t* xy = P.xy + b * P.cap * 2;
+	float* key = P.key + b * P.cap;
+	int* idx = P.idx + b * P.cap;
+	for (int i = lane; i < n; i += 64) {
+		const int x = xy[2 * i], y = xy[2 * i + 1];
+		const float v = (x >= 0 && x < P.w && y >= 0 && y < P.h) ? img[(long long)y * P.stride + x] : 0.f;
+		key[i] = P.maximize ? -v : v;
+		idx[i] = i;
+	}
+	__threadfence_block();
+	__builtin_amdgcn_wave_barrier();
+	if (lane == 0 && n > 0) quickSelectIndexSeq(key, N, n, idx);
+	__threadfence_block();
+	__builtin_amdgcn_wave_barrier();
+	for (int i = lane; i < N; i += 64) {
+		const int c = idx[i];
+		P.outXY[(b * P.maxMatches + i) * 2] = xy[2 * c];
+		P.outXY[(b * P.maxMatches + i) * 2 + 1] = xy[2 * c + 1];
+		const int x = xy[2 * c], y = xy[2 * c + 1];
+		const float v = (x >= 0 && x < P.w && y >= 0 && y < P.h) ? img[(long long)y * P.stride + x] : 0.f;
+		P.outScore[b * P.maxMatches + i] = P.maximize ? v : -v;   // -(sgn * intensity)
+	}
+	if (lane == 0) P.outN[b] = N;
+}
+
+int bhip_launch_template_select(bhip_ctx* ctx, DevImg<const float> img, const int16_t* xy, const int* n, int cap, int maxMatches, bool maximize, float* key,
+								int* idx, int16_t* outXY, float* outScore, int* outN) {
+	if (img.batch <= 0) return BHIP_OK;
+	TemplateSelectParams P{img.data, img.imageStride, img.stride, img.width, img.height, xy, n, cap, maxMatches, maximize ? 1 : 0, key, idx, outXY, outScore, outN};
+	{
+		ProfScope ps(ctx, "k_template_select");
+		hipLaunchKernelGGL(k_template_select, dim3(img.batch), dim3(64), 0, ctx->stream, P);
+	}
+	BHIP_HIP(ctx, hipGetLastError());
+	return BHIP_OK;
+}
+
 // ---- stand-alone NMS over a batch of intensity images (BOverrideFactoryFeatureExtractor.nonmax, GeneralFeatureDetector, config-5 chain) ----
 // Same structure as k_nms_scalespace: NMS_ROWS rows per thread, a cheap four-neighbour test, survivors compacted per block and tested
 // densely.  An accepted pixel sets the bit of its (r+1)^2 block (at most one pixel per block can pass) and records its position inside the

@@ -12,6 +12,8 @@ Names follow the reference classes the host-buffer forms in boofcv_amd/api.py mi
   DeviceImageOps.nonmaxMinMax   NonMaxBlockSearchStrict.Min / .Max / .MinMax        F:alg/feature/detect/extract/NonMaxBlockSearchStrict.java:56-248
   DeviceImageOps.fast           FastCornerDetector.process                          F:alg/feature/detect/intensity/FastCornerDetector.java:123-189
   DeviceImageOps.disparityBM    StereoDisparity.process (blockMatch, SAD, GrayU8)   F:factory/feature/disparity/FactoryStereoDisparity.java:62-144
+  DeviceImageOps.templateIntensity  TemplateMatchingIntensity.process (SAD, SSE, NCC)   F:alg/feature/detect/template/TemplateIntensityImage.java:56-125
+  DeviceImageOps.templateMatch  TemplateMatching.process                            F:alg/feature/detect/template/TemplateMatching.java:117-176
   DeviceImageOps.distort        ImageDistort.apply (distortSB, GrayU8 / GrayF32)    I:alg/distort/ImageDistortBasic_SB.java:56-135, ImageDistortCache_SB.java:76-206
   DeviceImageOps.pyramid        PyramidDiscreteSampleBlur.process                   I:alg/transform/pyramid/PyramidDiscreteSampleBlur.java:88-118
   DeviceImageOps.cornerIntensity  GradientCornerIntensity.process                   F:alg/feature/detect/intensity/impl/ImplSsdCorner_F32.java:62-196
@@ -25,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .api import Context, IllegalArgumentException, _check
+from .api import Context, IllegalArgumentException, TemplateScoreType, _check
 
 INTENSITY_E, INTENSITY_ABS, INTENSITY_SQ = 0, 1, 2
 
@@ -256,6 +258,65 @@ class DeviceImageOps:
             fn = self.L.bhip_distort_model_dev_u8 if dt == torch.uint8 else self.L.bhip_distort_model_dev_f32
             _check(self.ctx, fn(self.ctx._h, sp, sis, srs, sw, sh, B, int(model), coeff.ctypes.data_as(_lib._fp), *tail))
         return out
+
+    def _template(self, t, dtype, B, what):
+        """(ptr, imageStride, rowStride, w, h) of a template or mask: [h,w] is shared by the batch (image stride 0), [B,h,w] is one per image"""
+        p, tis, trs, tw, th, tb = _geom(t, dtype)
+        if t.dim() == 2:
+            tis = 0
+        elif tb != B:
+            raise IllegalArgumentException("%s: one per image of the batch, or a single [h,w] one" % what)
+        return p, tis, trs, tw, th
+
+    def templateIntensity(self, images, template, mask=None, score="SUM_ABSOLUTE_DIFFERENCE", out=None):
+        """TemplateMatchingIntensity.process(template[, mask]) of FactoryTemplateMatching.createIntensity(score, GrayU8 | GrayF32) on uint8 or
+        float32 images [B,H,W] -> the intensity float32 [B,H,W], 0 in the border (`out`, any row / image stride, is written in place and as a
+        whole).  template / mask: [th,tw] shared by the batch or [B,th,tw]; same dtype as the images.  score: a TemplateScoreType name."""
+        if score not in TemplateScoreType._ORDINAL:
+            raise IllegalArgumentException("Unknown")
+        if images.dtype not in (torch.uint8, torch.float32):
+            raise IllegalArgumentException("Image type not supported. " + str(images.dtype))
+        dt = images.dtype
+        ip, iis, irs, W, H, B = _geom(images, dt)
+        if template.dtype != dt or (mask is not None and mask.dtype != dt):
+            raise IllegalArgumentException("image, template and mask must have one type")
+        tp, tis, trs, tw, th = self._template(template, dt, B, "template")
+        mp, mis, mrs, mw, mh = self._template(mask, dt, B, "mask") if mask is not None else (None, 0, 0, 0, 0)
+        if out is None:
+            out = torch.empty((B, H, W), dtype=torch.float32, device=images.device)
+        op, ois, ors, W2, H2, B2 = _geom(out)
+        if (W, H, B) != (W2, H2, B2):
+            raise IllegalArgumentException("input and intensity shapes differ")
+        fn = self.L.bhip_template_intensity_dev_u8 if dt == torch.uint8 else self.L.bhip_template_intensity_dev_f32
+        _check(self.ctx, fn(self.ctx._h, TemplateScoreType._ORDINAL[score], ip, iis, irs, W, H, B, tp, tis, trs, tw, th, mp, mis, mrs, mw, mh, op, ois, ors))
+        return out
+
+    def templateMatch(self, images, template, mask=None, score="SUM_ABSOLUTE_DIFFERENCE", maxMatches=1, radius=2, cap=None):
+        """TemplateMatching (setMinimumSeparation(radius), setTemplate(template, mask, maxMatches), setImage, process, getResults) on every image
+        of a batch: templateIntensity, the strict block non-maximum suppression on the intensity sub-image (nonmaxMinMax) and the N best
+        (bhip_template_select_dev_f32) -> (xy int16 [B, maxMatches, 2] top-left corners, scores float32 [B, maxMatches], counts int32 [B],
+        candidates int32 [B]); rows past counts[b] are 0.  cap: candidates kept per image (default: one per suppression block, at most
+        BHIP_TEMPLATE_MAX_CANDIDATES); where candidates[b] > cap the list was cut and the matches are those of the cut list."""
+        maximize = score == "NCC"
+        inten = self.templateIntensity(images, template, mask, score)
+        th, tw = template.shape[-2:]
+        B, H, W = inten.shape
+        sub = inten[:, th // 2:th // 2 + H - th + 1, tw // 2:tw // 2 + W - tw + 1]
+        if cap is None:
+            step = radius + 1
+            cap = max(1, min(((sub.shape[2] + step - 1) // step) * ((sub.shape[1] + step - 1) // step), _lib.BHIP_TEMPLATE_MAX_CANDIDATES))
+        fmax = float(np.finfo(np.float32).max)
+        xyMin, nMin, xyMax, nMax = self.nonmaxMinMax(sub, radius, fmax, -fmax, 0, detectMin=not maximize, detectMax=maximize, cap=cap)
+        cxy, cn = (xyMax, nMax) if maximize else (xyMin, nMin)
+        xy = torch.zeros((B, max(maxMatches, 1), 2), dtype=torch.int16, device=images.device)
+        scores = torch.zeros((B, max(maxMatches, 1)), dtype=torch.float32, device=images.device)
+        counts = torch.empty((B,), dtype=torch.int32, device=images.device)
+        torch.cuda.current_stream(images.device).synchronize()   # the zero fills run on torch's stream: order them before the kernel of the ctx
+        sp, sis, srs, w, h, _ = _geom(sub)
+        _check(self.ctx, self.L.bhip_template_select_dev_f32(self.ctx._h, sp, sis, srs, w, h, B, C.c_void_p(cxy.data_ptr()), C.c_void_p(cn.data_ptr()), cap,
+                                                           int(maxMatches), 1 if maximize else 0, C.c_void_p(xy.data_ptr()),
+                                                           C.c_void_p(scores.data_ptr()), C.c_void_p(counts.data_ptr())))
+        return xy[:, :maxMatches], scores[:, :maxMatches], counts, cn
 
     def cornerIntensity(self, kind, radius, kappa, dx, dy, out=None, weighted=False):
         """kind: 0 Shi-Tomasi, 1 Harris.  float32 derivatives: ImplSsdCorner_F32 / ImplSsdCornerWeighted_F32; int16 derivatives:

@@ -349,6 +349,57 @@ int bhip_distort_model_f32(bhip_ctx* ctx, const float* src, int sStart, int sStr
  * min(n, target) pairs.  Used by FastHessianFeatureDetector (maxFeaturesPerScale > 0) and GeneralFeatureDetector (maxFeatures > 0). */
 int bhip_select_nbest_f32(bhip_ctx* ctx, const float* intensity, int start, int stride, int width, int height, const int16_t* xy, int n, int target,
 						  int positive, int16_t* out_xy, int* out_n);
+/* ---- template matching: TemplateMatchingIntensity / TemplateMatching of FactoryTemplateMatching.createIntensity / createMatcher (template.hip) ---- */
+typedef enum { BHIP_TEMPLATE_SAD = 0, BHIP_TEMPLATE_SSE = 1, BHIP_TEMPLATE_NCC = 2, BHIP_TEMPLATE_CORRELATION = 3 } bhip_template_score;   /* TemplateScoreType ordinals */
+#define BHIP_TEMPLATE_MAX_WIDTH 160          /* template columns the kernel's staged rows hold; the template height is not limited */
+#define BHIP_TEMPLATE_MAX_CANDIDATES 65536   /* candidates per image bhip_template_select_f32 / _dev_f32 take */
+/* TemplateMatchingIntensity.setInputImage(image); process(template) / process(template, mask); getIntensity() of
+ * FactoryTemplateMatching.createIntensity(SUM_ABSOLUTE_DIFFERENCE | SUM_SQUARE_ERROR | NCC, GrayU8.class | GrayF32.class)
+ * (F:factory/feature/detect/template/FactoryTemplateMatching.java:47-99): TemplateIntensityImage
+ * (F:alg/feature/detect/template/TemplateIntensityImage.java:56-125) over TemplateSumAbsoluteDifference (TemplateSumAbsoluteDifference.java:46-128),
+ * TemplateSumSquaredError (TemplateSumSquaredError.java:46-144) or TemplateNCC (TemplateNCC.java:54-274).  mask == NULL: process(template).
+ * Single-threaded reference results, bit for bit (the library is built with -ffp-contract=off; divide and sqrt are correctly rounded).
+ * The image is W x H, the template tw x th: w = W-tw+1, h = H-th+1, bx0 = tw/2, by0 = th/2, bx1 = tw-bx0, by1 = th-by0.
+ *   intensity[y+by0][x+bx0] = evaluate(x, y) for x < w, y < h; every other pixel of the W x H intensity image is 0.
+ * evaluate(x, y) compares I = image[y+j][x+i] with T = template[j][i] (and m = mask[j][i]) for j < th (outer loop), i < tw (inner loop); fp32
+ * operations are separate (no fused multiply-add), `total` is a float that starts at 0:
+ *   SAD  GrayU8:  int rowTotal = sum_i |I-T|, masked sum_i m*|I-T|; total += rowTotal (int to float, then the fp32 add), row by row.
+ *        GrayF32: float rowTotal += |I-T|, masked rowTotal += m*|I-T|, in order; total += rowTotal.
+ *   SSE  div = 255.0f*255.0f.  GrayU8: int rowTotal = sum_i e*e with e = I-T, masked sum_i m*e*e in Java int arithmetic (it wraps at 32 bits);
+ *        total += rowTotal/div.  GrayF32: float rowTotal += e*e, masked rowTotal += (m*e)*e; total += rowTotal/div.
+ *   NCC  area = (float)(tw*th).  Once per template, in order: templateMean = (sum of T)/area, templateSigma = (float)sqrt((sum of
+ *        (T-templateMean)^2)/area).  Per pixel the image sum comes first (GrayU8: int imageSum, imageMean = imageSum/area; GrayF32: a sequential
+ *        float sum, then /= area); a second pass accumulates, with diff = I-imageMean, imageSigma += diff*diff and top += diff*(T-templateMean),
+ *        masked top += (m*diff)*(T-templateMean) -- the mask enters nothing else; imageSigma = (float)sqrt(imageSigma/area); the result is
+ *        top/(EPS + imageSigma*templateSigma).  EPS = UtilEjml.F_EPS; EJML is not part of the reference tree: the library uses (float)2^-21,
+ *        EJML's definition -- "parity unpinned" against the jar.
+ * isMaximize(): NCC true, SAD and SSE false.  isBorderProcessed(): false.
+ * Deviation: the masked process(template, mask) of the reference does not fill the border, which keeps what an earlier call left there; the
+ * library writes the whole intensity view on every call, 0 in the border (the result of a freshly constructed object).
+ * BHIP_ERR_UNSUPPORTED and nothing is written: score CORRELATION (TemplateCorrelationFFT); tw > BHIP_TEMPLATE_MAX_WIDTH (160).
+ * BHIP_ERR_INVALID and nothing is written: an unknown score; an empty image or template; a template larger than the image (the reference
+ * indexes outside its arrays); a mask whose size is not the template's.
+ * Domain: inputs are finite.  With NaN / Inf nothing outside the views is read or written; the values are unspecified.
+ * Image, template, mask and intensity must not overlap (not detected).  Host form: one image; start / stride in elements. */
+int bhip_template_intensity_u8(bhip_ctx* ctx, int score, const uint8_t* image, int iStart, int iStride, int width, int height, const uint8_t* templ, int tStart,
+							   int tStride, int tWidth, int tHeight, const uint8_t* mask, int mStart, int mStride, int mWidth, int mHeight, float* intensity, int oStart,
+							   int oStride);
+int bhip_template_intensity_f32(bhip_ctx* ctx, int score, const float* image, int iStart, int iStride, int width, int height, const float* templ, int tStart,
+								int tStride, int tWidth, int tHeight, const float* mask, int mStart, int mStride, int mWidth, int mHeight, float* intensity, int oStart,
+								int oStride);
+/* The selection of TemplateMatching.process() (F:alg/feature/detect/template/TemplateMatching.java:117-176) after the non-maximum suppression:
+ * `intensity` is the sub-image [bx0, bx0+w) x [by0, by0+h) of the template intensity, xy the n candidates the extractor found in it (the
+ * maxima of bhip_nonmax_block_f32 for NCC, the minima of bhip_nonmax_block_minmax_f32 for SAD / SSE; radius 2 unless setMinimumSeparation,
+ * threshold -Float.MAX_VALUE, border 0).  scores[i] = sgn*intensity(xy[i]) with sgn = -1 when maximize and +1 otherwise, N = min(maxMatches, n),
+ * QuickSelect.selectIndex(scores, N, n, indexes) -- also when N == n: the list is permuted, there is no shortcut -- then match i is
+ * out_xy[i] = xy[indexes[i]] (the template's top-left corner) with out_score[i] = -scores[indexes[i]], the score of that candidate: the
+ * intensity for NCC, minus the intensity for SAD / SSE (the reference's own TestTemplateMatching pins a match's score to its candidate's
+ * intensity; the restated routine permutes the key array it is given, so the score is read from the keys as they were before it ran).
+ * *out_n = N; n == 0 gives no matches.  The routine is the restated one of bhip_select_nbest_f32: the kept set is pinned, the order is
+ * "parity unpinned" against the ddogleg jar.
+ * BHIP_ERR_INVALID: a candidate outside the view, n or maxMatches < 0.  BHIP_ERR_UNSUPPORTED: n > BHIP_TEMPLATE_MAX_CANDIDATES (65536). */
+int bhip_template_select_f32(bhip_ctx* ctx, const float* intensity, int start, int stride, int width, int height, const int16_t* xy, int n, int maxMatches,
+							 int maximize, int16_t* out_xy, float* out_score, int* out_n);
 /* FastHessianFeatureDetector.detect(ii) (F:alg/feature/detect/interest/FastHessianFeatureDetector.java:156-188) on a host integral image */
 int bhip_fh_detect_f32(bhip_ctx* ctx, const bhip_fh_cfg* cfg, const float* ii, int iiStart, int iiStride, int width, int height, double* xy_scale,
 					   int cap, int* n);
@@ -586,6 +637,24 @@ int bhip_disparity_bm_dev_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg,
 int bhip_disparity_bm_dev_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* dev_left, long long lImageStride, int lStride,
 								 const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, float* dev_disp,
 								 long long dImageStride, int dStride);
+/* bhip_template_intensity_u8 / _f32 on a batch of device images (strides in elements; any byte alignment of a GrayU8 view): image b is
+ * dev_image + b*iImageStride and writes dev_intensity + b*oImageStride, the whole width x height view and nothing outside it.  tImageStride /
+ * mImageStride 0: one template / mask shared by the batch; otherwise image b is matched against dev_templ + b*tImageStride (and
+ * dev_mask + b*mImageStride).  dev_mask == NULL: no mask.  No host synchronisation. */
+int bhip_template_intensity_dev_u8(bhip_ctx* ctx, int score, const uint8_t* dev_image, long long iImageStride, int iStride, int width, int height, int batch,
+								   const uint8_t* dev_templ, long long tImageStride, int tStride, int tWidth, int tHeight, const uint8_t* dev_mask,
+								   long long mImageStride, int mStride, int mWidth, int mHeight, float* dev_intensity, long long oImageStride, int oStride);
+int bhip_template_intensity_dev_f32(bhip_ctx* ctx, int score, const float* dev_image, long long iImageStride, int iStride, int width, int height, int batch,
+									const float* dev_templ, long long tImageStride, int tStride, int tWidth, int tHeight, const float* dev_mask,
+									long long mImageStride, int mStride, int mWidth, int mHeight, float* dev_intensity, long long oImageStride, int oStride);
+/* bhip_template_select_f32 on every image of a batch: image b's candidates are dev_xy[b*cap ...], the first min(dev_n[b], cap) of them (the
+ * lists and counts of bhip_nonmax_block_dev_f32 / bhip_nonmax_block_minmax_dev_f32: a list the extractor cut at cap is selected from as it
+ * is); its matches go to dev_out_xy[b*maxMatches ...] and dev_out_score[b*maxMatches ...], their number to dev_out_n[b].  A candidate outside
+ * the view reads as intensity 0.  One wave per image runs the sequential routine on one lane, as for the N best per scale.
+ * BHIP_ERR_UNSUPPORTED: cap > BHIP_TEMPLATE_MAX_CANDIDATES (65536).  No host synchronisation. */
+int bhip_template_select_dev_f32(bhip_ctx* ctx, const float* dev_intensity, long long imageStride, int stride, int width, int height, int batch,
+								 const int16_t* dev_xy, const int* dev_n, int cap, int maxMatches, int maximize, int16_t* dev_out_xy, float* dev_out_score,
+								 int* dev_out_n);
 /* bhip_distort_map_u8 / _f32 on a batch of device images (strides in elements; any byte alignment of a GrayU8 view): image b reads
  * dev_src + b*sImageStride (sw x sh) and the map dev_map + b*mapImageStride (dw*dh interleaved float (x, y) pairs, dense; mapImageStride in
  * floats, 0 = one map shared by the batch, the usual case of one map per camera), and writes the crop of dev_dst + b*dImageStride (dw x dh)
