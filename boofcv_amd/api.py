@@ -43,6 +43,35 @@ def _check(ctx, status):
     raise RuntimeError("boofhip status %d: %s" % (status, msg))
 
 
+class _NativeObject:
+    """A Python object that owns one native handle (_h) created on a Context (ctx): bhip_surf, bhip_klt or bhip_bg, destroyed with the
+    export named by _destroy.  close() (or garbage collection) destroys it; closing the context closes it first."""
+    _destroy = None
+    _h = None
+
+    def _adopt(self, handle):
+        self._h = handle
+        self.ctx._children.add(self)
+
+    def _closed(self):
+        """what a subclass forgets with its handle"""
+
+    def close(self):
+        """Releases the native object (idempotent; safe after its context has been closed)."""
+        if self._h:
+            getattr(_lib.load(), self._destroy)(self._h)
+            self._h = None
+            self._closed()
+
+    def __del__(self, _finalizing=sys.is_finalizing):   # (bound at definition: module globals are gone when this runs late in shutdown)
+        try:
+            if _finalizing():
+                return   # the atexit hook below has closed what was alive; the native library ignores destroy calls after exit began
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     """bhip_ctx: one per host thread per device.
 
@@ -99,13 +128,7 @@ class Context:
             _lib.load().bhip_ctx_destroy(self._h)
             self._h = None
 
-    def __del__(self, _finalizing=sys.is_finalizing):   # (bound at definition: module globals are gone when this runs late in shutdown)
-        try:
-            if _finalizing():
-                return   # the atexit hook below has closed what was alive; the native library ignores destroy calls after exit began
-            self.close()
-        except Exception:
-            pass
+    __del__ = _NativeObject.__del__
 
     @classmethod
     def _close_all(cls):
@@ -497,11 +520,12 @@ class ConfigExtract:
 # ------------------------------------------------------------------------------------------------------------------
 # detect + describe
 # ------------------------------------------------------------------------------------------------------------------
-class DetectDescribePoint:
+class DetectDescribePoint(_NativeObject):
     """DetectDescribePoint<GrayF32,BrightFeature> backed by bhip_surf (WrapDetectDescribeSurf.java:47-159).
 
     Results are recycled on the next detect(), instances are not thread safe -- both as in the reference.
     detectBatch() is the batched extension (one launch sequence for many frames)."""
+    _destroy = "bhip_surf_destroy"
 
     def __init__(self, stable, configDetector, configDescribe, configOrientation, ctx=None):
         self.ctx = ctx or Context.default()
@@ -521,26 +545,11 @@ class DetectDescribePoint:
             raise RuntimeError("useHaar=true is not implemented on the GPU (use the Java path)")
         h = C.c_void_p()
         _check(self.ctx, L.bhip_surf_create(self.ctx._h, C.byref(fh), C.byref(sd), C.byref(oc), 1 if stable else 0, C.byref(h)))
-        self._h = h
-        self.ctx._children.add(self)
+        self._adopt(h)
         self._dof = L.bhip_surf_dof(h)
         self._batch = 0
         self._image = 0
         self._cache = {}
-
-    def close(self):
-        """Releases the native object (idempotent; safe after its context has been closed)."""
-        if self._h:
-            _lib.load().bhip_surf_destroy(self._h)
-            self._h = None
-
-    def __del__(self, _finalizing=sys.is_finalizing):
-        try:
-            if _finalizing():
-                return
-            self.close()
-        except Exception:
-            pass
 
     # --- DescriptorInfo
     def createDescription(self):
@@ -905,8 +914,7 @@ class DetectDescribeFusion(DetectDescribePoint):
         h = C.c_void_p()
         _check(self.ctx, L.bhip_surf_create_brief(self.ctx._h, C.byref(fh), d.radius, describe.length, d.samplePoints.ctypes.data_as(_lib._i32p),
                                                   d.compare.ctypes.data_as(_lib._i32p), C.byref(h)))
-        self._h = h
-        self.ctx._children.add(self)
+        self._adopt(h)
         self._dof = 0
         self._batch = 0
         self._image = 0
@@ -2285,13 +2293,14 @@ class PyramidKltTracker:
         return self.tracker.getError()
 
 
-class PointTrackerKltPyramid:
+class PointTrackerKltPyramid(_NativeObject):
     """G:abst/feature/tracker/PointTrackerKltPyramid.java:139-348 as FactoryPointTracker.klt builds it (Shi-Tomasi radius 1 unweighted, Sobel with
     BorderType.EXTENDED, discreteGaussian(scaling, -1, 2), bilinear interpolation; imageType GrayF32 with GrayF32 derivatives, or GrayU8 with
     GrayS16 derivatives on bhip_klt_create_u8 / bhip_klt_process_u8) over one bhip_klt with batch = 1: pyramid, gradient, tracking,
     re-description, corner detection and the track lists all stay on the device.  Differences from the Java object: the lists are returned as
     fresh PointTrack objects (positions are the float PyramidKltFeature.x,y; cookie / description are not kept between calls), dropTrack finds
     its track by featureId, addTrack gives featureId -1, and a track at a position where the reference throws is dropped (fault 5)."""
+    _destroy = "bhip_klt_destroy"
 
     def __init__(self, config, templateRadius, scaling, configExtract, ctx=None, detectBorder=None, imageType=None):
         self.ctx = _ctx(ctx)
@@ -2305,9 +2314,7 @@ class PointTrackerKltPyramid:
             raise RuntimeError("only the strict maxima extractor is implemented on the GPU")
         # FactoryDetectPoint.createGeneral: ignoreBorder += radius; GeneralFeatureDetector: at least the intensity's own border (Shi-Tomasi radius 1)
         self.detectBorder = max(self.configExtract.ignoreBorder + self.configExtract.radius, 1) if detectBorder is None else int(detectBorder)
-        self._h = None
         self._shape = None
-        self.ctx._children.add(self)
 
     def _create(self, width, height):
         self.close()
@@ -2318,19 +2325,8 @@ class PointTrackerKltPyramid:
         create = L.bhip_klt_create_u8 if self.imageType is GrayU8 else L.bhip_klt_create
         _check(self.ctx, create(self.ctx._h, C.byref(cfg), self.templateRadius, sc, len(self.scaling), int(self.configExtract.radius),
                                 float(self.configExtract.threshold), int(self.detectBorder), width, height, 1, C.byref(h)))
-        self._h, self._shape = h, (width, height)
-
-    def close(self):
-        if self._h:
-            _lib.load().bhip_klt_destroy(self._h)
-            self._h = None
-
-    def __del__(self, _finalizing=sys.is_finalizing):
-        try:
-            if not _finalizing():
-                self.close()
-        except Exception:
-            pass
+        self._adopt(h)
+        self._shape = (width, height)
 
     def _need(self):
         if not self._h:
@@ -3059,17 +3055,17 @@ def _bg_image_kind(imageType):
     return family, (_lib.BHIP_PIXEL_U8 if band is GrayU8 else _lib.BHIP_PIXEL_F32), bands
 
 
-class BackgroundModelStationary:
+class BackgroundModelStationary(_NativeObject):
     """BackgroundModel + BackgroundModelStationary (F:alg/background/BackgroundModel.java, BackgroundModelStationary.java) over one bhip_bg with
     one stream.  The native handle has a fixed frame size: this class creates it at the first frame and replaces it when the reference
     re-initialises for another size; the InputSanityCheck errors are raised here."""
     _alg = None
+    _destroy = "bhip_bg_destroy"
 
     def __init__(self, imageType, ctx=None):
         self.imageType = imageType
         self._family, self._pixel, self._bands = _bg_image_kind(imageType)
-        self._ctx = ctx
-        self._h = None
+        self.ctx = ctx              # None: Context.default(), looked up when the handle is created
         self._size = None           # (width, height) the handle was created for
         self.unknownValue = 0
         self._mw = self._mh = 0     # the reference model's width / height ("not initialised" is a test on them)
@@ -3083,40 +3079,30 @@ class BackgroundModelStationary:
             raise IllegalArgumentException("out of range. 0 to 255")
         self.unknownValue = int(unknownValue)
         if self._h:
-            _check(self._ctx, _lib.load().bhip_bg_set_unknown_value(self._h, self.unknownValue))
+            _check(self.ctx, _lib.load().bhip_bg_set_unknown_value(self._h, self.unknownValue))
 
     def getImageType(self):
         return self.imageType
 
-    def close(self):
-        if self._h:
-            _lib.load().bhip_bg_destroy(self._h)
-            self._h = None
-            self._size = None
-
-    def __del__(self, _finalizing=sys.is_finalizing):
-        try:
-            if not _finalizing():
-                self.close()
-        except Exception:
-            pass
+    def _closed(self):
+        self._size = None
 
     # ---- the native side ----
     def _set(self, name, value):
         if self._h:
-            _check(self._ctx, getattr(_lib.load(), "bhip_bg_set_" + name)(self._h, value))
+            _check(self.ctx, getattr(_lib.load(), "bhip_bg_set_" + name)(self._h, value))
 
     def _handle(self, width, height):
         """the handle for width x height frames, created (and the old one dropped) when the size differs"""
         if self._h and self._size == (width, height):
             return
         self.close()
-        if self._ctx is None:
-            self._ctx = Context.default()
+        if self.ctx is None:
+            self.ctx = Context.default()
         h = C.c_void_p()
-        _check(self._ctx, self._create(_lib.load(), width, height, h))
-        self._h, self._size = h, (width, height)
-        self._ctx._children.add(self)
+        _check(self.ctx, self._create(_lib.load(), width, height, h))
+        self._adopt(h)
+        self._size = (width, height)
         self._push()
         self._set("unknown_value", self.unknownValue)
 
@@ -3139,18 +3125,18 @@ class BackgroundModelStationary:
         mp, ms, mst = (mask._p(), mask.startIndex, mask.stride) if mask is not None else (None, 0, 0)
         if segment:
             fn = L.bhip_bg_segment_u8 if u8 else L.bhip_bg_segment_f32
-            _check(self._ctx, fn(self._h, ptr, start, 0, bandStride, stride, mp, ms, 0, mst))
+            _check(self.ctx, fn(self._h, ptr, start, 0, bandStride, stride, mp, ms, 0, mst))
         else:
             fn = L.bhip_bg_update_u8 if u8 else L.bhip_bg_update_f32
-            _check(self._ctx, fn(self._h, ptr, start, 0, 0, bandStride, stride, 1, mp, ms, 0, 0, mst))
+            _check(self.ctx, fn(self._h, ptr, start, 0, 0, bandStride, stride, 1, mp, ms, 0, 0, mst))
         del keep
 
     def _fetch(self):
         L = _lib.load()
         n = C.c_longlong()
-        _check(self._ctx, L.bhip_bg_model_floats(self._h, C.byref(n)))
+        _check(self.ctx, L.bhip_bg_model_floats(self._h, C.byref(n)))
         out = np.zeros(n.value, np.float32)
-        _check(self._ctx, L.bhip_bg_fetch_model(self._h, 0, out.ctypes.data_as(_lib._fp)))
+        _check(self.ctx, L.bhip_bg_fetch_model(self._h, 0, out.ctypes.data_as(_lib._fp)))
         return out
 
     @staticmethod
@@ -3166,7 +3152,7 @@ class BackgroundModelStationary:
     def reset(self):
         self._mw = self._mh = self._reset_size
         if self._h:
-            _check(self._ctx, _lib.load().bhip_bg_reset(self._h, -1))
+            _check(self.ctx, _lib.load().bhip_bg_reset(self._h, -1))
 
 
 class BackgroundStationaryBasic(BackgroundModelStationary):
@@ -3183,7 +3169,7 @@ class BackgroundStationaryBasic(BackgroundModelStationary):
         cfg = _lib.BgBasicCfg()
         L.bhip_bg_basic_cfg_default(C.byref(cfg))
         cfg.threshold = 1
-        return L.bhip_bg_create_basic(self._ctx._h, C.byref(cfg), self._family, self._pixel, self._bands, width, height, 1, C.byref(h))
+        return L.bhip_bg_create_basic(self.ctx._h, C.byref(cfg), self._family, self._pixel, self._bands, width, height, 1, C.byref(h))
 
     def _push(self):
         self._set("learn_rate", self.learnRate)
@@ -3210,7 +3196,7 @@ class BackgroundStationaryBasic(BackgroundModelStationary):
         """updateBackground(frame) or updateBackground(frame, segment): update, then segment"""
         if self._uninitialised(frame):
             self._handle(frame.width, frame.height)
-            _check(self._ctx, _lib.load().bhip_bg_reset(self._h, -1))
+            _check(self.ctx, _lib.load().bhip_bg_reset(self._h, -1))
             self._mw, self._mh = frame.width, frame.height
         elif (self._mw, self._mh) != (frame.width, frame.height):
             raise IllegalArgumentException("Image shapes do not match")
@@ -3255,7 +3241,7 @@ class BackgroundStationaryGaussian(BackgroundStationaryBasic):
         cfg = _lib.BgGaussianCfg()
         L.bhip_bg_gaussian_cfg_default(C.byref(cfg))
         cfg.threshold = 1
-        return L.bhip_bg_create_gaussian(self._ctx._h, C.byref(cfg), self._family, self._pixel, self._bands, width, height, 1, C.byref(h))
+        return L.bhip_bg_create_gaussian(self.ctx._h, C.byref(cfg), self._family, self._pixel, self._bands, width, height, 1, C.byref(h))
 
     def _push(self):
         BackgroundStationaryBasic._push(self)
@@ -3310,7 +3296,7 @@ class BackgroundStationaryGmm(BackgroundModelStationary):
         L.bhip_bg_gmm_cfg_default(C.byref(cfg))
         cfg.numberOfGaussian = self.maxGaussians
         cfg.decayCoefient = self.decay
-        return L.bhip_bg_create_gmm(self._ctx._h, C.byref(cfg), self._family, self._pixel, self._bands, width, height, 1, C.byref(h))
+        return L.bhip_bg_create_gmm(self.ctx._h, C.byref(cfg), self._family, self._pixel, self._bands, width, height, 1, C.byref(h))
 
     def _push(self):
         self._set("learning_period", self._period)
@@ -3352,7 +3338,7 @@ class BackgroundStationaryGmm(BackgroundModelStationary):
     def updateBackground(self, frame, mask=None):
         if (self._mw, self._mh) != (frame.width, frame.height):
             self._handle(frame.width, frame.height)
-            _check(self._ctx, _lib.load().bhip_bg_reset(self._h, -1))
+            _check(self.ctx, _lib.load().bhip_bg_reset(self._h, -1))
             self._mw, self._mh = frame.width, frame.height
         if mask is not None:
             mask.reshape(frame.width, frame.height)

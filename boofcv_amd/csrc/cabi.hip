@@ -7,6 +7,7 @@
 #include <atomic>
 #include <memory>
 #include <mutex>
+#include <unordered_map>
 #include <unordered_set>
 
 // Per-context scratch that the stateless entry points reuse (freed with the context).  The staging slots belong to the host-buffer export
@@ -26,19 +27,18 @@ struct bhip_ctx_full : bhip_ctx {
 };
 static CtxScratch* scratchOf(bhip_ctx* ctx) { return &static_cast<bhip_ctx_full*>(ctx)->scratch; }
 
-// Handle registry: which bhip_ctx / bhip_surf pointers are live.  The destroy calls may arrive in any order (a garbage-collected host
-// language finalises objects in no particular order; a caller may close the context first) and more than once: destroying a context
-// releases the device side of every detect+describe object created on it and leaves those objects as inert shells (every call on them
-// returns BHIP_ERR_INVALID, bhip_surf_destroy only frees the shell); a pointer that is not in the registry is refused instead of
-// dereferenced.  Once the process has started to exit (atexit) the destroy calls touch neither the HIP runtime nor the handles -- the
-// runtime's own teardown may already have run.  The registry is a leaked singleton so it outlives every static destructor.  Creating an
-// object holds the lock from the context's liveness check to the insert, so a concurrent bhip_ctx_destroy waits for it.
+// Handle registry: which bhip_ctx pointers and which of their children (bhip_surf, bhip_klt, bhip_bg) are live.  The destroy calls may
+// arrive in any order (a garbage-collected host language finalises objects in no particular order; a caller may close the context first)
+// and more than once: destroying a context releases the device side of every child created on it and leaves those objects as inert shells
+// (every call on them returns BHIP_ERR_INVALID, their destroy only frees the shell); a pointer that is not in the registry, or is a child
+// of another kind, is refused instead of dereferenced.  Once the process has started to exit (atexit) the destroy calls touch neither the
+// HIP runtime nor the handles -- the runtime's own teardown may already have run.  The registry is a leaked singleton so it outlives
+// every static destructor.
+using OrphanFn = void (*)(void* child, bhip_ctx* ctx);   // orphanIfOn<X>; its address is also what tells the kinds of children apart
 struct HandleRegistry {
 	std::mutex m;
 	std::unordered_set<bhip_ctx*> ctxs;
-	std::unordered_set<bhip_surf*> surfs;
-	std::unordered_set<bhip_klt*> klts;
-	std::unordered_set<bhip_bg*> bgs;
+	std::unordered_map<void*, OrphanFn> children;
 	std::atomic<bool> exiting{false};
 };
 static HandleRegistry& registry() {
@@ -49,9 +49,55 @@ static HandleRegistry& registry() {
 	}();
 	return *r;
 }
-static void surfOrphanChildren(bhip_ctx* ctx);   // registry lock held: releases the device side of every live bhip_surf created on ctx
-static void kltOrphanChildren(bhip_ctx* ctx);    // the same for every live bhip_klt
-static void bgOrphanChildren(bhip_ctx* ctx);     // and every live bhip_bg
+
+// What the three kinds of children share: Dev is everything the object holds on its context's device, dropped as a whole by destruction
+// or by releaseDevice; ctx == nullptr marks the inert shell.
+template <class Dev>
+struct CtxChild : Dev {
+	using Device = Dev;
+	bhip_ctx* ctx = nullptr;
+	void onRelease() {}   // a type's own part of releaseDevice; the context's stream has been synchronized, the device side is still there
+};
+// Frees everything x holds on the device (its context must still be alive) and detaches it from the context.  Registry lock held.
+template <class X>
+static void releaseDevice(X* x) {
+	if (!x->ctx) return;   // the context went first
+	(void)hipSetDevice(x->ctx->device);
+	(void)hipStreamSynchronize(x->ctx->stream);
+	x->onRelease();
+	static_cast<typename X::Device&>(*x) = typename X::Device();
+	x->ctx = nullptr;
+}
+template <class X>
+static void orphanIfOn(void* child, bhip_ctx* ctx) {
+	if (static_cast<X*>(child)->ctx == ctx) releaseDevice(static_cast<X*>(child));
+}
+// The create call of a child: holds the registry lock from the context's liveness check to the insert, so a concurrent bhip_ctx_destroy
+// waits for it.  build(std::unique_ptr<X>&) does the type's own argument checks (a null `out` among them) and the construction.
+template <class X, class Build>
+static int createChild(bhip_ctx* ctx, X** out, Build build) {
+	HandleRegistry& R = registry();
+	std::lock_guard<std::mutex> lock(R.m);
+	if (!ctx || !R.ctxs.count(ctx)) return BHIP_ERR_INVALID;
+	std::unique_ptr<X> x;
+	BHIP_TRY(build(x));
+	R.children.emplace(x.get(), &orphanIfOn<X>);
+	*out = x.release();
+	return BHIP_OK;
+}
+template <class X>
+static int destroyChild(X* x) {
+	if (!x) return BHIP_OK;
+	HandleRegistry& R = registry();
+	std::lock_guard<std::mutex> lock(R.m);
+	if (R.exiting) return BHIP_OK;                                                       // process teardown: the runtime reclaims everything
+	auto it = R.children.find(x);
+	if (it == R.children.end() || it->second != &orphanIfOn<X>) return BHIP_ERR_INVALID;   // not a live object of this kind (destroyed twice, never created, another kind)
+	R.children.erase(it);
+	releaseDevice(x);
+	delete x;
+	return BHIP_OK;
+}
 
 extern "C" {
 
@@ -121,10 +167,7 @@ int bhip_ctx_destroy(bhip_ctx* c) {
 	R.ctxs.erase(c);
 	(void)hipSetDevice(c->device);
 	(void)hipStreamSynchronize(c->stream);
-	// detect+describe objects still alive on this context lose their device side now and become inert shells
-	surfOrphanChildren(c);
-	kltOrphanChildren(c);
-	bgOrphanChildren(c);
+	for (auto& child : R.children) child.second(child.first, c);   // children still alive on this context become inert shells now
 	delete static_cast<bhip_ctx_full*>(c);   // scratch, profiling events, staging block, then the stream it owns
 	return BHIP_OK;
 }
@@ -495,8 +538,7 @@ struct FhDetector {
 // ---------------------------------------------------------------------------------------------------------------
 // SURF detect + describe object
 // ---------------------------------------------------------------------------------------------------------------
-// Everything a detect+describe object holds on its context's device.  It is dropped as a whole, by destruction or by assigning an empty
-// SurfDevice (surfReleaseDevice); the owner synchronizes the context stream and the copy stream first.
+// Everything a detect+describe object holds on its context's device (CtxChild); its owner synchronizes the copy stream too before dropping it.
 struct SurfDevice {
 	FhDetector det;
 	DevBuf tabBuf, inBuf, iiBuf, startBuf, angBuf, descBuf, whiteBuf, xysBuf, tmpKp, tmpAng, tmpDesc, tmpWhite, permBuf;
@@ -509,8 +551,11 @@ struct SurfDevice {
 	const int* briefBorrow = nullptr;   // chunk worker: the owner's BRIEF table (not owned: never freed twice)
 };
 
-struct bhip_surf : SurfDevice {
-	bhip_ctx* ctx = nullptr;
+struct bhip_surf : CtxChild<SurfDevice> {
+	void onRelease() {   // the chunk worker is owned by this object and is not in the registry: it goes with the SurfDevice
+		if (copyStream) (void)hipStreamSynchronize(copyStream);
+		haveResult = false;
+	}
 	int stable = 1;
 	bhip_surf_cfg sd;
 	bhip_ori_cfg ori;
@@ -826,22 +871,6 @@ static int surfCreateUnregistered(bhip_ctx* ctx, const bhip_fh_cfg* fh, const bh
 	return BHIP_OK;
 }
 
-// Frees everything s holds on the device (its context must still be alive) and detaches it from the context: s is an inert shell afterwards.
-// The chunk worker is owned by s and is not in the registry.
-static void surfReleaseDevice(bhip_surf* s) {
-	if (!s->ctx) return;
-	(void)hipSetDevice(s->ctx->device);
-	(void)hipStreamSynchronize(s->ctx->stream);
-	if (s->copyStream) (void)hipStreamSynchronize(s->copyStream);
-	static_cast<SurfDevice&>(*s) = SurfDevice();
-	s->haveResult = false;
-	s->ctx = nullptr;
-}
-static void surfOrphanChildren(bhip_ctx* ctx) {
-	for (bhip_surf* s : registry().surfs)
-		if (s->ctx == ctx) surfReleaseDevice(s);
-}
-
 // every sample point the pairs use lies within [-radius, radius]^2: the LDS-patch BRIEF kernel may be used (ip.hip, k_brief_patch)
 static bool briefPatchOk(const int32_t* samplePoints, int nSamples, int radius) {
 	for (int i = 0; i < 2 * nSamples; i++)
@@ -960,30 +989,15 @@ static int fhDetect(bhip_ctx* ctx, const bhip_fh_cfg* cfg, HostImg<const T> hin,
 extern "C" {
 
 int bhip_surf_create(bhip_ctx* ctx, const bhip_fh_cfg* fh, const bhip_surf_cfg* surf, const bhip_ori_cfg* ori, int stable, bhip_surf** out) {
-	HandleRegistry& R = registry();
-	std::lock_guard<std::mutex> lock(R.m);
-	if (!ctx || !R.ctxs.count(ctx)) return BHIP_ERR_INVALID;
-	CHECK_CTX(ctx);
-	if (!out) return bhip_fail(ctx, BHIP_ERR_INVALID, "null output");
-	*out = nullptr;
-	std::unique_ptr<bhip_surf> s;
-	BHIP_TRY(surfCreateUnregistered(ctx, fh, surf, ori, stable, s));
-	R.surfs.insert(s.get());
-	*out = s.release();
-	return BHIP_OK;
+	return createChild(ctx, out, [&](std::unique_ptr<bhip_surf>& s) -> int {
+		CHECK_CTX(ctx);
+		if (!out) return bhip_fail(ctx, BHIP_ERR_INVALID, "null output");
+		*out = nullptr;
+		return surfCreateUnregistered(ctx, fh, surf, ori, stable, s);
+	});
 }
 
-int bhip_surf_destroy(bhip_surf* s) {
-	if (!s) return BHIP_OK;
-	HandleRegistry& R = registry();
-	std::lock_guard<std::mutex> lock(R.m);
-	if (R.exiting) return BHIP_OK;                       // process teardown: the runtime reclaims everything
-	if (!R.surfs.count(s)) return BHIP_ERR_INVALID;      // not a live object (destroyed twice, or never created)
-	R.surfs.erase(s);
-	surfReleaseDevice(s);                                // no-op when the context went first
-	delete s;
-	return BHIP_OK;
-}
+int bhip_surf_destroy(bhip_surf* s) { return destroyChild(s); }
 
 int bhip_surf_dof(bhip_surf* s) { return s ? s->dofOut() : 0; }
 
@@ -1115,31 +1129,27 @@ int bhip_surf_dev_view(bhip_surf* s, int image, const double** dev_desc, const d
 // (F:factory/feature/detdesc/FactoryDetectDescribe.java:279-284, F:factory/feature/describe/FactoryDescribeRegionPoint.java:187-202 with
 // config.fixed): the returned object is driven through the same bhip_surf_detect_* / _count / _fetch calls as the SURF one.
 int bhip_surf_create_brief(bhip_ctx* ctx, const bhip_fh_cfg* fh, int radius, int numPoints, const int32_t* samplePoints, const int32_t* compare, bhip_surf** out) {
-	HandleRegistry& R = registry();
-	std::lock_guard<std::mutex> lock(R.m);
-	if (!ctx || !R.ctxs.count(ctx)) return BHIP_ERR_INVALID;
-	CHECK_CTX(ctx);
-	if (!out) return bhip_fail(ctx, BHIP_ERR_INVALID, "null output");
-	*out = nullptr;
-	if (radius < 0 || numPoints <= 0 || !samplePoints || !compare) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad BRIEF definition");
-	int maxIdx = 0;
-	for (int i = 0; i < 2 * numPoints; i++) {
-		if (compare[i] < 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "negative sample index");
-		maxIdx = std::max(maxIdx, compare[i]);
-	}
-	std::unique_ptr<bhip_surf> s;
-	BHIP_TRY(surfCreateUnregistered(ctx, fh, nullptr, nullptr, 0, s));   // (the SURF tables of the shell are never used)
-	s->brief = true;
-	s->briefRadius = radius; s->briefPoints = numPoints; s->briefWords = (numPoints + 31) / 32;
-	const size_t nSample = (size_t)(maxIdx + 1) * 2, nCompare = (size_t)numPoints * 2;
-	s->briefCompareOff = nSample;
-	s->briefPatch = briefPatchOk(samplePoints, maxIdx + 1, radius);
-	BHIP_TRY(s->briefTab.reserve(ctx, (nSample + nCompare) * 4));
-	if (hipMemcpy(s->briefTab.p, samplePoints, nSample * 4, hipMemcpyHostToDevice) != hipSuccess) return bhip_fail(ctx, BHIP_ERR_HIP, "BRIEF table upload");
-	if (hipMemcpy(s->briefTab.as<int>() + nSample, compare, nCompare * 4, hipMemcpyHostToDevice) != hipSuccess) return bhip_fail(ctx, BHIP_ERR_HIP, "BRIEF table upload");
-	R.surfs.insert(s.get());
-	*out = s.release();
-	return BHIP_OK;
+	return createChild(ctx, out, [&](std::unique_ptr<bhip_surf>& s) -> int {
+		CHECK_CTX(ctx);
+		if (!out) return bhip_fail(ctx, BHIP_ERR_INVALID, "null output");
+		*out = nullptr;
+		if (radius < 0 || numPoints <= 0 || !samplePoints || !compare) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad BRIEF definition");
+		int maxIdx = 0;
+		for (int i = 0; i < 2 * numPoints; i++) {
+			if (compare[i] < 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "negative sample index");
+			maxIdx = std::max(maxIdx, compare[i]);
+		}
+		BHIP_TRY(surfCreateUnregistered(ctx, fh, nullptr, nullptr, 0, s));   // (the SURF tables of the shell are never used)
+		s->brief = true;
+		s->briefRadius = radius; s->briefPoints = numPoints; s->briefWords = (numPoints + 31) / 32;
+		const size_t nSample = (size_t)(maxIdx + 1) * 2, nCompare = (size_t)numPoints * 2;
+		s->briefCompareOff = nSample;
+		s->briefPatch = briefPatchOk(samplePoints, maxIdx + 1, radius);
+		BHIP_TRY(s->briefTab.reserve(ctx, (nSample + nCompare) * 4));
+		if (hipMemcpy(s->briefTab.p, samplePoints, nSample * 4, hipMemcpyHostToDevice) != hipSuccess) return bhip_fail(ctx, BHIP_ERR_HIP, "BRIEF table upload");
+		if (hipMemcpy(s->briefTab.as<int>() + nSample, compare, nCompare * 4, hipMemcpyHostToDevice) != hipSuccess) return bhip_fail(ctx, BHIP_ERR_HIP, "BRIEF table upload");
+		return BHIP_OK;
+	});
 }
 
 // getDescription(i).data of every feature of one image (image >= 0: count * words ints) or of the whole batch (image = -1: total * words
@@ -2586,15 +2596,15 @@ struct KltTypes {
 using KltF32 = KltTypes<float, float>;      // bhip_klt_create: GrayF32 frames and derivatives
 using KltU8 = KltTypes<uint8_t, int16_t>;   // bhip_klt_create_u8: GrayU8 frames, GrayS16 derivatives
 
-// everything a tracker holds on its context's device; dropped as a whole like SurfDevice
+// everything a tracker holds on its context's device (CtxChild)
 struct KltDevice {
 	KltTable tab;
 	DevBuf frames, pyr, dx, dy, intensity, candXY, candN, stage;
 	PinnedBuf pinned;
 };
 
-struct bhip_klt : KltDevice {
-	bhip_ctx* ctx = nullptr;
+struct bhip_klt : CtxChild<KltDevice> {
+	void onRelease() { haveFrame = false; }
 	bhip_klt_cfg cfg;
 	int r = 0, L = 0, W = 0, H = 0, batch = 0;
 	int scales[BHIP_KLT_MAX_LAYERS];
@@ -2623,19 +2633,6 @@ struct bhip_klt : KltDevice {
 		return P;
 	}
 };
-
-static void kltReleaseDevice(bhip_klt* k) {
-	if (!k->ctx) return;
-	(void)hipSetDevice(k->ctx->device);
-	(void)hipStreamSynchronize(k->ctx->stream);
-	static_cast<KltDevice&>(*k) = KltDevice();
-	k->haveFrame = false;
-	k->ctx = nullptr;
-}
-static void kltOrphanChildren(bhip_ctx* ctx) {
-	for (bhip_klt* k : registry().klts)
-		if (k->ctx == ctx) kltReleaseDevice(k);
-}
 
 static bool kltRangeOk(int radius, int numLayers) { return radius >= 1 && radius <= BHIP_KLT_MAX_RADIUS && numLayers >= 1 && numLayers <= BHIP_KLT_MAX_LAYERS; }
 
@@ -2818,36 +2815,33 @@ static int kltCreate(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int templateRadius,
 					 int detectBorder, int width, int height, int batch, bool u8, bhip_klt** out) {
 	if (out) *out = nullptr;
 	if (!kltRangeOk(templateRadius, numLayers)) return BHIP_ERR_UNSUPPORTED;   // templateRadius 1..7, numLayers 1..8; nothing is touched, not even ctx
-	HandleRegistry& R = registry();
-	std::lock_guard<std::mutex> lock(R.m);
-	if (!ctx || !R.ctxs.count(ctx)) return BHIP_ERR_INVALID;
-	if (!out) return bhip_fail(ctx, BHIP_ERR_INVALID, "null output");
-	if (cfg && cfg->maxIterations < 1) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "maxIterations must be >= 1");
-	if (!scales || width <= 0 || height <= 0 || batch <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad tracker arguments");
-	CHECK_CTX(ctx);
-	std::unique_ptr<bhip_klt> k(new (std::nothrow) bhip_klt());
-	if (!k) return bhip_fail(ctx, BHIP_ERR_NOMEM, "out of host memory");
-	k->ctx = ctx;
-	if (cfg) k->cfg = *cfg; else bhip_klt_cfg_default(&k->cfg);
-	k->r = templateRadius; k->L = numLayers; k->W = width; k->H = height; k->batch = batch;
-	k->detectRadius = detectRadius; k->detectThreshold = detectThreshold; k->detectBorder = detectBorder;
-	for (int l = 0; l < numLayers; l++) k->scales[l] = scales[l];
-	if (bhip_pyramid_layout(width, height, scales, numLayers, k->dims, k->offs, &k->total) != BHIP_OK) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad pyramid scales");
-	for (int l = 1; l < numLayers; l++)
-		if (scales[l] / scales[l - 1] <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Skip must be >= 1");
-	k->u8 = u8;
-	if (u8) k->kernelS32 = bhip_gaussian1d_s32(2);
-	else k->kernel = bhip_gaussian1d_f32(-1, 2);
-	const size_t elems = (size_t)k->total * batch;
-	BHIP_TRY(k->pyr.reserve(ctx, elems * (u8 ? 1 : 4)));
-	BHIP_TRY(k->dx.reserve(ctx, elems * (u8 ? 2 : 4)));
-	BHIP_TRY(k->dy.reserve(ctx, elems * (u8 ? 2 : 4)));
-	BHIP_TRY(k->tab.alloc(ctx, batch, 1024, numLayers, templateRadius));
-	BHIP_TRY(bhip_launch_klt_init(ctx, k->tab.v, 0));
-	BHIP_TRY(bhip_ctx_synchronize(ctx));
-	R.klts.insert(k.get());
-	*out = k.release();
-	return BHIP_OK;
+	return createChild(ctx, out, [&](std::unique_ptr<bhip_klt>& k) -> int {
+		if (!out) return bhip_fail(ctx, BHIP_ERR_INVALID, "null output");
+		if (cfg && cfg->maxIterations < 1) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "maxIterations must be >= 1");
+		if (!scales || width <= 0 || height <= 0 || batch <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad tracker arguments");
+		CHECK_CTX(ctx);
+		k.reset(new (std::nothrow) bhip_klt());
+		if (!k) return bhip_fail(ctx, BHIP_ERR_NOMEM, "out of host memory");
+		k->ctx = ctx;
+		if (cfg) k->cfg = *cfg; else bhip_klt_cfg_default(&k->cfg);
+		k->r = templateRadius; k->L = numLayers; k->W = width; k->H = height; k->batch = batch;
+		k->detectRadius = detectRadius; k->detectThreshold = detectThreshold; k->detectBorder = detectBorder;
+		for (int l = 0; l < numLayers; l++) k->scales[l] = scales[l];
+		if (bhip_pyramid_layout(width, height, scales, numLayers, k->dims, k->offs, &k->total) != BHIP_OK) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad pyramid scales");
+		for (int l = 1; l < numLayers; l++)
+			if (scales[l] / scales[l - 1] <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Skip must be >= 1");
+		k->u8 = u8;
+		if (u8) k->kernelS32 = bhip_gaussian1d_s32(2);
+		else k->kernel = bhip_gaussian1d_f32(-1, 2);
+		const size_t elems = (size_t)k->total * batch;
+		BHIP_TRY(k->pyr.reserve(ctx, elems * (u8 ? 1 : 4)));
+		BHIP_TRY(k->dx.reserve(ctx, elems * (u8 ? 2 : 4)));
+		BHIP_TRY(k->dy.reserve(ctx, elems * (u8 ? 2 : 4)));
+		BHIP_TRY(k->tab.alloc(ctx, batch, 1024, numLayers, templateRadius));
+		BHIP_TRY(bhip_launch_klt_init(ctx, k->tab.v, 0));
+		BHIP_TRY(bhip_ctx_synchronize(ctx));
+		return BHIP_OK;
+	});
 }
 
 extern "C" {
@@ -2861,17 +2855,7 @@ int bhip_klt_create_u8(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int templateRadiu
 	return kltCreate(ctx, cfg, templateRadius, scales, numLayers, detectRadius, detectThreshold, detectBorder, width, height, batch, true, out);
 }
 
-int bhip_klt_destroy(bhip_klt* k) {
-	if (!k) return BHIP_OK;
-	HandleRegistry& R = registry();
-	std::lock_guard<std::mutex> lock(R.m);
-	if (R.exiting) return BHIP_OK;
-	if (!R.klts.count(k)) return BHIP_ERR_INVALID;
-	R.klts.erase(k);
-	kltReleaseDevice(k);
-	delete k;
-	return BHIP_OK;
-}
+int bhip_klt_destroy(bhip_klt* k) { return destroyChild(k); }
 
 int bhip_klt_process_dev_f32(bhip_klt* k, const float* dev_frames, long long imageStride, int stride) {
 	return kltProcessDev<KltF32>(k, dev_frames, imageStride, stride);
@@ -3178,12 +3162,11 @@ int bhip_klt_track_u8(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const 
 
 // ---- stationary background models (background.hip): FactoryBackgroundModel.stationaryBasic / stationaryGaussian / stationaryGmm ----
 extern "C++" {
-// everything a background object holds on its context's device; dropped as a whole like SurfDevice
+// everything a background object holds on its context's device (CtxChild)
 struct BgDevice {
 	DevBuf model, state, stageFrames, stageMasks;
 };
-struct bhip_bg : BgDevice {
-	bhip_ctx* ctx = nullptr;
+struct bhip_bg : CtxChild<BgDevice> {
 	BgShape sh{};
 	BgConfig cfg{};
 	bool u8 = false;
@@ -3193,18 +3176,6 @@ struct bhip_bg : BgDevice {
 	long long plane() const { return (long long)sh.width * sh.height; }
 	long long modelFloats() const { return plane() * bhip_bg_components(sh); }
 };
-
-static void bgReleaseDevice(bhip_bg* g) {
-	if (!g->ctx) return;
-	(void)hipSetDevice(g->ctx->device);
-	(void)hipStreamSynchronize(g->ctx->stream);
-	static_cast<BgDevice&>(*g) = BgDevice();
-	g->ctx = nullptr;
-}
-static void bgOrphanChildren(bhip_ctx* ctx) {
-	for (bhip_bg* g : registry().bgs)
-		if (g->ctx == ctx) bgReleaseDevice(g);
-}
 
 #define CHECK_BG(g)                     \
 	if (!(g)) return BHIP_ERR_INVALID;  \
@@ -3225,34 +3196,31 @@ static int bgSyncState(bhip_bg* g) {
 static int bgCreate(bhip_ctx* ctx, int alg, const BgConfig& cfg, const char* rejected, int maxGaussians, int family, int pixelType, int bands, int width, int height,
 					int streams, bhip_bg** out) {
 	if (out) *out = nullptr;
-	HandleRegistry& R = registry();
-	std::lock_guard<std::mutex> lock(R.m);
-	if (!ctx || !R.ctxs.count(ctx)) return BHIP_ERR_INVALID;
-	if (!out) return bhip_fail(ctx, BHIP_ERR_INVALID, "null output");
-	if (rejected) return bhip_fail(ctx, BHIP_ERR_INVALID, rejected);
-	if (width <= 0 || height <= 0 || streams <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "background model: width, height and streams must be positive");
-	if (family != BHIP_IMAGE_GRAY && family != BHIP_IMAGE_PLANAR && family != BHIP_IMAGE_INTERLEAVED) return bhip_fail(ctx, BHIP_ERR_INVALID, "Unknown image type");
-	if (family != BHIP_IMAGE_GRAY && bands < 1) return bhip_fail(ctx, BHIP_ERR_INVALID, "background model: a multi-band image has at least one band");
-	if (family == BHIP_IMAGE_INTERLEAVED) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "background models on the GPU: Gray and Planar images; for interleaved images use the Java path");
-	if (pixelType != BHIP_PIXEL_U8 && pixelType != BHIP_PIXEL_F32) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "background models on the GPU: GrayU8 and GrayF32 bands");
-	if (family == BHIP_IMAGE_PLANAR && bands > BHIP_BG_MAX_BANDS) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "background models on the GPU: at most 4 bands");
-	if (alg == BHIP_BG_GMM && maxGaussians > BHIP_BG_MAX_GAUSSIANS) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "GMM background on the GPU: at most 8 Gaussians per pixel");
-	CHECK_CTX(ctx);
-	std::unique_ptr<bhip_bg> g(new (std::nothrow) bhip_bg());
-	if (!g) return bhip_fail(ctx, BHIP_ERR_NOMEM, "out of host memory");
-	g->ctx = ctx;
-	g->sh = {alg, family == BHIP_IMAGE_GRAY ? 0 : bands, alg == BHIP_BG_GMM ? maxGaussians : 1, width, height, streams};
-	g->cfg = cfg;
-	g->u8 = pixelType == BHIP_PIXEL_U8;
-	g->stateHost.assign((size_t)streams * 2, 0);
-	const size_t bytes = (size_t)g->modelFloats() * streams * sizeof(float);
-	BHIP_TRY(g->model.reserve(ctx, bytes));
-	BHIP_TRY(g->state.reserve(ctx, g->stateHost.size() * sizeof(int)));
-	BHIP_HIP(ctx, hipMemsetAsync(g->model.p, 0, bytes, ctx->stream));
-	BHIP_TRY(bhip_ctx_synchronize(ctx));
-	R.bgs.insert(g.get());
-	*out = g.release();
-	return BHIP_OK;
+	return createChild(ctx, out, [&](std::unique_ptr<bhip_bg>& g) -> int {
+		if (!out) return bhip_fail(ctx, BHIP_ERR_INVALID, "null output");
+		if (rejected) return bhip_fail(ctx, BHIP_ERR_INVALID, rejected);
+		if (width <= 0 || height <= 0 || streams <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "background model: width, height and streams must be positive");
+		if (family != BHIP_IMAGE_GRAY && family != BHIP_IMAGE_PLANAR && family != BHIP_IMAGE_INTERLEAVED) return bhip_fail(ctx, BHIP_ERR_INVALID, "Unknown image type");
+		if (family != BHIP_IMAGE_GRAY && bands < 1) return bhip_fail(ctx, BHIP_ERR_INVALID, "background model: a multi-band image has at least one band");
+		if (family == BHIP_IMAGE_INTERLEAVED) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "background models on the GPU: Gray and Planar images; for interleaved images use the Java path");
+		if (pixelType != BHIP_PIXEL_U8 && pixelType != BHIP_PIXEL_F32) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "background models on the GPU: GrayU8 and GrayF32 bands");
+		if (family == BHIP_IMAGE_PLANAR && bands > BHIP_BG_MAX_BANDS) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "background models on the GPU: at most 4 bands");
+		if (alg == BHIP_BG_GMM && maxGaussians > BHIP_BG_MAX_GAUSSIANS) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "GMM background on the GPU: at most 8 Gaussians per pixel");
+		CHECK_CTX(ctx);
+		g.reset(new (std::nothrow) bhip_bg());
+		if (!g) return bhip_fail(ctx, BHIP_ERR_NOMEM, "out of host memory");
+		g->ctx = ctx;
+		g->sh = {alg, family == BHIP_IMAGE_GRAY ? 0 : bands, alg == BHIP_BG_GMM ? maxGaussians : 1, width, height, streams};
+		g->cfg = cfg;
+		g->u8 = pixelType == BHIP_PIXEL_U8;
+		g->stateHost.assign((size_t)streams * 2, 0);
+		const size_t bytes = (size_t)g->modelFloats() * streams * sizeof(float);
+		BHIP_TRY(g->model.reserve(ctx, bytes));
+		BHIP_TRY(g->state.reserve(ctx, g->stateHost.size() * sizeof(int)));
+		BHIP_HIP(ctx, hipMemsetAsync(g->model.p, 0, bytes, ctx->stream));
+		BHIP_TRY(bhip_ctx_synchronize(ctx));
+		return BHIP_OK;
+	});
 }
 
 template <class T>
@@ -3400,17 +3368,7 @@ int bhip_bg_create_gmm(bhip_ctx* ctx, const bhip_bg_gmm_cfg* cfg, int family, in
 	c.unknownValue = d.unknownValue;
 	return bgCreate(ctx, BHIP_BG_GMM, c, bad, d.numberOfGaussian, family, pixelType, bands, width, height, streams, out);
 }
-int bhip_bg_destroy(bhip_bg* g) {
-	if (!g) return BHIP_OK;
-	HandleRegistry& R = registry();
-	std::lock_guard<std::mutex> lock(R.m);
-	if (R.exiting) return BHIP_OK;
-	if (!R.bgs.count(g)) return BHIP_ERR_INVALID;
-	R.bgs.erase(g);
-	bgReleaseDevice(g);
-	delete g;
-	return BHIP_OK;
-}
+int bhip_bg_destroy(bhip_bg* g) { return destroyChild(g); }
 int bhip_bg_reset(bhip_bg* g, int stream) {
 	CHECK_BG(g);
 	if (stream >= g->sh.streams) return bhip_fail(ctx, BHIP_ERR_INVALID, "no such stream");

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .api import Context, IllegalArgumentException, TemplateScoreType, _check
+from .api import Context, IllegalArgumentException, TemplateScoreType, _check, _NativeObject
 
 INTENSITY_E, INTENSITY_ABS, INTENSITY_SQ = 0, 1, 2
 
@@ -382,13 +382,14 @@ class DeviceImageOps:
         return out
 
 
-class DeviceKltTracker:
+class DeviceKltTracker(_NativeObject):
     """PointTrackerKltPyramid (G:abst/feature/tracker/PointTrackerKltPyramid.java:139-348, as FactoryPointTracker.klt builds it) for B independent
     GrayF32 or GrayU8 sequences at once, on one bhip_klt: process(frames) takes a [B,H,W] float32 or uint8 CUDA tensor (the first call decides; a
     uint8 tracker has a uint8 pyramid and int16 derivatives) and queues pyramid, Sobel (EXTENDED border), tracking,
     re-description and the list update on the context's stream without a host synchronisation; spawn() detects Shi-Tomasi corners
     (radius 1, unweighted) with the strict non-max extractor (detectRadius, detectThreshold, detectBorder) and starts tracks on them
     (maxFeatures <= 0).  Sequence b's results equal those of a single-sequence tracker fed with frames[b]."""
+    _destroy = "bhip_klt_destroy"
 
     def __init__(self, scales, templateRadius, config=None, detectRadius=1, detectThreshold=0.0, ctx=None, detectBorder=None, device=0):
         from .api import KltConfig
@@ -400,21 +401,8 @@ class DeviceKltTracker:
         self.detectRadius, self.detectThreshold = int(detectRadius), float(detectThreshold)
         # FactoryDetectPoint.createGeneral + GeneralFeatureDetector: ignoreBorder + radius, at least the Shi-Tomasi window radius (1)
         self.detectBorder = max(self.detectRadius, 1) if detectBorder is None else int(detectBorder)
-        self._h = None
         self._shape = None
         self._dtype = None
-        self.ctx._children.add(self)
-
-    def close(self):
-        if self._h:
-            self.L.bhip_klt_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _need(self):
         if not self._h:
@@ -434,7 +422,8 @@ class DeviceKltTracker:
             create = self.L.bhip_klt_create_u8 if u8 else self.L.bhip_klt_create
             _check(self.ctx, create(self.ctx._h, C.byref(cfg), self.templateRadius, sc, len(self.scales), self.detectRadius, self.detectThreshold,
                                     self.detectBorder, W, H, B, C.byref(h)))
-            self._h, self._shape, self._dtype = h, (W, H, B), dtype
+            self._adopt(h)
+            self._shape, self._dtype = (W, H, B), dtype
         _check(self.ctx, (self.L.bhip_klt_process_dev_u8 if u8 else self.L.bhip_klt_process_dev_f32)(self._h, ptr, imageStride, stride))
 
     def spawn(self):
@@ -528,7 +517,7 @@ class DeviceKltTracker:
         return out
 
 
-class DeviceBackgroundModel:
+class DeviceBackgroundModel(_NativeObject):
     """FactoryBackgroundModel.stationaryBasic / stationaryGaussian / stationaryGmm for S independent camera streams at once, on one bhip_bg
     (F:factory/background/FactoryBackgroundModel.java:47-64,112-141,193-225; stream s is one Java object).
 
@@ -541,6 +530,7 @@ class DeviceBackgroundModel:
     segment()   segment(frame, mask) with frames [S,(B,)H,W] -> uint8 [S,H,W]
     Frames and masks may be strided views (unit stride along x).  The handle is created at the first call, for its stream count and frame size."""
     ALGORITHMS = ("basic", "gaussian", "gmm")
+    _destroy = "bhip_bg_destroy"
 
     def __init__(self, algorithm, config=None, dtype=torch.uint8, bands=0, ctx=None, device=0):
         from . import api
@@ -558,21 +548,8 @@ class DeviceBackgroundModel:
         self.L = _lib.load()
         self.device = torch.device("cuda", self.ctx.device)
         self.algorithm, self.config, self.dtype, self.bands = algorithm, config, dtype, int(bands)
-        self._h = None
         self._shape = None          # (S, H, W)
         self._unknown = None if algorithm == "basic" else config.unknownValue
-        self.ctx._children.add(self)
-
-    def close(self):
-        if self._h:
-            self.L.bhip_bg_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _create(self, S, H, W):
         if self._h:
@@ -593,7 +570,8 @@ class DeviceBackgroundModel:
             cfg = _lib.BgGmmCfg(c.learningPeriod, c.initialVariance, c.decayCoefient, c.maxDistance, c.numberOfGaussian, c.significantWeight, c.unknownValue)
             st = self.L.bhip_bg_create_gmm(self.ctx._h, C.byref(cfg), family, pixel, self.bands, W, H, S, C.byref(h))
         _check(self.ctx, st)
-        self._h, self._shape = h, (S, H, W)
+        self._adopt(h)
+        self._shape = (S, H, W)
         if self.algorithm == "basic" and self._unknown is not None:
             _check(self.ctx, self.L.bhip_bg_set_unknown_value(self._h, self._unknown))
 
