@@ -22,17 +22,24 @@ def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*.hip"))) + sorted(glob.glob(os.path.join(CSRC, "*.cpp")))
 
 
+def common_deps():
+    """What every object depends on besides its own source."""
+    return glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "..", "include", "boofhip.h"), os.path.abspath(__file__)]
+
+
 def needs_build(lib=LIB):
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)
-    deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "..", "include", "boofhip.h")]
-    return any(os.path.getmtime(d) > t for d in deps)
+    return any(os.path.getmtime(d) > t for d in sources() + common_deps())
 
 
 def build(force=False, verbose=False, experiments=False):
     """experiments=True builds libboofhip_exp.so with the timing-experiment switches compiled in (select it with BHIP_LIB=...);
-    the default product library contains none of them (tests/test_cabi_symbols.py)."""
+    the default product library contains none of them (tests/test_cabi_symbols.py).
+    Only the objects older than their source or than common_deps() are compiled again, then everything is linked; force=True (and
+    with it every BHIP_EXP_DEFS variant) compiles all of them.  The skip trusts modification times alone: an object left half-written by
+    a killed compiler, or compiled under another HIPCC or environment into the same directory, is linked as it is -- use force=True then."""
     lib = LIB_EXPERIMENTS if experiments else LIB
     extra = []
     if experiments and os.environ.get("BHIP_EXP_DEFS"):
@@ -47,9 +54,12 @@ def build(force=False, verbose=False, experiments=False):
     objdir = os.path.join(HERE, ("build_exp_" + os.environ.get("BHIP_EXP_TAG", "variant")) if extra else "build_exp" if experiments else "build")
     os.makedirs(objdir, exist_ok=True)
     procs = []
+    newest = max(os.path.getmtime(d) for d in common_deps())
     for src in sources():
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         objs.append(obj)
+        if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(newest, os.path.getmtime(src)):
+            continue
         cmd = [hipcc, "--offload-arch=" + ARCH] + FLAGS + (["-DBHIP_EXPERIMENTS"] if experiments else []) + extra + ["-c", src, "-o", obj]
         if src.endswith(".cpp"):
             cmd.insert(1, "-x")

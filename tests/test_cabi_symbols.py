@@ -1,6 +1,8 @@
 """CPU-side checks of the drop-in boundary: libboofhip.so loads without a GPU and exports exactly what include/boofhip.h declares."""
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
@@ -23,6 +25,17 @@ def test_library_builds_loads_and_exports_every_declared_symbol():
         assert hasattr(L, name), "libboofhip.so does not export " + name
     assert sorted(_lib.SIGNATURES) == declared, "ctypes table and header disagree"
     assert b"gfx950" in L.bhip_version()
+
+
+def test_library_exports_no_bhip_symbol_that_the_header_does_not_declare():
+    """The converse: the defined dynamic symbols with an unmangled bhip_ name are the header's set, no more.  A host helper shared between
+    the cabi*.hip files is C++-mangled; one that slipped into an extern "C" block would show up here."""
+    from boofcv_amd import build
+    lib = build.build()
+    nm = next(p for p in ("/opt/rocm/llvm/bin/llvm-nm", shutil.which("llvm-nm"), shutil.which("nm")) if p and os.path.exists(p))   # same options
+    out = subprocess.check_output([nm, "-D", "--defined-only", lib]).decode()
+    exported = sorted(f[-1] for f in (line.split() for line in out.splitlines()) if f and f[-1].startswith("bhip_"))
+    assert exported == _declared()
 
 
 def test_no_cpu_fallback_without_gpu():
