@@ -56,7 +56,7 @@ struct FusedParams {
 	int expW, expH;
 	long long expImageStride;
 	long long expSlotOff[2];
-	int ablate;   // timing experiments only (BHIP_FUSED_ABLATE): 1 skip the intensity phase, 2 skip the NMS phase, 4 skip staging
+	int ablate;   // timing experiments only (BHIP_FUSED_ABLATE): 1 skip the intensity phase, 2 skip the NMS phase, 4 skip staging, 32 frame tiles stop after staging
 };
 
 __device__ __forceinline__ float fblock_zero(const float* __restrict__ d, int stride, int W, int H, int x0, int y0, int x1, int y1) {
@@ -270,7 +270,7 @@ struct FixedGeo {
 	static constexpr int K0 = rFmax + 1;                          // column of (xx) inside the patch, minus SKIP*(x - x0 + R)
 	// LDS offset of the tap at (row offset ro, column offset co) relative to the pixel's base pointer (row yy-Y0, column slot x-x0+R)
 	static constexpr int tap(int ro, int co) { return ((K0 + co) % SKIP) * plane + ro * IWp + (K0 + co) / SKIP; }
-	// run-time form for the border formula: absolute patch coordinates (r, c) -> LDS index
+	// run-time form for the guarded staging: absolute patch coordinates (r, c) -> LDS index
 	static __device__ __forceinline__ int at(int r, int c) { return (c % SKIP) * plane + r * IWp + c / SKIP; }
 	static constexpr int size(int L) { return SIZE0 + L * STEPSZ; }
 	static constexpr int bS(int L) { return size(L) / 3; }
@@ -280,24 +280,11 @@ struct FixedGeo {
 	static constexpr int border(int L) { return (rF(L) + 1 + (SKIP - (rF(L) + 1) % SKIP)) / SKIP; }
 };
 
-// block_zero on the phase-plane patch (see lblock_zero)
 // T = float (GrayF32 integral image) or int (GrayS32: the box sums are exact integers and become floats exactly where the reference's S32
 // code assigns them to a float, ImplIntegralImageFeatureIntensity.java:245-390)
 template <class T> struct TapVec2;
 template <> struct TapVec2<float> { typedef float2 type; };
 template <> struct TapVec2<int> { typedef int2 type; };
-
-template <class G, class T>
-__device__ __forceinline__ T pblock_zero(const T* iiT, int X0, int Y0, int W, int H, int x0, int y0, int x1, int y1) {
-	x0 = min(x0, W - 1); y0 = min(y0, H - 1); x1 = min(x1, W - 1); y1 = min(y1, H - 1);
-	const int cx0 = max(x0, 0) - X0, cy0 = max(y0, 0) - Y0, cx1 = max(x1, 0) - X0, cy1 = max(y1, 0) - Y0;
-	const T vbr = iiT[G::at(cy1, cx1)], vtr = iiT[G::at(cy0, cx1)], vbl = iiT[G::at(cy1, cx0)], vtl = iiT[G::at(cy0, cx0)];
-	const T br = (x1 >= 0 && y1 >= 0) ? vbr : T(0);
-	const T tr = (y0 >= 0 && x1 >= 0) ? vtr : T(0);
-	const T bl = (x0 >= 0 && y1 >= 0) ? vbl : T(0);
-	const T tl = (x0 >= 0 && y0 >= 0) ? vtl : T(0);
-	return br - tr - bl + tl;
-}
 
 // the 32 taps of one inner pixel, reference order (hessianInner :183-201); c = patch row of yy, column slot of x
 template <class G, int L, class T>
@@ -366,31 +353,59 @@ __device__ __forceinline__ f32x2 fusedInnerDet2(const float* c) {
 	return Dxx * Dyy - 0.81f * Dxy * Dxy;
 }
 
-// Intensity of level L at intensity-space pixel (x, y), any position class: -inf outside the image (never >= anything, as if the
-// neighbourhood were clamped), the unrolled inner form (hessianInner) for inner pixels, the clamped border form (hessianBorder) otherwise
-template <class G, int SKIP, int L, class T>
-__device__ __forceinline__ float fusedPixel(int W, int H, int pw, int ph, const T* iiT, int x, int y, int x0, int y0, int X0, int Y0) {
-	constexpr int size = G::size(L), bS = G::bS(L), bLg = G::bL(L), border = G::border(L), R = G::HALO;
+// The clamped border form (hessianBorder :72-118, IntegralImageOps.block_zero) of level L at tile pixel (px, py) = (x - x0 + R, y - y0 + R),
+// on the phase-plane patch: every clamped corner of a pixel of this tile lies inside the patch (clamping only moves a corner towards the
+// pixel), so no global memory is read.  The eight boxes have 32 corners but only ten distinct columns and ten distinct rows (the offsets
+// below), so each coordinate is clamped once and turned once into its LDS byte offset (column: phase plane + slot, row: row * pitch); a tap
+// is then one add and one ds_read.  block_zero's rule "a corner with a negative coordinate counts as zero" is folded into the clamp: such
+// a coordinate is clamped to -1 instead of 0, and row -1 / column -1 of the patch hold T(0) -- a patch that reaches outside the image is
+// staged by the guarded loads, which write T(0) there, and a negative corner of a pixel of this tile is never left of / above the patch
+// (X0 <= c < 0).  CX / CY = false: the caller knows that no column / no row of this pixel is clamped (x / y at least `border` away from
+// both image edges, as for an inner pixel), so those offsets are the inner form's compile-time ones and fold into the ds_read.  Every box
+// keeps block_zero's order br - tr - bl + tl, and the derivatives keep the reference's `ret += block * T(+-k)` accumulation in T.
+template <class G, int SKIP, int L, class T, bool CX = true, bool CY = true>
+__device__ __forceinline__ float fusedBorderDet(int W, int H, const T* iiT, int px, int py, int X0, int Y0) {
+	constexpr int size = G::size(L), bS = G::bS(L), bLg = G::bL(L);
 	constexpr float norm = 1.0f / (float)(size * size);
 	constexpr int r1 = bS / 2, r2 = bS + r1, r3 = bLg / 2, b = bS;
-	if (x < 0 || x >= pw || y < 0 || y >= ph) return -INFINITY;
-	const int xx = x * SKIP, yy = y * SKIP;
-	const bool inner = x >= border && x < pw - border && y >= border && y < ph - border;
-	if (inner) return fusedInnerDet<G, L, T>(iiT + (yy - Y0) * G::IWp + (x - x0 + R));
+	enum { M2, P2, M1, P1, M3, P3, MB, N1, Z0, PB, NOFF };
+	constexpr int off[NOFF] = {-r2 - 1, r2, -r1 - 1, r1, -r3 - 1, r3, -b - 1, -1, 0, b};
+	const char* col[NOFF];   // patch base + byte offset of the column
+	int row[NOFF];           // byte offset of the row
+	// in patch coordinates: pixel, last image column / row, and column / row -1 of the image
+	const int xb = px * SKIP + G::K0, yb = py * SKIP + G::K0, xHi = W - 1 - X0, yHi = H - 1 - Y0, xLo = -1 - X0, yLo = -1 - Y0;
+	const char* base = (const char*)(iiT + (CY ? 0 : py * SKIP * G::IWp) + (CX ? 0 : px));
+#pragma unroll
+	for (int k = 0; k < NOFF; k++) {
+		if constexpr (CX) {
+			const unsigned int lx = (unsigned)max(min(xb + off[k], xHi), xLo);
+			col[k] = base + 4 * ((lx % SKIP) * G::plane + lx / SKIP);
+		} else {
+			col[k] = base + 4 * (((G::K0 + off[k]) % SKIP) * G::plane + (G::K0 + off[k]) / SKIP);
+		}
+		if constexpr (CY) row[k] = __mul24(max(min(yb + off[k], yHi), yLo), 4 * G::IWp);
+		else row[k] = 4 * (G::K0 + off[k]) * G::IWp;
+	}
+	// block_zero(x0, y0, x1, y1)
+	auto box = [&](int x0, int y0, int x1, int y1) -> T {
+		const T br = *(const T*)(col[x1] + row[y1]), tr = *(const T*)(col[x1] + row[y0]);
+		const T bl = *(const T*)(col[x0] + row[y1]), tl = *(const T*)(col[x0] + row[y0]);
+		return br - tr - bl + tl;
+	};
 	float Dxx, Dyy, Dxy;
 	T ret = 0;
-	ret += pblock_zero<G, T>(iiT, X0, Y0, W, H, xx - r2 - 1, yy - r3 - 1, xx + r2, yy + r3) * T(1);
-	ret += pblock_zero<G, T>(iiT, X0, Y0, W, H, xx - r1 - 1, yy - r3 - 1, xx + r1, yy + r3) * T(-3);
+	ret += box(M2, M3, P2, P3) * T(1);
+	ret += box(M1, M3, P1, P3) * T(-3);
 	Dxx = (float)ret;
 	ret = 0;
-	ret += pblock_zero<G, T>(iiT, X0, Y0, W, H, xx - r3 - 1, yy - r2 - 1, xx + r3, yy + r2) * T(1);
-	ret += pblock_zero<G, T>(iiT, X0, Y0, W, H, xx - r3 - 1, yy - r1 - 1, xx + r3, yy + r1) * T(-3);
+	ret += box(M3, M2, P3, P2) * T(1);
+	ret += box(M3, M1, P3, P1) * T(-3);
 	Dyy = (float)ret;
 	ret = 0;
-	ret += pblock_zero<G, T>(iiT, X0, Y0, W, H, xx - b - 1, yy - b - 1, xx - 1, yy - 1) * T(1);
-	ret += pblock_zero<G, T>(iiT, X0, Y0, W, H, xx, yy - b - 1, xx + b, yy - 1) * T(-1);
-	ret += pblock_zero<G, T>(iiT, X0, Y0, W, H, xx, yy, xx + b, yy + b) * T(1);
-	ret += pblock_zero<G, T>(iiT, X0, Y0, W, H, xx - b - 1, yy, xx - 1, yy + b) * T(-1);
+	ret += box(MB, MB, N1, N1) * T(1);
+	ret += box(Z0, MB, PB, N1) * T(-1);
+	ret += box(Z0, Z0, PB, PB) * T(1);
+	ret += box(MB, Z0, N1, PB) * T(-1);
 	Dxy = (float)ret;
 	Dxx *= norm;
 	Dxy *= norm;
@@ -398,12 +413,37 @@ __device__ __forceinline__ float fusedPixel(int W, int H, int pw, int ph, const 
 	return Dxx * Dyy - 0.81f * Dxy * Dxy;
 }
 
-// Out-of-line form for the rare callers (frame tiles, NMS survivors, exported outer levels): one copy of the 32-tap body + the border
-// formula per level instead of one per call site keeps the kernel's register count at what the dense loop needs.
+// Intensity of level L at intensity-space pixel (x, y), any position class: -inf outside the image (never >= anything, as if the
+// neighbourhood were clamped), the unrolled inner form (hessianInner) for inner pixels, the clamped border form (hessianBorder) otherwise
+template <class G, int SKIP, int L, class T>
+__device__ __forceinline__ float fusedPixel(int W, int H, int pw, int ph, const T* iiT, int x, int y, int x0, int y0, int X0, int Y0) {
+	constexpr int border = G::border(L), R = G::HALO;
+	if (x < 0 || x >= pw || y < 0 || y >= ph) return -INFINITY;
+	const bool inner = x >= border && x < pw - border && y >= border && y < ph - border;
+	if (inner) return fusedInnerDet<G, L, T>(iiT + (y * SKIP - Y0) * G::IWp + (x - x0 + R));
+	return fusedBorderDet<G, SKIP, L, T>(W, H, iiT, x - x0 + R, y - y0 + R, X0, Y0);
+}
+
+// Out-of-line forms for the rare callers (NMS survivors and exported outer levels: any class; the strips of a frame tile: never inner): one
+// copy of the 32-tap body and / or the border formula per level instead of one per call site keeps the kernel's register count at what the
+// dense loop needs.
 template <class G, int SKIP, int L, class T>
 __device__ __noinline__ float fusedPixelCall(int W, int H, int pw, int ph, const T* iiT, int x, int y, int x0, int y0, int X0, int Y0) {
 	return fusedPixel<G, SKIP, L, T>(W, H, pw, ph, iiT, x, y, x0, y0, X0, Y0);
 }
+template <class G, int SKIP, int L, class T, bool CX, bool CY>
+__device__ __noinline__ float fusedOuterCall(int W, int H, int pw, int ph, const T* iiT, int px, int py, int xs, int ys, int X0, int Y0) {
+	const int x = xs + px, y = ys + py;
+	if (x < 0 || x >= pw || y < 0 || y >= ph) return -INFINITY;
+	return fusedBorderDet<G, SKIP, L, T, CX, CY>(W, H, iiT, px, py, X0, Y0);
+}
+
+// n / d for 0 <= n < 2048 and 1 <= d <= 32 by one multiplication (mul = ceil(2^16 / d) overshoots by less than 32 / 2^16 per unit of n)
+struct SmallDiv {
+	unsigned int mul;
+	__device__ __forceinline__ explicit SmallDiv(int d) : mul((65536u + (unsigned)d - 1u) / (unsigned)d) {}
+	__device__ __forceinline__ int operator()(int n) const { return (int)(((unsigned)n * mul) >> 16); }
+};
 
 // Dense intensity tile (core + halo) of level L into `out` ([ITH][ITp])
 template <class G, int SKIP, int R, int L, class T>
@@ -430,10 +470,70 @@ __device__ __forceinline__ void fusedLevelDense(const FusedParams& P, const T* i
 			}
 		}
 	} else {
+		// Frame tile.  The inner pixels of this level inside tile + halo form one rectangle [ix0, ix1) x [iy0, iy1) (tile coordinates; empty,
+		// or all of the tile for a level with a smaller border than the one that made this a frame tile): it runs through the inline
+		// inner forms above with compact indices and no per-pixel test.  What is left -- border pixels and pixels outside the image -- is the
+		// rows above and below the rectangle plus the columns left and right of it, enumerated compactly further down, so that no wave
+		// holds inner and other pixels at once.
+		static_assert(G::ITH * G::ITW <= 2048 && G::ITW <= 32, "SmallDiv range");
+		const int xs = x0 - R, ys = y0 - R;
+		int ix0 = min(max(border - xs, 0), G::ITW), ix1 = min(max(P.w - border - xs, 0), G::ITW);
+		int iy0 = min(max(border - ys, 0), G::ITH), iy1 = min(max(P.h - border - ys, 0), G::ITH);
+		if (ix1 <= ix0 || iy1 <= iy0) { ix0 = ix1 = 0; iy0 = iy1 = G::ITH; }   // no inner pixel: every row is a row above the rectangle
+		const int wI = ix1 - ix0, hI = iy1 - iy0;
+		const int rowBase = ys * SKIP - Y0;   // == rFmax + 1
+		const SmallDiv divI(max(wI, 1));
+		if constexpr (SKIP == 1 && T(0.5f) != T(0)) {
+			// pairs on even columns as in an interior tile; a rectangle that starts or ends on an odd column has that column done one by one
+			const int ex0 = (ix0 + 1) & ~1, ex1 = ix1 & ~1;
+			const int nP = (ex1 - ex0) >> 1;
+			const SmallDiv divP(max(nP, 1));
+			for (int it = tid; it < hI * nP; it += G::NT) {
+				const int r = divP(it);
+				const int px = ex0 + 2 * (it - r * nP), py = iy0 + r;
+				const f32x2 det = fusedInnerDet2<G, L>((const float*)iiT + (rowBase + py * SKIP) * pitch + px);
+				out[py * G::ITp + px] = det.x;
+				out[py * G::ITp + px + 1] = det.y;
+			}
+			const int oddL = ix0 & 1, nOdd = oddL + (ix1 & 1);
 #pragma unroll 1
-		for (int it = tid; it < G::ITH * G::ITW; it += G::NT) {
-			const int px = it & (G::ITW - 1), py = it / G::ITW;
-			out[py * G::ITp + px] = fusedPixelCall<G, SKIP, L, T>(P.ii.width, P.ii.height, P.w, P.h, iiT, x0 - R + px, y0 - R + py, x0, y0, X0, Y0);
+			for (int it = tid; it < hI * nOdd; it += G::NT) {
+				const bool right = it >= hI || !oddL;
+				const int px = right ? ix1 - 1 : ix0, py = iy0 + (it >= hI ? it - hI : it);
+				out[py * G::ITp + px] = fusedInnerDet<G, L, T>(iiT + (rowBase + py * SKIP) * pitch + px);
+			}
+		} else {
+#pragma unroll 1
+			for (int it = tid; it < hI * wI; it += G::NT) {
+				const int r = divI(it);
+				const int px = ix0 + (it - r * wI), py = iy0 + r;
+				out[py * G::ITp + px] = fusedInnerDet<G, L, T>(iiT + (rowBase + py * SKIP) * pitch + px);
+			}
+		}
+		// the rest, one linear index: the columns left and right of the rectangle on its hI rows (no row of such a pixel is clamped), the
+		// rectangle's wI columns on the rows above and below it (no column is clamped), and the four corners
+		const int wS = G::ITW - wI, hS = G::ITH - hI;
+		const int nSide = hI * wS, nMid = hS * wI;
+		const SmallDiv divS(max(wS, 1));
+#pragma unroll 1
+		for (int it = tid; it < nSide + nMid + hS * wS; it += G::NT) {
+			float v;
+			if (it < nSide) {
+				const int r = divS(it), c = it - r * wS;
+				const int px = c < ix0 ? c : c + wI, py = iy0 + r;
+				v = fusedOuterCall<G, SKIP, L, T, true, false>(P.ii.width, P.ii.height, P.w, P.h, iiT, px, py, xs, ys, X0, Y0);
+				out[py * G::ITp + px] = v;
+			} else if (it < nSide + nMid) {
+				const int k = it - nSide, r = divI(k);
+				const int px = ix0 + (k - r * wI), py = r < iy0 ? r : r + hI;
+				v = fusedOuterCall<G, SKIP, L, T, false, true>(P.ii.width, P.ii.height, P.w, P.h, iiT, px, py, xs, ys, X0, Y0);
+				out[py * G::ITp + px] = v;
+			} else {
+				const int k = it - nSide - nMid, r = divS(k), c = k - r * wS;
+				const int px = c < ix0 ? c : c + wI, py = r < iy0 ? r : r + hI;
+				v = fusedOuterCall<G, SKIP, L, T, true, true>(P.ii.width, P.ii.height, P.w, P.h, iiT, px, py, xs, ys, X0, Y0);
+				out[py * G::ITp + px] = v;
+			}
 		}
 	}
 }
@@ -659,6 +759,10 @@ __global__ __launch_bounds__(NTT) void k_detect_fused_fixed(FusedParams P) {
 		}
 	}
 	__syncthreads();
+#ifdef BHIP_EXPERIMENTS
+	// what the frame tiles (tiles whose halo touches the border ring of a dense level; level 2 has the wider ring) cost after staging
+	if (BHIP_ABLATE(P, 32) && !(x0 - R >= G::border(2) && x0 + G::TX + R <= P.w - G::border(2) && y0 - R >= G::border(2) && y0 + G::TY + R <= P.h - G::border(2))) return;
+#endif
 	// ---- intensity.  The 3x3x3 scale-space test only ever looks at the outer levels (0 and 3) in the 3x3 neighbourhood of a pixel that is
 	// already a strict (2R+1)^2 maximum of a mid level (1 or 2), so only the two mid levels are built densely over the tile; the outer
 	// levels are evaluated on demand at the few NMS survivors (nine values each).  Same functions of (pixel, kernel size), same decisions.
