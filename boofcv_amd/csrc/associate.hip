@@ -197,6 +197,8 @@ static int launchScan(bhip_ctx* ctx, const typename Scorer::elem* U, int nU, con
 	per = ((per + VT - 1) / VT) * VT;
 	dim3 grid((nU + 255) / 256, splits);
 	const size_t lds = (size_t)VT * len * sizeof(typename Scorer::elem);
+	// SURF descriptors of more than 128 values (6x6 and 8x8 grids: 144, 256) need more than the default 64 KB of dynamic LDS for the tile
+	if (lds > 65536) BHIP_HIP(ctx, hipFuncSetAttribute((const void*)k_assoc_scan<Scorer, COLMODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 	{
 		// one multiply-add pair per descriptor element per (u,v) pair: the N x M x len contraction of SURVEY 8d
 		ProfScope ps(ctx, COLMODE ? "k_assoc_scan_cols" : "k_assoc_scan_rows", 0, 2.0 * nU * (double)nV * len);
@@ -209,7 +211,7 @@ static int launchScan(bhip_ctx* ctx, const typename Scorer::elem* U, int nU, con
 template <bool COLMODE>
 static int scanL2(bhip_ctx* ctx, const double* U, int nU, const double* V, int nV, int dof, int vBase, double maxErr, int sqrtScore, void* partial,
 				  int splits) {
-	if ((size_t)VT * dof * 8 > 64 * 1024) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "descriptor too long for the LDS tile");
+	if ((size_t)VT * dof * 8 > 160 * 1024) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "descriptor too long for the LDS tile");   // dof <= 320
 	if (dof == 64) return launchScan<L2Scorer<64>, COLMODE>(ctx, U, nU, V, nV, dof, vBase, maxErr, sqrtScore, partial, splits);
 	return launchScan<L2ScorerDyn, COLMODE>(ctx, U, nU, V, nV, dof, vBase, maxErr, sqrtScore, partial, splits);
 }

@@ -1068,6 +1068,8 @@ struct DescribePointSurf {
 	// :235-295 features
 	virtual void features(double c_x, double c_y, double c, double s, double scale, bool safe, double* features) {
 		int regionSize = widthLargeGrid * widthSubRegion;
+		// :241-243 -- the constructor's kernel is 2*(regionSize/2) wide, so an odd regionSize always throws here
+		if (weight.width != regionSize) throw std::invalid_argument("Weighting kernel has an unexpected size");
 		int regionR = regionSize / 2;
 		int regionEnd = regionSize - regionR;
 		int regionIndex = 0;

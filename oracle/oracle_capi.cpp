@@ -160,23 +160,27 @@ int orc_sparse_gradient(const orc_image* ii, double width, int x, int y, float* 
 	return 1;
 }
 
-// ---- descriptor ---- stable: 1 = DescribePointSurfMod, 0 = DescribePointSurf
-void orc_describe(const orc_image* ii, int stable, const orc_surf_cfg* cfg, double x, double y, double angle, double scale, double* desc, uint8_t* white,
+// ---- descriptor ---- stable: 1 = DescribePointSurfMod, 0 = DescribePointSurf.  Returns -1 where the reference throws
+// (DescribePointSurf.features on a grid whose widthLargeGrid * widthSubRegion is odd), 0 otherwise.
+int orc_describe(const orc_image* ii, int stable, const orc_surf_cfg* cfg, double x, double y, double angle, double scale, double* desc, uint8_t* white,
 				  int normalize) {
 	GrayF32 v = view(ii);
 	BrightFeature bf;
 	ConfigSurfDescribe c = toSd(cfg);
-	if (stable) {
-		DescribePointSurfMod d(c); d.setImage(v);
-		if (normalize) d.describe(x, y, angle, scale, bf);
-		else { bf.value.resize(d.featureDOF); d.describeTuple(x, y, angle, scale, bf.value.data()); }
-	} else {
-		DescribePointSurf d(c); d.setImage(v);
-		if (normalize) d.describe(x, y, angle, scale, bf);
-		else { bf.value.resize(d.featureDOF); d.describeTuple(x, y, angle, scale, bf.value.data()); }
-	}
+	try {
+		if (stable) {
+			DescribePointSurfMod d(c); d.setImage(v);
+			if (normalize) d.describe(x, y, angle, scale, bf);
+			else { bf.value.resize(d.featureDOF); d.describeTuple(x, y, angle, scale, bf.value.data()); }
+		} else {
+			DescribePointSurf d(c); d.setImage(v);
+			if (normalize) d.describe(x, y, angle, scale, bf);
+			else { bf.value.resize(d.featureDOF); d.describeTuple(x, y, angle, scale, bf.value.data()); }
+		}
+	} catch (const std::invalid_argument&) { return -1; }
 	std::memcpy(desc, bf.value.data(), sizeof(double) * bf.value.size());
 	*white = bf.white ? 1 : 0;
+	return 0;
 }
 
 
@@ -224,7 +228,10 @@ struct orc_surf {
 	DetectDescribeSurf* dd;
 	SurfResult res;
 };
+// Returns NULL for a configuration on which the reference throws at the first described point: surfFast with an odd
+// widthLargeGrid * widthSubRegion (DescribePointSurf.java:241-243, "Weighting kernel has an unexpected size").
 void* orc_surf_create(int stable, const orc_fh_cfg* fh, const orc_surf_cfg* sd, const orc_ori_cfg* ori) {
+	if (!stable && ((sd->widthLargeGrid * sd->widthSubRegion) & 1)) return nullptr;
 	orc_surf* s = new orc_surf();
 	s->dd = new DetectDescribeSurf(stable != 0, toFh(fh), toSd(sd), stable ? toSliding(ori) : ConfigSlidingIntegral(),
 								   stable ? ConfigAverageIntegral() : toAverage(ori));

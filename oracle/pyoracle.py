@@ -92,7 +92,7 @@ def lib():
             "orc_select_nbest": (C.c_int, [IM, P(C.c_int16), C.c_int, C.c_int, C.c_int, P(C.c_int16)]),
             "orc_orientation": (C.c_double, [IM, C.c_int, P(OriCfg), C.c_double, C.c_double, C.c_double]),
             "orc_sparse_gradient": (C.c_int, [IM, C.c_double, C.c_int, C.c_int, P(C.c_float), P(C.c_float)]),
-            "orc_describe": (None, [IM, C.c_int, P(SurfCfg), C.c_double, C.c_double, C.c_double, C.c_double, P(C.c_double), P(C.c_uint8), C.c_int]),
+            "orc_describe": (C.c_int, [IM, C.c_int, P(SurfCfg), C.c_double, C.c_double, C.c_double, C.c_double, P(C.c_double), P(C.c_uint8), C.c_int]),
             "orc_surf_is_inside": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]),
             "orc_surf_is_inside_region": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double]),
             "orc_normalize_l2": (None, [P(C.c_double), C.c_int]),
@@ -277,7 +277,8 @@ def describe(ii, x, y, angle, scale, stable=True, cfg=None, normalize=True):
     cfg = cfg or SurfCfg()
     desc = np.zeros(cfg.widthLargeGrid * cfg.widthLargeGrid * 4, dtype=np.float64)
     white = C.c_uint8(0)
-    lib().orc_describe(ii.c(), 1 if stable else 0, C.byref(cfg), x, y, angle, scale, _fp(desc, C.c_double), C.byref(white), 1 if normalize else 0)
+    if lib().orc_describe(ii.c(), 1 if stable else 0, C.byref(cfg), x, y, angle, scale, _fp(desc, C.c_double), C.byref(white), 1 if normalize else 0) != 0:
+        raise ValueError("Weighting kernel has an unexpected size")   # DescribePointSurf.java:241-243: widthLargeGrid * widthSubRegion is odd
     return desc, bool(white.value)
 
 
@@ -291,11 +292,14 @@ class Surf:
         self.ori = ori or (OriCfg.sliding() if stable else OriCfg.average())
         self.dof = self.sd.widthLargeGrid * self.sd.widthLargeGrid * 4
         self._h = lib().orc_surf_create(1 if stable else 0, C.byref(self.fh), C.byref(self.sd), C.byref(self.ori))
+        if not self._h:
+            raise ValueError("Weighting kernel has an unexpected size")   # surfFast on an odd widthLargeGrid * widthSubRegion, see orc_surf_create
         self.n = 0
 
     def __del__(self):
         try:
-            lib().orc_surf_destroy(self._h)
+            if getattr(self, "_h", None):
+                lib().orc_surf_destroy(self._h)
         except Exception:
             pass
 
