@@ -200,6 +200,40 @@ struct FhDetector {
 
 	// level l of the intensity planes of stand-alone octave o
 	DevImg<float> level(const FhOctavePlan& o, int l) const { return {inten.as<float>() + o.intenOff + (size_t)l * o.w * o.h, o.intenImageStride, o.w, o.w, o.h, batch}; }
+	// the stand-alone octaves plan[k0 .. k1): intensity levels, then NMS + scale-space test of their middle levels
+	template <class T>
+	int runStandAlone(bhip_ctx* ctx, DevImg<const T> ii, size_t k0, size_t k1) {
+		std::vector<HessLevelSource> from((k1 - k0) * BHIP_MAX_LEVELS);
+		std::vector<HessOctave> octs;
+		std::vector<NmsLevelArgs> nms;
+		for (size_t k = k0; k < k1; k++) {
+			const FhOctavePlan& o = plan[k];
+			HessLevelSource* f = &from[(k - k0) * BHIP_MAX_LEVELS];
+			for (int i = 0; i < o.nlevels; i++) {
+				f[i] = HessLevelSource{nullptr, 0, 0, 1, 0};
+				const int j = o.shareFrom[i];
+				if (j < 0 || k == 0) continue;
+				const FhOctavePlan& p = plan[k - 1];
+				if (p.fused) f[i] = HessLevelSource{level(o, i).data, o.intenImageStride, o.w, 1, 1};   // written in place by the fused octave
+				else f[i] = HessLevelSource{level(p, j).data, p.intenImageStride, p.w, 2, 0};
+			}
+			unsigned int skipMask = 0;
+			for (int i = 0; i < o.nlevels; i++)
+				if (o.onDemand[i]) skipMask |= 1u << i;
+			octs.push_back(HessOctave{o.skip, o.nlevels, o.sizes, level(o, 0), (long long)o.w * o.h, f, skipMask});
+			auto held = [&](int l) { DevImg<const float> v = level(o, l); if (o.onDemand[l]) v.data = nullptr; return v; };   // nullptr: not in memory
+			for (auto& m : o.mids) nms.push_back(NmsLevelArgs{held(m.level - 1), level(o, m.level), held(m.level + 1), m.p});
+		}
+		BHIP_TRY(bhip_launch_hessian_octaves(ctx, ii, (int)octs.size(), octs.data()));
+		if (nBest()) {
+			for (auto& a : nms)
+				BHIP_TRY(bhip_launch_nms_scalespace(ctx, a.lower, a.mid, a.upper, a.p, cfg.extractRadius, cfg.detectThreshold, bitmap.as<unsigned int>(), bitmapWords,
+													cand.as<KeyPoint>(), count.as<int>(), cap, true, ii));
+			return BHIP_OK;
+		}
+		return bhip_launch_nms_scalespace_levels(ctx, (int)nms.size(), nms.data(), cfg.extractRadius, cfg.detectThreshold, bitmap.as<unsigned int>(), bitmapWords,
+												 cand.as<KeyPoint>(), count.as<int>(), cap, ii);
+	}
 	// ii: the dense integral images prepare<T>() planned for.  Leaves the ordered key points in `sorted` ([image][cap]) and their counts in `counts`.
 	template <class T>
 	int run(bhip_ctx* ctx, DevImg<const T> ii) {
@@ -231,23 +265,12 @@ struct FhDetector {
 													  ex.n > 0 ? &ex : nullptr));
 					continue;
 				}
-				HessLevelSource from[BHIP_MAX_LEVELS];
-				for (int i = 0; i < o.nlevels; i++) {
-					from[i] = HessLevelSource{nullptr, 0, 0, 1, 0};
-					const int j = o.shareFrom[i];
-					if (j < 0 || k == 0) continue;
-					const FhOctavePlan& p = plan[k - 1];
-					if (p.fused) from[i] = HessLevelSource{level(o, i).data, o.intenImageStride, o.w, 1, 1};   // written in place by the fused octave
-					else from[i] = HessLevelSource{level(p, j).data, p.intenImageStride, p.w, 2, 0};
-				}
-				unsigned int skipMask = 0;
-				for (int i = 0; i < o.nlevels; i++)
-					if (o.onDemand[i]) skipMask |= 1u << i;
-				BHIP_TRY(bhip_launch_hessian(ctx, ii, o.skip, o.nlevels, o.sizes, level(o, 0), (long long)o.w * o.h, from, skipMask));
-				auto held = [&](int l) { DevImg<const float> v = level(o, l); if (o.onDemand[l]) v.data = nullptr; return v; };   // nullptr: not in memory
-				for (auto& m : o.mids)
-					BHIP_TRY(bhip_launch_nms_scalespace(ctx, held(m.level - 1), level(o, m.level), held(m.level + 1), m.p, cfg.extractRadius, cfg.detectThreshold,
-														bitmap.as<unsigned int>(), bitmapWords, cand.as<KeyPoint>(), count.as<int>(), cap, nBest(), ii));
+				// a run of stand-alone octaves: their Hessian launches, then the NMS of all their middle levels in one launch.  (N-best
+				// selection lists every level's maxima by itself: octave by octave, level by level.)
+				size_t end = k + 1;
+				while (!nBest() && end < plan.size() && !plan[end].fused) end++;
+				BHIP_TRY(runStandAlone(ctx, ii, k, end));
+				k = end - 1;
 			}
 			BHIP_TRY(bhip_launch_word_prefix(ctx, bitmap.as<unsigned int>(), bitmapWords, batch, prefix.as<unsigned int>(), count.as<int>() + batch));
 			counts.resize(batch);

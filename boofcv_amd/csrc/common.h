@@ -242,6 +242,17 @@ struct HessLevelSource {
 template <class T>
 int bhip_launch_hessian(bhip_ctx* ctx, DevImg<const T> ii, int skip, int nlevels, const int* sizes, DevImg<float> level0, long long levelStride,
 						const HessLevelSource* from, unsigned int skipMask);
+// several octaves of one batch of integral images, in order (an octave may copy levels from the one before): the arguments of bhip_launch_hessian
+struct HessOctave {
+	int skip, nlevels;
+	const int* sizes;
+	DevImg<float> level0;
+	long long levelStride;
+	const HessLevelSource* from;
+	unsigned int skipMask;
+};
+template <class T>
+int bhip_launch_hessian_octaves(bhip_ctx* ctx, DevImg<const T> ii, int noct, const HessOctave* octs);
 
 // colour SURF (see DescParams): the band integral images the descriptor is built from.  nBands == 0: grey SURF, nothing else is read
 struct DescPlanar {
@@ -261,6 +272,14 @@ template <class T>
 int bhip_launch_nms_scalespace(bhip_ctx* ctx, DevImg<const float> lower, DevImg<const float> mid, DevImg<const float> upper, DetectLevelParams p, int radius,
 							   float threshold, unsigned int* bitmap, int bitmapWords, KeyPoint* cand, int* candCount, int cap, bool listOnly,
 							   DevImg<const T> ii);
+// the same for n levels, of one octave or of several, in one launch per four levels (never the N-best list form)
+struct NmsLevelArgs {
+	DevImg<const float> lower, mid, upper;
+	DetectLevelParams p;
+};
+template <class T>
+int bhip_launch_nms_scalespace_levels(bhip_ctx* ctx, int n, const NmsLevelArgs* lv, int radius, float threshold, unsigned int* bitmap, int bitmapWords,
+									  KeyPoint* cand, int* candCount, int cap, DevImg<const T> ii);
 int bhip_launch_select_nbest(bhip_ctx* ctx, DevImg<const float> lower, DevImg<const float> mid, DevImg<const float> upper, DetectLevelParams p, int radius,
 							 int target, const unsigned int* bitmap, const unsigned int* prefix, int bitmapWords, const KeyPoint* nms, int cap, float* keyBuf,
 							 int* idxBuf, KeyPoint* out, int* levelStart, int* levelCount, int levelIndex, int nlv);

@@ -145,12 +145,12 @@ __device__ __forceinline__ void emitKeyPoint(const NmsParams& P, int img, int x,
 	}
 }
 
-__global__ __launch_bounds__(256) void k_nms_scalespace(NmsParams P) {
+// one workgroup: 256 columns x NMS_ROWS rows (block bx, by of the level's NMS region) of image img
+__device__ __forceinline__ void nmsScalespaceBlock(const NmsParams& P, int bx, int by, int img) {
 	const int b = P.p.border;
 	const int w = P.p.w, h = P.p.h;
-	const int x = b + blockIdx.x * blockDim.x + threadIdx.x;
-	const int yBase = b + blockIdx.y * NMS_ROWS;
-	const int img = blockIdx.z;
+	const int x = b + bx * blockDim.x + threadIdx.x;
+	const int yBase = b + by * NMS_ROWS;
 	const float* mid = P.mid + (long long)img * P.imageStride;
 	const int stride = P.stride;
 	const int r = P.radius;
@@ -202,7 +202,7 @@ __global__ __launch_bounds__(256) void k_nms_scalespace(NmsParams P) {
 		const int ci = c0 + threadIdx.x;
 		if ((int)threadIdx.x < passN && ci < ncand) {
 			const int code = candList[ci];
-			const int x = b + blockIdx.x * blockDim.x + (code & 0xFFFF);
+			const int x = b + bx * blockDim.x + (code & 0xFFFF);
 			const int y = yBase + (code >> 16);
 			const float val = mid[(long long)y * stride + x];
 			if (r == 2 ? strictLocalMax<2>(mid, stride, w, h, x, y, r, val, P.threshold) : strictLocalMax<0>(mid, stride, w, h, x, y, r, val, P.threshold)) {
@@ -270,14 +270,33 @@ __global__ __launch_bounds__(256) void k_nms_scalespace(NmsParams P) {
 	}
 }
 
+__global__ __launch_bounds__(256) void k_nms_scalespace(NmsParams P) { nmsScalespaceBlock(P, blockIdx.x, blockIdx.y, blockIdx.z); }
+
+// Several levels (of any octaves) in one launch: the blocks of an image are numbered level by level, blockIdx.y is the image.  The small
+// launches of the coarse octaves each end in a tail of a few long-lived workgroups; together they fill the device.
+#define BHIP_NMS_MULTI 4
+struct NmsMultiParams {
+	int end[BHIP_NMS_MULTI];   // blocks of an image below end[l]: level l or one before it (end of an unused level = end of the last level)
+	int gx[BHIP_NMS_MULTI];    // blocks per row band of level l
+	NmsParams lv[BHIP_NMS_MULTI];
+};
+__global__ __launch_bounds__(256) void k_nms_scalespace_multi(NmsMultiParams M) {
+	const int b = blockIdx.x;
+	const int l = (b >= M.end[0]) + (b >= M.end[1]) + (b >= M.end[2]);
+	const int local = b - (l > 0 ? M.end[l - 1] : 0);
+	const int by = local / M.gx[l];
+	nmsScalespaceBlock(M.lv[l], local - by * M.gx[l], by, blockIdx.y);
+}
+
+// the kernel arguments of one level; *blocks == 0: the level has no NMS region
 template <class T>
-int bhip_launch_nms_scalespace(bhip_ctx* ctx, DevImg<const float> lower, DevImg<const float> mid, DevImg<const float> upper, DetectLevelParams p, int radius,
-							   float threshold, unsigned int* bitmap, int bitmapWords, KeyPoint* cand, int* candCount, int cap, bool listOnly,
-							   DevImg<const T> ii) {
+static int nmsMakeParams(bhip_ctx* ctx, DevImg<const float> lower, DevImg<const float> mid, DevImg<const float> upper, DetectLevelParams p, int radius,
+						 float threshold, unsigned int* bitmap, int bitmapWords, KeyPoint* cand, int* candCount, int cap, bool listOnly, DevImg<const T> ii,
+						 NmsParams& P, int* gx, int* gy) {
 	const int rw = p.w - 2 * p.border, rh = p.h - 2 * p.border;
+	*gx = *gy = 0;
 	if (rw <= 0 || rh <= 0) return BHIP_OK;
-	const int batch = mid.batch;
-	NmsParams P{lower.data, mid.data, upper.data, mid.imageStride, mid.stride, p, radius, threshold, bitmap, bitmapWords, cand, candCount, cap, listOnly ? 1 : 0, {}};
+	P = NmsParams{lower.data, mid.data, upper.data, mid.imageStride, mid.stride, p, radius, threshold, bitmap, bitmapWords, cand, candCount, cap, listOnly ? 1 : 0, {}};
 	P.virt.lower.on = P.virt.upper.on = 0;
 	P.virt.intTaps = std::is_same<T, int32_t>::value ? 1 : 0;
 	if (!lower.data || !upper.data) {
@@ -287,14 +306,59 @@ int bhip_launch_nms_scalespace(bhip_ctx* ctx, DevImg<const float> lower, DevImg<
 		if (!lower.data) { P.virt.lower.on = 1; P.virt.lower.L = bhipMakeHessLevel(p.sizeLower, p.skip); }
 		if (!upper.data) { P.virt.upper.on = 1; P.virt.upper.L = bhipMakeHessLevel(p.sizeUpper, p.skip); }
 	}
-	dim3 grid((rw + 255) / 256, (rh + NMS_ROWS - 1) / NMS_ROWS, batch);
+	*gx = (rw + 255) / 256; *gy = (rh + NMS_ROWS - 1) / NMS_ROWS;
+	return BHIP_OK;
+}
+
+template <class T>
+int bhip_launch_nms_scalespace(bhip_ctx* ctx, DevImg<const float> lower, DevImg<const float> mid, DevImg<const float> upper, DetectLevelParams p, int radius,
+							   float threshold, unsigned int* bitmap, int bitmapWords, KeyPoint* cand, int* candCount, int cap, bool listOnly,
+							   DevImg<const T> ii) {
+	NmsParams P;
+	int gx, gy;
+	BHIP_TRY(nmsMakeParams<T>(ctx, lower, mid, upper, p, radius, threshold, bitmap, bitmapWords, cand, candCount, cap, listOnly, ii, P, &gx, &gy));
+	if (gx == 0) return BHIP_OK;
 	{
-		ProfScope ps(ctx, "k_nms_scalespace", 4.0 * p.w * p.h * batch);  // the mid level read once
-		hipLaunchKernelGGL(k_nms_scalespace, grid, dim3(256), 0, ctx->stream, P);
+		ProfScope ps(ctx, "k_nms_scalespace", 4.0 * p.w * p.h * mid.batch);  // the mid level read once
+		hipLaunchKernelGGL(k_nms_scalespace, dim3(gx, gy, mid.batch), dim3(256), 0, ctx->stream, P);
 	}
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
 }
+
+template <class T>
+int bhip_launch_nms_scalespace_levels(bhip_ctx* ctx, int n, const NmsLevelArgs* lv, int radius, float threshold, unsigned int* bitmap, int bitmapWords,
+									  KeyPoint* cand, int* candCount, int cap, DevImg<const T> ii) {
+	for (int l0 = 0; l0 < n; l0 += BHIP_NMS_MULTI) {
+		const int m = std::min(n - l0, BHIP_NMS_MULTI);
+		if (m == 1) {
+			const NmsLevelArgs& a = lv[l0];
+			BHIP_TRY(bhip_launch_nms_scalespace<T>(ctx, a.lower, a.mid, a.upper, a.p, radius, threshold, bitmap, bitmapWords, cand, candCount, cap, false, ii));
+			continue;
+		}
+		NmsMultiParams M;
+		memset(&M, 0, sizeof M);
+		int blocks = 0;
+		double bytes = 0;
+		for (int l = 0; l < BHIP_NMS_MULTI; l++) {
+			M.gx[l] = 1;
+			if (l < m) {
+				const NmsLevelArgs& a = lv[l0 + l];
+				int gx, gy;
+				BHIP_TRY(nmsMakeParams<T>(ctx, a.lower, a.mid, a.upper, a.p, radius, threshold, bitmap, bitmapWords, cand, candCount, cap, false, ii, M.lv[l], &gx, &gy));
+				if (gx > 0) { M.gx[l] = gx; blocks += gx * gy; bytes += 4.0 * a.p.w * a.p.h * a.mid.batch; }
+			}
+			M.end[l] = blocks;
+		}
+		if (blocks == 0) continue;
+		ProfScope ps(ctx, "k_nms_scalespace", bytes);
+		hipLaunchKernelGGL(k_nms_scalespace_multi, dim3(blocks, lv[l0].mid.batch), dim3(256), 0, ctx->stream, M);
+	}
+	BHIP_HIP(ctx, hipGetLastError());
+	return BHIP_OK;
+}
+template int bhip_launch_nms_scalespace_levels(bhip_ctx*, int, const NmsLevelArgs*, int, float, unsigned int*, int, KeyPoint*, int*, int, DevImg<const float>);
+template int bhip_launch_nms_scalespace_levels(bhip_ctx*, int, const NmsLevelArgs*, int, float, unsigned int*, int, KeyPoint*, int*, int, DevImg<const int32_t>);
 template int bhip_launch_nms_scalespace(bhip_ctx*, DevImg<const float>, DevImg<const float>, DevImg<const float>, DetectLevelParams, int, float, unsigned int*, int,
 										KeyPoint*, int*, int, bool, DevImg<const float>);
 template int bhip_launch_nms_scalespace(bhip_ctx*, DevImg<const float>, DevImg<const float>, DevImg<const float>, DetectLevelParams, int, float, unsigned int*, int,

@@ -8,8 +8,10 @@
 // Two plans, equally exact.  Gather (k_hessian): every pixel of every level of one octave is one thread that fetches its taps itself.
 // Staged rows (k_hessian_rows, octaves with a power-of-two step >= 4): the inner pixels of a computed level take their taps from LDS, where
 // a workgroup has put the ten image rows of one output row with coalesced loads; the border pixels and the shared levels' pixels that
-// must be recomputed or copied go through the gather form in a compact launch (k_hessian_frame).  BHIP_DETECT_GATHER=1 forces the gather
-// plan.  fp32, no FMA contraction (-ffp-contract=off), expressions in the reference's order.
+// must be recomputed or copied go through the gather form in a compact launch (k_hessian_frame).  The staged levels of the default
+// schedule (size 75 at step 4, 99 and 147 at step 8) take k_hessian_rows_fixed: compile-time geometry, a band of rows per workgroup, the
+// levels of several octaves in one launch.  BHIP_DETECT_GATHER=1 forces the gather plan, BHIP_HESSIAN_ROWS_GENERIC=1 the run-time rows
+// kernel.  fp32, no FMA contraction (-ffp-contract=off), expressions in the reference's order.
 // Bound: HBM (+L2 gather).  Algorithmic bytes per octave: 4P (ii read) + levels * 4P/skip^2 (intensity write).
 #include "hessian_dev.h"
 #include <algorithm>
@@ -197,6 +199,133 @@ __global__ __launch_bounds__(256) void k_hessian_rows(HessRowParams P) {
 		hessianDeterminant(Dxx, Dyy, Dxy, L.norm);
 }
 
+// ---------------- staged rows, compile-time geometry ----------------
+// The computed levels of the coarse octaves of the reference's default schedule: size 75 at step 4, sizes 99 and 147 at step 8.  For these
+// everything hessPlanRows derives from (step, size) is a constant of the instantiation: the ten row distances, the column distances, plane
+// and group of every tap (each tap is a ds_read with an immediate offset).  The planes have a fixed pitch of 256 words whatever the tile
+// width, so a workgroup always holds 32 KiB of LDS.
+#define BHIP_HESS_PITCH 256
+template <int SKIP, int SIZE>
+struct HessFixedGeo {
+	static constexpr int bS = SIZE / 3, bL = SIZE - bS - 1, rF = SIZE / 2, rS = bL / 2;
+	static constexpr int borderOrig = rF + 1 + (SKIP - (rF + 1) % SKIP), border = borderOrig / SKIP, lost = borderOrig - rF - 1;
+	static constexpr int xyOff(int i) { return i == 0 ? 0 : i == 1 ? bS : i == 2 ? bS + 1 : 2 * bS + 1; }
+	// staged row r (0-1 Dxx, 2-5 Dyy, 6-9 Dxy): its distance from row y * SKIP, and the column of its tap k from the output's first tap column
+	static constexpr int dy(int r) { return r < 2 ? -rS - 1 + r * bL : r < 6 ? -rF - 1 + (r - 2) * bS : -bS - 1 + xyOff(r - 6); }
+	static constexpr int off(int r, int k) { return r < 2 ? k * bS : r < 6 ? rF - rS + k * bL : rF - bS + xyOff(k); }
+	static constexpr int dc(int r) { return lost + off(r, 0); }
+	static constexpr int plane(int r, int k) { return (off(r, k) - off(r, 0)) % SKIP; }
+	static constexpr int group(int r, int k) { return (off(r, k) - off(r, 0)) / SKIP; }
+	static constexpr int maxGroup = 3 * bS / SKIP;   // the last Dxx tap: 3 bS >= bL, 2 bS + 1
+	static constexpr int txCap = BHIP_HESS_PITCH - (maxGroup + 1);
+	static constexpr int base(int r) { return BHIP_HESS_PITCH * (r <= 2 ? 4 * r : r <= 6 ? 8 + 2 * (r - 2) : 16 + 4 * (r - 6)); }
+	static constexpr int tap(int r, int k) { return base(r) + plane(r, k) * BHIP_HESS_PITCH + group(r, k); }
+	static constexpr bool planesFit() {
+		for (int r = 0; r < BHIP_HESS_ROWS; r++)
+			for (int k = 0; k < hessRowWords(r); k++)
+				if (plane(r, k) >= hessRowWords(r) || group(r, k) > maxGroup) return false;
+		return true;
+	}
+};
+#define BHIP_HESS_FIXED_LDS (32 * BHIP_HESS_PITCH * 4)
+
+template <class T, class G>
+struct HessTapsFixed {
+	const T* lds;   // + the output's index in its tile
+	__device__ __forceinline__ T xx(int r, int k) const { return lds[G::tap(r, k)]; }
+	__device__ __forceinline__ T yy(int k, int s) const { return lds[G::tap(2 + k, s)]; }
+	__device__ __forceinline__ T xy(int r, int c) const { return lds[G::tap(6 + r, c)]; }
+};
+
+// what is left of a level at run time: where its inner pixels are, how they are tiled, where they go
+struct HessFixedLevel {
+	float* out;             // the level's plane of image 0
+	long long imageStrideOut;
+	int outStride;
+	int x0, nx, y0, ny;     // the inner region, in output pixels
+	int TX, ntiles;
+	float norm;
+};
+#define BHIP_HESS_FIXED_LEVELS 3   // (4, 75), (8, 99), (8, 147), in this order
+struct HessFixedParams {
+	ImgView ii;
+	int batch, band;        // band: output rows per workgroup
+	int end0, end1;         // blocks of an image below end0: level 0, below end1: level 1, the others: level 2
+	int blocksPerImage;
+	HessFixedLevel lv[BHIP_HESS_FIXED_LEVELS];
+};
+
+// One workgroup: one x-tile and `band` consecutive output rows (fewer at the lower end of the inner region) of one level of one image.
+// Everything that does not depend on the row is set up once; a row is ten loads per thread, a barrier, 32 taps, a store.  The loads of a
+// row wait in registers while the taps of the row before are read from LDS.
+template <class T, int SKIP, int SIZE>
+__device__ __forceinline__ void hessRowsBand(const ImgView& ii, const HessFixedLevel& L, int band, int img, int blk, unsigned int* lds) {
+	typedef HessFixedGeo<SKIP, SIZE> G;
+	static_assert((SKIP & (SKIP - 1)) == 0 && SKIP >= 4 && SIZE % 3 == 0 && G::planesFit() && G::txCap >= 64, "not a staged-rows geometry");
+	const int tile = blk % L.ntiles, yFirst = L.y0 + (blk / L.ntiles) * band;
+	const int yEnd = min(yFirst + band, L.y0 + L.ny);
+	const int first = tile * L.TX;                 // first output of the tile, counted from the first inner column
+	const int n = min(L.TX, L.nx - first);         // outputs of this tile
+	const int W = ii.width;
+	const int q = threadIdx.x;
+	const bool stages = q < n + G::maxGroup + 1;   // the groups the tile's n outputs reach
+	const int c0 = (first + q) * SKIP;
+	// row r of output row y starts at src + dy(r) * stride + dc(r); nothing outside [0, W) of an image row is touched
+	const unsigned int* __restrict__ src = (const unsigned int*)ii.data + (long long)img * ii.imageStride + (long long)(yFirst * SKIP) * ii.stride + c0;
+	float* __restrict__ dst = L.out + (long long)img * L.imageStrideOut + (long long)yFirst * L.outStride + L.x0 + first + q;
+	unsigned int v[BHIP_HESS_ROWS][4];
+	auto loadRows = [&]() {
+#pragma unroll
+		for (int r = 0; r < BHIP_HESS_ROWS; r++) {
+			const int rw = hessRowWords(r);
+			const int c = c0 + G::dc(r);
+			const unsigned int* __restrict__ s = src + (long long)G::dy(r) * ii.stride + G::dc(r);
+			if (c >= 0 && c + rw <= W) {
+				if (rw == 4) { const hess_u4 t = *(const hess_u4*)s; v[r][0] = t.x; v[r][1] = t.y; v[r][2] = t.z; v[r][3] = t.w; }
+				else { const hess_u2 t = *(const hess_u2*)s; v[r][0] = t.x; v[r][1] = t.y; }
+			} else {
+#pragma unroll
+				for (int e = 0; e < rw; e++) v[r][e] = c + e >= 0 && c + e < W ? s[e] : 0;
+			}
+		}
+	};
+	if (stages) loadRows();
+	for (int y = yFirst; y < yEnd; y++) {
+		if (y > yFirst) __syncthreads();   // the row before has been read
+		if (stages) {
+#pragma unroll
+			for (int r = 0; r < BHIP_HESS_ROWS; r++)
+#pragma unroll
+				for (int e = 0; e < hessRowWords(r); e++) lds[G::base(r) + e * BHIP_HESS_PITCH + q] = v[r][e];
+		}
+		__syncthreads();
+		src += (long long)SKIP * ii.stride;
+		if (stages && y + 1 < yEnd) loadRows();   // the next row's loads are in flight while this row's taps are read
+		if (q < n) {
+			float Dxx, Dyy, Dxy;
+			hessianInnerExpr<T>(HessTapsFixed<T, G>{(const T*)lds + q}, Dxx, Dyy, Dxy);
+			*dst = hessianDeterminant(Dxx, Dyy, Dxy, L.norm);
+		}
+		dst += L.outStride;
+	}
+}
+
+// Block b runs on XCD b % 8 and takes image (b / 8 / blocksPerImage) * 8 + b % 8, as in k_hessian_rows: an XCD works through whole images,
+// and within an image level by level, the bands of a level in row order.
+template <class T>
+__global__ __launch_bounds__(256) void k_hessian_rows_fixed(HessFixedParams P) {
+	extern __shared__ __attribute__((aligned(16))) unsigned int hessLds[];
+	const int slot = blockIdx.x >> 3;
+	const int img = (slot / P.blocksPerImage) * 8 + (blockIdx.x & 7);
+	if (img >= P.batch) return;
+	const int within = slot % P.blocksPerImage;
+	if (within < P.end0) hessRowsBand<T, 4, 75>(P.ii, P.lv[0], P.band, img, within, hessLds);
+	else if (within < P.end1) hessRowsBand<T, 8, 99>(P.ii, P.lv[1], P.band, img, within - P.end0, hessLds);
+	else hessRowsBand<T, 8, 147>(P.ii, P.lv[2], P.band, img, within - P.end1, hessLds);
+}
+static int hessFixedIndex(int skip, int size) { return skip == 4 && size == 75 ? 0 : skip == 8 && size == 99 ? 1 : skip == 8 && size == 147 ? 2 : -1; }
+#define BHIP_HESS_BAND 2   // output rows per workgroup of k_hessian_rows_fixed: 1, 2, 3, 4, 6, 8, 16 measured ("Open performance items", item 3)
+
 // Plans the staged-rows form of a launch: which levels are staged and how (R), and which pixels are left to the gather form (F).  False:
 // the launch stays with the gather plan (a step that is not a power of two or below 4, taps whose column phases span more than the
 // 16- or 8-byte run of their row, a kernel so wide that a tile would hold fewer than 64 outputs, no computed level with inner pixels).
@@ -282,9 +411,69 @@ static bool hessPlanRows(const HessParams& P, int batch, HessRowParams& R, HessF
 	return true;
 }
 
+// the rows of an octave on the staged-rows plan that have not been launched yet
+struct HessPendingRows {
+	HessRowParams R;
+	int size[BHIP_MAX_LEVELS];   // kernel size of R.lv[i]
+	int ldsBytes;
+	double bytes;                // algorithmic bytes of the octave
+};
+
 template <class T>
-int bhip_launch_hessian(bhip_ctx* ctx, DevImg<const T> ii, int skip, int nlevels, const int* sizes, DevImg<float> level0, long long levelStride,
-						const HessLevelSource* from, unsigned int skipMask) {
+static int hessLaunchPending(bhip_ctx* ctx, std::vector<HessPendingRows>& pending, const ImgView& iiView, int batch, bool generic) {
+	if (pending.empty()) return BHIP_OK;
+	// the compile-time-geometry kernel takes the launch when every staged level is one of its three, each at most once
+	const HessRowLevel* fixedLevel[BHIP_HESS_FIXED_LEVELS] = {nullptr, nullptr, nullptr};
+	const HessRowParams* fixedOctave[BHIP_HESS_FIXED_LEVELS] = {nullptr, nullptr, nullptr};
+	bool fixed = !generic;
+	double bytes = 0;
+	for (const HessPendingRows& p : pending) {
+		bytes += p.bytes - (&p == &pending[0] ? 0.0 : 4.0 * iiView.width * iiView.height * batch);   // the integral image counts once
+		for (int i = 0; i < p.R.nlv && fixed; i++) {
+			const int k = hessFixedIndex(p.R.skip, p.size[i]);
+			if (k < 0 || fixedLevel[k]) fixed = false;
+			else { fixedLevel[k] = &p.R.lv[i]; fixedOctave[k] = &p.R; }
+		}
+	}
+	if (fixed) {
+		HessFixedParams X;
+		memset(&X, 0, sizeof X);
+		X.ii = iiView; X.batch = batch; X.band = BHIP_HESS_BAND;
+#ifdef BHIP_EXPERIMENTS
+		if (const char* e = getenv("BHIP_HESSIAN_ROWS_BAND")) X.band = std::min(std::max(atoi(e), 1), 64);
+#endif
+		int blocks[BHIP_HESS_FIXED_LEVELS];
+		for (int k = 0; k < BHIP_HESS_FIXED_LEVELS; k++) {
+			blocks[k] = 0;
+			if (!fixedLevel[k]) continue;
+			const HessRowLevel& V = *fixedLevel[k];
+			const HessRowParams& R = *fixedOctave[k];
+			X.lv[k] = HessFixedLevel{R.out + (long long)V.level * R.levelStride, R.imageStrideOut, R.outStride, V.x0, V.nx, V.y0, V.ny, V.TX, V.ntiles, V.norm};
+			blocks[k] = V.ntiles * ((V.ny + X.band - 1) / X.band);
+		}
+		X.end0 = blocks[0]; X.end1 = blocks[0] + blocks[1]; X.blocksPerImage = X.end1 + blocks[2];
+		ProfScope ps(ctx, "k_hessian_rows", bytes);
+		hipLaunchKernelGGL(k_hessian_rows_fixed<T>, dim3(8 * ((batch + 7) / 8) * X.blocksPerImage), dim3(256), BHIP_HESS_FIXED_LDS, ctx->stream, X);
+	} else {
+		for (const HessPendingRows& p : pending) {
+			ProfScope ps(ctx, "k_hessian_rows", p.bytes);
+			hipLaunchKernelGGL(k_hessian_rows<T>, dim3(8 * ((batch + 7) / 8) * p.R.blocksPerImage), dim3(256), p.ldsBytes, ctx->stream, p.R);
+		}
+	}
+	pending.clear();
+	BHIP_HIP(ctx, hipGetLastError());
+	return BHIP_OK;
+}
+
+// One octave of bhip_launch_hessian_octaves: the gather plan is one launch; the staged-rows plan launches its frame pixels and queues its rows.
+template <class T>
+static int hessLaunchOctave(bhip_ctx* ctx, DevImg<const T> ii, const HessOctave& oct, bool gather, bool generic, std::vector<HessPendingRows>& pending) {
+	const int skip = oct.skip, nlevels = oct.nlevels;
+	const int* sizes = oct.sizes;
+	const DevImg<float> level0 = oct.level0;
+	const long long levelStride = oct.levelStride;
+	const HessLevelSource* from = oct.from;
+	const unsigned int skipMask = oct.skipMask;
 	if (nlevels > BHIP_MAX_LEVELS) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "too many scales per octave");
 	const int batch = ii.batch;
 	HessParams P;
@@ -311,10 +500,19 @@ int bhip_launch_hessian(bhip_ctx* ctx, DevImg<const T> ii, int skip, int nlevels
 	if (P.w <= 0 || P.h <= 0 || P.nrun == 0) return BHIP_OK;
 	// algorithmic bytes: the integral image once + every level's intensity written once
 	const double bytes = 4.0 * ii.width * ii.height * batch + 4.0 * P.nrun * (double)P.w * P.h * batch;
-	HessRowParams R;
+	// a level copied from a plane whose rows are still queued: those rows go first
+	for (int i = 0; i < nlevels; i++) {
+		const HessLevelSource& S = P.from[i];
+		if (!S.src || S.inPlace) continue;
+		bool waits = false;
+		for (const HessPendingRows& p : pending)
+			for (int k = 0; k < p.R.nlv; k++)
+				if (S.src == p.R.out + (long long)p.R.lv[k].level * p.R.levelStride) waits = true;
+		if (waits) { BHIP_TRY(hessLaunchPending<T>(ctx, pending, P.ii, batch, generic)); break; }
+	}
+	HessPendingRows Q;
 	HessFrameParams F;
-	int ldsBytes = 0;
-	if (bhip_env_flag("BHIP_DETECT_GATHER") || !hessPlanRows(P, batch, R, F, &ldsBytes)) {   // BHIP_DETECT_GATHER: parity cross-check of the two plans
+	if (gather || !hessPlanRows(P, batch, Q.R, F, &Q.ldsBytes)) {
 		dim3 grid((P.w + 255) / 256, P.h, batch * P.nrun);
 		ProfScope ps(ctx, skip == 1 ? "k_hessian_skip1" : "k_hessian_skipN", bytes);
 		hipLaunchKernelGGL(k_hessian<T>, grid, dim3(256), 0, ctx->stream, P);
@@ -325,11 +523,33 @@ int bhip_launch_hessian(bhip_ctx* ctx, DevImg<const T> ii, int skip, int nlevels
 			ProfScope ps(ctx, "k_hessian_frame");
 			hipLaunchKernelGGL(k_hessian_frame<T>, dim3((maxCount + 255) / 256, batch * P.nrun), dim3(256), 0, ctx->stream, P, F);
 		}
-		ProfScope ps(ctx, "k_hessian_rows", bytes);
-		hipLaunchKernelGGL(k_hessian_rows<T>, dim3(8 * ((batch + 7) / 8) * R.blocksPerImage), dim3(256), ldsBytes, ctx->stream, R);
+		for (int k = 0; k < Q.R.nlv; k++) Q.size[k] = sizes[Q.R.lv[k].level];
+		Q.bytes = bytes;
+		pending.push_back(Q);
 	}
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
+}
+
+// The octaves in order.  The rows of the octaves on the staged-rows plan depend on the integral image alone and write pixels no frame
+// launch touches, so they wait for one launch behind the last octave.  Only where a later octave copies from a plane whose rows are
+// still waiting are these launched first.
+template <class T>
+int bhip_launch_hessian_octaves(bhip_ctx* ctx, DevImg<const T> ii, int noct, const HessOctave* octs) {
+	const bool gather = bhip_env_flag("BHIP_DETECT_GATHER");              // parity cross-check of the two plans
+	const bool generic = bhip_env_flag("BHIP_HESSIAN_ROWS_GENERIC");      // parity cross-check of the two staged-rows kernels
+	std::vector<HessPendingRows> pending;
+	for (int o = 0; o < noct; o++) BHIP_TRY(hessLaunchOctave<T>(ctx, ii, octs[o], gather, generic, pending));
+	return hessLaunchPending<T>(ctx, pending, bhip_kernel_view(ii), ii.batch, generic);
+}
+template int bhip_launch_hessian_octaves(bhip_ctx*, DevImg<const int32_t>, int, const HessOctave*);
+template int bhip_launch_hessian_octaves(bhip_ctx*, DevImg<const float>, int, const HessOctave*);
+
+template <class T>
+int bhip_launch_hessian(bhip_ctx* ctx, DevImg<const T> ii, int skip, int nlevels, const int* sizes, DevImg<float> level0, long long levelStride,
+						const HessLevelSource* from, unsigned int skipMask) {
+	const HessOctave o{skip, nlevels, sizes, level0, levelStride, from, skipMask};
+	return bhip_launch_hessian_octaves<T>(ctx, ii, 1, &o);
 }
 template int bhip_launch_hessian(bhip_ctx*, DevImg<const int32_t>, int, int, const int*, DevImg<float>, long long, const HessLevelSource*, unsigned int);
 template int bhip_launch_hessian(bhip_ctx*, DevImg<const float>, int, int, const int*, DevImg<float>, long long, const HessLevelSource*, unsigned int);
