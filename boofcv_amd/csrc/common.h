@@ -525,3 +525,20 @@ int bhip_launch_klt_drop_all(bhip_ctx* ctx, KltTab T, int resetTotal);
 int bhip_launch_klt_stats(bhip_ctx* ctx, KltTab T, unsigned long long* out);   // out[3] += tracks, iterations, border-form iterations of the last process()
 int bhip_launch_klt_gather(bhip_ctx* ctx, KltTab T, int which, int seq, int n, long long* id, float* xy, int* fault, float* err);
 int bhip_launch_klt_gather_templates(bhip_ctx* ctx, KltTab T, int which, int seq, int layer, int n, float* tmpl, float* G);
+
+// ---------------- dense KLT optical flow (flow.hip; the generic track kernel is in klt.hip) ----------------
+// one record per pixel, what DenseOpticalFlowKlt.process knows about a pixel's own track before checkNeighbors: the fault (KltTrackFault ordinal,
+// BHIP_KLT_REFERENCE_THROWS, or BHIP_FLOW_NO_DESCRIPTION), and where it is BHIP_KLT_SUCCESS tracker.getError() and (feature.x - x, feature.y - y); 0 elsewhere
+struct FlowRec {
+	int fault;
+	float error, dx, dy;
+};
+#define BHIP_FLOW_LANE_MAX_RADIUS 3   // the lane-per-pixel form keeps 3 (2r+1)^2 floats per lane in LDS
+// one wave per pixel (any radius up to BHIP_KLT_MAX_RADIUS); P is the source pyramid with its gradient, dst the destination pyramid in the same layout
+int bhip_launch_flow_track_wave(bhip_ctx* ctx, KltPyr P, const float* dst, int r, bhip_klt_cfg cfg, int batch, FlowRec* rec, unsigned long long* stats);
+int bhip_launch_flow_track_wave(bhip_ctx* ctx, KltPyrU8 P, const uint8_t* dst, int r, bhip_klt_cfg cfg, int batch, FlowRec* rec, unsigned long long* stats);
+// one lane per pixel, r <= BHIP_FLOW_LANE_MAX_RADIUS
+int bhip_launch_flow_track_lane(bhip_ctx* ctx, KltPyr P, const float* dst, int r, bhip_klt_cfg cfg, int batch, FlowRec* rec, unsigned long long* stats);
+int bhip_launch_flow_track_lane(bhip_ctx* ctx, KltPyrU8 P, const uint8_t* dst, int r, bhip_klt_cfg cfg, int batch, FlowRec* rec, unsigned long long* stats);
+// checkNeighbors as an order-free reduction: flow[b][y][x] = (x, y) floats at flow.data + b * imageStride + y * stride + 2 * x (strides in floats)
+int bhip_launch_flow_reduce(bhip_ctx* ctx, const FlowRec* rec, int r, DevImg<float> flow);

@@ -17,6 +17,7 @@
 // _S16 are the F32 expression on the four taps converted to float (& 0xFF, sign-extended), every such integer is exact in fp32, so the
 // integer instantiation performs the fp32 operations of the float one on float copies of the same arrays.
 #include "common.h"
+#include "klt_dev.h"
 #include <cfloat>
 #include <cmath>
 
@@ -30,82 +31,6 @@ struct KltShared {
 	unsigned char ok[KLT_LEN + 3];                    // element takes part in the sums
 	float sum[5];
 	int cnt;
-};
-
-// ---- BilinearRectangle_F32.region ----
-struct KltRegion {
-	int xt, yt, regW, regH;
-	bool bR, bB, bad;
-	float ax, ay, bx, by, a0, a1, a2, a3;
-};
-__device__ __forceinline__ KltRegion kltRegion(float tlx, float tly, int w, int h, int W, int H) {
-	KltRegion R;
-	// region() :65 throws on this test; a NaN corner passes it in Java and then reads from pixel 0, which the integer test below also
-	// allows only when the patch fits
-	R.bad = tlx < 0 || tly < 0 || tlx + w > W || tly + h > H || w <= 0 || h <= 0;
-	R.xt = tlx == tlx ? (int)fminf(fmaxf(tlx, -1.0f), 1.0e9f) : 0;
-	R.yt = tly == tly ? (int)fminf(fmaxf(tly, -1.0f), 1.0e9f) : 0;
-	if (R.xt < 0 || R.yt < 0 || R.xt + w > W || R.yt + h > H) R.bad = true;   // :89 "requested region is out of bounds"
-	R.ax = tlx - R.xt;
-	R.ay = tly - R.yt;
-	R.bx = 1.0f - R.ax;
-	R.by = 1.0f - R.ay;
-	R.a0 = R.bx * R.by;
-	R.a1 = R.ax * R.by;
-	R.a2 = R.ax * R.ay;
-	R.a3 = R.bx * R.ay;
-	R.bR = R.xt + w == W;
-	R.bB = R.yt + h == H;
-	R.regW = R.bR ? w - 1 : w;
-	R.regH = R.bB ? h - 1 : h;
-	return R;
-}
-// output pixel (j, i) of region(); the image border cases are handleBorder :128-172 as written (including the bottom-only corner, which
-// reads row regHeight of the image and mixes with by / ay)
-template <class T>
-__device__ __forceinline__ float kltRegionAt(const KltRegion& R, const T* p, int stride, int j, int i) {
-	const T* q = p + (long long)(R.yt + i) * stride + R.xt + j;
-	if (j < R.regW && i < R.regH) {
-		const float XY = q[0], xY = q[1], Xy = q[stride], xy = q[stride + 1];
-		return R.a0 * XY + R.a1 * xY + R.a2 * xy + R.a3 * Xy;
-	}
-	if (i < R.regH) return R.by * q[0] + R.ay * q[stride];   // right border column
-	if (j == R.regW) return q[0];                             // corner, right and bottom border
-	if (!R.bR && j == R.regW - 1) {
-		const float XY = q[0], Xy = p[(long long)R.regH * stride + R.xt + R.regW];
-		return R.by * XY + R.ay * Xy;
-	}
-	return R.bx * q[0] + R.ax * q[1];                         // bottom border row
-}
-
-// ---- KltTracker.computeSubImageBounds :421-457 ----
-struct KltSub {
-	int dx0, dy0, dx1, dy1;
-	float sx0, sy0;
-	bool bad;
-};
-__device__ __forceinline__ KltSub kltSubBounds(float cx, float cy, int r, int wF, int W, int H) {
-	KltSub B;
-	B.dx0 = 0; B.dy0 = 0; B.dx1 = wF; B.dy1 = wF;
-	B.sx0 = cx - r;
-	B.sy0 = cy - r;
-	const float sx1 = B.sx0 + wF, sy1 = B.sy0 + wF;
-	if (B.sx0 < 0) { B.dx0 = (int)-floorf(B.sx0); B.sx0 += B.dx0; }
-	if (sx1 > W) { B.dx1 -= (int)ceilf(sx1 - W); B.dx1 -= (B.sx0 + (B.dx1 - B.dx0) > W ? 1 : 0); }
-	if (B.sy0 < 0) { B.dy0 = (int)-floorf(B.sy0); B.sy0 += B.dy0; }
-	if (sy1 > H) { B.dy1 -= (int)ceilf(sy1 - H); B.dy1 -= (B.sy0 + (B.dy1 - B.dy0) > H ? 1 : 0); }
-	B.bad = B.sx0 < 0 || B.sy0 < 0 || B.sx0 + (B.dx1 - B.dx0) > W || B.sy0 + (B.dy1 - B.dy0) > H;
-	return B;
-}
-
-struct KltBounds {
-	float aL, aR, aT, aB, oL, oR, oT, oB;
-	__device__ __forceinline__ KltBounds(int r, int W, int H) {   // setAllowedBounds :330-344
-		aL = r; aT = r; aR = W - r - 1; aB = H - r - 1;
-		oL = -r; oT = -r; oR = W + r - 1; oB = H + r - 1;
-	}
-	__device__ __forceinline__ bool inside(float x, float y) const { return !(x < aL || x > aR) && !(y < aT || y > aB); }
-	__device__ __forceinline__ bool outside(float x, float y) const { return x < oL || x > oR || y < oT || y > oB; }
 };
 
 // one lane per sum adds `arr` over the elements whose ok flag is set, in template order; lane 0 also counts them
@@ -558,6 +483,60 @@ __global__ __launch_bounds__(256) void k_klt_stats(KltTab T, unsigned long long*
 	if (threadIdx.x == 0) atomicAdd(out, (unsigned long long)(na + nd));
 }
 
+// ---- dense optical flow, generic form: one wave per pixel (DenseOpticalFlowKlt.process :78-98, the part before checkNeighbors) ----
+// feature.setPosition(px, py); setDescription on the source pyramid (every layer, PyramidKltTracker :58-71), then track on the destination
+// pyramid (:113-151).  The templates of all layers stay in dynamic LDS ([L][3][len], then Gxx, Gxy, Gyy of every layer): nothing goes to a
+// track table.  The record holds the fault, and error and flow = (feature.x - px, feature.y - py) where the track succeeded (0 elsewhere).
+template <class TI, class TD>
+__global__ __launch_bounds__(64) void k_klt_flow_track(KltPyrT<TI, TD> P, const TI* dst, int r, bhip_klt_cfg cfg, FlowRec* rec, unsigned long long* stats) {
+	__shared__ KltShared S;
+	extern __shared__ float flowStore[];
+	const int lane = threadIdx.x, px = blockIdx.x, py = blockIdx.y, b = blockIdx.z;
+	const int len = (2 * r + 1) * (2 * r + 1);
+	float* G = flowStore + P.numLayers * 3 * len;
+	const long long frame = (long long)b * P.frameStride;
+	const float fx0 = px, fy0 = py;
+	int fault = BHIP_KLT_SUCCESS, iters = 0;
+	for (int l = 0; l < P.numLayers; l++) {
+		const float scale = P.scale[l];
+		const long long o = frame + P.off[l];
+		float* t = flowStore + l * 3 * len;
+		float Gxx = 0, Gxy = 0, Gyy = 0;
+		const int ok = kltDescribeLayer(P.img + o, P.dx + o, P.dy + o, P.stride[l], P.w[l], P.h[l], r, cfg, fx0 / scale, fy0 / scale, t, t + len, t + 2 * len, Gxx, Gxy,
+										Gyy, S, lane);
+		if (ok != 1) { fault = ok < 0 ? BHIP_KLT_REFERENCE_THROWS : BHIP_FLOW_NO_DESCRIPTION; break; }
+		if (lane == 0) { G[3 * l] = Gxx; G[3 * l + 1] = Gxy; G[3 * l + 2] = Gyy; }
+	}
+	float x = fx0, y = fy0, error = 0;
+	if (fault == BHIP_KLT_SUCCESS) {
+		for (int l = P.numLayers - 1; l >= 0; l--) {
+			const float scale = P.scale[l];
+			x /= scale;
+			y /= scale;
+			const float* t = flowStore + l * 3 * len;
+			__syncthreads();
+			for (int e = lane; e < len; e += 64) {
+				const float d = t[e], gx = t[len + e], gy = t[2 * len + e];
+				S.D[e] = d; S.X[e] = gx; S.Y[e] = gy;
+				S.pXX[e] = gx * gx; S.pYY[e] = gy * gy; S.pXY[e] = gx * gy;
+			}
+			__syncthreads();
+			float fx = x, fy = y;
+			fault = kltTrackLayer(dst + frame + P.off[l], P.stride[l], P.w[l], P.h[l], r, cfg, fx, fy, G[3 * l], G[3 * l + 1], G[3 * l + 2], error, iters, S, lane);
+			if (fault != BHIP_KLT_SUCCESS) break;
+			x = fx * scale;
+			y = fy * scale;
+		}
+	}
+	if (lane == 0) {
+		const bool ok = fault == BHIP_KLT_SUCCESS;
+		FlowRec R;
+		R.fault = fault; R.error = ok ? error : 0.0f; R.dx = ok ? x - fx0 : 0.0f; R.dy = ok ? y - fy0 : 0.0f;
+		rec[((long long)b * P.frameH + py) * P.frameW + px] = R;
+		if (iters & 0xffff) atomicAdd(stats, (unsigned long long)(iters & 0xffff));
+	}
+}
+
 // ---- launchers ----
 #define KLT_DONE(ctx) do { BHIP_HIP(ctx, hipGetLastError()); return BHIP_OK; } while (0)
 
@@ -639,4 +618,17 @@ int bhip_launch_klt_gather(bhip_ctx* ctx, KltTab T, int which, int seq, int n, l
 	if (n <= 0) return BHIP_OK;
 	hipLaunchKernelGGL(k_klt_gather, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, T, which, seq, n, id, xy, fault, err);
 	KLT_DONE(ctx);
+}
+template <class TI, class TD>
+static int flowTrackWave(bhip_ctx* ctx, const char* tag, KltPyrT<TI, TD> P, const TI* dst, int r, bhip_klt_cfg cfg, int batch, FlowRec* rec, unsigned long long* stats) {
+	ProfScope prof(ctx, tag);
+	const size_t lds = ((size_t)P.numLayers * 3 * (2 * r + 1) * (2 * r + 1) + 3 * P.numLayers) * sizeof(float);
+	hipLaunchKernelGGL((k_klt_flow_track<TI, TD>), dim3(P.frameW, P.frameH, batch), dim3(64), lds, ctx->stream, P, dst, r, cfg, rec, stats);
+	KLT_DONE(ctx);
+}
+int bhip_launch_flow_track_wave(bhip_ctx* ctx, KltPyr P, const float* dst, int r, bhip_klt_cfg cfg, int batch, FlowRec* rec, unsigned long long* stats) {
+	return flowTrackWave(ctx, "k_flow_track_wave", P, dst, r, cfg, batch, rec, stats);
+}
+int bhip_launch_flow_track_wave(bhip_ctx* ctx, KltPyrU8 P, const uint8_t* dst, int r, bhip_klt_cfg cfg, int batch, FlowRec* rec, unsigned long long* stats) {
+	return flowTrackWave(ctx, "k_flow_track_wave_u8", P, dst, r, cfg, batch, rec, stats);
 }

@@ -17,6 +17,7 @@ Names follow the reference classes the host-buffer forms in boofcv_amd/api.py mi
   DeviceImageOps.distort        ImageDistort.apply (distortSB, GrayU8 / GrayF32)    I:alg/distort/ImageDistortBasic_SB.java:56-135, ImageDistortCache_SB.java:76-206
   DeviceImageOps.pyramid        PyramidDiscreteSampleBlur.process                   I:alg/transform/pyramid/PyramidDiscreteSampleBlur.java:88-118
   DeviceImageOps.cornerIntensity  GradientCornerIntensity.process                   F:alg/feature/detect/intensity/impl/ImplSsdCorner_F32.java:62-196
+  DeviceImageOps.denseFlowKlt   DenseOpticalFlow.process (flowKlt, GrayF32 / GrayU8)  F:factory/flow/FactoryDenseOpticalFlow.java:61-82
   DeviceImageOps.brief          DescribePointBrief.process                          F:alg/feature/describe/DescribePointBrief.java:73-89
   DeviceKltTracker              PointTrackerKltPyramid, batched over sequences      main/boofcv-geo/.../abst/feature/tracker/PointTrackerKltPyramid.java:139-348
   DeviceBackgroundModel         BackgroundStationaryBasic / Gaussian / Gmm, batched over streams   F:alg/background/stationary/*.java
@@ -195,6 +196,44 @@ class DeviceImageOps:
         fn = self.L.bhip_disparity_bm_dev_u8_f32 if subpixel else self.L.bhip_disparity_bm_dev_u8_u8
         _check(self.ctx, fn(self.ctx._h, C.byref(config._c()) if config is not None else None, lp, lis, lrs, rp, ris, rrs, W, H, B, op, ois, ors))
         return out
+
+    def denseFlowKlt(self, prev, curr, config=None, radius=3, out=None, tracks=None, form=_lib.BHIP_FLOW_FORM_AUTO):
+        """DenseOpticalFlow.process of FactoryDenseOpticalFlow.flowKlt on float32 or uint8 pairs [B,H,W] -> the flow [B,H,W,2] float32, invalid
+        pixels (NaN, 0).  config: a PkltConfig (its KltConfig and pyramidScaling; templateRadius is not read), None = the reference defaults.
+        `out`: any image / row stride with (x, y) adjacent, written in place.  tracks: None, True (allocated) or a contiguous int32 [B,H,W,4]
+        tensor that receives every pixel's own track {fault, error, dx, dy} (the three floats as their bit patterns); returned second when given.
+        form: BHIP_FLOW_FORM_AUTO / _LANE / _WAVE selects the track kernel (same results)."""
+        from .api import PkltConfig
+        config = config or PkltConfig()
+        u8 = prev.dtype == torch.uint8
+        dt = torch.uint8 if u8 else torch.float32
+        pp, pis, prs, W, H, B = _geom(prev, dt)
+        cp, cis, crs, W2, H2, B2 = _geom(curr, dt)
+        if (W, H, B) != (W2, H2, B2):
+            raise IllegalArgumentException("Image shapes do not match")
+        if out is None:
+            out = torch.empty((B, H, W, 2), dtype=torch.float32, device=prev.device)
+        if out.dim() != 4 or out.dtype != torch.float32 or not out.is_cuda or tuple(out.shape) != (B, H, W, 2):
+            raise IllegalArgumentException("the flow must be a [%d,%d,%d,2] float32 CUDA tensor" % (B, H, W))
+        if out.stride(3) != 1 or out.stride(2) != 2 or (H > 1 and out.stride(1) < 2 * W) or (B > 1 and out.stride(0) < 0):
+            raise IllegalArgumentException("the flow's (x, y) pairs and pixels of a row must be adjacent")
+        ois = out.stride(0) if B > 1 else H * out.stride(1)
+        ors = out.stride(1) if H > 1 else max(2 * W, out.stride(1))
+        if tracks is True:
+            tracks = torch.empty((B, H, W, 4), dtype=torch.int32, device=prev.device)
+        if tracks is not None and (tracks.dtype != torch.int32 or tuple(tracks.shape) != (B, H, W, 4) or not tracks.is_contiguous() or not tracks.is_cuda):
+            raise IllegalArgumentException("tracks must be a contiguous [%d,%d,%d,4] int32 CUDA tensor" % (B, H, W))
+        scales = (C.c_int * len(config.pyramidScaling))(*config.pyramidScaling)
+        fn = self.L.bhip_flow_klt_dev_u8 if u8 else self.L.bhip_flow_klt_dev_f32
+        _check(self.ctx, fn(self.ctx._h, C.byref(config.config._c()), int(radius), scales, len(scales), pp, pis, prs, cp, cis, crs, W, H, B,
+                            C.c_void_p(out.data_ptr()), ois, ors, C.c_void_p(tracks.data_ptr()) if tracks is not None else None, int(form)))
+        return out if tracks is None else (out, tracks)
+
+    def denseFlowStats(self):
+        """(pixels, Lucas-Kanade iterations) of the last denseFlowKlt on this context (synchronises)"""
+        n, it = C.c_longlong(), C.c_longlong()
+        _check(self.ctx, self.L.bhip_flow_klt_stats(self.ctx._h, C.byref(n), C.byref(it)))
+        return n.value, it.value
 
     def distortBuildMap(self, model, coeff, dw, dh, out=None):
         """bhip_distort_build_map: the [dh,dw,2] float32 map of an affine (model 1, six coefficients) or homography (model 2, nine) model"""

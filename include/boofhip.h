@@ -916,6 +916,50 @@ int bhip_bg_model_floats(bhip_bg* bg, long long* floats);
 int bhip_bg_fetch_model(bhip_bg* bg, int stream, float* model);
 int bhip_bg_store_model(bhip_bg* bg, int stream, const float* model);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Dense KLT optical flow: DenseOpticalFlow.process(source, destination, flow) of FactoryDenseOpticalFlow.flowKlt(PkltConfig, radius, GrayF32 | GrayU8,
+ * GrayF32 | GrayS16) (F:factory/flow/FactoryDenseOpticalFlow.java:61-82): FlowKlt_to_DenseOpticalFlow.process (F:abst/flow/FlowKlt_to_DenseOpticalFlow.java:76-86)
+ * builds FactoryPyramid.discreteGaussian(scales, -1, 2, true) of both frames and the FactoryDerivative.sobel gradient (BorderType.EXTENDED; GrayU8 ->
+ * GrayS16) of every source layer, then DenseOpticalFlowKlt.process (F:alg/flow/DenseOpticalFlowKlt.java:62-131): for every pixel (x, y) in raster order
+ * feature.setPosition(x, y), PyramidKltTracker.setDescription on the source pyramid (F:alg/tracker/klt/PyramidKltTracker.java:58-71), track on the
+ * destination pyramid (:113-151); on SUCCESS score = tracker.getError(), the pixel's slot is set to (score * 0.7f, flow = (feature.x - x, feature.y - y))
+ * and checkNeighbors offers (score, flow) to every slot of the (2*radius+1)^2 window clipped to the image: a slot takes it when its score is greater, or
+ * equal with flowX^2 + flowY^2 strictly smaller than its own.  `radius` is the template radius of the tracker and the radius of that window.  The
+ * raster-order pass is computed as a reduction per slot ("Dense KLT optical flow"); every value equals the single-threaded Java arithmetic
+ * bit for bit.  cfg == NULL: KltConfig's defaults.
+ *   flow    pixel (x, y) of pair b is the two floats (x, y) at dev_flow[b*fImageStride + y*fStride + 2*x] (strides in floats, fStride >= 2*width);
+ *           an invalid pixel (ImageFlow.D.markInvalid) is (NaN, 0)
+ *   tracks  NULL, or [batch][height][width] records {int fault; float error, dx, dy} (16 bytes, dense) of every pixel's own track: fault is a
+ *           BHIP_KLT_* value or BHIP_FLOW_NO_DESCRIPTION (setDescription returned false); error and (dx, dy) are tracker.getError() and the flow
+ *           where fault is BHIP_KLT_SUCCESS, 0 elsewhere
+ *   form    which track kernel runs: BHIP_FLOW_FORM_AUTO (lane per pixel for radius <= 3, else wave per pixel), BHIP_FLOW_FORM_LANE (radius <= 3 only),
+ *           BHIP_FLOW_FORM_WAVE (any radius); the results are the same bit for bit
+ * Validation, BHIP_ERR_INVALID and nothing is written: radius < 1, numLayers < 1, scales[0] != 1, a scale smaller than the layer below or not a multiple
+ * of it (ImagePyramidBase.checkScales, PyramidDiscrete.setScaleFactors), non-positive sizes, strides smaller than a row, an unknown form.
+ * Deviations: a pixel whose track reaches one of the positions where the reference throws (BHIP_KLT_REFERENCE_THROWS) counts as a failed track; y of
+ * an invalid pixel is 0, the result for a freshly constructed ImageFlow, where the reference keeps what the caller's ImageFlow held (a caller that has
+ * to reproduce that merges the kept y values, as the Python mirror does).
+ * Limits, BHIP_ERR_UNSUPPORTED and nothing is written: radius > 7, numLayers > 8, maxIterations < 1, batch > 65535, BHIP_FLOW_FORM_LANE with radius > 3.
+ * The _dev forms do not synchronise; scratch (pyramids, gradients, records) belongs to the context. */
+#define BHIP_FLOW_NO_DESCRIPTION 6
+#define BHIP_FLOW_FORM_AUTO 0
+#define BHIP_FLOW_FORM_LANE 1
+#define BHIP_FLOW_FORM_WAVE 2
+int bhip_flow_klt_dev_f32(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const int* scales, int numLayers, const float* dev_src, long long sImageStride,
+						  int sStride, const float* dev_dst, long long dImageStride, int dStride, int width, int height, int batch, float* dev_flow,
+						  long long fImageStride, int fStride, void* dev_tracks, int form);
+int bhip_flow_klt_dev_u8(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const int* scales, int numLayers, const uint8_t* dev_src, long long sImageStride,
+						 int sStride, const uint8_t* dev_dst, long long dImageStride, int dStride, int width, int height, int batch, float* dev_flow,
+						 long long fImageStride, int fStride, void* dev_tracks, int form);
+/* the same on one pair of host images: pixel (x, y) at src[sStart + y*sStride + x], its flow at flow[fStart + y*fStride + 2*x]; staged, run through the
+ * _dev form (BHIP_FLOW_FORM_AUTO), synchronised */
+int bhip_flow_klt_f32(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const int* scales, int numLayers, const float* src, int sStart, int sStride,
+					  const float* dst, int dStart, int dStride, int width, int height, float* flow, int fStart, int fStride);
+int bhip_flow_klt_u8(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const int* scales, int numLayers, const uint8_t* src, int sStart, int sStride,
+					 const uint8_t* dst, int dStart, int dStride, int width, int height, float* flow, int fStart, int fStride);
+/* pixels tracked and Lucas-Kanade iterations run by the last bhip_flow_klt_* call on this context (synchronises) */
+int bhip_flow_klt_stats(bhip_ctx* ctx, long long* pixels, long long* iterations);
+
 #ifdef __cplusplus
 }
 #endif
