@@ -2,7 +2,7 @@
 
 torch is used for what it is good at here -- device memory and the current stream; every operation is one call into libboofhip.so
 (hand-written HIP kernels).  A batch is a [B, H, W] float32 tensor whose last dimension is contiguous; rows may be strided (views work).
-Names follow the reference classes the host-buffer forms in boofcv_amd/api.py mirror:
+Names follow the reference classes the host-buffer forms in boofcv_amd/api/ mirror:
 
   DeviceImageOps.convolve*      ConvolveImageNoBorder / ConvolveImageNormalized      I:alg/filter/convolve/*.java
   DeviceImageOps.gaussian       BlurImageOps.gaussian                               I:alg/filter/blur/BlurImageOps.java:406-425
@@ -28,7 +28,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .api import Context, IllegalArgumentException, TemplateScoreType, _check, _NativeObject
+from .api.background import ConfigBackgroundGmm
+from .api.core import Context, IllegalArgumentException, _check, _NativeObject
+from .api.klt import KltConfig, PkltConfig, _klt_fetch
+from .api.template import TemplateScoreType
 
 INTENSITY_E, INTENSITY_ABS, INTENSITY_SQ = 0, 1, 2
 
@@ -203,7 +206,6 @@ class DeviceImageOps:
         `out`: any image / row stride with (x, y) adjacent, written in place.  tracks: None, True (allocated) or a contiguous int32 [B,H,W,4]
         tensor that receives every pixel's own track {fault, error, dx, dy} (the three floats as their bit patterns); returned second when given.
         form: BHIP_FLOW_FORM_AUTO / _LANE / _WAVE selects the track kernel (same results)."""
-        from .api import PkltConfig
         config = config or PkltConfig()
         u8 = prev.dtype == torch.uint8
         dt = torch.uint8 if u8 else torch.float32
@@ -431,7 +433,6 @@ class DeviceKltTracker(_NativeObject):
     _destroy = "bhip_klt_destroy"
 
     def __init__(self, scales, templateRadius, config=None, detectRadius=1, detectThreshold=0.0, ctx=None, detectBorder=None, device=0):
-        from .api import KltConfig
         self.ctx = ctx or Context(device, stream=torch.cuda.current_stream(device).cuda_stream)
         self.L = _lib.load()
         self.scales = [int(s) for s in scales]
@@ -510,7 +511,6 @@ class DeviceKltTracker(_NativeObject):
         return tuple(x.value for x in v)
 
     def _fetch(self, which, seq):
-        from .api import _klt_fetch
         self._need()
         ids, xy, fault, err = _klt_fetch(self.ctx, self._h, which, int(seq), self._shape[2])
         return dict(featureId=ids, xy=xy, fault=fault, error=err)
@@ -572,13 +572,12 @@ class DeviceBackgroundModel(_NativeObject):
     _destroy = "bhip_bg_destroy"
 
     def __init__(self, algorithm, config=None, dtype=torch.uint8, bands=0, ctx=None, device=0):
-        from . import api
         if algorithm not in self.ALGORITHMS:
             raise IllegalArgumentException("algorithm must be one of %s" % (self.ALGORITHMS,))
         if dtype not in (torch.uint8, torch.float32):
             raise RuntimeError("only uint8 and float32 frames are implemented on the GPU (use the Java path)")
         if config is None and algorithm == "gmm":
-            config = api.ConfigBackgroundGmm()
+            config = ConfigBackgroundGmm()
         elif config is None:
             raise IllegalArgumentException("ConfigBackgroundBasic / ConfigBackgroundGaussian: threshold has no default")
         else:

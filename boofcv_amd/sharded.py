@@ -20,7 +20,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from .api import Context, Double_MAX_VALUE, _check
+from .api.core import Context, Double_MAX_VALUE, _check
 
 RECORD_BYTES = 24  # struct ColTop {double min1, min2; int idx1, pad;}  == bhip_assoc_coltop_bytes()
 
