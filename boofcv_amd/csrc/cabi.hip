@@ -169,7 +169,7 @@ struct FhDetector {
 		constexpr bool isInt = std::is_same<T, int32_t>::value;
 		if (width != W || height != H || plannedInt != isInt) { BHIP_TRY(makePlan(ctx, width, height)); plannedInt = isInt; planExecution(); }
 		W = width; H = height; batch = batch_;
-		if (cap == 0) cap = 8192;
+		if (cap == 0) cap = BHIP_SURF_INITIAL_CAPACITY;
 		return allocate(ctx);
 	}
 	int allocate(bhip_ctx* ctx) {

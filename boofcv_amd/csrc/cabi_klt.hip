@@ -297,7 +297,7 @@ static int kltCreate(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int templateRadius,
 		BHIP_TRY(k->pyr.reserve(ctx, elems * (u8 ? 1 : 4)));
 		BHIP_TRY(k->dx.reserve(ctx, elems * (u8 ? 2 : 4)));
 		BHIP_TRY(k->dy.reserve(ctx, elems * (u8 ? 2 : 4)));
-		BHIP_TRY(k->tab.alloc(ctx, batch, 1024, numLayers, templateRadius));
+		BHIP_TRY(k->tab.alloc(ctx, batch, BHIP_KLT_INITIAL_CAPACITY, numLayers, templateRadius));
 		BHIP_TRY(bhip_launch_klt_init(ctx, k->tab.v, 0));
 		BHIP_TRY(bhip_ctx_synchronize(ctx));
 		return BHIP_OK;

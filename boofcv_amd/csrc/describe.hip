@@ -543,6 +543,9 @@ __device__ __forceinline__ bool countingSortScatter(const double (&a)[EPLT], con
 // Every test the reference makes is made here on the same set of elements; the window sum is taken as a difference of prefix sums
 // over the sorted samples instead of the reference's running add/subtract chain, so the two differ only by fp64 rounding of the
 // sums (~1e-15 relative), far inside the 1e-5 descriptor bar.  The first maximum in sweep order wins, as in the reference.
+// That rounding decides the winner when two candidate windows tie (mirror-symmetric sample sets: the quantized round-off gradients of a
+// flat GrayF32 region tie exactly).  So when two candidates lie within 1e-9 of the maximum, the lanes put the samples back (they still
+// hold them in registers) and the key point goes to the serial sweep, whose sums are the reference's own.
 // The full-circle regime (some window wraps all the way round: ramps, flat patches) is detected and left to the serial code.
 // Returns false when the caller must run the serial sweep (the arrays are then still the sorted samples).
 template <int EPLT>
@@ -717,8 +720,9 @@ __device__ __forceinline__ bool slidingWindowFast(double* dX, double* dY, const 
 	lastE = __shfl(lastE, (n - 1) / EPL, 64);  // E(n-1): one past the last end position that is ever tested
 	WSTAMP(9);
 	// ---- inclusive prefix sums of (dX, dY) in sorted order, in place: window sum(a..E) = I[E] - I[a-1]
+	double vx[EPLT], vy[EPLT];   // this lane's samples: put back into dX, dY when the sweep ends in a near tie
 	{
-		double lx[EPLT], ly[EPLT], vx[EPLT], vy[EPLT];
+		double lx[EPLT], ly[EPLT];
 #pragma unroll
 		for (int e = 0; e < EPLT; e++) {
 			vx[e] = e < cnt ? dX[p0 + e] : 0.0;
@@ -746,7 +750,7 @@ __device__ __forceinline__ bool slidingWindowFast(double* dX, double* dY, const 
 	const double totX = dX[n - 1], totY = dY[n - 1];
 	WSTAMP(10);
 	// ---- candidate windows, one per end position E in [1, E(n-1))
-	double bMag = -1.0, bX = 0, bY = 0;
+	double bMag = -1.0, bMag2 = -1.0, bX = 0, bY = 0;   // bMag2: the lane's second largest magnitude
 	int bPos = 0x7fffffff;
 	if (lane == 0) { bX = dX[0]; bY = dY[0]; bMag = bX * bX + bY * bY; bPos = 0; }
 	// Owner of end position E: a(E) = min{a : E(a) > E} = #{a <= n-2 : E(a) <= E} (E(a) never decreases; E(a) > a always, so the owner
@@ -794,7 +798,8 @@ __device__ __forceinline__ bool slidingWindowFast(double* dX, double* dY, const 
 				if (E < n) { sx = ex - ax; sy = ey - ay; }
 				else { sx = (totX - ax) + ex; sy = (totY - ay) + ey; }
 				const double mag = sx * sx + sy * sy;
-				if (mag > bMag) { bMag = mag; bX = sx; bY = sy; bPos = E; }   // E increases within a lane: strict > keeps the first
+				if (mag > bMag) { bMag2 = bMag; bMag = mag; bX = sx; bY = sy; bPos = E; }   // E increases within a lane: strict > keeps the first
+				else if (mag > bMag2) bMag2 = mag;
 			}
 		}
 	}
@@ -810,6 +815,15 @@ __device__ __forceinline__ bool slidingWindowFast(double* dX, double* dY, const 
 	const int src = __ffsll((long long)owner) - 1;
 	bestX = __shfl(bX, src, 64);
 	bestY = __shfl(bY, src, 64);
+	const double tieFloor = m - m * 1.0e-9;
+	if (__popcll(__ballot(bMag >= tieFloor)) + __popcll(__ballot(bMag2 >= tieFloor)) > 1) {   // wave-uniform
+		waveSync();
+#pragma unroll
+		for (int e = 0; e < EPLT; e++)
+			if (e < cnt) { dX[p0 + e] = vx[e]; dY[p0 + e] = vy[e]; }
+		waveSync();
+		return false;
+	}
 	WSTAMP(12);
 	return true;
 #undef WSTAMP

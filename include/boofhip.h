@@ -145,6 +145,7 @@ int bhip_profile_report(bhip_ctx* ctx, char* out, int cap);
 /* ---- detect + describe: FactoryDetectDescribe.surfStable / surfFast -> DetectDescribePoint<GrayF32,BrightFeature>
  *      (F:factory/feature/detdesc/FactoryDetectDescribe.java:118-135,209-226; F:abst/feature/detdesc/DetectDescribePoint.java:32-46;
  *       F:abst/feature/detdesc/WrapDetectDescribeSurf.java:93-159).  NULL config = reference defaults. ---- */
+#define BHIP_SURF_INITIAL_CAPACITY 8192   /* key-point lists start at this many entries per image and regrow; results do not depend on it */
 int bhip_surf_create(bhip_ctx* ctx, const bhip_fh_cfg* fh, const bhip_surf_cfg* surf, const bhip_ori_cfg* ori, int stable, bhip_surf** out);
 int bhip_surf_destroy(bhip_surf* s);
 /* detect(T input) on a batch of host images (batch = 1 is the reference call).  Results are recycled by the next detect,
@@ -713,6 +714,7 @@ int bhip_brief_dev_f32(bhip_ctx* ctx, const float* dev_img, long long imageStrid
  *      bhip_klt_add_tracks has featureId -1 (the reference leaves whatever the recycled PointTrack held); a track that process() drops after a
  *      successful track() (centre outside the frame, or setDescription false) keeps fault BHIP_KLT_SUCCESS.  templateRadius 1..7, numLayers 1..8,
  *      maxIterations >= 1, otherwise BHIP_ERR_UNSUPPORTED. ---- */
+#define BHIP_KLT_INITIAL_CAPACITY 1024   /* track lists start at this many entries per sequence and regrow; results do not depend on it */
 int bhip_klt_create(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int templateRadius, const int* scales, int numLayers, int detectRadius, float detectThreshold,
 					int detectBorder, int width, int height, int batch, bhip_klt** out);
 int bhip_klt_destroy(bhip_klt* k);

@@ -180,8 +180,9 @@ def test_config5_4k_device_chain(api, orc):
 @pytest.mark.parametrize("B,route", [(256, "device"), (130, "host")])
 def test_config2_full_batch_every_frame(api, orc, B, route):
     """BASELINE config 2 at batch size: 256 device-resident 1920x1080 S-blobs frames through bhip_surf_detect_dev_f32 (the bench path: fused
-    integral kernel, capacity regrow, tile-ordered / XCD-chunked describe over ~550 k key points) and 130 host frames through
-    bhip_surf_detect_f32.  EVERY frame's key points are compared with the oracle bit for bit (count, order, location, scale, Laplacian
+    integral kernel, tile-ordered / XCD-chunked describe over ~550 k key points) and 130 host frames through
+    bhip_surf_detect_f32.  (These frames have about 2150 key points each, far below BHIP_SURF_INITIAL_CAPACITY: the key-point list never
+    regrows here; tests/test_gpu_surf_regrow.py covers that.)  EVERY frame's key points are compared with the oracle bit for bit (count, order, location, scale, Laplacian
     sign); descriptors and orientations of every 8th frame against the 1e-5 / 1e-12 bars with no exception list."""
     torch = pytest.importorskip("torch")
     import sys
