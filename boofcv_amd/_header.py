@@ -1,7 +1,7 @@
 """include/boofhip.h read as data: the one description of the C ABI that the ctypes binding (_lib.py) and the JNI generator
 (scripts/gen_jni.py) are both derived from.  Pure text processing: no ctypes, no JNI names.
 
-    parse(text) -> Header(functions, structs, constants)
+    parse(text) -> Header(functions, structs, constants, tagged)
     classify(ctype, pname) -> (kind, element type, is_const)
     load() -> parse() of HEADER, cached
 """
@@ -17,8 +17,9 @@ ELEMENTS = ("float", "double", "uint8_t", "int", "int32_t", "int16_t", "long lon
 _COMMENT = re.compile(r"/\*.*?\*/", re.S)
 _FUNCTION = re.compile(r"^[ \t]*(int|void|const char\*)\s+(bhip_\w+)\s*\(([^;{}()]*)\)\s*;", re.M)
 
-# functions: [(ret, name, [(ctype, pname)])] in header order; structs: {bhip_*_cfg: [(ctype, field)]}; constants: {BHIP_*: int}
-Header = collections.namedtuple("Header", "functions structs constants")
+# functions: [(ret, name, [(ctype, pname)])] in header order; structs: {bhip_*_cfg: [(ctype, field)]}, the anonymous `typedef struct { } name;`
+# ones; tagged: the same for `typedef struct name { } name;`; constants: {BHIP_*: int}
+Header = collections.namedtuple("Header", "functions structs constants tagged")
 
 
 def _declarator(text):
@@ -77,6 +78,9 @@ def parse(text):
     structs = {}
     for m in re.finditer(r"typedef\s+struct\s*\{([^{}]*)\}\s*(bhip_\w+_cfg)\s*;", text):
         structs[m.group(2)] = [_declarator(f) for f in m.group(1).split(";") if f.strip()]
+    tagged = {}
+    for m in re.finditer(r"typedef\s+struct\s+(bhip_\w+_cfg)\s*\{([^{}]*)\}\s*\1\s*;", text):
+        tagged[m.group(1)] = [_declarator(f) for f in m.group(2).split(";") if f.strip()]
     constants = {}
     for m in re.finditer(r"typedef\s+enum\s*\{([^{}]*)\}\s*\w+\s*;", text):
         value = -1
@@ -90,7 +94,7 @@ def parse(text):
             constants[m.group(1)] = int(m.group(2), 0)
         except ValueError:
             pass   # not an integer constant
-    return Header(functions, structs, constants)
+    return Header(functions, structs, constants, tagged)
 
 
 _cached = None

@@ -234,16 +234,20 @@ class Kernel2D_F32:
 
 
 class BlurImageOps:
+    """GrayF32, and for mean / gaussian GrayU8 as well (the blurs of the local thresholds)"""
+
     @staticmethod
     def mean(input, output, radiusX, radiusY=None, storage=None, ctx=None):
-        """BOverrideBlurImageOps.mean target (I:alg/filter/blur/BlurImageOps.java:343-376)"""
+        """BOverrideBlurImageOps.mean target (I:alg/filter/blur/BlurImageOps.java:343-376; GrayU8 :75-92)"""
         ctx = _ctx(ctx)
         radiusY = radiusX if radiusY is None else radiusY
         if radiusX <= 0 or radiusY <= 0:
             raise IllegalArgumentException("Radius must be > 0")
+        u8 = isinstance(input, GrayU8)
         if output is None:
-            output = GrayF32(input.width, input.height)
-        _check(ctx, _lib.load().bhip_mean_f32(ctx._h, *input._in(), int(radiusX), int(radiusY), *output._out()))
+            output = type(input)(input.width, input.height) if u8 else GrayF32(input.width, input.height)
+        fn = _lib.load().bhip_mean_u8 if u8 else _lib.load().bhip_mean_f32
+        _check(ctx, fn(ctx._h, *input._in(), int(radiusX), int(radiusY), *output._out()))
         return output
 
     @staticmethod
@@ -259,8 +263,17 @@ class BlurImageOps:
 
     @staticmethod
     def gaussian(input, output, sigma, radius, storage=None, ctx=None):
-        """BOverrideBlurImageOps.gaussian target (I:alg/filter/blur/BlurImageOps.java:406-425)"""
+        """BOverrideBlurImageOps.gaussian target (I:alg/filter/blur/BlurImageOps.java:406-425; GrayU8 :122-141 with sigma <= 0: the kernel of the radius)"""
         ctx = _ctx(ctx)
+        if isinstance(input, GrayU8):
+            if sigma > 0:
+                raise IllegalArgumentException("the GrayU8 Gaussian blur on the GPU takes its kernel from the radius (sigma <= 0)")
+            if radius <= 0:
+                raise IllegalArgumentException("Sigma must be > 0")
+            if output is None:
+                output = GrayU8(input.width, input.height)
+            _check(ctx, _lib.load().bhip_gaussian_u8(ctx._h, *input._in(), int(radius), *output._out()))
+            return output
         if output is None:
             output = GrayF32(input.width, input.height)
         _check(ctx, _lib.load().bhip_gaussian_f32(ctx._h, *input._in(), float(sigma), int(radius), *output._out()))

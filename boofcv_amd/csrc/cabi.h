@@ -22,8 +22,10 @@
 // host export calls can overwrite what it staged.
 struct CtxScratch {
 	DevBuf in0, in1, out0, out1, tmp0, tmp1;                                 // staging
-	DevBuf work, assocCol, nmsBitmap, nmsPrefix, nmsPos, ipTmp, ipKernel, fast, disparity, distortMap, templ, flow;   // device side
+	DevBuf work, assocCol, nmsBitmap, nmsPrefix, nmsPos, ipTmp, ipKernel, fast, disparity, distortMap, templ, flow, threshold;   // device side
 	long long flowPixels = 0;   // pixels of the last bhip_flow_klt_* call (bhip_flow_klt_stats)
+	DevBuf thresholdTaps;           // the Kernel1D_S32 Gaussian taps of the GrayU8 blurs, for thresholdTapsRadius (0: none yet)
+	int thresholdTapsRadius = 0;
 	AssocMfmaWork mfma;
 	int assocExactOnly = -1;  // BHIP_ASSOC_EXACT=1 forces the exact VALU association kernels (parity cross-check)
 };
@@ -202,5 +204,7 @@ template <class T>
 int pyramidImpl(bhip_ctx* ctx, const typename PyrTraits<T>::Kernel* kernel, int kw, const int* scales, int n, DevImg<const T> in, T* out,
 				bool layer0Present = false);
 bool briefPatchOk(const int32_t* samplePoints, int nSamples, int radius);
+// cabi_ip.hip; the GrayF32 local thresholds (cabi_threshold.hip) blur with them
+int gaussianImpl(bhip_ctx* ctx, double sigma, int radius, DevImg<const float> in, DevImg<float> out);
 
 #pragma GCC visibility pop

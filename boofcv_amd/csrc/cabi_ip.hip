@@ -9,7 +9,7 @@
 #include "cabi.h"
 
 // BlurImageOps.gaussian: one fused pass, or a horizontal pass into the library's `storage` and a vertical pass into `out`
-static int gaussianImpl(bhip_ctx* ctx, double sigma, int radius, DevImg<const float> in, DevImg<float> out) {
+int gaussianImpl(bhip_ctx* ctx, double sigma, int radius, DevImg<const float> in, DevImg<float> out) {
 	std::vector<float> k = bhip_gaussian1d_f32(sigma, radius);
 	const int kw = (int)k.size(), koff = kw / 2;
 	bool fused = false;

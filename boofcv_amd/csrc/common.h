@@ -364,9 +364,9 @@ int bhip_launch_brief(bhip_ctx* ctx, DevImg<const float> img, int radius, int nu
 					  int* out, const int* start, int maxCount, int xyStride, long long xyImageStride, bool patchOk);
 int bhip_launch_brief(bhip_ctx* ctx, DevImg<const uint8_t> img, int radius, int numPoints, const int* samplePoints, const int* compare, const double* xy, int n,
 					  int* out, const int* start, int maxCount, int xyStride, long long xyImageStride, bool patchOk);
+int bhip_launch_mean(bhip_ctx* ctx, bool vertical, DevImg<const float> in, DevImg<float> out, int radius);   // one direction of the mean blur, batched
 // single images (batch 1)
 int bhip_launch_conv2d(bhip_ctx* ctx, const float* kernel, int kw, int koff, DevImg<const float> in, DevImg<float> out);
-int bhip_launch_mean(bhip_ctx* ctx, bool vertical, DevImg<const float> in, DevImg<float> out, int radius);   // one direction of the mean blur
 int bhip_launch_median(bhip_ctx* ctx, DevImg<const float> in, DevImg<float> out, int radius);
 int bhip_launch_integral_u8(bhip_ctx* ctx, DevImg<const uint8_t> in, DevImg<int32_t> out);   // IntegralImageOps.transform(GrayU8, GrayS32)
 // stand-alone strict block NMS over a batch (detect.hip): bitmap of accepted blocks + the pixel's position inside its block
@@ -542,3 +542,30 @@ int bhip_launch_flow_track_lane(bhip_ctx* ctx, KltPyr P, const float* dst, int r
 int bhip_launch_flow_track_lane(bhip_ctx* ctx, KltPyrU8 P, const uint8_t* dst, int r, bhip_klt_cfg cfg, int batch, FlowRec* rec, unsigned long long* stats);
 // checkNeighbors as an order-free reduction: flow[b][y][x] = (x, y) floats at flow.data + b * imageStride + y * stride + 2 * x (strides in floats)
 int bhip_launch_flow_reduce(bhip_ctx* ctx, const FlowRec* rec, int r, DevImg<float> flow);
+
+// ---------------- thresholding, FactoryThresholdBinary, and the GrayU8 blurs (threshold.hip) ----------------
+#define BHIP_THRESH_FUSED_MAX_RADIUS 16   // blur radius up to which a GrayU8 local threshold (and blur) runs as one launch out of LDS
+// the compare of a pixel with its threshold: px <= thr (down), px > thr (up: fixed, local, min/max), !(px <= thr) (up: block mean, Otsu; differs on NaN)
+enum { BHIP_CMP_LE = 0, BHIP_CMP_GT = 1, BHIP_CMP_NOT_LE = 2 };
+// thr: the int or float threshold; imageThr != nullptr: one int threshold per image in device memory instead (GrayU8)
+int bhip_launch_threshold_global(bhip_ctx* ctx, DevImg<const uint8_t> in, DevImg<uint8_t> out, int thr, const int* imageThr, int mode);
+int bhip_launch_threshold_global(bhip_ctx* ctx, DevImg<const float> in, DevImg<uint8_t> out, float thr, const int* imageThr, int mode);
+int bhip_launch_hist_u8(bhip_ctx* ctx, DevImg<const uint8_t> in, int* hist);   // hist[batch][256] += counts (zeroed by the caller)
+int bhip_launch_otsu_global(bhip_ctx* ctx, const int* hist, int batch, int totalPixels, double scale, int* thr);
+template <class T>
+int bhip_launch_local_compare(bhip_ctx* ctx, DevImg<const T> in, DevImg<const T> blur, DevImg<uint8_t> out, float scale, bool down);
+// one direction of BlurImageOps.mean / gaussian on GrayU8; devTaps: 2*radius+1 Kernel1D_S32 taps in device memory, nullptr = the mean
+int bhip_launch_blur_u8_pass(bhip_ctx* ctx, bool vertical, const int32_t* devTaps, int radius, DevImg<const uint8_t> in, DevImg<uint8_t> out);
+// both directions, radius <= BHIP_THRESH_FUSED_MAX_RADIUS; hostTaps: the taps in host memory (nullptr = the mean); compare: `out` is the local
+// threshold's 0/1 image instead of the blurred one
+int bhip_launch_blur_u8_fused(bhip_ctx* ctx, const int32_t* hostTaps, int radius, DevImg<const uint8_t> in, DevImg<uint8_t> out, bool compare, float scale, bool down);
+struct ThreshBlocks {
+	int kind;                // BHIP_THRESHOLD_BLOCK_MIN_MAX / _MEAN / _OTSU
+	int bw, bh, nbx, nby;    // ThresholdBlock.selectBlockSize and the stats grid
+	int local, down, useOtsu2;
+	double scale, minimumSpread, tuning;
+};
+size_t bhip_block_threshold_scratch(int kind, int nbx, int nby, int images);
+// `chunk` images go through the three stages at a time; scratch: bhip_block_threshold_scratch(kind, nbx, nby, chunk) bytes
+template <class T>
+int bhip_launch_block_threshold(bhip_ctx* ctx, const ThreshBlocks& c, DevImg<const T> in, DevImg<uint8_t> out, void* scratch, int chunk);

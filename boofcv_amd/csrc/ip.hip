@@ -1802,13 +1802,14 @@ int bhip_launch_conv2d(bhip_ctx* ctx, const float* kernel, int kw, int koff, Dev
 //   interior: float running sums, total / divisor   I:alg/filter/convolve/noborder/ImplConvolveMean.java:281-357 (single-threaded order)
 //   border: ConvolveNormalized_JustBorder_SB with the table kernel (k_conv mode 3)
 // As in the corner intensity, a row (then a column) is one sequential chain; one thread each.
-__global__ __launch_bounds__(64) void k_mean_rows(const float* __restrict__ in, int inStride, float* __restrict__ out, int outStride, int width, int height, int radius) {
+__global__ __launch_bounds__(64) void k_mean_rows(const float* __restrict__ in, long long inImageStride, int inStride, float* __restrict__ out,
+												  long long outImageStride, int outStride, int width, int height, int radius) {
 	const int y = blockIdx.x * blockDim.x + threadIdx.x;
 	if (y >= height) return;
 	const int kw = 2 * radius + 1;
 	const float divisor = (float)kw;
-	const float* r = in + (long long)y * inStride;
-	float* o = out + (long long)y * outStride;
+	const float* r = in + (long long)blockIdx.z * inImageStride + (long long)y * inStride;
+	float* o = out + (long long)blockIdx.z * outImageStride + (long long)y * outStride;
 	float total = 0;
 	for (int i = 0; i < kw; i++) total += r[i];
 	o[radius] = total / divisor;
@@ -1828,9 +1829,12 @@ __global__ __launch_bounds__(64) void k_mean_rows(const float* __restrict__ in, 
 		o[i - radius] = total / divisor;
 	}
 }
-__global__ __launch_bounds__(256) void k_mean_cols(const float* __restrict__ in, int inStride, float* __restrict__ out, int outStride, int width, int height, int radius) {
+__global__ __launch_bounds__(256) void k_mean_cols(const float* __restrict__ in, long long inImageStride, int inStride, float* __restrict__ out,
+												   long long outImageStride, int outStride, int width, int height, int radius) {
 	const int x = blockIdx.x * blockDim.x + threadIdx.x;
 	if (x >= width) return;
+	in += (long long)blockIdx.z * inImageStride;
+	out += (long long)blockIdx.z * outImageStride;
 	const int kw = 2 * radius + 1;
 	const float divisor = (float)kw;
 	float total = 0;
@@ -1854,7 +1858,7 @@ __global__ __launch_bounds__(256) void k_mean_cols(const float* __restrict__ in,
 		out[(long long)y * outStride + x] = total / divisor;
 	}
 }
-// one direction of the mean blur: in / out of the same shape
+// one direction of the mean blur: in / out of the same shape, every image of the batch
 int bhip_launch_mean(bhip_ctx* ctx, bool vertical, DevImg<const float> in, DevImg<float> out, int radius) {
 	const int width = in.width, height = in.height;
 	const int kw = 2 * radius + 1;
@@ -1868,16 +1872,20 @@ int bhip_launch_mean(bhip_ctx* ctx, bool vertical, DevImg<const float> in, DevIm
 	{
 		ConvParams P;
 		P.in = in.data; P.out = out.data; P.inStride = in.stride; P.outStride = out.stride; P.width = width; P.height = height; P.kw = kw; P.koff = radius;
-		P.inImageStride = 0; P.outImageStride = 0; P.borderOnly = 0;
+		P.inImageStride = in.imageStride; P.outImageStride = out.imageStride; P.borderOnly = 0;
 		for (int i = 0; i < kw; i++) P.k[i] = ker[i];
 		P.unrolled = 0; P.mode = 3;
-		dim3 grid((width + 255) / 256, height);
+		dim3 grid((width + 255) / 256, height, in.batch);
 		if (vertical) hipLaunchKernelGGL(k_conv<true>, grid, dim3(256), 0, ctx->stream, P);
 		else hipLaunchKernelGGL(k_conv<false>, grid, dim3(256), 0, ctx->stream, P);
 	}
-	ProfScope prof(ctx, vertical ? "k_mean_cols" : "k_mean_rows", 8.0 * width * height);
-	if (vertical) hipLaunchKernelGGL(k_mean_cols, dim3((width + 255) / 256), dim3(256), 0, ctx->stream, in.data, in.stride, out.data, out.stride, width, height, radius);
-	else hipLaunchKernelGGL(k_mean_rows, dim3((height + 63) / 64), dim3(64), 0, ctx->stream, in.data, in.stride, out.data, out.stride, width, height, radius);
+	ProfScope prof(ctx, vertical ? "k_mean_cols" : "k_mean_rows", 8.0 * width * height * in.batch);
+	if (vertical)
+		hipLaunchKernelGGL(k_mean_cols, dim3((width + 255) / 256, 1, in.batch), dim3(256), 0, ctx->stream, in.data, in.imageStride, in.stride, out.data, out.imageStride,
+						   out.stride, width, height, radius);
+	else
+		hipLaunchKernelGGL(k_mean_rows, dim3((height + 63) / 64, 1, in.batch), dim3(64), 0, ctx->stream, in.data, in.imageStride, in.stride, out.data, out.imageStride,
+						   out.stride, width, height, radius);
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
 }

@@ -18,6 +18,8 @@ Names follow the reference classes the host-buffer forms in boofcv_amd/api/ mirr
   DeviceImageOps.pyramid        PyramidDiscreteSampleBlur.process                   I:alg/transform/pyramid/PyramidDiscreteSampleBlur.java:88-118
   DeviceImageOps.cornerIntensity  GradientCornerIntensity.process                   F:alg/feature/detect/intensity/impl/ImplSsdCorner_F32.java:62-196
   DeviceImageOps.denseFlowKlt   DenseOpticalFlow.process (flowKlt, GrayF32 / GrayU8)  F:factory/flow/FactoryDenseOpticalFlow.java:61-82
+  DeviceImageOps.threshold      InputToBinary.process (FactoryThresholdBinary.threshold)  I:factory/filter/binary/FactoryThresholdBinary.java:318-372
+  DeviceImageOps.meanU8 / gaussianU8  BlurImageOps.mean / gaussian on GrayU8           I:alg/filter/blur/BlurImageOps.java:75-141
   DeviceImageOps.brief          DescribePointBrief.process                          F:alg/feature/describe/DescribePointBrief.java:73-89
   DeviceKltTracker              PointTrackerKltPyramid, batched over sequences      main/boofcv-geo/.../abst/feature/tracker/PointTrackerKltPyramid.java:139-348
   DeviceBackgroundModel         BackgroundStationaryBasic / Gaussian / Gmm, batched over streams   F:alg/background/stationary/*.java
@@ -88,6 +90,41 @@ class DeviceImageOps:
         ip, iis, irs, W, H, B = _geom(src)
         op, ois, ors, _, _, _ = _geom(out)
         _check(self.ctx, self.L.bhip_gaussian_dev_f32(self.ctx._h, ip, iis, irs, W, H, B, float(sigma), int(radius), op, ois, ors))
+        return out
+
+    def _u8_out(self, src, out, B, H, W):
+        if out is None:
+            out = torch.empty((B, H, W), dtype=torch.uint8, device=src.device)
+        op, ois, ors, W2, H2, B2 = _geom(out, torch.uint8)
+        if (W, H, B) != (W2, H2, B2):
+            raise IllegalArgumentException("input and output shapes differ")
+        return out, op, ois, ors
+
+    def threshold(self, src, config, out=None):
+        """InputToBinary.process of FactoryThresholdBinary.threshold(config, GrayU8 | GrayF32) on uint8 or float32 frames [B,H,W] of any row / image
+        stride -> the uint8 0/1 images [B,H,W] (`out`, any stride, is written in place and as a whole).  config: a binary.ConfigThreshold; the
+        types and image types binary.InputToBinary refuses are refused here too.  No host synchronisation."""
+        from . import binary
+        u8 = src.dtype == torch.uint8
+        binary.InputToBinary(config, binary.GrayU8 if u8 else binary.GrayF32)   # the refusals
+        ip, iis, irs, W, H, B = _geom(src, torch.uint8 if u8 else torch.float32)
+        out, op, ois, ors = self._u8_out(src, out, B, H, W)
+        fn = self.L.bhip_threshold_dev_u8 if u8 else self.L.bhip_threshold_dev_f32
+        _check(self.ctx, fn(self.ctx._h, C.byref(config._c()), ip, iis, irs, W, H, B, op, ois, ors))
+        return out
+
+    def meanU8(self, src, radiusX, radiusY=None, out=None):
+        """BlurImageOps.mean on uint8 frames [B,H,W]"""
+        ip, iis, irs, W, H, B = _geom(src, torch.uint8)
+        out, op, ois, ors = self._u8_out(src, out, B, H, W)
+        _check(self.ctx, self.L.bhip_mean_dev_u8(self.ctx._h, ip, iis, irs, W, H, B, int(radiusX), int(radiusX if radiusY is None else radiusY), op, ois, ors))
+        return out
+
+    def gaussianU8(self, src, radius, out=None):
+        """BlurImageOps.gaussian(GrayU8, -1, radius) on uint8 frames [B,H,W]"""
+        ip, iis, irs, W, H, B = _geom(src, torch.uint8)
+        out, op, ois, ors = self._u8_out(src, out, B, H, W)
+        _check(self.ctx, self.L.bhip_gaussian_dev_u8(self.ctx._h, ip, iis, irs, W, H, B, int(radius), op, ois, ors))
         return out
 
     def _grad(self, fn, src, border, dx, dy):

@@ -962,6 +962,84 @@ int bhip_flow_klt_u8(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const i
 /* pixels tracked and Lucas-Kanade iterations run by the last bhip_flow_klt_* call on this context (synchronises) */
 int bhip_flow_klt_stats(bhip_ctx* ctx, long long* pixels, long long* iterations);
 
+/* ---- thresholding: FactoryThresholdBinary.threshold(ConfigThreshold, GrayU8 | GrayF32) -> InputToBinary.process (threshold.hip),
+ *      I:factory/filter/binary/FactoryThresholdBinary.java:318-372; the provider seam is I:factory/filter/binary/BOverrideFactoryThresholdBinary.java.
+ *      The output is the GrayU8 0/1 image, bit for bit the single-threaded Java result.
+ *   FIXED           GlobalFixedBinaryFilter -> ImplThresholdImageOps.threshold (I:alg/filter/binary/impl/ImplThresholdImageOps.java:46-134); GrayU8
+ *                   compares with (int)fixedThreshold, GrayF32 with (float)fixedThreshold
+ *   GLOBAL_OTSU     GrayU8 with minPixelValue 0 and maxPixelValue 255: GlobalBinaryFilter.process (I:abst/filter/binary/GlobalBinaryFilter.java:57-88)
+ *                   on GThresholdImageOps.computeOtsu (I:alg/filter/binary/GThresholdImageOps.java:56-142), histogram and threshold on the device
+ *   LOCAL_MEAN      ImplThresholdImageOps.localMean (:226-270 GrayU8, :424-468 GrayF32) on BlurImageOps.mean
+ *   LOCAL_GAUSSIAN  ImplThresholdImageOps.localGaussian (:272-323, :470-520) on BlurImageOps.gaussian(.., -1, radius, ..)
+ *   BLOCK_MIN_MAX   ThresholdBlock (I:alg/filter/binary/ThresholdBlock.java:90-170) with impl/ThresholdBlockMinMax_U8 / _F32
+ *   BLOCK_MEAN      ThresholdBlock with impl/ThresholdBlockMean_U8 / _F32 (GrayF32: the block sum runs in raster order, as there)
+ *   BLOCK_OTSU      GrayU8: ThresholdBlockOtsu.java:73-145 with ComputeOtsu.java:71-170 (useOtsu2, tuning, scale)
+ * The local radius is ConfigLength.computeI(min(width, height)) / 2 (T:struct/ConfigLength.java:74-84), the requested block width computeI of the same.
+ * BHIP_ERR_UNSUPPORTED and nothing is written: GLOBAL_ENTROPY, GLOBAL_LI, GLOBAL_HUANG, LOCAL_OTSU, LOCAL_SAVOLA, LOCAL_NICK; GLOBAL_OTSU and
+ * BLOCK_OTSU on GrayF32 (InputToBinarySwitch's conversion in the reference); GLOBAL_OTSU with another pixel range; a GrayF32 local threshold
+ * whose blur kernel is wider than 255 taps (the limit of bhip_mean_f32 / bhip_gaussian_f32).
+ * BHIP_ERR_INVALID and nothing is written, where the reference throws: an unknown type, a local radius <= 0, a requested block width <= 0,
+ * empty images, strides smaller than a row.
+ * Fields mirror ConfigThreshold (I:factory/filter/binary/ConfigThreshold.java:30-86), ConfigThresholdBlockMinMax and ConfigThresholdLocalOtsu;
+ * widthLength / widthFraction are ConfigLength.length / fraction (fraction < 0: a fixed length). */
+#define BHIP_THRESHOLD_FIXED 0 /* ThresholdType ordinals (I:factory/filter/binary/ThresholdType.java:28-109) */
+#define BHIP_THRESHOLD_GLOBAL_ENTROPY 1
+#define BHIP_THRESHOLD_GLOBAL_OTSU 2
+#define BHIP_THRESHOLD_GLOBAL_LI 3
+#define BHIP_THRESHOLD_GLOBAL_HUANG 4
+#define BHIP_THRESHOLD_LOCAL_GAUSSIAN 5
+#define BHIP_THRESHOLD_LOCAL_MEAN 6
+#define BHIP_THRESHOLD_LOCAL_OTSU 7
+#define BHIP_THRESHOLD_BLOCK_MIN_MAX 8
+#define BHIP_THRESHOLD_BLOCK_MEAN 9
+#define BHIP_THRESHOLD_BLOCK_OTSU 10
+#define BHIP_THRESHOLD_LOCAL_SAVOLA 11
+#define BHIP_THRESHOLD_LOCAL_NICK 12
+typedef struct bhip_threshold_cfg {
+	int type;                     /* BHIP_THRESHOLD_* */
+	double fixedThreshold;        /* FIXED */
+	double scale;                 /* 1.0; 0.95 for the local and block types (ConfigThreshold.local) */
+	int down;                     /* 1 */
+	double widthLength;           /* 11 */
+	double widthFraction;         /* -1 */
+	int minPixelValue;            /* 0 */
+	int maxPixelValue;            /* 255 */
+	int thresholdFromLocalBlocks; /* 1 */
+	double minimumSpread;         /* 10 (ConfigThresholdBlockMinMax) */
+	int useOtsu2;                 /* 1 (ConfigThresholdLocalOtsu) */
+	double tuning;                /* 0 */
+} bhip_threshold_cfg;
+/* ConfigThreshold.fixed(0) / global(type) / local(type, 11) (ConfigThreshold.java:88-133); BHIP_ERR_INVALID for a type outside the list */
+int bhip_threshold_cfg_default(int type, bhip_threshold_cfg* cfg);
+/* ThresholdBlock.selectBlockSize (ThresholdBlock.java:112-127); the stats grid is (width / blockWidth) x (height / blockHeight) and the last
+ * block of a direction takes the remainder.  BHIP_ERR_INVALID: non-positive sizes or requestedWidth.  Host only. */
+int bhip_threshold_block_size(int width, int height, int requestedWidth, int* blockWidth, int* blockHeight);
+/* batch images at dev_in + b*inImageStride -> dev_out + b*outImageStride (strides in elements, any alignment).  The whole width x height view of
+ * every output image is written and nothing outside it.  Asynchronous on the context's stream, no host synchronisation; scratch belongs to the
+ * context.  GrayU8 local thresholds run as one launch out of LDS up to radius 16, beyond it (and for kernels wider than the image) as two blur
+ * passes and a compare. */
+int bhip_threshold_dev_u8(bhip_ctx* ctx, const bhip_threshold_cfg* cfg, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height,
+						  int batch, uint8_t* dev_out, long long outImageStride, int outStride);
+int bhip_threshold_dev_f32(bhip_ctx* ctx, const bhip_threshold_cfg* cfg, const float* dev_in, long long inImageStride, int inStride, int width, int height,
+						   int batch, uint8_t* dev_out, long long outImageStride, int outStride);
+/* the same on one host image view: staged, run through the _dev form, synchronised */
+int bhip_threshold_u8(bhip_ctx* ctx, const bhip_threshold_cfg* cfg, const uint8_t* in, int inStart, int inStride, int width, int height, uint8_t* out,
+					  int outStart, int outStride);
+int bhip_threshold_f32(bhip_ctx* ctx, const bhip_threshold_cfg* cfg, const float* in, int inStart, int inStride, int width, int height, uint8_t* out,
+					   int outStart, int outStride);
+/* BOverrideBlurImageOps.mean / gaussian targets for GrayU8: BlurImageOps.mean(GrayU8, .., radiusX, radiusY, ..) (I:alg/filter/blur/BlurImageOps.java:75-92:
+ * ConvolveImageMean.horizontal then .vertical with a GrayU8 image between them, I:alg/filter/convolve/ConvolveImageMean.java:168-215) and
+ * BlurImageOps.gaussian(GrayU8, .., -1, radius, ..) (:122-141: the Kernel1D_S32 of bhip_gaussian_kernel1d_s32 through
+ * ConvolveImageNormalized.horizontal / vertical).  Every pixel is (total + weight/2) / weight over the taps inside the image, any radius >= 1;
+ * BHIP_ERR_INVALID for a radius <= 0 ("Radius must be > 0").  The _dev forms are batched and do not synchronise. */
+int bhip_mean_u8(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, int radiusX, int radiusY, uint8_t* out, int outStart,
+				 int outStride);
+int bhip_gaussian_u8(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, int radius, uint8_t* out, int outStart, int outStride);
+int bhip_mean_dev_u8(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, int radiusX, int radiusY,
+					 uint8_t* dev_out, long long outImageStride, int outStride);
+int bhip_gaussian_dev_u8(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, int radius,
+						 uint8_t* dev_out, long long outImageStride, int outStride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,21 +2,28 @@ package boofcv.hip;
 
 import boofcv.abst.feature.detect.extract.ConfigExtract;
 import boofcv.abst.feature.detect.extract.NonMaxSuppression;
+import boofcv.abst.filter.binary.InputToBinary;
 import boofcv.alg.filter.blur.BOverrideBlurImageOps;
 import boofcv.alg.filter.convolve.BOverrideConvolveImage;
 import boofcv.alg.filter.convolve.BOverrideConvolveImageNormalized;
 import boofcv.alg.filter.convolve.border.ConvolveJustBorder_General_SB;
 import boofcv.core.image.border.ImageBorder_F32;
 import boofcv.factory.feature.detect.extract.BOverrideFactoryFeatureExtractor;
+import boofcv.factory.filter.binary.BOverrideFactoryThresholdBinary;
+import boofcv.struct.ConfigLength;
 import boofcv.struct.QueueCorner;
 import boofcv.struct.convolve.Kernel1D_F32;
 import boofcv.struct.convolve.Kernel2D_F32;
 import boofcv.struct.image.GrayF32;
+import boofcv.struct.image.GrayU8;
+import boofcv.struct.image.ImageGray;
 
 /**
  * Installs every BOverride hook the library implements (I:override/BOverrideManager.java:33-39 lists the hook classes).  A hook that throws
  * RuntimeException means "not handled, run the Java code" (BOverrideConvolveImage.java:53-62), which is what BoofHip.check does for any
- * non-zero status and what the type guards below do for images / kernels other than GrayF32 / Kernel*_F32.
+ * non-zero status and what the type guards below do for images / kernels other than GrayF32 / Kernel*_F32 (the blurs also take GrayU8).
+ * The hooks of BOverrideFactoryThresholdBinary have no such answer: they return an InputToBinary, the device's or the Java one
+ * (FactoryThresholdBinaryHip).
  */
 public final class BoofHipOverrides {
 	private BoofHipOverrides() {}
@@ -64,6 +71,12 @@ public final class BoofHipOverrides {
 		};
 		// BlurImageOps.mean / median / gaussian (BOverrideBlurImageOps.java:36-50)
 		BOverrideBlurImageOps.mean = (input, output, radiusX, radiusY, storage) -> {
+			if (input instanceof GrayU8) {   // BlurImageOps.mean(GrayU8): both passes round to bytes
+				GrayU8 in = (GrayU8)input, out = (GrayU8)output;
+				long ctx = BoofHipContext.get();
+				BoofHip.check(ctx, BoofHip.meanU8(ctx, in.data, in.startIndex, in.stride, in.width, in.height, radiusX, radiusY, out.data, out.startIndex, out.stride));
+				return;
+			}
 			if (!(input instanceof GrayF32)) throw declined();
 			GrayF32 in = (GrayF32)input, out = (GrayF32)output;
 			long ctx = BoofHipContext.get();
@@ -76,6 +89,13 @@ public final class BoofHipOverrides {
 			BoofHip.check(ctx, BoofHip.medianF32(ctx, in.data, in.startIndex, in.stride, in.width, in.height, radius, out.data, out.startIndex, out.stride));
 		};
 		BOverrideBlurImageOps.gaussian = (input, output, sigmaX, radiusX, sigmaY, radiusY, storage) -> {
+			if (input instanceof GrayU8) {   // the C ABI has the kernel FactoryKernelGaussian derives from the radius (sigma <= 0)
+				if (sigmaX > 0 || sigmaY > 0 || radiusX != radiusY || radiusX <= 0) throw declined();
+				GrayU8 in = (GrayU8)input, out = (GrayU8)output;
+				long ctx = BoofHipContext.get();
+				BoofHip.check(ctx, BoofHip.gaussianU8(ctx, in.data, in.startIndex, in.stride, in.width, in.height, radiusX, out.data, out.startIndex, out.stride));
+				return;
+			}
 			if (!(input instanceof GrayF32) || sigmaX != sigmaY || radiusX != radiusY) throw declined();   // the C ABI has the isotropic form
 			GrayF32 in = (GrayF32)input, out = (GrayF32)output;
 			long ctx = BoofHipContext.get();
@@ -86,6 +106,41 @@ public final class BoofHipOverrides {
 			config.checkValidity();
 			if (!config.useStrictRule) throw declined();
 			return new NonMaxHip(config);
+		};
+		// FactoryThresholdBinary: the types FactoryThresholdBinaryHip runs on the device.  Their handle methods are generic, hence classes, not lambdas.
+		// globalOtsu stays unset: the factory does not pass `scale` to that hook (FactoryThresholdBinary.java:277-281).
+		BOverrideFactoryThresholdBinary.globalFixed = new BOverrideFactoryThresholdBinary.GlobalFixed() {
+			@Override public <T extends ImageGray<T>> InputToBinary<T> handle(double threshold, boolean down, Class<T> inputType) {
+				return FactoryThresholdBinaryHip.globalFixed(threshold, down, inputType);
+			}
+		};
+		BOverrideFactoryThresholdBinary.localMean = new BOverrideFactoryThresholdBinary.LocalMean() {
+			@Override public <T extends ImageGray<T>> InputToBinary<T> handle(ConfigLength regionWidth, double scale, boolean down, Class<T> inputType) {
+				return FactoryThresholdBinaryHip.localMean(regionWidth, scale, down, inputType);
+			}
+		};
+		BOverrideFactoryThresholdBinary.localGaussian = new BOverrideFactoryThresholdBinary.LocalGaussian() {
+			@Override public <T extends ImageGray<T>> InputToBinary<T> handle(ConfigLength regionWidth, double scale, boolean down, Class<T> inputType) {
+				return FactoryThresholdBinaryHip.localGaussian(regionWidth, scale, down, inputType);
+			}
+		};
+		BOverrideFactoryThresholdBinary.blockMinMax = new BOverrideFactoryThresholdBinary.LocalBlockMinMax() {
+			@Override public <T extends ImageGray<T>> InputToBinary<T> handle(ConfigLength regionWidth, double scale, boolean down, double minimumSpread,
+																			  boolean thresholdFromLocalBlocks, Class<T> inputType) {
+				return FactoryThresholdBinaryHip.blockMinMax(regionWidth, scale, down, minimumSpread, thresholdFromLocalBlocks, inputType);
+			}
+		};
+		BOverrideFactoryThresholdBinary.blockMean = new BOverrideFactoryThresholdBinary.LocalBlockMean() {
+			@Override public <T extends ImageGray<T>> InputToBinary<T> handle(ConfigLength regionWidth, double scale, boolean down, boolean thresholdFromLocalBlocks,
+																			  Class<T> inputType) {
+				return FactoryThresholdBinaryHip.blockMean(regionWidth, scale, down, thresholdFromLocalBlocks, inputType);
+			}
+		};
+		BOverrideFactoryThresholdBinary.blockOtsu = new BOverrideFactoryThresholdBinary.LocalBlockOtsu() {
+			@Override public <T extends ImageGray<T>> InputToBinary<T> handle(boolean otsu2, ConfigLength regionWidth, double tuning, double scale, boolean down,
+																			  boolean thresholdFromLocalBlocks, Class<T> inputType) {
+				return FactoryThresholdBinaryHip.blockOtsu(otsu2, regionWidth, tuning, scale, down, thresholdFromLocalBlocks, inputType);
+			}
 		};
 	}
 
