@@ -6,5 +6,6 @@ the `boofcv_amd.api` package mirrors the reference's Java interfaces on top of i
 from . import _lib  # noqa: F401
 from .api import *  # noqa: F401,F403
 from .binary import *  # noqa: F401,F403  (thresholding: a module beside the api package)
+from .census import *  # noqa: F401,F403  (census transform and census block matching: likewise)
 
 __version__ = "0.1"

@@ -1,7 +1,7 @@
 // C ABI, whole-image operations: dense stereo disparity, image remap, template matching.
 #include "cabi.h"
 
-// ---- dense stereo disparity (disparity.hip): StereoDisparity.process of FactoryStereoDisparity.blockMatch, SAD on GrayU8 pairs ----
+// ---- dense stereo disparity (disparity.hip): StereoDisparity.process of FactoryStereoDisparity.blockMatch, SAD and CENSUS on GrayU8 pairs ----
 // Java's (int) of a double: NaN -> 0, saturating
 static int javaDoubleToInt(double v) {
 	if (v != v) return 0;
@@ -36,15 +36,38 @@ static int disparityParams(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int 
 	return BHIP_OK;
 }
 
+// errorType = CENSUS: the census form a CensusVariants ordinal is matched with -- wordBytes 1 (BLOCK_3_3, GrayU8), 4 (BLOCK_5_5, GrayS32) or 8 (a
+// GrayS64 sample list, in s) -- after the checks of the census transform; nothing for SAD (variant == DISP_SAD)
+#define DISP_SAD (-1)
+struct DispCensusForm {
+	int wordBytes = 0;
+	CensusSamples s;
+};
+static int disparityCensusForm(bhip_ctx* ctx, int variant, int width, int height, DispCensusForm& f) {
+	if (variant == DISP_SAD) return BHIP_OK;
+	int xy[2 * BHIP_CENSUS_MAX_SAMPLES];
+	const int n = bhip_census_variant_list(variant, xy);
+	if (n < 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Unknown type " + std::to_string(variant));
+	BHIP_TRY(bhip_census_samples(xy, n, f.s));
+	if (width < f.s.radius + 1 || height < f.s.radius + 1) return bhip_fail(ctx, BHIP_ERR_INVALID, "the image is smaller than the census region's radius + 1");
+	f.wordBytes = variant == BHIP_CENSUS_BLOCK_3_3 ? 1 : variant == BHIP_CENSUS_BLOCK_5_5 ? 4 : 8;
+	return BHIP_OK;
+}
+
 template <class OutT>
-static int disparityDevice(bhip_ctx* ctx, const DispBmParams& p, DevImg<const uint8_t> left, DevImg<const uint8_t> right, DevImg<OutT> disp) {
+static int disparityDevice(bhip_ctx* ctx, const DispBmParams& p, const DispCensusForm& f, DevImg<const uint8_t> left, DevImg<const uint8_t> right,
+						   DevImg<OutT> disp) {
 	DevBuf& scratch = scratchOf(ctx)->disparity;
+	if (f.wordBytes) {
+		BHIP_TRY(scratch.reserve(ctx, bhip_disparity_census_scratch(left.width, left.height, left.batch, f.wordBytes)));
+		return bhip_launch_disparity_bm_census<OutT>(ctx, left, right, p, f.wordBytes, &f.s, scratch.as<uint8_t>(), disp);
+	}
 	BHIP_TRY(scratch.reserve(ctx, bhip_disparity_scratch(left.width, left.height, left.batch)));
 	return bhip_launch_disparity_bm<OutT>(ctx, left, right, p, scratch.as<uint8_t>(), disp);
 }
 
 template <class OutT>
-static int disparityDev(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* dev_left, long long lImageStride, int lStride, const uint8_t* dev_right,
+static int disparityDev(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* dev_left, long long lImageStride, int lStride, const uint8_t* dev_right,
 						long long rImageStride, int rStride, int width, int height, int batch, OutT* dev_disp, long long dImageStride, int dStride) {
 	CHECK_CTX(ctx);
 	const DevImg<const uint8_t> left{dev_left, lImageStride, lStride, width, height, batch}, right{dev_right, rImageStride, rStride, width, height, batch};
@@ -53,12 +76,14 @@ static int disparityDev(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const u
 	CHECK_IMG(ctx, right);
 	CHECK_IMG(ctx, disp);
 	DispBmParams p;
+	DispCensusForm f;
 	BHIP_TRY(disparityParams<OutT>(ctx, cfg, width, height, p));
-	return disparityDevice<OutT>(ctx, p, left, right, disp);
+	BHIP_TRY(disparityCensusForm(ctx, variant, width, height, f));
+	return disparityDevice<OutT>(ctx, p, f, left, right, disp);
 }
 
 template <class OutT>
-static int disparityHost(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* left, int lStart, int lStride, const uint8_t* right, int rStart, int rStride,
+static int disparityHost(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* left, int lStart, int lStride, const uint8_t* right, int rStart, int rStride,
 						 int width, int height, OutT* disp, int dStart, int dStride) {
 	const HostImg<const uint8_t> hl{left, lStart, lStride, width, height}, hr{right, rStart, rStride, width, height};
 	const HostImg<OutT> hd{disp, dStart, dStride, width, height};
@@ -67,14 +92,16 @@ static int disparityHost(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const 
 	CHECK_IMG(ctx, hr);
 	CHECK_IMG(ctx, hd);
 	DispBmParams p;
+	DispCensusForm f;
 	BHIP_TRY(disparityParams<OutT>(ctx, cfg, width, height, p));
+	BHIP_TRY(disparityCensusForm(ctx, variant, width, height, f));
 	CtxScratch* sc = scratchOf(ctx);
 	DevImg<uint8_t> dl, dr;
 	DevImg<OutT> dd;
 	BHIP_TRY(stageIn(ctx, sc->in0, hl, width, dl));
 	BHIP_TRY(stageIn(ctx, sc->in1, hr, width, dr));
 	BHIP_TRY(stageIn(ctx, sc->out0, hd, width, dd, false));
-	BHIP_TRY(disparityDevice<OutT>(ctx, p, dl, dr, dd));
+	BHIP_TRY(disparityDevice<OutT>(ctx, p, f, dl, dr, dd));
 	BHIP_TRY(stageOut(ctx, hd, dd));
 	return bhip_ctx_synchronize(ctx);
 }
@@ -218,21 +245,46 @@ extern "C" {
 
 int bhip_disparity_bm_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* left, int lStart, int lStride, const uint8_t* right, int rStart,
 							int rStride, int width, int height, uint8_t* disp, int dStart, int dStride) {
-	return disparityHost<uint8_t>(ctx, cfg, left, lStart, lStride, right, rStart, rStride, width, height, disp, dStart, dStride);
+	return disparityHost<uint8_t>(ctx, cfg, DISP_SAD, left, lStart, lStride, right, rStart, rStride, width, height, disp, dStart, dStride);
 }
 int bhip_disparity_bm_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* left, int lStart, int lStride, const uint8_t* right, int rStart,
 							 int rStride, int width, int height, float* disp, int dStart, int dStride) {
-	return disparityHost<float>(ctx, cfg, left, lStart, lStride, right, rStart, rStride, width, height, disp, dStart, dStride);
+	return disparityHost<float>(ctx, cfg, DISP_SAD, left, lStart, lStride, right, rStart, rStride, width, height, disp, dStart, dStride);
 }
 int bhip_disparity_bm_dev_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* dev_left, long long lImageStride, int lStride,
 								const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, uint8_t* dev_disp,
 								long long dImageStride, int dStride) {
-	return disparityDev<uint8_t>(ctx, cfg, dev_left, lImageStride, lStride, dev_right, rImageStride, rStride, width, height, batch, dev_disp, dImageStride, dStride);
+	return disparityDev<uint8_t>(ctx, cfg, DISP_SAD, dev_left, lImageStride, lStride, dev_right, rImageStride, rStride, width, height, batch, dev_disp, dImageStride, dStride);
 }
 int bhip_disparity_bm_dev_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* dev_left, long long lImageStride, int lStride,
 								 const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, float* dev_disp,
 								 long long dImageStride, int dStride) {
-	return disparityDev<float>(ctx, cfg, dev_left, lImageStride, lStride, dev_right, rImageStride, rStride, width, height, batch, dev_disp, dImageStride, dStride);
+	return disparityDev<float>(ctx, cfg, DISP_SAD, dev_left, lImageStride, lStride, dev_right, rImageStride, rStride, width, height, batch, dev_disp, dImageStride, dStride);
+}
+
+int bhip_disparity_bm_census_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* left, int lStart, int lStride,
+								   const uint8_t* right, int rStart, int rStride, int width, int height, uint8_t* disp, int dStart, int dStride) {
+	if (variant == DISP_SAD) return bhip_fail(ctx, BHIP_ERR_INVALID, "Unknown type -1");
+	return disparityHost<uint8_t>(ctx, cfg, variant, left, lStart, lStride, right, rStart, rStride, width, height, disp, dStart, dStride);
+}
+int bhip_disparity_bm_census_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* left, int lStart, int lStride,
+									const uint8_t* right, int rStart, int rStride, int width, int height, float* disp, int dStart, int dStride) {
+	if (variant == DISP_SAD) return bhip_fail(ctx, BHIP_ERR_INVALID, "Unknown type -1");
+	return disparityHost<float>(ctx, cfg, variant, left, lStart, lStride, right, rStart, rStride, width, height, disp, dStart, dStride);
+}
+int bhip_disparity_bm_census_dev_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* dev_left, long long lImageStride, int lStride,
+									   const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, uint8_t* dev_disp,
+									   long long dImageStride, int dStride) {
+	if (variant == DISP_SAD) return bhip_fail(ctx, BHIP_ERR_INVALID, "Unknown type -1");
+	return disparityDev<uint8_t>(ctx, cfg, variant, dev_left, lImageStride, lStride, dev_right, rImageStride, rStride, width, height, batch, dev_disp, dImageStride,
+								 dStride);
+}
+int bhip_disparity_bm_census_dev_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* dev_left, long long lImageStride, int lStride,
+										const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, float* dev_disp,
+										long long dImageStride, int dStride) {
+	if (variant == DISP_SAD) return bhip_fail(ctx, BHIP_ERR_INVALID, "Unknown type -1");
+	return disparityDev<float>(ctx, cfg, variant, dev_left, lImageStride, lStride, dev_right, rImageStride, rStride, width, height, batch, dev_disp, dImageStride,
+							   dStride);
 }
 
 int bhip_distort_map_u8(bhip_ctx* ctx, const uint8_t* src, int sStart, int sStride, int sw, int sh, const float* map, int dw, int dh, int x0, int y0, int x1,

@@ -404,6 +404,31 @@ size_t bhip_disparity_scratch(int width, int height, int batch);   // bytes of d
 template <class OutT>
 int bhip_launch_disparity_bm(bhip_ctx* ctx, DevImg<const uint8_t> left, DevImg<const uint8_t> right, const DispBmParams& c, uint8_t* scratch, DevImg<OutT> out);
 
+// ---------------- census transform (census.hip) and census block matching (disparity.hip) ----------------
+#define BHIP_CENSUS_MAX_SAMPLES 64   // FilterCensusTransformSampleS64's own limit
+#define BHIP_CENSUS_MAX_OFFSET 7     // |dx|, |dy| of a sample the kernel's halo holds
+// a sample list as the kernel reads it: n and radius (the largest |dx|, |dy|) are those of the whole list, dx / dy the first 32 samples --
+// `int bit` of sample_S64 is 0 from sample 32 on
+struct CensusSamples {
+	int n = 0, radius = 0;
+	signed char dx[32] = {}, dy[32] = {};
+};
+// samplesXY = (x, y) pairs -> s and BHIP_OK; BHIP_ERR_INVALID: nSamples outside 0..64 or the list is missing; BHIP_ERR_UNSUPPORTED: an offset outside -7..7
+int bhip_census_samples(const int* samplesXY, int nSamples, CensusSamples& s);
+// the reference's sample list of a CensusVariants ordinal into samplesXY (room for 64 pairs) -> its length, -1: no such variant
+int bhip_census_variant_list(int variant, int* samplesXY);
+// OutT = uint8_t: dense3x3 (denseRadius 1); int32_t: dense5x5 (denseRadius 2), or with denseRadius 0 the low 32 bits of sample_S64's word;
+// long long: sample_S64 (denseRadius 0).  REFLECT border; the whole output view is written.  Needs width, height >= radius + 1.
+template <class OutT>
+int bhip_launch_census(bhip_ctx* ctx, DevImg<const uint8_t> in, int denseRadius, const CensusSamples* s, DevImg<OutT> out);
+// bytes of device scratch one bhip_launch_disparity_bm_census call needs: the right-to-left minima and the two census images
+size_t bhip_disparity_census_scratch(int width, int height, int batch, int wordBytes);
+// bhip_launch_disparity_bm with the Hamming distance of census words as the cost: wordBytes 1 (3x3), 4 (5x5) or 8 (the sample list s, matched
+// on the low 32 bits of its words).  Census of both images into scratch, then the SAD entry's launches; no host synchronisation.
+template <class OutT>
+int bhip_launch_disparity_bm_census(bhip_ctx* ctx, DevImg<const uint8_t> left, DevImg<const uint8_t> right, const DispBmParams& c, int wordBytes,
+									const CensusSamples* s, uint8_t* scratch, DevImg<OutT> out);
+
 // ---------------- image remap, ImageDistort (distort.hip) ----------------
 // where the source coordinates of a destination pixel come from: model == 0, a device map of (x, y) pairs, dw*dh per image and mapImageStride
 // floats from one image's map to the next (0: one map for the batch); otherwise BHIP_DISTORT_AFFINE / _HOMOGRAPHY with 6 / 9 coefficients

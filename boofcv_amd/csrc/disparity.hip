@@ -1,4 +1,5 @@
-// Dense stereo disparity by SAD block matching on GrayU8 pairs: FactoryStereoDisparity.blockMatch(ConfigDisparityBM, GrayU8, GrayU8 | GrayF32), errorType = SAD.
+// Dense stereo disparity by block matching on GrayU8 pairs: FactoryStereoDisparity.blockMatch(ConfigDisparityBM, GrayU8, GrayU8 | GrayF32), errorType = SAD
+// on the pair itself, errorType = CENSUS on the census images of the pair (census.hip).
 //
 // Reference (F: = main/boofcv-feature/src/main/java/boofcv/):
 //   DisparityBlockMatchRowFormat.process              F:alg/feature/disparity/DisparityBlockMatchRowFormat.java:95-107
@@ -7,10 +8,14 @@
 //   SelectErrorWithChecks_S32.process / selectRightToLeft  F:alg/feature/disparity/block/select/SelectErrorWithChecks_S32.java:73-162
 //   SelectErrorWithChecks_S32.DispU8.setDisparity     :172-190        SelectErrorSubpixel.S32_F32.setDisparity   SelectErrorSubpixel.java:46-75
 //   WrapBaseBlockMatch.process (the fill value)       F:abst/feature/disparity/WrapBaseBlockMatch.java:42-85
+//   BlockRowScoreCensus.U8 / S32 / S64 (CENSUS)       F:alg/feature/disparity/block/BlockRowScoreCensus.java:39-85; DescriptorDistance.hamming   F:alg/descriptor/DescriptorDistance.java:213-224
+//   WrapDisparityBlockMatchCensus._process            F:abst/feature/disparity/WrapDisparityBlockMatchCensus.java:55-63
 //
 // With rw = 2*rx+1, rh = 2*ry+1 the cost of the left block that starts at column c against the right block that starts at c - minD - i is
 //   C(y,c,i) = sum_{dy=-ry..ry} sum_{j<rw} |L[y+dy][c+j] - R[y+dy][c-minD-i+j]|        (int; integers make the reference's running sums exact)
 // for i < lm = min(c - minD + 1, range); the result goes to pixel (c + rx, y).  Selection, checks and the sub-pixel rule: include/boofhip.h.
+// CENSUS: L and R are the census images and |a - b| is hamming(a ^ b); everything after the cost is the same code (the reference builds the
+// same DisparityScoreBM_S32 and S32 selector on the census images).
 //
 // Two stages, separable in the code: the cost stage (dispCostRow, the per-pixel cost is the template parameter Cost) fills a slab
 // V[anchor column][disparity] of one output row in LDS; the selection stage (dispFirstMin, dispSecondMin, dispChecks) reduces the slab.  k_disparity_bm runs both, in two
@@ -30,8 +35,21 @@
 // (cost << 9 | disparity).
 // LDS: slab 64 * 258 * 2 = 33024 B, staged rows 30 * (80 + 336) = 12480 B; 45504 B per workgroup, three workgroups per CU.
 //
+// Census words (the Cost's Elem): the staged rows hold words instead of pixels, the slab is the same (costs <= 64 * 15 * 15 = 14400).
+//   BLOCK_3_3, GrayU8 words    1-byte elements: the SAD geometry and budget, 45504 B, three workgroups per CU.
+//   BLOCK_5_5, GrayS32 words   4-byte elements.  30 staged rows would take 30 * 416 * 4 = 49920 B + the slab = 82944 B: one workgroup per CU
+//                              (160 KiB).  The band is cut to DISP_ROWS_W32 = 22 staged rows instead, 22 - 2*ry output rows per workgroup (16 at
+//                              the default ry = 3, 8 at ry = 7): 22 * 416 * 4 = 36608 B + 33024 B = 69632 B, two workgroups per CU.  The price
+//                              is the first row of a band, which sums rh rows where a later row adds one and drops one: (rh + 2 * (th - 1)) / th
+//                              row costs per output row, 2.3 at ry = 3 as for SAD, 3.6 at ry = 7 (SAD: 2.8).
+//   GrayS64 words              folded to their low 32 bits, which carry all the information (census.hip: a word is the sign extension of its
+//                              low word): the census stage writes 4-byte words, the cost is popc(x) + 32 * (x >> 31) -- bits 0..30 count once,
+//                              bit 31 stands for the 33 bits 31..63 -- and the geometry is that of GrayS32.  8-byte elements would need
+//                              22 * 416 * 8 + 33024 = 106240 B, one workgroup per CU, and twice the scratch traffic for nothing.
+// The SAD instantiations compile to the instructions they had before the cost became a type with an element (checked on the assembly).
+//
 // Deviations from the reference (include/boofhip.h): the output view is written as a whole on every call (the result of a freshly constructed
-// reference object); height < rh is refused.  Limits: rx, ry <= 7, rangeDisparity <= 256.
+// reference object); height < rh is refused.  Limits: rx, ry <= 7, rangeDisparity <= 256.  CENSUS: the census images are context scratch.
 #include "common.h"
 
 #define DISP_TW 64       // anchor columns per workgroup
@@ -41,10 +59,43 @@
 #define DISP_MPITCH 336  // DISP_TW + 2 * BHIP_DISP_MAX_RADIUS + BHIP_DISP_MAX_RANGE - 1, rounded up to dwords
 #define DISP_ROWS (DISP_TH + 2 * BHIP_DISP_MAX_RADIUS)
 
+#define DISP_ROWS_W32 22  // staged rows of a cost with 32-bit elements: 22 - 2 * ry output rows per workgroup (16 at the default radius 3, 8 at radius 7)
+
+// A cost: Elem, the staged element; ROWS, the staged rows per workgroup (DISP_ROWS: the fixed DISP_TH output rows; fewer: ROWS - 2 * ry output rows);
+// add(acc, a, b) = acc + the cost of two elements.
 // BlockRowScoreSad.U8: acc + |a - b| of two pixels (one v_sad_u8: the upper three bytes of a and b are zero)
 struct DispCostSad {
+	using Elem = uint8_t;
+	static constexpr int ROWS = DISP_ROWS;
 	static __device__ __forceinline__ int add(int acc, unsigned int a, unsigned int b) { return (int)__builtin_amdgcn_sad_u8(a, b, (unsigned int)acc); }
 };
+// BlockRowScoreCensus.U8 / S32: acc + DescriptorDistance.hamming(a ^ b) of two census words (3x3: 8 bits, 5x5: 24 bits)
+struct DispCostCensus8 {
+	using Elem = uint8_t;
+	static constexpr int ROWS = DISP_ROWS;
+	static __device__ __forceinline__ int add(int acc, unsigned int a, unsigned int b) { return acc + __popc(a ^ b); }
+};
+struct DispCostCensus32 {
+	using Elem = uint32_t;
+	static constexpr int ROWS = DISP_ROWS_W32;
+	static __device__ __forceinline__ int add(int acc, unsigned int a, unsigned int b) { return acc + __popc(a ^ b); }
+};
+// BlockRowScoreCensus.S64 on the low 32 bits of the words: a GrayS64 census word is the sign extension of its low word (census.hip), so
+// hamming(long) of the xor is the bits that differ among 0..30, plus 33 (bits 31..63) when the sample-31 bits differ: popc(x) + 32 * bit 31
+struct DispCostCensus64 {
+	using Elem = uint32_t;
+	static constexpr int ROWS = DISP_ROWS_W32;
+	static __device__ __forceinline__ int add(int acc, unsigned int a, unsigned int b) {
+		const unsigned int x = a ^ b;
+		return acc + __popc(x) + (int)((x >> 31) << 5);
+	}
+};
+// output rows per workgroup
+template <class Cost>
+__host__ __device__ __forceinline__ int dispTileRows(int ry) {
+	if constexpr (Cost::ROWS == DISP_ROWS) return DISP_TH;
+	else return Cost::ROWS - 2 * ry;
+}
 
 struct DispKernelParams {
 	const uint8_t* left;
@@ -86,10 +137,22 @@ __device__ __forceinline__ void dispStage(uint8_t* dst, int pitch, const uint8_t
 	}
 }
 
+// The same for a dense, aligned image of 32-bit census words (context scratch): one element per load
+__device__ __forceinline__ void dispStage(uint32_t* dst, int pitch, const uint32_t* img, int stride, int w, int y0, int rows, int x0, int count) {
+	const int xs = max(x0, 0), xe = min(x0 + count, w);
+	const int len = xe - xs;
+	if (len <= 0) return;
+	for (int s = threadIdx.x; s < rows * len; s += 256) {
+		const int r = s / len, k = s - r * len;
+		dst[r * pitch + (xs - x0) + k] = img[(long long)(y0 + r) * stride + xs + k];
+	}
+}
+
 // Cost stage, one staged row pair into the slab entries (columns c0 .. c0+cs-1, disparity s) of the calling thread:
 // v[col] += H(an, mn)(col) - H(ao, mo)(col), H(col) = sum_{j<rw} cost(a[col + j], m[col + j]); HASOLD = false adds only.
 template <class Cost, bool HASOLD>
-__device__ __forceinline__ void dispCostRow(unsigned short* v, const uint8_t* an, const uint8_t* mn, const uint8_t* ao, const uint8_t* mo, int c0, int cs, int rw) {
+__device__ __forceinline__ void dispCostRow(unsigned short* v, const typename Cost::Elem* an, const typename Cost::Elem* mn, const typename Cost::Elem* ao,
+											const typename Cost::Elem* mo, int c0, int cs, int rw) {
 	int hsum = 0;
 	for (int j = 0; j < rw; j++) {
 		const int x = c0 + j;
@@ -145,20 +208,22 @@ __device__ __forceinline__ int dispChecks(const DispBmParams& c, int best, int s
 template <class Cost, bool RTOL, class OutT>
 __global__ __launch_bounds__(256) void k_disparity_bm(DispKernelParams P) {
 	__shared__ __attribute__((aligned(16))) unsigned short V[DISP_TW * DISP_VPITCH];
-	__shared__ __attribute__((aligned(16))) uint8_t sa[DISP_ROWS * DISP_APITCH];
-	__shared__ __attribute__((aligned(16))) uint8_t sm[DISP_ROWS * DISP_MPITCH];
+	using Elem = typename Cost::Elem;
+	__shared__ __attribute__((aligned(16))) Elem sa[Cost::ROWS * DISP_APITCH];
+	__shared__ __attribute__((aligned(16))) Elem sm[Cost::ROWS * DISP_MPITCH];
 	const DispBmParams& c = P.c;
 	const int w = P.w, h = P.h, S = c.range, rw = 2 * c.rx + 1, rh = 2 * c.ry + 1;
 	const long long b = blockIdx.z;
-	const uint8_t* L = P.left + b * P.lImageStride;
-	const uint8_t* R = P.right + b * P.rImageStride;
+	const Elem* L = (const Elem*)P.left + b * P.lImageStride;
+	const Elem* R = (const Elem*)P.right + b * P.rImageStride;
 	const int a0 = (RTOL ? 0 : c.minD) + blockIdx.x * DISP_TW;   // block start column of the tile's first anchor
-	const int yb0 = c.ry + blockIdx.y * DISP_TH, yb1 = min(yb0 + DISP_TH, h - c.ry);
+	const int th = dispTileRows<Cost>(c.ry);
+	const int yb0 = c.ry + blockIdx.y * th, yb1 = min(yb0 + th, h - c.ry);
 	const int nrows = yb1 - yb0 + 2 * c.ry;                       // staged image rows yb0 - ry ..
 	const int acount = DISP_TW + rw - 1, mcount = acount + S - 1;
 	const int m0 = RTOL ? a0 + c.minD : a0 - c.minD - (S - 1);    // image column of sm[0]
-	for (int i = threadIdx.x; i < DISP_ROWS * DISP_APITCH / 4; i += 256) ((unsigned int*)sa)[i] = 0u;
-	for (int i = threadIdx.x; i < DISP_ROWS * DISP_MPITCH / 4; i += 256) ((unsigned int*)sm)[i] = 0u;
+	for (int i = threadIdx.x; i < Cost::ROWS * DISP_APITCH * (int)sizeof(Elem) / 4; i += 256) ((unsigned int*)sa)[i] = 0u;
+	for (int i = threadIdx.x; i < Cost::ROWS * DISP_MPITCH * (int)sizeof(Elem) / 4; i += 256) ((unsigned int*)sm)[i] = 0u;
 	__syncthreads();
 	dispStage(sa, DISP_APITCH, RTOL ? R : L, RTOL ? P.rStride : P.lStride, w, yb0 - c.ry, nrows, a0, acount);
 	dispStage(sm, DISP_MPITCH, RTOL ? L : R, RTOL ? P.lStride : P.rStride, w, yb0 - c.ry, nrows, m0, mcount);
@@ -229,32 +294,75 @@ __global__ __launch_bounds__(256) void k_disparity_border(OutT* out, long long i
 
 size_t bhip_disparity_scratch(int width, int height, int batch) { return (size_t)width * height * batch; }
 
-template <class OutT>
-int bhip_launch_disparity_bm(bhip_ctx* ctx, DevImg<const uint8_t> left, DevImg<const uint8_t> right, const DispBmParams& c, uint8_t* scratch, DevImg<OutT> out) {
+// the launches of one batch on images of Cost::Elem (the GrayU8 pair, or its two census images): border fill, right-to-left minima, selection
+template <class Cost, class OutT>
+static int dispLaunch(bhip_ctx* ctx, const char* what, DevImg<const typename Cost::Elem> left, DevImg<const typename Cost::Elem> right, const DispBmParams& c,
+					  uint8_t* rtol, DevImg<OutT> out) {
 	const int w = left.width, h = left.height, batch = left.batch;
 	const int rw = 2 * c.rx + 1, rh = 2 * c.ry + 1;
 	if (batch <= 0 || w <= 0 || h <= 0) return BHIP_OK;
 	if (c.rx < 0 || c.ry < 0 || c.rx > BHIP_DISP_MAX_RADIUS || c.ry > BHIP_DISP_MAX_RADIUS || c.range < 1 || c.range > BHIP_DISP_MAX_RANGE || c.minD < 0 ||
 		c.minD + c.range > w - 2 * c.rx || h < rh)
-		return bhip_fail(ctx, BHIP_ERR_INVALID, "bhip_launch_disparity_bm: outside the kernel's limits");
-	DispKernelParams P{left.data, right.data, left.imageStride, right.imageStride, left.stride, right.stride, w, h, c, scratch, out.data, out.imageStride, out.stride};
-	const dim3 grid((w - rw - c.minD + 1 + DISP_TW - 1) / DISP_TW, (h - 2 * c.ry + DISP_TH - 1) / DISP_TH, batch);
-	const double px = (double)w * h * batch, ops = px * c.range;
+		return bhip_fail(ctx, BHIP_ERR_INVALID, std::string(what) + ": outside the kernel's limits");
+	DispKernelParams P{(const uint8_t*)left.data, (const uint8_t*)right.data, left.imageStride, right.imageStride, left.stride, right.stride, w, h, c, rtol,
+					   out.data, out.imageStride, out.stride};
+	const int th = dispTileRows<Cost>(c.ry);
+	const dim3 grid((w - rw - c.minD + 1 + DISP_TW - 1) / DISP_TW, (h - 2 * c.ry + th - 1) / th, batch);
+	const double px = (double)w * h * batch, ops = px * c.range, eb = sizeof(typename Cost::Elem);
 	{
 		ProfScope ps(ctx, "k_disparity_border", 0);
 		hipLaunchKernelGGL(k_disparity_border<OutT>, dim3((w + 63) / 64, (h + 3) / 4, batch), dim3(256), 0, ctx->stream, out.data, out.imageStride, out.stride, w, h,
 						   c.rx + c.minD, w - c.rx, c.ry, h - c.ry, (OutT)c.range);
 	}
 	if (c.rtolTol >= 0) {
-		ProfScope ps(ctx, "k_disparity_rtol", 3.0 * px, ops);
-		hipLaunchKernelGGL((k_disparity_bm<DispCostSad, true, uint8_t>), grid, dim3(256), 0, ctx->stream, P);
+		ProfScope ps(ctx, "k_disparity_rtol", (2.0 * eb + 1.0) * px, ops);
+		hipLaunchKernelGGL((k_disparity_bm<Cost, true, uint8_t>), grid, dim3(256), 0, ctx->stream, P);
 	}
 	{
-		ProfScope ps(ctx, sizeof(OutT) == 1 ? "k_disparity_bm_u8" : "k_disparity_bm_f32", (2.0 + sizeof(OutT) + (c.rtolTol >= 0 ? 1.0 : 0.0)) * px, ops);
-		hipLaunchKernelGGL((k_disparity_bm<DispCostSad, false, OutT>), grid, dim3(256), 0, ctx->stream, P);
+		ProfScope ps(ctx, sizeof(OutT) == 1 ? "k_disparity_bm_u8" : "k_disparity_bm_f32", (2.0 * eb + sizeof(OutT) + (c.rtolTol >= 0 ? 1.0 : 0.0)) * px, ops);
+		hipLaunchKernelGGL((k_disparity_bm<Cost, false, OutT>), grid, dim3(256), 0, ctx->stream, P);
 	}
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
 }
+
+template <class OutT>
+int bhip_launch_disparity_bm(bhip_ctx* ctx, DevImg<const uint8_t> left, DevImg<const uint8_t> right, const DispBmParams& c, uint8_t* scratch, DevImg<OutT> out) {
+	return dispLaunch<DispCostSad, OutT>(ctx, "bhip_launch_disparity_bm", left, right, c, scratch, out);
+}
 template int bhip_launch_disparity_bm(bhip_ctx*, DevImg<const uint8_t>, DevImg<const uint8_t>, const DispBmParams&, uint8_t*, DevImg<uint8_t>);
 template int bhip_launch_disparity_bm(bhip_ctx*, DevImg<const uint8_t>, DevImg<const uint8_t>, const DispBmParams&, uint8_t*, DevImg<float>);
+
+// scratch of the census form: [right-to-left minima, one byte per pixel, rounded up to 16 B][census of the left images][census of the right images],
+// the census images dense, in 1-byte (3x3) or 4-byte (5x5; the low words of a sample list) elements
+static size_t dispCensusRtolBytes(int width, int height, int batch) { return ((size_t)width * height * batch + 15) & ~(size_t)15; }
+size_t bhip_disparity_census_scratch(int width, int height, int batch, int wordBytes) {
+	return dispCensusRtolBytes(width, height, batch) + 2 * (size_t)width * height * batch * (wordBytes == 1 ? 1 : 4);
+}
+
+template <class Cost, class OutT>
+static int dispCensus(bhip_ctx* ctx, DevImg<const uint8_t> left, DevImg<const uint8_t> right, const DispBmParams& c, int denseRadius, const CensusSamples* s,
+					  uint8_t* scratch, DevImg<OutT> out) {
+	using Elem = typename Cost::Elem;
+	using Word = std::conditional_t<sizeof(Elem) == 1, uint8_t, int32_t>;   // what bhip_launch_census writes
+	const int w = left.width, h = left.height, batch = left.batch;
+	Elem* cl = (Elem*)(scratch + dispCensusRtolBytes(w, h, batch));
+	Elem* cr = cl + (size_t)w * h * batch;
+	const DevImg<Elem> dl{cl, (long long)w * h, w, w, h, batch}, dr{cr, (long long)w * h, w, w, h, batch};
+	BHIP_TRY(bhip_launch_census<Word>(ctx, left, denseRadius, s, DevImg<Word>{(Word*)cl, dl.imageStride, w, w, h, batch}));
+	BHIP_TRY(bhip_launch_census<Word>(ctx, right, denseRadius, s, DevImg<Word>{(Word*)cr, dr.imageStride, w, w, h, batch}));
+	return dispLaunch<Cost, OutT>(ctx, "bhip_launch_disparity_bm_census", dl, dr, c, scratch, out);
+}
+
+template <class OutT>
+int bhip_launch_disparity_bm_census(bhip_ctx* ctx, DevImg<const uint8_t> left, DevImg<const uint8_t> right, const DispBmParams& c, int wordBytes,
+									const CensusSamples* s, uint8_t* scratch, DevImg<OutT> out) {
+	if (wordBytes == 1) return dispCensus<DispCostCensus8, OutT>(ctx, left, right, c, 1, nullptr, scratch, out);
+	if (wordBytes == 4) return dispCensus<DispCostCensus32, OutT>(ctx, left, right, c, 2, nullptr, scratch, out);
+	if (wordBytes == 8 && s) return dispCensus<DispCostCensus64, OutT>(ctx, left, right, c, 0, s, scratch, out);
+	return bhip_fail(ctx, BHIP_ERR_INVALID, "bhip_launch_disparity_bm_census: no such census word");
+}
+template int bhip_launch_disparity_bm_census(bhip_ctx*, DevImg<const uint8_t>, DevImg<const uint8_t>, const DispBmParams&, int, const CensusSamples*, uint8_t*,
+											 DevImg<uint8_t>);
+template int bhip_launch_disparity_bm_census(bhip_ctx*, DevImg<const uint8_t>, DevImg<const uint8_t>, const DispBmParams&, int, const CensusSamples*, uint8_t*,
+											 DevImg<float>);

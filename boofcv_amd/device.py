@@ -237,6 +237,55 @@ class DeviceImageOps:
         _check(self.ctx, fn(self.ctx._h, C.byref(config._c()) if config is not None else None, lp, lis, lrs, rp, ris, rrs, W, H, B, op, ois, ors))
         return out
 
+    def census(self, src, variant, out=None):
+        """FilterImageInterface.process of FactoryCensusTransform.variant(variant, GrayU8) on uint8 frames [B,H,W] of any row / image stride ->
+        the census words [B,H,W]: uint8 (BLOCK_3_3), int32 (BLOCK_5_5) or int64 (the other variants).  variant: a census.CensusVariants, or a
+        sample list [(x, y)] (at most 64, offsets within -7 .. 7) for sample_S64 -> int64.  `out`, any stride, is written in place and as a
+        whole.  No host synchronisation."""
+        from . import census
+        ip, iis, irs, W, H, B = _geom(src, torch.uint8)
+        samples = None
+        if isinstance(variant, (list, tuple, np.ndarray)):
+            samples = [tuple(p) for p in variant]
+        else:
+            try:
+                variant = census.CensusVariants(variant)
+            except ValueError:
+                raise IllegalArgumentException("Unknown type %s" % (variant,))
+            if variant not in (census.CensusVariants.BLOCK_3_3, census.CensusVariants.BLOCK_5_5):
+                samples = census._variant_samples(variant)
+        dt = torch.int64 if samples is not None else torch.uint8 if variant == census.CensusVariants.BLOCK_3_3 else torch.int32
+        if out is None:
+            out = torch.empty((B, H, W), dtype=dt, device=src.device)
+        op, ois, ors, W2, H2, B2 = _geom(out, dt)
+        if (W, H, B) != (W2, H2, B2):
+            raise IllegalArgumentException("input and output shapes differ")
+        if samples is not None:
+            xy, p, n = census._samples_arg(samples)
+            _check(self.ctx, self.L.bhip_census_sample_dev_u8_s64(self.ctx._h, p, n, ip, iis, irs, W, H, B, op, ois, ors))
+        else:
+            fn = self.L.bhip_census_dev_u8_u8 if dt == torch.uint8 else self.L.bhip_census_dev_u8_s32
+            _check(self.ctx, fn(self.ctx._h, ip, iis, irs, W, H, B, op, ois, ors))
+        return out
+
+    def disparityBMCensus(self, left, right, config=None, variant=_lib.BHIP_CENSUS_BLOCK_5_5, subpixel=True, out=None):
+        """StereoDisparity.process of FactoryStereoDisparity.blockMatch with errorType = CENSUS and configCensus.variant = variant on uint8 pairs
+        [B,H,W] -> the disparity [B,H,W]: float32 when subpixel, uint8 otherwise (config.subpixel and config.errorType are not read; `out`, any
+        row / image stride, is written in place and as a whole).  config: a ConfigDisparityBM, None = the reference defaults."""
+        lp, lis, lrs, W, H, B = _geom(left, torch.uint8)
+        rp, ris, rrs, W2, H2, B2 = _geom(right, torch.uint8)
+        if (W, H, B) != (W2, H2, B2):
+            raise IllegalArgumentException("Image shapes do not match")
+        dt = torch.float32 if subpixel else torch.uint8
+        if out is None:
+            out = torch.empty((B, H, W), dtype=dt, device=left.device)
+        op, ois, ors, W3, H3, B3 = _geom(out, dt)
+        if (W, H, B) != (W3, H3, B3):
+            raise IllegalArgumentException("input and disparity shapes differ")
+        fn = self.L.bhip_disparity_bm_census_dev_u8_f32 if subpixel else self.L.bhip_disparity_bm_census_dev_u8_u8
+        _check(self.ctx, fn(self.ctx._h, C.byref(config._c()) if config is not None else None, int(variant), lp, lis, lrs, rp, ris, rrs, W, H, B, op, ois, ors))
+        return out
+
     def denseFlowKlt(self, prev, curr, config=None, radius=3, out=None, tracks=None, form=_lib.BHIP_FLOW_FORM_AUTO):
         """DenseOpticalFlow.process of FactoryDenseOpticalFlow.flowKlt on float32 or uint8 pairs [B,H,W] -> the flow [B,H,W,2] float32, invalid
         pixels (NaN, 0).  config: a PkltConfig (its KltConfig and pyramidScaling; templateRadius is not read), None = the reference defaults.

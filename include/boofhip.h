@@ -290,11 +290,63 @@ int bhip_fast_f32(bhip_ctx* ctx, const float* image, int start, int stride, int 
  * rangeDisparity outside the region above, where the reference leaves what an earlier pair put there -- the result of a freshly constructed
  * reference object.
  * Limits: regionRadiusX, regionRadiusY <= 7 and rangeDisparity <= 256 (<= 253 for U8, by the validation); beyond them BHIP_ERR_UNSUPPORTED and
- * nothing is written.  blockMatchBest5, CENSUS, NCC, SGM and the GrayF32 / GrayU16 / GrayS16 inputs have no entry point. */
+ * nothing is written.  errorType = CENSUS: bhip_disparity_bm_census_u8_u8 / _u8_f32.  blockMatchBest5, NCC, SGM and the GrayF32 / GrayU16 / GrayS16
+ * inputs have no entry point. */
 int bhip_disparity_bm_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* left, int lStart, int lStride, const uint8_t* right, int rStart,
 							int rStride, int width, int height, uint8_t* disp, int dStart, int dStride);
 int bhip_disparity_bm_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* left, int lStart, int lStride, const uint8_t* right, int rStart,
 							 int rStride, int width, int height, float* disp, int dStart, int dStride);
+/* ---- census transform: FilterImageInterface<GrayU8, GrayU8 | GrayS32 | GrayS64> of FactoryCensusTransform (census.hip) ---- */
+typedef enum { BHIP_CENSUS_BLOCK_3_3 = 0, BHIP_CENSUS_BLOCK_5_5 = 1, BHIP_CENSUS_BLOCK_7_7 = 2, BHIP_CENSUS_BLOCK_9_7 = 3, BHIP_CENSUS_BLOCK_13_5 = 4,
+			   BHIP_CENSUS_CIRCLE_9 = 5 } bhip_census_variant;   /* CensusVariants ordinals (I:factory/transform/census/CensusVariants.java) */
+/* The reference's sample list of a variant, as (x, y) pairs into samplesXY[0 .. 2*cap) and its length into *n: CensusTransform.createBlockSamples(r),
+ * createBlockSamples(rx, ry), createCircleSamples (I:alg/transform/census/CensusTransform.java:53-98) as FactoryCensusTransform.variant picks them
+ * (I:factory/transform/census/FactoryCensusTransform.java:48-93).  Order: row-major over dy, then dx, without the centre.
+ *   BLOCK_3_3   3x3, 8 samples (GrayU8 words)         BLOCK_9_7    blockDense(4,3): 9x7, 62 samples
+ *   BLOCK_5_5   5x5, 24 samples (GrayS32 words)       BLOCK_13_5   blockDense(5,2): 11x5 despite its name, 54 samples
+ *   BLOCK_7_7   7x7, 48 samples (GrayS64 words)       CIRCLE_9     56 samples, set(row-4, col-4): the loop's row is x
+ * samplesXY == NULL: only *n is written.  BHIP_ERR_INVALID and nothing is written: no such variant, n == NULL, cap smaller than the list.  No
+ * context: the lists exist once, here. */
+int bhip_census_variant_samples(int variant, int* samplesXY, int cap, int* n);
+/* FilterCensusTransformD33U8 / D55S32 / SampleS64.process(in, out) (I:abst/transform/census/) with the factory's border, CENSUS_BORDER = REFLECT:
+ * CensusTransform.dense3x3 / dense5x5 / sample_S64 (I:alg/transform/census/CensusTransform.java:107-225) over ImplCensusTransformInner and
+ * ImplCensusTransformBorder (I:alg/transform/census/impl/).  Facts read from those files:
+ *   formula  the inner and the border code compute the same thing, so one rule covers the image: with c = in(x,y), bit i of out(x,y) is set iff
+ *            in(reflect(x+dx_i), reflect(y+dy_i)) > c; reflect(k) = -k for k < 0, 2*len-2-k for k >= len (I:core/image/border/BorderIndex1D_Reflect.java:34-41).
+ *   order    3x3 and 5x5: row-major over dy, then dx, without the centre; bit 0 is the first sample (8 and 24 bits).  The sample form: the list's order.
+ *   S64      sample_S64 counts its bits in an int (`long census; int bit = 1; census |= bit; bit <<= 1`, inner :203-209, border :153-167): samples
+ *            0..30 set bits 0..30, sample 31 ORs in 0x80000000 sign-extended and sets bits 31..63, samples 32 and up add nothing.  Every word is
+ *            the sign extension of its low 32 bits.  This is reproduced bit for bit.
+ *   size     one reflection must land inside: width, height >= radius + 1, radius = 1, 2, or the largest |dx|, |dy| of the whole list as
+ *            sample_S64 computes it.
+ * samplesXY: nSamples (x, y) pairs.  Validation, BHIP_ERR_INVALID and nothing is written: a bad view, nSamples < 0 or > 64
+ * (FilterCensusTransformSampleS64's constructor), samplesXY == NULL with nSamples > 0, an image smaller than radius + 1 in either direction.
+ * Limits, BHIP_ERR_UNSUPPORTED and nothing is written: a sample with |dx| or |dy| > 7.
+ * Deviations: an image smaller than radius + 1 is refused, where the reference throws or writes outside the image; the output view is written
+ * as a whole and must have the input's size (the reference reshapes it).  GrayU16 inputs and sample_IU16 have no entry point. */
+int bhip_census_u8_u8(bhip_ctx* ctx, const uint8_t* in, int start, int stride, int width, int height, uint8_t* out, int oStart, int oStride);
+int bhip_census_u8_s32(bhip_ctx* ctx, const uint8_t* in, int start, int stride, int width, int height, int32_t* out, int oStart, int oStride);
+int bhip_census_sample_u8_s64(bhip_ctx* ctx, const int* samplesXY, int nSamples, const uint8_t* in, int start, int stride, int width, int height, long long* out,
+							  int oStart, int oStride);
+/* StereoDisparity.process(left, right) of FactoryStereoDisparity.blockMatch with errorType = CENSUS and configCensus.variant = `variant`
+ * (F:factory/feature/disparity/FactoryStereoDisparity.java:85-102): WrapDisparityBlockMatchCensus (F:abst/feature/disparity/WrapDisparityBlockMatchCensus.java:32-80)
+ * runs FactoryCensusTransform.variant(variant) on both images (bhip_census_*) and the block matching of bhip_disparity_bm_u8_u8 / _u8_f32 on the
+ * census images, with BlockRowScoreCensus.U8 / S32 / S64 (F:alg/feature/disparity/block/BlockRowScoreCensus.java:39-85) as the row score:
+ *   cost    C(y,c,i) = sum over dy = -ry..ry, j < rw of hamming(CL[y+dy][c+j] ^ CR[y+dy][c-minDisparity-i+j]), CL / CR the census images and hamming
+ *           DescriptorDistance.hamming(int | long) (F:alg/descriptor/DescriptorDistance.java:213-224), the number of set bits.  Between two GrayS64
+ *           words that is the number of differing bits among 0..30, plus 33 when their sample-31 bits differ (bits 31..63 are copies of it).
+ *   rest    best, error, R to L, texture, store and the border value: exactly the rules of bhip_disparity_bm_u8_u8.  createDisparitySelect is called
+ *           with the input image type, so the selector is the S32 one and maxError = (int)((rw*rh)*maxPerPixelError) counts differing bits.
+ * cfg == NULL: the reference defaults (ConfigDisparityError.Census's default variant is BLOCK_5_5; here the variant is an argument).
+ * Validation, BHIP_ERR_INVALID and nothing is written: that of bhip_disparity_bm_u8_u8, a variant outside 0..5, an image smaller than the variant's
+ * radius + 1 in either direction (bhip_census_*).
+ * Limits, BHIP_ERR_UNSUPPORTED and nothing is written: regionRadiusX, regionRadiusY <= 7, rangeDisparity <= 256 (<= 253 for U8 by the validation).
+ * Deviations: those of bhip_disparity_bm_u8_u8 and of bhip_census_*; the census images are context scratch (getCLeft / getCRight of the
+ * reference's wrapper: run bhip_census_* on the input).  blockMatchBest5, NCC, SGM and the GrayF32 / GrayU16 / GrayS16 inputs have no entry point. */
+int bhip_disparity_bm_census_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* left, int lStart, int lStride,
+								   const uint8_t* right, int rStart, int rStride, int width, int height, uint8_t* disp, int dStart, int dStride);
+int bhip_disparity_bm_census_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* left, int lStart, int lStride,
+									const uint8_t* right, int rStart, int rStride, int width, int height, float* disp, int dStart, int dStride);
 /* ---- image remap: ImageDistort<T,T>, GrayU8 -> GrayU8 and GrayF32 -> GrayF32 (distort.hip) ---- */
 typedef enum { BHIP_INTERP_NEAREST_NEIGHBOR = 0, BHIP_INTERP_BILINEAR = 1, BHIP_INTERP_BICUBIC = 2, BHIP_INTERP_POLYNOMIAL4 = 3 } bhip_interp;   /* InterpolationType ordinals */
 typedef enum { BHIP_BORDER_SKIP = 0, BHIP_BORDER_EXTENDED = 1, BHIP_BORDER_NORMALIZED = 2, BHIP_BORDER_REFLECT = 3, BHIP_BORDER_WRAP = 4, BHIP_BORDER_ZERO = 5 } bhip_border;   /* BorderType ordinals */
@@ -638,6 +690,26 @@ int bhip_disparity_bm_dev_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg,
 int bhip_disparity_bm_dev_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* dev_left, long long lImageStride, int lStride,
 								 const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, float* dev_disp,
 								 long long dImageStride, int dStride);
+/* bhip_census_u8_u8 / bhip_census_u8_s32 / bhip_census_sample_u8_s64 on a batch of device images (strides in elements; any byte alignment and stride
+ * of the GrayU8 view): image b is dev_in + b*iImageStride and writes dev_out + b*oImageStride, the whole width x height view and nothing outside it.
+ * One launch: a tile of 64 x 16 pixels and its halo are staged in LDS with the reflected indices resolved, one lane per output pixel.  samplesXY is
+ * host memory (the list travels in the kernel arguments).  No host synchronisation. */
+int bhip_census_dev_u8_u8(bhip_ctx* ctx, const uint8_t* dev_in, long long iImageStride, int iStride, int width, int height, int batch, uint8_t* dev_out,
+						  long long oImageStride, int oStride);
+int bhip_census_dev_u8_s32(bhip_ctx* ctx, const uint8_t* dev_in, long long iImageStride, int iStride, int width, int height, int batch, int32_t* dev_out,
+						   long long oImageStride, int oStride);
+int bhip_census_sample_dev_u8_s64(bhip_ctx* ctx, const int* samplesXY, int nSamples, const uint8_t* dev_in, long long iImageStride, int iStride, int width,
+								  int height, int batch, long long* dev_out, long long oImageStride, int oStride);
+/* bhip_disparity_bm_census_u8_u8 / _u8_f32 on a batch of device pairs (strides in elements; any byte alignment of a GrayU8 view): pair b is
+ * dev_left + b*lImageStride, dev_right + b*rImageStride and writes dev_disp + b*dImageStride, the whole width x height view and nothing outside it.
+ * Two stages without a host synchronisation: the census of both images into context scratch (1 byte per pixel for BLOCK_3_3, 4 for BLOCK_5_5 and --
+ * the low words, which carry all the information -- for the GrayS64 variants), then the launches of bhip_disparity_bm_dev_u8_u8 on the census images. */
+int bhip_disparity_bm_census_dev_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* dev_left, long long lImageStride, int lStride,
+									   const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, uint8_t* dev_disp,
+									   long long dImageStride, int dStride);
+int bhip_disparity_bm_census_dev_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* dev_left, long long lImageStride, int lStride,
+										const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, float* dev_disp,
+										long long dImageStride, int dStride);
 /* bhip_template_intensity_u8 / _f32 on a batch of device images (strides in elements; any byte alignment of a GrayU8 view): image b is
  * dev_image + b*iImageStride and writes dev_intensity + b*oImageStride, the whole width x height view and nothing outside it.  tImageStride /
  * mImageStride 0: one template / mask shared by the batch; otherwise image b is matched against dev_templ + b*tImageStride (and
