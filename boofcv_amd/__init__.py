@@ -7,5 +7,6 @@ from . import _lib  # noqa: F401
 from .api import *  # noqa: F401,F403
 from .binary import *  # noqa: F401,F403  (thresholding: a module beside the api package)
 from .census import *  # noqa: F401,F403  (census transform and census block matching: likewise)
+from .best5 import *  # noqa: F401,F403  (five-region block matching, blockMatchBest5: likewise)
 
 __version__ = "0.1"

@@ -1,7 +1,7 @@
 // C ABI, whole-image operations: dense stereo disparity, image remap, template matching.
 #include "cabi.h"
 
-// ---- dense stereo disparity (disparity.hip): StereoDisparity.process of FactoryStereoDisparity.blockMatch, SAD and CENSUS on GrayU8 pairs ----
+// ---- dense stereo disparity (disparity.hip): StereoDisparity.process of FactoryStereoDisparity.blockMatch / blockMatchBest5, SAD and CENSUS on GrayU8 pairs ----
 // Java's (int) of a double: NaN -> 0, saturating
 static int javaDoubleToInt(double v) {
 	if (v != v) return 0;
@@ -11,9 +11,10 @@ static int javaDoubleToInt(double v) {
 }
 
 // the checks of ConfigDisparityBM.checkValidity, DisparityBlockMatchRowFormat.process and SelectDisparityWithChecksWta.configure, then the
-// kernel's limits; fills the selector's parameters
+// kernel's limits; fills the selector's parameters.  five: blockMatchBest5, whose checks are the same (DisparityBlockMatchRowFormat.process tests
+// radiusX, not 2*radiusX) and whose maxError counts three regions
 template <class OutT>
-static int disparityParams(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int width, int height, DispBmParams& p) {
+static int disparityParams(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int width, int height, DispBmParams& p, bool five = false) {
 	bhip_disparity_bm_cfg c;
 	if (cfg) c = *cfg; else bhip_disparity_bm_cfg_default(&c);
 	if (c.minDisparity < 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "miDisparity < 0");
@@ -28,7 +29,9 @@ static int disparityParams(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int 
 	if (c.regionRadiusX > BHIP_DISP_MAX_RADIUS || c.regionRadiusY > BHIP_DISP_MAX_RADIUS || c.rangeDisparity > BHIP_DISP_MAX_RANGE)
 		return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "block matching on the GPU: region radius <= 7, rangeDisparity <= 256");
 	const int rw = 2 * c.regionRadiusX + 1, rh = 2 * c.regionRadiusY + 1;
-	const int maxError = javaDoubleToInt((rw * rh) * c.maxPerPixelError);   // FactoryStereoDisparity.java:75,79
+	double maxErrorD = (rw * rh) * c.maxPerPixelError;                      // FactoryStereoDisparity.java:75,79
+	if (five) maxErrorD *= 3;                                               // :159-162
+	const int maxError = javaDoubleToInt(maxErrorD);
 	p.minD = c.minDisparity; p.range = c.rangeDisparity; p.rx = c.regionRadiusX; p.ry = c.regionRadiusY;
 	p.maxError = maxError <= 0 ? 2147483647 : maxError;                     // SelectDisparityWithChecksWta.java:83
 	p.rtolTol = c.validateRtoL;
@@ -56,19 +59,21 @@ static int disparityCensusForm(bhip_ctx* ctx, int variant, int width, int height
 
 template <class OutT>
 static int disparityDevice(bhip_ctx* ctx, const DispBmParams& p, const DispCensusForm& f, DevImg<const uint8_t> left, DevImg<const uint8_t> right,
-						   DevImg<OutT> disp) {
+						   DevImg<OutT> disp, bool five = false) {
 	DevBuf& scratch = scratchOf(ctx)->disparity;
 	if (f.wordBytes) {
 		BHIP_TRY(scratch.reserve(ctx, bhip_disparity_census_scratch(left.width, left.height, left.batch, f.wordBytes)));
+		if (five) return bhip_launch_disparity_bm5_census<OutT>(ctx, left, right, p, f.wordBytes, &f.s, scratch.as<uint8_t>(), disp);
 		return bhip_launch_disparity_bm_census<OutT>(ctx, left, right, p, f.wordBytes, &f.s, scratch.as<uint8_t>(), disp);
 	}
 	BHIP_TRY(scratch.reserve(ctx, bhip_disparity_scratch(left.width, left.height, left.batch)));
+	if (five) return bhip_launch_disparity_bm5<OutT>(ctx, left, right, p, scratch.as<uint8_t>(), disp);
 	return bhip_launch_disparity_bm<OutT>(ctx, left, right, p, scratch.as<uint8_t>(), disp);
 }
 
 template <class OutT>
 static int disparityDev(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* dev_left, long long lImageStride, int lStride, const uint8_t* dev_right,
-						long long rImageStride, int rStride, int width, int height, int batch, OutT* dev_disp, long long dImageStride, int dStride) {
+						long long rImageStride, int rStride, int width, int height, int batch, OutT* dev_disp, long long dImageStride, int dStride, bool five = false) {
 	CHECK_CTX(ctx);
 	const DevImg<const uint8_t> left{dev_left, lImageStride, lStride, width, height, batch}, right{dev_right, rImageStride, rStride, width, height, batch};
 	const DevImg<OutT> disp{dev_disp, dImageStride, dStride, width, height, batch};
@@ -77,14 +82,14 @@ static int disparityDev(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int var
 	CHECK_IMG(ctx, disp);
 	DispBmParams p;
 	DispCensusForm f;
-	BHIP_TRY(disparityParams<OutT>(ctx, cfg, width, height, p));
+	BHIP_TRY(disparityParams<OutT>(ctx, cfg, width, height, p, five));
 	BHIP_TRY(disparityCensusForm(ctx, variant, width, height, f));
-	return disparityDevice<OutT>(ctx, p, f, left, right, disp);
+	return disparityDevice<OutT>(ctx, p, f, left, right, disp, five);
 }
 
 template <class OutT>
 static int disparityHost(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* left, int lStart, int lStride, const uint8_t* right, int rStart, int rStride,
-						 int width, int height, OutT* disp, int dStart, int dStride) {
+						 int width, int height, OutT* disp, int dStart, int dStride, bool five = false) {
 	const HostImg<const uint8_t> hl{left, lStart, lStride, width, height}, hr{right, rStart, rStride, width, height};
 	const HostImg<OutT> hd{disp, dStart, dStride, width, height};
 	CHECK_CTX(ctx);
@@ -93,7 +98,7 @@ static int disparityHost(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int va
 	CHECK_IMG(ctx, hd);
 	DispBmParams p;
 	DispCensusForm f;
-	BHIP_TRY(disparityParams<OutT>(ctx, cfg, width, height, p));
+	BHIP_TRY(disparityParams<OutT>(ctx, cfg, width, height, p, five));
 	BHIP_TRY(disparityCensusForm(ctx, variant, width, height, f));
 	CtxScratch* sc = scratchOf(ctx);
 	DevImg<uint8_t> dl, dr;
@@ -101,7 +106,7 @@ static int disparityHost(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int va
 	BHIP_TRY(stageIn(ctx, sc->in0, hl, width, dl));
 	BHIP_TRY(stageIn(ctx, sc->in1, hr, width, dr));
 	BHIP_TRY(stageIn(ctx, sc->out0, hd, width, dd, false));
-	BHIP_TRY(disparityDevice<OutT>(ctx, p, f, dl, dr, dd));
+	BHIP_TRY(disparityDevice<OutT>(ctx, p, f, dl, dr, dd, five));
 	BHIP_TRY(stageOut(ctx, hd, dd));
 	return bhip_ctx_synchronize(ctx);
 }
@@ -285,6 +290,51 @@ int bhip_disparity_bm_census_dev_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_c
 	if (variant == DISP_SAD) return bhip_fail(ctx, BHIP_ERR_INVALID, "Unknown type -1");
 	return disparityDev<float>(ctx, cfg, variant, dev_left, lImageStride, lStride, dev_right, rImageStride, rStride, width, height, batch, dev_disp, dImageStride,
 							   dStride);
+}
+
+// blockMatchBest5: the same staging and checks, the five-region launches
+int bhip_disparity_bm5_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* left, int lStart, int lStride, const uint8_t* right, int rStart,
+							int rStride, int width, int height, uint8_t* disp, int dStart, int dStride) {
+	return disparityHost<uint8_t>(ctx, cfg, DISP_SAD, left, lStart, lStride, right, rStart, rStride, width, height, disp, dStart, dStride, true);
+}
+int bhip_disparity_bm5_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* left, int lStart, int lStride, const uint8_t* right, int rStart,
+							 int rStride, int width, int height, float* disp, int dStart, int dStride) {
+	return disparityHost<float>(ctx, cfg, DISP_SAD, left, lStart, lStride, right, rStart, rStride, width, height, disp, dStart, dStride, true);
+}
+int bhip_disparity_bm5_dev_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* dev_left, long long lImageStride, int lStride,
+								const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, uint8_t* dev_disp,
+								long long dImageStride, int dStride) {
+	return disparityDev<uint8_t>(ctx, cfg, DISP_SAD, dev_left, lImageStride, lStride, dev_right, rImageStride, rStride, width, height, batch, dev_disp, dImageStride, dStride, true);
+}
+int bhip_disparity_bm5_dev_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* dev_left, long long lImageStride, int lStride,
+								 const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, float* dev_disp,
+								 long long dImageStride, int dStride) {
+	return disparityDev<float>(ctx, cfg, DISP_SAD, dev_left, lImageStride, lStride, dev_right, rImageStride, rStride, width, height, batch, dev_disp, dImageStride, dStride, true);
+}
+
+int bhip_disparity_bm5_census_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* left, int lStart, int lStride,
+								   const uint8_t* right, int rStart, int rStride, int width, int height, uint8_t* disp, int dStart, int dStride) {
+	if (variant == DISP_SAD) return bhip_fail(ctx, BHIP_ERR_INVALID, "Unknown type -1");
+	return disparityHost<uint8_t>(ctx, cfg, variant, left, lStart, lStride, right, rStart, rStride, width, height, disp, dStart, dStride, true);
+}
+int bhip_disparity_bm5_census_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* left, int lStart, int lStride,
+									const uint8_t* right, int rStart, int rStride, int width, int height, float* disp, int dStart, int dStride) {
+	if (variant == DISP_SAD) return bhip_fail(ctx, BHIP_ERR_INVALID, "Unknown type -1");
+	return disparityHost<float>(ctx, cfg, variant, left, lStart, lStride, right, rStart, rStride, width, height, disp, dStart, dStride, true);
+}
+int bhip_disparity_bm5_census_dev_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* dev_left, long long lImageStride, int lStride,
+									   const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, uint8_t* dev_disp,
+									   long long dImageStride, int dStride) {
+	if (variant == DISP_SAD) return bhip_fail(ctx, BHIP_ERR_INVALID, "Unknown type -1");
+	return disparityDev<uint8_t>(ctx, cfg, variant, dev_left, lImageStride, lStride, dev_right, rImageStride, rStride, width, height, batch, dev_disp, dImageStride,
+								 dStride, true);
+}
+int bhip_disparity_bm5_census_dev_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* dev_left, long long lImageStride, int lStride,
+										const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, float* dev_disp,
+										long long dImageStride, int dStride) {
+	if (variant == DISP_SAD) return bhip_fail(ctx, BHIP_ERR_INVALID, "Unknown type -1");
+	return disparityDev<float>(ctx, cfg, variant, dev_left, lImageStride, lStride, dev_right, rImageStride, rStride, width, height, batch, dev_disp, dImageStride,
+							   dStride, true);
 }
 
 int bhip_distort_map_u8(bhip_ctx* ctx, const uint8_t* src, int sStart, int sStride, int sw, int sh, const float* map, int dw, int dh, int x0, int y0, int x1,

@@ -428,6 +428,14 @@ size_t bhip_disparity_census_scratch(int width, int height, int batch, int wordB
 template <class OutT>
 int bhip_launch_disparity_bm_census(bhip_ctx* ctx, DevImg<const uint8_t> left, DevImg<const uint8_t> right, const DispBmParams& c, int wordBytes,
 									const CensusSamples* s, uint8_t* scratch, DevImg<OutT> out);
+// FactoryStereoDisparity.blockMatchBest5: DisparityScoreBMBestFive_S32 with the same selectors (c.maxError holds the factory's 3 * rw * rh *
+// maxPerPixelError), SAD and CENSUS; scratch as for the plain forms.  An image with no selector column (W - (4*rx+1) < minD) or no output row
+// (H < 4*ry + 1) is filled with rangeDisparity.
+template <class OutT>
+int bhip_launch_disparity_bm5(bhip_ctx* ctx, DevImg<const uint8_t> left, DevImg<const uint8_t> right, const DispBmParams& c, uint8_t* scratch, DevImg<OutT> out);
+template <class OutT>
+int bhip_launch_disparity_bm5_census(bhip_ctx* ctx, DevImg<const uint8_t> left, DevImg<const uint8_t> right, const DispBmParams& c, int wordBytes,
+									 const CensusSamples* s, uint8_t* scratch, DevImg<OutT> out);
 
 // ---------------- image remap, ImageDistort (distort.hip) ----------------
 // where the source coordinates of a destination pixel come from: model == 0, a device map of (x, y) pairs, dw*dh per image and mapImageStride

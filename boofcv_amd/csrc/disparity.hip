@@ -1,5 +1,6 @@
 // Dense stereo disparity by block matching on GrayU8 pairs: FactoryStereoDisparity.blockMatch(ConfigDisparityBM, GrayU8, GrayU8 | GrayF32), errorType = SAD
-// on the pair itself, errorType = CENSUS on the census images of the pair (census.hip).
+// on the pair itself, errorType = CENSUS on the census images of the pair (census.hip).  FactoryStereoDisparity.blockMatchBest5, the five-region
+// form of both: k_disparity_bm5 in the second half of this file, on the same stages.
 //
 // Reference (F: = main/boofcv-feature/src/main/java/boofcv/):
 //   DisparityBlockMatchRowFormat.process              F:alg/feature/disparity/DisparityBlockMatchRowFormat.java:95-107
@@ -149,8 +150,8 @@ __device__ __forceinline__ void dispStage(uint32_t* dst, int pitch, const uint32
 }
 
 // Cost stage, one staged row pair into the slab entries (columns c0 .. c0+cs-1, disparity s) of the calling thread:
-// v[col] += H(an, mn)(col) - H(ao, mo)(col), H(col) = sum_{j<rw} cost(a[col + j], m[col + j]); HASOLD = false adds only.
-template <class Cost, bool HASOLD>
+// v[col] += H(an, mn)(col) - H(ao, mo)(col), H(col) = sum_{j<rw} cost(a[col + j], m[col + j]); HASOLD = false adds only.  VPITCH: u16 per slab row.
+template <class Cost, bool HASOLD, int VPITCH = DISP_VPITCH>
 __device__ __forceinline__ void dispCostRow(unsigned short* v, const typename Cost::Elem* an, const typename Cost::Elem* mn, const typename Cost::Elem* ao,
 											const typename Cost::Elem* mo, int c0, int cs, int rw) {
 	int hsum = 0;
@@ -164,7 +165,7 @@ __device__ __forceinline__ void dispCostRow(unsigned short* v, const typename Co
 		const int x0 = col - 1, x1 = col + rw - 1;
 		hsum = Cost::add(hsum, an[x1], mn[x1]) - Cost::add(0, an[x0], mn[x0]);
 		if constexpr (HASOLD) hsum += Cost::add(0, ao[x0], mo[x0]) - Cost::add(0, ao[x1], mo[x1]);
-		v += DISP_VPITCH;
+		v += VPITCH;
 		*v = (unsigned short)(*v + hsum);
 	}
 }
@@ -341,6 +342,11 @@ size_t bhip_disparity_census_scratch(int width, int height, int batch, int wordB
 }
 
 template <class Cost, class OutT>
+static int disp5Launch(bhip_ctx* ctx, const char* what, DevImg<const typename Cost::Elem> left, DevImg<const typename Cost::Elem> right, const DispBmParams& c,
+					   uint8_t* rtol, DevImg<OutT> out);
+
+// FIVE: the five-region launches (blockMatchBest5) on the census images instead of the plain ones
+template <class Cost, class OutT, bool FIVE = false>
 static int dispCensus(bhip_ctx* ctx, DevImg<const uint8_t> left, DevImg<const uint8_t> right, const DispBmParams& c, int denseRadius, const CensusSamples* s,
 					  uint8_t* scratch, DevImg<OutT> out) {
 	using Elem = typename Cost::Elem;
@@ -351,7 +357,8 @@ static int dispCensus(bhip_ctx* ctx, DevImg<const uint8_t> left, DevImg<const ui
 	const DevImg<Elem> dl{cl, (long long)w * h, w, w, h, batch}, dr{cr, (long long)w * h, w, w, h, batch};
 	BHIP_TRY(bhip_launch_census<Word>(ctx, left, denseRadius, s, DevImg<Word>{(Word*)cl, dl.imageStride, w, w, h, batch}));
 	BHIP_TRY(bhip_launch_census<Word>(ctx, right, denseRadius, s, DevImg<Word>{(Word*)cr, dr.imageStride, w, w, h, batch}));
-	return dispLaunch<Cost, OutT>(ctx, "bhip_launch_disparity_bm_census", dl, dr, c, scratch, out);
+	if constexpr (FIVE) return disp5Launch<Cost, OutT>(ctx, "bhip_launch_disparity_bm5_census", dl, dr, c, scratch, out);
+	else return dispLaunch<Cost, OutT>(ctx, "bhip_launch_disparity_bm_census", dl, dr, c, scratch, out);
 }
 
 template <class OutT>
@@ -366,3 +373,224 @@ template int bhip_launch_disparity_bm_census(bhip_ctx*, DevImg<const uint8_t>, D
 											 DevImg<uint8_t>);
 template int bhip_launch_disparity_bm_census(bhip_ctx*, DevImg<const uint8_t>, DevImg<const uint8_t>, const DispBmParams&, int, const CensusSamples*, uint8_t*,
 											 DevImg<float>);
+
+// ---------------- five-region block matching: FactoryStereoDisparity.blockMatchBest5 ----------------
+// Reference:
+//   FactoryStereoDisparity.blockMatchBest5            F:factory/feature/disparity/FactoryStereoDisparity.java:146-201 (maxError * 3)
+//   DisparityScoreBMBestFive_S32                      F:alg/feature/disparity/block/score/DisparityScoreBMBestFive_S32.java:147-267
+//   DisparityBlockMatchBestFive (border 2 * radius)   F:alg/feature/disparity/DisparityBlockMatchBestFive.java
+// With V(y, c, i) the sub-block cost C above, the score of selector column col (pixel col + 2*rx, row y) at disparity minD + i is
+//   F(y, col, i) = V(y, col+rx, i) + the two smallest of { V(y-ry, col, i), V(y-ry, col+2rx, i), V(y+ry, col, i), V(y+ry, col+2rx, i) }
+// (computeScoreFive's three compare() branches, compare(a, b) = Integer.compare(-a, -b)), and the selector is the S32 selector of plain block
+// matching configured with radius 2*rx: columns minD .. W-(4rx+1), region width 4rx+1 in selectRightToLeft.  Output rows are
+// max(2ry, 1) .. H-2ry-1: computeFirstRow selects nothing and computeRemainingRows starts at image row rh, so with ry = 0 row 0 is never
+// selected (plain block matching selects it in computeFirstRow).  On the right-anchored slab Vr(k, j) = V(k + minD + j, j) a shift of col by rx
+// at a fixed disparity is a shift of k by rx, so the right-to-left pass has the same five-region shape.
+//
+// k_disparity_bm5: a workgroup of 256 owns DISP5_TW = 32 selector columns x th output rows of one pair and keeps three u16 slabs in LDS, top =
+// V(y-ry), mid = V(y), bottom = V(y+ry), each TW + 2*rx anchor columns by `range` entries.  Each slab slides down the band with
+// V += H(entering row) - H(leaving row): six dispCostRow calls per output row where plain block matching has two, on th + 4*ry staged rows.
+// The selection stage evaluates F from five LDS reads, in 32 bits (F <= 3 * 57375 = 172125 does not fit u16; F << 9 | i needs 27 bits), for the
+// first minimum, the second minimum and the three scores of the sub-pixel fit.  Eight lanes share a column; a slab row is RC + 8 u16 = 68 or 132
+// dwords, 4 mod 32, so the 8 columns x 4 dwords a wave reads fall into 32 different banks.  RC, the slab's disparity capacity, is a template
+// parameter (128 or 256): the default range of 100 then runs three workgroups per CU where the full slab allows one.
+//   LDS per workgroup                          RC = 128 (range <= 128)                          RC = 256
+//   1-byte elements (SAD, census 3x3)          3*46*272 + 44*(60+188)   = 48448 B, 3 per CU     3*46*528 + 44*(60+316)   =  89408 B, 1 per CU
+//   4-byte elements (census 5x5, S64)          3*46*272 + 32*(60+188)*4 = 69280 B, 2 per CU     3*46*528 + 32*(60+316)*4 = 120992 B, 1 per CU
+// 1-byte elements: th = DISP5_TH = 16, 16 + 4*ry <= 44 staged rows.  4-byte elements: DISP5_ROWS_W32 = 32 staged rows, th = 32 - 4*ry output
+// rows (20 at the default ry = 3, 4 at ry = 7).
+#define DISP5_TW 32                                           // selector columns per workgroup
+#define DISP5_TH 16                                           // output rows per workgroup, 1-byte elements
+#define DISP5_COLS (DISP5_TW + 2 * BHIP_DISP_MAX_RADIUS)      // anchor columns of a slab
+#define DISP5_APITCH (DISP5_TW + 4 * BHIP_DISP_MAX_RADIUS)    // staged anchor elements per row: TW + 2*rx + rw - 1
+#define DISP5_ROWS (DISP5_TH + 4 * BHIP_DISP_MAX_RADIUS)      // staged rows, 1-byte elements
+#define DISP5_ROWS_W32 32                                     // staged rows, 4-byte elements: 32 - 4 * ry output rows per workgroup
+#define DISP5_LPC (256 / DISP5_TW)                            // lanes per selector column
+
+template <class Cost>
+__host__ __device__ __forceinline__ int disp5TileRows(int ry) {
+	if constexpr (sizeof(typename Cost::Elem) == 1) return DISP5_TH;
+	else return DISP5_ROWS_W32 - 4 * ry;
+}
+// first output row: DisparityScoreBMBestFive_S32 selects from image row max(rh, 4*ry) on
+__host__ __device__ __forceinline__ int disp5FirstRow(int ry) { return ry ? 2 * ry : 1; }
+
+// the five-region score of one selector column: slab rows of top / bottom at col and col + 2*rx, of mid at col + rx
+struct Disp5Score {
+	const unsigned short *t0, *t1, *m, *b0, *b1;
+	__device__ __forceinline__ int operator()(int i) const {
+		const int v0 = t0[i], v1 = t1[i], v2 = b0[i], v3 = b1[i];
+		const int lo01 = min(v0, v1), hi01 = max(v0, v1), lo23 = min(v2, v3), hi23 = max(v2, v3);
+		return (int)m[i] + min(lo01, lo23) + min(max(lo01, lo23), min(hi01, hi23));   // the two smallest of four
+	}
+};
+// dispFirstMin / dispSecondMin on F, DISP5_LPC lanes (q) per column
+__device__ __forceinline__ unsigned int disp5FirstMin(const Disp5Score& F, int lm, int q) {
+	unsigned int key = 0xFFFFFFFFu;
+	for (int i = q; i < lm; i += DISP5_LPC) key = min(key, ((unsigned int)F(i) << 9) | (unsigned int)i);
+#pragma unroll
+	for (int m = 1; m < DISP5_LPC; m <<= 1) key = min(key, (unsigned int)__shfl_xor((int)key, m, 64));
+	return key;
+}
+__device__ __forceinline__ int disp5SecondMin(const Disp5Score& F, int lm, int q, int best, bool on) {
+	int second = 2147483647;
+	if (on)
+		for (int i = q; i < lm; i += DISP5_LPC)
+			if (i < best - 1 || i > best + 1) second = min(second, F(i));
+#pragma unroll
+	for (int m = 1; m < DISP5_LPC; m <<= 1) second = min(second, __shfl_xor(second, m, 64));
+	return second;
+}
+
+template <class Cost, int RC, bool RTOL, class OutT>
+__global__ __launch_bounds__(256) void k_disparity_bm5(DispKernelParams P) {
+	using Elem = typename Cost::Elem;
+	constexpr int VP = RC + 8, MP = DISP5_APITCH + RC, ROWS = sizeof(Elem) == 1 ? DISP5_ROWS : DISP5_ROWS_W32, SLAB = DISP5_COLS * VP;
+	__shared__ __attribute__((aligned(16))) unsigned short V[3 * SLAB];   // top, mid, bottom
+	__shared__ __attribute__((aligned(16))) Elem sa[ROWS * DISP5_APITCH];
+	__shared__ __attribute__((aligned(16))) Elem sm[ROWS * MP];
+	const DispBmParams& c = P.c;
+	const int w = P.w, h = P.h, S = c.range, rx = c.rx, ry = c.ry, rw = 2 * rx + 1, rh = 2 * ry + 1, rw5 = 4 * rx + 1;
+	const long long b = blockIdx.z;
+	const Elem* L = (const Elem*)P.left + b * P.lImageStride;
+	const Elem* R = (const Elem*)P.right + b * P.rImageStride;
+	const int nc = DISP5_TW + 2 * rx;                                 // anchor columns of the slabs
+	const int a0 = (RTOL ? 0 : c.minD) + blockIdx.x * DISP5_TW;       // the tile's first selector column = block start column of its first anchor
+	const int th = disp5TileRows<Cost>(ry);
+	const int yb0 = disp5FirstRow(ry) + blockIdx.y * th, yb1 = min(yb0 + th, h - 2 * ry);
+	const int nrows = yb1 - yb0 + 4 * ry;                             // staged image rows yb0 - 2*ry ..
+	const int acount = nc + rw - 1, mcount = acount + S - 1;
+	const int m0 = RTOL ? a0 + c.minD : a0 - c.minD - (S - 1);        // image column of sm[0]
+	for (int i = threadIdx.x; i < ROWS * DISP5_APITCH * (int)sizeof(Elem) / 4; i += 256) ((unsigned int*)sa)[i] = 0u;
+	for (int i = threadIdx.x; i < ROWS * MP * (int)sizeof(Elem) / 4; i += 256) ((unsigned int*)sm)[i] = 0u;
+	__syncthreads();
+	dispStage(sa, DISP5_APITCH, RTOL ? R : L, RTOL ? P.rStride : P.lStride, w, yb0 - 2 * ry, nrows, a0, acount);
+	dispStage(sm, MP, RTOL ? L : R, RTOL ? P.lStride : P.rStride, w, yb0 - 2 * ry, nrows, m0, mcount);
+	__syncthreads();
+	// cost stage: thread = (column segment, disparity s)
+	const int sp = S <= 64 ? 64 : S <= 128 ? 128 : 256;
+	const int s = threadIdx.x & (sp - 1), seg = threadIdx.x / sp, cs = (nc * sp + 255) / 256;
+	const int cb = seg * cs, cn = min(cs, nc - cb);                   // this thread's anchor columns cb .. cb + cn - 1
+	const int mofs = RTOL ? s : S - 1 - s;
+	unsigned short* vt = V + cb * VP + s;
+	unsigned short* vm = vt + SLAB;
+	unsigned short* vb = vm + SLAB;
+	// selection stage: thread = (selector column, lane q of DISP5_LPC)
+	const int col = threadIdx.x / DISP5_LPC, q = threadIdx.x % DISP5_LPC;
+	const int x = a0 + col;
+	const Disp5Score F{V + col * VP, V + (col + 2 * rx) * VP, V + SLAB + (col + rx) * VP, V + 2 * SLAB + col * VP, V + 2 * SLAB + (col + 2 * rx) * VP};
+	int lm = 0;   // disparities to search; 0: no selector column here
+	if constexpr (RTOL) {
+		if (x <= w - rw5 - c.minD) lm = max(min(w - rw5, x + c.minD + S) - x - c.minD, 1);   // selectRightToLeft, region width 4*rx + 1
+	} else {
+		if (x <= w - rw5) lm = min(x - c.minD + 1, S);                                         // maxDisparityAtColumnL2R
+	}
+	for (int y = yb0; y < yb1; y++) {
+		const int r0 = y - yb0;   // staged index of image row y - 2*ry: top = rows r0 .. r0+2ry, mid = r0+ry .. r0+3ry, bottom = r0+2ry .. r0+4ry
+		if (s < S && cn > 0) {
+			if (y == yb0) {
+				for (int k = 0; k < cn; k++) vt[k * VP] = vm[k * VP] = vb[k * VP] = 0;
+				for (int d = 0; d < rh; d++) {
+					dispCostRow<Cost, false, VP>(vt, sa + (r0 + d) * DISP5_APITCH, sm + (r0 + d) * MP + mofs, nullptr, nullptr, cb, cn, rw);
+					dispCostRow<Cost, false, VP>(vm, sa + (r0 + ry + d) * DISP5_APITCH, sm + (r0 + ry + d) * MP + mofs, nullptr, nullptr, cb, cn, rw);
+					dispCostRow<Cost, false, VP>(vb, sa + (r0 + 2 * ry + d) * DISP5_APITCH, sm + (r0 + 2 * ry + d) * MP + mofs, nullptr, nullptr, cb, cn, rw);
+				}
+			} else {
+				const int nt = r0 + 2 * ry, ot = r0 - 1;   // entering and leaving row of top; mid: + ry; bottom: + 2*ry
+				dispCostRow<Cost, true, VP>(vt, sa + nt * DISP5_APITCH, sm + nt * MP + mofs, sa + ot * DISP5_APITCH, sm + ot * MP + mofs, cb, cn, rw);
+				dispCostRow<Cost, true, VP>(vm, sa + (nt + ry) * DISP5_APITCH, sm + (nt + ry) * MP + mofs, sa + (ot + ry) * DISP5_APITCH,
+											sm + (ot + ry) * MP + mofs, cb, cn, rw);
+				dispCostRow<Cost, true, VP>(vb, sa + (nt + 2 * ry) * DISP5_APITCH, sm + (nt + 2 * ry) * MP + mofs, sa + (ot + 2 * ry) * DISP5_APITCH,
+											sm + (ot + 2 * ry) * MP + mofs, cb, cn, rw);
+			}
+		}
+		__syncthreads();
+		const unsigned int key = disp5FirstMin(F, lm, q);
+		const int best = (int)(key & 511u), sBest = (int)(key >> 9);
+		if constexpr (RTOL) {
+			if (lm > 0 && q == 0) P.rtol[(b * h + y) * w + x] = (uint8_t)best;
+		} else {
+			const int second = disp5SecondMin(F, lm, q, best, c.textureThr > 0 && lm >= 3);
+			if (lm > 0 && q == 0) {
+				int rBest = 0;
+				if (c.rtolTol >= 0 && sBest <= c.maxError) rBest = P.rtol[(b * h + y) * w + (x - best - c.minD)];
+				const int d = dispChecks(c, best, sBest, second, lm, rBest);
+				OutT* o = (OutT*)P.out + b * P.oImageStride + (long long)y * P.oStride + (x + 2 * rx);
+				if constexpr (sizeof(OutT) == 1) {
+					*o = (OutT)d;   // (byte)value
+				} else {
+					float f = (float)d;
+					if (d > 0 && d < lm - 1) {   // the rejection value range + 1 is >= lm - 1
+						const int c0 = F(d - 1), c1 = F(d), c2 = F(d + 1);
+						const float offset = (float)(c0 - c2) / (float)(2 * (c0 - 2 * c1 + c2));
+						f = (float)d + offset;
+					}
+					*o = f;
+				}
+			}
+		}
+		__syncthreads();
+	}
+}
+
+// the launches of one batch: border fill (the whole view where no selector column or output row exists), right-to-left minima, selection
+template <class Cost, int RC, class OutT>
+static int disp5LaunchRC(bhip_ctx* ctx, DevImg<const typename Cost::Elem> left, DevImg<const typename Cost::Elem> right, const DispBmParams& c, uint8_t* rtol,
+						 DevImg<OutT> out) {
+	const int w = left.width, h = left.height, batch = left.batch;
+	const int y0 = disp5FirstRow(c.ry), y1 = h - 2 * c.ry, ncol = w - (4 * c.rx + 1) - c.minD + 1;
+	DispKernelParams P{(const uint8_t*)left.data, (const uint8_t*)right.data, left.imageStride, right.imageStride, left.stride, right.stride, w, h, c, rtol,
+					   out.data, out.imageStride, out.stride};
+	const double px = (double)w * h * batch, ops = 3.0 * px * c.range, eb = sizeof(typename Cost::Elem);
+	{
+		ProfScope ps(ctx, "k_disparity_border", 0);
+		hipLaunchKernelGGL(k_disparity_border<OutT>, dim3((w + 63) / 64, (h + 3) / 4, batch), dim3(256), 0, ctx->stream, out.data, out.imageStride, out.stride, w, h,
+						   2 * c.rx + c.minD, w - 2 * c.rx, y0, y1, (OutT)c.range);
+	}
+	if (ncol > 0 && y1 > y0) {
+		const int th = disp5TileRows<Cost>(c.ry);
+		const dim3 grid((ncol + DISP5_TW - 1) / DISP5_TW, (y1 - y0 + th - 1) / th, batch);
+		if (c.rtolTol >= 0) {
+			ProfScope ps(ctx, "k_disparity_bm5_rtol", (2.0 * eb + 1.0) * px, ops);
+			hipLaunchKernelGGL((k_disparity_bm5<Cost, RC, true, uint8_t>), grid, dim3(256), 0, ctx->stream, P);
+		}
+		{
+			ProfScope ps(ctx, sizeof(OutT) == 1 ? "k_disparity_bm5_u8" : "k_disparity_bm5_f32", (2.0 * eb + sizeof(OutT) + (c.rtolTol >= 0 ? 1.0 : 0.0)) * px, ops);
+			hipLaunchKernelGGL((k_disparity_bm5<Cost, RC, false, OutT>), grid, dim3(256), 0, ctx->stream, P);
+		}
+	}
+	BHIP_HIP(ctx, hipGetLastError());
+	return BHIP_OK;
+}
+
+template <class Cost, class OutT>
+static int disp5Launch(bhip_ctx* ctx, const char* what, DevImg<const typename Cost::Elem> left, DevImg<const typename Cost::Elem> right, const DispBmParams& c,
+					   uint8_t* rtol, DevImg<OutT> out) {
+	const int w = left.width, h = left.height, batch = left.batch;
+	if (batch <= 0 || w <= 0 || h <= 0) return BHIP_OK;
+	if (c.rx < 0 || c.ry < 0 || c.rx > BHIP_DISP_MAX_RADIUS || c.ry > BHIP_DISP_MAX_RADIUS || c.range < 1 || c.range > BHIP_DISP_MAX_RANGE || c.minD < 0 ||
+		c.minD + c.range > w - 2 * c.rx || h < 2 * c.ry + 1)
+		return bhip_fail(ctx, BHIP_ERR_INVALID, std::string(what) + ": outside the kernel's limits");
+	if (c.range <= 128) return disp5LaunchRC<Cost, 128, OutT>(ctx, left, right, c, rtol, out);
+	return disp5LaunchRC<Cost, 256, OutT>(ctx, left, right, c, rtol, out);
+}
+
+template <class OutT>
+int bhip_launch_disparity_bm5(bhip_ctx* ctx, DevImg<const uint8_t> left, DevImg<const uint8_t> right, const DispBmParams& c, uint8_t* scratch, DevImg<OutT> out) {
+	return disp5Launch<DispCostSad, OutT>(ctx, "bhip_launch_disparity_bm5", left, right, c, scratch, out);
+}
+template int bhip_launch_disparity_bm5(bhip_ctx*, DevImg<const uint8_t>, DevImg<const uint8_t>, const DispBmParams&, uint8_t*, DevImg<uint8_t>);
+template int bhip_launch_disparity_bm5(bhip_ctx*, DevImg<const uint8_t>, DevImg<const uint8_t>, const DispBmParams&, uint8_t*, DevImg<float>);
+
+template <class OutT>
+int bhip_launch_disparity_bm5_census(bhip_ctx* ctx, DevImg<const uint8_t> left, DevImg<const uint8_t> right, const DispBmParams& c, int wordBytes,
+									 const CensusSamples* s, uint8_t* scratch, DevImg<OutT> out) {
+	if (wordBytes == 1) return dispCensus<DispCostCensus8, OutT, true>(ctx, left, right, c, 1, nullptr, scratch, out);
+	if (wordBytes == 4) return dispCensus<DispCostCensus32, OutT, true>(ctx, left, right, c, 2, nullptr, scratch, out);
+	if (wordBytes == 8 && s) return dispCensus<DispCostCensus64, OutT, true>(ctx, left, right, c, 0, s, scratch, out);
+	return bhip_fail(ctx, BHIP_ERR_INVALID, "bhip_launch_disparity_bm5_census: no such census word");
+}
+template int bhip_launch_disparity_bm5_census(bhip_ctx*, DevImg<const uint8_t>, DevImg<const uint8_t>, const DispBmParams&, int, const CensusSamples*, uint8_t*,
+											  DevImg<uint8_t>);
+template int bhip_launch_disparity_bm5_census(bhip_ctx*, DevImg<const uint8_t>, DevImg<const uint8_t>, const DispBmParams&, int, const CensusSamples*, uint8_t*,
+											  DevImg<float>);

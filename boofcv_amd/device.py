@@ -286,6 +286,30 @@ class DeviceImageOps:
         _check(self.ctx, fn(self.ctx._h, C.byref(config._c()) if config is not None else None, int(variant), lp, lis, lrs, rp, ris, rrs, W, H, B, op, ois, ors))
         return out
 
+    def disparityBM5(self, left, right, config=None, variant=None, subpixel=True, out=None):
+        """StereoDisparity.process of FactoryStereoDisparity.blockMatchBest5 on uint8 pairs [B,H,W] -> the disparity [B,H,W]: float32 when subpixel,
+        uint8 otherwise.  variant None: errorType = SAD; a census.CensusVariants: errorType = CENSUS with that variant (config.subpixel and
+        config.errorType are not read; `out`, any row / image stride, is written in place and as a whole).  config: a ConfigDisparityBMBest5 or
+        ConfigDisparityBM, None = the reference defaults."""
+        lp, lis, lrs, W, H, B = _geom(left, torch.uint8)
+        rp, ris, rrs, W2, H2, B2 = _geom(right, torch.uint8)
+        if (W, H, B) != (W2, H2, B2):
+            raise IllegalArgumentException("Image shapes do not match")
+        dt = torch.float32 if subpixel else torch.uint8
+        if out is None:
+            out = torch.empty((B, H, W), dtype=dt, device=left.device)
+        op, ois, ors, W3, H3, B3 = _geom(out, dt)
+        if (W, H, B) != (W3, H3, B3):
+            raise IllegalArgumentException("input and disparity shapes differ")
+        cfg = C.byref(config._c()) if config is not None else None
+        if variant is None:
+            fn = self.L.bhip_disparity_bm5_dev_u8_f32 if subpixel else self.L.bhip_disparity_bm5_dev_u8_u8
+            _check(self.ctx, fn(self.ctx._h, cfg, lp, lis, lrs, rp, ris, rrs, W, H, B, op, ois, ors))
+        else:
+            fn = self.L.bhip_disparity_bm5_census_dev_u8_f32 if subpixel else self.L.bhip_disparity_bm5_census_dev_u8_u8
+            _check(self.ctx, fn(self.ctx._h, cfg, int(variant), lp, lis, lrs, rp, ris, rrs, W, H, B, op, ois, ors))
+        return out
+
     def denseFlowKlt(self, prev, curr, config=None, radius=3, out=None, tracks=None, form=_lib.BHIP_FLOW_FORM_AUTO):
         """DenseOpticalFlow.process of FactoryDenseOpticalFlow.flowKlt on float32 or uint8 pairs [B,H,W] -> the flow [B,H,W,2] float32, invalid
         pixels (NaN, 0).  config: a PkltConfig (its KltConfig and pyramidScaling; templateRadius is not read), None = the reference defaults.

@@ -290,8 +290,8 @@ int bhip_fast_f32(bhip_ctx* ctx, const float* image, int start, int stride, int 
  * rangeDisparity outside the region above, where the reference leaves what an earlier pair put there -- the result of a freshly constructed
  * reference object.
  * Limits: regionRadiusX, regionRadiusY <= 7 and rangeDisparity <= 256 (<= 253 for U8, by the validation); beyond them BHIP_ERR_UNSUPPORTED and
- * nothing is written.  errorType = CENSUS: bhip_disparity_bm_census_u8_u8 / _u8_f32.  blockMatchBest5, NCC, SGM and the GrayF32 / GrayU16 / GrayS16
- * inputs have no entry point. */
+ * nothing is written.  errorType = CENSUS: bhip_disparity_bm_census_u8_u8 / _u8_f32.  blockMatchBest5: bhip_disparity_bm5_*.  NCC, SGM and the
+ * GrayF32 / GrayU16 / GrayS16 inputs have no entry point. */
 int bhip_disparity_bm_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* left, int lStart, int lStride, const uint8_t* right, int rStart,
 							int rStride, int width, int height, uint8_t* disp, int dStart, int dStride);
 int bhip_disparity_bm_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* left, int lStart, int lStride, const uint8_t* right, int rStart,
@@ -342,11 +342,44 @@ int bhip_census_sample_u8_s64(bhip_ctx* ctx, const int* samplesXY, int nSamples,
  * radius + 1 in either direction (bhip_census_*).
  * Limits, BHIP_ERR_UNSUPPORTED and nothing is written: regionRadiusX, regionRadiusY <= 7, rangeDisparity <= 256 (<= 253 for U8 by the validation).
  * Deviations: those of bhip_disparity_bm_u8_u8 and of bhip_census_*; the census images are context scratch (getCLeft / getCRight of the
- * reference's wrapper: run bhip_census_* on the input).  blockMatchBest5, NCC, SGM and the GrayF32 / GrayU16 / GrayS16 inputs have no entry point. */
+ * reference's wrapper: run bhip_census_* on the input).  blockMatchBest5: bhip_disparity_bm5_census_*.  NCC, SGM and the GrayF32 / GrayU16 / GrayS16
+ * inputs have no entry point. */
 int bhip_disparity_bm_census_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* left, int lStart, int lStride,
 								   const uint8_t* right, int rStart, int rStride, int width, int height, uint8_t* disp, int dStart, int dStride);
 int bhip_disparity_bm_census_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* left, int lStart, int lStride,
 									const uint8_t* right, int rStart, int rStride, int width, int height, float* disp, int dStart, int dStride);
+/* StereoDisparity.process(left, right) of FactoryStereoDisparity.blockMatchBest5(ConfigDisparityBMBest5, GrayU8.class, GrayU8.class | GrayF32.class)
+ * (F:factory/feature/disparity/FactoryStereoDisparity.java:146-201): DisparityScoreBMBestFive_S32 (F:alg/feature/disparity/block/score/
+ * DisparityScoreBMBestFive_S32.java:147-267) over the row scores and the selectors of bhip_disparity_bm_u8_u8 / _u8_f32 (SAD) and of
+ * bhip_disparity_bm_census_u8_u8 / _u8_f32 (CENSUS, `variant` a CensusVariants ordinal).  ConfigDisparityBMBest5 adds no field to ConfigDisparityBM,
+ * so cfg is a bhip_disparity_bm_cfg; cfg == NULL: the reference defaults.  With V(y,c,i) = the cost C(y,c,i) of bhip_disparity_bm_u8_u8 (the
+ * sub-block that starts at column c, rows y-ry..y+ry), rx = regionRadiusX, ry = regionRadiusY, rw = 2*rx+1, rh = 2*ry+1:
+ *   score   for a selector column col in [minDisparity, W-(4*rx+1)] and i in [0, lm), lm = min(col - minDisparity + 1, rangeDisparity):
+ *           F(y,col,i) = V(y,col+rx,i) + the two smallest of { V(y-ry,col,i), V(y-ry,col+2*rx,i), V(y+ry,col,i), V(y+ry,col+2*rx,i) }
+ *           (computeScoreFive's three compare() tests with SelectErrorWithChecks_S32.compare(a,b) = Integer.compare(-a,-b); ties give equal sums).
+ *           The result goes to pixel (col + 2*rx, y).  F reaches 3*255*15*15 = 172125: an int, not 16 bits.
+ *   select  best, error, R to L, texture and store: the rules of bhip_disparity_bm_u8_u8 on F, the selector configured with radius 2*rx
+ *           (computeDisparity.configure(disparity, minDisparity, maxDisparity, radiusX*2)): region width 4*rx+1 in the R to L search,
+ *           n = min(W-(4*rx+1), k+maxD) - k - minDisparity.
+ *   error   maxError = (int)(rw*rh*maxPerPixelError*3) in double (FactoryStereoDisparity.java:159-162: three regions).
+ *   rows    max(2*ry, 1) <= y < H-2*ry: computeFirstRow selects nothing and computeRemainingRows selects from image row max(rh, 4*ry) on, so
+ *           with ry == 0 row 0 is never selected (plain block matching selects it in computeFirstRow).
+ *   rest    every other pixel -- rows outside that range, columns < 2*rx+minDisparity and >= W-2*rx -- holds rangeDisparity.
+ * Validation, BHIP_ERR_INVALID and nothing is written: everything bhip_disparity_bm_u8_u8 refuses, with the same tests --
+ * minDisparity + rangeDisparity > W - 2*regionRadiusX (DisparityBlockMatchRowFormat.process tests radiusX, not 2*radiusX) and H < rh, where the
+ * reference indexes outside the image; for the census forms also what bhip_disparity_bm_census_u8_u8 refuses.  Two shapes are legal and answer
+ * BHIP_OK with the whole view set to rangeDisparity: rh <= H < 4*ry+1 (no output row), and W-(4*rx+1) < minDisparity (no selector column).
+ * Limits, BHIP_ERR_UNSUPPORTED and nothing is written: regionRadiusX, regionRadiusY <= 7, rangeDisparity <= 256 (<= 253 for U8 by the validation).
+ * Deviations: those of bhip_disparity_bm_u8_u8 (the view is written as a whole: the result of a freshly constructed reference object, single
+ * threaded: BoofConcurrency.USE_CONCURRENT = false, one block over all rows) and, for the census forms, of bhip_disparity_bm_census_u8_u8. */
+int bhip_disparity_bm5_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* left, int lStart, int lStride, const uint8_t* right, int rStart,
+							 int rStride, int width, int height, uint8_t* disp, int dStart, int dStride);
+int bhip_disparity_bm5_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* left, int lStart, int lStride, const uint8_t* right, int rStart,
+							  int rStride, int width, int height, float* disp, int dStart, int dStride);
+int bhip_disparity_bm5_census_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* left, int lStart, int lStride,
+									const uint8_t* right, int rStart, int rStride, int width, int height, uint8_t* disp, int dStart, int dStride);
+int bhip_disparity_bm5_census_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* left, int lStart, int lStride,
+									 const uint8_t* right, int rStart, int rStride, int width, int height, float* disp, int dStart, int dStride);
 /* ---- image remap: ImageDistort<T,T>, GrayU8 -> GrayU8 and GrayF32 -> GrayF32 (distort.hip) ---- */
 typedef enum { BHIP_INTERP_NEAREST_NEIGHBOR = 0, BHIP_INTERP_BILINEAR = 1, BHIP_INTERP_BICUBIC = 2, BHIP_INTERP_POLYNOMIAL4 = 3 } bhip_interp;   /* InterpolationType ordinals */
 typedef enum { BHIP_BORDER_SKIP = 0, BHIP_BORDER_EXTENDED = 1, BHIP_BORDER_NORMALIZED = 2, BHIP_BORDER_REFLECT = 3, BHIP_BORDER_WRAP = 4, BHIP_BORDER_ZERO = 5 } bhip_border;   /* BorderType ordinals */
@@ -710,6 +743,23 @@ int bhip_disparity_bm_census_dev_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cf
 int bhip_disparity_bm_census_dev_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* dev_left, long long lImageStride, int lStride,
 										const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, float* dev_disp,
 										long long dImageStride, int dStride);
+/* bhip_disparity_bm5_u8_u8 / _u8_f32 / _census_u8_u8 / _census_u8_f32 on a batch of device pairs (strides in elements; any byte alignment of a GrayU8
+ * view): pair b is dev_left + b*lImageStride, dev_right + b*rImageStride and writes dev_disp + b*dImageStride, the whole width x height view and
+ * nothing outside it.  The census forms first write the census images into context scratch, as bhip_disparity_bm_census_dev_u8_u8 does.  Then
+ * three launches without a host synchronisation: the fill, the right-to-left minima of F (one byte per pixel of context scratch), the selection.
+ * No cost volume leaves the chip: a workgroup keeps the three rows of sub-block sums it needs in LDS. */
+int bhip_disparity_bm5_dev_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* dev_left, long long lImageStride, int lStride,
+								 const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, uint8_t* dev_disp,
+								 long long dImageStride, int dStride);
+int bhip_disparity_bm5_dev_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, const uint8_t* dev_left, long long lImageStride, int lStride,
+								  const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, float* dev_disp,
+								  long long dImageStride, int dStride);
+int bhip_disparity_bm5_census_dev_u8_u8(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* dev_left, long long lImageStride, int lStride,
+										const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, uint8_t* dev_disp,
+										long long dImageStride, int dStride);
+int bhip_disparity_bm5_census_dev_u8_f32(bhip_ctx* ctx, const bhip_disparity_bm_cfg* cfg, int variant, const uint8_t* dev_left, long long lImageStride, int lStride,
+										 const uint8_t* dev_right, long long rImageStride, int rStride, int width, int height, int batch, float* dev_disp,
+										 long long dImageStride, int dStride);
 /* bhip_template_intensity_u8 / _f32 on a batch of device images (strides in elements; any byte alignment of a GrayU8 view): image b is
  * dev_image + b*iImageStride and writes dev_intensity + b*oImageStride, the whole width x height view and nothing outside it.  tImageStride /
  * mImageStride 0: one template / mask shared by the batch; otherwise image b is matched against dev_templ + b*tImageStride (and

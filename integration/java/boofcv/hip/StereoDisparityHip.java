@@ -20,8 +20,8 @@ import java.nio.ByteOrder;
  *  Results are bit for bit those of the Java classes.  Deviations (include/boofhip.h): the disparity image is written as a whole by every
  *  process() -- rangeDisparity in the rows and columns the Java code never writes, where it keeps what an earlier pair left there (the result of
  *  a freshly constructed Java object); an image lower than the region is refused.  Limits: regionRadiusX / Y &lt;= 7, rangeDisparity &lt;= 256;
- *  beyond them check() throws RuntimeException and the caller uses the Java path, as for NCC, blockMatchBest5 and the other input types.
- *  errorType = CENSUS: StereoDisparityCensusHip.
+ *  beyond them check() throws RuntimeException and the caller uses the Java path, as for NCC and the other input types.
+ *  errorType = CENSUS: StereoDisparityCensusHip.  blockMatchBest5: StereoDisparityBest5Hip.
  *  UNCOMPILED SOURCE. */
 public class StereoDisparityHip<DI extends ImageGray<DI>> implements StereoDisparity<GrayU8, DI> {
 	private final ConfigDisparityBM config;
