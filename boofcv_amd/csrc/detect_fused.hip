@@ -56,7 +56,8 @@ struct FusedParams {
 	int expW, expH;
 	long long expImageStride;
 	long long expSlotOff[2];
-	int ablate;   // timing experiments only (BHIP_FUSED_ABLATE): 1 skip the intensity phase, 2 skip the NMS phase, 4 skip staging, 32 frame tiles stop after staging
+	int ablate;   // timing experiments only (BHIP_FUSED_ABLATE): 1 skip the intensity phase, 2 skip the NMS phase, 4 skip staging, 32 frame tiles stop after staging,
+	              // 64 skip the export phase, 128 stop in front of the two global atomics of an emission
 };
 
 __device__ __forceinline__ float fblock_zero(const float* __restrict__ d, int stride, int W, int H, int x0, int y0, int x1, int y1) {
@@ -260,13 +261,11 @@ struct FixedGeo {
 	// lanes' consecutive output pixels (columns xx = x*SKIP apart) then reads consecutive LDS words -- no bank conflicts for SKIP > 1.
 	static constexpr int IWp = ((IW + SKIP - 1) / SKIP) | 1;      // pitch of one plane row
 	static constexpr int plane = IH * IWp;
-	// LDS: the patch, the two dense mid levels (1 and 2 of the four), survivor list + their nine sparse outer-level values
-	static constexpr int SURV = 2 * ((TX + R) / (R + 1)) * ((TY + R) / (R + 1));   // strict (2R+1)^2 maxima of two mid levels: one per (R+1)^2 block at most
-	static constexpr int CHUNK = 64;   // survivors whose nine outer-level values are held at a time
+	// LDS: the patch, the two dense mid levels (1 and 2 of the four), the NMS candidate codes and their counter
 	static constexpr int NCAND = TX * TY + 2;                     // two mid levels, at most every second core pixel (rounded up) each
 	static_assert(TX < 64 && TY < 64, "16-bit NMS candidate codes");
-	static constexpr int SPARSE = CHUNK * 9 > (NCAND + 1) / 2 ? CHUNK * 9 : (NCAND + 1) / 2;   // floats: sparse values, before that the candidate codes
-	static constexpr int ldsFloats = SKIP * plane + 2 * ITH * ITp + SURV + SPARSE + 4;
+	static constexpr int CANDF = (NCAND + 1) / 2;                 // floats that hold the candidate codes
+	static constexpr int ldsFloats = SKIP * plane + 2 * ITH * ITp + CANDF + 4;
 	static constexpr int K0 = rFmax + 1;                          // column of (xx) inside the patch, minus SKIP*(x - x0 + R)
 	// LDS offset of the tap at (row offset ro, column offset co) relative to the pixel's base pointer (row yy-Y0, column slot x-x0+R)
 	static constexpr int tap(int ro, int co) { return ((K0 + co) % SKIP) * plane + ro * IWp + (K0 + co) / SKIP; }
@@ -538,26 +537,11 @@ __device__ __forceinline__ void fusedLevelDense(const FusedParams& P, const T* i
 	}
 }
 
-// checkMax on the lower and the upper level + polyPeak fits + emission for an NMS survivor of mid slot m at tile pixel (px, py):
-// FastHessianFeatureDetector.findLocalScaleSpaceMax :278-297.  The outer level on the far side of the mid level (level 0 below mid level 1,
-// level 3 above mid level 2) arrives as "all nine neighbours below val" + its centre value; the other neighbour level is the other dense
-// mid level.
+// polyPeak fits + emission for a pixel that has passed checkMax on the lower and the upper level, mid slot M at image pixel (x, y):
+// FastHessianFeatureDetector.findLocalScaleSpaceMax :285-297.  `self` points at the pixel in its mid-level tile; lowerC / upperC are the
+// centre values of the two neighbour levels.
 template <class G, int SKIP, int R>
-__device__ __forceinline__ void fusedFinish(const FusedParams& P, const FusedMid& M, const float* mid1, const float* mid2, bool outerBelow, float outerCentre,
-											int px, int py, int x, int y, float val, int img) {
-	const bool lowMid = M.level == 1;
-	const float* self = (lowMid ? mid1 : mid2) + (py + R) * G::ITp + (px + R);
-	const float* other = (lowMid ? mid2 : mid1) + (py + R) * G::ITp + (px + R);
-	if (!outerBelow) return;
-	float dn[9];
-	bool ok = true;
-#pragma unroll
-	for (int q = 0; q < 9; q++) {
-		dn[q] = other[(q / 3 - 1) * G::ITp + (q % 3 - 1)];
-		if (dn[q] >= val) ok = false;
-	}
-	if (!ok) return;
-	const float lowerC = lowMid ? outerCentre : dn[4], upperC = lowMid ? dn[4] : outerCentre;
+__device__ __forceinline__ void fusedFinish(const FusedParams& P, const FusedMid& M, const float* self, float lowerC, float upperC, int x, int y, float val, int img) {
 	const float peakX = fpolyPeak(self[-1], val, self[1]);
 	const float peakY = fpolyPeak(self[-G::ITp], val, self[G::ITp]);
 	const float peakS = fpolyPeak(lowerC, val, upperC);
@@ -566,7 +550,7 @@ __device__ __forceinline__ void fusedFinish(const FusedParams& P, const FusedMid
 	const float interpS = (float)M.sizeMid + peakS * (float)(M.sizeMid - M.sizeLower);
 	const double scale = 1.2 * (double)interpS / 9.0;
 	constexpr int step = R + 1;
-	if (BHIP_ABLATE(P, 7)) return;   // timing experiments run on garbage: never emit
+	if (BHIP_ABLATE(P, 7 | 128)) return;   // timing experiments run on garbage: never emit (128: everything but the emission)
 	const int b = M.border;
 	const unsigned int bit = M.bitBase + (unsigned)((y - b) / step) * (unsigned)M.nbx + (unsigned)((x - b) / step);
 	atomicOr(&P.bitmap[(long long)img * P.bitmapWords + (bit >> 5)], 1u << (bit & 31));
@@ -583,11 +567,12 @@ __device__ __forceinline__ void fusedFinish(const FusedParams& P, const FusedMid
 }
 
 template <class T, int SKIP, int SIZE0, int STEPSZ, int NL, int R, int ITWT, int TYT, int NTT = 256>
-__global__ __launch_bounds__(NTT) void k_detect_fused_fixed(FusedParams P) {
+// (sixteen waves per workgroup: two workgroups per CU are eight waves per SIMD, which leaves 64 VGPRs each)
+__global__ __launch_bounds__(NTT, NTT == 1024 ? 8 : 1) void k_detect_fused_fixed(FusedParams P) {
 	typedef FixedGeo<SKIP, SIZE0, STEPSZ, NL, R, ITWT, TYT, NTT> G;
 	extern __shared__ __attribute__((aligned(16))) float fl[];
 	T* iiT = (T*)fl;   // 32-bit words either way
-	float* inten = fl + SKIP * G::plane;   // the two dense mid levels, then the survivor list and its sparse outer-level values
+	float* inten = fl + SKIP * G::plane;   // the two dense mid levels, then the NMS candidate codes
 	const int tid = threadIdx.x;
 	// XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8 share one L2), so block b takes
 	// tile (b % 8) * chunk + b / 8 -- every XCD walks its own contiguous run of tiles (row after row of one image) and the halo
@@ -771,36 +756,35 @@ __global__ __launch_bounds__(NTT) void k_detect_fused_fixed(FusedParams P) {
 	const FusedMid M0 = P.mid[0], M1 = P.mid[P.nmid > 1 ? 1 : 0];
 	float* mid1 = inten;                          // level 1  [ITH][ITp]
 	float* mid2 = inten + G::ITH * G::ITp;        // level 2
-	int* survList = (int*)(inten + 2 * G::ITH * G::ITp);   // [SURV] packed (m << 16 | py << 8 | px)
-	float* sparse = (float*)(survList + G::SURV);          // [SURV][9] outer-level values around each survivor
-	int* survCount = (int*)(sparse + G::SPARSE);
-	int* candCount = survCount + 1;
-	unsigned short* candList = (unsigned short*)sparse;    // [NCAND] pixels above the threshold and their four direct neighbours (m << 12 | py << 6 | px); dead before `sparse` is written
-	if (tid == 0) { *survCount = 0; *candCount = 0; }
+	unsigned short* candList = (unsigned short*)(inten + 2 * G::ITH * G::ITp);   // [NCAND] pixels above the threshold and their four direct neighbours (m << 12 | py << 6 | px)
+	int* candCount = (int*)(inten + 2 * G::ITH * G::ITp + G::CANDF);
+	if (tid == 0) *candCount = 0;
 	if (!BHIP_ABLATE(P, 1)) {
 		fusedLevelDense<G, SKIP, R, 1, T>(P, iiT, mid1, tid, x0, y0, X0, Y0);
 		fusedLevelDense<G, SKIP, R, 2, T>(P, iiT, mid2, tid, x0, y0, X0, Y0);
 	}
 	__syncthreads();
-	if (P.nexp > 0) {
-		// even pixels of the tile core -> pixel (x/2, y/2) of the next octave.  A mid level is read from its tile, an outer level is
-		// evaluated here (a quarter of the core's pixels).
+	// Export: even pixels of the tile core -> pixel (x/2, y/2) of the next octave, one slot after the other.  A mid level is read from its
+	// tile, an outer level is evaluated here (a quarter of the core's pixels).  The level and the plane of a slot are wave-uniform scalars
+	// (k is the counter of a loop that every thread of the workgroup walks alike): a per-lane index into P.expLevel[] / P.expSlotOff[] is a kernarg load + wait per item.
+	const int nexp = BHIP_ABLATE(P, 64) ? 0 : P.nexp;
+#pragma unroll 1
+	for (int k = 0; k < nexp; k++) {
+		const int lv = P.expLevel[k];
 		constexpr int HX = (G::TX + 1) / 2, HY = (G::TY + 1) / 2;
 		const int ex0 = (x0 + 1) >> 1, ey0 = (y0 + 1) >> 1;   // first even pixel of the core, in next-octave coordinates
-		for (int it = tid; it < P.nexp * HX * HY; it += G::NT) {
-			const int k = it / (HX * HY);
-			const int rem = it - k * (HX * HY);
-			const int jy = rem / HX, jx = rem - jy * HX;
+		float* __restrict__ dst = P.expOut + ((long long)img * P.expImageStride + P.expSlotOff[k]);
+		for (int it = tid; it < HX * HY; it += G::NT) {
+			const int jy = it / HX, jx = it - jy * HX;
 			const int ex = ex0 + jx, ey = ey0 + jy;
 			const int px = 2 * ex - x0, py = 2 * ey - y0;   // core coordinates in this tile
 			if (px < G::TX && py < G::TY && 2 * ex < P.w && 2 * ey < P.h && ex < P.expW && ey < P.expH) {
-				const int lv = P.expLevel[k];
 				float v;
 				if (lv == 1) v = mid1[(py + R) * G::ITp + (px + R)];
 				else if (lv == 2) v = mid2[(py + R) * G::ITp + (px + R)];
 				else if (lv == 0) v = fusedPixelCall<G, SKIP, 0, T>(P.ii.width, P.ii.height, P.w, P.h, iiT, x0 + px, y0 + py, x0, y0, X0, Y0);
 				else v = fusedPixelCall<G, SKIP, 3, T>(P.ii.width, P.ii.height, P.w, P.h, iiT, x0 + px, y0 + py, x0, y0, X0, Y0);
-				P.expOut[(long long)img * P.expImageStride + P.expSlotOff[k] + (long long)ey * P.expW + ex] = v;
+				dst[(long long)ey * P.expW + ex] = v;
 			}
 		}
 	}
@@ -810,7 +794,7 @@ __global__ __launch_bounds__(NTT) void k_detect_fused_fixed(FusedParams P) {
 	//      walks down its rows with the value above / at / below in registers -- one LDS read per pixel -- and tests the threshold and
 	//      the two vertical neighbours; the few pixels that pass read their two horizontal neighbours.  What is left (a few per cent:
 	//      most pixels above the threshold lose against a direct neighbour) is compacted into a workgroup-wide list;
-	//   2. one listed pixel per thread: frame tests, the full window, the ignore border -> survivor list.
+	//   2. one listed pixel per group of 16 lanes: the full window, the ignore border, the scale-space test and the emission (further down).
 	{
 		static_assert(G::ITW == 32, "a wave = two mid levels x 32 columns");
 		constexpr int RB = (G::TY + G::NW - 1) / G::NW;     // rows per band
@@ -834,58 +818,52 @@ __global__ __launch_bounds__(NTT) void k_detect_fused_fixed(FusedParams P) {
 		}
 	}
 	__syncthreads();
+	// ---- everything behind the candidate list in one phase, no LDS write and no barrier: a group of 16 consecutive lanes (one DPP row) owns
+	// one candidate, NT / 16 candidates per round, rounds until the list is done (one for all but the most crowded tiles); a wave with no
+	// group to serve retires.  Every decision is uniform within a group, so the ballots below see all 16 lanes of every group that is still
+	// in the loop.
 	{
+		static_assert(R == 2, "24 window neighbours on 16 lanes, two each");
 		const int ncand = *candCount;
-		for (int ci = tid; ci < ncand; ci += G::NT) {
+		const int gl = tid & 15, gshift = tid & 48;   // lane within the group, first lane of the group within the wave
+		// the 24 neighbours of the (2R+1)^2 window in raster order, the centre (raster index 12) skipped: neighbour gl, and neighbour gl + 16
+		// on the lanes below 8 (the others test their first neighbour twice)
+		const int n0 = gl < 12 ? gl : gl + 1, n1 = gl < 8 ? gl + 17 : n0;
+		const int off0 = (n0 / 5 - R) * G::ITp + (n0 % 5 - R), off1 = (n1 / 5 - R) * G::ITp + (n1 % 5 - R);
+		const int qx = gl % 3 - 1, qy = (gl < 9 ? gl / 3 : 1) - 1;   // lanes 0..8: one of the 3x3 scale-space neighbours each
+		for (int ci = tid >> 4; ci < ncand; ci += G::NT / 16) {
 			const int cc = candList[ci];
 			const int m = cc >> 12, py = (cc >> 6) & 63, px = cc & 63;
-			const int code = (m << 16) | (py << 8) | px;
-			const float* mid = ((m == 0 ? M0.level : M1.level) == 1 ? mid1 : mid2) + (py + R) * G::ITp + (px + R);
-			const float val = mid[0];
+			const bool lowMid = (m == 0 ? M0.level : M1.level) == 1;
+			const float* self = (lowMid ? mid1 : mid2) + (py + R) * G::ITp + (px + R);
+			const float* other = (lowMid ? mid2 : mid1) + (py + R) * G::ITp + (px + R);
+			const float val = self[0];
 			const int b = m == 0 ? M0.border : M1.border;
 			const int x = x0 + px, y = y0 + py;
-			if (x < b || x >= P.w - b || y < b || y >= P.h - b) continue;
-			bool isMax = true;
-#pragma unroll
-			for (int j = -R; j <= R; j++)
-#pragma unroll
-				for (int i = -R; i <= R; i++)
-					if ((i != 0 || j != 0) && mid[j * G::ITp + i] >= val) isMax = false;
-			if (!isMax) continue;
-			// candidates hugging the ignore border are dropped (FastHessianFeatureDetector.java:270-276)
+			// strict maximum of the window
+			const bool loses = self[off0] >= val || self[off1] >= val;
+			const unsigned int anyLoses = (unsigned int)(__ballot(loses) >> gshift) & 0xffffu;
+			// candidates hugging the ignore border are dropped (FastHessianFeatureDetector.java:270-276; b + R >= b: the frame test is contained)
 			const int ignoreR = b + R;
-			if (x < ignoreR || x >= P.w - ignoreR || y < ignoreR || y >= P.h - ignoreR) continue;
-			// two strict (2R+1)^2 maxima are more than R apart: at most one per (R+1)^2 block, SURV = 2 * blocks per tile holds them all
-			const int slot = atomicAdd(survCount, 1);
-			if (slot < G::SURV) survList[slot] = code;
+			const bool alive = anyLoses == 0 && !(x < ignoreR || x >= P.w - ignoreR || y < ignoreR || y >= P.h - ignoreR);
+			// checkMax on the two neighbour levels: the outer level on the far side of the mid level (level 0 below mid level 1, level 3 above mid
+			// level 2) is evaluated here, one of its nine values per lane; the other neighbour level is the other dense mid level
+			float outer = 0.0f;
+			bool above = false;
+			if (alive && gl < 9) {
+				outer = lowMid ? fusedPixelCall<G, SKIP, 0, T>(P.ii.width, P.ii.height, P.w, P.h, iiT, x + qx, y + qy, x0, y0, X0, Y0)
+							   : fusedPixelCall<G, SKIP, 3, T>(P.ii.width, P.ii.height, P.w, P.h, iiT, x + qx, y + qy, x0, y0, X0, Y0);
+				above = outer >= val || other[qy * G::ITp + qx] >= val;
+			}
+			const unsigned int anyAbove = (unsigned int)(__ballot(above) >> gshift) & 0xffffu;
+			const float outerCentre = __shfl(outer, 4, 16);
+			if (alive && anyAbove == 0 && gl == 0) {
+				const float otherCentre = other[0];
+				const float lowerC = lowMid ? outerCentre : otherCentre, upperC = lowMid ? otherCentre : outerCentre;
+				if (m == 0) fusedFinish<G, SKIP, R>(P, M0, self, lowerC, upperC, x, y, val, img);
+				else fusedFinish<G, SKIP, R>(P, M1, self, lowerC, upperC, x, y, val, img);
+			}
 		}
-	}
-	__syncthreads();
-	const int nSurv = min(*survCount, G::SURV);
-	for (int base = 0; base < nSurv; base += G::CHUNK) {   // one round for all but the densest tiles
-		const int nHere = min(G::CHUNK, nSurv - base);
-		// ---- outer level around every survivor: nine values each, one (survivor, neighbour) pair per thread
-		for (int it = tid; it < nHere * 9; it += G::NT) {
-			const int sv = it / 9, q = it - sv * 9;
-			const int code = survList[base + sv];
-			const int m = code >> 16, py = (code >> 8) & 0xff, px = code & 0xff;
-			const int x = x0 + px + q % 3 - 1, y = y0 + py + q / 3 - 1;
-			sparse[it] = (m == 0 ? M0.level : M1.level) == 1 ? fusedPixelCall<G, SKIP, 0, T>(P.ii.width, P.ii.height, P.w, P.h, iiT, x, y, x0, y0, X0, Y0)
-															  : fusedPixelCall<G, SKIP, 3, T>(P.ii.width, P.ii.height, P.w, P.h, iiT, x, y, x0, y0, X0, Y0);
-		}
-		__syncthreads();
-		for (int sv = tid; sv < nHere; sv += G::NT) {
-			const int code = survList[base + sv];
-			const int m = code >> 16, py = (code >> 8) & 0xff, px = code & 0xff;
-			const float val = ((m == 0 ? M0.level : M1.level) == 1 ? mid1 : mid2)[(py + R) * G::ITp + (px + R)];
-			bool below = true;
-#pragma unroll
-			for (int q = 0; q < 9; q++)
-				if (sparse[sv * 9 + q] >= val) below = false;
-			if (m == 0) fusedFinish<G, SKIP, R>(P, M0, mid1, mid2, below, sparse[sv * 9 + 4], px, py, x0 + px, y0 + py, val, img);
-			else fusedFinish<G, SKIP, R>(P, M1, mid1, mid2, below, sparse[sv * 9 + 4], px, py, x0 + px, y0 + py, val, img);
-		}
-		if (base + G::CHUNK < nSurv) __syncthreads();
 	}
 }
 
@@ -1015,11 +993,13 @@ int bhip_launch_detect_fused(bhip_ctx* ctx, DevImg<const T> ii, int skip, int nl
 				else if (v == 'b') LAUNCH_FIXED(2, 15, 12, 32, 16, 256);   // round-1 shape: 28x16 outputs, four waves
 				else if (v == 'w') LAUNCH_FIXED(2, 15, 12, 32, 32, 512);
 				else if (v == 'z') LAUNCH_FIXED(2, 15, 12, 32, 24, 512);
+				else if (v == 'h') LAUNCH_FIXED(2, 15, 12, 32, 40, 512);    // the shipped tile on eight waves (the shape before the single tail phase)
 				else
 #endif
-				// 28x40 outputs on eight waves (the tallest tile that leaves two workgroups per CU): 14 staged floats per output instead of 22.9,
-				// halo rows 44/40 instead of 20/16, 16 waves per CU instead of 12 -- 3.98 -> 3.1 ms
-				LAUNCH_FIXED(2, 15, 12, 32, 40, 512);
+				// 28x40 outputs (the tallest tile that leaves two workgroups per CU): 14 staged floats per output instead of 22.9, halo rows 44/40
+				// instead of 20/16 -- 3.98 -> 3.1 ms on eight waves.  Sixteen waves (32 per CU, 64 VGPRs each, which both instantiations meet
+				// without scratch): the staging and dense rounds of a thread halve, 2.47 -> 2.39 ms
+				LAUNCH_FIXED(2, 15, 12, 32, 40, 1024);
 			}
 #undef LAUNCH_FIXED
 		}
