@@ -16,6 +16,10 @@ ARCH = "gfx950"
 
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math",
          "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
+# Per-source additions.  describe.hip: k_describe's waves loop over key points, and with the whole kernel body inside a loop the machine-level
+# loop-invariant code motion parks every fp64 constant of the atan2 / merge / window code in vector registers across it (192 VGPRs, two waves
+# per SIMD instead of four); without that pass the kernel keeps its four waves ("describe: persistent waves").
+SOURCE_FLAGS = {"describe.hip": ["-mllvm", "-disable-machine-licm"]}
 
 
 def sources():
@@ -60,7 +64,7 @@ def build(force=False, verbose=False, experiments=False):
         objs.append(obj)
         if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(newest, os.path.getmtime(src)):
             continue
-        cmd = [hipcc, "--offload-arch=" + ARCH] + FLAGS + (["-DBHIP_EXPERIMENTS"] if experiments else []) + extra + ["-c", src, "-o", obj]
+        cmd = [hipcc, "--offload-arch=" + ARCH] + FLAGS + (["-DBHIP_EXPERIMENTS"] if experiments else []) + extra + SOURCE_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
         if src.endswith(".cpp"):
             cmd.insert(1, "-x")
             cmd.insert(2, "hip")

@@ -28,6 +28,7 @@ struct CtxScratch {
 	int thresholdTapsRadius = 0;
 	AssocMfmaWork mfma;
 	int assocExactOnly = -1;  // BHIP_ASSOC_EXACT=1 forces the exact VALU association kernels (parity cross-check)
+	DevBuf describeQueue;     // slot counters of the k_describe launch in flight (BHIP_DESCRIBE_QUEUE_BYTES)
 };
 inline CtxScratch* scratchOf(bhip_ctx* ctx);
 

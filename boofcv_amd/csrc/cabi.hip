@@ -23,6 +23,7 @@ static int ctxCreate(int device, void* stream, bool useGiven, bhip_ctx** out) {
 	std::unique_ptr<bhip_ctx_full> ctx(new (std::nothrow) bhip_ctx_full());
 	if (!ctx) return BHIP_ERR_NOMEM;
 	ctx->device = device;
+	if (hipDeviceGetAttribute(&ctx->cuCount, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ctx->cuCount <= 0) return BHIP_ERR_HIP;
 	if (useGiven) {
 		ctx->stream = (hipStream_t)stream;
 	} else {
@@ -500,7 +501,8 @@ static int surfRun(bhip_surf* s, DevImg<const T> in, int bands, SurfReturn ret) 
 	BHIP_TRY(s->descBuf.reserve(ctx, (size_t)std::max<long long>(total, 1) * 8 * dof));
 	BHIP_TRY(s->whiteBuf.reserve(ctx, (size_t)std::max<long long>(total, 1)));
 	// processing order of the describe stage: key points of one image grouped by coarse tile (L2 locality of the gathers)
-	const int* perm = nullptr;
+	const KpOrder* perm = nullptr;
+	BHIP_TRY(scratchOf(ctx)->describeQueue.reserve(ctx, BHIP_DESCRIBE_QUEUE_BYTES));
 	{
 #ifdef BHIP_EXPERIMENTS
 		const bool noOrder = bhip_env_flag("BHIP_DESCRIBE_NOORDER");
@@ -510,15 +512,16 @@ static int surfRun(bhip_surf* s, DevImg<const T> in, int bands, SurfReturn ret) 
 		int maxCount = 0;
 		for (int c : s->det.counts) maxCount = std::max(maxCount, c);
 		if (!noOrder && total > 0) {
-			BHIP_TRY(s->permBuf.reserve(ctx, (size_t)total * 4 + (size_t)batch * 64 * 4));
-			int* hist = s->permBuf.as<int>() + total;
+			BHIP_TRY(s->permBuf.reserve(ctx, (size_t)total * sizeof(KpOrder) + (size_t)batch * 64 * 4));
+			int* hist = (int*)(s->permBuf.as<KpOrder>() + total);
 			BHIP_TRY(bhip_launch_kp_spatial_order(ctx, s->det.sorted.as<KeyPoint>(), s->det.cap, s->startBuf.as<int>(), batch, maxCount, W, H, hist,
-												  s->permBuf.as<int>()));
-			perm = s->permBuf.as<int>();
+												  s->permBuf.as<KpOrder>()));
+			perm = s->permBuf.as<KpOrder>();
 		}
 	}
 	BHIP_TRY(bhip_launch_describe_ex(ctx, ii, s->det.sorted.as<KeyPoint>(), s->det.cap, s->startBuf.as<int>(), 0, total, s->tables, nullptr,
-									 s->angBuf.as<double>(), s->descBuf.as<double>(), s->whiteBuf.as<uint8_t>(), perm, s->planar()));
+									 s->angBuf.as<double>(), s->descBuf.as<double>(), s->whiteBuf.as<uint8_t>(), perm, scratchOf(ctx)->describeQueue.as<int>(),
+									 s->planar()));
 	// host-frame callers may reuse their frames (and the upload buffer) as soon as the call returns; a device-resident batch was consumed before
 	// the detector's count read-back, so its call returns with the describe kernels still in flight (stream order covers every later use)
 	if (ret == SurfReturn::SYNCHRONIZED) BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1031,10 +1034,11 @@ int bhip_surf_describe_points(bhip_surf* s, int image, const double* xy_scale, i
 	BHIP_TRY(s->tmpAng.reserve(ctx, (size_t)n * 8));
 	BHIP_TRY(s->tmpDesc.reserve(ctx, (size_t)n * 8 * dof));
 	BHIP_TRY(s->tmpWhite.reserve(ctx, (size_t)n));
+	BHIP_TRY(scratchOf(ctx)->describeQueue.reserve(ctx, BHIP_DESCRIBE_QUEUE_BYTES));
 	BHIP_HIP(ctx, hipMemcpyAsync(s->tmpKp.p, kps.data(), (size_t)n * sizeof(KeyPoint), hipMemcpyHostToDevice, ctx->stream));
 	BHIP_TRY(withIntegral(s, [&](auto ii) {
 		return bhip_launch_describe_ex(ctx, ii, s->tmpKp.as<KeyPoint>(), 0, nullptr, image, n, s->tables, nullptr, s->tmpAng.as<double>(),
-									   s->tmpDesc.as<double>(), s->tmpWhite.as<uint8_t>(), nullptr, s->planar());
+									   s->tmpDesc.as<double>(), s->tmpWhite.as<uint8_t>(), nullptr, scratchOf(ctx)->describeQueue.as<int>(), s->planar());
 	}));
 	if (angle) BHIP_HIP(ctx, hipMemcpyAsync(angle, s->tmpAng.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
 	if (white) BHIP_HIP(ctx, hipMemcpyAsync(white, s->tmpWhite.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));

@@ -77,6 +77,7 @@ struct bhip_ctx {
 	std::vector<ProfRecord> profRecords;
 	std::vector<HipEvent> eventPool;
 	size_t integralLdsAttr = 0;   // largest dynamic-LDS size k_integral_fused has been configured for on this ctx's device
+	int cuCount = 0;              // compute units of the device (sizes the persistent grid of k_describe)
 };
 
 // RAII bracket around one kernel launch: records a start/stop event pair on the ctx stream when profiling is on
@@ -291,11 +292,17 @@ int bhip_launch_rank_scatter(bhip_ctx* ctx, const unsigned int* bitmap, int bitm
 int bhip_launch_word_prefix(bhip_ctx* ctx, const unsigned int* bitmap, int bitmapWords, int batch, unsigned int* wordPrefix, int* totals);
 
 // describe.hip, detect.hip, associate.hip, assoc_mfma.hip, detect_fused.hip: what only the C ABI layer calls
-// ii: the grey integral images of the batch.  imageStart == nullptr: kps is a flat list for image `singleImage`; perm: optional processing order
+// one slot of the describe stage's processing order (k_kp_tile_scatter): key point g of the compact list is key point `local` of image `img`
+struct __attribute__((aligned(16))) KpOrder { int g, img, local, pad; };
+#define BHIP_DESCRIBE_QUEUE_BYTES (8 * 128)   // k_describe's slot counters: one int per XCD chunk, each on a 128-byte line of its own
+// ii: the grey integral images of the batch.  imageStart == nullptr: kps is a flat list for image `singleImage`; perm: optional processing order;
+// queue: BHIP_DESCRIBE_QUEUE_BYTES of device memory that belong to this launch until it has finished (zeroed here, on the stream)
 template <class T>
 int bhip_launch_describe_ex(bhip_ctx* ctx, DevImg<const T> ii, const KeyPoint* kps, int cap, const int* imageStart, int singleImage, long long total,
-							SurfTables t, const double* anglesIn, double* angles, double* desc, uint8_t* white, const int* perm, DescPlanar planar);
-int bhip_launch_kp_spatial_order(bhip_ctx* ctx, const KeyPoint* kps, int cap, const int* start, int batch, int maxCount, int W, int H, int* hist, int* perm);
+							SurfTables t, const double* anglesIn, double* angles, double* desc, uint8_t* white, const KpOrder* perm, int* queue,
+							DescPlanar planar);
+int bhip_launch_kp_spatial_order(bhip_ctx* ctx, const KeyPoint* kps, int cap, const int* start, int batch, int maxCount, int W, int H, int* hist,
+								 KpOrder* perm);
 // per-split partial records of the association scans (associate.hip's VALU kernels and assoc_ham_mfma.hip write the same ones)
 struct ColTop {
 	double min1, min2;

@@ -17,8 +17,9 @@
 // outside the image) and the isInside test disappears.  The orientation angles are ordered by (angle, sample index): the
 // reference's ddogleg QuickSort_F64 is unstable and its tie order is not pinned by any reference test (SURVEY hard part 5).
 //
-// Structure: one wavefront per key point, four per workgroup; every phase keeps many independent loads in flight (the kernel is bound by
-// LDS / L2 round trips at 4 waves per SIMD, not by arithmetic):
+// Structure: one wavefront per key point at a time, four per workgroup, each taking key point after key point from per-XCD queues (see
+// k_describe); every phase keeps many independent loads in flight (the kernel is bound by LDS / L2 round trips at 4 waves per SIMD, not
+// by arithmetic):
 //   * gathers are branch-free (out-of-bounds samples read a safe address and are zeroed afterwards) and issued in unrolled batches;
 //     key points are worked on in coarse-tile order per image and XCD-chunked block order, so the taps of the waves in flight hit L2;
 //   * the 289 (angle, index) pairs are sorted by merge path on 32-bit keys with an fp64 check (fp64 merge sort as the fallback);
@@ -44,7 +45,8 @@ struct DescParams {
 	double* angles;           // [total]
 	double* desc;             // [total][dof]
 	uint8_t* white;           // [total]
-	const int* perm;          // optional processing order: slot -> key point index
+	const KpOrder* perm;      // optional processing order: slot -> key point index, its image and its index there
+	int* queue;               // slots taken so far from each of the 8 XCD chunks of the processing order (ints 128 bytes apart, zero at launch)
 	// colour SURF (DescribePointSurfPlanar): the descriptor is built band by band from these integral images ([image][band][H][W]),
 	// concatenated un-normalised and normalised once; orientation and Laplacian sign still come from `ii` (the grey integral image).
 	// nBands == 0: single-band descriptor from `ii`.
@@ -60,6 +62,7 @@ struct DescParams {
 #ifdef BHIP_EXPERIMENTS
 	int stopAfter;            // BHIP_DESCRIBE_STOP=k: waves return at phase boundary k (instruction counts per phase by difference; results are garbage)
 	int windowStop;           // BHIP_DESCRIBE_WSTOP=k (8..12): the window sweep returns at its internal boundary k (use with BHIP_DESCRIBE_STOP=3)
+	int variant;              // BHIP_DESCRIBE_VARIANT: DESC_VAR_* bits (A/B runs of the queue's parts inside one build)
 #endif
 };
 
@@ -180,6 +183,26 @@ __device__ __forceinline__ void waveSync() {
 	__builtin_amdgcn_wave_barrier();
 	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+
+// Shuffles addressed from the caller's lane index.  The kernel makes that index opaque once per key point; the library forms compute their
+// source lanes from the hardware lane id, which is the same for every key point, so each of their address registers would be held across
+// the key-point loop.  Same data movement (ds_bpermute), width 64.
+template <class T>
+__device__ __forceinline__ T wavePermute(T v, int srcLane) {
+	static_assert(sizeof(T) == 4 || sizeof(T) == 8, "32- or 64-bit values");
+	const int addr = srcLane << 2;
+	if constexpr (sizeof(T) == 4) {
+		return __builtin_bit_cast(T, __builtin_amdgcn_ds_bpermute(addr, __builtin_bit_cast(int, v)));
+	} else {
+		const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+		const unsigned int lo = (unsigned int)__builtin_amdgcn_ds_bpermute(addr, (int)(unsigned int)b);
+		const unsigned int hi = (unsigned int)__builtin_amdgcn_ds_bpermute(addr, (int)(unsigned int)(b >> 32));
+		return __builtin_bit_cast(T, ((unsigned long long)hi << 32) | lo);
+	}
+}
+template <class T> __device__ __forceinline__ T laneShfl(T v, int src, int lane) { return wavePermute(v, (src & 63) | (lane & ~63)); }
+template <class T> __device__ __forceinline__ T laneShflXor(T v, int mask, int lane) { return wavePermute(v, lane ^ mask); }
+template <class T> __device__ __forceinline__ T laneShflUp(T v, int delta, int lane) { return wavePermute(v, lane >= delta ? lane - delta : lane); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Stable merge sort of the n (angle, index) pairs in LDS: runs of EPL consecutive elements per lane (insertion sort in registers),
@@ -462,7 +485,7 @@ __device__ __forceinline__ bool countingSortScatter(const double (&a)[EPLT], con
 		mx = max(mx, cnt[e]);
 	}
 #pragma unroll
-	for (int o = 32; o >= 1; o >>= 1) mx = max(mx, __shfl_xor(mx, o, 64));
+	for (int o = 32; o >= 1; o >>= 1) mx = max(mx, laneShflXor(mx, o, lane));
 	if (mx > ORI_BIN_MAX) return false;   // wave-uniform
 	waveSync();   // every count has been read before the counters turn into offsets
 	{
@@ -479,7 +502,7 @@ __device__ __forceinline__ bool countingSortScatter(const double (&a)[EPLT], con
 		unsigned int sc = run;
 #pragma unroll
 		for (int o = 1; o < 64; o <<= 1) {
-			const unsigned int t = __shfl_up(sc, o, 64);
+			const unsigned int t = laneShflUp(sc, o, lane);
 			if (lane >= o) sc += t;
 		}
 		const unsigned int base = sc - run;
@@ -679,10 +702,10 @@ __device__ __forceinline__ bool slidingWindowFast(double* dX, double* dY, const 
 	int scan = runMax;
 #pragma unroll
 	for (int o = 1; o < 64; o <<= 1) {
-		const int t = __shfl_up(scan, o, 64);
+		const int t = laneShflUp(scan, o, lane);
 		if (lane >= o) scan = max(scan, t);
 	}
-	int prevE = __shfl_up(scan, 1, 64);
+	int prevE = laneShflUp(scan, 1, lane);
 	if (lane == 0) prevE = 1;
 	prevE = max(prevE, 1);
 	// ---- validate the schedule (full-circle regime -> serial code), before the samples are overwritten by their prefix sums
@@ -717,7 +740,7 @@ __device__ __forceinline__ bool slidingWindowFast(double* dX, double* dY, const 
 		lastE = pe;
 	}
 	if (__any(abnormal)) return false;
-	lastE = __shfl(lastE, (n - 1) / EPL, 64);  // E(n-1): one past the last end position that is ever tested
+	lastE = laneShfl(lastE, (n - 1) / EPL, lane);  // E(n-1): one past the last end position that is ever tested
 	WSTAMP(9);
 	// ---- inclusive prefix sums of (dX, dY) in sorted order, in place: window sum(a..E) = I[E] - I[a-1]
 	double vx[EPLT], vy[EPLT];   // this lane's samples: put back into dX, dY when the sweep ends in a near tie
@@ -737,7 +760,7 @@ __device__ __forceinline__ bool slidingWindowFast(double* dX, double* dY, const 
 		double ox = tx, oy = ty;   // inclusive scan of the lane totals
 #pragma unroll
 		for (int o = 1; o < 64; o <<= 1) {
-			const double ux = __shfl_up(ox, o, 64), uy = __shfl_up(oy, o, 64);
+			const double ux = laneShflUp(ox, o, lane), uy = laneShflUp(oy, o, lane);
 			if (lane >= o) { ox += ux; oy += uy; }
 		}
 		ox -= tx; oy -= ty;        // exclusive
@@ -778,7 +801,7 @@ __device__ __forceinline__ bool slidingWindowFast(double* dX, double* dY, const 
 			unsigned int sc = run;
 #pragma unroll
 			for (int o = 1; o < 64; o <<= 1) {
-				const unsigned int t = __shfl_up(sc, o, 64);
+				const unsigned int t = laneShflUp(sc, o, lane);
 				if (lane >= o) sc += t;
 			}
 			const unsigned int base = sc - run;
@@ -807,14 +830,14 @@ __device__ __forceinline__ bool slidingWindowFast(double* dX, double* dY, const 
 	// ---- first maximum in sweep order across the wave: max magnitude, then the smallest position among the lanes that hold it
 	double m = bMag;
 #pragma unroll
-	for (int o = 32; o >= 1; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+	for (int o = 32; o >= 1; o >>= 1) m = fmax(m, laneShflXor(m, o, lane));
 	int pos = (bMag == m) ? bPos : 0x7fffffff;
 #pragma unroll
-	for (int o = 32; o >= 1; o >>= 1) pos = min(pos, __shfl_xor(pos, o, 64));
+	for (int o = 32; o >= 1; o >>= 1) pos = min(pos, laneShflXor(pos, o, lane));
 	const unsigned long long owner = __ballot(bMag == m && bPos == pos);
 	const int src = __ffsll((long long)owner) - 1;
-	bestX = __shfl(bX, src, 64);
-	bestY = __shfl(bY, src, 64);
+	bestX = laneShfl(bX, src, lane);
+	bestY = laneShfl(bY, src, lane);
 	const double tieFloor = m - m * 1.0e-9;
 	if (__popcll(__ballot(bMag >= tieFloor)) + __popcll(__ballot(bMag2 >= tieFloor)) > 1) {   // wave-uniform
 		waveSync();
@@ -842,44 +865,65 @@ __device__ __forceinline__ bool slidingWindowFast(double* dX, double* dY, const 
 // CFG: 0 = every size comes from the tables at run time; 1 = FactoryDetectDescribe.surfStable defaults (4x4 grid of 5-sample sub-regions,
 // overlap 2, 17x17 sliding-window orientation grid); 2 = surfFast defaults (4x4 grid of 5, no overlap, 13x13 average orientation).  With
 // the sizes known the index arithmetic (sample -> row/column, feature -> sub-region) folds to shifts and multiplies.
-template <bool STAMP, int EPLT, int TWT, class TAP, int CFG = 0>
-__global__ __launch_bounds__(256) void k_describe(DescParams P) {
-	extern __shared__ __attribute__((aligned(16))) unsigned char ldsAll[];
-	// the wave index is uniform by construction; telling the compiler so keeps everything derived from the key point (image, scale, kernel
-	// radius, tap strides) in scalar registers and the gathers in base + 32-bit-offset form
-	const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-	const int lane = threadIdx.x & 63;
-	// XCD-aware order (blocks are dealt round-robin over the 8 XCDs): block b takes key-point group (b % 8) * chunk + b / 8, so each
-	// XCD works through its own contiguous run of key points -- one or two images at a time in its L2 instead of the whole batch
-	const long long nblk = (P.total + 3) >> 2;
-	const long long chunk = (nblk + 7) >> 3;
-	const long long blk = (long long)(blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
-	if ((long long)(blockIdx.x >> 3) >= chunk) return;
-	const long long slot = blk * 4 + wave;
-	if (slot >= P.total) return;
-	const long long g = P.perm ? (long long)P.perm[slot] : slot;   // processing order (detect.hip, k_kp_tile_*); results stay at index g
-	unsigned char* lds = ldsAll + (size_t)wave * P.ldsPerWave;
-
-	// which image does key point g belong to?
-	int img, local;
-	if (P.imageStart) {
-		int lo = 0, hi = P.batch;  // find img with imageStart[img] <= g < imageStart[img+1]
-		while (hi - lo > 1) {
-			const int m = (lo + hi) >> 1;
-			if ((long long)P.imageStart[m] <= g) lo = m; else hi = m;
-		}
-		img = lo;
-		local = (int)(g - P.imageStart[img]);
+//
+// Hand-out of the key points: the waves are persistent.  The processing order is cut into 8 chunks, one per XCD (workgroups are dealt
+// round-robin over the XCDs, so blockIdx.x & 7 names the XCD: each works through its own contiguous run of key points -- one or two images
+// at a time in its L2 instead of the whole batch); a wave takes the next slot of its chunk with one atomic add on the chunk's counter, and
+// when the chunk is used up it goes on with the other chunks, the next XCD's first, before it retires.  A wave slot and its LDS slice are
+// never parked behind the slowest of four key points, and the launch ends balanced over the XCDs.  The waves of a workgroup share
+// nothing but the LDS allocation.
+#define DESC_VAR_ONESHOT 1      // experiments build: one key point per wave, four consecutive slots per workgroup (the launch before the queue)
+#define DESC_VAR_SEARCH 2       // experiments build: ignore the order record's image, search imageStart
+// the wave's next slot of the processing order; false: every chunk is used up.  cur: the chunk the wave draws from, tried: chunks it has found empty
+__device__ __forceinline__ bool queueNext(const DescParams& P, int lane, int& cur, int& tried, long long& slot) {
+	const long long chunkSlots = ((((P.total + 3) >> 2) + 7) >> 3) * 4;
+	while (tried < 8) {
+		int t = 0;
+		if (lane == 0) t = __hip_atomic_fetch_add(P.queue + cur * 32, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		t = __builtin_amdgcn_readfirstlane(t);
+		const long long len = P.total - cur * chunkSlots;   // slots of this chunk (when below chunkSlots; <= 0: none)
+		if (t < chunkSlots && t < len) { slot = cur * chunkSlots + t; return true; }
+		tried++;
+		cur = (cur + 1) & 7;
+	}
+	return false;
+}
+// slot -> key point g of the compact list, its image and its record
+__device__ __forceinline__ void loadSlot(const DescParams& P, long long slot, int variant, long long& g, int& img, KeyPoint& kp) {
+	int local;
+	if (P.perm && !(variant & DESC_VAR_SEARCH)) {
+		const KpOrder r = P.perm[slot];   // processing order (detect.hip, k_kp_tile_*); results stay at index g
+		g = r.g; img = r.img; local = r.local;
 	} else {
-		img = P.singleImage;
-		local = (int)g;
+		// no order record (describe-only calls): which image does key point g belong to?
+		g = P.perm ? (long long)P.perm[slot].g : slot;
+		if (P.imageStart) {
+			int lo = 0, hi = P.batch;  // find img with imageStart[img] <= g < imageStart[img+1]
+			while (hi - lo > 1) {
+				const int m = (lo + hi) >> 1;
+				if ((long long)P.imageStart[m] <= g) lo = m; else hi = m;
+			}
+			img = lo;
+			local = (int)(g - P.imageStart[img]);
+		} else {
+			img = P.singleImage;
+			local = (int)g;
+		}
 	}
 	img = (int)uniformU32((unsigned)img);
 	local = (int)uniformU32((unsigned)local);
-	const KeyPoint kp = P.imageStart ? P.kps[(long long)img * P.cap + local] : P.kps[local];
+	kp = P.imageStart ? P.kps[(long long)img * P.cap + local] : P.kps[local];
+}
+
+// One key point, by one wave in its own LDS slice `lds`; results go to index g.
+template <bool STAMP, int EPLT, int TWT, class TAP, int CFG>
+__device__ __forceinline__ void describeOne(const DescParams& P, const long long g, const int img, const KeyPoint kp, unsigned char* lds, const int lane) {
 	const TAP* __restrict__ d = (const TAP*)P.ii.data + (long long)img * P.ii.imageStride;
 	const int stride = P.ii.stride, W = P.ii.width, H = P.ii.height;
-	const SurfTables& T = P.t;
+	// The table values that enter fp64 arithmetic are made opaque per key point: their conversions and the window's derived constants are the
+	// same for every key point and have no scalar form, so they would be held in vector registers across the key-point loop.
+	SurfTables T = P.t;
+	asm volatile("" : "+s"(T.oriRadius), "+s"(T.oriKernelWidth), "+s"(T.widthSample), "+s"(T.oriWindow));
 
 	DSTAMP(0);
 	// ------------------------------------------------------------------ orientation
@@ -1009,8 +1053,8 @@ __global__ __launch_bounds__(256) void k_describe(DescParams P) {
 						start++;
 					}
 				}
-				bestX = __shfl(bestX, 0, 64);
-				bestY = __shfl(bestY, 0, 64);
+				bestX = laneShfl(bestX, 0, lane);
+				bestY = laneShfl(bestY, 0, lane);
 			}
 			angle = atan2(bestY, bestX);
 			dirX = bestX; dirY = bestY;
@@ -1019,8 +1063,8 @@ __global__ __launch_bounds__(256) void k_describe(DescParams P) {
 			if (lane == 0) {
 				for (int i = 0; i < n; i++) { Dx += dX[i]; Dy += dY[i]; }
 			}
-			Dx = __shfl(Dx, 0, 64);
-			Dy = __shfl(Dy, 0, 64);
+			Dx = laneShfl(Dx, 0, lane);
+			Dy = laneShfl(Dy, 0, lane);
 			angle = atan2(Dy, Dx);
 			dirX = Dx; dirY = Dy;
 		}
@@ -1184,7 +1228,7 @@ __global__ __launch_bounds__(256) void k_describe(DescParams P) {
 		}
 #pragma unroll
 		for (int o = 1; o <= 2; o <<= 1) {
-			a0 += __shfl_xor(a0, o, 64); a1 += __shfl_xor(a1, o, 64); a2 += __shfl_xor(a2, o, 64); a3 += __shfl_xor(a3, o, 64);
+			a0 += laneShflXor(a0, o, lane); a1 += laneShflXor(a1, o, lane); a2 += laneShflXor(a2, o, lane); a3 += laneShflXor(a3, o, lane);
 		}
 		double sum = q == 0 ? a0 : q == 1 ? a1 : q == 2 ? a2 : a3;
 		if (stableDesc) sum = T.weightGrid[sub] * sum;
@@ -1235,7 +1279,7 @@ __global__ __launch_bounds__(256) void k_describe(DescParams P) {
 	double norm = 0;
 	for (int f = lane; f < dofAll; f += 64) { const double v = feat[f]; norm += v * v; }
 #pragma unroll
-	for (int o = 32; o >= 1; o >>= 1) norm += __shfl_xor(norm, o, 64);
+	for (int o = 32; o >= 1; o >>= 1) norm += laneShflXor(norm, o, lane);
 	double* out = P.desc + g * dofAll;
 	if (norm == 0) {
 		for (int f = lane; f < dofAll; f += 64) out[f] = feat[f];
@@ -1248,7 +1292,7 @@ __global__ __launch_bounds__(256) void k_describe(DescParams P) {
 		TAP bs[4];
 #pragma unroll
 		for (int b = 0; b < 4; b++) {
-			const TAP br = __shfl(lapTap, 4 * b, 64), tr = __shfl(lapTap, 4 * b + 1, 64), bl = __shfl(lapTap, 4 * b + 2, 64), tl = __shfl(lapTap, 4 * b + 3, 64);
+			const TAP br = laneShfl(lapTap, 4 * b, lane), tr = laneShfl(lapTap, 4 * b + 1, lane), bl = laneShfl(lapTap, 4 * b + 2, lane), tl = laneShfl(lapTap, 4 * b + 3, lane);
 			bs[b] = br - tr - bl + tl;
 		}
 		// convolveSparse: ret = 0; ret += block * scale in the integral image's type (float scales for GrayF32, int for GrayS32), then widened
@@ -1263,6 +1307,51 @@ __global__ __launch_bounds__(256) void k_describe(DescParams P) {
 		if (lane == 0) P.white[g] = lap > 0 ? 1 : 0;
 	}
 	DSTAMP(6);
+}
+
+template <bool STAMP, int EPLT, int TWT, class TAP, int CFG = 0>
+__global__ __launch_bounds__(256) void k_describe(DescParams P) {
+	extern __shared__ __attribute__((aligned(16))) unsigned char ldsAll[];
+	// the wave index is uniform by construction; telling the compiler so keeps everything derived from the key point (image, scale, kernel
+	// radius, tap strides) in scalar registers and the gathers in base + 32-bit-offset form
+	const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+	const int lane0 = threadIdx.x & 63;
+	unsigned char* lds = ldsAll + (size_t)wave * P.ldsPerWave;
+#ifdef BHIP_EXPERIMENTS
+	const int variant = P.variant;
+#else
+	constexpr int variant = 0;
+#endif
+	unsigned long long waveStart = STAMP ? __builtin_readcyclecounter() : 0;   // stamp 7: before the address chain of a key point
+	int cur = blockIdx.x & 7, tried = 0;
+	long long slot = 0;
+	if (variant & DESC_VAR_ONESHOT) {
+		// block b takes key-point group (b % 8) * chunk + b / 8 of the processing order
+		const long long nblk = (P.total + 3) >> 2;
+		const long long chunk = (nblk + 7) >> 3;
+		const long long blk = (long long)(blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+		if ((long long)(blockIdx.x >> 3) >= chunk) return;
+		slot = blk * 4 + wave;
+		if (slot >= P.total) return;
+	} else if (!queueNext(P, lane0, cur, tried, slot)) {
+		return;
+	}
+	for (;;) {
+		// the lane index is made opaque once per key point: what depends on the lane alone (sample positions in the grids, LDS addresses,
+		// shuffle sources) would otherwise be hoisted out of this loop and held in registers across it, at the cost of the fourth wave per SIMD
+		int lane = lane0;
+		asm volatile("" : "+v"(lane));
+		long long g;
+		int img;
+		KeyPoint kp;
+		loadSlot(P, slot, variant, g, img, kp);
+		if (STAMP && lane == 0) P.stamps[g * 16 + 7] = waveStart;
+		describeOne<STAMP, EPLT, TWT, TAP, CFG>(P, g, img, kp, lds, lane);
+		if (variant & DESC_VAR_ONESHOT) break;
+		if (STAMP) waveStart = __builtin_readcyclecounter();
+		if (!queueNext(P, lane, cur, tried, slot)) break;
+		waveSync();   // the sums and the normalisation have read this slice; the next key point's orientation overwrites it
+	}
 }
 
 // 1 = FactoryDetectDescribe.surfStable defaults, 2 = surfFast defaults (the CFG template argument of k_describe), 0 = anything else
@@ -1288,13 +1377,68 @@ int bhip_describe_lds_bytes(const SurfTables& t, int nBands) {
 	return (b + 15) & ~15;
 }
 
+// Workgroups of a launch: the waves are persistent, so as many workgroups as the device holds at once -- the LDS of `ldsBytes` per workgroup
+// and the registers of `fn` decide how many a CU takes -- and never more than one per four slots.  0: the runtime could not say.
+static unsigned bhip_describe_grid(bhip_ctx* ctx, const void* fn, size_t ldsBytes, long long blocks, const DescParams& P) {
+#ifdef BHIP_EXPERIMENTS
+	if (P.variant & DESC_VAR_ONESHOT) return (unsigned)blocks;
+#endif
+	int perCU = 0;
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, fn, 256, ldsBytes) != hipSuccess || perCU <= 0) { (void)hipGetLastError(); return 0; }
+	return (unsigned)std::min<long long>(blocks, (long long)perCU * ctx->cuCount);
+}
+
+#ifdef BHIP_EXPERIMENTS
+// BHIP_DESCRIBE_STAMPS: how the key points were handed out.  Stamp 7 is taken before a key point's address chain, stamp 0 after it, stamp 6
+// at its end.  For the one-key-point-per-wave launch the four slots of a workgroup are grouped through the order records: the workgroup
+// holds its LDS and wave slots from its first stamp 7 to its last stamp 6, and a wave that has finished before that is parked.
+static void bhip_describe_stamp_queue_summary(FILE* f, const std::vector<unsigned long long>& h, const std::vector<KpOrder>& hp, long long total, int variant,
+											  int batch) {
+	double chain = 0, life = 0;
+	long long cnt = 0;
+	for (long long k = 0; k < total; k++) {
+		const unsigned long long* tt = &h[(size_t)k * 16];
+		if (!tt[6] || !tt[0] || !tt[7]) continue;
+		chain += (double)(tt[0] - tt[7]); life += (double)(tt[6] - tt[7]); cnt++;
+	}
+	if (!cnt) return;
+	fprintf(f, "batch %d  key points %lld  variant bits %d  avg cycles: wave start (or end of the previous key point) to stamp 0 %.0f  key point in all %.0f\n", batch, total,
+			variant, chain / cnt, life / cnt);
+	if (!(variant & DESC_VAR_ONESHOT)) return;
+	double ratio = 0, parked = 0, held = 0;
+	long long groups = 0;
+	for (long long s0 = 0; s0 < total; s0 += 4) {
+		unsigned long long first = ~0ull, last = 0;
+		double lifeMax = 0, lifeSum = 0, endSum = 0;
+		int n = 0;
+		for (long long s = s0; s < std::min(total, s0 + 4); s++) {
+			const long long g = hp.empty() ? s : hp[(size_t)s].g;
+			const unsigned long long* tt = &h[(size_t)g * 16];
+			if (!tt[6] || !tt[7]) continue;
+			first = std::min(first, tt[7]); last = std::max(last, tt[6]);
+			const double l = (double)(tt[6] - tt[7]);
+			lifeMax = std::max(lifeMax, l); lifeSum += l; endSum += (double)tt[6];
+			n++;
+		}
+		if (n < 4) continue;   // the ragged last group
+		ratio += lifeMax / (lifeSum / n);
+		parked += n * (double)last - endSum;
+		held += n * (double)(last - first);
+		groups++;
+	}
+	if (groups) fprintf(f, "   workgroups %lld  mean of max(life)/mean(life) %.3f  parked share of the held wave slots %.1f %%\n", groups, ratio / groups, 100.0 * parked / held);
+}
+#endif
+
 template <class T>
 int bhip_launch_describe_ex(bhip_ctx* ctx, DevImg<const T> ii, const KeyPoint* kps, int cap, const int* imageStart, int singleImage, long long total,
-							SurfTables t, const double* anglesIn, double* angles, double* desc, uint8_t* white, const int* perm, DescPlanar planar) {
+							SurfTables t, const double* anglesIn, double* angles, double* desc, uint8_t* white, const KpOrder* perm, int* queue,
+							DescPlanar planar) {
 	if (total <= 0) return BHIP_OK;
+	if (!queue || ctx->cuCount <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "describe: no slot counters");
 	DescParams P;
 	P.ii = bhip_kernel_view(ii); P.kps = kps; P.cap = cap; P.imageStart = imageStart; P.batch = ii.batch; P.singleImage = singleImage; P.total = total; P.t = t;
-	P.anglesIn = anglesIn; P.angles = angles; P.desc = desc; P.white = white; P.perm = perm;
+	P.anglesIn = anglesIn; P.angles = angles; P.desc = desc; P.white = white; P.perm = perm; P.queue = queue;
 	P.bandData = nullptr; P.bandImageStride = P.bandStride = 0; P.nBands = 0;
 	if (planar.nBands > 0) {
 		if (!planar.data) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad planar description request");
@@ -1308,12 +1452,23 @@ int bhip_launch_describe_ex(bhip_ctx* ctx, DevImg<const T> ii, const KeyPoint* k
 #ifdef BHIP_EXPERIMENTS
 	{ const char* e = getenv("BHIP_DESCRIBE_STOP"); P.stopAfter = e ? atoi(e) : -1; }
 	{ const char* e = getenv("BHIP_DESCRIBE_WSTOP"); P.windowStop = e ? atoi(e) : -1; }
+	{
+		// w: the launch before the queue (one key point per wave, image by search); i: the same with the order record's image; anything else:
+		// what ships
+		const char* e = getenv("BHIP_DESCRIBE_VARIANT");
+		const char v = e ? e[0] : 0;
+		P.variant = v == 'w' ? (DESC_VAR_ONESHOT | DESC_VAR_SEARCH) : v == 'i' ? DESC_VAR_ONESHOT : 0;
+		// the two-launch experiments share one set of counters: they run the launch before the queue
+		const char* sp = getenv("BHIP_DESCRIBE_SPLIT");
+		if (sp && (sp[0] == '1' || sp[0] == '2')) P.variant |= DESC_VAR_ONESHOT;
+	}
 #endif
 	if (t.oriWidth * t.oriWidth > 64 * ORI_EPL_MAX) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "orientation sample grid too large for the GPU path");
 	if (t.widthSubRegion + 2 * (t.stable ? t.overLap : 0) > DESC_ROW_MAX) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "SURF sub-region too wide for the GPU path");
 	if (P.ldsPerWave * 4 > 160 * 1024) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "orientation/descriptor sample grid too large for LDS");
-	const long long blocks = ((((total + 3) / 4) + 7) / 8) * 8;   // whole rounds over the 8 XCDs
+	const long long blocks = ((((total + 3) / 4) + 7) / 8) * 8;   // four slots per workgroup, whole rounds over the 8 XCDs
 	if (blocks > 0x7fffffffLL) return bhip_fail(ctx, BHIP_ERR_INVALID, "too many key points");
+	BHIP_HIP(ctx, hipMemsetAsync(queue, 0, BHIP_DESCRIBE_QUEUE_BYTES, ctx->stream));
 	if ((long long)ii.stride * ii.height > 0x3fffffffLL || ii.stride >= (1 << 17)) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "integral image too large for 32-bit tap offsets");
 #ifdef BHIP_EXPERIMENTS
 	const char* stampPath = getenv("BHIP_DESCRIBE_STAMPS");
@@ -1324,13 +1479,14 @@ int bhip_launch_describe_ex(bhip_ctx* ctx, DevImg<const T> ii, const KeyPoint* k
 			(void)hipMemsetAsync(dev, 0, (size_t)total * 128, ctx->stream);
 			P.stamps = dev;
 			{
-				const int epl = (t.oriWidth * t.oriWidth + 63) / 64;
-				const int tw = t.widthSubRegion + 2 * (t.stable ? t.overLap : 0);
-				if (bhip_describe_default_cfg(t) == 1) hipLaunchKernelGGL((k_describe<true, 5, 9, float, 1>), dim3((unsigned)blocks), dim3(256), (size_t)P.ldsPerWave * 4, ctx->stream, P);
-				else hipLaunchKernelGGL((k_describe<true, 8, 16, float>), dim3((unsigned)blocks), dim3(256), (size_t)P.ldsPerWave * 4, ctx->stream, P);
+				const void* sfn = bhip_describe_default_cfg(t) == 1 ? (const void*)k_describe<true, 5, 9, float, 1> : (const void*)k_describe<true, 8, 16, float>;
+				void* sargs[] = {(void*)&P};
+				(void)hipLaunchKernel(sfn, dim3(bhip_describe_grid(ctx, sfn, (size_t)P.ldsPerWave * 4, blocks, P)), dim3(256), sargs, (size_t)P.ldsPerWave * 4, ctx->stream);
 			}
 			std::vector<unsigned long long> h((size_t)total * 16);
+			std::vector<KpOrder> hp(P.perm ? (size_t)total : 0);
 			(void)hipMemcpyAsync(h.data(), dev, (size_t)total * 128, hipMemcpyDeviceToHost, ctx->stream);
+			if (P.perm) (void)hipMemcpyAsync(hp.data(), P.perm, (size_t)total * sizeof(KpOrder), hipMemcpyDeviceToHost, ctx->stream);
 			(void)hipStreamSynchronize(ctx->stream);
 			(void)hipFree(dev);
 			double sum[7] = {0}, wsum[6] = {0};
@@ -1343,6 +1499,7 @@ int bhip_launch_describe_ex(bhip_ctx* ctx, DevImg<const T> ii, const KeyPoint* k
 				cnt++;
 			}
 			FILE* f = fopen(stampPath, "a");
+			if (f) bhip_describe_stamp_queue_summary(f, h, hp, total, P.variant, ii.batch);
 			if (f && cnt) {
 				fprintf(f, "waves %lld  avg cycles: samples %.0f  sort %.0f  window+atan2 %.0f  descSamples %.0f  sums %.0f  norm+laplace %.0f\n", cnt,
 						sum[1] / cnt, sum[2] / cnt, sum[3] / cnt, sum[4] / cnt, sum[5] / cnt, sum[6] / cnt);
@@ -1363,7 +1520,7 @@ int bhip_launch_describe_ex(bhip_ctx* ctx, DevImg<const T> ii, const KeyPoint* k
 		ProfScope ps(ctx, "k_describe", perKp * (double)total);
 		const int epl = (t.oriWidth * t.oriWidth + 63) / 64;
 		const int tw = t.widthSubRegion + 2 * (t.stable ? t.overLap : 0);
-		const dim3 grid((unsigned)blocks), block(256);
+		const dim3 block(256);
 		size_t ldsBytes = (size_t)P.ldsPerWave * 4;
 #ifdef BHIP_EXPERIMENTS
 		{ const char* e = getenv("BHIP_DESCRIBE_LDSPAD"); if (e) ldsBytes += (size_t)atoi(e); }   // occupancy experiments only
@@ -1381,6 +1538,8 @@ int bhip_launch_describe_ex(bhip_ctx* ctx, DevImg<const T> ii, const KeyPoint* k
 		// colour SURF with many bands / large sample grids need more than the default 64 KB of dynamic LDS
 		if (ldsBytes > 65536) BHIP_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes));
 		void* args[] = {(void*)&P};
+		const dim3 grid(bhip_describe_grid(ctx, fn, ldsBytes, blocks, P));
+		if (grid.x == 0) return bhip_fail(ctx, BHIP_ERR_HIP, "k_describe: no workgroup fits a compute unit");
 #ifdef BHIP_EXPERIMENTS
 		{
 			// experiment: orientation and descriptor as two launches of the same kernel (how long does each half take on its own?)
@@ -1424,5 +1583,5 @@ int bhip_launch_describe_ex(bhip_ctx* ctx, DevImg<const T> ii, const KeyPoint* k
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
 }
-template int bhip_launch_describe_ex(bhip_ctx*, DevImg<const float>, const KeyPoint*, int, const int*, int, long long, SurfTables, const double*, double*, double*,  uint8_t*, const int*, DescPlanar);
-template int bhip_launch_describe_ex(bhip_ctx*, DevImg<const int32_t>, const KeyPoint*, int, const int*, int, long long, SurfTables, const double*, double*, double*,  uint8_t*, const int*, DescPlanar);
+template int bhip_launch_describe_ex(bhip_ctx*, DevImg<const float>, const KeyPoint*, int, const int*, int, long long, SurfTables, const double*, double*, double*,  uint8_t*, const KpOrder*, int*, DescPlanar);
+template int bhip_launch_describe_ex(bhip_ctx*, DevImg<const int32_t>, const KeyPoint*, int, const int*, int, long long, SurfTables, const double*, double*, double*,  uint8_t*, const KpOrder*, int*, DescPlanar);

@@ -805,7 +805,8 @@ int bhip_launch_blocks_to_xy(bhip_ctx* ctx, const unsigned int* bitmap, const un
 // ---------------------------------------------------------------------------------------------------------------
 // Processing order for the describe stage.  Results stay in detection order; only the order in which key points are WORKED ON changes:
 // image-major, then by coarse image tile (KPT x KPT tiles per image, raster), so the key points in flight on one XCD gather from one
-// compact part of the integral image and their taps hit that XCD's L2.  perm[slot] = compact index of the key point handled by slot.
+// compact part of the integral image and their taps hit that XCD's L2.  perm[slot] = compact index of the key point handled by slot, with
+// its image and its index there: this side knows both, so k_describe needs no search of the image starts.
 // ---------------------------------------------------------------------------------------------------------------
 #define KPT 8
 __global__ __launch_bounds__(256) void k_kp_tile_count(const KeyPoint* __restrict__ kps, int cap, const int* __restrict__ start, int W, int H,
@@ -831,7 +832,7 @@ __global__ __launch_bounds__(64) void k_kp_tile_scan(int* __restrict__ hist) {
 	hist[img * 64 + lane] = sc - c;
 }
 __global__ __launch_bounds__(256) void k_kp_tile_scatter(const KeyPoint* __restrict__ kps, int cap, const int* __restrict__ start, int W, int H,
-														 int* __restrict__ cursor, int* __restrict__ perm) {
+														 int* __restrict__ cursor, KpOrder* __restrict__ perm) {
 	const int img = blockIdx.y;
 	const int s0 = start[img];
 	const int n = start[img + 1] - s0;
@@ -840,11 +841,11 @@ __global__ __launch_bounds__(256) void k_kp_tile_scatter(const KeyPoint* __restr
 	const KeyPoint kp = kps[(long long)img * cap + i];
 	const int tx = min(KPT - 1, max(0, (int)(kp.x * KPT / W))), ty = min(KPT - 1, max(0, (int)(kp.y * KPT / H)));
 	const int pos = atomicAdd(&cursor[img * (KPT * KPT) + ty * KPT + tx], 1);
-	perm[s0 + pos] = s0 + i;
+	perm[s0 + pos] = KpOrder{s0 + i, img, i, 0};
 }
 
 int bhip_launch_kp_spatial_order(bhip_ctx* ctx, const KeyPoint* kps, int cap, const int* start, int batch, int maxCount, int W, int H, int* hist /*batch*64*/,
-								 int* perm) {
+								 KpOrder* perm) {
 	if (batch <= 0 || maxCount <= 0) return BHIP_OK;
 	static_assert(KPT * KPT == 64, "k_kp_tile_scan assumes 64 tiles");
 	BHIP_HIP(ctx, hipMemsetAsync(hist, 0, (size_t)batch * 64 * 4, ctx->stream));
