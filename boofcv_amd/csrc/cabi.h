@@ -24,6 +24,8 @@ struct CtxScratch {
 	DevBuf in0, in1, out0, out1, tmp0, tmp1;                                 // staging
 	DevBuf work, assocCol, nmsBitmap, nmsPrefix, nmsPos, ipTmp, ipKernel, fast, disparity, distortMap, templ, flow, threshold;   // device side
 	long long flowPixels = 0;   // pixels of the last bhip_flow_klt_* call (bhip_flow_klt_stats)
+	DevBuf binary, label;           // cabi_binary.hip: the two ping-pong images of a long erode / dilate run; parent[] and row counts of the labelling
+	DevBuf binaryTable;             // the host forms' relabel / labelToBinary lookup table
 	DevBuf thresholdTaps;           // the Kernel1D_S32 Gaussian taps of the GrayU8 blurs, for thresholdTapsRadius (0: none yet)
 	int thresholdTapsRadius = 0;
 	AssocMfmaWork mfma;

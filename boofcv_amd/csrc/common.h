@@ -609,3 +609,20 @@ size_t bhip_block_threshold_scratch(int kind, int nbx, int nby, int images);
 // `chunk` images go through the three stages at a time; scratch: bhip_block_threshold_scratch(kind, nbx, nby, chunk) bytes
 template <class T>
 int bhip_launch_block_threshold(bhip_ctx* ctx, const ThreshBlocks& c, DevImg<const T> in, DevImg<uint8_t> out, void* scratch, int chunk);
+
+// ---------------- BinaryImageOps: logic, morphology, label utilities (binary_ops.hip) and blob labelling (label.hip) ----------------
+// iterations of erode / dilate that one launch applies inside an LDS tile (its halo); longer runs ping-pong between context scratch images
+#define BHIP_MORPH_FUSED_MAX 4
+// the neighbourhood operations one kernel serves: BHIP_MORPH_ERODE4 .. BHIP_MORPH_DILATE8 of the header, then these
+#define BHIP_MORPH_EDGE4 4
+#define BHIP_MORPH_EDGE8 5
+#define BHIP_MORPH_REMOVE_POINT_NOISE 6
+// op: BHIP_LOGIC_*; b == nullptr: invert(a).  out may be a or b
+int bhip_launch_binary_logic(bhip_ctx* ctx, int op, DevImg<const uint8_t> a, const DevImg<const uint8_t>* b, DevImg<uint8_t> out);
+// n iterations (1 .. BHIP_MORPH_FUSED_MAX) of a BHIP_MORPH_* operation in one launch; in and out must not overlap
+int bhip_launch_binary_morph(bhip_ctx* ctx, int op, int outsideZero, int n, DevImg<const uint8_t> in, DevImg<uint8_t> out);
+int bhip_launch_relabel(bhip_ctx* ctx, DevImg<int32_t> img, const int* devLabels, int numLabels);
+int bhip_launch_label_to_binary(bhip_ctx* ctx, DevImg<const int32_t> in, DevImg<uint8_t> out, const uint8_t* devSelected, int numSelected);
+size_t bhip_label_scratch(int width, int height, int images);
+// width * height must fit an int and the image at most 65535 tiles of 32 rows high; scratch: bhip_label_scratch(width, height, in.batch) bytes
+int bhip_launch_label_blobs(bhip_ctx* ctx, bool eight, DevImg<const uint8_t> in, DevImg<int32_t> out, int* devNumBlobs, void* scratch);

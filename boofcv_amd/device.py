@@ -20,7 +20,10 @@ Names follow the reference classes the host-buffer forms in boofcv_amd/api/ mirr
   DeviceImageOps.denseFlowKlt   DenseOpticalFlow.process (flowKlt, GrayF32 / GrayU8)  F:factory/flow/FactoryDenseOpticalFlow.java:61-82
   DeviceImageOps.threshold      InputToBinary.process (FactoryThresholdBinary.threshold)  I:factory/filter/binary/FactoryThresholdBinary.java:318-372
   DeviceImageOps.meanU8 / gaussianU8  BlurImageOps.mean / gaussian on GrayU8           I:alg/filter/blur/BlurImageOps.java:75-141
-  DeviceImageOps.brief          DescribePointBrief.process                          F:alg/feature/describe/DescribePointBrief.java:73-89
+  DeviceImageOps.binaryLogic / binaryInvert / erode / dilate / edge / removePointNoise   BinaryImageOps (GrayU8 0/1)   I:alg/filter/binary/BinaryImageOps.java:69-411
+  DeviceImageOps.labelBlobs     the labelled image and blob count of BinaryImageOps.contour     I:alg/filter/binary/LinearContourLabelChang2004.java:96-152
+  DeviceImageOps.relabel / labelToBinary   BinaryImageOps.relabel / labelToBinary                I:alg/filter/binary/BinaryImageOps.java:509-557
+  DeviceImageOps.brief          DescribePointBrief.process                         F:alg/feature/describe/DescribePointBrief.java:73-89
   DeviceKltTracker              PointTrackerKltPyramid, batched over sequences      main/boofcv-geo/.../abst/feature/tracker/PointTrackerKltPyramid.java:139-348
   DeviceBackgroundModel         BackgroundStationaryBasic / Gaussian / Gmm, batched over streams   F:alg/background/stationary/*.java
 """
@@ -125,6 +128,94 @@ class DeviceImageOps:
         ip, iis, irs, W, H, B = _geom(src, torch.uint8)
         out, op, ois, ors = self._u8_out(src, out, B, H, W)
         _check(self.ctx, self.L.bhip_gaussian_dev_u8(self.ctx._h, ip, iis, irs, W, H, B, int(radius), op, ois, ors))
+        return out
+
+    # ---- BinaryImageOps on uint8 0/1 frames [B,H,W] and int32 label images (boofcv_amd/binaryops.py has the host-view forms) ----
+    def binaryLogic(self, op, a, b, out=None):
+        """BinaryImageOps.logicAnd / logicOr / logicXor: op is "and", "or", "xor" or a BHIP_LOGIC_* value.  `out` may be `a` or `b`."""
+        op = {"and": _lib.BHIP_LOGIC_AND, "or": _lib.BHIP_LOGIC_OR, "xor": _lib.BHIP_LOGIC_XOR}.get(op, op)
+        ap, ais, ars, W, H, B = _geom(a, torch.uint8)
+        bp, bis, brs, W2, H2, B2 = _geom(b, torch.uint8)
+        if (W, H, B) != (W2, H2, B2):
+            raise IllegalArgumentException("Image shapes do not match")
+        out, op_, ois, ors = self._u8_out(a, out, B, H, W)
+        _check(self.ctx, self.L.bhip_binary_logic_dev_u8(self.ctx._h, int(op), ap, ais, ars, bp, bis, brs, W, H, B, op_, ois, ors))
+        return out
+
+    def binaryInvert(self, src, out=None):
+        """BinaryImageOps.invert; `out` may be `src`"""
+        ip, iis, irs, W, H, B = _geom(src, torch.uint8)
+        out, op, ois, ors = self._u8_out(src, out, B, H, W)
+        _check(self.ctx, self.L.bhip_binary_invert_dev_u8(self.ctx._h, ip, iis, irs, W, H, B, op, ois, ors))
+        return out
+
+    def _morph(self, op, src, numTimes, out):
+        if op == _lib.BHIP_MORPH_ERODE4 and numTimes <= 0:
+            raise IllegalArgumentException("numTimes must be >= 1")
+        ip, iis, irs, W, H, B = _geom(src, torch.uint8)
+        out, op_, ois, ors = self._u8_out(src, out, B, H, W)
+        _check(self.ctx, self.L.bhip_binary_morph_dev_u8(self.ctx._h, op, int(numTimes), ip, iis, irs, W, H, B, op_, ois, ors))
+        return out
+
+    def erode(self, src, rule, numTimes=1, out=None):
+        """BinaryImageOps.erode4 / erode8(input, numTimes, output): rule 4 or 8.  Input and output must not overlap."""
+        return self._morph({4: _lib.BHIP_MORPH_ERODE4, 8: _lib.BHIP_MORPH_ERODE8}[int(rule)], src, numTimes, out)
+
+    def dilate(self, src, rule, numTimes=1, out=None):
+        """BinaryImageOps.dilate4 / dilate8(input, numTimes, output)"""
+        return self._morph({4: _lib.BHIP_MORPH_DILATE4, 8: _lib.BHIP_MORPH_DILATE8}[int(rule)], src, numTimes, out)
+
+    def edge(self, src, rule, outsideZero=True, out=None):
+        """BinaryImageOps.edge4 / edge8(input, output, outsideZero)"""
+        ip, iis, irs, W, H, B = _geom(src, torch.uint8)
+        out, op, ois, ors = self._u8_out(src, out, B, H, W)
+        _check(self.ctx, self.L.bhip_binary_edge_dev_u8(self.ctx._h, int(rule), int(bool(outsideZero)), ip, iis, irs, W, H, B, op, ois, ors))
+        return out
+
+    def removePointNoise(self, src, out=None):
+        """BinaryImageOps.removePointNoise"""
+        ip, iis, irs, W, H, B = _geom(src, torch.uint8)
+        out, op, ois, ors = self._u8_out(src, out, B, H, W)
+        _check(self.ctx, self.L.bhip_binary_remove_point_noise_dev_u8(self.ctx._h, ip, iis, irs, W, H, B, op, ois, ors))
+        return out
+
+    def labelBlobs(self, src, rule, out=None, numBlobs=None):
+        """The labelled image and the blob count of BinaryImageOps.contour(input, rule, output) on uint8 frames [B,H,W] -> (labels int32 [B,H,W],
+        numBlobs int32 [B]), both on the device: 0 for background, blobs numbered 1..N per image in the raster order of their first pixel.
+        `out` (int32, any stride) is written in place.  The contour point lists are not produced.  No host synchronisation."""
+        ip, iis, irs, W, H, B = _geom(src, torch.uint8)
+        if out is None:
+            out = torch.empty((B, H, W), dtype=torch.int32, device=src.device)
+        op, ois, ors, W2, H2, B2 = _geom(out, torch.int32)
+        if (W, H, B) != (W2, H2, B2):
+            raise IllegalArgumentException("input and output shapes differ")
+        if numBlobs is None:
+            numBlobs = torch.empty((B,), dtype=torch.int32, device=src.device)
+        if numBlobs.dtype != torch.int32 or numBlobs.shape != (B,) or not numBlobs.is_contiguous() or not numBlobs.is_cuda:
+            raise IllegalArgumentException("numBlobs must be a contiguous int32 CUDA tensor [B]")
+        _check(self.ctx, self.L.bhip_label_blobs_dev_u8_s32(self.ctx._h, int(rule), ip, iis, irs, W, H, B, op, ois, ors, C.c_void_p(numBlobs.data_ptr())))
+        return out, numBlobs
+
+    def relabel(self, labels, table):
+        """BinaryImageOps.relabel in place on int32 label images [B,H,W]; table: int32 CUDA tensor [numLabels].  A pixel outside the table stays."""
+        ip, iis, irs, W, H, B = _geom(labels, torch.int32)
+        if table.dtype != torch.int32 or table.dim() != 1 or not table.is_contiguous() or not table.is_cuda:
+            raise IllegalArgumentException("the table must be a contiguous 1-D int32 CUDA tensor")
+        _check(self.ctx, self.L.bhip_relabel_dev_s32(self.ctx._h, ip, iis, irs, W, H, B, C.c_void_p(table.data_ptr()), table.numel()))
+        return labels
+
+    def labelToBinary(self, labels, selected=None, out=None):
+        """BinaryImageOps.labelToBinary(labelImage, binaryImage[, selectedBlobs]); selected: uint8 / bool CUDA tensor [numLabels] or None"""
+        ip, iis, irs, W, H, B = _geom(labels, torch.int32)
+        out, op, ois, ors = self._u8_out(labels, out, B, H, W)
+        sp, n = None, 0
+        if selected is not None:
+            if selected.dtype == torch.bool:
+                selected = selected.to(torch.uint8)
+            if selected.dtype != torch.uint8 or selected.dim() != 1 or not selected.is_contiguous() or not selected.is_cuda:
+                raise IllegalArgumentException("selected must be a contiguous 1-D uint8 or bool CUDA tensor")
+            sp, n = C.c_void_p(selected.data_ptr()), selected.numel()
+        _check(self.ctx, self.L.bhip_label_to_binary_dev_s32_u8(self.ctx._h, ip, iis, irs, W, H, B, op, ois, ors, sp, n))
         return out
 
     def _grad(self, fn, src, border, dx, dy):

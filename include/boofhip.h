@@ -1162,6 +1162,80 @@ int bhip_mean_dev_u8(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStri
 int bhip_gaussian_dev_u8(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, int radius,
 						 uint8_t* dev_out, long long outImageStride, int outStride);
 
+/* ---- binary images: BinaryImageOps (I:alg/filter/binary/BinaryImageOps.java) on GrayU8 0/1 images and GrayS32 label images
+ *      (binary_ops.hip, label.hip).  There is no BOverride hook for BinaryImageOps in the reference: integration/java/boofcv/hip/BinaryImageOpsHip.java
+ *      is a provider class with the same static signatures.
+ * The _dev forms take batch images at dev_x + b*xImageStride (strides in elements, any alignment), write the whole width x height view of every
+ * output image and nothing outside it, are asynchronous on the context's stream without host synchronisation, and keep their scratch in the
+ * context.  The forms without _dev take one host image view each: staged, run through the _dev form, synchronised.
+ * Results equal the single-threaded Java results bit for bit on images that hold only 0 and 1.  Other byte values: the logic operations still
+ * follow the reference's tests (== 1, == 0, !=); the neighbourhood operations give an unspecified result inside the view (the reference sums
+ * raw signed bytes in its inner loops and unsigned get() values on the frame; here every byte counts as unsigned).
+ * Not provided: thin (BinaryThinning), the contour point lists of contour / contourExternal, labelToClusters, clusterToBinary, image types other
+ * than GrayU8 / GrayS32.
+ * BHIP_ERR_INVALID and nothing is written: empty images, strides smaller than a row, an unknown op or rule, erode4 with numTimes <= 0
+ * ("numTimes must be >= 1"), overlapping input and output of a neighbourhood operation.  BHIP_ERR_UNSUPPORTED: more than 65535 images in a
+ * batch; for the labelling, width * height beyond an int32 index or more than 2097120 rows. */
+#define BHIP_LOGIC_AND 0 /* ImplBinaryImageOps.logicAnd: a == 1 && a == b */
+#define BHIP_LOGIC_OR 1  /* a == 1 || b == 1 */
+#define BHIP_LOGIC_XOR 2 /* a != b */
+/* BinaryImageOps.logicAnd / logicOr / logicXor (:69-125, impl/ImplBinaryImageOps.java:30-78).  dev_out may be dev_a or dev_b (the same view). */
+int bhip_binary_logic_dev_u8(bhip_ctx* ctx, int op, const uint8_t* dev_a, long long aImageStride, int aStride, const uint8_t* dev_b, long long bImageStride,
+							 int bStride, int width, int height, int batch, uint8_t* dev_out, long long outImageStride, int outStride);
+int bhip_binary_logic_u8(bhip_ctx* ctx, int op, const uint8_t* a, int aStart, int aStride, const uint8_t* b, int bStart, int bStride, int width, int height,
+						 uint8_t* out, int outStart, int outStride);
+/* BinaryImageOps.invert (:134-145, ImplBinaryImageOps.java:80-93): in == 0 ? 1 : 0.  dev_out may be dev_in. */
+int bhip_binary_invert_dev_u8(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, uint8_t* dev_out,
+							  long long outImageStride, int outStride);
+int bhip_binary_invert_u8(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, uint8_t* out, int outStart, int outStride);
+/* BinaryImageOps.erode4 / dilate4 / erode8 / dilate8(input, numTimes, output) (:158-361): impl/ImplBinaryInnerOps.java for 1 <= x < width-1,
+ * 1 <= y < height-1, then impl/ImplBinaryBorderOps.java in its loop order (every x: top, bottom; every y: left, right -- the last write stands,
+ * which is what widths and heights of 1 and 2 and the corners come out of).  The value outside the image is 0 for erode4, dilate4 and dilate8
+ * and 1 for erode8 (ImplBinaryBorderOps.java:105), at every iteration.  erode4 refuses numTimes <= 0; the other three apply the operation once
+ * for numTimes <= 1.  Up to 4 iterations run in one launch inside an LDS tile with a halo; more repeat such launches between two scratch images.
+ * Input and output must not overlap. */
+#define BHIP_MORPH_ERODE4 0
+#define BHIP_MORPH_DILATE4 1
+#define BHIP_MORPH_ERODE8 2
+#define BHIP_MORPH_DILATE8 3
+int bhip_binary_morph_dev_u8(bhip_ctx* ctx, int op, int numTimes, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch,
+							 uint8_t* dev_out, long long outImageStride, int outStride);
+int bhip_binary_morph_u8(bhip_ctx* ctx, int op, int numTimes, const uint8_t* in, int inStart, int inStride, int width, int height, uint8_t* out, int outStart,
+						 int outStride);
+/* BinaryImageOps.edge4 / edge8(input, output, outsideZero) (:258-269, :378-389); rule: BHIP_CONNECT_*.  outsideZero != 0: the frame is a copy of
+ * the input (ImplBinaryBorderOps.edge_outside0), otherwise the value outside the image is 1.  Input and output must not overlap. */
+#define BHIP_CONNECT_FOUR 4 /* ConnectRule.FOUR (T:struct/ConnectRule.java) */
+#define BHIP_CONNECT_EIGHT 8
+int bhip_binary_edge_dev_u8(bhip_ctx* ctx, int rule, int outsideZero, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch,
+							uint8_t* dev_out, long long outImageStride, int outStride);
+int bhip_binary_edge_u8(bhip_ctx* ctx, int rule, int outsideZero, const uint8_t* in, int inStart, int inStride, int width, int height, uint8_t* out, int outStart,
+						int outStride);
+/* BinaryImageOps.removePointNoise (:400-411): 8-neighbour total < 2 -> 0, > 6 -> 1, else the input; outside is 0 and the frame rows and columns
+ * have no "> 6" branch (ImplBinaryBorderOps.java:297-339).  Input and output must not overlap. */
+int bhip_binary_remove_point_noise_dev_u8(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch,
+										  uint8_t* dev_out, long long outImageStride, int outStride);
+int bhip_binary_remove_point_noise_u8(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, uint8_t* out, int outStart, int outStride);
+/* The labelled image and getContours().size of BinaryImageOps.contour(input, rule, output) (:457-469, LinearContourLabelChang2004.process :96-152):
+ * a pixel equal to 1 is foreground, background gets 0, blobs are numbered 1..N per image in the raster order of their first pixel, and N goes to
+ * dev_numBlobs[b].  The contour point lists are not produced.  Parity holds for images of 0 and 1: on other values the reference scans and
+ * traces with != 1 but tests the pixel below with == 0 (step 2), so it is not the connected components of the 1s there; this is.  Union-find with the smallest linear index as root, then a raster-order rank of
+ * the roots: six launches, no workgroup waits for another.  Scratch: 4 bytes per pixel plus 4 per row, for at most 256 MiB of images at a time. */
+int bhip_label_blobs_dev_u8_s32(bhip_ctx* ctx, int rule, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch,
+								int32_t* dev_out, long long outImageStride, int outStride, int* dev_numBlobs);
+int bhip_label_blobs_u8_s32(bhip_ctx* ctx, int rule, const uint8_t* in, int inStart, int inStride, int width, int height, int32_t* out, int outStart, int outStride,
+							int* numBlobs);
+/* BinaryImageOps.relabel(GrayS32, int[] labels) in place (:509-515): pixel = labels[pixel].  Deviation: a pixel outside [0, numLabels) is left
+ * unchanged (the reference throws ArrayIndexOutOfBoundsException; the device form cannot report it without a synchronisation). */
+int bhip_relabel_dev_s32(bhip_ctx* ctx, int32_t* dev_img, long long imageStride, int stride, int width, int height, int batch, const int* dev_labels, int numLabels);
+int bhip_relabel_s32(bhip_ctx* ctx, int32_t* img, int start, int stride, int width, int height, const int* labels, int numLabels);
+/* BinaryImageOps.labelToBinary(GrayS32, GrayU8) (:524-534: pixel != 0) when selected is null, else labelToBinary(GrayS32, GrayU8, boolean[]
+ * selectedBlobs) (:545-557: selectedBlobs[pixel]) with one byte per entry, non-zero = true.  Deviation: a pixel outside [0, numSelected) gives 0
+ * (the reference throws). */
+int bhip_label_to_binary_dev_s32_u8(bhip_ctx* ctx, const int32_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, uint8_t* dev_out,
+									long long outImageStride, int outStride, const uint8_t* dev_selected, int numSelected);
+int bhip_label_to_binary_s32_u8(bhip_ctx* ctx, const int32_t* in, int inStart, int inStride, int width, int height, uint8_t* out, int outStart, int outStride,
+								const uint8_t* selected, int numSelected);
+
 #ifdef __cplusplus
 }
 #endif
