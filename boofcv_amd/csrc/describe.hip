@@ -28,6 +28,14 @@
 //     full-circle regime;
 //   * the 81-term sub-region sums keep the reference's sequential fp64 order per output but fetch a whole row of samples and
 //     weights per wait.
+//
+// Where the constant tables live (SurfTables: the same values for every key point of a launch):
+//   * surfStable defaults (CFG 1): weightSub (81 doubles) and weightGrid (16) are copied into the wave's LDS slice, behind feat, once per key
+//     point -- two loads per lane issued ahead of the descriptor's first taps, stored before the waveSync that ends the sampling -- and the
+//     sums read them with ds_read_b64; oriWeights: the lane's five values are loaded ahead of the orientation taps and used after them.  No
+//     phase waits on a vector-memory load of a table value at its point of use (behind sixteen waves' gathers such a wait is 1.6-1.8 k cycles).
+//   * surfFast defaults (CFG 2) and the generic kernels (CFG 0) read the tables through their device pointers where they use them; so does
+//     CFG 1 under BHIP_DESCRIBE_TABLEPTR=1 (the cross-check of the copies) and on the merge-sort fallback of the orientation.
 #include "common.h"
 #include <algorithm>
 #include <type_traits>
@@ -59,6 +67,8 @@ struct DescParams {
 	unsigned long long* stamps; // diagnostic build only: [total][16] cycle stamps
 	int sort64;               // BHIP_DESCRIBE_SORT64=1: always sort on the fp64 keys (cross-check of the 32-bit key sort)
 	int serialOnly;           // BHIP_DESCRIBE_SERIAL=1: always run the reference's serial window sweep (cross-check of the parallel form)
+	int tablePtr;             // BHIP_DESCRIBE_TABLEPTR=1: DESC_TBL_* bits, read the constant tables through their device pointers at the point of use
+	                          // (cross-check of the LDS copy / the early loads; the generic instantiations always do)
 #ifdef BHIP_EXPERIMENTS
 	int stopAfter;            // BHIP_DESCRIBE_STOP=k: waves return at phase boundary k (instruction counts per phase by difference; results are garbage)
 	int windowStop;           // BHIP_DESCRIBE_WSTOP=k (8..12): the window sweep returns at its internal boundary k (use with BHIP_DESCRIBE_STOP=3)
@@ -66,9 +76,15 @@ struct DescParams {
 #endif
 };
 
+#ifndef BHIP_DESCRIBE_KARGS
+#define BHIP_DESCRIBE_KARGS 0   // 1 (BHIP_EXP_DEFS=-DBHIP_DESCRIBE_KARGS=1): k_describe reads its arguments again per key point
+#endif
 #define ORI_EPL_MAX 8     // orientation samples per lane (n <= 512, i.e. radius <= 10)
 #define DESC_ROW_MAX 16   // samples per sub-region row (widthSubRegion + 2*overLap)
 #define DESC_BATCH 3      // descriptor samples per lane whose 12 taps each are in flight together
+#define DESC_TBL_SUMS 1   // DescParams::tablePtr: weightSub / weightGrid by pointer in the sums (default: the wave's LDS copy)
+#define DESC_TBL_ORI 2    // DescParams::tablePtr: oriWeights loaded where they are used, after the orientation taps (default: issued ahead of them)
+#define DESC_TBL_DOUBLES (81 + 16)   // CFG 1: weightSub (9x9) | weightGrid (4x4) in the wave's slice, behind feat
 
 // ---- sparse gradient (SparseIntegralGradient_NoBorder_F32) ----
 __device__ __forceinline__ int gradRadius(double width) {
@@ -953,6 +969,16 @@ __device__ __forceinline__ void describeOne(const DescParams& P, const long long
 		// keeps its samples (weighted gradient, angle) in registers: the counting sort scatters them straight to their sorted slots.
 		TAP gx[EPLT], gy[EPLT];
 		double dxr[EPLT], dyr[EPLT], ar[EPLT];
+		// The lane's orientation weights are the same for every key point, but holding them across the key-point loop costs registers the
+		// fourth wave per SIMD needs.  The surfStable defaults issue their loads ahead of the taps: loads return in order, so the weights
+		// are there when the first tap is and the fp64 tail never waits on a table value.  (Index clamped: no branch around the loads.)
+		// surfFast's kernels would pay six more VGPRs for it (73 against 67 / 69) and stay as they were.
+		const bool oriWeightsEarly = CFG == 1 && !(P.tablePtr & DESC_TBL_ORI);
+		double ow[EPLT];
+		if (T.oriHasWeights && oriWeightsEarly) {
+#pragma unroll
+			for (int e = 0; e < EPLT; e++) ow[e] = T.oriWeights[min(lane + 64 * e, n - 1)];
+		}
 		{
 			GradTaps<TAP> tp[EPLT];
 #pragma unroll
@@ -974,7 +1000,7 @@ __device__ __forceinline__ void describeOne(const DescParams& P, const long long
 				double dx = (double)gx[e], dy = (double)gy[e];
 				if (oriSliding) {
 					if (T.oriHasWeights) {
-						const double w = T.oriWeights[idx];
+						const double w = oriWeightsEarly ? ow[e] : T.oriWeights[idx];
 						dx *= w;
 						dy *= w;
 					}
@@ -983,7 +1009,7 @@ __device__ __forceinline__ void describeOne(const DescParams& P, const long long
 				} else {
 					// average variant accumulates w*gx (or gx) in row-major order; stage the addends
 					if (T.oriHasWeights) {
-						const double w = T.oriWeights[idx];
+						const double w = oriWeightsEarly ? ow[e] : T.oriWeights[idx];
 						dX[idx] = w * dx;
 						dY[idx] = w * dy;
 					} else {
@@ -1126,6 +1152,19 @@ __device__ __forceinline__ void describeOne(const DescParams& P, const long long
 	}
 	const int dof = CFG ? 64 : T.dof;
 	const int nb = P.nBands > 0 ? P.nBands : 1;
+	// surfStable defaults: the sums read weightSub and weightGrid from a copy in the wave's slice, behind feat (bhip_describe_lds_bytes leaves
+	// the room).  Two loads per lane, issued here, ahead of the first batch of taps, so their round trip hides under the gathers; stored
+	// before the waveSync that ends the sampling.  The orientation phase of the next key point overwrites the copy, so every key point
+	// makes it again -- a wave's only table traffic, and none of it waited for on its own.
+	const bool ldsTables = CFG == 1 && !(P.tablePtr & DESC_TBL_SUMS);
+	double* wTab = feat + dof * nb;   // [0, 81) weightSub, [81, 97) weightGrid
+	double tw0 = 0.0, tw1 = 0.0;
+	if (ldsTables) {
+		static_assert(DESC_TBL_DOUBLES == 97, "lane l: weightSub[l], then weightSub[64 + l] (l < 17) or weightGrid[l - 17] (l < 33)");
+		tw0 = T.weightSub[lane];
+		const double* second = lane < 17 ? T.weightSub + 64 + lane : T.weightGrid + ((lane - 17) & 15);
+		tw1 = *second;
+	}
 #pragma unroll 1
 	for (int band = 0; band < nb; band++) {
 	const TAP* __restrict__ db = P.nBands > 0 ? (const TAP*)P.bandData + (long long)img * P.bandImageStride + (long long)band * P.bandStride : d;
@@ -1201,6 +1240,10 @@ __device__ __forceinline__ void describeOne(const DescParams& P, const long long
 		}
 		}
 	}
+	if (ldsTables && band == 0) {
+		wTab[lane] = tw0;
+		if (lane < 33) wTab[64 + lane] = tw1;
+	}
 	waveSync();
 	DSTAMP(4);
 	const int T_w = widthSubRegion + 2 * overLap;  // samples per sub-region side (<= TWT, enforced on the host)
@@ -1216,22 +1259,40 @@ __device__ __forceinline__ void describeOne(const DescParams& P, const long long
 		const int nT = T_w * T_w;
 		const double ms = -s;
 		double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+		double wg = 1.0;   // weightGrid[sub] (stable); read on each path in its own block, or the two addresses merge into one flat load
+		if (ldsTables) {
+			// the loop below with both tables read from the wave's copy (one pointer that is LDS on one path and global on the other would make
+			// every access a flat one)
+			wg = wTab[81 + sub];
 #pragma unroll 3
-		for (int t = q; t < nT; t += 4) {
-			const int i = t / T_w, j = t - i * T_w;
-			const double vx = (double)sX[base + i * gridW + j], vy = (double)sY[base + i * gridW + j];
-			const double w = stableDesc ? T.weightSub[t] : T.weightFast[(regionR + rY + i) * regionSize + regionR + rX + j];
-			const double dx = w * vx, dy = w * vy;
-			const double pdx = c * dx + s * dy;
-			const double pdy = ms * dx + c * dy;
-			a0 += pdx; a1 += fabs(pdx); a2 += pdy; a3 += fabs(pdy);
+			for (int t = q; t < nT; t += 4) {
+				const int i = t / T_w, j = t - i * T_w;
+				const double vx = (double)sX[base + i * gridW + j], vy = (double)sY[base + i * gridW + j];
+				const double w = wTab[t];
+				const double dx = w * vx, dy = w * vy;
+				const double pdx = c * dx + s * dy;
+				const double pdy = ms * dx + c * dy;
+				a0 += pdx; a1 += fabs(pdx); a2 += pdy; a3 += fabs(pdy);
+			}
+		} else {
+#pragma unroll 3
+			for (int t = q; t < nT; t += 4) {
+				const int i = t / T_w, j = t - i * T_w;
+				const double vx = (double)sX[base + i * gridW + j], vy = (double)sY[base + i * gridW + j];
+				const double w = stableDesc ? T.weightSub[t] : T.weightFast[(regionR + rY + i) * regionSize + regionR + rX + j];
+				const double dx = w * vx, dy = w * vy;
+				const double pdx = c * dx + s * dy;
+				const double pdy = ms * dx + c * dy;
+				a0 += pdx; a1 += fabs(pdx); a2 += pdy; a3 += fabs(pdy);
+			}
 		}
 #pragma unroll
 		for (int o = 1; o <= 2; o <<= 1) {
 			a0 += laneShflXor(a0, o, lane); a1 += laneShflXor(a1, o, lane); a2 += laneShflXor(a2, o, lane); a3 += laneShflXor(a3, o, lane);
 		}
 		double sum = q == 0 ? a0 : q == 1 ? a1 : q == 2 ? a2 : a3;
-		if (stableDesc) sum = T.weightGrid[sub] * sum;
+		if (ldsTables) sum = wg * sum;
+		else if (stableDesc) sum = T.weightGrid[sub] * sum;
 		feat[band * dof + lane] = sum;
 	} else
 #pragma unroll 1
@@ -1344,12 +1405,23 @@ __global__ __launch_bounds__(256) void k_describe(DescParams P) {
 		long long g;
 		int img;
 		KeyPoint kp;
-		loadSlot(P, slot, variant, g, img, kp);
-		if (STAMP && lane == 0) P.stamps[g * 16 + 7] = waveStart;
-		describeOne<STAMP, EPLT, TWT, TAP, CFG>(P, g, img, kp, lds, lane);
+#if BHIP_DESCRIBE_KARGS
+		// A/B builds only (measured, no gain: DESIGN.md "describe: tables off the vector load path"): the default configurations read the
+		// arguments again for every key point, with scalar loads from the kernel-argument segment through an offset the compiler cannot see
+		// through, so that nothing of DescParams is held in scalar registers, or spilled to vector-register lanes, across the key-point loop.
+		// The generic kernels turn the freed scalar registers into longer live ranges (<3,5,T,0>: 111 VGPRs instead of 89) and keep the copy.
+		int kz = 0;
+		asm volatile("" : "+s"(kz));
+		const DescParams& Pk = CFG != 0 ? *(const DescParams*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + kz) : P;
+#else
+		const DescParams& Pk = P;
+#endif
+		loadSlot(Pk, slot, variant, g, img, kp);
+		if (STAMP && lane == 0) Pk.stamps[g * 16 + 7] = waveStart;
+		describeOne<STAMP, EPLT, TWT, TAP, CFG>(Pk, g, img, kp, lds, lane);
 		if (variant & DESC_VAR_ONESHOT) break;
 		if (STAMP) waveStart = __builtin_readcyclecounter();
-		if (!queueNext(P, lane, cur, tried, slot)) break;
+		if (!queueNext(Pk, lane, cur, tried, slot)) break;
 		waveSync();   // the sums and the normalisation have read this slice; the next key point's orientation overwrites it
 	}
 }
@@ -1372,7 +1444,8 @@ int bhip_describe_lds_bytes(const SurfTables& t, int nBands) {
 	const int ns = gridW * gridW;
 	// sX sY | feat; the default configurations store 4-byte samples (see k_describe)
 	const int sampBytes = bhip_describe_default_cfg(t) ? 4 : 8;
-	const int desc = 2 * ns * sampBytes + t.dof * 8 * (nBands > 0 ? nBands : 1);
+	// surfStable defaults: + the wave's copy of weightSub and weightGrid (k_describe, ldsTables)
+	const int desc = 2 * ns * sampBytes + t.dof * 8 * (nBands > 0 ? nBands : 1) + (bhip_describe_default_cfg(t) == 1 ? DESC_TBL_DOUBLES * 8 : 0);
 	int b = ori > desc ? ori : desc;
 	return (b + 15) & ~15;
 }
@@ -1449,6 +1522,7 @@ int bhip_launch_describe_ex(bhip_ctx* ctx, DevImg<const T> ii, const KeyPoint* k
 	P.stamps = nullptr;
 	P.serialOnly = bhip_env_flag("BHIP_DESCRIBE_SERIAL") ? 1 : 0;   // parity cross-checks of the two window sweeps / the two sort keys
 	P.sort64 = bhip_env_flag("BHIP_DESCRIBE_SORT64") ? 1 : 0;
+	P.tablePtr = bhip_env_flag("BHIP_DESCRIBE_TABLEPTR") ? (DESC_TBL_SUMS | DESC_TBL_ORI) : 0;   // cross-check of the table copies: the pointer path
 #ifdef BHIP_EXPERIMENTS
 	{ const char* e = getenv("BHIP_DESCRIBE_STOP"); P.stopAfter = e ? atoi(e) : -1; }
 	{ const char* e = getenv("BHIP_DESCRIBE_WSTOP"); P.windowStop = e ? atoi(e) : -1; }
@@ -1461,6 +1535,9 @@ int bhip_launch_describe_ex(bhip_ctx* ctx, DevImg<const T> ii, const KeyPoint* k
 		// the two-launch experiments share one set of counters: they run the launch before the queue
 		const char* sp = getenv("BHIP_DESCRIBE_SPLIT");
 		if (sp && (sp[0] == '1' || sp[0] == '2')) P.variant |= DESC_VAR_ONESHOT;
+		// s / o anywhere in the value: one table item back on its pointer path (A/B of the items inside one build)
+		if (e && strchr(e, 's')) P.tablePtr |= DESC_TBL_SUMS;
+		if (e && strchr(e, 'o')) P.tablePtr |= DESC_TBL_ORI;
 	}
 #endif
 	if (t.oriWidth * t.oriWidth > 64 * ORI_EPL_MAX) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "orientation sample grid too large for the GPU path");
