@@ -72,7 +72,7 @@ static int briefImpl(bhip_ctx* ctx, DevImg<const T> img, int radius, int numPoin
 	return bhip_launch_brief(ctx, img, radius, numPoints, dSample, dCompare, xy, n, out, dStart, maxCount, 2, 0, briefPatchOk(samplePoints, nSample, radius));
 }
 
-static bool gradBorderOk(int kind, int border) { return border == 0 || border == 1 || (border == 2 && kind == 0); }   // 2 = BorderType.EXTENDED: GradientSobel only
+static bool gradBorderOk(int kind, int border) { return border == 0 || border == 1 || (border == 2 && kind != 1); }   // 2 = BorderType.EXTENDED: GradientSobel and GradientPrewitt
 
 // host forms: GrayF32 gradients re-pitch rows to pitch4 (the streaming kernels), GrayU8 ones stay dense; without a border policy the frame
 // keeps the caller's values, so dx and dy are staged too
@@ -384,6 +384,15 @@ int bhip_three_u8_s16(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStrid
 	return gradHost<uint8_t, int16_t>(ctx, 1, {in, inStart, inStride, width, height}, {dx, outStart, outStride, width, height}, {dy, outStart, outStride, width, height}, border);
 }
 
+int bhip_prewitt_f32(bhip_ctx* ctx, const float* in, int inStart, int inStride, int width, int height, float* dx, float* dy, int outStart, int outStride,
+					 int border) {
+	return gradHost<float, float>(ctx, 2, {in, inStart, inStride, width, height}, {dx, outStart, outStride, width, height}, {dy, outStart, outStride, width, height}, border);
+}
+int bhip_prewitt_u8_s16(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, int16_t* dx, int16_t* dy, int outStart,
+						int outStride, int border) {
+	return gradHost<uint8_t, int16_t>(ctx, 2, {in, inStart, inStride, width, height}, {dx, outStart, outStride, width, height}, {dy, outStart, outStride, width, height}, border);
+}
+
 int bhip_corner_intensity_f32(bhip_ctx* ctx, int kind, int radius, float kappa, const float* derivX, const float* derivY, int dStart, int dStride, int width,
 							  int height, float* intensity, int iStart, int iStride) {
 	return cornerHost<float>(ctx, false, kind, radius, kappa, {derivX, dStart, dStride, width, height}, {derivY, dStart, dStride, width, height},
@@ -480,6 +489,17 @@ int bhip_sobel_dev_u8_s16(bhip_ctx* ctx, const uint8_t* dev_in, long long inImag
 int bhip_three_dev_u8_s16(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dev_dx,
 						  int16_t* dev_dy, long long outImageStride, int outStride, int border) {
 	return gradDev<uint8_t, int16_t>(ctx, 1, {dev_in, inImageStride, inStride, width, height, batch}, {dev_dx, outImageStride, outStride, width, height, batch},
+									 {dev_dy, outImageStride, outStride, width, height, batch}, border);
+}
+
+int bhip_prewitt_dev_f32(bhip_ctx* ctx, const float* dev_in, long long inImageStride, int inStride, int width, int height, int batch, float* dev_dx, float* dev_dy,
+						 long long outImageStride, int outStride, int border) {
+	return gradDev<float, float>(ctx, 2, {dev_in, inImageStride, inStride, width, height, batch}, {dev_dx, outImageStride, outStride, width, height, batch},
+								 {dev_dy, outImageStride, outStride, width, height, batch}, border);
+}
+int bhip_prewitt_dev_u8_s16(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dev_dx,
+							int16_t* dev_dy, long long outImageStride, int outStride, int border) {
+	return gradDev<uint8_t, int16_t>(ctx, 2, {dev_in, inImageStride, inStride, width, height, batch}, {dev_dx, outImageStride, outStride, width, height, batch},
 									 {dev_dy, outImageStride, outStride, width, height, batch}, border);
 }
 

@@ -349,7 +349,7 @@ int bhip_launch_conv_down(bhip_ctx* ctx, bool vertical, const int32_t* kernel, i
 int bhip_launch_copy_images(bhip_ctx* ctx, DevImg<const float> in, DevImg<float> out);
 int bhip_launch_copy_images(bhip_ctx* ctx, DevImg<const uint8_t> in, DevImg<uint8_t> out);
 int bhip_launch_planar_average(bhip_ctx* ctx, const float* bands, long long bandStride, int numBands, long long n, float* out);
-// GradientSobel / GradientThree (kind 0 / 1): GrayF32 -> GrayF32, GrayU8 -> GrayS16
+// GradientSobel / GradientThree / GradientPrewitt (kind 0 / 1 / 2): GrayF32 -> GrayF32, GrayU8 -> GrayS16
 int bhip_launch_gradient(bhip_ctx* ctx, int kind, DevImg<const float> in, DevImg<float> dx, DevImg<float> dy, int border);
 int bhip_launch_gradient(bhip_ctx* ctx, int kind, DevImg<const uint8_t> in, DevImg<int16_t> dx, DevImg<int16_t> dy, int border);
 int bhip_launch_grad_intensity(bhip_ctx* ctx, int kind, DevImg<const float> dx, DevImg<const float> dy, DevImg<float> out);
@@ -626,3 +626,29 @@ int bhip_launch_label_to_binary(bhip_ctx* ctx, DevImg<const int32_t> in, DevImg<
 size_t bhip_label_scratch(int width, int height, int images);
 // width * height must fit an int and the image at most 65535 tiles of 32 rows high; scratch: bhip_label_scratch(width, height, in.batch) bytes
 int bhip_launch_label_blobs(bhip_ctx* ctx, bool eight, DevImg<const uint8_t> in, DevImg<int32_t> out, int* devNumBlobs, void* scratch);
+
+// ---------------- line detection: edge features (edge.hip), Hough transforms, relaxed block NMS, mean-shift peaks (hough.hip) ----------------
+int bhip_launch_grad_intensity_abs_s16(bhip_ctx* ctx, DevImg<const int16_t> dx, DevImg<const int16_t> dy, DevImg<float> out);
+// GradientToEdgeFeatures.nonMaxSuppressionCrude4 on float or int16_t derivatives; intensity and out must not overlap
+template <class T>
+int bhip_launch_edge_nonmax_crude4(bhip_ctx* ctx, DevImg<const float> intensity, DevImg<const T> dx, DevImg<const T> dy, DevImg<float> out);
+// HoughTransformBinary.computeParameters with HoughParametersPolar: devCos / devSin are numBinsAngle floats, counts batch * numBinsAngle *
+// numBinsRange ints of scratch, transform numBinsRange wide and numBinsAngle high.  width * height <= 2^24, batch and numBinsAngle <= 65535
+int bhip_launch_hough_binary_polar(bhip_ctx* ctx, DevImg<const uint8_t> bin, const float* devCos, const float* devSin, int numBinsAngle, int numBinsRange, float rMax,
+								   DevImg<float> transform, int* counts);
+// HoughTransformGradient.transform with HoughParametersFootOfNorm (T: float or int16_t derivatives) on the images of the views: at most
+// 65535, and images * width * height < 2^32 - 1.  The first `cap` edge pixels of an image (raster order) vote; devN[b] is their number, which
+// may exceed cap.  scratch: bhip_hough_gradient_scratch(width, height, images, cap) bytes (0: the size could not be determined)
+size_t bhip_hough_gradient_scratch(int width, int height, int images, int cap);
+template <class T>
+int bhip_launch_hough_gradient_foot(bhip_ctx* ctx, DevImg<const T> dx, DevImg<const T> dy, DevImg<const uint8_t> bin, DevImg<float> transform, int cap, int* devN,
+									void* scratch);
+// NonMaxBlock with NonMaxBlockSearchRelaxed.Max: one bit per pixel in block-raster order (zeroed bitmap of `words` words per image, more
+// than nbx * nby * (radius+1)^2 bits); bhip_launch_word_prefix ranks them, bhip_launch_relaxed_to_xy writes the list
+int bhip_launch_nonmax_relaxed(bhip_ctx* ctx, DevImg<const float> img, int radius, float threshold, int border, unsigned int* bitmap, int words, int nbx);
+int bhip_launch_relaxed_to_xy(bhip_ctx* ctx, const unsigned int* bitmap, const unsigned int* wordPrefix, int words, int nbx, int batch, int radius, int border,
+							  int16_t* xy, int cap);
+// MeanShiftPeak.search from the first min(n[b], cap) integer peaks of every image (n == nullptr: cap of them); weights: device table of
+// (2*radius+1)^2 floats, unused when radius <= 0 (no refinement).  peak [batch][cap][2], intensity [batch][cap]: the image at the integer peak
+int bhip_launch_mean_shift_peak(bhip_ctx* ctx, DevImg<const float> img, const int16_t* xy, const int* n, int cap, int radius, int maxIterations, float convergenceTol,
+								const float* weights, float* peak, float* intensity);

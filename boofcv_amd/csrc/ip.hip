@@ -1230,7 +1230,30 @@ __device__ __forceinline__ float at0(const GradParams& P, const float* img, int 
 //                    (total = 0; total += get(x+j,y+i)*k in row-major kernel order)
 //   three-tap        GradientThree_Standard.process inside; with a border the first/last column (row) of derivX (derivY) takes the generic
 //                    form, rows {0,1,H-2,H-1} (columns for derivY) the unrolled 3-tap form
+//   Prewitt (KIND 2) GradientPrewitt_Shared.process(GrayF32, ...) (I:alg/filter/derivative/impl/GradientPrewitt_Shared.java:104-137) inside; frame
+//                    with a border = the same generic border convolution with GradientPrewitt.kernelDerivX/Y_F32 (GradientPrewitt.java:45-48,128-142)
 // Returns false when the pixel is left untouched (frame pixel, no border policy).
+// The generic border convolution of a frame pixel (ConvolveJustBorder_General_SB.convolve(Kernel2D_F32, ...)): total = 0, then
+// total += get(x+j, y+i) * k in row-major kernel order, for both kernels
+__device__ __forceinline__ void gradFrame3x3(const float a[3][3], int x, int y, int W, int H, int border, const float kx[9], const float ky[9], float& dx, float& dy) {
+	float tx = 0, ty = 0;
+	// border 2 = BorderType.EXTENDED (BorderIndex1D_Extend): an index outside the image is clamped, and the clamped pixel of a frame
+	// pixel's neighbourhood is always one of the nine values at hand
+	const int r0 = (border == 2 && y == 0) ? 1 : 0, r2 = (border == 2 && y == H - 1) ? 1 : 2;
+	const int c0 = (border == 2 && x == 0) ? 1 : 0, c2 = (border == 2 && x == W - 1) ? 1 : 2;
+#pragma unroll
+	for (int i = 0; i < 3; i++)
+#pragma unroll
+		for (int j = 0; j < 3; j++) {
+			const int ii = i == 0 ? r0 : i == 2 ? r2 : 1, jj = j == 0 ? c0 : j == 2 ? c2 : 1;
+			const float v = (ii == 0 ? (jj == 0 ? a[0][0] : jj == 1 ? a[0][1] : a[0][2])
+							 : ii == 1 ? (jj == 0 ? a[1][0] : jj == 1 ? a[1][1] : a[1][2])
+									   : (jj == 0 ? a[2][0] : jj == 1 ? a[2][1] : a[2][2]));
+			tx += v * kx[i * 3 + j];
+			ty += v * ky[i * 3 + j];
+		}
+	dx = tx; dy = ty;
+}
 template <int KIND>
 __device__ __forceinline__ bool gradOne(const float a[3][3], int x, int y, int W, int H, int border, float& dx, float& dy) {
 	const bool interior = x >= 1 && x < W - 1 && y >= 1 && y < H - 1;
@@ -1245,23 +1268,21 @@ __device__ __forceinline__ bool gradOne(const float a[3][3], int x, int y, int W
 		if (!border) return false;
 		const float kx[9] = {-0.25f, 0, 0.25f, -0.5f, 0, 0.5f, -0.25f, 0, 0.25f};
 		const float ky[9] = {-0.25f, -0.5f, -0.25f, 0, 0, 0, 0.25f, 0.5f, 0.25f};
-		float tx = 0, ty = 0;
-		// border 2 = BorderType.EXTENDED (BorderIndex1D_Extend): an index outside the image is clamped, and the clamped pixel of a frame
-		// pixel's neighbourhood is always one of the nine values at hand
-		const int r0 = (border == 2 && y == 0) ? 1 : 0, r2 = (border == 2 && y == H - 1) ? 1 : 2;
-		const int c0 = (border == 2 && x == 0) ? 1 : 0, c2 = (border == 2 && x == W - 1) ? 1 : 2;
-#pragma unroll
-		for (int i = 0; i < 3; i++)
-#pragma unroll
-			for (int j = 0; j < 3; j++) {
-				const int ii = i == 0 ? r0 : i == 2 ? r2 : 1, jj = j == 0 ? c0 : j == 2 ? c2 : 1;
-				const float v = (ii == 0 ? (jj == 0 ? a[0][0] : jj == 1 ? a[0][1] : a[0][2])
-								 : ii == 1 ? (jj == 0 ? a[1][0] : jj == 1 ? a[1][1] : a[1][2])
-										   : (jj == 0 ? a[2][0] : jj == 1 ? a[2][1] : a[2][2]));
-				tx += v * kx[i * 3 + j];
-				ty += v * ky[i * 3 + j];
-			}
-		dx = tx; dy = ty;
+		gradFrame3x3(a, x, y, W, H, border, kx, ky, dx, dy);
+		return true;
+	}
+	if (KIND == 2) {
+		if (interior) {
+			const float w = a[2][2] - a[0][0];
+			const float v = a[2][0] - a[0][2];
+			dy = a[2][1] + w + v - a[0][1];
+			dx = a[1][2] + w - v - a[1][0];
+			return true;
+		}
+		if (!border) return false;
+		const float kx[9] = {-1.0f, 0, 1.0f, -1.0f, 0, 1.0f, -1.0f, 0, 1.0f};
+		const float ky[9] = {-1.0f, -1.0f, -1.0f, 0, 0, 0, 1.0f, 1.0f, 1.0f};
+		gradFrame3x3(a, x, y, W, H, border, kx, ky, dx, dy);
 		return true;
 	}
 	if (!border) {
@@ -1378,15 +1399,17 @@ int bhip_launch_gradient(bhip_ctx* ctx, int kind, DevImg<const float> in, DevImg
 	if (width <= 0 || height <= 0 || batch <= 0) return BHIP_OK;
 	if (!sameLayout(dx, dy)) return bhip_fail(ctx, BHIP_ERR_INVALID, "dx and dy must share one layout");
 	GradParams P{in.data, dx.data, dy.data, in.imageStride, dx.imageStride, in.stride, dx.stride, width, height, border};
-	ProfScope prof(ctx, kind == 0 ? "k_sobel" : "k_three", 12.0 * width * height * batch);
+	ProfScope prof(ctx, kind == 0 ? "k_sobel" : kind == 2 ? "k_prewitt" : "k_three", 12.0 * width * height * batch);
 	const bool stream = vec4(in) && vec4(dx) && aligned16(dy.data);
 	if (stream) {
 		dim3 grid((width + 255) / 256, (height + 4 * GR_ROWS - 1) / (4 * GR_ROWS), batch);
 		if (kind == 0) hipLaunchKernelGGL(k_grad_stream<0>, grid, dim3(256), 0, ctx->stream, P);
+		else if (kind == 2) hipLaunchKernelGGL(k_grad_stream<2>, grid, dim3(256), 0, ctx->stream, P);
 		else hipLaunchKernelGGL(k_grad_stream<1>, grid, dim3(256), 0, ctx->stream, P);
 	} else {
 		dim3 grid((width + 255) / 256, height, batch);
 		if (kind == 0) hipLaunchKernelGGL(k_grad<0>, grid, dim3(256), 0, ctx->stream, P);
+		else if (kind == 2) hipLaunchKernelGGL(k_grad<2>, grid, dim3(256), 0, ctx->stream, P);
 		else hipLaunchKernelGGL(k_grad<1>, grid, dim3(256), 0, ctx->stream, P);
 	}
 	BHIP_HIP(ctx, hipGetLastError());
@@ -2068,6 +2091,12 @@ __global__ __launch_bounds__(256) void k_grad_u8(GradU8Params P) {
 					const int v = a22 - a00, w = a20 - a02;
 					dy[j] = (int16_t)((a21 - a01) * 2 + v + w);
 					dx[j] = (int16_t)((a12 - a10) * 2 + v - w);
+				} else if (KIND == 2) {
+					// GradientPrewitt_Shared.process(GrayU8, ...) (impl/GradientPrewitt_Shared.java:34-67); on the frame the int sums of the generic
+					// border convolution with GradientPrewitt.kernelDerivX/Y_I32 are the same expression over the padded pixels
+					const int w = a22 - a00, v = a20 - a02;
+					dy[j] = (int16_t)(a21 + w + v - a01);
+					dx[j] = (int16_t)(a12 + w - v - a10);
 				} else {
 					dx[j] = (int16_t)(a12 - a10);
 					dy[j] = (int16_t)(a21 - a01);
@@ -2098,9 +2127,10 @@ int bhip_launch_gradient(bhip_ctx* ctx, int kind, DevImg<const uint8_t> in, DevI
 	if (width <= 0 || height <= 0 || batch <= 0) return BHIP_OK;
 	if (!sameLayout(dx, dy)) return bhip_fail(ctx, BHIP_ERR_INVALID, "dx and dy must share one layout");
 	GradU8Params P{in.data, dx.data, dy.data, in.imageStride, dx.imageStride, in.stride, dx.stride, width, height, border};
-	ProfScope prof(ctx, kind == 0 ? "k_sobel_u8" : "k_three_u8", 5.0 * width * height * batch);
+	ProfScope prof(ctx, kind == 0 ? "k_sobel_u8" : kind == 2 ? "k_prewitt_u8" : "k_three_u8", 5.0 * width * height * batch);
 	dim3 grid((width + 255) / 256, (height + 4 * GR_ROWS - 1) / (4 * GR_ROWS), batch);
 	if (kind == 0) hipLaunchKernelGGL(k_grad_u8<0>, grid, dim3(256), 0, ctx->stream, P);
+	else if (kind == 2) hipLaunchKernelGGL(k_grad_u8<2>, grid, dim3(256), 0, ctx->stream, P);
 	else hipLaunchKernelGGL(k_grad_u8<1>, grid, dim3(256), 0, ctx->stream, P);
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;

@@ -23,7 +23,13 @@ Names follow the reference classes the host-buffer forms in boofcv_amd/api/ mirr
   DeviceImageOps.binaryLogic / binaryInvert / erode / dilate / edge / removePointNoise   BinaryImageOps (GrayU8 0/1)   I:alg/filter/binary/BinaryImageOps.java:69-411
   DeviceImageOps.labelBlobs     the labelled image and blob count of BinaryImageOps.contour     I:alg/filter/binary/LinearContourLabelChang2004.java:96-152
   DeviceImageOps.relabel / labelToBinary   BinaryImageOps.relabel / labelToBinary                I:alg/filter/binary/BinaryImageOps.java:509-557
-  DeviceImageOps.brief          DescribePointBrief.process                         F:alg/feature/describe/DescribePointBrief.java:73-89
+  DeviceImageOps.prewitt        GradientPrewitt.process                             I:alg/filter/derivative/GradientPrewitt.java:80-142
+  DeviceImageOps.edgeNonMaxCrude4   GradientToEdgeFeatures.nonMaxSuppressionCrude4  F:alg/feature/detect/edge/impl/ImplEdgeNonMaxSuppressionCrude.java:50-242
+  DeviceImageOps.houghBinaryPolar   HoughTransformBinary.computeParameters (polar)  F:alg/feature/detect/line/HoughTransformBinary.java:124-135
+  DeviceImageOps.houghGradientFoot  HoughTransformGradient.transform (foot of norm) F:alg/feature/detect/line/HoughTransformGradient.java:184-252
+  DeviceImageOps.nonmaxRelaxed  NonMaxBlock.process (NonMaxBlockSearchRelaxed.Max)  F:alg/feature/detect/extract/NonMaxBlockSearchRelaxed.java:69-98,227-251
+  DeviceImageOps.meanShiftPeak  MeanShiftPeak.search                                F:alg/feature/detect/peak/MeanShiftPeak.java:103-160
+  DeviceImageOps.brief          DescribePointBrief.process                        F:alg/feature/describe/DescribePointBrief.java:73-89
   DeviceKltTracker              PointTrackerKltPyramid, batched over sequences      main/boofcv-geo/.../abst/feature/tracker/PointTrackerKltPyramid.java:139-348
   DeviceBackgroundModel         BackgroundStationaryBasic / Gaussian / Gmm, batched over streams   F:alg/background/stationary/*.java
 """
@@ -247,15 +253,145 @@ class DeviceImageOps:
     def three(self, src, border=0, dx=None, dy=None):
         return self._grad((self.L.bhip_three_dev_f32, self.L.bhip_three_dev_u8_s16), src, border, dx, dy)
 
+    def prewitt(self, src, border="EXTENDED", dx=None, dy=None):
+        """GradientPrewitt.process: float32 -> float32 or uint8 -> int16; border as _grad describes (FactoryDerivative.prewitt's default is
+        EXTENDED)"""
+        return self._grad((self.L.bhip_prewitt_dev_f32, self.L.bhip_prewitt_dev_u8_s16), src, border, dx, dy)
+
     def intensity(self, kind, dx, dy, out=None):
+        """float32 derivatives: intensityE / intensityAbs / the squared magnitude (INTENSITY_*); int16 derivatives: intensityAbs only"""
+        s16 = dx.dtype == torch.int16
         out = self._like(dx) if out is None else out
-        xp, dis, drs, W, H, B = _geom(dx)
-        yp, dis2, drs2, _, _, _ = _geom(dy)
+        xp, dis, drs, W, H, B = _geom(dx, dx.dtype if s16 else torch.float32)
+        yp, dis2, drs2, W2, H2, B2 = _geom(dy, dx.dtype if s16 else torch.float32)
         if (dis, drs) != (dis2, drs2):
             raise IllegalArgumentException("derivX and derivY must share their layout")
-        op, ois, ors, _, _, _ = _geom(out)
-        _check(self.ctx, self.L.bhip_gradient_intensity_dev_f32(self.ctx._h, int(kind), xp, yp, dis, drs, W, H, B, op, ois, ors))
+        op, ois, ors, W3, H3, B3 = _geom(out)
+        if (W, H, B) != (W2, H2, B2) or (W, H, B) != (W3, H3, B3):
+            raise IllegalArgumentException("Image shapes do not match")
+        if s16:
+            if int(kind) != INTENSITY_ABS:
+                raise IllegalArgumentException("only intensityAbs is implemented for GrayS16 derivatives on the GPU")
+            _check(self.ctx, self.L.bhip_gradient_intensity_abs_dev_s16(self.ctx._h, xp, yp, dis, drs, W, H, B, op, ois, ors))
+        else:
+            _check(self.ctx, self.L.bhip_gradient_intensity_dev_f32(self.ctx._h, int(kind), xp, yp, dis, drs, W, H, B, op, ois, ors))
         return out
+
+    def _derivs(self, dx, dy):
+        """(ptrX, ptrY, imageStride, rowStride, W, H, B, int16?) of a derivative pair (float32 or int16) that shares one layout"""
+        if dx.dtype not in (torch.float32, torch.int16) or dy.dtype != dx.dtype:
+            raise IllegalArgumentException("derivatives are float32 (GrayF32) or int16 (GrayS16) and of one type; GrayS32 is not implemented on the GPU")
+        xp, dis, drs, W, H, B = _geom(dx, dx.dtype)
+        yp, dis2, drs2, W2, H2, B2 = _geom(dy, dx.dtype)
+        if (dis, drs) != (dis2, drs2):
+            raise IllegalArgumentException("derivX and derivY must share their layout")
+        if (W, H, B) != (W2, H2, B2):
+            raise IllegalArgumentException("Image shapes do not match")
+        return xp, yp, dis, drs, W, H, B, dx.dtype == torch.int16
+
+    def edgeNonMaxCrude4(self, intensity, dx, dy, out=None):
+        """GradientToEdgeFeatures.nonMaxSuppressionCrude4(intensity, derivX, derivY, output) on float32 or int16 derivatives -> float32 [B,H,W];
+        intensity and out must not overlap"""
+        xp, yp, dis, drs, W, H, B, s16 = self._derivs(dx, dy)
+        ip, iis, irs, W2, H2, B2 = _geom(intensity)
+        out = self._like(intensity) if out is None else out
+        op, ois, ors, W3, H3, B3 = _geom(out)
+        if (W, H, B) != (W2, H2, B2) or (W, H, B) != (W3, H3, B3):
+            raise IllegalArgumentException("Image shapes do not match")
+        fn = self.L.bhip_edge_nonmax_crude4_dev_s16 if s16 else self.L.bhip_edge_nonmax_crude4_dev_f32
+        _check(self.ctx, fn(self.ctx._h, ip, iis, irs, xp, yp, dis, drs, W, H, B, op, ois, ors))
+        return out
+
+    def houghPolarBins(self, width, height, rangeResolution):
+        """HoughParametersPolar.initialize -> (numBinsRange, r_max)"""
+        n, r = C.c_int(), C.c_float()
+        if self.L.bhip_hough_polar_bins(int(width), int(height), float(rangeResolution), C.byref(n), C.byref(r)) != 0:
+            raise IllegalArgumentException("bad image size")
+        return n.value, r.value
+
+    def houghBinaryPolar(self, binary, rangeResolution=2.0, numBinsAngle=180, cosTable=None, sinTable=None, out=None):
+        """HoughTransformBinary.computeParameters with HoughParametersPolar(rangeResolution, numBinsAngle) on uint8 frames [B,H,W] -> the
+        transform float32 [B, numBinsAngle, numBinsRange] (`out`, any row / image stride, is written as a whole).  cosTable / sinTable: the
+        numBinsAngle float32 values of the trigonometric table (default: lines.CachedSineCosine_F32(0, (float)Math.PI, numBinsAngle))."""
+        bp, bis, brs, W, H, B = _geom(binary, torch.uint8)
+        if cosTable is None or sinTable is None:
+            from . import lines
+            table = lines.CachedSineCosine_F32(0.0, np.float32(np.pi), int(numBinsAngle))
+            cosTable, sinTable = table.c, table.s
+        c, s = np.ascontiguousarray(cosTable, np.float32), np.ascontiguousarray(sinTable, np.float32)
+        if len(c) != numBinsAngle or len(s) != numBinsAngle:
+            raise IllegalArgumentException("the tables have numBinsAngle entries")
+        R, _ = self.houghPolarBins(W, H, rangeResolution)
+        if out is None:
+            if R <= 0 or numBinsAngle <= 0:
+                raise IllegalArgumentException("the transform has no bins")
+            if R * numBinsAngle > 1 << 28:
+                raise RuntimeError("transform too large for the GPU path")
+            out = torch.empty((B, int(numBinsAngle), R), dtype=torch.float32, device=binary.device)
+        tp, tis, trs, TW, TH, TB = _geom(out)
+        if TB != B:
+            raise IllegalArgumentException("one transform per image")
+        _check(self.ctx, self.L.bhip_hough_binary_polar_dev_u8(self.ctx._h, bp, bis, brs, W, H, B, float(rangeResolution), int(numBinsAngle),
+                                                             c.ctypes.data_as(_lib._fp), s.ctypes.data_as(_lib._fp), tp, tis, trs, TW, TH))
+        return out
+
+    def houghGradientFoot(self, dx, dy, binary, out=None, cap=None, counts=None):
+        """HoughTransformGradient.transform(derivX, derivY, binary) with HoughParametersFootOfNorm up to the transform image, on float32 or int16
+        derivatives and uint8 frames [B,H,W] -> (transform float32 [B,H,W], edge pixel counts int32 [B]).  cap: the edge pixels per image that
+        vote (default: all; a smaller cap bounds the scratch -- compare counts with it)."""
+        xp, yp, dis, drs, W, H, B, s16 = self._derivs(dx, dy)
+        bp, bis, brs, W2, H2, B2 = _geom(binary, torch.uint8)
+        if out is None:
+            out = torch.empty((B, H, W), dtype=torch.float32, device=binary.device)
+        tp, tis, trs, W3, H3, B3 = _geom(out)
+        if (W, H, B) != (W2, H2, B2) or (W, H, B) != (W3, H3, B3):
+            raise IllegalArgumentException("Image shapes do not match")
+        if counts is None:
+            counts = torch.empty((B,), dtype=torch.int32, device=binary.device)
+        if counts.dtype != torch.int32 or counts.shape != (B,) or not counts.is_contiguous() or not counts.is_cuda:
+            raise IllegalArgumentException("counts must be a contiguous int32 CUDA tensor [B]")
+        fn = self.L.bhip_hough_gradient_foot_dev_s16 if s16 else self.L.bhip_hough_gradient_foot_dev_f32
+        _check(self.ctx, fn(self.ctx._h, xp, yp, dis, drs, bp, bis, brs, W, H, B, tp, tis, trs, W * H if cap is None else int(cap), C.c_void_p(counts.data_ptr())))
+        return out, counts
+
+    def nonmaxRelaxed(self, intensity, radius, threshold, border=0, cap=None):
+        """NonMaxBlock.process with NonMaxBlockSearchRelaxed.Max -> (xy int16 [B, cap, 2], counts int32 [B]) on the device, in block-raster order
+        and raster order within a block; a count may exceed cap (default: every pixel inside the border)"""
+        ip, iis, irs, W, H, B = _geom(intensity)
+        if cap is None:
+            cap = max(1, max(W - 2 * border, 0) * max(H - 2 * border, 0))
+        xy = torch.empty((B, max(cap, 1), 2), dtype=torch.int16, device=intensity.device)
+        n = torch.empty((B,), dtype=torch.int32, device=intensity.device)
+        _check(self.ctx, self.L.bhip_nonmax_block_relaxed_dev_f32(self.ctx._h, ip, iis, irs, W, H, B, int(radius), float(threshold), int(border),
+                                                                C.c_void_p(xy.data_ptr()), int(cap), C.c_void_p(n.data_ptr())))
+        return xy[:, :cap], n
+
+    def meanShiftPeak(self, image, xy, counts=None, radius=3, weights=None, maxIterations=10, convergenceTol=0.001):
+        """MeanShiftPeak.search from the integer peaks xy int16 [B, cap, 2] (the first min(counts[b], cap) of image b; counts None: all) on float32
+        images [B,H,W] -> (peaks float32 [B, cap, 2], intensity float32 [B, cap]: the image at the integer peak).  weights: the (2*radius+1)^2
+        kernel of a WeightPixel_F32 (default: lines.weightPixelGaussian(radius)); radius <= 0: no refinement.  Rows past counts[b] are not written."""
+        ip, iis, irs, W, H, B = _geom(image)
+        if xy.dtype != torch.int16 or xy.dim() != 3 or xy.shape[0] != B or xy.shape[2] != 2 or not xy.is_contiguous() or not xy.is_cuda:
+            raise IllegalArgumentException("xy must be a contiguous int16 CUDA tensor [B, cap, 2]")
+        cap = xy.shape[1]
+        if counts is not None and (counts.dtype != torch.int32 or counts.shape != (B,) or not counts.is_contiguous() or not counts.is_cuda):
+            raise IllegalArgumentException("counts must be a contiguous int32 CUDA tensor [B]")
+        wp = None
+        if radius > 0:
+            if weights is None:
+                from . import lines
+                weights = lines.weightPixelGaussian(int(radius))
+            w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+            if w.size != (2 * radius + 1) ** 2:
+                raise IllegalArgumentException("the weight table has (2*radius+1)^2 entries")
+            wp = w.ctypes.data_as(_lib._fp)
+        peak = torch.empty((B, cap, 2), dtype=torch.float32, device=image.device)
+        inten = torch.empty((B, cap), dtype=torch.float32, device=image.device)
+        _check(self.ctx, self.L.bhip_mean_shift_peak_dev_f32(self.ctx._h, ip, iis, irs, W, H, B, C.c_void_p(xy.data_ptr()),
+                                                           C.c_void_p(counts.data_ptr()) if counts is not None else None, cap, int(radius),
+                                                           int(maxIterations), float(convergenceTol), wp, C.c_void_p(peak.data_ptr()),
+                                                           C.c_void_p(inten.data_ptr())))
+        return peak, inten
 
     def nonmax(self, intensity, radius, threshold, border, cap=None):
         """-> (xy int16 [B, cap, 2], counts int32 [B]) on the device; lists are in the reference's block-raster order"""

@@ -1236,6 +1236,90 @@ int bhip_label_to_binary_dev_s32_u8(bhip_ctx* ctx, const int32_t* dev_in, long l
 int bhip_label_to_binary_s32_u8(bhip_ctx* ctx, const int32_t* in, int inStart, int inStride, int width, int height, uint8_t* out, int outStart, int outStride,
 								const uint8_t* selected, int numSelected);
 
+/* ---- line detection: the stages of FactoryDetectLine.houghLinePolar(ConfigHoughBinary, ...) and houghLineFoot(ConfigHoughGradient, ...)
+ *      (F:factory/feature/detect/line/FactoryDetectLine.java:90-163; hough.hip, edge.hip, the Prewitt form of the gradient kernels in ip.hip).
+ *      The parity target is the single-threaded classes.  There is no BOverride hook for them: integration/java/boofcv/hip/HoughLinesHip.java is
+ *      a provider class.  The _dev forms take batch images at dev_x + b*xImageStride (strides in elements), write the whole view of every output
+ *      image and nothing outside it, are asynchronous on the context's stream without host synchronisation, and keep their scratch in the
+ *      context.  Every argument check comes before anything is queued: a refused call writes nothing.  BHIP_ERR_UNSUPPORTED: more than 65535
+ *      images in a batch or rows in an image.  Not provided: houghLinePolar(ConfigHoughGradient, ...), houghLineFootSub, lineRansac, GrayS32
+ *      derivatives, Planar / interleaved images; the candidates list of HoughTransformGradient (the block extractor ignores it). */
+/* GradientPrewitt.process (I:alg/filter/derivative/GradientPrewitt.java:80-142): GradientPrewitt_Shared.process inside
+ * (impl/GradientPrewitt_Shared.java:34-67 GrayU8 -> GrayS16, :104-137 GrayF32), ConvolveJustBorder_General_SB.convolve with
+ * kernelDerivX/Y on the frame.  border: 0 = null (frame untouched), 1 = ImageBorderValue(0), 2 = BorderType.EXTENDED (the default of
+ * FactoryDerivative.prewitt).  dx and dy share their start and strides. */
+int bhip_prewitt_f32(bhip_ctx* ctx, const float* in, int inStart, int inStride, int width, int height, float* dx, float* dy, int outStart, int outStride,
+					 int border);
+int bhip_prewitt_u8_s16(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, int16_t* dx, int16_t* dy, int outStart,
+						int outStride, int border);
+int bhip_prewitt_dev_f32(bhip_ctx* ctx, const float* dev_in, long long inImageStride, int inStride, int width, int height, int batch, float* dev_dx, float* dev_dy,
+						 long long outImageStride, int outStride, int border);
+int bhip_prewitt_dev_u8_s16(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, int16_t* dev_dx,
+							int16_t* dev_dy, long long outImageStride, int outStride, int border);
+/* GradientToEdgeFeatures.intensityAbs(GrayS16, GrayS16, GrayF32) (F:alg/feature/detect/edge/impl/ImplGradientToEdgeFeatures.java:151-169):
+ * |dx| + |dy| in int, stored as float (the GrayF32 form is bhip_gradient_intensity_dev_f32 with kind 1) */
+int bhip_gradient_intensity_abs_dev_s16(bhip_ctx* ctx, const int16_t* dev_dx, const int16_t* dev_dy, long long dImageStride, int dStride, int width, int height,
+										int batch, float* dev_out, long long outImageStride, int outStride);
+/* GradientToEdgeFeatures.nonMaxSuppressionCrude4 (F:alg/feature/detect/edge/GradientToEdgeFeatures.java:143-157, 248-262 ->
+ * impl/ImplEdgeNonMaxSuppressionCrude.java inner4 :50-115, border4 :155-242): the step is (+1 where the derivative is > 0, else -1) in x and
+ * y; out = 0 where the intensity one step back or one step forward is greater, else the intensity; outside the image the intensity is 0.
+ * BHIP_ERR_INVALID when intensity and out overlap. */
+int bhip_edge_nonmax_crude4_dev_f32(bhip_ctx* ctx, const float* dev_intensity, long long iImageStride, int iStride, const float* dev_dx, const float* dev_dy,
+									long long dImageStride, int dStride, int width, int height, int batch, float* dev_out, long long outImageStride, int outStride);
+int bhip_edge_nonmax_crude4_dev_s16(bhip_ctx* ctx, const float* dev_intensity, long long iImageStride, int iStride, const int16_t* dev_dx, const int16_t* dev_dy,
+									long long dImageStride, int dStride, int width, int height, int batch, float* dev_out, long long outImageStride, int outStride);
+/* HoughParametersPolar.initialize (F:alg/feature/detect/line/HoughParametersPolar.java:54-60): *rMax = (float)Math.sqrt(originX^2 + originY^2)
+ * with Java's int products, *numBinsRange = (int)Math.ceil(rMax / rangeResolution).  The transform is numBinsRange wide, numBinsAngle high.
+ * Either output may be NULL.  BHIP_ERR_INVALID: width or height <= 0. */
+int bhip_hough_polar_bins(int width, int height, double rangeResolution, int* numBinsRange, float* rMax);
+/* HoughTransformBinary.computeParameters (F:alg/feature/detect/line/HoughTransformBinary.java:124-135) with HoughParametersPolar.parameterize
+ * (HoughParametersPolar.java:97-114) after the fill with 0: every pixel != 0 adds 1 to one cell in each of the numBinsAngle rows, at
+ * col = (int)Math.floor(p * w2 / r_max) + w2 with p = x*c[i] + y*s[i] summed in float and widened, the rest in double.  cosTable / sinTable
+ * are the numBinsAngle floats of CachedSineCosine_F32(0, (float)Math.PI, numBinsAngle) (georegression; host arrays, the caller builds them).
+ * The Java linear index i*stride + col is kept: col == numBinsRange lands in the next row's first cell.  Deviation: an index outside the
+ * transform is dropped where Java throws ArrayIndexOutOfBoundsException.  Counted in int32 and converted, which equals Java's float++.
+ * BHIP_ERR_UNSUPPORTED: width * height > 2^24 (float++ stops counting there), numBinsAngle > 65535, numBinsAngle * numBinsRange > 2^28.
+ * BHIP_ERR_INVALID: numBinsAngle <= 0, numBinsRange <= 0 (bhip_hough_polar_bins), a transform view of another size. */
+int bhip_hough_binary_polar_dev_u8(bhip_ctx* ctx, const uint8_t* dev_binary, long long imageStride, int stride, int width, int height, int batch,
+								   double rangeResolution, int numBinsAngle, const float* cosTable, const float* sinTable, float* dev_transform,
+								   long long tImageStride, int tStride, int tWidth, int tHeight);
+int bhip_hough_binary_polar_u8(bhip_ctx* ctx, const uint8_t* binary, int start, int stride, int width, int height, double rangeResolution, int numBinsAngle,
+							   const float* cosTable, const float* sinTable, float* transform, int tStart, int tStride, int tWidth, int tHeight);
+/* HoughTransformGradient.transform(derivX, derivY, binary) up to the transform image (F:alg/feature/detect/line/HoughTransformGradient.java:
+ * 114-123, transform :238-252, parameterize :184-202, addParameters :204-213) with HoughParametersFootOfNorm.parameterize
+ * (HoughParametersFootOfNorm.java:76-85), on GrayF32 or GrayS16 derivatives of any source (Prewitt, Sobel, ...).  The transform has the
+ * image's size.  Java's float-to-int rules are kept (NaN -> 0, saturation, x0+1 wrapping, truncation toward zero, so a parameter in (-1, 0)
+ * gives x0 = 0 and a negative weight).  A cell is the float sum of its contributions in the order Java adds them -- edge pixels in raster
+ * order, within a pixel (x0,y0), (x0+1,y0), (x0,y0+1), (x0+1,y0+1) -- started from 0; no float atomics (records, a stable sort by cell, one
+ * lane per cell).  cap: the edge pixels per image that vote, in raster order (width * height: always all of them); dev_n[b] is image b's
+ * number of edge pixels and may exceed cap.  Scratch: 64 bytes per possible vote plus the sort's, for at most 1 GiB of images at a time.
+ * BHIP_ERR_UNSUPPORTED: width * height beyond 2^31 - 2.  BHIP_ERR_INVALID: cap < 0, a null count. */
+int bhip_hough_gradient_foot_dev_f32(bhip_ctx* ctx, const float* dev_dx, const float* dev_dy, long long dImageStride, int dStride, const uint8_t* dev_binary,
+									 long long bImageStride, int bStride, int width, int height, int batch, float* dev_transform, long long tImageStride,
+									 int tStride, int cap, int* dev_n);
+int bhip_hough_gradient_foot_dev_s16(bhip_ctx* ctx, const int16_t* dev_dx, const int16_t* dev_dy, long long dImageStride, int dStride, const uint8_t* dev_binary,
+									 long long bImageStride, int bStride, int width, int height, int batch, float* dev_transform, long long tImageStride,
+									 int tStride, int cap, int* dev_n);
+/* NonMaxBlock.process with NonMaxBlockSearchRelaxed.Max (F:alg/feature/detect/extract/NonMaxBlock.java:69-94, NonMaxBlockSearchRelaxed.java:69-98,
+ * checkLocalMax :227-251), the extractor FactoryFeatureExtractor.nonmax builds for ConfigExtract(radius, threshold, border, false).  Its quirks
+ * are kept: a pixel equal to the threshold is a peak, all equal maxima of a block are tested in raster order within the block, checkLocalMax
+ * rejects only on > over the clipped window, nothing is reported when the peak value is Float.MAX_VALUE.  Output as bhip_nonmax_block_dev_f32:
+ * (x,y) int16 pairs in block-raster order, image b's at dev_xy[b*cap ...], their number in dev_n[b] (it may exceed cap; only the first cap
+ * pairs are written).  BHIP_ERR_UNSUPPORTED: an image side of 32768 or more. */
+int bhip_nonmax_block_relaxed_dev_f32(bhip_ctx* ctx, const float* dev_intensity, long long imageStride, int stride, int width, int height, int batch, int radius,
+									  float threshold, int border, int16_t* dev_xy, int cap, int* dev_n);
+int bhip_nonmax_block_relaxed_f32(bhip_ctx* ctx, const float* intensity, int start, int stride, int width, int height, int radius, float threshold, int border,
+								  int16_t* xy, int cap, int* n);
+/* MeanShiftPeak.search(x, y) (F:alg/feature/detect/peak/MeanShiftPeak.java:103-160) from the first min(dev_n[b], cap) integer peaks
+ * dev_xy[b*cap ...] of every image, as HoughTransformGradient.extractLines runs it (:151): bilinear GrayF32 interpolation with the ZERO border
+ * (I:alg/interpolate/impl/ImplBilinearPixel_F32.java:48-90), the isInFastBounds choice per iteration, the three sums as sequential float chains
+ * in the reference's order, one lane per peak.  weights: the (2*radius+1)^2 floats of the WeightPixel_F32 kernel, row-major (host array;
+ * WeightPixelGaussian_F32 for the detector).  radius <= 0: no refinement (weights may be NULL).  dev_peak[(b*cap+i)*2 ...] = (peakX, peakY),
+ * dev_intensity[b*cap+i] = the image at the integer peak (0 for a peak outside the image).  dev_n == NULL: cap peaks in every image. */
+int bhip_mean_shift_peak_dev_f32(bhip_ctx* ctx, const float* dev_image, long long imageStride, int stride, int width, int height, int batch, const int16_t* dev_xy,
+								 const int* dev_n, int cap, int radius, int maxIterations, float convergenceTol, const float* weights, float* dev_peak,
+								 float* dev_intensity);
+
 #ifdef __cplusplus
 }
 #endif
