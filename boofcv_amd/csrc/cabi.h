@@ -27,7 +27,8 @@ struct CtxScratch {
 	DevBuf binary, label;           // cabi_binary.hip: the two ping-pong images of a long erode / dilate run; parent[] and row counts of the labelling
 	DevBuf binaryTable;             // the host forms' relabel / labelToBinary lookup table
 	DevBuf hough, houghTable;       // cabi_line.hip: vote counts / sort records of the Hough transforms; the sine / cosine and mean-shift weight tables
-	DevBuf thresholdTaps;           // the Kernel1D_S32 Gaussian taps of the GrayU8 blurs, for thresholdTapsRadius (0: none yet)
+	DevBuf enhance;                 // cabi_enhance.hip: the histogram / transform table of the host forms
+	DevBuf thresholdTaps;         // the Kernel1D_S32 Gaussian taps of the GrayU8 blurs, for thresholdTapsRadius (0: none yet)
 	int thresholdTapsRadius = 0;
 	AssocMfmaWork mfma;
 	int assocExactOnly = -1;  // BHIP_ASSOC_EXACT=1 forces the exact VALU association kernels (parity cross-check)

@@ -590,7 +590,9 @@ enum { BHIP_CMP_LE = 0, BHIP_CMP_GT = 1, BHIP_CMP_NOT_LE = 2 };
 // thr: the int or float threshold; imageThr != nullptr: one int threshold per image in device memory instead (GrayU8)
 int bhip_launch_threshold_global(bhip_ctx* ctx, DevImg<const uint8_t> in, DevImg<uint8_t> out, int thr, const int* imageThr, int mode);
 int bhip_launch_threshold_global(bhip_ctx* ctx, DevImg<const float> in, DevImg<uint8_t> out, float thr, const int* imageThr, int mode);
-int bhip_launch_hist_u8(bhip_ctx* ctx, DevImg<const uint8_t> in, int* hist);   // hist[batch][256] += counts (zeroed by the caller)
+// ImageStatistics.histogram(GrayU8, minValue, int[length]), length <= 256: hist[batch][length] += counts (zeroed by the caller); a value outside
+// [minValue, minValue + length) is dropped
+int bhip_launch_hist_u8(bhip_ctx* ctx, DevImg<const uint8_t> in, int* hist, int minValue = 0, int length = 256);
 int bhip_launch_otsu_global(bhip_ctx* ctx, const int* hist, int batch, int totalPixels, double scale, int* thr);
 template <class T>
 int bhip_launch_local_compare(bhip_ctx* ctx, DevImg<const T> in, DevImg<const T> blur, DevImg<uint8_t> out, float scale, bool down);
@@ -652,3 +654,17 @@ int bhip_launch_relaxed_to_xy(bhip_ctx* ctx, const unsigned int* bitmap, const u
 // (2*radius+1)^2 floats, unused when radius <= 0 (no refinement).  peak [batch][cap][2], intensity [batch][cap]: the image at the integer peak
 int bhip_launch_mean_shift_peak(bhip_ctx* ctx, DevImg<const float> img, const int16_t* xy, const int* n, int cap, int radius, int maxIterations, float convergenceTol,
 								const float* weights, float* peak, float* intensity);
+
+// ---------------- EnhanceImageOps: histogram equalisation, local equalisation, sharpen (enhance.hip; the histogram is k_hist_u8) ----------------
+// EnhanceImageOps.equalize on `batch` histograms of `length` <= 256 bins in device memory
+int bhip_launch_equalize_table(bhip_ctx* ctx, const int* hist, int length, int batch, int* transform);
+// applyTransform; tableStride: ints between the tables of two images, 0 = one table for the batch.  A pixel >= length gives 0.  out may be in
+int bhip_launch_apply_transform(bhip_ctx* ctx, DevImg<const uint8_t> in, DevImg<uint8_t> out, const int* table, long long tableStride, int length);
+// equalizeLocal as the rank of the centre pixel in its shifted window (enhance.hip): the direct count out of an LDS tile, which needs
+// bhip_equalize_local_direct_fits, and the sliding histogram, any radius.  in and out must not overlap; at most 65535 images
+bool bhip_equalize_local_direct_fits(int radius, int width, int height);
+int bhip_launch_equalize_local_direct(bhip_ctx* ctx, DevImg<const uint8_t> in, DevImg<uint8_t> out, int radius, int histogramLength);
+int bhip_launch_equalize_local_sliding(bhip_ctx* ctx, DevImg<const uint8_t> in, DevImg<uint8_t> out, int radius, int histogramLength);
+// sharpen4 / sharpen8 (rule 4 / 8), T = uint8_t or float; in and out must not overlap
+template <class T>
+int bhip_launch_sharpen(bhip_ctx* ctx, int rule, DevImg<const T> in, DevImg<T> out);

@@ -113,8 +113,10 @@ int bhip_launch_threshold_global(bhip_ctx* ctx, DevImg<const float> in, DevImg<u
 	return launchThresholdGlobal<float>(ctx, in, out, thr, imageThr, mode);
 }
 
-// GImageStatistics.histogram(GrayU8, 0, int[256]): counts per workgroup in LDS, then one global add per bin that was hit (hist zeroed by the caller)
-__global__ __launch_bounds__(256) void k_hist_u8(const uint8_t* __restrict__ in, long long inImageStride, int inStride, int width, int height, int* __restrict__ hist) {
+// ImageStatistics.histogram(GrayU8, minValue, int[length]), length <= 256: counts per workgroup in LDS, then one global add per bin that was
+// hit (hist[batch][length] zeroed by the caller).  A value outside [minValue, minValue + length) is dropped (the reference throws)
+__global__ __launch_bounds__(256) void k_hist_u8(const uint8_t* __restrict__ in, long long inImageStride, int inStride, int width, int height, int minValue,
+												 int length, int* __restrict__ hist) {
 	__shared__ int h[256];
 	h[threadIdx.x] = 0;
 	__syncthreads();
@@ -127,16 +129,16 @@ __global__ __launch_bounds__(256) void k_hist_u8(const uint8_t* __restrict__ in,
 			loadLane(src + (long long)y * inStride, n, v);
 #pragma unroll
 			for (int j = 0; j < 16; j++)
-				if (j < n) atomicAdd(&h[v[j]], 1);
+				if (j < n && (unsigned)(v[j] - minValue) < (unsigned)length) atomicAdd(&h[v[j] - minValue], 1);
 		}
 	}
 	__syncthreads();
-	if (h[threadIdx.x]) atomicAdd(&hist[blockIdx.z * 256 + threadIdx.x], h[threadIdx.x]);
+	if ((int)threadIdx.x < length && h[threadIdx.x]) atomicAdd(&hist[(long long)blockIdx.z * length + threadIdx.x], h[threadIdx.x]);
 }
-int bhip_launch_hist_u8(bhip_ctx* ctx, DevImg<const uint8_t> in, int* hist) {
+int bhip_launch_hist_u8(bhip_ctx* ctx, DevImg<const uint8_t> in, int* hist, int minValue, int length) {
 	ProfScope prof(ctx, "k_hist_u8", 1.0 * in.width * in.height * in.batch);
 	dim3 grid((in.width + 4095) / 4096, std::min(in.height, 128), in.batch);
-	hipLaunchKernelGGL(k_hist_u8, grid, dim3(256), 0, ctx->stream, in.data, in.imageStride, in.stride, in.width, in.height, hist);
+	hipLaunchKernelGGL(k_hist_u8, grid, dim3(256), 0, ctx->stream, in.data, in.imageStride, in.stride, in.width, in.height, minValue, length, hist);
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;
 }

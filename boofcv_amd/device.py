@@ -29,7 +29,10 @@ Names follow the reference classes the host-buffer forms in boofcv_amd/api/ mirr
   DeviceImageOps.houghGradientFoot  HoughTransformGradient.transform (foot of norm) F:alg/feature/detect/line/HoughTransformGradient.java:184-252
   DeviceImageOps.nonmaxRelaxed  NonMaxBlock.process (NonMaxBlockSearchRelaxed.Max)  F:alg/feature/detect/extract/NonMaxBlockSearchRelaxed.java:69-98,227-251
   DeviceImageOps.meanShiftPeak  MeanShiftPeak.search                                F:alg/feature/detect/peak/MeanShiftPeak.java:103-160
-  DeviceImageOps.brief          DescribePointBrief.process                        F:alg/feature/describe/DescribePointBrief.java:73-89
+  DeviceImageOps.histogram / equalizeTable / applyTransform   ImageStatistics.histogram, EnhanceImageOps.equalize / applyTransform   I:alg/enhance/EnhanceImageOps.java:65-94
+  DeviceImageOps.equalizeLocal  EnhanceImageOps.equalizeLocal (GrayU8)              I:alg/enhance/EnhanceImageOps.java:176-232
+  DeviceImageOps.sharpen        EnhanceImageOps.sharpen4 / sharpen8 (GrayU8, GrayF32)   I:alg/enhance/EnhanceImageOps.java:307-371
+  DeviceImageOps.brief          DescribePointBrief.process                       F:alg/feature/describe/DescribePointBrief.java:73-89
   DeviceKltTracker              PointTrackerKltPyramid, batched over sequences      main/boofcv-geo/.../abst/feature/tracker/PointTrackerKltPyramid.java:139-348
   DeviceBackgroundModel         BackgroundStationaryBasic / Gaussian / Gmm, batched over streams   F:alg/background/stationary/*.java
 """
@@ -222,6 +225,86 @@ class DeviceImageOps:
                 raise IllegalArgumentException("selected must be a contiguous 1-D uint8 or bool CUDA tensor")
             sp, n = C.c_void_p(selected.data_ptr()), selected.numel()
         _check(self.ctx, self.L.bhip_label_to_binary_dev_s32_u8(self.ctx._h, ip, iis, irs, W, H, B, op, ois, ors, sp, n))
+        return out
+
+    # ---- EnhanceImageOps on uint8 (sharpen: also float32) frames [B,H,W] (boofcv_amd/enhance.py has the host-view forms) ----
+    def _table(self, t, B, what, length=None):
+        """a contiguous int32 CUDA tensor [length] (shared by the batch) or [B, length] -> (pointer, ints between two images' tables, length)"""
+        if t.dtype != torch.int32 or t.dim() not in (1, 2) or not t.is_contiguous() or not t.is_cuda or not 1 <= t.shape[-1] <= 256:
+            raise IllegalArgumentException("%s must be a contiguous int32 CUDA tensor [length] or [B, length] with 1 <= length <= 256" % what)
+        if t.dim() == 2 and t.shape[0] != B:
+            raise IllegalArgumentException("%s holds %d tables for %d images" % (what, t.shape[0], B))
+        if length is not None and t.shape[-1] != length:
+            raise IllegalArgumentException("%s must have %d entries" % (what, length))
+        return C.c_void_p(t.data_ptr()), (t.shape[-1] if t.dim() == 2 else 0), t.shape[-1]
+
+    def histogram(self, src, minValue=0, length=256, out=None):
+        """ImageStatistics.histogram(GrayU8, minValue, int[length]) on uint8 frames [B,H,W] of any row / image stride -> int32 [B, length] on
+        the device (`out`, contiguous, is cleared and filled in place).  A pixel outside [minValue, minValue + length) is dropped where the
+        reference throws.  No host synchronisation."""
+        if not 1 <= length <= 256 or not 0 <= minValue <= 255:
+            raise IllegalArgumentException("histogram: length must be in 1 .. 256 and minValue in 0 .. 255")
+        ip, iis, irs, W, H, B = _geom(src, torch.uint8)
+        if out is None:
+            out = torch.empty((B, length), dtype=torch.int32, device=src.device)
+        if out.dim() != 2:
+            raise IllegalArgumentException("the histograms must be an int32 CUDA tensor [B, length]")
+        hp, _, _ = self._table(out, B, "the histograms", length)
+        _check(self.ctx, self.L.bhip_histogram_dev_u8(self.ctx._h, ip, iis, irs, W, H, B, int(minValue), int(length), hp))
+        return out
+
+    def equalizeTable(self, histograms, out=None):
+        """EnhanceImageOps.equalize on int32 histograms [B, length] (or [length]) on the device -> the transform tables of the same shape (`out`
+        may be `histograms`).  A histogram that sums to 0 gives zeros where the reference throws.  No host synchronisation."""
+        B = histograms.shape[0] if histograms.dim() == 2 else 1
+        hp, _, length = self._table(histograms, B, "the histograms")
+        if out is None:
+            out = torch.empty_like(histograms)
+        if out.shape != histograms.shape:
+            raise IllegalArgumentException("histograms and tables differ in shape")
+        tp, _, _ = self._table(out, B, "the tables", length)
+        _check(self.ctx, self.L.bhip_equalize_table_dev(self.ctx._h, hp, length, B, tp))
+        return out
+
+    def applyTransform(self, src, table, out=None):
+        """EnhanceImageOps.applyTransform on uint8 frames [B,H,W] of any row / image stride: out = (byte)table[src].  table: int32 on the
+        device, [B, length] (one table per image, as equalizeTable gives) or [length] (shared by the batch).  `out` (any stride) is written
+        in place and as a whole and may be `src`; a pixel beyond the table gives 0 where the reference throws.  No host synchronisation."""
+        ip, iis, irs, W, H, B = _geom(src, torch.uint8)
+        tp, ts, length = self._table(table, B, "the table")
+        out, op, ois, ors = self._u8_out(src, out, B, H, W)
+        _check(self.ctx, self.L.bhip_apply_transform_dev_u8(self.ctx._h, ip, iis, irs, W, H, B, tp, ts, length, op, ois, ors))
+        return out
+
+    def equalizeLocal(self, src, radius, histogramLength=256, out=None, path="auto"):
+        """EnhanceImageOps.equalizeLocal(input, radius, output, histogramLength, null) on uint8 frames [B,H,W] of any row / image stride -> the
+        uint8 images [B,H,W] (`out`, any stride, is written in place and as a whole; it must not overlap `src`).  0 <= radius <= 255,
+        1 <= histogramLength <= 256; a pixel >= histogramLength is ranked like any other where the reference throws.  path: "auto", or
+        "direct" / "sliding" to force one of the two kernels (the same image either way; "direct" is refused when its tile does not fit
+        LDS).  No host synchronisation."""
+        from . import enhance
+        enhance.check_equalize_local(radius, histogramLength)
+        ip, iis, irs, W, H, B = _geom(src, torch.uint8)
+        out, op, ois, ors = self._u8_out(src, out, B, H, W)
+        _check(self.ctx, self.L.bhip_equalize_local_dev_u8(self.ctx._h, ip, iis, irs, W, H, B, int(radius), int(histogramLength), enhance.path_value(path), op, ois, ors))
+        return out
+
+    def sharpen(self, src, rule, out=None):
+        """EnhanceImageOps.sharpen4 / sharpen8(input, output): rule 4 or 8, on uint8 or float32 frames [B,H,W] of any row / image stride -> images
+        of the same type (`out`, any stride, is written in place and as a whole; it must not overlap `src`).  No host synchronisation."""
+        if int(rule) not in (4, 8):
+            raise IllegalArgumentException("sharpen: rule must be 4 or 8")
+        dt = src.dtype
+        if dt not in (torch.uint8, torch.float32):
+            raise IllegalArgumentException("sharpen: expected uint8 or float32 frames")
+        ip, iis, irs, W, H, B = _geom(src, dt)
+        if out is None:
+            out = torch.empty((B, H, W), dtype=dt, device=src.device)
+        op, ois, ors, W2, H2, B2 = _geom(out, dt)
+        if (W, H, B) != (W2, H2, B2):
+            raise IllegalArgumentException("input and output shapes differ")
+        fn = self.L.bhip_sharpen_dev_u8 if dt == torch.uint8 else self.L.bhip_sharpen_dev_f32
+        _check(self.ctx, fn(self.ctx._h, int(rule), ip, iis, irs, W, H, B, op, ois, ors))
         return out
 
     def _grad(self, fn, src, border, dx, dy):

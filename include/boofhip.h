@@ -1320,6 +1320,65 @@ int bhip_mean_shift_peak_dev_f32(bhip_ctx* ctx, const float* dev_image, long lon
 								 const int* dev_n, int cap, int radius, int maxIterations, float convergenceTol, const float* weights, float* dev_peak,
 								 float* dev_intensity);
 
+/* ---- image enhancement: EnhanceImageOps (I:alg/enhance/EnhanceImageOps.java) and the histogram it starts from, on GrayU8 (sharpen also on
+ *      GrayF32) images (enhance.hip; the histogram kernel is threshold.hip's).  There is no BOverride hook for EnhanceImageOps in the reference:
+ *      integration/java/boofcv/hip/EnhanceImageOpsHip.java is a provider class with the same static signatures.
+ * The _dev forms take batch images at dev_x + b*xImageStride (strides in elements, any alignment), write the whole width x height view of every
+ * output image and nothing outside it, are asynchronous on the context's stream without host synchronisation and need no scratch.  The forms
+ * without _dev take one host image view each: staged, run through the same implementation, synchronised.  All of the GrayU8 arithmetic is
+ * integer, and the GrayF32 sharpen keeps Java's evaluation order without fused multiply-add: results equal the single-threaded Java results
+ * bit for bit.
+ * Not provided: the GrayU16 / GrayS8 / GrayS16 / GrayS32 forms of applyTransform and equalizeLocal.
+ * BHIP_ERR_INVALID and nothing is written: empty images, strides smaller than a row, a length or histogramLength outside 1 .. 256, a minValue
+ * outside 0 .. 255, a negative radius, an unknown path or rule, overlapping input and output of equalizeLocal or sharpen.
+ * BHIP_ERR_UNSUPPORTED: more than 65535 images in a batch, an equalizeLocal radius beyond 255, a forced path that cannot run the call. */
+/* ImageStatistics.histogram(GrayU8 input, int minValue, int[] histogram) (I:alg/misc/ImageStatistics.java:299-306,
+ * impl/ImplImageStatistics.java:206-221) with histogram.length = length <= 256: image b's counts go to dev_histogram[b*length ...], which is
+ * cleared first as Arrays.fill does.  Deviation: a pixel outside [minValue, minValue + length) is dropped (the reference throws
+ * ArrayIndexOutOfBoundsException). */
+int bhip_histogram_dev_u8(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, int minValue, int length,
+						  int* dev_histogram);
+int bhip_histogram_u8(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, int minValue, int length, int* histogram);
+/* EnhanceImageOps.equalize(histogram, transform) (:65-77) on `batch` histograms of `length` <= 256 ints in device memory:
+ * transform[i] = ((histogram[0] + .. + histogram[i]) * (length - 1)) / sum in Java's int arithmetic.  dev_transform may be dev_histogram.
+ * Deviation: a histogram whose sum is 0 gives a table of zeros (the reference throws ArithmeticException). */
+int bhip_equalize_table_dev(bhip_ctx* ctx, const int* dev_histogram, int length, int batch, int* dev_transform);
+/* EnhanceImageOps.applyTransform(GrayU8, int[] transform, GrayU8) (:86-94, impl/ImplEnhanceHistogram.java:42-53): out = (byte)transform[in].
+ * Image b reads the `length` ints at dev_transform + b*transformStride (transformStride 0: one table for the batch, `length`: the layout
+ * bhip_equalize_table_dev writes).  dev_out may be dev_in (the same view).  Deviation: a pixel >= length gives 0 (the reference throws). */
+int bhip_apply_transform_dev_u8(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch,
+								const int* dev_transform, long long transformStride, int length, uint8_t* dev_out, long long outImageStride, int outStride);
+int bhip_apply_transform_u8(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, const int* transform, int length, uint8_t* out,
+							int outStart, int outStride);
+/* EnhanceImageOps.equalizeLocal(GrayU8 input, radius, GrayU8 output, histogramLength, workArrays) (:176-232).  The reference's three branches --
+ * equalizeLocalInner + two equalizeLocalRow + two equalizeLocalCol (impl/ImplEnhanceHistogram.java:175-401) when both sides are >= 2*radius+1,
+ * the whole-image histogram when both are smaller, equalizeLocalNaive (:111-170) otherwise -- are one rule: with w = 2*radius+1,
+ * x0 = max(0, min(x - radius, width - w)), x1 = min(width, x0 + w) and the same in y,
+ * out(x,y) = (byte)((number of pixels in [x0,x1) x [y0,y1) with a value <= in(x,y)) * (histogramLength - 1) / ((x1-x0) * (y1-y0))).
+ * path: BHIP_EQLOCAL_DIRECT counts the window out of an LDS tile (it needs (64 + 2*radius) x (16 + 2*radius) bytes, each clipped to the image
+ * side, within 64 KiB), BHIP_EQLOCAL_SLIDING slides a 256-bin histogram along runs of a row (any radius, at most 65535 rows), BHIP_EQLOCAL_AUTO
+ * picks by radius; the three give the same image.  0 <= radius <= 255, 1 <= histogramLength <= 256; input and output must not overlap.
+ * Deviation: a pixel >= histogramLength is ranked like any other (the reference throws ArrayIndexOutOfBoundsException). */
+#define BHIP_EQLOCAL_AUTO 0
+#define BHIP_EQLOCAL_DIRECT 1
+#define BHIP_EQLOCAL_SLIDING 2
+int bhip_equalize_local_dev_u8(bhip_ctx* ctx, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, int radius,
+							   int histogramLength, int path, uint8_t* dev_out, long long outImageStride, int outStride);
+int bhip_equalize_local_u8(bhip_ctx* ctx, const uint8_t* in, int inStart, int inStride, int width, int height, int radius, int histogramLength, int path,
+						   uint8_t* out, int outStart, int outStride);
+/* EnhanceImageOps.sharpen4 / sharpen8 (:307-371; rule 4 or 8): impl/ImplEnhanceFilter.java sharpenInner4 / 8 (:43-64, :120-141, :197-226,
+ * :321-350) for 1 <= x < width-1, 1 <= y < height-1 -- 5*c - (((l + r) + u) + d), 9*c - (the eight neighbours in raster order) -- then
+ * sharpenBorder4 / 8 (:66-118, :143-195, :228-319, :352-443) through the clamping safeGet (:448-475) in its loop order (every x: top, bottom;
+ * every y in 1 .. height-2: left, right -- the last write stands, which is what sides of 1 and 2 and the corners come out of), clamped to
+ * [0, 255] as `if (a > 255) a = 255; else if (a < 0) a = 0`.  GrayF32 keeps the order of the additions and uses no fused multiply-add.
+ * Input and output must not overlap. */
+int bhip_sharpen_dev_u8(bhip_ctx* ctx, int rule, const uint8_t* dev_in, long long inImageStride, int inStride, int width, int height, int batch, uint8_t* dev_out,
+						long long outImageStride, int outStride);
+int bhip_sharpen_dev_f32(bhip_ctx* ctx, int rule, const float* dev_in, long long inImageStride, int inStride, int width, int height, int batch, float* dev_out,
+						 long long outImageStride, int outStride);
+int bhip_sharpen_u8(bhip_ctx* ctx, int rule, const uint8_t* in, int inStart, int inStride, int width, int height, uint8_t* out, int outStart, int outStride);
+int bhip_sharpen_f32(bhip_ctx* ctx, int rule, const float* in, int inStart, int inStride, int width, int height, float* out, int outStart, int outStride);
+
 #ifdef __cplusplus
 }
 #endif
