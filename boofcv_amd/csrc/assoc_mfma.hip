@@ -7,7 +7,10 @@
 // listed pairs (about 1.15 per row / column on SURF descriptors) are then re-scored with the reference's sequential fp64 loop and the
 // reference's rules are applied to those exact values.  Because the filter only needs a rigorous error bound, not accuracy, it runs in
 // fp16 (v_mfma_f32_32x32x16_f16, 16x the fp32 matrix rate) on descriptors scaled by one power of two 2^-q per call so that the largest
-// squared norm lies in [1/4, 1):
+// squared norm lies in [1/16, 1).  q is not measured first: the prep kernel converts with the exponent q_h the previous call measured
+// (AssocMfmaWork::scaleHint; 1 at first, the exponent of unit vectors) while it forms the norms, and the host accepts the run iff the
+// largest norm M it read back is 0 or 4^(q_h - 2) <= M < 4^q_h.  Otherwise the call is repeated once with the measured q (largest scaled
+// norm in [1/4, 1)) through k_assoc_norms + k_assoc_half.  The result does not depend on which q was used: the filter only selects.
 //     a^ = fl16(2^-q a),  n_a = |2^-q a|^2 (fp32, rounded up) = hi + lo (two fp16),
 //     d~(i,j) = 1 + n_a + n_b - 2 <a^_i, b^_j> -- ONE K = 80 contraction: the row holds [-2 a^ | hi lo 1 1 1 | 0...], the column [b^ | 1 1 hi lo 1 | 0...]
 //   (the constant 1 keeps every score a positive float, so minima are unsigned-integer minima of the bit patterns: v_min3_u32, no NaN
@@ -17,6 +20,12 @@
 //     norm split       2^-22 (n_a + n_b) + 2^-24 ;  norm round-up 4 * 2^-24 (n_a + n_b)
 //     fp32 accumulate  85 additions, <= 2^-23 relative each even if truncating: 2^-16 (1 + n_a + n_b + 2|a'||b'|) <= 2^-15 (n_a + n_b) + 1.6e-5
 //   =>  |d~ - 1 - d'| <= eps(i,j) = C16 (n_a + n_b) + ABS16,   C16 = 1.03e-3,  ABS16 = 2e-5   (d' = 2^-2q d, the exact scaled distance)
+//   The bound asks only for |a'|, |b'| < 1, i.e. a largest scaled norm below 1; how far below does not enter.  Line by line: input rounding
+//   splits into a part proportional to |a'||b'| <= (n_a + n_b) / 2 and the subnormal part, absolute once |a'| + |b'| < 2 (32 s < 1e-6);
+//   norm split and round-up are relative to n_a + n_b, the 2^-24 covers hi or lo falling into the fp16 subnormals whatever the size of n;
+//   the accumulation term is relative to 1 + n_a + n_b + 2|a'||b'| and its absolute part 2^-16 < 1.6e-5 comes from the constant 1 alone.
+//   A largest scaled norm in [1/16, 1/4) therefore keeps eps valid; it only lets the absolute terms weigh up to four times more against
+//   the scores, i.e. a slightly longer candidate list.  The padding "norm" BIG16 likewise needs real norms < 1 and nothing else.
 // Pass 1 reduces d~ to per-row and per-column minima.  Pass 2 recomputes the tiles (same instructions, same bits) and lists every pair with
 //     d~(i,j) <= rowmin~(i) + band(i)   /   d~(i,j) <= colmin~(j) + band(j),     band = 2 (C16 (n + max n) + ABS16)   (>= 2 eps)
 // The true row arg-min (and every exact tie of it) and the true column minimum (and every exact tie) are provably inside those lists and
@@ -35,6 +44,7 @@
 #include "common.h"
 #include <cfloat>
 #include <cmath>
+#include <cstring>
 #include <algorithm>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -65,11 +75,26 @@ __device__ __forceinline__ void waveSyncLds() {
 }
 
 // q with max norm * 2^-2q in [1/4, 1)  (0 when there is no positive norm)
-__device__ __forceinline__ int scaleExp(float maxN) {
+__host__ __device__ __forceinline__ int scaleExp(float maxN) {
 	if (!(maxN > 0.0f)) return 0;
 	int e;
 	(void)frexpf(maxN, &e);
 	return (e + 1) >> 1;
+}
+// a run scaled with 2^-q is usable: max norm * 2^-2q in [1/16, 1), or no positive norm at all.  maxN = m 2^e with m in [1/2, 1), so
+// 4^(q-2) <= maxN < 4^q is 2q - 3 <= e <= 2q (integers only: the host and the device decide alike)
+__host__ __device__ __forceinline__ bool scaleHolds(float maxN, int q) {
+	if (!(maxN > 0.0f)) return true;
+	int e;
+	(void)frexpf(maxN, &e);
+	return e >= 2 * q - 3 && e <= 2 * q;
+}
+// the filter's run is not to be used: a non-finite value, more listed pairs than the list holds, or a scale that does not fit the norms
+// flags: [0] non-finite seen, [1] max norm (float bits), [2] number of listed pairs, [3] scale exponent q of this run
+__host__ __device__ __forceinline__ bool assocDegenerate(const int* flags, int cap) {
+	float maxN;
+	memcpy(&maxN, &flags[1], 4);
+	return flags[0] != 0 || flags[2] > cap || !scaleHolds(maxN, flags[3]);
 }
 
 // ---- squared norms (fp32, rounded up); flags[0] = non-finite seen, flags[1] = max norm (float bits, non-negative) ----
@@ -104,12 +129,13 @@ __global__ __launch_bounds__(256) void k_assoc_norms(const double* __restrict__ 
 
 // ---- fp64 -> scaled fp16 rows [64 values | hi lo 1 1 1 0 0 0]; nrm is rescaled in place ----
 typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void k_assoc_half(const double* __restrict__ D, long long rows, float* __restrict__ nrm, const int* __restrict__ flags,
+__global__ __launch_bounds__(256) void k_assoc_half(const double* __restrict__ D, long long rows, float* __restrict__ nrm, int* __restrict__ flags,
 													  _Float16* __restrict__ Hrow) {
 	const long long row0 = (((long long)blockIdx.x * 256 + threadIdx.x) >> 4) * PREP_ROWS;
 	const int part = threadIdx.x & 15;
 	if (row0 >= rows) return;
 	const int q_ = scaleExp(__int_as_float(flags[1]));
+	if (blockIdx.x == 0 && threadIdx.x == 0) flags[3] = q_;   // the exponent of this run, for pass 2 and the validity checks
 	double2 v0[PREP_ROWS], v1[PREP_ROWS];
 #pragma unroll
 	for (int q = 0; q < PREP_ROWS; q++) {
@@ -136,29 +162,62 @@ __global__ __launch_bounds__(256) void k_assoc_half(const double* __restrict__ D
 	}
 }
 
-__global__ void k_fill_u32(unsigned int* p, long long n, unsigned int v) {
-	const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n) p[i] = v;
-}
-
-// thr = min~ + band, band = 2 (C16 (norm + maxNorm) + ABS16), scaled units
-__global__ void k_assoc_thresholds(const AssocProblem* __restrict__ probs, int count, const float* __restrict__ nrmS, const float* __restrict__ nrmD,
-								   const unsigned int* __restrict__ rowKey, const unsigned int* __restrict__ colKey, const int* __restrict__ flags,
-								   float* __restrict__ rowThr, float* __restrict__ colThr) {
-	const int p = blockIdx.y;
-	const AssocProblem P = probs[p];
-	const float maxRaw = __int_as_float(flags[1]);
-	const float maxN = ldexpf(maxRaw, -2 * scaleExp(maxRaw));
-	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < P.ns + P.nd; i += gridDim.x * blockDim.x) {
-		if (i < P.ns) {
-			const float band = 2.0f * (C16 * (nrmS[P.srcOff + i] + maxN) + ABS16);
-			rowThr[P.rowBase + i] = __uint_as_float(rowKey[P.rowBase + i]) + band;   // still carries the +1 of the scores
-		} else {
-			const int j = i - P.ns;
-			const float band = 2.0f * (C16 * (nrmD[P.dstOff + j] + maxN) + ABS16);
-			colThr[P.colBase + j] = __uint_as_float(colKey[P.colBase + j]) + band;
+// ---- both steps in one pass over the descriptors, with the scale exponent q_h assumed instead of measured (flags[3], set by k_assoc_init);
+// same loads, same norm expression and shuffle order as k_assoc_norms, same conversion as k_assoc_half: with q_h = q the rows, the norms
+// and the flags are the bits those two kernels write.  Whether q_h fitted is decided afterwards from flags[1] (scaleHolds) ----
+__global__ __launch_bounds__(256) void k_assoc_prep_hinted(const double* __restrict__ D, long long rows, int q_, float* __restrict__ nrm, int* __restrict__ flags,
+															 _Float16* __restrict__ Hrow) {
+	const long long row0 = (((long long)blockIdx.x * 256 + threadIdx.x) >> 4) * PREP_ROWS;
+	const int part = threadIdx.x & 15;
+	if (row0 >= rows) return;   // whole 16-lane groups leave together
+	double2 v0[PREP_ROWS], v1[PREP_ROWS];
+#pragma unroll
+	for (int q = 0; q < PREP_ROWS; q++) {
+		const long long row = min(row0 + q, rows - 1);
+		const double2* src = (const double2*)(D + row * 64 + 4 * part);
+		v0[q] = src[0]; v1[q] = src[1];
+	}
+#pragma unroll
+	for (int q = 0; q < PREP_ROWS; q++) {
+		double s = (v0[q].x * v0[q].x + v0[q].y * v0[q].y) + (v1[q].x * v1[q].x + v1[q].y * v1[q].y);
+#pragma unroll
+		for (int o = 8; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+		const long long row = row0 + q;
+		if (row >= rows) continue;   // the group's lanes agree (the shuffles above are done)
+		_Float16* out = Hrow + row * (ROW_CHUNKS * 8);
+		const h16x4 hv = {(_Float16)(float)ldexp(v0[q].x, -q_), (_Float16)(float)ldexp(v0[q].y, -q_), (_Float16)(float)ldexp(v1[q].x, -q_),
+						  (_Float16)(float)ldexp(v1[q].y, -q_)};
+		*(h16x4*)(out + 4 * part) = hv;
+		if (part == 0) {
+			const float nRaw = (float)s;
+			const float nUp = nRaw * (1.0f + 4.0f * 5.9604644775390625e-08f);   // rounded up: a band computed from it can only grow
+			if (!(s < 1e30)) atomicOr(&flags[0], 1);  // NaN, Inf or absurdly large: use the exact path
+			else if (__float_as_int(nUp) > __hip_atomic_load(&flags[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&flags[1], __float_as_int(nUp));
+			const float n = ldexpf(nUp, -2 * q_);
+			const _Float16 hi = (_Float16)n;
+			const _Float16 lo = (_Float16)(n - (float)hi);
+			const h16x8 e = {hi, lo, (_Float16)1.0f, (_Float16)1.0f, (_Float16)1.0f, (_Float16)0.0f, (_Float16)0.0f, (_Float16)0.0f};
+			*(h16x8*)(out + 64) = e;
+			nrm[row] = n;
 		}
 	}
+}
+
+// ---- the constants every call starts from, one launch: minima keys and exact minima at "+infinity", arg-max slots at -1, the column tie
+// counts at 0 (args = [rowArg | colArg | colCnt]) and the flags words ([3] = the scale exponent the prep kernel is given, 0 otherwise) ----
+// It also brings the problem and block tables over: tabSrc is the page-locked staging block itself, read through its device address, so no
+// copy command stands in the stream (one costs the stream about 18 us, whatever memory it reads from); tabWords = 0: they are in place
+__global__ __launch_bounds__(256) void k_assoc_init(unsigned int* __restrict__ keys, unsigned long long* __restrict__ best, int* __restrict__ args, long long nk,
+													  long long colTotal, int* __restrict__ flags, int q_, const uint4* __restrict__ tabSrc, uint4* __restrict__ tabDst,
+													  long long tabWords) {
+	const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+	if (i < tabWords) tabDst[i] = tabSrc[i];
+	if (i < 16) flags[i] = i == 3 ? q_ : 0;
+	if (i >= nk) return;
+	keys[i] = 0xFFFFFFFFu;
+	best[i] = ~0ull;
+	args[i] = -1;
+	if (i < colTotal) args[nk + i] = 0;
 }
 
 struct MfmaArgs {
@@ -168,8 +227,9 @@ struct MfmaArgs {
 	const AssocBlock* blocks;
 	unsigned int* rowKey;
 	unsigned int* colKey;
-	const float* rowThr;
-	const float* colThr;
+	const float* nrmS;   // scaled norms (pass 2 forms its thresholds from them, the minima keys and the largest norm)
+	const float* nrmD;
+	const int* flags;
 	AssocCand* cand;
 	int* counter;    // number of listed pairs
 	int cap;
@@ -224,6 +284,12 @@ __device__ __forceinline__ uint4 extChunk(float n0, float n1, float n2, float n3
 // B-stationary: a workgroup stages ONE column strip of a problem (<= STRIP_COLS destination rows, fragment order, 5.3 KB per 32 columns)
 // in LDS and then walks its row range in wave tiles of 64 rows -- no barrier and no global traffic inside the sweep except the A fragments
 // of the next tile.  The column minima of the strip accumulate in LDS over all row tiles and leave with one atomic per column.
+// BHIP_ASSOC_PEEL: the sweep's single last column tile of an odd tile count is a step of its own, so that the steps with two tiles have no
+// branch between their MFMAs and no accumulator set-up (pass 1 0.274 -> 0.256 ms, pass 2 0.442 -> 0.419 ms at 256 x 2150 key points;
+// DESIGN.md, "association: one-pass prep").  -DBHIP_ASSOC_PEEL=0 (BHIP_EXP_DEFS of build.py) builds the single loop for A/B runs.
+#ifndef BHIP_ASSOC_PEEL
+#define BHIP_ASSOC_PEEL 1
+#endif
 #define STRIP_COLS 384
 #define STRIP_TILES (STRIP_COLS / 32)
 template <int PASS>
@@ -269,8 +335,21 @@ __global__ __launch_bounds__(256, 2) void k_assoc_mfma(MfmaArgs A) {
 		}
 	}
 	for (int g = tid; g < ntile * 32; g += 256) tileB[g >> 5][9 * 33 + (g & 31)] = make_uint4(0, 0, 0, 0);
-	for (int c = tid; c < ntile * 32; c += 256)
-		colLds[c] = PASS == 1 ? 0xFFFFFFFFu : (c < ncol ? __float_as_uint(A.colThr[P.colBase + B.col0 + c]) : __float_as_uint(-INFINITY));
+	// PASS 2: thr = min~ + band, band = 2 (C16 (norm + maxNorm) + ABS16) in scaled units; min~ still carries the +1 of the scores
+	float maxN = 0.0f;
+	if (PASS == 2) maxN = ldexpf(__int_as_float(A.flags[1]), -2 * A.flags[3]);
+	for (int c = tid; c < ntile * 32; c += 256) {
+		unsigned int v = 0xFFFFFFFFu;
+		if (PASS == 2) {
+			float thr = -INFINITY;
+			if (c < ncol) {
+				const float band = 2.0f * (C16 * (A.nrmD[P.dstOff + B.col0 + c] + maxN) + ABS16);
+				thr = __uint_as_float(A.colKey[P.colBase + B.col0 + c]) + band;
+			}
+			v = __float_as_uint(thr);
+		}
+		colLds[c] = v;
+	}
 	__syncthreads();
 
 	// ---- row tiles of this block's row range, 64 rows per wave and turn ----
@@ -309,11 +388,20 @@ __global__ __launch_bounds__(256, 2) void k_assoc_mfma(MfmaArgs A) {
 		for (int k = 0; k < 32; k++) rowM[k] = 0xFFFFFFFFu;
 		if (PASS == 2) {
 			waveSyncLds();   // the previous tile's reads of rowThrLds are over
-			rowThrLds[wave][lane] = rowT + lane < B.row1 ? A.rowThr[P.rowBase + rowT + lane] : -INFINITY;
+			float thr = -INFINITY;
+			if (rowT + lane < B.row1) {
+				const float band = 2.0f * (C16 * (A.nrmS[P.srcOff + rowT + lane] + maxN) + ABS16);
+				thr = __uint_as_float(A.rowKey[P.rowBase + rowT + lane]) + band;
+			}
+			rowThrLds[wave][lane] = thr;
 			waveSyncLds();
 		}
-		for (int ct = 0; ct < ntile; ct += 2) {
-			const bool two = ct + 1 < ntile;   // wave-uniform: an odd tile count leaves the last step with one column tile
+		// one step = column tiles ct and ct + 1.  BHIP_ASSOC_PEEL: the steps with both tiles first (`two` is a constant in the unrolled
+		// round: no branch between their MFMAs, every accumulator starts from the zero operand), then the single last tile of an odd count
+#pragma unroll
+		for (int round = 0; round <= BHIP_ASSOC_PEEL; round++)
+		for (int ct = round == 0 ? 0 : (ntile & ~1); ct < (BHIP_ASSOC_PEEL && round == 0 ? (ntile & ~1) : ntile); ct += 2) {
+			const bool two = BHIP_ASSOC_PEEL ? round == 0 : ct + 1 < ntile;   // wave-uniform: an odd tile count leaves the last step with one column tile
 			const int cA_ = 32 * ct + r, cB_ = cA_ + 32;
 			f32x16 acc[2][2];
 #pragma unroll
@@ -448,8 +536,10 @@ __global__ __launch_bounds__(256) void k_assoc_argsel(const AssocProblem* __rest
 
 __global__ __launch_bounds__(256) void k_assoc_resolve(const AssocProblem* __restrict__ probs, double maxErr, int backwards,
 														 const unsigned long long* __restrict__ rowBest, const int* __restrict__ rowArg,
-														 const int* __restrict__ colArg, const int* __restrict__ colCnt, int* __restrict__ pairs,
-														 double* __restrict__ fit) {
+														 const int* __restrict__ colArg, const int* __restrict__ colCnt, const int* __restrict__ flags, int cap,
+														 int* __restrict__ pairs, double* __restrict__ fit) {
+	// launched before the host has seen the flags: a run the host will not use (it decides from the same words) writes nothing
+	if (assocDegenerate(flags, cap)) return;
 	const AssocProblem P = probs[blockIdx.y];
 	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < P.ns; i += gridDim.x * blockDim.x) {
 		const int m = rowArg[P.rowBase + i];
@@ -492,27 +582,29 @@ int bhip_assoc_l2_mfma_batched(bhip_ctx* ctx, AssocMfmaWork& W, const double* de
 	}
 	// block table: one block per (problem, column strip of <= STRIP_COLS columns, row chunk); the rows are split only when there are too few
 	// strips to fill the chip (a block then accumulates column minima over its chunk and the chunks meet in the global atomics)
-	long long strips = 0;
-	for (int p = 0; p < count; p++) strips += (nd[p] + STRIP_COLS - 1) / STRIP_COLS;
-	int rowSplit = (int)std::max<long long>(1, (1024 + strips - 1) / strips);
-	{ const char* e = getenv("BHIP_ASSOC_ROWSPLIT"); if (e && atoi(e) > 0) rowSplit = atoi(e); }   // tests: force row chunks / whole-problem sweeps
-	for (int p = 0; p < count; p++) {
-		int chunk = (ns[p] + rowSplit - 1) / rowSplit;
-		chunk = std::max(256, ((chunk + 255) / 256) * 256);   // whole turns of the four waves
-		for (int c0 = 0; c0 < nd[p]; c0 += STRIP_COLS)
-			for (int r0 = 0; r0 < ns[p]; r0 += chunk) blocks.push_back({p, r0, std::min(ns[p], r0 + chunk), c0, std::min(nd[p], c0 + STRIP_COLS)});
-	}
-	if (count >= 16) {
-		// Workgroup ids go round-robin over the 8 XCDs: give all blocks of a problem the same id residue so that its destination rows are
-		// fetched into ONE XCD's L2 instead of eight (problems are dealt to the residues in turn; short queues are padded with empty entries).
-		std::vector<AssocBlock> q[8];
-		for (const AssocBlock& b : blocks) q[b.p & 7].push_back(b);
-		size_t longest = 0;
-		for (int x = 0; x < 8; x++) longest = std::max(longest, q[x].size());
-		blocks.assign(longest * 8, AssocBlock{0, 0, 0, 0, 0});
-		for (int x = 0; x < 8; x++)
-			for (size_t k = 0; k < q[x].size(); k++) blocks[k * 8 + x] = q[x][k];
-	}
+	auto buildBlocks = [&]() {
+		long long strips = 0;
+		for (int p = 0; p < count; p++) strips += (nd[p] + STRIP_COLS - 1) / STRIP_COLS;
+		int rowSplit = (int)std::max<long long>(1, (1024 + strips - 1) / strips);
+		{ const char* e = getenv("BHIP_ASSOC_ROWSPLIT"); if (e && atoi(e) > 0) rowSplit = atoi(e); }   // tests: force row chunks / whole-problem sweeps
+		for (int p = 0; p < count; p++) {
+			int chunk = (ns[p] + rowSplit - 1) / rowSplit;
+			chunk = std::max(256, ((chunk + 255) / 256) * 256);   // whole turns of the four waves
+			for (int c0 = 0; c0 < nd[p]; c0 += STRIP_COLS)
+				for (int r0 = 0; r0 < ns[p]; r0 += chunk) blocks.push_back({p, r0, std::min(ns[p], r0 + chunk), c0, std::min(nd[p], c0 + STRIP_COLS)});
+		}
+		if (count >= 16) {
+			// Workgroup ids go round-robin over the 8 XCDs: give all blocks of a problem the same id residue so that its destination rows are
+			// fetched into ONE XCD's L2 instead of eight (problems are dealt to the residues in turn; short queues are padded with empty entries).
+			std::vector<AssocBlock> q[8];
+			for (const AssocBlock& b : blocks) q[b.p & 7].push_back(b);
+			size_t longest = 0;
+			for (int x = 0; x < 8; x++) longest = std::max(longest, q[x].size());
+			blocks.assign(longest * 8, AssocBlock{0, 0, 0, 0, 0});
+			for (int x = 0; x < 8; x++)
+				for (size_t k = 0; k < q[x].size(); k++) blocks[k * 8 + x] = q[x][k];
+		}
+	};
 	const bool shared = dev_src == dev_dst;
 	const long long rowsS = shared ? std::max(maxSrcRow, maxDstRow) : maxSrcRow;
 	const int cap = (int)std::min<long long>(0x3fffffffLL, 8 * (rowTotal + colTotal) + 4096);
@@ -523,84 +615,113 @@ int bhip_assoc_l2_mfma_batched(bhip_ctx* ctx, AssocMfmaWork& W, const double* de
 		BHIP_TRY(W.Fd.reserve(ctx, (size_t)maxDstRow * ROW_CHUNKS * 16));
 		BHIP_TRY(W.nrmD.reserve(ctx, (size_t)maxDstRow * 4));
 	}
-	BHIP_TRY(W.probs.reserve(ctx, probs.size() * sizeof(AssocProblem)));
-	BHIP_TRY(W.blocks.reserve(ctx, blocks.size() * sizeof(AssocBlock)));
 	BHIP_TRY(W.keys.reserve(ctx, (size_t)(rowTotal + colTotal) * 4));
-	BHIP_TRY(W.thr.reserve(ctx, (size_t)(rowTotal + colTotal) * 4));
 	BHIP_TRY(W.best.reserve(ctx, (size_t)(rowTotal + colTotal) * 8));
 	BHIP_TRY(W.args.reserve(ctx, (size_t)(rowTotal + 2 * colTotal) * 4));
 	BHIP_TRY(W.cand.reserve(ctx, (size_t)cap * sizeof(AssocCand)));
 	BHIP_TRY(W.flags.reserve(ctx, 64));
 
 	hipStream_t st = ctx->stream;
-	BHIP_HIP(ctx, hipMemcpyAsync(W.probs.p, probs.data(), probs.size() * sizeof(AssocProblem), hipMemcpyHostToDevice, st));
-	BHIP_HIP(ctx, hipMemcpyAsync(W.blocks.p, blocks.data(), blocks.size() * sizeof(AssocBlock), hipMemcpyHostToDevice, st));
-	BHIP_HIP(ctx, hipMemsetAsync(W.flags.p, 0, 64, st));
-	int* flags = W.flags.as<int>();       // [0] non-finite, [1] max norm bits, [2] number of listed pairs
+	int* flags = W.flags.as<int>();       // [0] non-finite, [1] max norm bits, [2] number of listed pairs, [3] scale exponent of the run
 	int* counters = flags + 2;
 	_Float16* Hs = W.Fs.as<_Float16>();
 	float* nS = W.nrmS.as<float>();
 	_Float16* Hd = shared ? Hs : W.Fd.as<_Float16>();
 	float* nD = shared ? nS : W.nrmD.as<float>();
-	{
-		ProfScope ps(ctx, "k_assoc_prep", (double)(rowsS + (shared ? 0 : maxDstRow)) * (2 * 64 * 8 + ROW_CHUNKS * 16));
-		const unsigned gS = (unsigned)((rowsS + 16 * PREP_ROWS - 1) / (16 * PREP_ROWS)), gD = (unsigned)((maxDstRow + 16 * PREP_ROWS - 1) / (16 * PREP_ROWS));
-		hipLaunchKernelGGL(k_assoc_norms, dim3(gS), dim3(256), 0, st, dev_src, rowsS, nS, flags);
-		if (!shared) hipLaunchKernelGGL(k_assoc_norms, dim3(gD), dim3(256), 0, st, dev_dst, maxDstRow, nD, flags);
-		hipLaunchKernelGGL(k_assoc_half, dim3(gS), dim3(256), 0, st, dev_src, rowsS, nS, flags, Hs);
-		if (!shared) hipLaunchKernelGGL(k_assoc_half, dim3(gD), dim3(256), 0, st, dev_dst, maxDstRow, nD, flags, Hd);
-	}
 	unsigned int* rowKey = W.keys.as<unsigned int>();
 	unsigned int* colKey = rowKey + rowTotal;
-	float* rowThr = W.thr.as<float>();
-	float* colThr = rowThr + rowTotal;
 	unsigned long long* rowBest = W.best.as<unsigned long long>();
 	unsigned long long* colBest = rowBest + rowTotal;
 	int* rowArg = W.args.as<int>();
 	int* colArg = rowArg + rowTotal;
 	int* colCnt = colArg + colTotal;
 	const long long nk = rowTotal + colTotal;
-	hipLaunchKernelGGL(k_fill_u32, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, rowKey, nk, 0xFFFFFFFFu);
-	BHIP_HIP(ctx, hipMemsetAsync(W.best.p, 0xFF, (size_t)nk * 8, st));                       // +"infinity" for the u64 minima
-	BHIP_HIP(ctx, hipMemsetAsync(rowArg, 0xFF, (size_t)(rowTotal + colTotal) * 4, st));      // -1
-	BHIP_HIP(ctx, hipMemsetAsync(colCnt, 0, (size_t)colTotal * 4, st));
+	int maxNs = 0;
+	for (int p = 0; p < count; p++) maxNs = std::max(maxNs, ns[p]);
+	// both tables live in one device buffer: [problems | blocks]
+	const size_t blocksAt = (probs.size() * sizeof(AssocProblem) + 15) & ~(size_t)15;
 
 	MfmaArgs A;
-	A.Hs = (const uint4*)Hs; A.Hd = (const uint4*)Hd; A.probs = W.probs.as<AssocProblem>(); A.blocks = W.blocks.as<AssocBlock>();
-	A.rowKey = rowKey; A.colKey = colKey; A.rowThr = rowThr; A.colThr = colThr;
+	A.Hs = (const uint4*)Hs; A.Hd = (const uint4*)Hd;
+	A.rowKey = rowKey; A.colKey = colKey; A.nrmS = nS; A.nrmD = nD; A.flags = flags;
 	A.cand = W.cand.as<AssocCand>(); A.counter = counters; A.cap = cap;
 #ifdef BHIP_EXPERIMENTS
 	{ const char* e = getenv("BHIP_ASSOC_ABLATE"); A.ablate = e ? atoi(e) : 0; }
 #endif
+	const unsigned gS = (unsigned)((rowsS + 16 * PREP_ROWS - 1) / (16 * PREP_ROWS)), gD = (unsigned)((maxDstRow + 16 * PREP_ROWS - 1) / (16 * PREP_ROWS));
+	const double prepRows = (double)(rowsS + (shared ? 0 : maxDstRow));
+
+	// The tables go into the page-locked staging block; k_assoc_init reads them from there.  The block is rewritten only after the launch
+	// that reads it has run: every complete call waits for an event recorded behind that launch (the flags read-back); a call that left
+	// early did not, and is waited for here.
+	buildBlocks();
+	const size_t tableBytes = (blocksAt + blocks.size() * sizeof(AssocBlock) + 15) & ~(size_t)15;
+	BHIP_TRY(W.probs.reserve(ctx, tableBytes));
+	if (W.tablesInFlight) { BHIP_HIP(ctx, hipStreamSynchronize(st)); W.tablesInFlight = false; }
+	if (tableBytes > W.tables.cap) BHIP_TRY(W.tables.reserve(ctx, tableBytes * 2));
+	memcpy(W.tables.p, probs.data(), probs.size() * sizeof(AssocProblem));
+	memcpy((char*)W.tables.p + blocksAt, blocks.data(), blocks.size() * sizeof(AssocBlock));
+	void* tablesDev = nullptr;   // the staging block as the device sees it
+	BHIP_HIP(ctx, hipHostGetDevicePointer(&tablesDev, W.tables.p, 0));
+	if (!W.flagsRead) BHIP_HIP(ctx, hipEventCreateWithFlags(&W.flagsRead.h, hipEventDisableTiming));
+	A.probs = W.probs.as<AssocProblem>();
+	A.blocks = (const AssocBlock*)((const char*)W.probs.p + blocksAt);
 	const unsigned nblocks = (unsigned)blocks.size();
-	{
-		ProfScope ps(ctx, "k_assoc_mfma_pass1", 0, flopsPerPass);
-		hipLaunchKernelGGL(k_assoc_mfma<1>, dim3(nblocks), dim3(256), 0, st, A);
+
+	// First run: the scale exponent of the previous call is assumed and the descriptors are read once.  Only when the norms read back at the
+	// end do not fit it is the whole path repeated with the measured exponent (k_assoc_norms, then k_assoc_half): a change of the inputs'
+	// magnitude by more than 4x between two calls on one context, which costs that call one extra run.
+	for (int run = 0; run < 2; run++) {
+		const bool hinted = run == 0;
+		const long long tabWords = hinted ? (long long)(tableBytes / 16) : 0;
+		W.tablesInFlight = true;
+		hipLaunchKernelGGL(k_assoc_init, dim3((unsigned)((std::max(nk, tabWords) + 255) / 256)), dim3(256), 0, st, rowKey, rowBest, rowArg, nk, colTotal, flags,
+						   hinted ? W.scaleHint : 0, (const uint4*)tablesDev, W.probs.as<uint4>(), tabWords);
+		if (hinted) {
+			ProfScope ps(ctx, "k_assoc_prep", prepRows * (64 * 8 + ROW_CHUNKS * 16));
+			hipLaunchKernelGGL(k_assoc_prep_hinted, dim3(gS), dim3(256), 0, st, dev_src, rowsS, W.scaleHint, nS, flags, Hs);
+			if (!shared) hipLaunchKernelGGL(k_assoc_prep_hinted, dim3(gD), dim3(256), 0, st, dev_dst, maxDstRow, W.scaleHint, nD, flags, Hd);
+		} else {
+			ProfScope ps(ctx, "k_assoc_prep", prepRows * (2 * 64 * 8 + ROW_CHUNKS * 16));
+			hipLaunchKernelGGL(k_assoc_norms, dim3(gS), dim3(256), 0, st, dev_src, rowsS, nS, flags);
+			if (!shared) hipLaunchKernelGGL(k_assoc_norms, dim3(gD), dim3(256), 0, st, dev_dst, maxDstRow, nD, flags);
+			hipLaunchKernelGGL(k_assoc_half, dim3(gS), dim3(256), 0, st, dev_src, rowsS, nS, flags, Hs);   // sets flags[3]
+			if (!shared) hipLaunchKernelGGL(k_assoc_half, dim3(gD), dim3(256), 0, st, dev_dst, maxDstRow, nD, flags, Hd);
+		}
+		{
+			ProfScope ps(ctx, "k_assoc_mfma_pass1", 0, flopsPerPass);
+			hipLaunchKernelGGL(k_assoc_mfma<1>, dim3(nblocks), dim3(256), 0, st, A);
+		}
+		{
+			ProfScope ps(ctx, "k_assoc_mfma_pass2", 0, flopsPerPass);
+			hipLaunchKernelGGL(k_assoc_mfma<2>, dim3(nblocks), dim3(256), 0, st, A);
+		}
+		{
+			ProfScope ps(ctx, "k_assoc_exact");
+			// about one listed pair per thread (the list length is only known on the device: 2.3 per row is typical, the grid-stride loop takes the rest)
+			const unsigned exactBlocks = (unsigned)std::min<long long>(16384, std::max<long long>(256, (3 * (rowTotal + colTotal) / 2 + 255) / 256));
+			hipLaunchKernelGGL(k_assoc_exact, dim3(exactBlocks), dim3(256), 0, st, dev_src, dev_dst, A.probs, A.cand, counters, cap, rowBest, colBest);
+			hipLaunchKernelGGL(k_assoc_argsel, dim3(exactBlocks), dim3(256), 0, st, A.probs, A.cand, counters, cap, rowBest, colBest, rowArg, colArg, colCnt);
+		}
+		// The result kernel goes out before the flags have come back, so the GPU does not wait for the host's answer: it reads the same
+		// flags and writes nothing for a run the host is about to reject (assocDegenerate on both sides).  The host waits for the
+		// read-back alone (the event behind it); the result kernel runs while the flags travel, and the caller's next work queues behind it.
+		BHIP_HIP(ctx, hipMemcpyAsync(ctx->hostScratch.p, flags, 16, hipMemcpyDeviceToHost, st));
+		BHIP_HIP(ctx, hipEventRecord(W.flagsRead, st));
+		hipLaunchKernelGGL(k_assoc_resolve, dim3((maxNs + 255) / 256, count), dim3(256), 0, st, A.probs, maxErr, backwards, rowBest, rowArg, colArg, colCnt,
+						   flags, cap, dev_pairs, dev_fit);
+		BHIP_HIP(ctx, hipEventSynchronize(W.flagsRead));
+		W.tablesInFlight = false;
+		BHIP_HIP(ctx, hipGetLastError());
+		const int* hf = ctx->hostScratch.as<int>();
+		if (hf[0] != 0) return BHIP_OK;  // non-finite values: *usedMfma stays 0, and the hint stays what it was
+		float maxRaw;
+		memcpy(&maxRaw, &hf[1], 4);
+		if (maxRaw > 0.0f) W.scaleHint = scaleExp(maxRaw);   // all-zero descriptors say nothing about the next call's
+		if (!scaleHolds(maxRaw, hf[3])) continue;            // the hint did not fit (the measured exponent always does)
+		if (hf[2] > cap) return BHIP_OK;                     // candidate list overflow: exact path
+		*usedMfma = 1;
+		return BHIP_OK;
 	}
-	int maxN = 0;
-	for (int p = 0; p < count; p++) maxN = std::max(maxN, ns[p] + nd[p]);
-	hipLaunchKernelGGL(k_assoc_thresholds, dim3((maxN + 255) / 256, count), dim3(256), 0, st, A.probs, count, nS, nD, rowKey, colKey, flags, rowThr, colThr);
-	{
-		ProfScope ps(ctx, "k_assoc_mfma_pass2", 0, flopsPerPass);
-		hipLaunchKernelGGL(k_assoc_mfma<2>, dim3(nblocks), dim3(256), 0, st, A);
-	}
-	{
-		ProfScope ps(ctx, "k_assoc_exact");
-		// about one listed pair per thread (the list length is only known on the device: 2.3 per row is typical, the grid-stride loop takes the rest)
-		const unsigned exactBlocks = (unsigned)std::min<long long>(16384, std::max<long long>(256, (3 * (rowTotal + colTotal) / 2 + 255) / 256));
-		hipLaunchKernelGGL(k_assoc_exact, dim3(exactBlocks), dim3(256), 0, st, dev_src, dev_dst, A.probs, A.cand, counters, cap, rowBest, colBest);
-		hipLaunchKernelGGL(k_assoc_argsel, dim3(exactBlocks), dim3(256), 0, st, A.probs, A.cand, counters, cap, rowBest, colBest, rowArg, colArg, colCnt);
-	}
-	// degenerate inputs? (one small read-back; the result kernels below are only trusted when the flags are clean)
-	BHIP_HIP(ctx, hipMemcpyAsync(ctx->hostScratch.p, flags, 16, hipMemcpyDeviceToHost, st));
-	BHIP_HIP(ctx, hipStreamSynchronize(st));
-	const int* hf = ctx->hostScratch.as<int>();
-	if (hf[0] != 0 || hf[2] > cap) return BHIP_OK;  // *usedMfma stays 0
-	int maxNs = 0;
-	for (int p = 0; p < count; p++) maxNs = std::max(maxNs, ns[p]);
-	hipLaunchKernelGGL(k_assoc_resolve, dim3((maxNs + 255) / 256, count), dim3(256), 0, st, A.probs, maxErr, backwards, rowBest, rowArg, colArg, colCnt,
-					   dev_pairs, dev_fit);
-	BHIP_HIP(ctx, hipGetLastError());
-	*usedMfma = 1;
 	return BHIP_OK;
 }

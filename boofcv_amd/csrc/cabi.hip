@@ -69,6 +69,7 @@ struct FhDetector {
 	bool nBest() const { return cfg.maxFeaturesPerScale > 0; }   // SelectNBestFeatures between the NMS and the scale-space test
 	std::vector<int> counts;   // per image, host
 	long long total = 0;
+	HipEvent countsRead;       // recorded behind the count read-back: the host waits for it alone, not for the ranking launched after it
 
 	static bool unfusedOnly() { return bhip_env_flag("BHIP_DETECT_UNFUSED"); }   // parity cross-check of the two detector paths
 	int makePlan(bhip_ctx* ctx, int width, int height) {
@@ -275,21 +276,31 @@ struct FhDetector {
 			}
 			BHIP_TRY(bhip_launch_word_prefix(ctx, bitmap.as<unsigned int>(), bitmapWords, batch, prefix.as<unsigned int>(), count.as<int>() + batch));
 			counts.resize(batch);
-			if ((size_t)batch * 4 <= (1u << 20)) {
-				BHIP_HIP(ctx, hipMemcpyAsync(ctx->hostScratch.p, count.p, (size_t)batch * 4, hipMemcpyDeviceToHost, ctx->stream));
-				BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-				memcpy(counts.data(), ctx->hostScratch.p, (size_t)batch * 4);
+			const bool viaScratch = (size_t)batch * 4 <= (1u << 20);
+			BHIP_HIP(ctx, hipMemcpyAsync(viaScratch ? ctx->hostScratch.p : (void*)counts.data(), count.p, (size_t)batch * 4, hipMemcpyDeviceToHost, ctx->stream));
+			if (!nBest()) {
+				// The ranking needs device data only: it is launched before the host has the counts and runs while they travel, so the GPU
+				// does not idle through the round trip.  The host waits for the copy alone (an event behind it), not for the ranking.  After
+				// an overflow the kernel has ranked an incomplete list (it keeps inside `sorted`) and the loop runs again.
+				// (N-best: the ranking and the selection both follow the read-back, as they always did.)
+				if (!countsRead) BHIP_HIP(ctx, hipEventCreateWithFlags(&countsRead.h, hipEventDisableTiming));
+				BHIP_HIP(ctx, hipEventRecord(countsRead, ctx->stream));
+				BHIP_TRY(bhip_launch_rank_scatter(ctx, bitmap.as<unsigned int>(), bitmapWords, prefix.as<unsigned int>(), cand.as<KeyPoint>(), count.as<int>(),
+												  cap, batch, sorted.as<KeyPoint>()));
+				BHIP_HIP(ctx, hipEventSynchronize(countsRead));
 			} else {
-				BHIP_HIP(ctx, hipMemcpyAsync(counts.data(), count.p, (size_t)batch * 4, hipMemcpyDeviceToHost, ctx->stream));
 				BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
 			}
+			if (viaScratch) memcpy(counts.data(), ctx->hostScratch.p, (size_t)batch * 4);
 			int maxCount = 0;
 			total = 0;
 			for (int c : counts) { maxCount = std::max(maxCount, c); total += c; }
 			if (maxCount <= cap) {
-				BHIP_TRY(bhip_launch_rank_scatter(ctx, bitmap.as<unsigned int>(), bitmapWords, prefix.as<unsigned int>(), cand.as<KeyPoint>(), count.as<int>(),
-												  cap, batch, sorted.as<KeyPoint>()));
-				if (nBest()) BHIP_TRY(selectNBest(ctx));
+				if (nBest()) {
+					BHIP_TRY(bhip_launch_rank_scatter(ctx, bitmap.as<unsigned int>(), bitmapWords, prefix.as<unsigned int>(), cand.as<KeyPoint>(), count.as<int>(),
+													  cap, batch, sorted.as<KeyPoint>()));
+					BHIP_TRY(selectNBest(ctx));
+				}
 				return BHIP_OK;
 			}
 			// candidate list overflowed: grow and run the detector again

@@ -135,7 +135,11 @@ inline int PinnedBuf::reserve(bhip_ctx* ctx, size_t bytes) {
 
 // work buffers of the MFMA association path (assoc_mfma.hip)
 struct AssocMfmaWork {
-	DevBuf Fs, Fd, nrmS, nrmD, probs, blocks, keys, thr, best, args, cand, flags;
+	DevBuf Fs, Fd, nrmS, nrmD, probs, keys, best, args, cand, flags;   // probs: the problem table, then the block table
+	PinnedBuf tables;            // page-locked staging copy of the problem and block tables; k_assoc_init reads it through its device address
+	bool tablesInFlight = false; // a launch that reads `tables` has been issued and not been waited for since
+	HipEvent flagsRead;          // recorded behind the flags read-back: the host waits for it alone, not for the result kernel after it
+	int scaleHint = 1;           // q_h: the scale exponent the one-pass prep assumes; 1 = largest squared norm in [1, 4) (unit vectors)
 };
 
 // ---------------- image view passed to kernels ----------------

@@ -418,7 +418,9 @@ __global__ __launch_bounds__(256) void k_rank_scatter(const unsigned int* __rest
 	const unsigned int word = kp.key >> 5, bit = kp.key & 31;
 	const unsigned int below = bitmap[(long long)img * words + word] & ((1u << bit) - 1u);
 	const unsigned int rank = prefix[(long long)img * words + word] + __popc(below);
-	sorted[(long long)img * cap + rank] = kp;
+	// The launch precedes the host's look at the counts.  When the list overflowed, the bitmap holds maxima that were never listed and a
+	// rank can lie past the image's slots; that run's output is discarded and the detector runs again with a longer list.
+	if (rank < (unsigned int)cap) sorted[(long long)img * cap + rank] = kp;
 }
 
 int bhip_launch_rank_scatter(bhip_ctx* ctx, const unsigned int* bitmap, int bitmapWords, unsigned int* wordPrefix, const KeyPoint* cand,
