@@ -24,6 +24,7 @@ struct CtxScratch {
 	DevBuf in0, in1, out0, out1, tmp0, tmp1;                                 // staging
 	DevBuf work, assocCol, nmsBitmap, nmsPrefix, nmsPos, ipTmp, ipKernel, fast, disparity, distortMap, templ, flow, threshold;   // device side
 	long long flowPixels = 0;   // pixels of the last bhip_flow_klt_* call (bhip_flow_klt_stats)
+	DevBuf flowHs;                  // cabi_flow.hip, Horn-Schunck: [derivatives when the caller keeps none | the two ping-pong flows]
 	DevBuf binary, label;           // cabi_binary.hip: the two ping-pong images of a long erode / dilate run; parent[] and row counts of the labelling
 	DevBuf binaryTable;             // the host forms' relabel / labelToBinary lookup table
 	DevBuf hough, houghTable;       // cabi_line.hip: vote counts / sort records of the Hough transforms; the sine / cosine and mean-shift weight tables

@@ -1,5 +1,6 @@
 // C ABI, dense KLT optical flow (kernels: flow.hip, the wave-per-pixel track kernel in klt.hip): DenseOpticalFlow.process of
-// FactoryDenseOpticalFlow.flowKlt.  Rules, deviations and limits: bhip_flow_klt_dev_f32 in include/boofhip.h.
+// FactoryDenseOpticalFlow.flowKlt.  Rules, deviations and limits: bhip_flow_klt_dev_f32 in include/boofhip.h.  Below it, Horn-Schunck
+// (FactoryDenseOpticalFlow.hornSchunck; kernels: hornschunck.hip).
 #include "cabi.h"
 
 namespace {
@@ -126,7 +127,106 @@ static int flowHost(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const in
 	return bhip_ctx_synchronize(ctx);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Horn-Schunck dense optical flow (kernels: hornschunck.hip): HornSchunck.process of FactoryDenseOpticalFlow.hornSchunck.  Rules, deviations and
+// limits: bhip_flow_hs_dev_f32 in include/boofhip.h.
+// ---------------------------------------------------------------------------------------------------------------
+// itersPerLaunch 0: the depth that scripts/bench_hornschunck.py measures as the fastest on 1080p pairs
+#define HS_AUTO_DEPTH BHIP_FLOW_HS_MAX_FUSED
+
+// the argument checks both forms share, before anything is staged or launched (ctx has been checked)
+static int hsCheck(bhip_ctx* ctx, int width, int height, int batch, int itersPerLaunch) {
+	if (width <= 0 || height <= 0 || batch <= 0) return bhip_fail(ctx, BHIP_ERR_INVALID, "Horn-Schunck: bad arguments");
+	if (itersPerLaunch < 0 || itersPerLaunch > BHIP_FLOW_HS_MAX_FUSED) return bhip_fail(ctx, BHIP_ERR_INVALID, "Horn-Schunck: itersPerLaunch must be 0 .. 8");
+	if (batch > 65535) return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "Horn-Schunck on the GPU: at most 65535 pairs per call");
+	if (width > (1 << 20) || height > (1 << 20) || (long long)width * height > (1LL << 28))
+		return bhip_fail(ctx, BHIP_ERR_UNSUPPORTED, "Horn-Schunck on the GPU: width, height <= 1048576 and width * height <= 2^28");
+	return BHIP_OK;
+}
+
+// HornSchunck.process :92-110 on device pairs: the three derivatives, then findFlow as launches of up to `depth` iterations that alternate
+// between the two scratch flows; the first starts from the zero flow (no buffer is read) and the last writes `flow`
+template <class T>
+static int hsDevice(bhip_ctx* ctx, float alpha, int numIterations, DevImg<const T> src, DevImg<const T> dst, DevImg<float> flow, float* deriv, int itersPerLaunch) {
+	CtxScratch* sc = scratchOf(ctx);
+	const int depth = itersPerLaunch ? itersPerLaunch : HS_AUTO_DEPTH;
+	int left = std::max(numIterations, 0);
+	const size_t px = (size_t)src.width * src.height * src.batch;
+	const size_t oFlow = deriv ? 0 : align256(px * 3 * sizeof(float)), flowBytes = align256(px * 2 * sizeof(float));
+	BHIP_TRY(sc->flowHs.reserve(ctx, oFlow + (left > depth ? 2 * flowBytes : 0)));
+	char* base = (char*)sc->flowHs.p;
+	if (!deriv) deriv = (float*)base;
+	float* tmp[2] = {(float*)(base + oFlow), (float*)(base + oFlow + flowBytes)};
+	BHIP_TRY(bhip_launch_hs_derivatives<T>(ctx, src, dst, deriv));
+	const float alpha2 = alpha * alpha;   // HornSchunck.java:68
+	const float* in = nullptr;
+	int which = 0;
+	do {
+		const int step = std::min(left, depth);
+		left -= step;
+		const DevImg<float> out = left == 0 ? flow : DevImg<float>{tmp[which], (long long)2 * src.width * src.height, 2 * src.width, src.width, src.height, src.batch};
+		BHIP_TRY(bhip_launch_hs_iterate(ctx, deriv, in, out, alpha2, step));
+		in = out.data;
+		which ^= 1;
+	} while (left > 0);
+	return BHIP_OK;
+}
+
+template <class T>
+static int hsDev(bhip_ctx* ctx, float alpha, int numIterations, const T* dev_src, long long sImageStride, int sStride, const T* dev_dst, long long dImageStride,
+				 int dStride, int width, int height, int batch, float* dev_flow, long long fImageStride, int fStride, float* dev_deriv, int itersPerLaunch) {
+	CHECK_CTX(ctx);
+	BHIP_TRY(hsCheck(ctx, width, height, batch, itersPerLaunch));
+	const DevImg<const T> src{dev_src, sImageStride, sStride, width, height, batch}, dst{dev_dst, dImageStride, dStride, width, height, batch};
+	CHECK_IMG(ctx, src);
+	CHECK_IMG(ctx, dst);
+	if (!dev_flow || fStride < 2 * width) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad flow image (null or stride < 2 * width)");
+	return hsDevice<T>(ctx, alpha, numIterations, src, dst, {dev_flow, fImageStride, fStride, width, height, batch}, dev_deriv, itersPerLaunch);
+}
+
+template <class T>
+static int hsHost(bhip_ctx* ctx, float alpha, int numIterations, const T* src, int sStart, int sStride, const T* dst, int dStart, int dStride, int width, int height,
+				  float* flow, int fStart, int fStride) {
+	CHECK_CTX(ctx);
+	BHIP_TRY(hsCheck(ctx, width, height, 1, 0));
+	const HostImg<const T> hs{src, sStart, sStride, width, height}, hd{dst, dStart, dStride, width, height};
+	CHECK_IMG(ctx, hs);
+	CHECK_IMG(ctx, hd);
+	if (!flow || fStride < 2 * width) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad flow image (null or stride < 2 * width)");
+	const HostImg<float> hf{flow, fStart, fStride, 2 * width, height};   // a row of (x, y) pairs
+	CtxScratch* sc = scratchOf(ctx);
+	DevImg<T> ds, dd;
+	DevImg<float> df;
+	BHIP_TRY(stageIn(ctx, sc->in0, hs, width, ds));
+	BHIP_TRY(stageIn(ctx, sc->in1, hd, width, dd));
+	BHIP_TRY(stageIn(ctx, sc->out0, hf, 2 * width, df, false));
+	BHIP_TRY(hsDevice<T>(ctx, alpha, numIterations, DevImg<const T>(ds), DevImg<const T>(dd), {df.data, df.imageStride, df.stride, width, height, 1}, nullptr, 0));
+	BHIP_TRY(stageOut(ctx, hf, df));
+	return bhip_ctx_synchronize(ctx);
+}
+
 extern "C" {
+
+int bhip_flow_hs_dev_f32(bhip_ctx* ctx, float alpha, int numIterations, const float* dev_src, long long sImageStride, int sStride, const float* dev_dst,
+						 long long dImageStride, int dStride, int width, int height, int batch, float* dev_flow, long long fImageStride, int fStride,
+						 float* dev_deriv, int itersPerLaunch) {
+	return hsDev<float>(ctx, alpha, numIterations, dev_src, sImageStride, sStride, dev_dst, dImageStride, dStride, width, height, batch, dev_flow, fImageStride, fStride,
+						dev_deriv, itersPerLaunch);
+}
+int bhip_flow_hs_dev_u8(bhip_ctx* ctx, float alpha, int numIterations, const uint8_t* dev_src, long long sImageStride, int sStride, const uint8_t* dev_dst,
+						long long dImageStride, int dStride, int width, int height, int batch, float* dev_flow, long long fImageStride, int fStride,
+						float* dev_deriv, int itersPerLaunch) {
+	return hsDev<uint8_t>(ctx, alpha, numIterations, dev_src, sImageStride, sStride, dev_dst, dImageStride, dStride, width, height, batch, dev_flow, fImageStride,
+						  fStride, dev_deriv, itersPerLaunch);
+}
+int bhip_flow_hs_f32(bhip_ctx* ctx, float alpha, int numIterations, const float* src, int sStart, int sStride, const float* dst, int dStart, int dStride,
+					 int width, int height, float* flow, int fStart, int fStride) {
+	return hsHost<float>(ctx, alpha, numIterations, src, sStart, sStride, dst, dStart, dStride, width, height, flow, fStart, fStride);
+}
+int bhip_flow_hs_u8(bhip_ctx* ctx, float alpha, int numIterations, const uint8_t* src, int sStart, int sStride, const uint8_t* dst, int dStart, int dStride,
+					int width, int height, float* flow, int fStart, int fStride) {
+	return hsHost<uint8_t>(ctx, alpha, numIterations, src, sStart, sStride, dst, dStart, dStride, width, height, flow, fStart, fStride);
+}
 
 int bhip_flow_klt_dev_f32(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const int* scales, int numLayers, const float* dev_src, long long sImageStride,
 						  int sStride, const float* dev_dst, long long dImageStride, int dStride, int width, int height, int batch, float* dev_flow,

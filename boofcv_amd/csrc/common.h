@@ -587,6 +587,17 @@ int bhip_launch_flow_track_lane(bhip_ctx* ctx, KltPyrU8 P, const uint8_t* dst, i
 // checkNeighbors as an order-free reduction: flow[b][y][x] = (x, y) floats at flow.data + b * imageStride + y * stride + 2 * x (strides in floats)
 int bhip_launch_flow_reduce(bhip_ctx* ctx, const FlowRec* rec, int r, DevImg<float> flow);
 
+// ---------------- Horn-Schunck dense optical flow (hornschunck.hip) ----------------
+#define BHIP_HS_TILE_W BHIP_FLOW_HS_TILE_WIDTH
+#define BHIP_HS_TILE_H BHIP_FLOW_HS_TILE_HEIGHT
+// computeDerivX / Y / T of HornSchunck_F32 (T = float) or HornSchunck_U8 (uint8_t; the GrayS16 values as floats) on every pair of a batch:
+// deriv is dense [batch][3][height][width]
+template <class T>
+int bhip_launch_hs_derivatives(bhip_ctx* ctx, DevImg<const T> src, DevImg<const T> dst, float* deriv);
+// n iterations (0 .. BHIP_FLOW_HS_MAX_FUSED) of findFlow in one launch.  in: the flow before, dense [batch][height][width] (x, y) pairs, nullptr = the
+// zero flow; out: (x, y) of pixel (x, y) at out.data + b * imageStride + y * stride + 2 * x (out.width in pixels, strides in floats); in != out
+int bhip_launch_hs_iterate(bhip_ctx* ctx, const float* deriv, const float* in, DevImg<float> out, float alpha2, int n);
+
 // ---------------- thresholding, FactoryThresholdBinary, and the GrayU8 blurs (threshold.hip) ----------------
 #define BHIP_THRESH_FUSED_MAX_RADIUS 16   // blur radius up to which a GrayU8 local threshold (and blur) runs as one launch out of LDS
 // the compare of a pixel with its threshold: px <= thr (down), px > thr (up: fixed, local, min/max), !(px <= thr) (up: block mean, Otsu; differs on NaN)

@@ -657,6 +657,34 @@ class DeviceImageOps:
         _check(self.ctx, self.L.bhip_flow_klt_stats(self.ctx._h, C.byref(n), C.byref(it)))
         return n.value, it.value
 
+    def denseFlowHornSchunck(self, prev, curr, alpha=20.0, numIterations=1000, out=None, derivs=None, itersPerLaunch=0):
+        """DenseOpticalFlow.process of FactoryDenseOpticalFlow.hornSchunck on float32 or uint8 pairs [B,H,W] -> the flow [B,H,W,2] float32.
+        `out`: any image / row stride with (x, y) adjacent, written in place.  derivs: None, True (allocated) or a contiguous float32 [B,3,H,W]
+        tensor that receives derivX, derivY, derivT (the GrayS16 values of uint8 pairs as floats); returned second when given.  itersPerLaunch:
+        0 = the library's choice, 1 .. BHIP_FLOW_HS_MAX_FUSED forces how many iterations one launch fuses (same results)."""
+        u8 = prev.dtype == torch.uint8
+        dt = torch.uint8 if u8 else torch.float32
+        pp, pis, prs, W, H, B = _geom(prev, dt)
+        cp, cis, crs, W2, H2, B2 = _geom(curr, dt)
+        if (W, H, B) != (W2, H2, B2):
+            raise IllegalArgumentException("Image shapes do not match")
+        if out is None:
+            out = torch.empty((B, H, W, 2), dtype=torch.float32, device=prev.device)
+        if out.dim() != 4 or out.dtype != torch.float32 or not out.is_cuda or tuple(out.shape) != (B, H, W, 2):
+            raise IllegalArgumentException("the flow must be a [%d,%d,%d,2] float32 CUDA tensor" % (B, H, W))
+        if out.stride(3) != 1 or out.stride(2) != 2 or (H > 1 and out.stride(1) < 2 * W) or (B > 1 and out.stride(0) < 0):
+            raise IllegalArgumentException("the flow's (x, y) pairs and pixels of a row must be adjacent")
+        ois = out.stride(0) if B > 1 else H * out.stride(1)
+        ors = out.stride(1) if H > 1 else max(2 * W, out.stride(1))
+        if derivs is True:
+            derivs = torch.empty((B, 3, H, W), dtype=torch.float32, device=prev.device)
+        if derivs is not None and (derivs.dtype != torch.float32 or tuple(derivs.shape) != (B, 3, H, W) or not derivs.is_contiguous() or not derivs.is_cuda):
+            raise IllegalArgumentException("derivs must be a contiguous [%d,3,%d,%d] float32 CUDA tensor" % (B, H, W))
+        fn = self.L.bhip_flow_hs_dev_u8 if u8 else self.L.bhip_flow_hs_dev_f32
+        _check(self.ctx, fn(self.ctx._h, float(alpha), int(numIterations), pp, pis, prs, cp, cis, crs, W, H, B, C.c_void_p(out.data_ptr()), ois, ors,
+                            C.c_void_p(derivs.data_ptr()) if derivs is not None else None, int(itersPerLaunch)))
+        return out if derivs is None else (out, derivs)
+
     def distortBuildMap(self, model, coeff, dw, dh, out=None):
         """bhip_distort_build_map: the [dh,dw,2] float32 map of an affine (model 1, six coefficients) or homography (model 2, nine) model"""
         coeff = np.ascontiguousarray(coeff, np.float32).reshape(-1)

@@ -1084,6 +1084,50 @@ int bhip_flow_klt_u8(bhip_ctx* ctx, const bhip_klt_cfg* cfg, int radius, const i
 /* pixels tracked and Lucas-Kanade iterations run by the last bhip_flow_klt_* call on this context (synchronises) */
 int bhip_flow_klt_stats(bhip_ctx* ctx, long long* pixels, long long* iterations);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Horn-Schunck dense optical flow: DenseOpticalFlow.process(source, destination, flow) of FactoryDenseOpticalFlow.hornSchunck(ConfigHornSchunck,
+ * GrayF32 | GrayU8) (F:factory/flow/FactoryDenseOpticalFlow.java:122-138): HornSchunck_to_DenseOpticalFlow over HornSchunck_F32 / HornSchunck_U8
+ * (F:alg/flow/HornSchunck.java:92-191, HornSchunck_F32.java:36-175, HornSchunck_U8.java:38-177).  process computes derivX, derivY, derivT of the
+ * pair (GrayU8: in int, GrayS16) and runs numIterations Jacobi iterations from the zero flow (resetOutput is true and has no setter): with w =
+ * width-1, h = height-1, A = source, B = destination,
+ *   derivX  x < w, y < h: 0.25f*(d0+d1+d2+d3), the x forward differences of A row y, A row y+1, B row y, B row y+1; y == h: 0.5f*(d0+d1) of A, B; x == w: 0
+ *   derivY  x < w, y < h: 0.25f*(d0+d1+d2+d3), the y forward differences of A column x, A column x+1, B column x, B column x+1; x == w, y < h:
+ *           0.5f*(d0+d1) of A, B; y == h: 0
+ *   derivT  0.25f*(d0+d1+d2+d3), dk = B - A at (x,y), (x+1,y), (x,y+1), (x+1,y+1) with the coordinates clamped to the image
+ *   GrayU8  the same taps in int, (..)/4 and (..)/2 truncating toward zero
+ *   every iteration, for every pixel from the flow of the iteration before (x and y clamped to the image, getExtend):
+ *           u = 0.1666667f*(f0+f1+f2+f3) + 0.08333333f*(f4+f5+f6+f7) over left, right, up, down, up-left, up-right, down-left, down-right, v alike;
+ *           r = (dx*u + dy*v + dt)/(alpha2 + dx*dx + dy*dy), alpha2 = alpha*alpha in float; flow = (u - dx*r, v - dy*r)
+ * IEEE fp32, nothing contracted, the division correctly rounded: every float equals the single-threaded Java result bit for bit (alpha = 0 on a
+ * flat patch gives 0/0 = NaN, which spreads one pixel per iteration, as in Java).  numIterations <= 0 gives the zero flow, as the Java loop does.
+ *   flow    pixel (x, y) of pair b is the two floats (x, y) at dev_flow[b*fImageStride + y*fStride + 2*x] (strides in floats, fStride >= 2*width)
+ *   deriv   NULL, or dense [batch][3][height][width] float32 that receives derivX, derivY, derivT (the GrayS16 values of GrayU8 pairs as floats)
+ *   itersPerLaunch  iterations one kernel launch runs on a BHIP_FLOW_HS_TILE_WIDTH x BHIP_FLOW_HS_TILE_HEIGHT tile out of LDS ("Horn-Schunck dense
+ *           optical flow"): 0 = the library's choice, 1 .. BHIP_FLOW_HS_MAX_FUSED forces the depth; the results are the same bit for bit
+ * Validation, BHIP_ERR_INVALID and nothing is written: non-positive sizes, strides smaller than a row, null images, itersPerLaunch outside
+ * 0 .. BHIP_FLOW_HS_MAX_FUSED.
+ * Deviations: derivY(w, h) is never written by the reference and keeps what the reused array held: it is 0 here, the value of a freshly
+ * constructed instance; HornSchunck_F32.computeDerivT :114 indexes image1 with image2.stride in its fourth tap: image1's pixel (x+1, y+1) is read
+ * here whatever the two strides are; the flow has the size of the images (the Java indexes past a smaller one; the mirrors refuse another size).
+ * Limits, BHIP_ERR_UNSUPPORTED and nothing is written: batch > 65535, width or height > 1048576, width * height > 2^28.
+ * The _dev forms do not synchronise; scratch (the derivatives when deriv is NULL, two flow images when there is more than one launch) belongs to
+ * the context. */
+#define BHIP_FLOW_HS_MAX_FUSED 8
+#define BHIP_FLOW_HS_TILE_WIDTH 112
+#define BHIP_FLOW_HS_TILE_HEIGHT 48
+int bhip_flow_hs_dev_f32(bhip_ctx* ctx, float alpha, int numIterations, const float* dev_src, long long sImageStride, int sStride, const float* dev_dst,
+						 long long dImageStride, int dStride, int width, int height, int batch, float* dev_flow, long long fImageStride, int fStride,
+						 float* dev_deriv, int itersPerLaunch);
+int bhip_flow_hs_dev_u8(bhip_ctx* ctx, float alpha, int numIterations, const uint8_t* dev_src, long long sImageStride, int sStride, const uint8_t* dev_dst,
+						long long dImageStride, int dStride, int width, int height, int batch, float* dev_flow, long long fImageStride, int fStride,
+						float* dev_deriv, int itersPerLaunch);
+/* the same on one pair of host images: pixel (x, y) at src[sStart + y*sStride + x], its flow at flow[fStart + y*fStride + 2*x]; staged, run through the
+ * _dev form (itersPerLaunch 0, no deriv), synchronised */
+int bhip_flow_hs_f32(bhip_ctx* ctx, float alpha, int numIterations, const float* src, int sStart, int sStride, const float* dst, int dStart, int dStride,
+					 int width, int height, float* flow, int fStart, int fStride);
+int bhip_flow_hs_u8(bhip_ctx* ctx, float alpha, int numIterations, const uint8_t* src, int sStart, int sStride, const uint8_t* dst, int dStart, int dStride,
+					int width, int height, float* flow, int fStart, int fStride);
+
 /* ---- thresholding: FactoryThresholdBinary.threshold(ConfigThreshold, GrayU8 | GrayF32) -> InputToBinary.process (threshold.hip),
  *      I:factory/filter/binary/FactoryThresholdBinary.java:318-372; the provider seam is I:factory/filter/binary/BOverrideFactoryThresholdBinary.java.
  *      The output is the GrayU8 0/1 image, bit for bit the single-threaded Java result.
