@@ -1,12 +1,14 @@
 """Builds boofcv_amd/libboofhip.so (hand-written HIP kernels + the C ABI) for gfx950 with hipcc.
 
-hipcc cross-compiles without a GPU.  -ffp-contract=off keeps Java's "no fused multiply-add" arithmetic in every kernel;
+hipcc cross-compiles without a GPU.  Every csrc/*.hip is one object; at most max_jobs() compilers run at once, and the link refuses
+undefined symbols.  -ffp-contract=off keeps Java's "no fused multiply-add" arithmetic in every kernel;
 fp32 divide/sqrt stay correctly rounded.
 """
 import glob
 import os
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
@@ -29,6 +31,14 @@ def sources():
 def common_deps():
     """What every object depends on besides its own source."""
     return glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "..", "include", "boofhip.h"), os.path.abspath(__file__)]
+
+
+def max_jobs():
+    """Compilers run at once: 16, fewer where MAX_JOBS or the CPUs this process may use are fewer."""
+    n = min(16, len(os.sched_getaffinity(0)))
+    if os.environ.get("MAX_JOBS"):
+        n = min(n, int(os.environ["MAX_JOBS"]))
+    return max(1, n)
 
 
 def needs_build(lib=LIB):
@@ -57,7 +67,7 @@ def build(force=False, verbose=False, experiments=False):
     objs = []
     objdir = os.path.join(HERE, ("build_exp_" + os.environ.get("BHIP_EXP_TAG", "variant")) if extra else "build_exp" if experiments else "build")
     os.makedirs(objdir, exist_ok=True)
-    procs = []
+    cmds = []
     newest = max(os.path.getmtime(d) for d in common_deps())
     for src in sources():
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
@@ -68,16 +78,26 @@ def build(force=False, verbose=False, experiments=False):
         if src.endswith(".cpp"):
             cmd.insert(1, "-x")
             cmd.insert(2, "hip")
+        cmds.append((src, cmd))
+    # the instantiation units (a few lines of source, the longest compiles) first, then the largest sources: a long compile never starts last
+    cmds.sort(key=lambda sc: (not os.path.basename(sc[0]).startswith("background_gmm_"), -os.path.getsize(sc[0])))
+
+    def compile_one(sc):
         if verbose:
-            print(" ".join(cmd), file=sys.stderr)
-        procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
-    for src, p in procs:
-        out, _ = p.communicate()
-        if p.returncode != 0:
-            raise RuntimeError("hipcc failed on %s:\n%s" % (src, out.decode(errors="replace")))
-        if verbose and out:
-            print(out.decode(errors="replace"), file=sys.stderr)
-    cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + objs
+            print(" ".join(sc[1]), file=sys.stderr)
+        return subprocess.run(sc[1], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+
+    pool = ThreadPoolExecutor(max_jobs())
+    try:
+        for (src, _), p in zip(cmds, pool.map(compile_one, cmds)):
+            if p.returncode != 0:
+                raise RuntimeError("hipcc failed on %s:\n%s" % (src, p.stdout.decode(errors="replace")))
+            if verbose and p.stdout:
+                print(p.stdout.decode(errors="replace"), file=sys.stderr)
+    finally:
+        pool.shutdown(cancel_futures=True)   # after a failure: start no further compiler
+    # -z defs: an instantiation that no unit provides fails the link, not the first call
+    cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-Wl,-z,defs", "-o", lib] + objs
     subprocess.check_call(cmd)
     return lib
 

@@ -1,0 +1,9 @@
+// GMM background kernels (update and segment): GrayU8 frames, 1 to 6 Gaussians.
+#include "background_dev.h"
+
+BG_GMM_LAUNCH(uint8_t, 1, 1, true);
+BG_GMM_LAUNCH(uint8_t, 1, 2, true);
+BG_GMM_LAUNCH(uint8_t, 1, 3, true);
+BG_GMM_LAUNCH(uint8_t, 1, 4, true);
+BG_GMM_LAUNCH(uint8_t, 1, 5, true);
+BG_GMM_LAUNCH(uint8_t, 1, 6, true);

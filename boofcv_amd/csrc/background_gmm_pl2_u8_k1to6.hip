@@ -1,0 +1,9 @@
+// GMM background kernels (update and segment): Planar frames of two bands, uint8_t pixels, 1 to 6 Gaussians.
+#include "background_dev.h"
+
+BG_GMM_LAUNCH(uint8_t, 2, 1, false);
+BG_GMM_LAUNCH(uint8_t, 2, 2, false);
+BG_GMM_LAUNCH(uint8_t, 2, 3, false);
+BG_GMM_LAUNCH(uint8_t, 2, 4, false);
+BG_GMM_LAUNCH(uint8_t, 2, 5, false);
+BG_GMM_LAUNCH(uint8_t, 2, 6, false);

@@ -1,6 +1,6 @@
 // ---------------------------------------------------------------------------------------------------------------
 // boofcv-ip front end.  Most operations have a host-buffer export (the caller's image view) and a device-batched _dev export (BASELINE
-// config 5: pyramid -> gradient -> NMS -> SURF on a 4K stream without leaving HBM).  Both run one implementation -- an ip.hip launcher or
+// config 5: pyramid -> gradient -> NMS -> SURF on a 4K stream without leaving HBM).  Both run one implementation -- a launcher of conv.hip, pyramid.hip, gradient.hip, corner.hip or brief.hip, or
 // an xxxImpl around several -- on DevImg views of device images, asynchronous on the ctx stream.  The _dev export wraps the caller's
 // pointers into views and calls it after its argument checks.  The host export checks its HostImg views, stages them (stageIn / hostInOut:
 // rows pitch4(width) apart where the tiled kernels apply, dense otherwise), calls it with batch 1, downloads and synchronizes; when the
@@ -47,7 +47,7 @@ int cornerImpl(bhip_ctx* ctx, bool weighted, int kind, int radius, float kappa, 
 template int cornerImpl<float>(bhip_ctx*, bool, int, int, float, DevImg<const float>, DevImg<const float>, DevImg<float>);
 template int cornerImpl<int16_t>(bhip_ctx*, bool, int, int, float, DevImg<const int16_t>, DevImg<const int16_t>, DevImg<float>);
 
-// every sample point the pairs use lies within [-radius, radius]^2: the LDS-patch BRIEF kernel may be used (ip.hip, k_brief_patch)
+// every sample point the pairs use lies within [-radius, radius]^2: the LDS-patch BRIEF kernel may be used (brief.hip, k_brief_patch)
 bool briefPatchOk(const int32_t* samplePoints, int nSamples, int radius) {
 	for (int i = 0; i < 2 * nSamples; i++)
 		if (samplePoints[i] < -radius || samplePoints[i] > radius) return false;

@@ -341,7 +341,8 @@ int bhip_launch_detect_fused(bhip_ctx* ctx, DevImg<const T> ii, int skip, int nl
 							 const int* midLevels, int radius, float threshold, unsigned int* bitmap, int bitmapWords, KeyPoint* cand, int* candCount,
 							 int cap, const FusedExport* exp);
 
-// ---------------- boofcv-ip front end (ip.hip) ----------------
+// ---------------- boofcv-ip front end (conv.hip, pyramid.hip, gradient.hip, corner.hip, brief.hip; the planar average and the GrayU8 integral
+// image: integral.hip; what the units share: ip_dev.h) ----------------
 // Images arrive as DevImg views.  Where the images of a call share one shape, width, height and batch are read from the first view; dx / dy
 // pairs share one layout.
 int bhip_launch_conv(bhip_ctx* ctx, bool vertical, bool normalized, const float* kernel, int kw, int koff, DevImg<const float> in, DevImg<float> out);
@@ -468,7 +469,7 @@ int bhip_launch_distort(bhip_ctx* ctx, DevImg<const T> src, const DistortCoords&
 // the map of a model, dw x dh entries, into device memory
 int bhip_launch_distort_build_map(bhip_ctx* ctx, int model, const float* coeff, int dw, int dh, float* map);
 
-// ---------------- stationary background models (background.hip) ----------------
+// ---------------- stationary background models (background.hip; kernels: background_dev.h, background_gmm_*.hip) ----------------
 #define BHIP_BG_MAX_BANDS 4
 #define BHIP_BG_MAX_GAUSSIANS 8   // the mixture is a register array of this many slots at most
 // what a bhip_bg was created for.  bands: 0 = a single-band Gray image (the reference's *_SB classes), 1..4 = a Planar image of that many bands

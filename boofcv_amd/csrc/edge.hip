@@ -1,7 +1,7 @@
 // ---------------------------------------------------------------------------------------------------------------
 // Edge features of a gradient on batches of device frames (F:alg/feature/detect/edge/*.java), any row / image stride:
 //   intensityAbs on GrayS16 derivatives      impl/ImplGradientToEdgeFeatures.java:151-169: |dx| + |dy| in int, stored as float
-//                                            (the GrayF32 form is k_grad_intensity of ip.hip)
+//                                            (the GrayF32 form is k_grad_intensity of gradient.hip)
 //   nonMaxSuppressionCrude4                  GradientToEdgeFeatures.java:143-157, 248-262 -> impl/ImplEdgeNonMaxSuppressionCrude.java
 //                                            inner4 :50-115, border4 :155-242 (GrayF32 derivatives) and the GrayI form after it
 // Crude suppression: the step (dx, dy) is the sign of the two derivatives (+1 where the derivative is > 0, else -1: zero and NaN step

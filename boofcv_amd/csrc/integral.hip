@@ -10,6 +10,7 @@
 // Memory: pass 1 reads rows through an LDS transpose so that HBM accesses stay coalesced (a wave reads 256 B row segments)
 // while every lane owns one row's chain; pass 2 is naturally coalesced (a wave owns 64 adjacent columns).
 // Bound: HBM.  Algorithmic bytes: 4P read + 4P write per pass.
+// At the end of the file: the band average that turns a Planar<GrayF32> frame into the detector's gray image, and the GrayU8 -> GrayS32 form.
 #include "common.h"
 #include <cstdlib>
 
@@ -365,6 +366,92 @@ int bhip_launch_integral(bhip_ctx* ctx, DevImg<const float> src, DevImg<float> d
 	{
 		ProfScope ps(ctx, "k_integral_cols", passBytes);
 		hipLaunchKernelGGL(k_integral_cols, grid, dim3(256), 0, ctx->stream, out);
+	}
+	BHIP_HIP(ctx, hipGetLastError());
+	return BHIP_OK;
+}
+
+// ---------------- band average of a planar image ----------------
+// ImplConvertPlanarToGray.average(Planar<GrayF32>, GrayF32)  I:core/image/impl/ImplConvertPlanarToGray.java:296-336:
+// one band: copy; three bands: sum = b0; sum += b1; sum += b2; sum / 3; otherwise sum = 0; sum += b_i ...; sum / numBands
+__global__ __launch_bounds__(256) void k_planar_average(const float* __restrict__ bands, long long bandStride, int numBands, long long n, float* __restrict__ out) {
+	const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	float r;
+	if (numBands == 1) {
+		r = bands[i];
+	} else if (numBands == 3) {
+		float sum = bands[i];
+		sum += bands[bandStride + i];
+		sum += bands[2 * bandStride + i];
+		r = sum / 3;
+	} else {
+		float sum = 0;
+		for (int b = 0; b < numBands; b++) sum += bands[b * bandStride + i];
+		r = sum / numBands;
+	}
+	out[i] = r;
+}
+int bhip_launch_planar_average(bhip_ctx* ctx, const float* bands, long long bandStride, int numBands, long long n, float* out) {
+	if (n <= 0) return BHIP_OK;
+	ProfScope prof(ctx, "k_planar_average", 4.0 * n * (numBands + 1));
+	hipLaunchKernelGGL(k_planar_average, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, bands, bandStride, numBands, n, out);
+	BHIP_HIP(ctx, hipGetLastError());
+	return BHIP_OK;
+}
+
+// ---------------- integral image of an 8-bit image ----------------
+// IntegralImageOps.transform(GrayU8, GrayS32)   I:alg/transform/ii/impl/ImplIntegralImageOps.java:94-118.  Integer sums are exact in any
+// order, so the row pass is a wave-parallel scan (one wave per row, 64 pixels per step with a carry) and the column pass one thread per
+// column.  Bound: HBM (P read as bytes, 4P written, then 8P for the column pass).
+__global__ __launch_bounds__(256) void k_integral_rows_u8(const unsigned char* __restrict__ in, long long inImageStride, int inStride, int* __restrict__ out,
+														  long long outImageStride, int outStride, int width, int height) {
+	const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+	if (row >= height) return;
+	const unsigned char* r = in + (long long)blockIdx.y * inImageStride + (long long)row * inStride;
+	int* o = out + (long long)blockIdx.y * outImageStride + (long long)row * outStride;
+	int carry = 0;
+	for (int x0 = 0; x0 < width; x0 += 64) {
+		const int x = x0 + lane;
+		int v = x < width ? (int)r[x] : 0;
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) {
+			const int t = __shfl_up(v, d, 64);
+			if (lane >= d) v += t;
+		}
+		if (x < width) o[x] = carry + v;
+		carry += __shfl(v, 63, 64);
+	}
+}
+__global__ __launch_bounds__(256) void k_integral_cols_s32(int* __restrict__ io, long long imageStride, int stride, int width, int height) {
+	const int x = blockIdx.x * blockDim.x + threadIdx.x;
+	if (x >= width) return;
+	int* p = io + (long long)blockIdx.y * imageStride;
+	int total = 0;
+	int y = 0;
+	for (; y + 8 <= height; y += 8) {   // eight independent loads in flight, then the carry chain
+		int v[8];
+#pragma unroll
+		for (int k = 0; k < 8; k++) v[k] = p[(long long)(y + k) * stride + x];
+#pragma unroll
+		for (int k = 0; k < 8; k++) { total += v[k]; p[(long long)(y + k) * stride + x] = total; }
+	}
+	for (; y < height; y++) {
+		total += p[(long long)y * stride + x];
+		p[(long long)y * stride + x] = total;
+	}
+}
+int bhip_launch_integral_u8(bhip_ctx* ctx, DevImg<const uint8_t> in, DevImg<int32_t> out) {
+	const int width = in.width, height = in.height, batch = in.batch;
+	if (width <= 0 || height <= 0 || batch <= 0) return BHIP_OK;
+	{
+		ProfScope prof(ctx, "k_integral_rows_u8", 5.0 * width * height * batch);
+		hipLaunchKernelGGL(k_integral_rows_u8, dim3((height + 3) / 4, batch), dim3(256), 0, ctx->stream, in.data, in.imageStride, in.stride, out.data, out.imageStride,
+						   out.stride, width, height);
+	}
+	{
+		ProfScope prof(ctx, "k_integral_cols_s32", 8.0 * width * height * batch);
+		hipLaunchKernelGGL(k_integral_cols_s32, dim3((width + 255) / 256, batch), dim3(256), 0, ctx->stream, out.data, out.imageStride, out.stride, width, height);
 	}
 	BHIP_HIP(ctx, hipGetLastError());
 	return BHIP_OK;

@@ -1281,7 +1281,7 @@ int bhip_label_to_binary_s32_u8(bhip_ctx* ctx, const int32_t* in, int inStart, i
 								const uint8_t* selected, int numSelected);
 
 /* ---- line detection: the stages of FactoryDetectLine.houghLinePolar(ConfigHoughBinary, ...) and houghLineFoot(ConfigHoughGradient, ...)
- *      (F:factory/feature/detect/line/FactoryDetectLine.java:90-163; hough.hip, edge.hip, the Prewitt form of the gradient kernels in ip.hip).
+ *      (F:factory/feature/detect/line/FactoryDetectLine.java:90-163; hough.hip, edge.hip, the Prewitt form of the gradient kernels in gradient.hip).
  *      The parity target is the single-threaded classes.  There is no BOverride hook for them: integration/java/boofcv/hip/HoughLinesHip.java is
  *      a provider class.  The _dev forms take batch images at dev_x + b*xImageStride (strides in elements), write the whole view of every output
  *      image and nothing outside it, are asynchronous on the context's stream without host synchronisation, and keep their scratch in the

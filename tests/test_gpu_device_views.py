@@ -4,7 +4,7 @@ hold the reference's result bit for bit, every element of the parent outside it 
 between two images, above the first or below the last image lands in the parent and fails the assertion), and the frame that the no-border
 convolutions and the border=None gradients leave to the caller must still hold the sentinel.  The input parents must come back unchanged.
 
-Shapes.  B = 2.  (W,H) = (259,131) is the smallest shape that crosses every strip boundary of the vector kernels of ip.hip: 256 columns per block
+Shapes.  B = 2.  (W,H) = (259,131) is the smallest shape that crosses every strip boundary of the vector kernels of conv.hip and gradient.hip: 256 columns per block
 with a 3-pixel scalar tail in the second strip (259 = 256 + 3), and more rows than 4*CS_ROWS = 32 (k_conv_h_stream), 4*CS_ROWS_V = 64
 (k_conv_v_stream), 4*GR_ROWS = 32 (k_grad_stream, k_grad_u8), 4*BF_ROWS = 128 (k_blur_fused) and CV_ROWS = 32 (k_conv_v_tile), with a partial
 last strip for each (131 = 128 + 3).  (30,9) covers kernels barely narrower than the image and the naive form of the normalised convolution.
@@ -12,7 +12,7 @@ last strip for each (131 = 128 + 3).  (30,9) covers kernels barely narrower than
 Layouts.  For each output layout of view_layouts.LAYOUTS the input is dense, and then in the output's layout: with pad4 / pad4_x4 the launchers'
 vec4(in) && vec4(out) holds in the second combination only.
 
-Which kernel serves which layout (from the launchers' predicates in ip.hip; float32 unless named):
+Which kernel serves which layout (from the launchers' predicates in conv.hip, gradient.hip, corner.hip and fast.hip; float32 unless named):
   convolve*            dense (pitch 259 or 30: no multiple of 4), pad4_x1, odd, and every pair with one of them on either side: k_conv (general).
                        pad4 and pad4_x4 on both sides: widths 3 and 11 k_conv_h_stream / k_conv_v_stream (+ k_conv borderOnly for the normalised
                        forms), widths 13 and 41 and the even kernel k_conv_h_tile<0> / k_conv_v_tile<0,16>; a kernel at least as wide as the

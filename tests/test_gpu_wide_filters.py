@@ -1,7 +1,7 @@
 """Wide filter kernels on every dispatch path, bit for bit against the CPU oracle (tests/test_oracle_wide_filters.py checks the oracle
 itself against an fp64 reference at the same widths).
 
-bhip_launch_conv (boofcv_amd/csrc/ip.hip) picks one of four kernels for a separable convolution; each case id names the class it targets:
+bhip_launch_conv (boofcv_amd/csrc/conv.hip) picks one of four kernels for a separable convolution; each case id names the class it targets:
   stream    widths 3..11, centred: k_conv_{h,v}_stream + the border fix-up of the general kernel
   tile      any other width up to 97 on 16-byte aligned rows: k_conv_h_tile<0> / k_conv_v_tile<0,16> (coefficients in LDS, a four-tap
             ds_read2st64 loop plus a remainder loop, packed fp32); the vertical block takes (32 + kw - 1) KiB of LDS, above 64 KiB from
