@@ -1,7 +1,7 @@
 """include/boofhip.h read as data: the one description of the C ABI that the ctypes binding (_lib.py) and the JNI generator
 (scripts/gen_jni.py) are both derived from.  Pure text processing: no ctypes, no JNI names.
 
-    parse(text) -> Header(functions, structs, constants, tagged)
+    parse(text) -> Header(functions, structs, constants, tagged, declared)
     classify(ctype, pname) -> (kind, element type, is_const)
     load() -> parse() of HEADER, cached
 """
@@ -18,8 +18,10 @@ _COMMENT = re.compile(r"/\*.*?\*/", re.S)
 _FUNCTION = re.compile(r"^[ \t]*(int|void|const char\*)\s+(bhip_\w+)\s*\(([^;{}()]*)\)\s*;", re.M)
 
 # functions: [(ret, name, [(ctype, pname)])] in header order; structs: {bhip_*_cfg: [(ctype, field)]}, the anonymous `typedef struct { } name;`
-# ones; tagged: the same for `typedef struct name { } name;`; constants: {BHIP_*: int}
-Header = collections.namedtuple("Header", "functions structs constants tagged")
+# ones; tagged: the same for `typedef struct name { } name;`; declared: the same for `struct name { }; typedef struct name name;` (the sets of
+# the first two spellings are pinned by tests/test_header_binding.py and tests/test_threshold_reference.py; a new config struct is declared
+# the third way); constants: {BHIP_*: int}
+Header = collections.namedtuple("Header", "functions structs constants tagged declared")
 
 
 def _declarator(text):
@@ -81,6 +83,9 @@ def parse(text):
     tagged = {}
     for m in re.finditer(r"typedef\s+struct\s+(bhip_\w+_cfg)\s*\{([^{}]*)\}\s*\1\s*;", text):
         tagged[m.group(1)] = [_declarator(f) for f in m.group(2).split(";") if f.strip()]
+    declared = {}
+    for m in re.finditer(r"(?<!typedef)\s+struct\s+(bhip_\w+_cfg)\s*\{([^{}]*)\}\s*;\s*typedef\s+struct\s+\1\s+\1\s*;", text):
+        declared[m.group(1)] = [_declarator(f) for f in m.group(2).split(";") if f.strip()]
     constants = {}
     for m in re.finditer(r"typedef\s+enum\s*\{([^{}]*)\}\s*\w+\s*;", text):
         value = -1
@@ -94,7 +99,7 @@ def parse(text):
             constants[m.group(1)] = int(m.group(2), 0)
         except ValueError:
             pass   # not an integer constant
-    return Header(functions, structs, constants, tagged)
+    return Header(functions, structs, constants, tagged, declared)
 
 
 _cached = None

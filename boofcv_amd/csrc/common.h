@@ -599,6 +599,47 @@ int bhip_launch_hs_derivatives(bhip_ctx* ctx, DevImg<const T> src, DevImg<const 
 // zero flow; out: (x, y) of pixel (x, y) at out.data + b * imageStride + y * stride + 2 * x (out.width in pixels, strides in floats); in != out
 int bhip_launch_hs_iterate(bhip_ctx* ctx, const float* deriv, const float* in, DevImg<float> out, float alpha2, int n);
 
+// ---------------- SIFT detector: scale space, DoG extrema (sift.hip) ----------------
+#define BHIP_SIFT_TILE_W BHIP_SIFT_LEVEL_TILE_WIDTH
+#define BHIP_SIFT_TILE_H BHIP_SIFT_LEVEL_TILE_HEIGHT
+#define BHIP_SIFT_FUSED_MAX_TAPS BHIP_SIFT_LEVEL_MAX_TAPS
+// GConvertImage.convert(GrayU8, GrayF32); ImplPyramidOps.scaleImageUp with the EXTENDED bilinear interpolator (out is in * scale);
+// ImplPyramidOps.scaleDown2 (out is in.width / 2 x in.height / 2); PixelMath.subtract (out = a - b).  Any strides, at most 65535 images
+int bhip_launch_sift_u8_to_f32(bhip_ctx* ctx, DevImg<const uint8_t> in, DevImg<float> out);
+int bhip_launch_sift_scale_up(bhip_ctx* ctx, DevImg<const float> in, DevImg<float> out, int scale);
+int bhip_launch_sift_scale_down2(bhip_ctx* ctx, DevImg<const float> in, DevImg<float> out);
+int bhip_launch_sift_subtract(bhip_ctx* ctx, DevImg<const float> a, DevImg<const float> b, DevImg<float> out);
+// One scale level in one launch: out = applyGaussian(in, kernel) and dog = out - in.  *done = false and nothing is queued when the shape is
+// outside the fused form (kw even, < 3 or > BHIP_SIFT_FUSED_MAX_TAPS, a kernel as wide as the image in either direction, rows of `in` that
+// are not 16-byte aligned): the caller then runs the two normalised passes and the subtract
+int bhip_launch_sift_level(bhip_ctx* ctx, const float* kernel, int kw, DevImg<const float> in, DevImg<float> out, DevImg<float> dog, bool* done);
+// What SiftDetector.detectFeatures does with the NonMaxLimiter list of one (octave, j) on every frame of a batch.  The list of frame b is its
+// nMin[b] minima then its nMax[b] maxima ([batch][listCap] (x, y) pairs each), read through sel ([batch][2 * listCap] entry indices, the
+// order QuickSelect left) and cut to maxFeatures when sel != nullptr.  Survivors are appended in list order behind count[b] records
+struct SiftCandParams {
+	const float *lower, *target, *upper;   // dog[j-1], dog[j], dog[j+1]
+	long long imageStride;
+	int stride, width, height, batch;
+	const int16_t *xyMin, *xyMax;
+	const int *nMin, *nMax;
+	int listCap;
+	const int* sel;
+	int maxFeatures;
+	double edgeThreshold, pixelScaleToInput, sigmaLower, sigmaTarget, sigmaUpper;
+	int octave, j;
+	double *x, *y, *scale;   // [batch][cap]
+	uint8_t* white;          // [batch][cap]
+	int16_t* where;          // [batch][cap][4]: octave, j, pixel x, pixel y
+	int* count;              // [batch], advanced by the number of survivors (which may carry it beyond cap)
+	int cap;
+};
+// bitmap, prefix: bhip_sift_cand_words(listCap) words per frame each; nPass: batch ints
+static inline int bhip_sift_cand_words(int listCap) { return (2 * listCap + 255) / 256 * 8; }
+int bhip_launch_sift_candidates(bhip_ctx* ctx, const SiftCandParams& P, unsigned int* bitmap, unsigned int* prefix, int* nPass);
+// NonMaxLimiter's cut: where a frame's list is longer than maxFeatures, the restated sequential QuickSelect on keys -|value| (one wave per
+// frame); sel and key are [batch][2 * listCap]
+int bhip_launch_sift_select(bhip_ctx* ctx, const SiftCandParams& P, float* key, int* sel);
+
 // ---------------- thresholding, FactoryThresholdBinary, and the GrayU8 blurs (threshold.hip) ----------------
 #define BHIP_THRESH_FUSED_MAX_RADIUS 16   // blur radius up to which a GrayU8 local threshold (and blur) runs as one launch out of LDS
 // the compare of a pixel with its threshold: px <= thr (down), px > thr (up: fixed, local, min/max), !(px <= thr) (up: block mean, Otsu; differs on NaN)

@@ -13,6 +13,7 @@
 // per-image bitmap, which makes the ordering a popcount-prefix: rank = #bits below.  No sort, no atomics on the ordering path.
 // fp32 compares only, so keypoint indices are bit-exact whenever the intensity image is.
 #include "hessian_dev.h"
+#include "select_dev.h"
 #include <cfloat>
 
 // strict-maximum test of NonMaxBlockSearchStrict.Max for pixel (x,y) with value v.  The window is read without early exits so the
@@ -476,35 +477,7 @@ __device__ __forceinline__ int bitRank(const unsigned int* __restrict__ bm, cons
 	return (int)(pf[bit >> 5] + __popc(bm[bit >> 5] & ((1u << (bit & 31)) - 1u)));
 }
 
-__device__ void quickSelectIndexSeq(float* data, int k, int n, int* indexes) {
-	int l = 0, ir = n - 1;
-#define QS_SWAP(a_, b_) do { const float tf = data[a_]; data[a_] = data[b_]; data[b_] = tf; const int ti = indexes[a_]; indexes[a_] = indexes[b_]; indexes[b_] = ti; } while (0)
-	for (;;) {
-		if (ir <= l + 1) {
-			if (ir == l + 1 && data[ir] < data[l]) QS_SWAP(l, ir);
-			return;
-		}
-		const int mid = (l + ir) >> 1, lp1 = l + 1;
-		QS_SWAP(mid, lp1);
-		if (data[l] > data[ir]) QS_SWAP(l, ir);
-		if (data[lp1] > data[ir]) QS_SWAP(lp1, ir);
-		if (data[l] > data[lp1]) QS_SWAP(l, lp1);
-		int i = lp1, j = ir;
-		const float a = data[lp1];
-		const int indexA = indexes[lp1];
-		for (;;) {
-			do i++; while (data[i] < a);   // data[ir] >= a and data[l] <= a are the sentinels, as in the sequential routine
-			do j--; while (data[j] > a);
-			if (j < i) break;
-			QS_SWAP(i, j);
-		}
-		data[lp1] = data[j]; data[j] = a;
-		indexes[lp1] = indexes[j]; indexes[j] = indexA;
-		if (j >= k) ir = j - 1;
-		if (j <= k) l = i;
-	}
-#undef QS_SWAP
-}
+// quickSelectIndexSeq: select_dev.h
 
 __global__ __launch_bounds__(64) void k_select_nbest(SelectParams P) {
 	__shared__ float ldsKey[SEL_LDS];

@@ -32,6 +32,7 @@ Names follow the reference classes the host-buffer forms in boofcv_amd/api/ mirr
   DeviceImageOps.histogram / equalizeTable / applyTransform   ImageStatistics.histogram, EnhanceImageOps.equalize / applyTransform   I:alg/enhance/EnhanceImageOps.java:65-94
   DeviceImageOps.equalizeLocal  EnhanceImageOps.equalizeLocal (GrayU8)              I:alg/enhance/EnhanceImageOps.java:176-232
   DeviceImageOps.sharpen        EnhanceImageOps.sharpen4 / sharpen8 (GrayU8, GrayF32)   I:alg/enhance/EnhanceImageOps.java:307-371
+  DeviceImageOps.siftScaleSpace / siftDetect   SiftScaleSpace.initialize + computeNextOctave, SiftDetector.process   F:alg/feature/detect/interest/SiftDetector.java:165-191
   DeviceImageOps.brief          DescribePointBrief.process                       F:alg/feature/describe/DescribePointBrief.java:73-89
   DeviceKltTracker              PointTrackerKltPyramid, batched over sequences      main/boofcv-geo/.../abst/feature/tracker/PointTrackerKltPyramid.java:139-348
   DeviceBackgroundModel         BackgroundStationaryBasic / Gaussian / Gmm, batched over streams   F:alg/background/stationary/*.java
@@ -684,6 +685,60 @@ class DeviceImageOps:
         _check(self.ctx, fn(self.ctx._h, float(alpha), int(numIterations), pp, pis, prs, cp, cis, crs, W, H, B, C.c_void_p(out.data_ptr()), ois, ors,
                             C.c_void_p(derivs.data_ptr()) if derivs is not None else None, int(itersPerLaunch)))
         return out if derivs is None else (out, derivs)
+
+    def siftLayout(self, width, height, configSS=None):
+        """bhip_sift_layout -> (dims [(w, h)] of the octaves SiftScaleSpace computes for a width x height frame, scaleFloats, dogFloats): a frame's
+        scale images are numScales+3 dense images per octave of plane = (w*h + 3) & ~3 floats each, octave after octave; its DoG images
+        numScales+2 per octave in the same way"""
+        from . import sift
+        c = sift._cfg(configSS, None)
+        dims = (C.c_int * 128)()
+        sf, df = C.c_longlong(0), C.c_longlong(0)
+        n = self.L.bhip_sift_layout(C.byref(c), int(width), int(height), dims, 64, C.byref(sf), C.byref(df))
+        if n < 0:
+            raise (RuntimeError if n == _lib.BHIP_ERR_UNSUPPORTED else IllegalArgumentException)("no SIFT scale space for a %d x %d frame with this config" % (width, height))
+        return [(dims[2 * i], dims[2 * i + 1]) for i in range(n)], sf.value, df.value
+
+    def siftScaleSpace(self, src, configSS=None):
+        """SiftScaleSpace.initialize and every computeNextOctave on uint8 or float32 frames [B,H,W] of any row / image stride -> (scale float32
+        [B, scaleFloats], dog float32 [B, dogFloats], dims) in the layout of siftLayout (padding floats are 0).  siftImages() cuts a frame's
+        buffers into its images.  No host synchronisation."""
+        from . import sift
+        u8 = src.dtype == torch.uint8
+        ip, iis, irs, W, H, B = _geom(src, torch.uint8 if u8 else torch.float32)
+        dims, sf, df = self.siftLayout(W, H, configSS)
+        scale = torch.zeros((B, sf), dtype=torch.float32, device=src.device)
+        dog = torch.zeros((B, df), dtype=torch.float32, device=src.device)
+        fn = self.L.bhip_sift_scale_space_dev_u8 if u8 else self.L.bhip_sift_scale_space_dev_f32
+        _check(self.ctx, fn(self.ctx._h, C.byref(sift._cfg(configSS, None)), ip, iis, irs, W, H, B, C.c_void_p(scale.data_ptr()), C.c_void_p(dog.data_ptr())))
+        return scale, dog, dims
+
+    @staticmethod
+    def siftImages(buf, dims, perOctave):
+        """the images of one frame's buffer (a 1-D tensor or array laid out by siftLayout): [[image [h, w]] * perOctave] per octave"""
+        out, off = [], 0
+        for w, h in dims:
+            plane = (w * h + 3) & ~3
+            out.append([buf[off + i * plane:off + i * plane + w * h].reshape(h, w) for i in range(perOctave)])
+            off += perOctave * plane
+        return out
+
+    def siftDetect(self, src, configSS=None, configDet=None, cap=4096):
+        """SiftDetector.process on uint8 or float32 frames [B,H,W] of any row / image stride -> (x, y, scale float64 [B, cap], white uint8 [B, cap],
+        where int16 [B, cap, 4] = octave, DoG index, pixel x, pixel y in that octave, count int32 [B]) on the device, every frame's detections
+        in the reference's order.  A count may exceed cap; only the first cap records are written.  No host synchronisation."""
+        from . import sift
+        u8 = src.dtype == torch.uint8
+        ip, iis, irs, W, H, B = _geom(src, torch.uint8 if u8 else torch.float32)
+        cap = int(cap)
+        x, y, scale = (torch.empty((B, max(cap, 0)), dtype=torch.float64, device=src.device) for _ in range(3))
+        white = torch.empty((B, max(cap, 0)), dtype=torch.uint8, device=src.device)
+        where = torch.empty((B, max(cap, 0), 4), dtype=torch.int16, device=src.device)
+        count = torch.empty((B,), dtype=torch.int32, device=src.device)
+        fn = self.L.bhip_sift_detect_dev_u8 if u8 else self.L.bhip_sift_detect_dev_f32
+        _check(self.ctx, fn(self.ctx._h, C.byref(sift._cfg(configSS, configDet)), ip, iis, irs, W, H, B, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()),
+                            C.c_void_p(scale.data_ptr()), C.c_void_p(white.data_ptr()), C.c_void_p(where.data_ptr()), C.c_void_p(count.data_ptr()), cap))
+        return x, y, scale, white, where, count
 
     def distortBuildMap(self, model, coeff, dw, dh, out=None):
         """bhip_distort_build_map: the [dh,dw,2] float32 map of an affine (model 1, six coefficients) or homography (model 2, nine) model"""

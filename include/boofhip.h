@@ -1423,6 +1423,76 @@ int bhip_sharpen_dev_f32(bhip_ctx* ctx, int rule, const float* dev_in, long long
 int bhip_sharpen_u8(bhip_ctx* ctx, int rule, const uint8_t* in, int inStart, int inStride, int width, int height, uint8_t* out, int outStart, int outStride);
 int bhip_sharpen_f32(bhip_ctx* ctx, int rule, const float* in, int inStart, int inStride, int width, int height, float* out, int outStart, int outStride);
 
+/* ---- SIFT detector: scale space and DoG extrema.  FactoryInterestPoint.sift (F:factory/feature/detect/interest/FactoryInterestPoint.java:133-148):
+ *      WrapSiftDetector (F:abst/feature/detect/interest/WrapSiftDetector.java:38-60) over SiftDetector (F:alg/feature/detect/interest/SiftDetector.java:
+ *      119-331), SiftScaleSpace (F:alg/feature/detect/interest/SiftScaleSpace.java:102-270) and NonMaxLimiter
+ *      (F:abst/feature/detect/extract/NonMaxLimiter.java:49-84) with FactoryFeatureExtractor.nonmax(ConfigExtract).  Orientation and description
+ *      (OrientationHistogramSift, DescribePointSift) are not provided. ----
+ * Every scale image, DoG image and detection equals the single-threaded Java result bit for bit: the border-normalised separable Gaussian
+ * convolutions (the arithmetic of bhip_conv_norm_h / _v, naive form included), a float subtraction, the strict block min / max non-maximum
+ * suppression with ignoreBorder 1, the 3x3x3 comparison, the edge test in double on three sparse float convolutions with an EXTENDED border, and
+ * polyPeak.  levelK, computeSigmaScale and pixelScaleCurrentToInput are the host's pow: unpinned against Java's Math.pow.  With
+ * maxFeaturesPerScale > 0 the list of a scale that is longer is cut by the project's restatement of QuickSelect.select on keys -|value|: the
+ * order it leaves is unpinned against the ddogleg jar, the kept set is pinned whenever no two |value| around the cut are equal.
+ * A scale level (octave[i] = blur(octave[i-1]), dog[i-1] = octave[i] - octave[i-1]) runs as one launch on BHIP_SIFT_LEVEL_TILE_WIDTH x
+ * BHIP_SIFT_LEVEL_TILE_HEIGHT tiles for odd kernels of 3 .. BHIP_SIFT_LEVEL_MAX_TAPS taps narrower than the image both ways over 16-byte aligned
+ * rows, and as the two normalised passes plus a subtract otherwise; BHIP_SIFT_TWO_PASS=1 in the environment forces the latter (same results).
+ * BHIP_ERR_INVALID and nothing is written, where the reference throws: lastOctave <= firstOctave, numScales < 1, edgeR < 1 (detect), an
+ * extractor with extractIgnoreBorder != 1, without minima or maxima, or with extractRadius < 1 (detect), sigma0 <= 0, empty images (an octave
+ * of no pixels included), strides smaller than a row, cap < 0.
+ * BHIP_ERR_UNSUPPORTED and nothing is written: an octave image wider or taller than 32767 (the lists are Point2D_I16), a blur kernel beyond 255
+ * taps, more than 65535 frames, extractUseStrictRule == 0 (the relaxed rule). */
+#define BHIP_SIFT_LEVEL_TILE_WIDTH 64
+#define BHIP_SIFT_LEVEL_TILE_HEIGHT 64
+#define BHIP_SIFT_LEVEL_MAX_TAPS 27
+/* (a struct tag and a typedef of it: the form boofcv_amd/_header.py reads as Header.declared) */
+struct bhip_sift_cfg {
+	int firstOctave;          /* ConfigSiftScaleSpace: 0 */
+	int lastOctave;           /* 5 */
+	int numScales;            /* 3 */
+	double sigma0;            /* (double)2.75f; SiftScaleSpace takes a double */
+	int extractRadius;        /* ConfigSiftDetector.extract = ConfigExtract(2, 0, 1, true, true, true): radius 2 */
+	float extractThreshold;   /* 0 (thresholdMax = threshold, thresholdMin = -threshold) */
+	int extractIgnoreBorder;  /* 1 */
+	int extractUseStrictRule; /* 1 */
+	int extractDetectMin;     /* 1 */
+	int extractDetectMax;     /* 1 */
+	int maxFeaturesPerScale;  /* 0: no limit */
+	double edgeR;             /* 10 */
+};
+typedef struct bhip_sift_cfg bhip_sift_cfg;
+/* new ConfigSiftScaleSpace() (F:abst/feature/describe/ConfigSiftScaleSpace.java) and new ConfigSiftDetector()
+ * (F:abst/feature/detect/interest/ConfigSiftDetector.java) */
+int bhip_sift_cfg_default(bhip_sift_cfg* cfg);
+/* Host only: the octaves SiftScaleSpace.initialize / computeNextOctave (:170-212) compute for a width x height frame.  Returns their number (>= 1)
+ * or a BHIP_ERR_* code; dims receives (width, height) of the first min(number, cap) octaves, octave firstOctave first.  A frame's scale images
+ * take *scaleFloats floats: octave after octave, numScales+3 dense images of plane = (w*h + 3) & ~3 floats each; its DoG images *dogFloats
+ * floats in the same way with numScales+2 images per octave.  dims, scaleFloats and dogFloats may be NULL. */
+int bhip_sift_layout(const bhip_sift_cfg* cfg, int width, int height, int* dims, int cap, long long* scaleFloats, long long* dogFloats);
+/* The scale space of `batch` device frames at dev_in + b*imageStride (rows `stride` elements apart, any alignment): frame b's images go to
+ * dev_scale + b * scaleFloats and dev_dog + b * dogFloats in the layout of bhip_sift_layout (the padding floats of a plane are not written).  The
+ * _u8 form converts as GConvertImage.convert does (& 0xFF to float) on the device.  Asynchronous on the context's stream, no host synchronisation. */
+int bhip_sift_scale_space_dev_f32(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const float* dev_in, long long imageStride, int stride, int width, int height,
+								  int batch, float* dev_scale, float* dev_dog);
+int bhip_sift_scale_space_dev_u8(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const uint8_t* dev_in, long long imageStride, int stride, int width, int height,
+								 int batch, float* dev_scale, float* dev_dog);
+/* SiftDetector.process on every frame, one octave at a time in context scratch.  Frame b's detections, in the reference's order, go to
+ * dev_x / dev_y / dev_scale + b*cap (ScalePoint x, y, scale), dev_white + b*cap (ScalePoint.white as 0 / 1) and dev_where + b*cap*4 (octave, the
+ * DoG index j, and the pixel (x, y) in that octave where the extremum was found); dev_count[b] is their number, which may exceed cap: only the
+ * first cap records are written.  No host synchronisation between the first launch and the last. */
+int bhip_sift_detect_dev_f32(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const float* dev_in, long long imageStride, int stride, int width, int height, int batch,
+							 double* dev_x, double* dev_y, double* dev_scale, uint8_t* dev_white, int16_t* dev_where, int* dev_count, int cap);
+int bhip_sift_detect_dev_u8(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const uint8_t* dev_in, long long imageStride, int stride, int width, int height, int batch,
+							double* dev_x, double* dev_y, double* dev_scale, uint8_t* dev_white, int16_t* dev_where, int* dev_count, int cap);
+/* the same on one host image view: staged, run through the _dev forms, synchronised.  scale / dog: scaleFloats / dogFloats floats (written as a
+ * whole, the padding floats of a plane as 0); x, y, scale, white: cap elements, where: 4 * cap; *count as dev_count. */
+int bhip_sift_scale_space_f32(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const float* in, int start, int stride, int width, int height, float* scale, float* dog);
+int bhip_sift_scale_space_u8(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const uint8_t* in, int start, int stride, int width, int height, float* scale, float* dog);
+int bhip_sift_detect_f32(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const float* in, int start, int stride, int width, int height, double* x, double* y,
+						 double* scale, uint8_t* white, int16_t* where, int* count, int cap);
+int bhip_sift_detect_u8(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const uint8_t* in, int start, int stride, int width, int height, double* x, double* y,
+						double* scale, uint8_t* white, int16_t* where, int* count, int cap);
+
 #ifdef __cplusplus
 }
 #endif
