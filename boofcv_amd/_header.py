@@ -1,7 +1,7 @@
 """include/boofhip.h read as data: the one description of the C ABI that the ctypes binding (_lib.py) and the JNI generator
 (scripts/gen_jni.py) are both derived from.  Pure text processing: no ctypes, no JNI names.
 
-    parse(text) -> Header(functions, structs, constants, tagged, declared)
+    parse(text) -> Header(functions, structs, constants, tagged, declared, forward)
     classify(ctype, pname) -> (kind, element type, is_const)
     load() -> parse() of HEADER, cached
 """
@@ -20,8 +20,9 @@ _FUNCTION = re.compile(r"^[ \t]*(int|void|const char\*)\s+(bhip_\w+)\s*\(([^;{}(
 # functions: [(ret, name, [(ctype, pname)])] in header order; structs: {bhip_*_cfg: [(ctype, field)]}, the anonymous `typedef struct { } name;`
 # ones; tagged: the same for `typedef struct name { } name;`; declared: the same for `struct name { }; typedef struct name name;` (the sets of
 # the first two spellings are pinned by tests/test_header_binding.py and tests/test_threshold_reference.py; a new config struct is declared
-# the third way); constants: {BHIP_*: int}
-Header = collections.namedtuple("Header", "functions structs constants tagged declared")
+# the third way -- or, now that tests/test_sift_reference.py pins that set too, the fourth: forward, `typedef struct name name; struct name { };`);
+# constants: {BHIP_*: int}
+Header = collections.namedtuple("Header", "functions structs constants tagged declared forward")
 
 
 def _declarator(text):
@@ -86,6 +87,9 @@ def parse(text):
     declared = {}
     for m in re.finditer(r"(?<!typedef)\s+struct\s+(bhip_\w+_cfg)\s*\{([^{}]*)\}\s*;\s*typedef\s+struct\s+\1\s+\1\s*;", text):
         declared[m.group(1)] = [_declarator(f) for f in m.group(2).split(";") if f.strip()]
+    forward = {}
+    for m in re.finditer(r"typedef\s+struct\s+(bhip_\w+_cfg)\s+\1\s*;\s*struct\s+\1\s*\{([^{}]*)\}\s*;", text):
+        forward[m.group(1)] = [_declarator(f) for f in m.group(2).split(";") if f.strip()]
     constants = {}
     for m in re.finditer(r"typedef\s+enum\s*\{([^{}]*)\}\s*\w+\s*;", text):
         value = -1
@@ -99,7 +103,7 @@ def parse(text):
             constants[m.group(1)] = int(m.group(2), 0)
         except ValueError:
             pass   # not an integer constant
-    return Header(functions, structs, constants, tagged, declared)
+    return Header(functions, structs, constants, tagged, declared, forward)
 
 
 _cached = None

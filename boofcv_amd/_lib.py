@@ -26,9 +26,9 @@ _CTYPES = {"int": _i, "float": _f, "double": _d, "long long": _ll, "uint8_t": C.
 
 # the header's config structs (c = bhip_<key>_cfg) under the names the package uses: FhCfg(detectThreshold, extractRadius, ...), fields in header order
 _STRUCT_NAMES = {"fh": "FhCfg", "surf": "SurfCfg", "ori": "OriCfg", "klt": "KltCfg", "disparity_bm": "DisparityBmCfg", "bg_basic": "BgBasicCfg",
-                 "bg_gaussian": "BgGaussianCfg", "bg_gmm": "BgGmmCfg", "threshold": "ThresholdCfg", "sift": "SiftCfg"}
+                 "bg_gaussian": "BgGaussianCfg", "bg_gmm": "BgGmmCfg", "threshold": "ThresholdCfg", "sift": "SiftCfg", "csift": "CompleteSiftCfg"}
 STRUCTS = {c: type(_STRUCT_NAMES[c[5:-4]], (C.Structure,), {"_fields_": [(name, _CTYPES[t]) for t, name in fields]})
-           for c, fields in list(_H.structs.items()) + list(_H.tagged.items()) + list(_H.declared.items())}
+           for c, fields in list(_H.structs.items()) + list(_H.tagged.items()) + list(_H.declared.items()) + list(_H.forward.items())}
 globals().update((cls.__name__, cls) for cls in STRUCTS.values())
 
 

@@ -30,6 +30,8 @@ struct CtxScratch {
 	DevBuf hough, houghTable;       // cabi_line.hip: vote counts / sort records of the Hough transforms; the sine / cosine and mean-shift weight tables
 	DevBuf enhance;                 // cabi_enhance.hip: the histogram / transform table of the host forms
 	DevBuf sift;                    // cabi_sift.hip: float frames, tempBlur, one octave's scale and DoG images, the NMS lists and candidate bitmaps
+	DevBuf siftTables;              // detect + describe: [exp table | bin angles | Gaussian weight] of the config last used ...
+	std::vector<char> siftTablesHost;   // ... and the host block they were copied from (uploaded again only when the config changes)
 	DevBuf thresholdTaps;         // the Kernel1D_S32 Gaussian taps of the GrayU8 blurs, for thresholdTapsRadius (0: none yet)
 	int thresholdTapsRadius = 0;
 	AssocMfmaWork mfma;

@@ -1,5 +1,7 @@
 // C ABI, SIFT detector (kernels: sift.hip; the normalised convolutions: conv.hip; the strict block NMS: detect.hip): SiftScaleSpace, SiftDetector,
 // NonMaxLimiter and WrapSiftDetector of FactoryInterestPoint.sift.  Rules, deviations and limits: bhip_sift_cfg in include/boofhip.h.
+// SIFT detect + describe (kernels: sift_describe.hip): CompleteSift and DetectDescribe_CompleteSift of FactoryDetectDescribe.sift, hooked into
+// the detector's per-octave loop.  Rules and limits: bhip_csift_cfg in include/boofhip.h.
 #include "cabi.h"
 
 namespace {
@@ -79,6 +81,52 @@ int siftDetectorCheck(const bhip_sift_cfg& c, const char** msg) {
 	return BHIP_OK;
 }
 
+// everything the host decides for orientation and description: the tables the kernels read (the C library's exp, cos, sqrt)
+struct SiftDescPlan {
+	bhip_csift_cfg cfg;
+	int dof = 0;
+	double histAngleBin = 0, histogramBinWidth = 0;
+	std::vector<double> expTable, binAngle;
+	std::vector<float> gaussianWeight;
+	bool generic = false;
+};
+
+// what the constructors of OrientationHistogramSift and DescribeSiftCommon need, and the limits of the kernels
+int siftDescCheck(const bhip_csift_cfg* desc, const char** msg) {
+	*msg = nullptr;
+	if (!desc) { *msg = "SIFT describe: null config"; return BHIP_ERR_INVALID; }
+	const bhip_csift_cfg& c = *desc;
+	if (c.histogramSize < 3) { *msg = "SIFT orientation: histogramSize must be >= 3"; return BHIP_ERR_INVALID; }
+	if (!(c.sigmaEnlarge > 0)) { *msg = "SIFT orientation: sigmaEnlarge must be > 0"; return BHIP_ERR_INVALID; }
+	if (c.widthSubregion < 1 || c.widthGrid < 1 || c.numHistogramBins < 1) { *msg = "SIFT describe: widthSubregion, widthGrid and numHistogramBins must be >= 1"; return BHIP_ERR_INVALID; }
+	if (!(c.sigmaToPixels > 0) || !(c.weightingSigmaFraction > 0) || !(c.maxDescriptorElementValue > 0)) {
+		*msg = "SIFT describe: sigmaToPixels, weightingSigmaFraction and maxDescriptorElementValue must be > 0";
+		return BHIP_ERR_INVALID;
+	}
+	if (c.histogramSize > BHIP_CSIFT_MAX_HISTOGRAM) { *msg = "SIFT on the GPU: histogramSize <= 256"; return BHIP_ERR_UNSUPPORTED; }
+	const long long sw = (long long)c.widthSubregion * c.widthGrid;
+	if (sw <= BHIP_CSIFT_MAX_SAMPLE_WIDTH && sw % 2) { *msg = "SIFT describe: widthSubregion * widthGrid must be even (the weight kernel has 2 * (width / 2) columns)"; return BHIP_ERR_INVALID; }
+	if (sw > BHIP_CSIFT_MAX_SAMPLE_WIDTH) { *msg = "SIFT on the GPU: widthSubregion * widthGrid <= 48"; return BHIP_ERR_UNSUPPORTED; }
+	if ((long long)c.widthGrid * c.widthGrid * c.numHistogramBins > BHIP_CSIFT_MAX_DOF) { *msg = "SIFT on the GPU: descriptors of at most 2048 elements"; return BHIP_ERR_UNSUPPORTED; }
+	return BHIP_OK;
+}
+
+int siftDescPlan(const bhip_csift_cfg* desc, SiftDescPlan& D, const char** msg) {
+	BHIP_TRY(siftDescCheck(desc, msg));
+	const bhip_csift_cfg& c = *desc;
+	D.cfg = c;
+	D.dof = c.widthGrid * c.widthGrid * c.numHistogramBins;                 // DescribeSiftCommon.getDescriptorLength
+	D.histAngleBin = 2.0 * M_PI / c.histogramSize;                          // OrientationHistogramSift :106
+	D.histogramBinWidth = 2.0 * M_PI / c.numHistogramBins;                  // DescribeSiftCommon :68
+	D.expTable = bhip_sift_exp_table();
+	D.binAngle.resize(c.numHistogramBins);
+	for (int k = 0; k < c.numHistogramBins; k++) D.binAngle[k] = k * D.histogramBinWidth;   // trilinearInterpolation :122
+	const int descriptorWindow = c.widthSubregion * c.widthGrid;
+	D.gaussianWeight = bhip_sift_gaussian_weight(descriptorWindow * c.weightingSigmaFraction, descriptorWindow / 2);   // :71-73
+	D.generic = bhip_env_flag("BHIP_SIFT_DESCRIBE_GENERIC");
+	return BHIP_OK;
+}
+
 // applyGaussian :241-245 through the launchers of bhip_conv_norm_h / _v; tmp: tempBlur, same shape
 int siftBlur(bhip_ctx* ctx, const std::vector<float>& k, DevImg<const float> in, DevImg<float> tmp, DevImg<float> out) {
 	const int kw = (int)k.size();
@@ -145,10 +193,18 @@ struct SiftBuffers {
 	float* key;
 	long long bigPlane;   // floats of the largest image any buffer holds
 	int listCap, words;
+	// detect + describe: the detections of one (octave, j) -- at most 2 * listCap a frame, the whole list -- with their angle counts, scan and
+	// first angles; the tables (siftTables)
+	double *detX, *detY, *detScale, *angles, *expTable, *binAngle;
+	uint8_t* detWhite;
+	int16_t* detWhere;
+	int *detN, *nAngles, *angleOffset, *nFeat;
+	float* gaussianWeight;
+	int detCap;
 };
 
 // detect: the octave images and the lists live in scratch; scaleSpaceOnly: the caller holds the images
-void siftCarve(SiftScratch& S, const SiftPlan& P, int batch, bool needFrames, bool scaleSpaceOnly, SiftBuffers& B) {
+void siftCarve(SiftScratch& S, const SiftPlan& P, int batch, bool needFrames, bool scaleSpaceOnly, SiftBuffers& B, const SiftDescPlan* D = nullptr) {
 	const long long frame = planeOf(P.w0, P.h0), first = planeOf(P.upW, P.upH);
 	B.bigPlane = std::max(frame, first);
 	B.frames = needFrames ? S.take<float>((size_t)frame * batch) : nullptr;
@@ -175,6 +231,20 @@ void siftCarve(SiftScratch& S, const SiftPlan& P, int batch, bool needFrames, bo
 	const bool cut = P.cfg.maxFeaturesPerScale > 0;
 	B.sel = cut ? S.take<int>((size_t)B.listCap * 2 * batch) : nullptr;
 	B.key = cut ? S.take<float>((size_t)B.listCap * 2 * batch) : nullptr;
+	B.detCap = 0;
+	if (!D) return;
+	B.detCap = 2 * B.listCap;
+	const size_t dets = (size_t)B.detCap * batch;
+	B.detX = S.take<double>(dets);
+	B.detY = S.take<double>(dets);
+	B.detScale = S.take<double>(dets);
+	B.angles = S.take<double>(dets * BHIP_CSIFT_ANGLE_SLOTS);
+	B.detWhere = S.take<int16_t>(dets * 4);
+	B.nAngles = S.take<int>(dets);
+	B.angleOffset = S.take<int>(dets);
+	B.detWhite = S.take<uint8_t>(dets);
+	B.detN = S.take<int>(batch);
+	B.nFeat = S.take<int>(batch);
 }
 
 template <class T>
@@ -191,14 +261,14 @@ int siftFrames<uint8_t>(bhip_ctx* ctx, DevImg<const uint8_t> in, float* frames, 
 	return bhip_launch_sift_u8_to_f32(ctx, in, f);
 }
 
-int siftReserve(bhip_ctx* ctx, const SiftPlan& P, int batch, bool needFrames, bool scaleSpaceOnly, SiftBuffers& B) {
+int siftReserve(bhip_ctx* ctx, const SiftPlan& P, int batch, bool needFrames, bool scaleSpaceOnly, SiftBuffers& B, const SiftDescPlan* D = nullptr) {
 	SiftScratch measure;
-	siftCarve(measure, P, batch, needFrames, scaleSpaceOnly, B);
+	siftCarve(measure, P, batch, needFrames, scaleSpaceOnly, B, D);
 	DevBuf& buf = scratchOf(ctx)->sift;
 	BHIP_TRY(buf.reserve(ctx, measure.used));
 	SiftScratch S;
 	S.base = buf.as<char>();
-	siftCarve(S, P, batch, needFrames, scaleSpaceOnly, B);
+	siftCarve(S, P, batch, needFrames, scaleSpaceOnly, B, D);
 	return BHIP_OK;
 }
 
@@ -228,22 +298,53 @@ int scaleSpaceDevice(bhip_ctx* ctx, const SiftPlan& P, DevImg<const T> in, float
 	return BHIP_OK;
 }
 
+// The tables of a describe config on the device.  They stay with the context, next to a host copy to compare with, and are uploaded again
+// only when the config changes: an asynchronous copy's source must outlive it, so an upload is followed by a synchronisation -- paid on a
+// change alone, and before the first launch
+int siftTables(bhip_ctx* ctx, const SiftDescPlan& D, SiftBuffers& B) {
+	CtxScratch* sc = scratchOf(ctx);
+	const size_t nE = D.expTable.size() * 8, nB = D.binAngle.size() * 8, nG = D.gaussianWeight.size() * 4;
+	std::vector<char> blob(nE + nB + nG);
+	std::memcpy(blob.data(), D.expTable.data(), nE);
+	std::memcpy(blob.data() + nE, D.binAngle.data(), nB);
+	std::memcpy(blob.data() + nE + nB, D.gaussianWeight.data(), nG);
+	if (!sc->siftTables.p || sc->siftTablesHost != blob) {
+		BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		sc->siftTablesHost.clear();
+		BHIP_TRY(sc->siftTables.reserve(ctx, blob.size()));
+		BHIP_HIP(ctx, hipMemcpyAsync(sc->siftTables.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
+		BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));   // `blob` is this call's
+		sc->siftTablesHost.swap(blob);
+	}
+	char* p = sc->siftTables.as<char>();
+	B.expTable = (double*)p;
+	B.binAngle = (double*)(p + nE);
+	B.gaussianWeight = (float*)(p + nE + nB);
+	return BHIP_OK;
+}
+
 struct SiftOut {
 	double *x, *y, *scale;
 	uint8_t* white;
 	int16_t* where;
 	int* count;
 	int cap;
+	double *orientation = nullptr, *desc = nullptr;   // detect + describe (where is not an output then)
 };
 
-// bhip_sift_detect_dev_*: SiftDetector.process :165-191
+// bhip_sift_detect_dev_*: SiftDetector.process :165-191.  With D, bhip_csift_dev_*: CompleteSift.process -- detectFeatures (:97-111) takes the
+// gradient of scale image j and handleDetection (:113-134) turns every detection into its features while the octave is in scratch
 template <class T>
-int detectDevice(bhip_ctx* ctx, const SiftPlan& P, DevImg<const T> in, const SiftOut& out) {
+int detectDevice(bhip_ctx* ctx, const SiftPlan& P, DevImg<const T> in, const SiftOut& out, const SiftDescPlan* D = nullptr) {
 	const int batch = in.batch, ns = P.cfg.numScales;
 	const bhip_sift_cfg& c = P.cfg;
 	SiftBuffers B;
-	BHIP_TRY(siftReserve(ctx, P, batch, std::is_same<T, uint8_t>::value, false, B));
+	BHIP_TRY(siftReserve(ctx, P, batch, std::is_same<T, uint8_t>::value, false, B, D));
 	BHIP_HIP(ctx, hipMemsetAsync(out.count, 0, (size_t)batch * 4, ctx->stream));
+	if (D) {
+		BHIP_HIP(ctx, hipMemsetAsync(B.detN, 0, (size_t)batch * 4, ctx->stream));
+		BHIP_TRY(siftTables(ctx, *D, B));
+	}
 	DevImg<const float> frames;
 	BHIP_TRY(siftFrames<T>(ctx, in, B.frames, frames));
 	const DevImg<float> work0{B.work0, B.bigPlane, 0, 0, 0, batch}, work1{B.work1, B.bigPlane, 0, 0, 0, batch}, tmp{B.tmp, B.bigPlane, 0, 0, 0, batch};
@@ -275,8 +376,23 @@ int detectDevice(bhip_ctx* ctx, const SiftPlan& P, DevImg<const T> in, const Sif
 			K.sigmaLower = sigmaScale(c, octave, j - 1); K.sigmaTarget = sigmaScale(c, octave, j); K.sigmaUpper = sigmaScale(c, octave, j + 1);
 			K.octave = octave; K.j = j;
 			K.x = out.x; K.y = out.y; K.scale = out.scale; K.white = out.white; K.where = out.where; K.count = out.count; K.cap = out.cap;
+			if (D) {   // the slice's detections stay in scratch: detN is zero here, so the list starts at record 0 and always fits
+				K.x = B.detX; K.y = B.detY; K.scale = B.detScale; K.white = B.detWhite; K.where = B.detWhere; K.count = B.detN; K.cap = B.detCap;
+			}
 			if (K.sel) BHIP_TRY(bhip_launch_sift_select(ctx, K, B.key, B.sel));
 			BHIP_TRY(bhip_launch_sift_candidates(ctx, K, B.bitmap, B.prefix, B.nPass));
+			if (!D) continue;
+			SiftDescParams Q;
+			Q.image = oct[j].data; Q.imageStride = plane; Q.stride = w; Q.width = w; Q.height = h; Q.batch = batch;
+			Q.detX = B.detX; Q.detY = B.detY; Q.detScale = B.detScale; Q.detWhite = B.detWhite; Q.detN = B.detN; Q.detCap = B.detCap;
+			Q.pixelScaleToInput = K.pixelScaleToInput;
+			Q.histogramSize = D->cfg.histogramSize; Q.sigmaEnlarge = D->cfg.sigmaEnlarge; Q.histAngleBin = D->histAngleBin; Q.expTable = B.expTable;
+			Q.nAngles = B.nAngles; Q.angleOffset = B.angleOffset; Q.angles = B.angles; Q.nFeat = B.nFeat;
+			Q.widthSubregion = D->cfg.widthSubregion; Q.widthGrid = D->cfg.widthGrid; Q.numHistogramBins = D->cfg.numHistogramBins; Q.dof = D->dof;
+			Q.sigmaToPixels = D->cfg.sigmaToPixels; Q.histogramBinWidth = D->histogramBinWidth; Q.maxDescriptorElementValue = D->cfg.maxDescriptorElementValue;
+			Q.binAngle = B.binAngle; Q.gaussianWeight = B.gaussianWeight;
+			Q.x = out.x; Q.y = out.y; Q.scale = out.scale; Q.orientation = out.orientation; Q.desc = out.desc; Q.white = out.white; Q.count = out.count; Q.cap = out.cap;
+			BHIP_TRY(bhip_launch_sift_describe(ctx, Q, D->generic));
 		}
 	}
 	return BHIP_OK;
@@ -371,9 +487,109 @@ int detectHost(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const T* in, int start, 
 	return bhip_ctx_synchronize(ctx);
 }
 
+template <class T>
+int csiftDev(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const bhip_csift_cfg* desc, const T* dev_in, long long imageStride, int stride, int width, int height, int batch,
+			 const SiftOut& out) {
+	CHECK_CTX(ctx);
+	const DevImg<const T> in{dev_in, imageStride, stride, width, height, batch};
+	SiftPlan P;
+	BHIP_TRY(planFor<T>(ctx, cfg, in, true, P));
+	SiftDescPlan D;
+	const char* msg;
+	const int s = siftDescPlan(desc, D, &msg);
+	if (s != BHIP_OK) return bhip_fail(ctx, s, msg);
+	CHECK_IMG(ctx, in);
+	if (!out.count || out.cap < 0 || (out.cap > 0 && (!out.x || !out.y || !out.scale || !out.orientation || !out.white || !out.desc))) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad output");
+	return detectDevice<T>(ctx, P, in, out, &D);
+}
+
+template <class T>
+int csiftHost(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const bhip_csift_cfg* desc, const T* in, int start, int stride, int width, int height, double* x, double* y,
+			  double* scale, double* orientation, uint8_t* white, double* descriptors, int* count, int cap) {
+	CHECK_CTX(ctx);
+	const HostImg<const T> hin{in, start, stride, width, height};
+	SiftPlan P;
+	BHIP_TRY(planFor<T>(ctx, cfg, DevImg<const T>{in, 0, stride, width, height, 1}, true, P));
+	SiftDescPlan D;
+	const char* msg;
+	const int s = siftDescPlan(desc, D, &msg);
+	if (s != BHIP_OK) return bhip_fail(ctx, s, msg);
+	CHECK_IMG(ctx, hin);
+	if (!count || cap < 0 || (cap > 0 && (!x || !y || !scale || !orientation || !white || !descriptors))) return bhip_fail(ctx, BHIP_ERR_INVALID, "bad output");
+	CtxScratch* sc = scratchOf(ctx);
+	DevImg<T> din;
+	BHIP_TRY(stageIn(ctx, sc->in0, hin, width, din));
+	// out0 = [x | y | scale | orientation | descriptors | white | count]
+	const size_t c1 = (size_t)std::max(cap, 1), c8 = align256(c1 * 8), cd = align256(c1 * 8 * D.dof);
+	BHIP_TRY(sc->out0.reserve(ctx, 4 * c8 + cd + align256(c1) + 256));
+	char* base = sc->out0.as<char>();
+	SiftOut out;
+	out.x = (double*)base; out.y = (double*)(base + c8); out.scale = (double*)(base + 2 * c8); out.orientation = (double*)(base + 3 * c8);
+	out.desc = (double*)(base + 4 * c8); out.white = (uint8_t*)(base + 4 * c8 + cd); out.count = (int*)(base + 4 * c8 + cd + align256(c1));
+	out.where = nullptr;
+	out.cap = cap;
+	BHIP_TRY(detectDevice<T>(ctx, P, DevImg<const T>(din), out, &D));
+	BHIP_HIP(ctx, hipMemcpyAsync(ctx->hostScratch.p, out.count, 4, hipMemcpyDeviceToHost, ctx->stream));
+	BHIP_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the one synchronisation that decides how much to copy
+	*count = ctx->hostScratch.as<int>()[0];
+	const size_t n = (size_t)std::min(*count, cap);
+	if (n > 0) {
+		BHIP_HIP(ctx, hipMemcpyAsync(x, out.x, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+		BHIP_HIP(ctx, hipMemcpyAsync(y, out.y, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+		BHIP_HIP(ctx, hipMemcpyAsync(scale, out.scale, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+		BHIP_HIP(ctx, hipMemcpyAsync(orientation, out.orientation, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+		BHIP_HIP(ctx, hipMemcpyAsync(descriptors, out.desc, n * 8 * D.dof, hipMemcpyDeviceToHost, ctx->stream));
+		BHIP_HIP(ctx, hipMemcpyAsync(white, out.white, n, hipMemcpyDeviceToHost, ctx->stream));
+	}
+	return bhip_ctx_synchronize(ctx);
+}
+
 }   // namespace
 
 extern "C" {
+
+int bhip_csift_cfg_default(bhip_csift_cfg* desc) {
+	if (!desc) return BHIP_ERR_INVALID;
+	desc->histogramSize = 36; desc->sigmaEnlarge = 2.0;
+	desc->widthSubregion = 4; desc->widthGrid = 4; desc->numHistogramBins = 8;
+	desc->sigmaToPixels = 1.0; desc->weightingSigmaFraction = 0.5; desc->maxDescriptorElementValue = 0.2;
+	return BHIP_OK;
+}
+
+int bhip_csift_dof(const bhip_csift_cfg* desc) {
+	const char* msg;
+	const int s = siftDescCheck(desc, &msg);
+	return s != BHIP_OK ? s : desc->widthGrid * desc->widthGrid * desc->numHistogramBins;
+}
+
+int bhip_csift_weights(const bhip_csift_cfg* desc, double* expTable, float* gaussianWeight) {
+	SiftDescPlan D;
+	const char* msg;
+	BHIP_TRY(siftDescPlan(desc, D, &msg));
+	if (expTable) std::copy(D.expTable.begin(), D.expTable.end(), expTable);
+	if (gaussianWeight) std::copy(D.gaussianWeight.begin(), D.gaussianWeight.end(), gaussianWeight);
+	return BHIP_OK;
+}
+
+int bhip_csift_dev_f32(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const bhip_csift_cfg* desc, const float* dev_in, long long imageStride, int stride, int width,
+					   int height, int batch, double* dev_x, double* dev_y, double* dev_scale, double* dev_orientation, uint8_t* dev_white, double* dev_desc,
+					   int* dev_count, int cap) {
+	return csiftDev<float>(ctx, cfg, desc, dev_in, imageStride, stride, width, height, batch, {dev_x, dev_y, dev_scale, dev_white, nullptr, dev_count, cap, dev_orientation, dev_desc});
+}
+int bhip_csift_dev_u8(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const bhip_csift_cfg* desc, const uint8_t* dev_in, long long imageStride, int stride, int width,
+					  int height, int batch, double* dev_x, double* dev_y, double* dev_scale, double* dev_orientation, uint8_t* dev_white, double* dev_desc,
+					  int* dev_count, int cap) {
+	return csiftDev<uint8_t>(ctx, cfg, desc, dev_in, imageStride, stride, width, height, batch, {dev_x, dev_y, dev_scale, dev_white, nullptr, dev_count, cap, dev_orientation, dev_desc});
+}
+int bhip_csift_f32(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const bhip_csift_cfg* desc, const float* in, int start, int stride, int width, int height, double* x,
+				   double* y, double* scale, double* orientation, uint8_t* white, double* descriptors, int* count, int cap) {
+	return csiftHost<float>(ctx, cfg, desc, in, start, stride, width, height, x, y, scale, orientation, white, descriptors, count, cap);
+}
+int bhip_csift_u8(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const bhip_csift_cfg* desc, const uint8_t* in, int start, int stride, int width, int height, double* x,
+				  double* y, double* scale, double* orientation, uint8_t* white, double* descriptors, int* count, int cap) {
+	return csiftHost<uint8_t>(ctx, cfg, desc, in, start, stride, width, height, x, y, scale, orientation, white, descriptors, count, cap);
+}
+
 
 int bhip_sift_cfg_default(bhip_sift_cfg* cfg) {
 	if (!cfg) return BHIP_ERR_INVALID;

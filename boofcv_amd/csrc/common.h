@@ -640,6 +640,46 @@ int bhip_launch_sift_candidates(bhip_ctx* ctx, const SiftCandParams& P, unsigned
 // frame); sel and key are [batch][2 * listCap]
 int bhip_launch_sift_select(bhip_ctx* ctx, const SiftCandParams& P, float* key, int* sel);
 
+// ---------------- SIFT orientation and description (sift_describe.hip) ----------------
+// What CompleteSift.handleDetection does with the detections of one (octave, j) on every frame of a batch.  The detections of frame b are
+// detN[b] records of [batch][detCap] arrays in list order (bhip_launch_sift_candidates with count = detN, zero before it); the features go
+// behind count[b] records of the [batch][cap] outputs, count[b] moves on by their number, and detN[b] is cleared for the next slice
+struct SiftDescParams {
+	const float* image;   // scale image j of the octave (not a DoG image)
+	long long imageStride;
+	int stride, width, height, batch;
+	const double *detX, *detY, *detScale;   // ScalePoint x, y, scale: input pixels
+	const uint8_t* detWhite;
+	int* detN;
+	int detCap;
+	double pixelScaleToInput;
+	// OrientationHistogramSift
+	int histogramSize;
+	double sigmaEnlarge, histAngleBin;
+	const double* expTable;   // BHIP_CSIFT_EXP_TABLE samples of exp(-0.5 * i * 0.1)
+	int* nAngles;             // [batch][detCap]
+	int* angleOffset;         // [batch][detCap]: the exclusive scan of nAngles
+	double* angles;           // [batch][detCap][BHIP_CSIFT_ANGLE_SLOTS]
+	int* nFeat;               // [batch]
+	// DescribePointSift
+	int widthSubregion, widthGrid, numHistogramBins, dof;
+	double sigmaToPixels, histogramBinWidth, maxDescriptorElementValue;
+	const double* binAngle;       // k * histogramBinWidth, numHistogramBins of them
+	const float* gaussianWeight;  // (widthSubregion * widthGrid)^2
+	// the features
+	double *x, *y, *scale, *orientation;   // [batch][cap]
+	double* desc;                          // [batch][cap][dof]
+	uint8_t* white;                        // [batch][cap]
+	int* count;                            // [batch]
+	int cap;
+};
+// generic: the describe kernel that takes any grid, also for the default one (BHIP_SIFT_DESCRIBE_GENERIC: parity cross-check of the two)
+int bhip_launch_sift_describe(bhip_ctx* ctx, const SiftDescParams& P, bool generic);
+// tables.cpp.  The BHIP_CSIFT_EXP_TABLE doubles of OrientationHistogramSift's approximateGauss, and DescribeSiftCommon.createGaussianWeightKernel:
+// gaussian2D_F32(sigma, radius, odd = false, normalize = false) divided by its largest element, (2 * radius)^2 floats
+std::vector<double> bhip_sift_exp_table();
+std::vector<float> bhip_sift_gaussian_weight(double sigma, int radius);
+
 // ---------------- thresholding, FactoryThresholdBinary, and the GrayU8 blurs (threshold.hip) ----------------
 #define BHIP_THRESH_FUSED_MAX_RADIUS 16   // blur radius up to which a GrayU8 local threshold (and blur) runs as one launch out of LDS
 // the compare of a pixel with its threshold: px <= thr (down), px > thr (up: fixed, local, min/max), !(px <= thr) (up: block mean, Otsu; differs on NaN)

@@ -87,3 +87,32 @@ std::vector<int32_t> bhip_gaussian1d_s32(int radius) {
 	for (float v : k) out.push_back((int32_t)(v / min));
 	return out;
 }
+
+// OrientationHistogramSift's constructor (F:alg/feature/orientation/OrientationHistogramSift.java:108-114): (int)(4*4/0.1) samples of
+// exp(-0.5 * (i * 0.1)), the host's exp (unpinned against Java's Math.exp)
+std::vector<double> bhip_sift_exp_table() {
+	const double approximateStep = 0.1;
+	std::vector<double> samples((size_t)(int)(4 * 4 / approximateStep));
+	for (size_t i = 0; i < samples.size(); i++) {
+		const double dx2 = (double)(int)i * approximateStep;
+		samples[i] = std::exp(-0.5 * dx2);
+	}
+	return samples;
+}
+
+// DescribeSiftCommon.createGaussianWeightKernel (F:alg/feature/describe/DescribeSiftCommon.java:103-108): gaussian1D_F32(sigma, radius, odd = false,
+// normalize = false) (:226-231: the float PDF at i - 0.5, i = radius .. -radius + 1), KernelMath.convolve2D (float products), divided by
+// KernelMath.maxAbs over all 4 * radius^2 elements
+std::vector<float> bhip_sift_gaussian_weight(double sigma, int radius) {
+	std::vector<float> k1;
+	for (int i = radius; i > -radius; i--) k1.push_back((float)pdf(sigma, i - 0.5));
+	const size_t w = k1.size();
+	std::vector<float> out(w * w);
+	size_t idx = 0;
+	for (size_t i = 0; i < w; i++)
+		for (size_t j = 0; j < w; j++) out[idx++] = k1[i] * k1[j];
+	float max = 0;
+	for (float v : out) if (std::fabs(v) > max) max = std::fabs(v);
+	for (float& v : out) v /= max;
+	return out;
+}

@@ -33,6 +33,7 @@ Names follow the reference classes the host-buffer forms in boofcv_amd/api/ mirr
   DeviceImageOps.equalizeLocal  EnhanceImageOps.equalizeLocal (GrayU8)              I:alg/enhance/EnhanceImageOps.java:176-232
   DeviceImageOps.sharpen        EnhanceImageOps.sharpen4 / sharpen8 (GrayU8, GrayF32)   I:alg/enhance/EnhanceImageOps.java:307-371
   DeviceImageOps.siftScaleSpace / siftDetect   SiftScaleSpace.initialize + computeNextOctave, SiftDetector.process   F:alg/feature/detect/interest/SiftDetector.java:165-191
+  DeviceImageOps.siftDetectDescribe            CompleteSift.process (orientation histograms, 128-element descriptors)    F:alg/feature/detdesc/CompleteSift.java:89-134
   DeviceImageOps.brief          DescribePointBrief.process                       F:alg/feature/describe/DescribePointBrief.java:73-89
   DeviceKltTracker              PointTrackerKltPyramid, batched over sequences      main/boofcv-geo/.../abst/feature/tracker/PointTrackerKltPyramid.java:139-348
   DeviceBackgroundModel         BackgroundStationaryBasic / Gaussian / Gmm, batched over streams   F:alg/background/stationary/*.java
@@ -739,6 +740,31 @@ class DeviceImageOps:
         _check(self.ctx, fn(self.ctx._h, C.byref(sift._cfg(configSS, configDet)), ip, iis, irs, W, H, B, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()),
                             C.c_void_p(scale.data_ptr()), C.c_void_p(white.data_ptr()), C.c_void_p(where.data_ptr()), C.c_void_p(count.data_ptr()), cap))
         return x, y, scale, white, where, count
+
+    def siftDetectDescribe(self, src, config=None, cap=4096):
+        """CompleteSift.process (FactoryDetectDescribe.sift(config); None: new ConfigCompleteSift()) on uint8 or float32 frames [B,H,W] of any row /
+        image stride -> (x, y, scale, orientation float64 [B, cap], white uint8 [B, cap], descriptors float64 [B, cap, dof], count int32 [B]) on
+        the device: every frame's features in the reference's order, the descriptors in the layout associateL2 reads.  A count may exceed cap;
+        only the first cap records are written.  No host synchronisation."""
+        from . import sift
+        if config is None:
+            config = sift.ConfigCompleteSift()
+        u8 = src.dtype == torch.uint8
+        ip, iis, irs, W, H, B = _geom(src, torch.uint8 if u8 else torch.float32)
+        cap = int(cap)
+        dc = sift._desc_cfg(config.orientation, config.describe)
+        dof = self.L.bhip_csift_dof(C.byref(dc))
+        if dof < 0:
+            raise (RuntimeError if dof == _lib.BHIP_ERR_UNSUPPORTED else IllegalArgumentException)("no SIFT descriptor for this orientation / describe config")
+        x, y, scale, ori = (torch.empty((B, max(cap, 0)), dtype=torch.float64, device=src.device) for _ in range(4))
+        white = torch.empty((B, max(cap, 0)), dtype=torch.uint8, device=src.device)
+        desc = torch.empty((B, max(cap, 0), dof), dtype=torch.float64, device=src.device)
+        count = torch.empty((B,), dtype=torch.int32, device=src.device)
+        fn = self.L.bhip_csift_dev_u8 if u8 else self.L.bhip_csift_dev_f32
+        _check(self.ctx, fn(self.ctx._h, C.byref(sift._cfg(config.scaleSpace, config.detector)), C.byref(dc), ip, iis, irs, W, H, B, C.c_void_p(x.data_ptr()),
+                            C.c_void_p(y.data_ptr()), C.c_void_p(scale.data_ptr()), C.c_void_p(ori.data_ptr()), C.c_void_p(white.data_ptr()),
+                            C.c_void_p(desc.data_ptr()), C.c_void_p(count.data_ptr()), cap))
+        return x, y, scale, ori, white, desc, count
 
     def distortBuildMap(self, model, coeff, dw, dh, out=None):
         """bhip_distort_build_map: the [dh,dw,2] float32 map of an affine (model 1, six coefficients) or homography (model 2, nine) model"""

@@ -1427,7 +1427,7 @@ int bhip_sharpen_f32(bhip_ctx* ctx, int rule, const float* in, int inStart, int 
  *      WrapSiftDetector (F:abst/feature/detect/interest/WrapSiftDetector.java:38-60) over SiftDetector (F:alg/feature/detect/interest/SiftDetector.java:
  *      119-331), SiftScaleSpace (F:alg/feature/detect/interest/SiftScaleSpace.java:102-270) and NonMaxLimiter
  *      (F:abst/feature/detect/extract/NonMaxLimiter.java:49-84) with FactoryFeatureExtractor.nonmax(ConfigExtract).  Orientation and description
- *      (OrientationHistogramSift, DescribePointSift) are not provided. ----
+ *      (OrientationHistogramSift, DescribePointSift, CompleteSift): the bhip_csift_* section below. ----
  * Every scale image, DoG image and detection equals the single-threaded Java result bit for bit: the border-normalised separable Gaussian
  * convolutions (the arithmetic of bhip_conv_norm_h / _v, naive form included), a float subtraction, the strict block min / max non-maximum
  * suppression with ignoreBorder 1, the 3x3x3 comparison, the edge test in double on three sparse float convolutions with an EXTENDED border, and
@@ -1492,6 +1492,69 @@ int bhip_sift_detect_f32(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const float* i
 						 double* scale, uint8_t* white, int16_t* where, int* count, int cap);
 int bhip_sift_detect_u8(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const uint8_t* in, int start, int stride, int width, int height, double* x, double* y,
 						double* scale, uint8_t* white, int16_t* where, int* count, int cap);
+
+/* ---- SIFT detect + describe: FactoryDetectDescribe.sift(ConfigCompleteSift) (F:factory/feature/detdesc/FactoryDetectDescribe.java:72-96):
+ *      DetectDescribe_CompleteSift (F:abst/feature/detdesc/DetectDescribe_CompleteSift.java) over CompleteSift
+ *      (F:alg/feature/detdesc/CompleteSift.java:89-134), OrientationHistogramSift (F:alg/feature/orientation/OrientationHistogramSift.java:135-309)
+ *      and DescribePointSift / DescribeSiftCommon (F:alg/feature/describe/DescribePointSift.java:105-165, DescribeSiftCommon.java:60-131). ----
+ * The detector is the one above (bhip_sift_cfg, bit for bit).  For every detection of (octave, j), on scale image j of the octave with
+ * GradientThree's EXTENDED-border gradient: the orientation histograms (every bin the reference's ordered double sum), the peaks, the angles,
+ * and one feature per angle: the 128-element (widthGrid^2 * numHistogramBins) descriptor, normalised twice.  Discrete results -- the number of
+ * angles of every detection, hence the count and order of features; x, y, scale, white -- equal the single-threaded Java result exactly.
+ * Angles and descriptor elements differ from it by the last ulp of atan2 / sin / cos alone (Java's, the host's and the device library's are
+ * three implementations): where an argument of atan2 is zero the results the Java specification fixes are selected explicitly, so samples
+ * on a bin edge are binned as in Java.  Host decisions, unpinned against Java's Math.exp / Math.sqrt: the exp table of the orientation
+ * weight and the Gaussian weight of the descriptor (bhip_csift_weights returns both).  UtilAngle.domain2PI / dist / bound are georegression's,
+ * restated from their contract.
+ * BHIP_ERR_INVALID and nothing is written, beyond the detector's: histogramSize < 3, sigmaEnlarge, sigmaToPixels, weightingSigmaFraction or
+ * maxDescriptorElementValue not > 0, widthSubregion, widthGrid or numHistogramBins < 1, widthSubregion * widthGrid odd (the reference indexes
+ * its weight kernel out of range), cap < 0.
+ * BHIP_ERR_UNSUPPORTED and nothing is written, beyond the detector's: histogramSize > BHIP_CSIFT_MAX_HISTOGRAM, widthSubregion * widthGrid >
+ * BHIP_CSIFT_MAX_SAMPLE_WIDTH, a descriptor of more than BHIP_CSIFT_MAX_DOF elements (the kernels' LDS).  The orientation window has no limit:
+ * r = ceil(sigma * sigmaEnlarge) is walked in chunks whatever its size.
+ * BHIP_SIFT_DESCRIBE_GENERIC=1 in the environment runs the default grid (4, 4, 8) through the describe kernel that takes any grid (same results). */
+#define BHIP_CSIFT_EXP_TABLE 160
+#define BHIP_CSIFT_ANGLE_SLOTS 3
+#define BHIP_CSIFT_MAX_HISTOGRAM 256
+#define BHIP_CSIFT_MAX_SAMPLE_WIDTH 48
+#define BHIP_CSIFT_MAX_DOF 2048
+/* (the typedef, then the struct: the form boofcv_amd/_header.py reads as Header.forward) */
+typedef struct bhip_csift_cfg bhip_csift_cfg;
+struct bhip_csift_cfg {
+	int histogramSize;                /* ConfigSiftOrientation: 36 */
+	double sigmaEnlarge;              /* 2.0 (createPaper: 1.5) */
+	int widthSubregion;               /* ConfigSiftDescribe: 4 */
+	int widthGrid;                    /* 4 */
+	int numHistogramBins;             /* 8 */
+	double sigmaToPixels;             /* 1.0 */
+	double weightingSigmaFraction;    /* 0.5 */
+	double maxDescriptorElementValue; /* 0.2 */
+};
+/* new ConfigSiftOrientation() (F:abst/feature/orientation/ConfigSiftOrientation.java) and new ConfigSiftDescribe()
+ * (F:abst/feature/describe/ConfigSiftDescribe.java) */
+int bhip_csift_cfg_default(bhip_csift_cfg* desc);
+/* Host only: DescribeSiftCommon.getDescriptorLength, or a BHIP_ERR_* code for a config the calls below refuse. */
+int bhip_csift_dof(const bhip_csift_cfg* desc);
+/* Host only: the tables the kernels are given.  expTable: BHIP_CSIFT_EXP_TABLE doubles, exp(-0.5 * i * 0.1); gaussianWeight:
+ * (widthSubregion * widthGrid)^2 floats, DescribeSiftCommon.gaussianWeight.  Either may be NULL. */
+int bhip_csift_weights(const bhip_csift_cfg* desc, double* expTable, float* gaussianWeight);
+/* CompleteSift.process on every frame, one octave at a time in context scratch.  Frame b's features, in the reference's order (detection
+ * order, then the order of the angle list), go to dev_x / dev_y / dev_scale / dev_orientation + b*cap (the ScalePoint and the angle),
+ * dev_white + b*cap and dev_desc + b*cap*dof (dof doubles per feature: the layout bhip_assoc_l2_dev and bhip_assoc_l2_dev_batched read);
+ * dev_count[b] is their number, exact also where it exceeds cap: only the first cap records are written.  No host synchronisation between
+ * the first launch and the last. */
+int bhip_csift_dev_f32(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const bhip_csift_cfg* desc, const float* dev_in, long long imageStride, int stride, int width,
+					   int height, int batch, double* dev_x, double* dev_y, double* dev_scale, double* dev_orientation, uint8_t* dev_white, double* dev_desc,
+					   int* dev_count, int cap);
+int bhip_csift_dev_u8(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const bhip_csift_cfg* desc, const uint8_t* dev_in, long long imageStride, int stride, int width,
+					  int height, int batch, double* dev_x, double* dev_y, double* dev_scale, double* dev_orientation, uint8_t* dev_white, double* dev_desc,
+					  int* dev_count, int cap);
+/* the same on one host image view: staged, run through the _dev forms, synchronised.  x, y, scale, orientation, white: cap elements; descriptors:
+ * cap * dof doubles; *count as dev_count. */
+int bhip_csift_f32(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const bhip_csift_cfg* desc, const float* in, int start, int stride, int width, int height, double* x,
+				   double* y, double* scale, double* orientation, uint8_t* white, double* descriptors, int* count, int cap);
+int bhip_csift_u8(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const bhip_csift_cfg* desc, const uint8_t* in, int start, int stride, int width, int height, double* x,
+				  double* y, double* scale, double* orientation, uint8_t* white, double* descriptors, int* count, int cap);
 
 #ifdef __cplusplus
 }

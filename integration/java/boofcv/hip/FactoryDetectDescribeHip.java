@@ -6,6 +6,7 @@ import javax.annotation.Nullable;
 
 import boofcv.abst.feature.describe.ConfigBrief;
 import boofcv.abst.feature.describe.ConfigSurfDescribe;
+import boofcv.abst.feature.detdesc.ConfigCompleteSift;
 import boofcv.abst.feature.detdesc.DetectDescribePoint;
 import boofcv.abst.feature.detect.interest.ConfigFastHessian;
 import boofcv.abst.feature.orientation.ConfigAverageIntegral;
@@ -22,12 +23,21 @@ import boofcv.struct.image.Planar;
 
 /** Same signatures as FactoryDetectDescribe (main/boofcv-feature/.../factory/feature/detdesc/FactoryDetectDescribe.java) for what the library
  *  implements, returning the same interface types, backed by libboofhip.so: surfFast / surfStable (:118-135, 209-226) on GrayF32 and GrayU8,
- *  surfColorFast / surfColorStable (:154-176, 246-268) on Planar<GrayF32>, and fuseTogether(fastHessian, null, brief) (:279-284).
+ *  surfColorFast / surfColorStable (:154-176, 246-268) on Planar<GrayF32>, fuseTogether(fastHessian, null, brief) (:279-284), and sift (:72-96)
+ *  on GrayF32 and GrayU8.
  *  UNCOMPILED SOURCE (no JDK in the build image). */
 public class FactoryDetectDescribeHip {
 	private static void checkGray(Class<?> imageType) {
 		if (imageType != GrayF32.class && imageType != GrayU8.class)
 			throw new IllegalArgumentException("Image type not supported");   // the reference's own message for types it does not handle
+	}
+
+	/** sift(config) (:72-96); the reference's method is generic in T alone, the image class is an argument here as in the SURF methods */
+	public static <T extends ImageGray<T>> DetectDescribePoint<T, BrightFeature>
+	sift(@Nullable ConfigCompleteSift config, Class<T> imageType) {
+		checkGray(imageType);
+		if (config == null) config = new ConfigCompleteSift();
+		return new DetectDescribeSiftHip<>(config, imageType);
 	}
 
 	public static <T extends ImageGray<T>> DetectDescribePoint<T, BrightFeature>
