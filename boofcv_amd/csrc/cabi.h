@@ -32,6 +32,9 @@ struct CtxScratch {
 	DevBuf sift;                    // cabi_sift.hip: float frames, tempBlur, one octave's scale and DoG images, the NMS lists and candidate bitmaps
 	DevBuf siftTables;              // detect + describe: [exp table | bin angles | Gaussian weight] of the config last used ...
 	std::vector<char> siftTablesHost;   // ... and the host block they were copied from (uploaded again only when the config changes)
+	DevBuf dense;                   // cabi_dense.hip: the fast HOG's cell histograms, or the per-pixel values of standard HOG / dense SIFT, of the frames in flight
+	DevBuf denseTables[2];          // [0] standard HOG: the block's pixel weights; [1] dense SIFT: [bin angles | Gaussian weight]; of the config last used ...
+	std::vector<char> denseTablesHost[2];  // ... and the host blocks they were copied from
 	DevBuf thresholdTaps;         // the Kernel1D_S32 Gaussian taps of the GrayU8 blurs, for thresholdTapsRadius (0: none yet)
 	int thresholdTapsRadius = 0;
 	AssocMfmaWork mfma;

@@ -680,6 +680,49 @@ int bhip_launch_sift_describe(bhip_ctx* ctx, const SiftDescParams& P, bool gener
 std::vector<double> bhip_sift_exp_table();
 std::vector<float> bhip_sift_gaussian_weight(double sigma, int radius);
 
+// ---------------- dense descriptors: HOG and dense SIFT (dense.hip) ----------------
+// The records of frame b: desc + b*cap*dof, xy + b*cap*2; only the first cap of a frame's `total` descriptors are written (`total` is the
+// host's: the grid of a frame depends on its size alone)
+struct DenseOut {
+	double* desc;
+	int32_t* xy;
+	int cap;
+};
+struct DenseHogParams {
+	int orientationBins, pixelsPerCell, cellsPerBlockX, cellsPerBlockY, stepBlock;
+	int cellRows, cellCols;   // fast variant: the cell grid of the frame
+	int numX, numY, dof;      // descriptors per row / per column of the frame
+};
+struct DenseSiftParams {
+	int widthSubregion, widthGrid, numHistogramBins, dof;
+	double histogramBinWidth, maxDescriptorElementValue;
+	int x0, y0, spanX, spanY;   // X0, Y0, X1 - X0, Y1 - Y0 of DescribeDenseSiftAlg.process
+	int numX, numY;
+};
+// every count[b] = total
+int bhip_launch_dense_count(bhip_ctx* ctx, int* count, int batch, int total);
+// DescribeDenseHogFastAlg.computeCellHistograms: cells[batch][cellRows][cellCols][orientationBins]; T: float or uint8_t (converted, exact)
+template <class T>
+int bhip_launch_dense_hog_cells(bhip_ctx* ctx, DevImg<const T> in, const DenseHogParams& P, float* cells);
+// computeDescriptor of every block: the copy into doubles and normalizeDescriptor(d, 0.2)
+int bhip_launch_dense_hog_blocks(bhip_ctx* ctx, const DenseHogParams& P, const float* cells, int batch, DenseOut out);
+// DescribeDenseHogAlg.computePixelFeatures, as far as it is shared by the blocks of a pixel: findex[batch][H][W] = orientation / angleBinSize and
+// sumsq = dx*dx + dy*dy, both float (the magnitude is Math.sqrt of the widened sum)
+template <class T>
+int bhip_launch_dense_hog_pixels(bhip_ctx* ctx, DevImg<const T> in, int orientationBins, float* findex, float* sumsq);
+// DescribeDenseHogAlg.process; weights: computeWeightBlockPixels, (cellsPerBlockY * pixelsPerCell) x (cellsPerBlockX * pixelsPerCell) doubles on the device
+int bhip_launch_dense_hog_std(bhip_ctx* ctx, const DenseHogParams& P, const float* findex, const float* sumsq, const double* weights, int width, int height,
+							  int batch, DenseOut out);
+// DescribeDenseSiftAlg.precomputeAngles: angle[batch][H][W] double, magnitude float.  s16: T is uint8_t and the gradient is GradientThree's GrayS16
+// one (b - a, read through getF); otherwise (a - b) * 0.5f
+template <class T>
+int bhip_launch_dense_sift_pixels(bhip_ctx* ctx, DevImg<const T> in, double* angle, float* magnitude);
+// DescribeDenseSiftAlg.process; gaussianWeight, binAngle: on the device, as SiftDescParams'
+int bhip_launch_dense_sift(bhip_ctx* ctx, const DenseSiftParams& P, const double* angle, const float* magnitude, const float* gaussianWeight, const double* binAngle,
+						   int width, int height, int batch, DenseOut out);
+// tables.cpp.  DescribeDenseHogAlg.computeWeightBlockPixels: rows x cols doubles
+std::vector<double> bhip_dense_hog_weight_table(int rows, int cols);
+
 // ---------------- thresholding, FactoryThresholdBinary, and the GrayU8 blurs (threshold.hip) ----------------
 #define BHIP_THRESH_FUSED_MAX_RADIUS 16   // blur radius up to which a GrayU8 local threshold (and blur) runs as one launch out of LDS
 // the compare of a pixel with its threshold: px <= thr (down), px > thr (up: fixed, local, min/max), !(px <= thr) (up: block mean, Otsu; differs on NaN)

@@ -88,6 +88,30 @@ std::vector<int32_t> bhip_gaussian1d_s32(int radius) {
 	return out;
 }
 
+// DescribeDenseHogAlg.computeWeightBlockPixels (F:alg/feature/dense/DescribeDenseHogAlg.java:121-161): computePDF(0, radius, d) per axis with
+// sigma = half the side, an offset of 0.5 on even sides, the products divided by the largest.  A side of one pixel has sigma 0: the reference's
+// arithmetic then gives NaN, and so does this
+std::vector<double> bhip_dense_hog_weight_table(int rows, int cols) {
+	std::vector<double> weights((size_t)rows * cols);
+	const double offsetRow = rows % 2 == 0 ? 0.5 : 0, offsetCol = cols % 2 == 0 ? 0.5 : 0;
+	const int radiusRow = rows / 2, radiusCol = cols / 2;
+	size_t index = 0;
+	for (int row = 0; row < rows; row++) {
+		const double drow = row - radiusRow + offsetRow;
+		const double pdfRow = pdf(radiusRow, drow);
+		for (int col = 0; col < cols; col++) {
+			const double dcol = col - radiusCol + offsetCol;
+			const double pdfCol = pdf(radiusCol, dcol);
+			weights[index++] = pdfCol * pdfRow;
+		}
+	}
+	double max = 0;
+	for (double v : weights)
+		if (v > max) max = v;
+	for (double& v : weights) v /= max;
+	return weights;
+}
+
 // OrientationHistogramSift's constructor (F:alg/feature/orientation/OrientationHistogramSift.java:108-114): (int)(4*4/0.1) samples of
 // exp(-0.5 * (i * 0.1)), the host's exp (unpinned against Java's Math.exp)
 std::vector<double> bhip_sift_exp_table() {

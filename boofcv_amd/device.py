@@ -34,7 +34,8 @@ Names follow the reference classes the host-buffer forms in boofcv_amd/api/ mirr
   DeviceImageOps.sharpen        EnhanceImageOps.sharpen4 / sharpen8 (GrayU8, GrayF32)   I:alg/enhance/EnhanceImageOps.java:307-371
   DeviceImageOps.siftScaleSpace / siftDetect   SiftScaleSpace.initialize + computeNextOctave, SiftDetector.process   F:alg/feature/detect/interest/SiftDetector.java:165-191
   DeviceImageOps.siftDetectDescribe            CompleteSift.process (orientation histograms, 128-element descriptors)    F:alg/feature/detdesc/CompleteSift.java:89-134
-  DeviceImageOps.brief          DescribePointBrief.process                       F:alg/feature/describe/DescribePointBrief.java:73-89
+  DeviceImageOps.denseHog / denseSift          DescribeDenseHogFastAlg / DescribeDenseHogAlg / DescribeDenseSiftAlg .process       F:alg/feature/dense/*.java
+  DeviceImageOps.brief          DescribePointBrief.process                      F:alg/feature/describe/DescribePointBrief.java:73-89
   DeviceKltTracker              PointTrackerKltPyramid, batched over sequences      main/boofcv-geo/.../abst/feature/tracker/PointTrackerKltPyramid.java:139-348
   DeviceBackgroundModel         BackgroundStationaryBasic / Gaussian / Gmm, batched over streams   F:alg/background/stationary/*.java
 """
@@ -765,6 +766,49 @@ class DeviceImageOps:
                             C.c_void_p(y.data_ptr()), C.c_void_p(scale.data_ptr()), C.c_void_p(ori.data_ptr()), C.c_void_p(white.data_ptr()),
                             C.c_void_p(desc.data_ptr()), C.c_void_p(count.data_ptr()), cap))
         return x, y, scale, ori, white, desc, count
+
+    def _dense(self, src, cap, layout, call, extra=()):
+        u8 = src.dtype == torch.uint8
+        ip, iis, irs, W, H, B = _geom(src, torch.uint8 if u8 else torch.float32)
+        dof = C.c_int(0)
+        n = layout(W, H, C.byref(dof))
+        if n < 0:
+            raise (RuntimeError if n == _lib.BHIP_ERR_UNSUPPORTED else IllegalArgumentException)("no dense descriptors for a %d x %d frame with this config" % (W, H))
+        cap = n if cap is None else int(cap)
+        desc = torch.empty((B, max(cap, 0), dof.value), dtype=torch.float64, device=src.device)
+        xy = torch.empty((B, max(cap, 0), 2), dtype=torch.int32, device=src.device)
+        count = torch.empty((B,), dtype=torch.int32, device=src.device)
+        _check(self.ctx, call(u8)(ip, iis, irs, W, H, B, C.c_void_p(desc.data_ptr()), C.c_void_p(xy.data_ptr()), C.c_void_p(count.data_ptr()), cap, *extra))
+        return desc, xy, count
+
+    def denseHog(self, src, config=None, cap=None, cells=None):
+        """DescribeDenseHogFastAlg / DescribeDenseHogAlg (FactoryDescribeImageDense.hog(config); None: new ConfigDenseHoG()) on uint8 or float32 frames
+        [B,H,W] of any row / image stride -> (descriptors float64 [B, cap, dof], xy int32 [B, cap, 2]: the blocks' top-left pixels, count int32 [B]) on
+        the device, in the reference's row-major order, the descriptors in the layout associateL2 reads.  cap None: room for all of them; a count
+        may exceed cap, only the first cap records are written.  cells (fast variant): a contiguous float32 [B, H // pixelsPerCell,
+        W // pixelsPerCell, orientationBins] CUDA tensor that receives the cell histograms.  No host synchronisation."""
+        from . import dense
+        config = dense.ConfigDenseHoG() if config is None else config
+        a = dense._hog_args(config)
+        if cells is not None:
+            B, H, W = (1,) + tuple(src.shape) if src.dim() == 2 else tuple(src.shape)
+            if not config.fastVariant:
+                raise IllegalArgumentException("only the fast variant has cell histograms")
+            if cells.dtype != torch.float32 or not cells.is_cuda or not cells.is_contiguous() or tuple(cells.shape) != (B, H // a[1], W // a[1], a[0]):
+                raise IllegalArgumentException("cells is a contiguous [B, H // pixelsPerCell, W // pixelsPerCell, orientationBins] float32 CUDA tensor")
+        return self._dense(src, cap, lambda W, H, dof: self.L.bhip_dense_hog_layout(*a, W, H, None, None, dof, None, 0),
+                           lambda u8: (lambda *r: (self.L.bhip_dense_hog_dev_u8 if u8 else self.L.bhip_dense_hog_dev_f32)(self.ctx._h, *a, *r)),
+                           (None if cells is None else C.c_void_p(cells.data_ptr()),))
+
+    def denseSift(self, src, config=None, cap=None):
+        """DescribeDenseSiftAlg behind DescribeImageDenseSift (FactoryDescribeImageDense.sift(config); None: new ConfigDenseSift()) on uint8 (GrayS16
+        gradient) or float32 frames [B,H,W] of any row / image stride -> (descriptors float64 [B, cap, dof], xy int32 [B, cap, 2]: the window centres,
+        count int32 [B]) on the device, as denseHog.  No host synchronisation."""
+        from . import dense
+        config = dense.ConfigDenseSift() if config is None else config
+        g, rest = dense._sift_args(config)
+        return self._dense(src, cap, lambda W, H, dof: self.L.bhip_dense_sift_layout(*g, rest[2], rest[3], W, H, None, None, dof, None, 0),
+                           lambda u8: (lambda *r: (self.L.bhip_dense_sift_dev_u8 if u8 else self.L.bhip_dense_sift_dev_f32)(self.ctx._h, *g, *rest, *r)))
 
     def distortBuildMap(self, model, coeff, dw, dh, out=None):
         """bhip_distort_build_map: the [dh,dw,2] float32 map of an affine (model 1, six coefficients) or homography (model 2, nine) model"""

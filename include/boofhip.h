@@ -1556,6 +1556,79 @@ int bhip_csift_f32(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const bhip_csift_cfg
 int bhip_csift_u8(bhip_ctx* ctx, const bhip_sift_cfg* cfg, const bhip_csift_cfg* desc, const uint8_t* in, int start, int stride, int width, int height, double* x,
 				  double* y, double* scale, double* orientation, uint8_t* white, double* descriptors, int* count, int cap);
 
+/* ---- Dense descriptors: FactoryDescribeImageDense.hog(ConfigDenseHoG, imageType), both variants, and FactoryDescribeImageDense.sift(ConfigDenseSift,
+ *      imageType) (F:factory/feature/dense/FactoryDescribeImageDense.java:108-165) on single-band GrayF32 / GrayU8 frames: DescribeDenseHogFastAlg
+ *      (F:alg/feature/dense/DescribeDenseHogFastAlg.java:80-215), DescribeDenseHogAlg (F:alg/feature/dense/DescribeDenseHogAlg.java:121-339) and
+ *      DescribeDenseSiftAlg (F:alg/feature/dense/DescribeDenseSiftAlg.java:120-198) with DescribeSiftCommon.  The configuration values are plain
+ *      arguments: ConfigDenseHoG (9, 8, 3, 3, 1, fastVariant = 1) and ConfigSiftDescribe (4, 4, 8, 0.5, 0.2; sigmaToPixels is not used) with
+ *      DenseSampling (6, 6). ----
+ * The gradient is GradientThree with the EXTENDED border.  HOG on GrayU8 converts to GrayF32 first (DescribeImageDense_Convert, exact);
+ * dense SIFT on GrayU8 takes the GrayS16 gradient, which in this reference is b - a with no divisor (kernel -1 0 1), read through getF.
+ * Counts, locations and their order equal the single-threaded Java result exactly.  HOG: every operation between the pixels and the
+ * descriptor is IEEE-specified except the one Math.atan of a pixel, whose double result is narrowed to float at once: the fast variant's float
+ * cell histograms and the descriptors of both variants equal Java's bit for bit wherever the host's / device's / Java's atan narrow to the same
+ * float.  Dense SIFT: Math.atan2 stays a double (where an argument is zero the results the Java specification fixes are selected), so descriptor
+ * elements differ from Java's by its last ulp.  Every ordered sum -- a cell's bin in pixel raster order; a standard-HOG element over the cells of
+ * the block in row-major order, their pixels in raster order and a pixel's adds as written (a contribution with a zero spatial weight adds +0.0
+ * and is skipped); a SIFT element over the window's samples in raster order; both L2 sums in index order -- is taken in that order by one lane.
+ * UtilAngle.atanSafe / domain2PI / dist (georegression) and UtilGaussian.computePDF (ddogleg) are restated from their contract, unpinned.
+ * Locations: HOG, the block's top-left pixel (BaseDenseHog.getLocations; DescribeImageDenseHoG.process adds half the region afterwards); dense
+ * SIFT, the window's centre.
+ * BHIP_ERR_INVALID and nothing is written, where the reference throws or divides by zero: stepBlock <= 0; orientationBins, pixelsPerCell,
+ * cellsPerBlockX / Y, widthSubregion, widthGrid, numHistogramBins < 1; periods, weightingSigmaFraction, maxDescriptorElementValue not > 0;
+ * widthSubregion * widthGrid odd (the reference indexes its weight kernel out of range); empty images, strides smaller than a row, cap < 0, a
+ * cell-histogram output with the standard variant; dense SIFT with one row of descriptors (numY == 1), or with one column (numX == 1) and at
+ * least one row: the reference divides by numX - 1 in int arithmetic.
+ * BHIP_ERR_UNSUPPORTED and nothing is written: a descriptor of more than BHIP_DENSE_MAX_DOF elements, more than BHIP_DENSE_MAX_BINS orientation /
+ * histogram bins, pixelsPerCell > BHIP_DENSE_MAX_CELL, a dense-SIFT window wider than BHIP_DENSE_MAX_SAMPLE_WIDTH samples, more than 65535 frames, more
+ * than 65535 image rows, a grid whose count or whose (X1 - X0) * (numX - 1) is beyond int.
+ * An image too small for one block or window gives count 0.
+ * BHIP_DENSE_SIFT_GENERIC=1 in the environment runs the default grid (4, 4, 8) through the kernel that takes any grid (same results). */
+#define BHIP_DENSE_MAX_DOF 2048
+#define BHIP_DENSE_MAX_BINS 64
+#define BHIP_DENSE_MAX_CELL 32
+#define BHIP_DENSE_MAX_SAMPLE_WIDTH 48
+/* Host only: the grid of a width x height frame.  Returns the number of descriptors (>= 0) or a BHIP_ERR_* code; *perRow descriptors in a row of
+ * the grid, *perCol rows, *dof elements per descriptor, and xy receives (x, y) of the first min(number, cap) descriptors in row-major order.  Any
+ * of the pointers may be NULL. */
+int bhip_dense_hog_layout(int orientationBins, int pixelsPerCell, int cellsPerBlockX, int cellsPerBlockY, int stepBlock, int fastVariant, int width, int height,
+						  int* perRow, int* perCol, int* dof, int32_t* xy, int cap);
+int bhip_dense_sift_layout(int widthSubregion, int widthGrid, int numHistogramBins, double periodX, double periodY, int width, int height, int* perRow, int* perCol,
+						   int* dof, int32_t* xy, int cap);
+/* Host only: DescribeDenseHogAlg.computeWeightBlockPixels, (cellsPerBlockY * pixelsPerCell) rows of (cellsPerBlockX * pixelsPerCell) doubles.  Returns
+ * their number or a BHIP_ERR_* code; weights may be NULL. */
+int bhip_dense_hog_weights(int pixelsPerCell, int cellsPerBlockX, int cellsPerBlockY, double* weights);
+/* Every frame of a device batch at dev_in + b*imageStride (rows `stride` elements apart, any alignment).  Frame b's descriptors, in the
+ * reference's row-major order, go to dev_desc + b*cap*dof (dof doubles each: the layout bhip_assoc_l2_dev and bhip_assoc_l2_dev_batched read) and
+ * their locations to dev_xy + b*cap*2; dev_count[b] is their number, which may exceed cap: only the first cap records are written.  dev_cells,
+ * fast variant only and optional (NULL): the cell histograms, [batch][height / pixelsPerCell][width / pixelsPerCell][orientationBins] floats.
+ * The per-pixel values and cell histograms live in context scratch; a batch whose scratch would exceed 256 MiB runs as several groups of frames.
+ * Asynchronous on the context's stream, no host synchronisation (the weight tables are uploaded, with one, when the configuration changes). */
+int bhip_dense_hog_dev_f32(bhip_ctx* ctx, int orientationBins, int pixelsPerCell, int cellsPerBlockX, int cellsPerBlockY, int stepBlock, int fastVariant,
+						   const float* dev_in, long long imageStride, int stride, int width, int height, int batch, double* dev_desc, int32_t* dev_xy, int* dev_count,
+						   int cap, float* dev_cells);
+int bhip_dense_hog_dev_u8(bhip_ctx* ctx, int orientationBins, int pixelsPerCell, int cellsPerBlockX, int cellsPerBlockY, int stepBlock, int fastVariant,
+						  const uint8_t* dev_in, long long imageStride, int stride, int width, int height, int batch, double* dev_desc, int32_t* dev_xy, int* dev_count,
+						  int cap, float* dev_cells);
+int bhip_dense_sift_dev_f32(bhip_ctx* ctx, int widthSubregion, int widthGrid, int numHistogramBins, double weightingSigmaFraction, double maxDescriptorElementValue,
+							double periodX, double periodY, const float* dev_in, long long imageStride, int stride, int width, int height, int batch, double* dev_desc,
+							int32_t* dev_xy, int* dev_count, int cap);
+int bhip_dense_sift_dev_u8(bhip_ctx* ctx, int widthSubregion, int widthGrid, int numHistogramBins, double weightingSigmaFraction, double maxDescriptorElementValue,
+						   double periodX, double periodY, const uint8_t* dev_in, long long imageStride, int stride, int width, int height, int batch, double* dev_desc,
+						   int32_t* dev_xy, int* dev_count, int cap);
+/* the same on one host image view: staged, run through the _dev forms, synchronised.  descriptors: cap * dof doubles; xy: cap * 2; *count as
+ * dev_count; cells (fast variant, may be NULL): (height / pixelsPerCell) * (width / pixelsPerCell) * orientationBins floats. */
+int bhip_dense_hog_f32(bhip_ctx* ctx, int orientationBins, int pixelsPerCell, int cellsPerBlockX, int cellsPerBlockY, int stepBlock, int fastVariant, const float* in,
+					   int start, int stride, int width, int height, double* descriptors, int32_t* xy, int* count, int cap, float* cells);
+int bhip_dense_hog_u8(bhip_ctx* ctx, int orientationBins, int pixelsPerCell, int cellsPerBlockX, int cellsPerBlockY, int stepBlock, int fastVariant, const uint8_t* in,
+					  int start, int stride, int width, int height, double* descriptors, int32_t* xy, int* count, int cap, float* cells);
+int bhip_dense_sift_f32(bhip_ctx* ctx, int widthSubregion, int widthGrid, int numHistogramBins, double weightingSigmaFraction, double maxDescriptorElementValue,
+						double periodX, double periodY, const float* in, int start, int stride, int width, int height, double* descriptors, int32_t* xy, int* count,
+						int cap);
+int bhip_dense_sift_u8(bhip_ctx* ctx, int widthSubregion, int widthGrid, int numHistogramBins, double weightingSigmaFraction, double maxDescriptorElementValue,
+					   double periodX, double periodY, const uint8_t* in, int start, int stride, int width, int height, double* descriptors, int32_t* xy, int* count,
+					   int cap);
+
 #ifdef __cplusplus
 }
 #endif
